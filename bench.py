@@ -18,6 +18,7 @@ through compress and then decompress.  Inputs are in HBM when the timed region s
 
     python bench.py                      # 1 GPU, 4 GiB shard
     python bench.py --gpus N             # N ranks started by bench.py itself (fresh child processes, one per GPU)
+    python bench.py --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy (same arguments: same inputs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -101,6 +102,41 @@ def launch_ranks(n):
     sys.exit(rc if rc > 0 else (1 if rc else 0))
 
 
+DUMP_UNITS = 1 << 20          # per-unit arrays: the first 2^20 units at most
+DUMP_SAMPLE = 32              # units whose compressed and decompressed bytes are written
+DUMP_SEED = 20241015
+DUMP_LIMIT = 64_000_000
+
+
+def dump_outputs(dst, nblocks, comp_total, d_comp, ulen, ucrc, d_out, mstat):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as DIR/<name>.npy.  The compress leg returns
+    the packed raw-deflate stream (its units in order) with every unit's compressed size and CRC-32, the inflate leg the
+    decompressed bytes with every member's status.  The per-unit arrays are written whole up to DUMP_UNITS units, the streams
+    for a fixed, seeded sample of DUMP_SAMPLE units (the same units for the same --size-mib / --scaling / --gpus)."""
+    import numpy as np
+    os.makedirs(dst, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(nblocks, size=min(nblocks, DUMP_SAMPLE), replace=False))
+    offs = np.concatenate([[0], np.cumsum(ulen.astype(np.int64))])
+    comp = [d_comp[int(offs[u]):int(offs[u + 1])].cpu() for u in pick]
+    back = [d_out[int(u) * BLOCK:(int(u) + 1) * BLOCK].cpu() for u in pick]
+    k = min(nblocks, DUMP_UNITS)
+    arrays = {
+        "compressed_total_bytes": np.array([comp_total], np.float64),
+        "unit_compressed_bytes": ulen[:k].astype(np.float64),
+        "unit_crc32": ucrc[:k].astype(np.float64),
+        "member_status": mstat[:k].astype(np.float64),
+        "sample_units": pick.astype(np.float64),
+        "compressed_sample": np.concatenate(comp).astype(np.float32),
+        "decompressed_sample": np.concatenate(back).astype(np.float32),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    for name, a in arrays.items():
+        np.save(os.path.join(dst, name + ".npy"), a)
+    print(f"bench.py: {len(arrays)} arrays ({total / 1e6:.1f} MB) written to {dst}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -116,7 +152,11 @@ def main():
     ap.add_argument("--cpu-sample-mib", type=int, default=0, help="0 = sized for ~10-30 s")
     ap.add_argument("--no-api", action="store_true", help="skip the drop-in API leg (host buffers over PCIe; outside the timed region)")
     ap.add_argument("--no-heldout", action="store_true", help="skip the held-out ratio leg (small deflate calls outside the timed region; counter passes average per launch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what rank 0's last step computed to DIR/<name>.npy "
+                                                          "(float32 / float64, a fixed sample of the larger arrays, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus)                  # does not return
     # stdout carries exactly ONE line, the JSON result: file descriptor 1 is pointed at stderr for the run (RCCL prints a version
@@ -275,6 +315,10 @@ def main():
     ctx.profiling(False)
     if exchange:
         dt = comm.max(dt)
+    if args.dump_outputs and rank == 0:
+        # before the checks below, which reuse d_out
+        dump_outputs(args.dump_outputs, nblocks, comp_total.value, d_comp, i32(d_ulen).view(np.uint32), i32(d_ucrc).view(np.uint32),
+                     d_out, i32(d_mstat))
     # the segment index of the compress leg's last call (what the writer puts behind its data member): taken now, before any
     # other deflate call of this context replaces it
     d_index = ctx.deflate_index(n_units) if (rank == 0 and blo == 0 and BLOCK_FLAGS and not args.no_foreign) else None

@@ -82,7 +82,8 @@ def mixed(nbytes, seed=5):
 
 
 def heldout(max_bytes=4 << 20):
-    """Held-out real files for the ratio gates (tests/test_oracle_ratio_heldout.py, bench.py `ratio_heldout`): data the level
+    """Held-out real files for the ratio gates (bench.py `ratio_heldout`; the tests read a stored sample of them made by
+    tests/golden/make_heldout.py): data the level
     table was NOT designed on a generator for.  Assembled at run time from files any box with Python has; a corpus whose
     files are missing is left out.  -> {name: bytes}, each at most max_bytes."""
     import glob

@@ -13,6 +13,13 @@ for p in (ROOT, PKG_DIR):
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
+def heldout_corpora():
+    """The held-out corpora of the ratio gates, stored under tests/golden/heldout (tests/golden/make_heldout.py) -> {name: bytes}"""
+    import lzma
+    d = os.path.join(GOLDEN, "heldout")
+    return {f[:-3]: lzma.decompress(open(os.path.join(d, f), "rb").read()) for f in sorted(os.listdir(d)) if f.endswith(".xz")}
+
+
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 

@@ -132,7 +132,7 @@ def _gloo_worker(rank, world, port, q, path):
         os.pwrite(fd, header, 0)
         os.pwrite(fd, trailer, len(header) + total)
     os.close(fd)
-    dist.barrier()
+    dist.monitored_barrier()                    # gloo's host-side barrier: dist.barrier() would open the GPU in every rank
     ok = ok and gzip.decompress(open(path, "rb").read()) == data
     # (3) the launcher-free hand-over of the communicator id: rank 0 serves 128 bytes over TCP
     uid = bytes(range(128)) if rank == 0 else None
@@ -142,7 +142,7 @@ def _gloo_worker(rank, world, port, q, path):
 
 
 def test_two_rank_allgather_reassembly_gloo(tmp_path):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp          # (not torch's: torch stays out of this process, whose later GPU tests load the engine's own RCCL)
     path = str(tmp_path / "written_by_two_ranks.gz")
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -198,7 +198,7 @@ def _gloo_worker8(rank, world, port, q, path):
         os.pwrite(fd, header, 0)
         os.pwrite(fd, trailer, len(header) + total)
     os.close(fd)
-    dist.barrier()
+    dist.monitored_barrier()                    # gloo's host-side barrier: dist.barrier() would open the GPU in every rank
     import gzip
     ok = ok and gzip.decompress(open(path, "rb").read()) == rng_bytes
     q.put((rank, ok, total))
@@ -206,7 +206,7 @@ def _gloo_worker8(rank, world, port, q, path):
 
 
 def test_eight_rank_layout_with_empty_and_uneven_slices_gloo(tmp_path):
-    import torch.multiprocessing as mp
+    import multiprocessing as mp          # (not torch's: torch stays out of this process, whose later GPU tests load the engine's own RCCL)
     path = str(tmp_path / "written_by_eight_ranks.gz")
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

@@ -4,7 +4,8 @@ The reference's level is zlib-ng's (zlib_ngmodule.c:1645 zng_deflateInit2(level,
 "other levels better than zlib" (README.rst:129-130).  zlib-ng is absent here, so the bar is the system zlib at the SAME level under
 the bench's own protocol -- 128 KiB units, each primed with the previous 32 KiB of input, one sync flush per unit
 (gzip_ng_threaded.py:317, zlib_ngmodule.c:1725-1742): compressed size within 2 % of zlib's at levels 1, 6 and 9 on every corpus
-(Python sources, two ELF binaries, C headers -- assembled at run time by zlib_ng_amd.corpus.heldout), and the synthetic corpora
+(Python sources, two ELF binaries, C headers: 2 MiB of each, stored under tests/golden/heldout by tests/golden/make_heldout.py
+from what zlib_ng_amd.corpus.heldout assembles), and the synthetic corpora
 the earlier rounds calibrated on still at least as good as zlib.  tests/test_gpu_ratio_heldout.py is the twin through the HIP path.
 """
 import zlib
@@ -16,8 +17,7 @@ UNIT = 131072
 WIN = 32768
 TOL = 1.02
 # The bars below were set against zlib 1.2.x (1.2.11 in this image).  Another deflate behind the same module name (zlib-ng's compat
-# build, a later zlib with other level tables) is another bar, and the corpora are whatever files this box has: the gate is then
-# skipped, not failed.  (bench.py reports the same comparison, with the library's version beside it, on every box.)
+# build, a later zlib with other level tables) is another bar: the gate is then skipped, not failed.  (bench.py reports the same comparison, with the library's version beside it, on every box.)
 pytestmark = pytest.mark.skipif(not zlib.ZLIB_RUNTIME_VERSION.startswith("1.2."),
                                 reason="ratio bars were set against zlib 1.2.x, this box has " + zlib.ZLIB_RUNTIME_VERSION)
 
@@ -46,10 +46,9 @@ def oracle_units(O, data, level, check=True):
 
 @pytest.fixture(scope="module")
 def corpora():
-    from zlib_ng_amd import corpus
-    c = corpus.heldout(4 << 20)
-    if not c:
-        pytest.skip("no held-out files on this box")
+    from conftest import heldout_corpora
+    c = heldout_corpora()
+    assert len(c) == 4, sorted(c)
     return c
 
 
