@@ -61,6 +61,15 @@ typedef struct zngamd_ctx zngamd_ctx;
 /* window of the stream the blocks belong to: match distances stay within 2^bits (deflateInit2's windowBits 9..15).
  * Taken from the FIRST block of a call and applied to all of them; 0 = 15. */
 #define ZNGAMD_FLAG_WBITS(bits) (((uint32_t)(bits) & 15u) << 8)
+/* compression strategy of the blocks (deflateInit2's strategy, ZNGAMD_STRATEGY_*).  Like the window, taken from the FIRST block
+ * of a call and applied to all of them; 0 = the default.  Level 0 writes stored blocks whatever the strategy, as zlib does. */
+#define ZNGAMD_FLAG_STRATEGY(s) (((uint32_t)(s) & 7u) << 12)
+#define ZNGAMD_STRATEGY_OF(flags) ((int)(((flags) >> 12) & 7u))
+#define ZNGAMD_STRATEGY_DEFAULT      0   /* Z_DEFAULT_STRATEGY */
+#define ZNGAMD_STRATEGY_FILTERED     1   /* Z_FILTERED: matches of 5 bytes or fewer are not taken */
+#define ZNGAMD_STRATEGY_HUFFMAN_ONLY 2   /* Z_HUFFMAN_ONLY: literals only, no match search */
+#define ZNGAMD_STRATEGY_RLE          3   /* Z_RLE: matches of distance 1 only (runs), no match search */
+#define ZNGAMD_STRATEGY_FIXED        4   /* Z_FIXED: fixed-code blocks (or stored), never a dynamic block */
 
 #define ZNGAMD_UNIT_MAX        131072u  /* largest span one kernel unit covers */
 #define ZNGAMD_SLOT_STRIDE     131136u  /* bytes reserved per unit in a device slot buffer */
@@ -104,7 +113,7 @@ typedef struct {
     uint64_t off;        /* offset of the block's first byte in `in` */
     uint32_t len;        /* block length (any size; cut into <=128 KiB units inside) */
     uint32_t dict_len;   /* bytes of `in` directly before `off` that prime the window (<= 32768) */
-    uint32_t flags;      /* ZNGAMD_FLAG_FINAL | ZNGAMD_FLAG_WBITS(n) */
+    uint32_t flags;      /* ZNGAMD_FLAG_FINAL | ZNGAMD_FLAG_WBITS(n) | ZNGAMD_FLAG_STRATEGY(s) */
     uint32_t reserved;
 } zngamd_block;
 

@@ -88,7 +88,9 @@ struct ZaPlan {
 // chain: steps of the walk over table A; cap: bytes compared per candidate (16 or 258; the winner is extended afterwards);
 // use_c: table C's candidate too; dp: the dynamic programme (stage 3a) between search and parse;
 // too_far3 / too_far4: a match of 3 / 4 bytes farther back than this is dropped
-struct ZaLevel { int chain, nice, max_dist, cap, use_c, dp, too_far3, too_far4; };
+// min_len: the shortest match the parse (and the dynamic programme) accepts -- 3, or 6 under Z_FILTERED (zlib's deflate_slow
+// drops matches of 5 bytes or fewer there); fixed_cost: the dynamic programme weighs the fixed code's costs (Z_FIXED)
+struct ZaLevel { int chain, nice, max_dist, cap, use_c, dp, too_far3, too_far4, min_len, fixed_cost; };
 
 typedef uint32_t __attribute__((aligned(1))) za_u32u;
 typedef uint64_t __attribute__((aligned(1))) za_u64u;

@@ -16,7 +16,10 @@
 //             follows its choices
 //   k_parse   one wave per unit, one lane per segment: greedy selection, symbol histogram with LDS atomics, CRC-32 per segment
 //             folded with GF(2) products
-//   k_plan    one wave per unit: length-limited canonical Huffman, block-type choice, header bits, the unit's exact size
+//   k_parse_rle  (Z_HUFFMAN_ONLY / Z_RLE, in place of chains, search, dynamic programme and parse) one wave per unit, one lane per
+//             segment: every byte a literal, or zlib's deflate_rle (runs as matches of distance 1) over the input staged through LDS;
+//             the same token words, histogram and CRC-32 as k_parse
+//   k_plan    one wave per unit: length-limited canonical Huffman, block-type choice, header bits, the unit's exact size (Z_FIXED: never a dynamic block)
 //   k_pack    one wave per unit, token-parallel: bit lengths -> wave prefix sum -> an LDS ring of the stream's open dwords
 #include "za_common.h"
 #include "za_crc.h"
@@ -1308,6 +1311,13 @@ __global__ __launch_bounds__(64) void za_k_optparse(const ZaUnit *__restrict__ u
     uint32_t *best = best_ws + (size_t)blockIdx.x * ZA_BEST_STRIDE;
     if (n == 0) return;
     for (int i = lane; i < ZA_DP_COSTS; i += 64) costt[i] = cost_ws[(size_t)blockIdx.x * ZA_DP_COSTS + i];
+    // Z_FIXED: the block will be coded with the fixed code, so its costs are the ones to weigh (quarter bits: literals 8 or 9 bits,
+    // a match 7 + 5 bits before extra bits) -- the unit's estimated dynamic costs would make literals of a small alphabet look cheap
+    if (L.fixed_cost) {
+        __syncthreads();
+        for (int i = lane; i < 256; i += 64) costt[i] = i < 144 ? 32u : 36u;
+        if (lane == 0) costt[256] = 48u;
+    }
     for (int len = lane; len <= ZA_MAX_MATCH; len += 64) {
         const int l0 = len > 7 ? len - ZA_DP_SUB : 3;
         uint32_t x[ZA_DP_SUB + 1];
@@ -1316,7 +1326,7 @@ __global__ __launch_bounds__(64) void za_k_optparse(const ZaUnit *__restrict__ u
             const int l = l0 + k;
             int lc, ln = 0, le;
             if (l <= ZA_MAX_MATCH) za_len_sym(l, lc, ln, le);
-            x[k] = (len >= 3 && l <= len) ? (uint32_t)(4 * ln) : 0x3FFFu;
+            x[k] = (len >= 3 && l <= len && l >= L.min_len) ? (uint32_t)(4 * ln) : 0x3FFFu;     // (min_len: 6 under Z_FILTERED)
         }
         xt[3 * len] = x[0] | (x[1] << 16); xt[3 * len + 1] = x[2] | (x[3] << 16); xt[3 * len + 2] = x[4] | ((uint32_t)l0 << 16);
     }
@@ -1516,6 +1526,12 @@ __global__ __launch_bounds__(64) void za_k_optparse(const ZaUnit *__restrict__ u
     if (has_long) walk(std::true_type{}); else walk(std::false_type{});
 }
 
+// a match length as the parse takes it: under Z_FILTERED (FILT) one shorter than L.min_len is no match
+template <bool FILT> __device__ __forceinline__ uint32_t za_minlen(uint32_t lf, const ZaLevel &L)
+{
+    return (!FILT || lf >= (uint32_t)L.min_len) ? lf : 0u;
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_parse  (+ histogram + CRC-32)
 // ------------------------------------------------------------------------------------------------
@@ -1530,6 +1546,8 @@ __global__ __launch_bounds__(64) void za_k_optparse(const ZaUnit *__restrict__ u
 // chunk (slot 0): the token at a chunk's last position looks at best[p + 1] (literals share token words) and is decided one chunk later.
 
 
+// FILT (Z_FILTERED): a match shorter than L.min_len is taken as a literal (the search's entries are left as they are)
+template <bool FILT>
 __global__ __launch_bounds__(64) void za_k_parse(const ZaUnit *__restrict__ units,
                                                  const uint32_t *__restrict__ best_ws, uint32_t *__restrict__ tok_ws,
                                                  uint32_t *__restrict__ segtok_ws, uint32_t *__restrict__ hist_ws,
@@ -1625,7 +1643,7 @@ __global__ __launch_bounds__(64) void za_k_parse(const ZaUnit *__restrict__ unit
                 while (p < lim) {
                     const uint32_t b = myb[p - cb + 1], bn = myb[p - cb + 2], e2 = myb[p - cb + 3];
                     // (greedy over the entries: on levels 4-9 the dynamic programme has rewritten them so that this IS its parse)
-                    const uint32_t lf = ZA_ELEN(b), nlf = ZA_ELEN(bn);
+                    const uint32_t lf = za_minlen<FILT>(ZA_ELEN(b), L), nlf = za_minlen<FILT>(ZA_ELEN(bn), L);
                     const bool is_match = lf != 0u;
                     const int len = (int)lf;
                     const uint32_t lit = b >> 24;
@@ -1640,7 +1658,7 @@ __global__ __launch_bounds__(64) void za_k_parse(const ZaUnit *__restrict__ unit
                     // text are literals, 3.8 in a row, and fewer token words are fewer stores here and fewer loads in the packer.
                     // (Their entries were read together with this position's: one LDS round trip per round.)
                     const bool c1 = lf == 0u && p + 1 < ce && nlf == 0u;
-                    const bool c2 = c1 && p + 2 < ce && ZA_ELEN(e2) == 0u;
+                    const bool c2 = c1 && p + 2 < ce && za_minlen<FILT>(ZA_ELEN(e2), L) == 0u;
                     const uint32_t l1 = bn >> 24, l2 = e2 >> 24;
                     const uint32_t t = is_match ? (0x80000000u | ((uint32_t)lc << 26) | ((uint32_t)le << 21) | ((uint32_t)dc << 16) | (uint32_t)de)
                                                 : lit | (c1 ? l1 << 8 : 0u) | (c2 ? l2 << 16 : 0u) | (((c1 ? 1u : 0u) + (c2 ? 1u : 0u)) << 24);
@@ -1689,6 +1707,191 @@ __global__ __launch_bounds__(64) void za_k_parse(const ZaUnit *__restrict__ unit
             for (int m = tail; m; m >>= 1) { if (m & 1) xt = za_multmodp(sq, xt); sq = za_multmodp(sq, sq); }
             // x^(8 * seg * k), k = the whole segments between mine and the last: from the table for 2 KiB segments, worked out for
             // the smaller segments of small units (x^8 squared sshift times, raised to the k)
+            uint32_t xk = 0x80000000u;
+            if (sshift == ZA_SEG_SHIFT) xk = x8k_table[nseg - 2 - lane];
+            else {
+                uint32_t xs = 0x00800000u;
+                for (int i = 0; i < sshift; i++) xs = za_multmodp(xs, xs);
+                for (int m = nseg - 2 - lane; m; m >>= 1) { if (m & 1) xk = za_multmodp(xs, xk); xs = za_multmodp(xs, xs); }
+            }
+            cseg = za_multmodp(za_multmodp(xk, xt), cseg);
+        }
+    }
+    cseg = za_wave_xor_reduce(cseg);
+    if (lane == 0) crc_out[blockIdx.x] = cseg;
+    segtok_ws[(size_t)blockIdx.x * ZA_MAX_SEGS + lane] = ntok;
+    __syncthreads();
+    if (lane == 0) hist[256] = 1;
+    __syncthreads();
+    for (int i = lane; i < ZA_HIST_STRIDE; i += 64) hist_ws[(size_t)blockIdx.x * ZA_HIST_STRIDE + i] = hist[i];
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_parse_rle  (Z_HUFFMAN_ONLY / Z_RLE: the whole match finder, + histogram + CRC-32)
+// ------------------------------------------------------------------------------------------------
+// Takes the place of chains + search (+ dynamic programme) + parse for the two strategies that need no hash table, and leaves
+// what k_parse leaves -- token words at the segments' slots, token counts, the 320-entry histogram, the unit's CRC-32 -- so that
+// plan and pack run unchanged.  One wave per unit, one lane per segment.  RUNS = false (Huffman-only): every byte a literal.
+// RUNS = true: zlib's deflate_rle inside each segment -- at p, with b = in[p - 1], a match of distance 1 if in[p], in[p + 1] and
+// in[p + 2] all equal b, as long as the run of b goes on (at most 258, and never past the segment's end), else a literal.  Walked
+// as a stream of bytes: `pend` bytes equal to `prev` are held back; a different byte (or the segment's end) turns them into a
+// match if there are 3 or more, else into literals; 258 held back leave as a match at once.  The byte in front of a segment is
+// its neighbour's last one, in front of the unit's first the dictionary's (none without one).  Distance 1 lies inside any window.
+// The input is read here (there are no `best` entries): staged through LDS like k_parse's entries, in chunks of 64 bytes per
+// segment, TRANSPOSED -- four lanes fetch the four aligned 16-byte pieces of one segment's row, so an instruction touches sixteen
+// rows, not 64 scattered lines -- with the next chunk's loads in flight while the current one is walked.  A row starts at the
+// aligned piece that holds the segment's first byte: every piece loaded holds at least one byte of the segment.
+#define ZA_RCH 64                       // bytes of a segment's row per chunk
+#define ZA_RROW (ZA_RCH / 4 + 1)        // dwords of a lane's byte row in LDS: an odd stride
+// Token slots of a lane's row per chunk.  A byte step emits at most two tokens (a held-back match, and the literal word in front
+// of it), and only a step that ends a run of 3 or more -- three steps that emit nothing before it, in this chunk or the one
+// before -- emits two; with the segment end's flush a chunk of 64 steps leaves at most 67.
+#define ZA_RTOK 68
+#define ZA_RTROW (ZA_RTOK + 1)
+template <bool RUNS>
+__global__ __launch_bounds__(64) void za_k_parse_rle(const uint8_t *__restrict__ in, const ZaUnit *__restrict__ units,
+                                                     uint32_t *__restrict__ tok_ws, uint32_t *__restrict__ segtok_ws,
+                                                     uint32_t *__restrict__ hist_ws, uint32_t *__restrict__ crc_out,
+                                                     const uint32_t *__restrict__ crc_table,   // [256]
+                                                     const uint32_t *__restrict__ x8k_table)   // [64] x^(8*2048*k)
+{
+    __shared__ uint32_t hist[ZA_HIST_STRIDE];
+    __shared__ uint32_t crct[256];
+    __shared__ uint32_t rowb[64 * ZA_RROW];
+    __shared__ uint32_t tokb[64 * ZA_RTROW];
+    const ZaUnit u = units[blockIdx.x];
+    const int n = (int)u.in_len;
+    const int lane = za_lane();
+    const int sshift = ZA_UNIT_SEG_SHIFT(u.flags), seg = 1 << sshift;      // the unit's segment size: 32 .. 2 048
+    const int nseg = (n + seg - 1) >> sshift;
+    for (int i = lane; i < ZA_HIST_STRIDE; i += 64) hist[i] = 0;
+    for (int i = lane; i < 256; i += 64) crct[i] = crc_table[i];
+    __syncthreads();
+
+    const uint8_t *ub = in + u.in_off;
+    const int s0 = lane << sshift;
+    int s1 = s0 + seg;
+    if (s1 > n) s1 = n;
+    const bool active = lane < nseg;
+    const int sh = (int)((uintptr_t)(ub + s0) & 15u);         // row index of my first byte
+    const int rend = active ? sh + (s1 - s0) : 0;             // ... and of my end
+    const uint32_t *myrow = rowb + lane * ZA_RROW;
+    uint32_t *mytok = tokb + lane * ZA_RTROW;
+
+    typedef uint32_t za_v4u __attribute__((ext_vector_type(4)));
+    za_v4u pb[4];                  // piece lane & 3 of the rows of segments 16 j + (lane >> 2)
+    auto prefetch = [&](int c) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int sg = 16 * j + (lane >> 2);
+            pb[j] = za_v4u{0u, 0u, 0u, 0u};
+            if (sg < nseg) {
+                const uint8_t *first = ub + (sg << sshift);
+                const int send = ((sg + 1) << sshift) < n ? ((sg + 1) << sshift) : n;
+                const uint8_t *a = (const uint8_t *)((uintptr_t)first & ~(uintptr_t)15) + c * ZA_RCH + 16 * (lane & 3);
+                // (streamed once: a non-temporal load; aligned, and only a piece that holds a byte of the segment)
+                if (a < ub + send) pb[j] = __builtin_nontemporal_load((const za_v4u *)a);
+            }
+        }
+    };
+
+    uint32_t crc_r = 0xFFFFFFFFu;
+    uint32_t ntok = 0, nchunk = 0;                // tokens of the segment stored so far / of the current chunk in my row
+    uint32_t litw = 0, litn = 0;                  // the literal word being filled, and its literals
+    uint32_t prev = 0x100u, pend = 0;             // (RUNS) the byte in front, and the bytes equal to it held back
+    if (RUNS && active && (s0 > 0 || u.dict_len > 0)) prev = ub[s0 - 1];
+    bool done = !active;
+    auto push = [&](uint32_t t) { mytok[nchunk] = t; nchunk++; };
+    auto lit = [&](uint32_t b) {
+        litw |= b << (8u * litn);
+        atomicAdd(&hist[b], 1u);
+        if (++litn == 3u) { push(litw | (2u << 24)); litw = 0; litn = 0; }
+    };
+    auto flush_lits = [&]() { if (litn) { push(litw | ((litn - 1u) << 24)); litw = 0; litn = 0; } };
+    auto match = [&](uint32_t len) {              // distance 1: distance code 0, no extra bits
+        flush_lits();
+        int lc, ln, le;
+        za_len_sym((int)len, lc, ln, le);
+        push(0x80000000u | ((uint32_t)lc << 26) | ((uint32_t)le << 21));
+        atomicAdd(&hist[257 + lc], 1u);
+        atomicAdd(&hist[288], 1u);
+    };
+    auto close_run = [&]() {
+        if (pend >= 3u) match(pend);
+        else for (uint32_t k = 0; k < pend; k++) lit(prev);
+        pend = 0;
+    };
+
+    const int nch = (15 + (n < seg ? n : seg) + ZA_RCH - 1) / ZA_RCH;      // chunks of the longest row
+    prefetch(0);
+#pragma unroll 1
+    for (int c = 0; c < nch; c++) {
+        const int ib = c * ZA_RCH;                // row index of the chunk's first byte
+        if (__ballot(ib < rend) == 0ull) break;   // (wave-uniform) every row is behind its end
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            uint32_t *r = rowb + (16 * j + (lane >> 2)) * ZA_RROW + 4 * (lane & 3);
+            r[0] = pb[j].x; r[1] = pb[j].y; r[2] = pb[j].z; r[3] = pb[j].w;
+        }
+        __builtin_amdgcn_wave_barrier();
+        prefetch(c + 1);
+        if (ib < rend) {
+#pragma unroll 2
+            for (int k = 0; k < ZA_RCH / 4; k++) {
+                const uint32_t w = myrow[k];      // (every lane reads dword k of its row: conflict free)
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const int i = ib + 4 * k + b;
+                    if (i >= sh && i < rend) {
+                        const uint32_t x = (w >> (8 * b)) & 0xFFu;
+                        crc_r = crct[(crc_r ^ x) & 0xFFu] ^ (crc_r >> 8);
+                        if (RUNS && x == prev) {
+                            if (++pend == (uint32_t)ZA_MAX_MATCH) { match(pend); pend = 0; }
+                        } else {
+                            if (RUNS) { close_run(); prev = x; }
+                            lit(x);
+                        }
+                    }
+                }
+            }
+        }
+        if (!done && rend <= ib + ZA_RCH) {       // my segment ends in this chunk
+            if (RUNS) close_run();
+            flush_lits();
+            done = true;
+        }
+        // ---- the chunk's tokens leave: lane (8 j + g, piece) stores tokens 4 q .. 4 q + 3 of segment 8 j + g, q = piece + 8 r
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const int sg = 8 * j + (lane >> 3);
+            const uint32_t cnt = (uint32_t)__shfl((int)nchunk, sg, 64), at = (uint32_t)__shfl((int)ntok, sg, 64);
+            const uint32_t *r = tokb + sg * ZA_RTROW;
+            uint32_t *dst = tok_ws + (size_t)blockIdx.x * ZA_TOK_STRIDE + ((size_t)sg << sshift) + at;
+#pragma unroll
+            for (int q = 0; q < 3; q++) {
+                const uint32_t first = 4u * (uint32_t)((lane & 7) + 8 * q);
+                // whole 16-byte pieces (up to three slots of no meaning behind the tokens: the next chunk's land on them), token by
+                // token only where a piece would leave the segment's slots (k_parse does the same)
+                if (first < cnt) {
+                    if (at + first + 4u <= (uint32_t)seg) { ZaU4u v; v.x = r[first]; v.y = r[first + 1]; v.z = r[first + 2]; v.w = r[first + 3]; *(ZaU4u *)(dst + first) = v; }
+                    else for (uint32_t i = first; i < cnt && i < first + 4u; i++) dst[i] = r[i];
+                }
+            }
+        }
+        ntok += nchunk; nchunk = 0;
+        __builtin_amdgcn_wave_barrier();
+    }
+    // ---- fold the per-segment CRCs: crc(A||B) = crc(A) * x^(8|B|) ^ crc(B)  (as k_parse)
+    uint32_t cseg = 0;
+    if (active) {
+        cseg = crc_r ^ 0xFFFFFFFFu;
+        if (lane < nseg - 1) {
+            const int tail = n - ((nseg - 1) << sshift);
+            uint32_t xt = 0x80000000u, sq = 0x00800000u;
+            for (int m = tail; m; m >>= 1) { if (m & 1) xt = za_multmodp(sq, xt); sq = za_multmodp(sq, sq); }
             uint32_t xk = 0x80000000u;
             if (sshift == ZA_SEG_SHIFT) xk = x8k_table[nseg - 2 - lane];
             else {
@@ -2086,7 +2289,7 @@ __device__ unsigned long long za_plan_stat[16];   // profiling build only: clock
 __global__ __launch_bounds__(64) void za_k_plan(const ZaUnit *__restrict__ units, const uint32_t *__restrict__ hist_ws,
                                                 uint32_t *__restrict__ code_ws, ZaPlan *__restrict__ plan_ws,
                                                 uint8_t *__restrict__ out, uint32_t out_stride, int level,
-                                                uint8_t *__restrict__ hdr_ws, uint32_t *__restrict__ unit_len)
+                                                uint8_t *__restrict__ hdr_ws, uint32_t *__restrict__ unit_len, int fixed_only)
 {
     __shared__ ZaPlanLds S;
     const ZaUnit u = units[blockIdx.x];
@@ -2261,6 +2464,9 @@ __global__ __launch_bounds__(64) void za_k_plan(const ZaUnit *__restrict__ units
     unsigned long long bestc = cost_dyn; int btype = 2;
     if (cost_fix <= bestc) { bestc = cost_fix; btype = 1; }
     if (cost_sto <= bestc) { bestc = cost_sto; btype = 0; }
+    // Z_FIXED: never a dynamic block -- fixed, or stored where stored beats BOTH Huffman forms (zlib's _tr_flush_block: stored if
+    // stored_len + 4 <= min(opt_lenb, static_lenb), else static under Z_FIXED)
+    if (fixed_only && btype == 2) btype = 1;
     ZA_PLAN_T(7);
     plan.btype = (uint32_t)btype;
     if (unit_len && lane == 0) {

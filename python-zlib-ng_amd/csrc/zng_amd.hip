@@ -25,13 +25,13 @@ static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT +
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
 // the level table (the same numbers as the oracle's): chain steps over table A, nice, cap, table C, dynamic programme,
-// too_far3, too_far4.  Within 2 % of zlib 1.2.11 at the same level on held-out real files, at least zlib on the synthetic corpora.
+// too_far3, too_far4, shortest match (6 under Z_FILTERED, set per call), fixed-code costs (Z_FIXED, set per call).  Within 2 % of zlib 1.2.11 at the same level on held-out real files, at least zlib on the synthetic corpora.
 #define ZA_CH_STREAMS_PER_CU (ZA_HASH_BITS >= 14 ? 2u : 3u)     // what the chain kernel's LDS (table + 14 KiB) lets a CU hold
 static const ZaLevel ZA_LEVELS[10] = {
-    {0, 0, ZA_WIN, 0, 0, 0, 0, 0},
-    {1, 16, ZA_WIN, 16, 0, 0, 256, 4096}, {2, 16, ZA_WIN, 16, 0, 0, 256, 4096}, {3, 16, ZA_WIN, 16, 0, 0, 256, 4096},
-    {2, 16, ZA_WIN, 16, 0, 1, 4096, 32768}, {2, 16, ZA_WIN, 16, 1, 1, 4096, 32768}, {3, 16, ZA_WIN, 16, 1, 1, 4096, 32768},
-    {4, 32, ZA_WIN, 258, 1, 1, 4096, 32768}, {8, 64, ZA_WIN, 258, 1, 1, 4096, 32768}, {12, 128, ZA_WIN, 258, 1, 1, 4096, 32768}};
+    {0, 0, ZA_WIN, 0, 0, 0, 0, 0, 3, 0},
+    {1, 16, ZA_WIN, 16, 0, 0, 256, 4096, 3, 0}, {2, 16, ZA_WIN, 16, 0, 0, 256, 4096, 3, 0}, {3, 16, ZA_WIN, 16, 0, 0, 256, 4096, 3, 0},
+    {2, 16, ZA_WIN, 16, 0, 1, 4096, 32768, 3, 0}, {2, 16, ZA_WIN, 16, 1, 1, 4096, 32768, 3, 0}, {3, 16, ZA_WIN, 16, 1, 1, 4096, 32768, 3, 0},
+    {4, 32, ZA_WIN, 258, 1, 1, 4096, 32768, 3, 0}, {8, 64, ZA_WIN, 258, 1, 1, 4096, 32768, 3, 0}, {12, 128, ZA_WIN, 258, 1, 1, 4096, 32768, 3, 0}};
 
 template <typename T> struct DevBuf {
     T *p = nullptr; size_t cap = 0;
@@ -486,6 +486,9 @@ try {
 // ---------------------------------------------------------------------------------------------
 int zngamd_level_ok(int level) { return level >= -1 && level <= 9; }
 
+// the strategy of a call: ZNGAMD_FLAG_STRATEGY of its first block, like the window (0 = the default; 5..7 are refused)
+static int strategy_of(const zngamd_block *blocks, uint32_t n_blocks) { return n_blocks ? ZNGAMD_STRATEGY_OF(blocks[0].flags) : ZNGAMD_STRATEGY_DEFAULT; }
+
 static uint32_t unit_size_of(const zngamd_block &b) { return (b.flags & ZNGAMD_FLAG_UNITS16K) ? ZA_SMALL_UNIT : (uint32_t)ZA_MAX_UNIT; }
 static uint32_t units_of(const zngamd_block &b) { const uint64_t U = unit_size_of(b); return b.len == 0 ? 1u : (uint32_t)(((uint64_t)b.len + U - 1) / U); }
 
@@ -530,16 +533,20 @@ struct PackedDst { uint8_t *d_dst = nullptr; uint64_t cap = 0; uint64_t *d_unit_
                    uint64_t *d_total = nullptr; uint32_t *d_status = nullptr; };      // (optional) where the stream's size and the units' pack status go: a caller that fetches all results with one copy
 static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const std::vector<ZaUnit> &hu, int level,
                              uint8_t *d_slots, uint32_t *d_unit_len, uint32_t *d_unit_crc, int max_dist = ZA_WIN,
-                             const PackedDst *packed = nullptr)
+                             const PackedDst *packed = nullptr, int strategy = ZNGAMD_STRATEGY_DEFAULT)
 {
     if (level == -1) level = 6;
     if (level < 0 || level > 9) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (strategy < ZNGAMD_STRATEGY_DEFAULT || strategy > ZNGAMD_STRATEGY_FIXED) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression strategy");
+    // Z_HUFFMAN_ONLY / Z_RLE (level >= 1): no link tables, no search -- k_parse_rle reads the input itself
+    const bool runs_only = level > 0 && (strategy == ZNGAMD_STRATEGY_HUFFMAN_ONLY || strategy == ZNGAMD_STRATEGY_RLE);
+    const bool search = level > 0 && !runs_only;
     const uint32_t n = (uint32_t)hu.size();
     if (n == 0) return ZNGAMD_OK;
     HIPCHK(c, hipSetDevice(c->device));
     uint32_t ch = std::min(n, c->chunk_units);
     const size_t ntab = ZA_LEVELS[level].use_c ? 3 : 2;
-    if (level > 0) {
+    if (search) {
         // a chunk's workspaces must fit what the device has free (plus what these buffers hold already): halve it until they do
         // (a hipMalloc failure further down is still a hard error, but no longer the first thing a smaller device or a second
         // context on this one meets)
@@ -551,7 +558,19 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
         }
     }
     HIPCHK(c, c->units.ensure(n)); HIPCHK(c, c->segbits.ensure((size_t)n * ZA_SEGB_STRIDE)); HIPCHK(c, c->cidx.ensure((size_t)n * ZA_CIDX_STRIDE)); HIPCHK(c, c->status.ensure(n));
-    if (level > 0) {
+    if (runs_only) {
+        // only the token words: in the link tables' buffer (grown to 512 KiB a unit if a search never made it larger), or, when the
+        // debug copies are kept, in their own
+        const size_t held = c->links.cap * 2 + (c->debug_keep ? c->tok.cap * 4 : 0);
+        size_t free_b = 0, total_b = 0;
+        if (ch > 64 && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            auto need = [&](uint32_t k) { return (size_t)k * (ZA_TOK_STRIDE * 4 + 8192); };
+            while (ch > 64 && need(ch) > held && need(ch) - held > free_b - free_b / 16) ch = (ch + 1) / 2;
+        }
+        if (c->debug_keep) { HIPCHK(c, c->tok.ensure((size_t)ch * ZA_TOK_STRIDE)); c->tok_p = c->tok.p; }
+        else { HIPCHK(c, c->links.ensure((size_t)ch * ZA_TOK_STRIDE * 2)); c->tok_p = (uint32_t *)c->links.p; }
+    }
+    if (search) {
         const size_t tab = (size_t)ch * ZA_PREV_STRIDE + 8;              // entries of one link table (+ slack for the search's four-link loads)
         HIPCHK(c, c->links.ensure(ntab * tab)); HIPCHK(c, c->best.ensure((size_t)ch * ZA_BEST_STRIDE));
         c->prev_p = c->links.p; c->linkb_p = c->links.p + tab; c->linkc_p = ntab > 2 ? c->links.p + 2 * tab : nullptr;
@@ -633,6 +652,9 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
     // (no memset of the slots: the pack kernel zeroes the few words it merges with atomic OR and writes the rest whole)
     ZaLevel L = ZA_LEVELS[level];
     L.max_dist = (max_dist < 1 || max_dist > ZA_WIN) ? ZA_WIN : max_dist;
+    if (strategy == ZNGAMD_STRATEGY_FILTERED) L.min_len = 6;             // zlib's deflate_slow under Z_FILTERED: match_length <= 5 is dropped
+    const int fixed_only = strategy == ZNGAMD_STRATEGY_FIXED ? 1 : 0;
+    L.fixed_cost = fixed_only;
     size_t run_pos = 0;
     for (uint32_t c0 = 0; c0 < n; c0 += ch) {
         const uint32_t m = std::min(ch, n - c0);
@@ -641,7 +663,15 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
         while (run_start[run_pos + nruns] != m) nruns++;
         const uint32_t *d_runs = c->runs.p + run_pos;
         run_pos += nruns + 1;
-        if (level > 0) {
+        if (runs_only) {
+            ProfScope ps(c, ZNGAMD_K_PARSE);
+            if (strategy == ZNGAMD_STRATEGY_RLE)
+                hipLaunchKernelGGL(za_k_parse_rle<true>, dim3(m), dim3(64), 0, c->stream, d_in, du, c->tok_p, c->segtok.p, c->hist.p,
+                                   d_unit_crc + c0, c->d_crc_table, c->d_x8k);
+            else
+                hipLaunchKernelGGL(za_k_parse_rle<false>, dim3(m), dim3(64), 0, c->stream, d_in, du, c->tok_p, c->segtok.p, c->hist.p,
+                                   d_unit_crc + c0, c->d_crc_table, c->d_x8k);
+        } else if (search) {
             { ProfScope ps(c, ZNGAMD_K_CHAINS);
               hipLaunchKernelGGL(za_k_chains<ZA_TABLE_A>, dim3(nruns), dim3(256), 0, c->stream, d_in, du, d_runs, c->prev_p, L.dp ? c->dpcost.p : (uint32_t *)nullptr);
               hipLaunchKernelGGL(za_k_chains<ZA_TABLE_B>, dim3(nruns), dim3(256), 0, c->stream, d_in, du, d_runs, c->linkb_p, (uint32_t *)nullptr);
@@ -664,8 +694,12 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
                 hipLaunchKernelGGL(za_k_optparse, dim3(m), dim3(64), 0, c->stream, du, c->best.p, c->dpcost.p, c->tok_p, L);
             }
             { ProfScope ps(c, ZNGAMD_K_PARSE);
-              hipLaunchKernelGGL(za_k_parse, dim3(m), dim3(64), 0, c->stream, du, c->best.p, c->tok_p, c->segtok.p, c->hist.p,
-                                 d_unit_crc + c0, c->d_crc_table, c->d_x8k, L); }
+              if (L.min_len > ZA_MIN_MATCH)
+                  hipLaunchKernelGGL(za_k_parse<true>, dim3(m), dim3(64), 0, c->stream, du, c->best.p, c->tok_p, c->segtok.p, c->hist.p,
+                                     d_unit_crc + c0, c->d_crc_table, c->d_x8k, L);
+              else
+                  hipLaunchKernelGGL(za_k_parse<false>, dim3(m), dim3(64), 0, c->stream, du, c->best.p, c->tok_p, c->segtok.p, c->hist.p,
+                                     d_unit_crc + c0, c->d_crc_table, c->d_x8k, L); }
         } else {       // level 0: stored blocks, nothing to search or parse -- only the units' CRC-32
             ProfScope ps(c, ZNGAMD_K_PARSE);
             hipLaunchKernelGGL(za_k_unit_crc, dim3(m), dim3(64), 0, c->stream, d_in, du, d_unit_crc + c0, c->d_crc_table, c->d_x8k);
@@ -673,7 +707,7 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
         if (packed) {
             { ProfScope ps(c, ZNGAMD_K_PLAN);
               hipLaunchKernelGGL(za_k_plan, dim3(m), dim3(64), 0, c->stream, du, c->hist.p, c->codes.p, c->plan.p,
-                                 (uint8_t *)nullptr, 0u, level, c->hdr.p, d_unit_len + c0); }
+                                 (uint8_t *)nullptr, 0u, level, c->hdr.p, d_unit_len + c0, fixed_only); }
             { ProfScope ps(c, ZNGAMD_K_GATHER);          // (what is left of the gather: the prefix sum)
               hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(m <= 64 ? 64 : 1024), 0, c->stream, d_unit_len + c0, m, 0u, 0ull, d_offs + c0, d_run_total,
                                  (const ZaUnit *)nullptr, c0 ? (const uint64_t *)d_run_total : (const uint64_t *)nullptr, 1); }
@@ -684,7 +718,7 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
         } else {
         { ProfScope ps(c, ZNGAMD_K_PLAN);
           hipLaunchKernelGGL(za_k_plan, dim3(m), dim3(64), 0, c->stream, du, c->hist.p, c->codes.p, c->plan.p,
-                             d_slots + (size_t)c0 * ZNGAMD_SLOT_STRIDE, (uint32_t)ZNGAMD_SLOT_STRIDE, level, (uint8_t *)nullptr, (uint32_t *)nullptr); }
+                             d_slots + (size_t)c0 * ZNGAMD_SLOT_STRIDE, (uint32_t)ZNGAMD_SLOT_STRIDE, level, (uint8_t *)nullptr, (uint32_t *)nullptr, fixed_only); }
         { ProfScope ps(c, ZNGAMD_K_PACK);
           hipLaunchKernelGGL(za_k_pack, dim3(m), dim3(64), 0, c->stream, d_in, du, c->tok_p, c->segtok.p, c->codes.p, c->plan.p,
                              c->segbits.p + (size_t)c0 * ZA_SEGB_STRIDE, c->cidx.p + (size_t)c0 * ZA_CIDX_STRIDE, d_slots + (size_t)c0 * ZNGAMD_SLOT_STRIDE,
@@ -713,7 +747,8 @@ try {
     }
     const std::vector<ZaUnit> &hu = c->blocks_hu;
     if (h_unit_block) for (size_t i = 0; i < hu.size(); i++) h_unit_block[i] = hu[i].block;
-    r = deflate_units_dev(c, (const uint8_t *)d_in, in_len, hu, level, (uint8_t *)d_slots, d_unit_len, d_unit_crc);
+    r = deflate_units_dev(c, (const uint8_t *)d_in, in_len, hu, level, (uint8_t *)d_slots, d_unit_len, d_unit_crc, ZA_WIN, nullptr,
+                          strategy_of(blocks, n_blocks));
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -741,7 +776,7 @@ try {
     *total_bytes = 0;
     if (hu.empty()) return ZNGAMD_OK;
     PackedDst pd; pd.d_dst = (uint8_t *)d_out; pd.cap = out_cap; pd.d_unit_off = d_unit_off;
-    r = deflate_units_dev(c, (const uint8_t *)d_in, in_len, hu, level, nullptr, d_unit_len, d_unit_crc, ZA_WIN, &pd);
+    r = deflate_units_dev(c, (const uint8_t *)d_in, in_len, hu, level, nullptr, d_unit_len, d_unit_crc, ZA_WIN, &pd, strategy_of(blocks, n_blocks));
     if (r) return r;
     const uint64_t *d_run_total = (const uint64_t *)((const uint8_t *)c->d_small + 224);
     std::vector<uint32_t> st(hu.size());
@@ -903,7 +938,8 @@ static int deflate_host_common(zngamd_ctx *c, uint64_t in_len, const zngamd_bloc
                            (ZaCkPart *)(d_head + o_ck), ck->want_crc ? 1 : 0, ck->want_adler ? 1 : 0);
     }
     { PhaseClock pc(c, "deflate kernels");
-      r = deflate_units_dev(c, c->st_in.p, in_len, hu, level, nullptr, (uint32_t *)(d_head + o_len), (uint32_t *)(d_head + o_crc), max_dist, &pd); }
+      r = deflate_units_dev(c, c->st_in.p, in_len, hu, level, nullptr, (uint32_t *)(d_head + o_len), (uint32_t *)(d_head + o_crc), max_dist, &pd,
+                            strategy_of(blocks, n_blocks)); }
     if (r) return r;
     const bool direct = direct_out != nullptr;
     // One round trip for the results, and for a small stream the bytes as well (its upper bound travels: the size is not known yet)

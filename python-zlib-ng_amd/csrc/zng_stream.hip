@@ -36,6 +36,7 @@ typedef std::vector<uint8_t, ZsNoInit<uint8_t>> ZsBytes;
 
 struct ZsDeflate {
     int level = 6, kind = 1 /* 0 raw, 1 zlib, 2 gzip */, wb = 15;
+    int strategy = 0;                        // ZNGAMD_STRATEGY_* (deflateInit2's strategy), on every block of the stream
     std::vector<uint8_t> pending, tail;      // pending = [pend_tail bytes of tail][collected input] (empty: nothing collected)
     size_t pend_tail = 0;
     bool started = false, finished = false, has_dict = false;
@@ -119,7 +120,7 @@ static int zs_deflate_batch(zngamd_stream *s, const uint8_t *data, size_t n, boo
         std::vector<uint8_t> hb(d.tail.size() + head);
         if (!d.tail.empty()) memcpy(hb.data(), d.tail.data(), d.tail.size());
         if (head) memcpy(hb.data() + d.tail.size(), data + pos, head);
-        const uint32_t wflag = ZNGAMD_FLAG_WBITS(d.wb);
+        const uint32_t wflag = ZNGAMD_FLAG_WBITS(d.wb) | ZNGAMD_FLAG_STRATEGY(d.strategy);
         auto run = [&](const uint8_t *buf, size_t buf_len, size_t off, size_t len, size_t dict, bool fin) -> int {
             zngamd_block B; B.off = off; B.len = (uint32_t)len; B.dict_len = (uint32_t)dict; B.flags = wflag | (fin ? ZNGAMD_FLAG_FINAL : 0u); B.reserved = 0;
             const uint64_t cap = len + len / 8 + (len / ZA_MAX_UNIT + 2) * 64 + 64;
@@ -167,7 +168,7 @@ static int zs_deflate_pending(zngamd_stream *s, bool final)
     if (d.pending.empty()) { d.pending = d.tail; d.pend_tail = d.tail.size(); }        // (final with nothing collected)
     const size_t tl = d.pend_tail, n = d.pending.size() - tl;
     if (n > (1u << 30)) return ZNGAMD_E_ARG;          // (cannot happen: collected input is emitted at 32 MiB, larger pieces go direct)
-    zngamd_block B; B.off = tl; B.len = (uint32_t)n; B.dict_len = (uint32_t)tl; B.flags = ZNGAMD_FLAG_WBITS(d.wb) | (final ? ZNGAMD_FLAG_FINAL : 0u); B.reserved = 0;
+    zngamd_block B; B.off = tl; B.len = (uint32_t)n; B.dict_len = (uint32_t)tl; B.flags = ZNGAMD_FLAG_WBITS(d.wb) | ZNGAMD_FLAG_STRATEGY(d.strategy) | (final ? ZNGAMD_FLAG_FINAL : 0u); B.reserved = 0;
     const uint64_t cap = n + n / 8 + (n / ZA_MAX_UNIT + 2) * 64 + 64;
     const size_t at = st->outq.size();
     st->outq.resize(at + cap);
@@ -229,7 +230,7 @@ try {
     else return ZNGAMD_STREAM_ERROR;
     zngamd_stream_state *st = new zngamd_stream_state();
     st->ctx = c; st->is_deflate = true;
-    st->d.level = level; st->d.kind = kind; st->d.wb = wb;
+    st->d.level = level; st->d.kind = kind; st->d.wb = wb; st->d.strategy = strategy;
     s->state = st;
     s->adler = kind == 2 ? 0u : 1u;
     return ZNGAMD_OK;
@@ -309,14 +310,14 @@ try {
     return ZNGAMD_OK;
 } ZS_GUARD
 
-// zng_deflateReset (zlib_ngmodule.c:1725): back to the state right behind deflate_init -- level, container and window kept,
+// zng_deflateReset (zlib_ngmodule.c:1725): back to the state right behind deflate_init -- level, strategy, container and window kept,
 // everything collected, the history, a preset dictionary and the checksums forgotten
 int zngamd_stream_deflate_reset(zngamd_stream *s)
 try {
     if (!s || !s->state || !s->state->is_deflate) return ZNGAMD_STREAM_ERROR;
     zngamd_stream_state *st = s->state;
     ZsDeflate fresh;
-    fresh.level = st->d.level; fresh.kind = st->d.kind; fresh.wb = st->d.wb;
+    fresh.level = st->d.level; fresh.kind = st->d.kind; fresh.wb = st->d.wb; fresh.strategy = st->d.strategy;
     st->d = fresh;
     st->outq.clear(); st->outpos = 0; st->msg.clear();
     s->msg = nullptr; s->total_in = s->total_out = 0; s->adler = fresh.kind == 2 ? 0u : 1u;

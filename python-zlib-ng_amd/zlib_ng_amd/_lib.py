@@ -29,6 +29,26 @@ SLOT_STRIDE = 131136
 SEG = 2048
 INDEX_STRIDE = 68        # ZNGAMD_INDEX_STRIDE
 FLAG_FINAL, FLAG_FLATHDR, FLAG_SEG2K, FLAG_UNITS16K = 1, 2, 16, 32
+# ZNGAMD_STRATEGY_* (zlib's values), carried by a call's first block as ZNGAMD_FLAG_STRATEGY
+STRATEGY_DEFAULT, STRATEGY_FILTERED, STRATEGY_HUFFMAN_ONLY, STRATEGY_RLE, STRATEGY_FIXED = 0, 1, 2, 3, 4
+
+
+def flag_strategy(strategy):
+    """ZNGAMD_FLAG_STRATEGY(strategy)"""
+    if not STRATEGY_DEFAULT <= strategy <= STRATEGY_FIXED:
+        raise ValueError(f"bad compression strategy {strategy}")
+    return strategy << 12
+
+
+def with_strategy(table, strategy):
+    """A copy of a block table (from block_table()) with `strategy` on every block: the caller's table is left as it is."""
+    arr, n = table
+    fl = flag_strategy(strategy)
+    out = (Block * max(n, 1))()
+    C.memmove(out, arr, C.sizeof(Block) * max(n, 1))
+    for i in range(n):
+        out[i].flags = (out[i].flags & ~(7 << 12)) | fl
+    return out, n
 # The writer's segment index in a FILE (r06): behind the data member, EMPTY gzip members (header with FEXTRA, `03 00`, zero CRC and
 # ISIZE) whose 'Z','A' subfield holds: version 3, kind 1, the number of records (u16), the first record's unit number (u32), then
 # records of 138 bytes -- a unit's compressed bytes (u32, sync marker included), its output bytes (u32), 65 x u16: the bit offset of
@@ -556,7 +576,7 @@ class Context:
         return self.L.zngamd_crc32_combine(crc1 & 0xFFFFFFFF, crc2 & 0xFFFFFFFF, len2)
 
     # ---- deflate
-    def deflate_blocks(self, buf, blocks, level, out_cap, joined=False, into=None, index=False):
+    def deflate_blocks(self, buf, blocks, level, out_cap, joined=False, into=None, index=False, strategy=STRATEGY_DEFAULT):
         """blocks: list of (off, len, dict_len, flags), or a table made by block_table() (a writer whose batches have the
         same shape makes it once).  -> (list of bytes|None, list of crc, overflowed); with joined=True the first element is
         ONE object, the blocks' outputs back to back (a writer that only concatenates them saves the allocation and release
@@ -566,8 +586,10 @@ class Context:
         writes into warm memory; a fresh object costs a page fault per 4 KiB).  `index` (joined only): the segment-index records
         of the call's units come back as a fifth element (None after an overflow) -- from the SAME engine call
         (zngamd_deflate_blocks_packed_indexed): a context that several writer threads share answers zngamd_deflate_index for its
-        last deflate call, whoever made it."""
+        last deflate call, whoever made it.  `strategy`: zlib's compression strategy (STRATEGY_*) for every block of the call."""
         arr, n = blocks if isinstance(blocks, tuple) and len(blocks) == 2 and isinstance(blocks[0], C.Array) else block_table(blocks)
+        if strategy != STRATEGY_DEFAULT:
+            arr, n = with_strategy((arr, n), strategy)
         p, keep = _addr(buf)
         lens = (C.c_uint32 * max(n, 1))()
         crcs = (C.c_uint32 * max(n, 1))()
