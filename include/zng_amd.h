@@ -242,6 +242,34 @@ int zngamd_gzip_inflate_plain_members_dev(zngamd_ctx *ctx, const void *d_in, uin
                                           const zngamd_member *d_members, uint32_t n_members,
                                           void *d_out, uint64_t out_cap, int32_t *d_status);
 
+/* ---- spans of a seek-point index (zlib_ng_amd/gzip_index.py): pieces of gzip members' deflate data that decode on their own.
+ * A span starts at a deflate block header, absolute bit in_bit of d_in, with win_len (0..32768) bytes of d_windows at win_off as
+ * history.  It ends at the block header at absolute bit end_bit, or where its member's final block ends (end_bit = that end
+ * rounded up to a whole byte).  It must produce exactly out_len bytes (at out_off of d_out) whose CRC-32 is crc.  One 64-lane
+ * wavefront per span, all spans in one launch.  d_in must hold ZNGAMD_SPAN_PAD readable bytes behind the end of every span; no
+ * span reads outside [in_bit / 8, end_bit / 8 + ZNGAMD_SPAN_PAD) or writes outside its output range.  d_status[i] receives a
+ * ZNGAMD_SPAN_* code (an entry that points outside the buffers is ZNGAMD_SPAN_DATA). */
+typedef struct {
+    uint64_t in_bit, end_bit;
+    uint64_t win_off, out_off;
+    uint32_t win_len, out_len;
+    uint32_t crc, reserved;
+} zngamd_span;
+#define ZNGAMD_SPAN_OK     0
+#define ZNGAMD_SPAN_DATA   1
+#define ZNGAMD_SPAN_LENGTH 2
+#define ZNGAMD_SPAN_CRC    3
+#define ZNGAMD_SPAN_PAD    64
+int zngamd_inflate_spans_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_span *d_spans, uint32_t n,
+                             const void *d_windows, uint64_t windows_len, void *d_out, uint64_t out_cap, int32_t *d_status);
+/* Host-buffer form: stages in (padded here), the span table and the windows, launches once, copies the statuses (n entries)
+ * and out_cap bytes of output back.  Returns ZNGAMD_OK when the call ran; the verdict per span is in status[]. */
+int zngamd_inflate_spans(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_span *spans, uint32_t n,
+                         const uint8_t *windows, uint64_t windows_len, uint8_t *out, uint64_t out_cap, int32_t *status);
+/* what the span decoder did since the last reset: out[0] spans launched (either form), out[1] output bytes of the spans that
+ * zngamd_inflate_spans decoded with ZNGAMD_SPAN_OK (the device form leaves its statuses on the device and does not count bytes) */
+int zngamd_span_stats(zngamd_ctx *ctx, uint64_t *out /*[2]*/, int reset);
+
 /* One raw deflate stream that lies in device memory (d_in must be readable 64 bytes past in_len), decoded into device
  * memory: chunk-parallel where the stream offers block boundaries (sync-flush points, dynamic block headers), else on one
  * wavefront.  Returns ZNGAMD_STREAM_END when the final block ended; *out_len = bytes produced, *in_used = bytes consumed. */

@@ -7,6 +7,7 @@
 #include "za_deflate.hip"
 #include "za_inflate.hip"
 #include "za_inflate_units.hip"
+#include "za_inflate_spans.hip"
 #include "za_checksum.hip"
 #include "../../include/zng_amd.h"
 
@@ -21,6 +22,7 @@
 #include <vector>
 
 static_assert(sizeof(zngamd_member) == sizeof(ZaMember), "member layout");
+static_assert(sizeof(zngamd_span) == sizeof(ZaSpan) && ZNGAMD_SPAN_PAD == ZA_SPAN_PAD && ZNGAMD_SPAN_CRC == ZA_SPAN_CRC, "span layout");
 static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT + 32, "slot stride");
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
@@ -99,6 +101,8 @@ struct zngamd_ctx {
     // profiling
     uint64_t paths[4] = {0, 0, 0, 0};            // members decoded per path, see zngamd_decode_paths
     uint64_t indexed_units = 0;                  // units decoded with a writer's index (zngamd_indexed_units)
+    uint64_t span_stats[2] = {0, 0};             // spans and bytes of the span decoder (zngamd_span_stats)
+    DevBuf<uint8_t> sp_in, sp_win, sp_out; DevBuf<ZaSpan> sp_tab; DevBuf<int32_t> sp_status;      // staging of zngamd_inflate_spans
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
     uint8_t *h_tab = nullptr; size_t h_tab_cap = 0;
@@ -234,6 +238,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->st_in.release(); c->st_out.release(); c->st_slots.release(); c->st_aux.release(); c->st_len.release(); c->st_crc.release();
     c->ccand.release(); c->csurv.release(); c->cres.release(); c->cchunks.release(); c->out16.release(); c->ccomp.release(); c->winbuf.release(); c->uarea.release();
     c->st_off.release(); c->runs.release(); c->ck.release(); c->matchq.release(); c->cands.release(); c->members.release(); c->mstatus.release();
+    c->sp_in.release(); c->sp_win.release(); c->sp_out.release(); c->sp_tab.release(); c->sp_status.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -1471,6 +1476,67 @@ try {
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- spans of a seek-point index (za_inflate_spans.hip)
+static int inflate_spans_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaSpan *d_spans, uint32_t n, const uint8_t *d_windows,
+                             uint64_t windows_len, uint8_t *d_out, uint64_t out_cap, int32_t *d_status)
+{
+    if (n) {
+        ProfScope ps(c, ZNGAMD_K_INFLATE);
+        hipLaunchKernelGGL(za_k_inflate_spans, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_spans, d_windows, windows_len, d_out, out_cap,
+                           c->d_crc_table, c->d_x8k, d_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    c->span_stats[0] += n;
+    return ZNGAMD_OK;
+}
+
+int zngamd_inflate_spans_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_span *d_spans, uint32_t n,
+                             const void *d_windows, uint64_t windows_len, void *d_out, uint64_t out_cap, int32_t *d_status)
+try {
+    if (!c || (n && (!d_in || !d_spans || !d_out || !d_status)) || (windows_len && !d_windows)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = inflate_spans_dev(c, (const uint8_t *)d_in, in_len, (const ZaSpan *)d_spans, n, (const uint8_t *)d_windows, windows_len,
+                              (uint8_t *)d_out, out_cap, d_status);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_inflate_spans(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_span *spans, uint32_t n,
+                         const uint8_t *windows, uint64_t windows_len, uint8_t *out, uint64_t out_cap, int32_t *status)
+try {
+    if (!c || (!in && in_len) || (n && (!spans || !status)) || (!windows && windows_len) || (!out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->sp_in.ensure(in_len + ZA_SPAN_PAD)); HIPCHK(c, c->sp_win.ensure(windows_len + 1)); HIPCHK(c, c->sp_out.ensure(out_cap + 64));
+    HIPCHK(c, c->sp_tab.ensure(n + 1)); HIPCHK(c, c->sp_status.ensure(n + 1));
+    if (in_len) HIPCHK(c, hipMemcpyAsync(c->sp_in.p, in, in_len, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->sp_in.p + in_len, 0, ZA_SPAN_PAD, c->stream));
+    if (windows_len) HIPCHK(c, hipMemcpyAsync(c->sp_win.p, windows, windows_len, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(c, hipMemcpyAsync(c->sp_tab.p, spans, (size_t)n * sizeof(ZaSpan), hipMemcpyHostToDevice, c->stream));
+    // (the copies read pageable host memory: the stream is drained before the caller may touch it again, below)
+    int r = inflate_spans_dev(c, c->sp_in.p, in_len + ZA_SPAN_PAD, c->sp_tab.p, n, c->sp_win.p, windows_len, c->sp_out.p, out_cap, c->sp_status.p);
+    if (r) return r;
+    if (n) HIPCHK(c, hipMemcpyAsync(status, c->sp_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (out_cap) { const int rc_ = d2h_payload(c, out, c->sp_out.p, out_cap); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    for (uint32_t i = 0; i < n; i++) if (status[i] == ZA_SPAN_OK) c->span_stats[1] += spans[i].out_len;
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_span_stats(zngamd_ctx *c, uint64_t *out, int reset)
+try {
+    if (!c || !out) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    out[0] = c->span_stats[0]; out[1] = c->span_stats[1];
+    if (reset) c->span_stats[0] = c->span_stats[1] = 0;
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
 

@@ -76,12 +76,22 @@ SYMBOLS = [
     "zngamd_comm_allgather_stream", "zngamd_comm_offsets", "zngamd_comm_wait", "zngamd_comm_barrier", "zngamd_comm_max_f64",
     "zngamd_gunzip", "zngamd_gunzip_partial", "zngamd_gunzip_stream", "zngamd_gzip_members", "zngamd_gzip_members_dev", "zngamd_profiling",
     "zngamd_kernel_times", "zngamd_kernel_class_count", "zngamd_abi", "zngamd_decode_paths", "zngamd_deflate_index_dev", "zngamd_inflate_units_indexed_dev", "zngamd_index_create", "zngamd_index_destroy", "zngamd_deflate_index", "zngamd_deflate_blocks_packed_indexed", "zngamd_indexed_units", "zngamd_debug_fetch", "zngamd_debug_keep", "zngamd_d2d", "zngamd_dmemset", "zngamd_mem_info",
+    "zngamd_inflate_spans_dev", "zngamd_inflate_spans", "zngamd_span_stats",
 ]
 
 
 class GzState(C.Structure):                    # zngamd_gz_state
     _fields_ = [("in_member", C.c_uint32), ("start_bit", C.c_uint32), ("crc", C.c_uint32), ("window_len", C.c_uint32),
                 ("out_total", C.c_uint64), ("window", C.c_uint8 * 32768), ("index", C.c_void_p)]
+
+
+class Span(C.Structure):                       # zngamd_span
+    _fields_ = [("in_bit", C.c_uint64), ("end_bit", C.c_uint64), ("win_off", C.c_uint64), ("out_off", C.c_uint64),
+                ("win_len", C.c_uint32), ("out_len", C.c_uint32), ("crc", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SPAN_OK, SPAN_DATA, SPAN_LENGTH, SPAN_CRC = 0, 1, 2, 3
+SPAN_PAD = 64
 
 
 class Block(C.Structure):
@@ -159,6 +169,9 @@ def load():
         L.zngamd_gzip_inflate_members_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp]
         L.zngamd_gzip_inflate_plain_members_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp]
         L.zngamd_inflate_raw_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.zngamd_inflate_spans_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp]
+        L.zngamd_inflate_spans.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, u8p, C.c_uint64, u8p, C.c_uint64, vp]
+        L.zngamd_span_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         L.zngamd_compare_dev.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.zngamd_crc32_fold_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
         L.zngamd_gunzip.argtypes = [vp, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64),
@@ -819,6 +832,31 @@ class Context:
             raise EngineError(E_ARG, "segment index out of range")
         rec["e"] = d.astype(np.uint16)
         return rec
+
+    # ---- spans of a seek-point index (gzip_index.py)
+    def inflate_spans(self, data, spans, windows, out_cap):
+        """zngamd_inflate_spans: data = the packed compressed bytes (a bytes-like object), spans = a ctypes array of Span,
+        windows = the dictionaries the spans name (bytes-like).  One launch.  -> (statuses: list of int, out bytes)"""
+        n = len(spans)
+        p, keep = _addr(data)
+        wp, wkeep = _addr(windows) if len(windows) else (None, None)
+        out, op = _new_bytes(out_cap)
+        st = (C.c_int32 * max(1, n))()
+        self._chk(self.L.zngamd_inflate_spans(self.h, p, memoryview(data).nbytes, C.cast(spans, C.c_void_p) if n else None, n,
+                                              wp, len(windows), op, out_cap, st))
+        return list(st[:n]), _take(out, out_cap)
+
+    def inflate_spans_dev(self, d_in, in_len, d_spans, n, d_windows, windows_len, d_out, out_cap, d_status):
+        """zngamd_inflate_spans_dev on device pointers (ints or c_void_p); the statuses stay in d_status."""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        self._chk(self.L.zngamd_inflate_spans_dev(self.h, v(d_in), in_len, v(d_spans), n, v(d_windows), windows_len, v(d_out), out_cap,
+                                                  v(d_status)))
+
+    def span_stats(self, reset=True):
+        """(spans launched, bytes decoded OK by the host-buffer form) since the last reset"""
+        m = (C.c_uint64 * 2)()
+        self._chk(self.L.zngamd_span_stats(self.h, m, 1 if reset else 0))
+        return int(m[0]), int(m[1])
 
     # ---- measurement
     def profiling(self, on):

@@ -39,9 +39,10 @@ def _is_pathlike(obj):
     return isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__")
 
 
-def open(filename, mode="rb", compresslevel=_COMPRESS_LEVEL_TRADEOFF, encoding=None, errors=None, newline=None):
+def open(filename, mode="rb", compresslevel=_COMPRESS_LEVEL_TRADEOFF, encoding=None, errors=None, newline=None, *, index=None):
     """gzip.open look-alike (gzip_ng.py:51-95): binary modes give a GzipNGFile, text modes wrap it in a
-    TextIOWrapper."""
+    TextIOWrapper.  index (reading only): a gzip_index.GzipIndex of the file, or the path of a saved one -- seeks then jump to
+    the nearest seek point instead of decoding from the start."""
     text = "t" in mode
     if text and "b" in mode:
         raise ValueError("Invalid mode: %r" % (mode,))
@@ -61,9 +62,9 @@ def open(filename, mode="rb", compresslevel=_COMPRESS_LEVEL_TRADEOFF, encoding=N
             buffer_size=(1 << 16) - 1)
         return io.TextIOWrapper(fobj, encoding, errors, newline) if text else fobj
     if _is_pathlike(filename):
-        fobj = GzipNGFile(filename, raw_mode, compresslevel)
+        fobj = GzipNGFile(filename, raw_mode, compresslevel, index=index)
     elif hasattr(filename, "read") or hasattr(filename, "write"):
-        fobj = GzipNGFile(None, raw_mode, compresslevel, filename)
+        fobj = GzipNGFile(None, raw_mode, compresslevel, filename, index=index)
     else:
         raise TypeError("filename must be a str or bytes object, or a file")
     return io.TextIOWrapper(fobj, encoding, errors, newline) if text else fobj
@@ -193,13 +194,15 @@ class _PipelinedDeflate:
 class GzipNGFile(gzip.GzipFile):
     """gzip.GzipFile whose deflate / inflate / CRC work runs on the GPU engine (gzip_ng.py:98-176)."""
 
-    def __init__(self, filename=None, mode=None, compresslevel=_COMPRESS_LEVEL_BEST, fileobj=None, mtime=None):
+    def __init__(self, filename=None, mode=None, compresslevel=_COMPRESS_LEVEL_BEST, fileobj=None, mtime=None, *, index=None):
         super().__init__(filename, mode, compresslevel, fileobj, mtime)
+        if index is not None and self.mode != READ:
+            raise ValueError("an index is for reading")
         if self.mode == WRITE:
             self.compress = _PipelinedDeflate(compresslevel)
             self._small, self._small_n = [], 0       # writes below _SMALL_WRITE wait here for a batch
         elif self.mode == READ:
-            self._buffer = io.BufferedReader(_GzipReader(self.fileobj, READ_BUFFER_SIZE))
+            self._buffer = io.BufferedReader(_GzipReader(self.fileobj, READ_BUFFER_SIZE, index=index))
 
     def __repr__(self):
         return "<gzip_ng " + repr(self.fileobj)[1:-1] + " " + hex(id(self)) + ">"

@@ -762,7 +762,7 @@ class _GzipReader:
     output, CRC and length in a small state).  An error found after N good bytes is raised when the reader reaches byte N, as
     the streaming reference does."""
 
-    def __init__(self, fp, /, buffersize=32 * 1024):
+    def __init__(self, fp, /, buffersize=32 * 1024, index=None):
         if buffersize < 1:
             raise ValueError(f"buffersize must be at least 1, got {buffersize}")
         self._fp = fp
@@ -807,7 +807,19 @@ class _GzipReader:
                         self._index = h
             except Exception:
                 self._index = None
+        self._window_after = None
         self._reset()
+        # a seek-point index of the file (gzip_index.GzipIndex, or the path of a saved one): seeks jump to the nearest point
+        self._gzindex = None
+        if index is not None:
+            from . import gzip_index
+            if not isinstance(index, gzip_index.GzipIndex):
+                index = gzip_index.GzipIndex.load(index)
+            if not self._bulk_ok or self._start != 0:
+                raise ValueError("an index needs a seekable file read from its first byte")
+            index.check_file(fp)                 # ValueError: the index belongs to another file
+            fp.seek(self._start)
+            self._gzindex = index
 
     @property
     def _last_mtime(self):
@@ -943,6 +955,8 @@ class _GzipReader:
             self._in_eof = eof
             return view[:keep + got]
         need = keep + self._window
+        if self._window_after is not None:      # (the first window behind a jump to a seek point is that point's span)
+            self._window, self._window_after = self._window_after, None
         old = self._in_buf
         if old is None or len(old) < need:
             self._in_buf = _lib.take_buffer(need)            # (pooled, not zero-filled by us: only what the file delivers is used)
@@ -1169,6 +1183,8 @@ class _GzipReader:
                 target = offset
             elif whence == 1:
                 target = self._pos + offset
+            elif whence == 2 and self._gzindex is not None:
+                target = self._gzindex.size + offset     # (the index knows the size: nothing is decoded)
             elif whence == 2:
                 # the size is only known at the end of the stream
                 self._skip_to(1 << 62)
@@ -1179,6 +1195,15 @@ class _GzipReader:
             else:
                 raise ValueError(f"Invalid format for whence: {whence}")
             target = max(0, target)
+            if self._gzindex is not None and not (self._pos - self._boff <= target <= self._pos + len(self._buf) - self._boff):
+                if target >= self._gzindex.size:     # at or past the end: nothing to decode
+                    size = self._size
+                    self._reset()
+                    self._size, self._pos, self._done = size, self._gzindex.size, True
+                    return self._pos
+                i = self._gzindex.point_for(target)
+                if target < self._pos or self._gzindex.points[i].out_off > self._pos:
+                    self._jump(i)
             if target < self._pos:
                 # backwards: decode again from the start (what the reference's reader does as well)
                 back = self._pos - target
@@ -1195,6 +1220,48 @@ class _GzipReader:
                     self._fp.seek(self._start)
             self._skip_to(target)
             return self._pos
+
+    def _jump(self, i):
+        """Continue at seek point i of the index: the engine's stream state restored from the point, the file at the point's byte,
+        the point's span decoded (its compressed extent is the first window) and checked against the CRC-32 the index recorded
+        for it before any of it is handed out."""
+        from . import gzip_index
+        ix = self._gzindex
+        p = ix.points[i]
+        size = self._size
+        self._reset()                            # (joins a decode-ahead or read-ahead that is still using the file and the state)
+        self._size = size
+        self._first = False
+        st = self._state
+        st.index = None
+        if p.is_block:
+            w = ix.window(i)
+            st.in_member, st.start_bit, st.crc, st.out_total, st.window_len = 1, p.in_bit & 7, p.member_crc, p.member_out, len(w)
+            _C.memmove(st.window, w, len(w))
+        if p.kernel and not p.flags & gzip_index.F_FINAL:
+            end = (p.end_bit + 7) >> 3
+        else:                                    # the span ends its member: the trailer and any NUL padding go with it
+            end = ix.points[i + 1].in_bit >> 3 if i + 1 < len(ix.points) else ix.file_size
+        extent = end - (p.in_bit >> 3)
+        self._window_after, self._window = self._window, max(1, extent)
+        self._fp.seek(self._start + (p.in_bit >> 3))
+        self._pos = p.out_off
+        if not p.kernel:
+            return                               # whole members: their trailers are checked as the reader goes
+        parts, got, done, err = [], 0, False, None
+        while got < p.out_len and not done and err is None:
+            buf, pair, done, err = self._decode_window()
+            parts.append(bytes(buf))
+            got += len(buf)
+            if pair is not None:
+                _lib.give_buffer(pair[0])
+        data = b"".join(parts)
+        if len(data) < p.out_len or crc32(memoryview(data)[:p.out_len]) != p.span_crc:
+            self._done = True
+            raise err if err is not None else BadGzipFile(f"the span at byte {p.out_off} does not match its index entry")
+        self._buf, self._boff, self._done, self._error = data, 0, done or err is not None, err
+        if err is not None:
+            self._done = True
 
     def tell(self):
         self._check()
