@@ -270,6 +270,47 @@ int zngamd_inflate_spans(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, co
  * zngamd_inflate_spans decoded with ZNGAMD_SPAN_OK (the device form leaves its statuses on the device and does not count bytes) */
 int zngamd_span_stats(zngamd_ctx *ctx, uint64_t *out /*[2]*/, int reset);
 
+/* ---- the batch API (zlib_ng_amd/batch.py): many independent streams per call.  One 64-lane wavefront per item, all items of a call in
+ * one launch; a status per item.  Items lie anywhere in one input buffer (in_off, in_len); each decodes into its own output range
+ * (out_off, out_cap).  Tables given to the device forms are untrusted: an entry that points outside the buffers gets
+ * ZNGAMD_BATCH_TABLE and nothing of it is read or written. */
+typedef struct { uint64_t in_off, out_off; uint32_t in_len, out_cap; uint32_t reserved[2]; } zngamd_batch_item;     /* 32 B */
+typedef struct { int32_t status; uint32_t out_len; uint32_t in_used; uint32_t reserved; } zngamd_batch_result;   /* 16 B */
+#define ZNGAMD_BATCH_OK        0
+#define ZNGAMD_BATCH_TRUNCATED 1    /* Z_BUF_ERROR: the stream or its trailer needs bytes beyond the item ("incomplete or truncated stream") */
+#define ZNGAMD_BATCH_OUTFULL   2    /* out_cap reached: not an error, the item's size comes from a count-only pass */
+#define ZNGAMD_BATCH_NEED_DICT 3    /* Z_NEED_DICT: a zlib header with FDICT */
+#define ZNGAMD_BATCH_HEADER    4    /* "incorrect header check" */
+#define ZNGAMD_BATCH_WINDOW    5    /* "invalid window size" */
+#define ZNGAMD_BATCH_METHOD    6    /* "unknown compression method" (gzip) */
+#define ZNGAMD_BATCH_FLAGS     7    /* "unknown header flags set" (gzip) */
+#define ZNGAMD_BATCH_HCRC      8    /* "header crc mismatch" (gzip FHCRC) */
+#define ZNGAMD_BATCH_DATA      9    /* invalid deflate data */
+#define ZNGAMD_BATCH_CHECK     10   /* "incorrect data check" (Adler-32 / CRC-32) */
+#define ZNGAMD_BATCH_LENGTH    11   /* "incorrect length check" (gzip ISIZE) */
+#define ZNGAMD_BATCH_TABLE     12   /* the table entry lies outside the buffers */
+#define ZNGAMD_BATCH_PAD       64   /* readable bytes the device input must hold behind in_len */
+/* the host forms hand their output to memory the caller allocates once the size is known: alloc(user, bytes) returns it (NULL = fail) */
+typedef void *(*zngamd_alloc_fn)(void *user, uint64_t bytes);
+/* Decode: wbits takes zlib_ng.decompress's classes (zlib 0 / 8..15, raw -8..-15, gzip 16 / 24..31, auto 32 / 40..47 per item by its first
+ * two bytes).  Device form: one launch over d_items (in device memory); count_only: the same walk and checks with nothing stored,
+ * out_len = the exact output size (d_out may be NULL).  d_results[i] gets status, out_len, in_used (bytes up to the trailer's end). */
+int zngamd_inflate_batch_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n, int wbits,
+                             int count_only, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results);
+/* Host form: items (host) give in_off / in_len and a room guess out_cap (0: the engine guesses: gzip ISIZE, else a multiple of in_len);
+ * an item that outgrows its room is sized by a count pass and decoded again with exactly that room.  On return items[i].out_off /
+ * out_cap say where item i's output lies in the buffer alloc() gave, results[i] what became of it. */
+int zngamd_inflate_batch(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
+                         zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results);
+/* Encode: every item becomes the stream zngamd_deflate_stream + the one-shot's container would write for it (wbits: zlib_ng.compress's
+ * classes; strategy: ZNGAMD_STRATEGY_*).  items: HOST table (in_off, in_len read; out_off written); the framed items lie back to back
+ * in d_out, results[i].out_len bytes each.  *total = the bytes written; ZNGAMD_BUF_ERROR with *total = the size needed when out_cap is
+ * too small.  Device form: d_in holds ZNGAMD_BATCH_PAD readable bytes behind in_len; d_results in device memory. */
+int zngamd_deflate_batch_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                             int strategy, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results, uint64_t *total);
+int zngamd_deflate_batch(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                         int strategy, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results, uint64_t *total);
+
 /* One raw deflate stream that lies in device memory (d_in must be readable 64 bytes past in_len), decoded into device
  * memory: chunk-parallel where the stream offers block boundaries (sync-flush points, dynamic block headers), else on one
  * wavefront.  Returns ZNGAMD_STREAM_END when the final block ended; *out_len = bytes produced, *in_used = bytes consumed. */

@@ -8,6 +8,7 @@
 #include "za_inflate.hip"
 #include "za_inflate_units.hip"
 #include "za_inflate_spans.hip"
+#include "za_batch.hip"
 #include "za_checksum.hip"
 #include "../../include/zng_amd.h"
 
@@ -23,6 +24,8 @@
 
 static_assert(sizeof(zngamd_member) == sizeof(ZaMember), "member layout");
 static_assert(sizeof(zngamd_span) == sizeof(ZaSpan) && ZNGAMD_SPAN_PAD == ZA_SPAN_PAD && ZNGAMD_SPAN_CRC == ZA_SPAN_CRC, "span layout");
+static_assert(sizeof(zngamd_batch_item) == sizeof(ZaBatchItem) && sizeof(zngamd_batch_result) == sizeof(ZaBatchResult) &&
+              ZNGAMD_BATCH_PAD == ZA_BATCH_PAD && ZNGAMD_BATCH_TABLE == ZA_BATCH_TABLE && ZNGAMD_BATCH_OUTFULL == ZA_BATCH_OUTFULL, "batch layout");
 static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT + 32, "slot stride");
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
@@ -103,6 +106,8 @@ struct zngamd_ctx {
     uint64_t indexed_units = 0;                  // units decoded with a writer's index (zngamd_indexed_units)
     uint64_t span_stats[2] = {0, 0};             // spans and bytes of the span decoder (zngamd_span_stats)
     DevBuf<uint8_t> sp_in, sp_win, sp_out; DevBuf<ZaSpan> sp_tab; DevBuf<int32_t> sp_status;      // staging of zngamd_inflate_spans
+    DevBuf<uint8_t> bt_out, bt_out2, bt_def; DevBuf<ZaBatchItem> bt_items, bt_items2; DevBuf<ZaBatchResult> bt_res, bt_res2;    // the batch API (za_batch.hip)
+    DevBuf<uint32_t> bt_first, bt_ulen, bt_ucrc; DevBuf<uint64_t> bt_uoff, bt_total;
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
     uint8_t *h_tab = nullptr; size_t h_tab_cap = 0;
@@ -239,6 +244,8 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->ccand.release(); c->csurv.release(); c->cres.release(); c->cchunks.release(); c->out16.release(); c->ccomp.release(); c->winbuf.release(); c->uarea.release();
     c->st_off.release(); c->runs.release(); c->ck.release(); c->matchq.release(); c->cands.release(); c->members.release(); c->mstatus.release();
     c->sp_in.release(); c->sp_win.release(); c->sp_out.release(); c->sp_tab.release(); c->sp_status.release();
+    c->bt_out.release(); c->bt_out2.release(); c->bt_def.release(); c->bt_items.release(); c->bt_items2.release(); c->bt_res.release(); c->bt_res2.release();
+    c->bt_first.release(); c->bt_ulen.release(); c->bt_ucrc.release(); c->bt_uoff.release(); c->bt_total.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -1537,6 +1544,263 @@ try {
     std::lock_guard<std::mutex> g(c->mu);
     out[0] = c->span_stats[0]; out[1] = c->span_stats[1];
     if (reset) c->span_stats[0] = c->span_stats[1] = 0;
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- the batch API (za_batch.hip): many independent streams per call, one wavefront per item
+// zlib_ng.decompress's wbits classes -> container and the largest window a zlib header may name (0: any)
+static int batch_inflate_container(int wbits, int *kind, int *wmax)
+{
+    *wmax = 0;
+    if (wbits == 0 || (wbits >= 8 && wbits <= 15)) { *kind = ZA_BATCH_ZLIB; *wmax = wbits; return ZNGAMD_OK; }
+    if (wbits >= -15 && wbits <= -8) { *kind = ZA_BATCH_RAW; return ZNGAMD_OK; }
+    if (wbits == 16 || (wbits >= 24 && wbits <= 31)) { *kind = ZA_BATCH_GZIP; return ZNGAMD_OK; }
+    if (wbits == 32 || (wbits >= 40 && wbits <= 47)) { *kind = ZA_BATCH_AUTO; *wmax = wbits - 32; return ZNGAMD_OK; }
+    return ZNGAMD_STREAM_ERROR;
+}
+
+// zlib_ng.compress's wbits classes (_container) -> container and window bits
+static int batch_deflate_container(int wbits, int *kind, int *wb)
+{
+    if (wbits >= 9 && wbits <= 15) { *kind = ZA_BATCH_ZLIB; *wb = wbits; return ZNGAMD_OK; }
+    if (wbits >= -15 && wbits <= -9) { *kind = ZA_BATCH_RAW; *wb = -wbits; return ZNGAMD_OK; }
+    if (wbits >= 25 && wbits <= 31) { *kind = ZA_BATCH_GZIP; *wb = wbits - 16; return ZNGAMD_OK; }
+    if (wbits == 8) { *kind = ZA_BATCH_ZLIB; *wb = 9; return ZNGAMD_OK; }
+    if (wbits == 24) { *kind = ZA_BATCH_GZIP; *wb = 9; return ZNGAMD_OK; }
+    return ZNGAMD_STREAM_ERROR;
+}
+
+// the one-shot's header bytes (_zlib_header / _gzip_header in zlib_ng.py)
+static uint32_t batch_header(int kind, int level, int wb, ZaBatchFrameHdr *h)
+{
+    memset(h, 0, sizeof(*h));
+    const int lv = level == -1 ? 6 : level;
+    if (kind == ZA_BATCH_ZLIB) {
+        const int flevel = lv < 2 ? 0 : lv < 6 ? 1 : lv == 6 ? 2 : 3;
+        uint32_t head = ((((uint32_t)(wb - 8) << 4) | 8u) << 8) | ((uint32_t)flevel << 6);
+        head += 31u - head % 31u;
+        h->b[0] = (uint8_t)(head >> 8); h->b[1] = (uint8_t)head;
+        return 2;
+    }
+    if (kind == ZA_BATCH_GZIP) {
+        const uint8_t g[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, (uint8_t)(lv == 9 ? 2 : lv == 1 ? 4 : 0), 3};
+        memcpy(h->b, g, 10);
+        return 10;
+    }
+    return 0;
+}
+
+static uint32_t batch_trailer(int kind) { return kind == ZA_BATCH_ZLIB ? 4u : kind == ZA_BATCH_GZIP ? 8u : 0u; }
+
+static int inflate_batch_launch(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaBatchItem *d_items, uint32_t n, int kind, int wmax,
+                                bool count_only, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res)
+{
+    if (n) {
+        ProfScope ps(c, ZNGAMD_K_INFLATE);
+        if (count_only)
+            hipLaunchKernelGGL(za_k_inflate_batch<1>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res);
+        else
+            hipLaunchKernelGGL(za_k_inflate_batch<0>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res);
+    }
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_inflate_batch_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n, int wbits,
+                             int count_only, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results)
+try {
+    if (!c || (n && (!d_in || !d_items || !d_results)) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    int kind, wmax;
+    if (batch_inflate_container(wbits, &kind, &wmax)) return fail(c, ZNGAMD_STREAM_ERROR, "invalid wbits");
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = inflate_batch_launch(c, (const uint8_t *)d_in, in_len, (const ZaBatchItem *)d_items, n, kind, wmax, count_only != 0, (uint8_t *)d_out,
+                                 d_out ? out_cap : 0, (ZaBatchResult *)d_results);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// The first decode's room for an item the caller left at out_cap 0: a gzip member's ISIZE (bounded by deflate's largest ratio),
+// else a multiple of its compressed size.  An item that does not fit is sized exactly by the count pass.
+static uint32_t batch_guess(const uint8_t *in, uint64_t in_len, const zngamd_batch_item &it, int kind)
+{
+    const uint64_t hi = std::min<uint64_t>(1032ull * it.in_len + 1024, 0xFFFFFFFFull);
+    if (it.in_off > in_len || in_len - it.in_off < it.in_len) return 0;            // (the kernel reports the entry)
+    const uint8_t *p = in + it.in_off;
+    const bool gz = kind == ZA_BATCH_GZIP || (kind == ZA_BATCH_AUTO && it.in_len >= 2 && p[0] == 0x1f && p[1] == 0x8b);
+    if (gz && it.in_len >= 18) {
+        const uint32_t isize = (uint32_t)p[it.in_len - 4] | ((uint32_t)p[it.in_len - 3] << 8) | ((uint32_t)p[it.in_len - 2] << 16) | ((uint32_t)p[it.in_len - 1] << 24);
+        return (uint32_t)std::min<uint64_t>(isize, hi);
+    }
+    return (uint32_t)std::min<uint64_t>(4ull * it.in_len + 1024, hi);
+}
+
+int zngamd_inflate_batch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
+                         zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results)
+try {
+    if (!c || (!in && in_len) || (n && (!items || !results || !alloc))) return ZNGAMD_E_ARG;
+    int kind, wmax;
+    if (batch_inflate_container(wbits, &kind, &wmax)) return fail(c, ZNGAMD_STREAM_ERROR, "invalid wbits");
+    if (n == 0) return ZNGAMD_OK;
+    std::lock_guard<std::mutex> g(c->mu);
+    int r = stage_in(c, in, in_len);                    // (64 zero bytes behind the input: ZA_BATCH_PAD)
+    if (r) return r;
+    // first decode: every item with its guessed room, back to back
+    std::vector<ZaBatchItem> t1(n);
+    uint64_t r1 = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t cap = items[i].out_cap ? items[i].out_cap : batch_guess(in, in_len, items[i], kind);
+        t1[i].in_off = items[i].in_off; t1[i].in_len = items[i].in_len; t1[i].out_off = r1; t1[i].out_cap = cap;
+        t1[i].reserved[0] = t1[i].reserved[1] = 0;
+        r1 += cap;
+    }
+    HIPCHK(c, c->bt_items.ensure(n)); HIPCHK(c, c->bt_res.ensure(n)); HIPCHK(c, c->bt_out.ensure(r1 + 64));
+    HIPCHK(c, hipMemcpyAsync(c->bt_items.p, t1.data(), (size_t)n * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
+    r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items.p, n, kind, wmax, false, c->bt_out.p, r1, c->bt_res.p);
+    if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(results, c->bt_res.p, (size_t)n * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->up_busy = false;
+    for (uint32_t i = 0; i < n; i++) { items[i].out_off = t1[i].out_off; items[i].out_cap = t1[i].out_cap; }
+    // items that ran out of room: their exact size from one count pass, then one more decode with exactly that room
+    std::vector<uint32_t> full;
+    for (uint32_t i = 0; i < n; i++) if (results[i].status == ZA_BATCH_OUTFULL) full.push_back(i);
+    uint64_t r2 = 0;
+    if (!full.empty()) {
+        const uint32_t m = (uint32_t)full.size();
+        std::vector<ZaBatchItem> t2(m);
+        std::vector<ZaBatchResult> res2(m);
+        for (uint32_t k = 0; k < m; k++) { t2[k] = t1[full[k]]; t2[k].out_off = 0; t2[k].out_cap = 0; }
+        HIPCHK(c, c->bt_items2.ensure(m)); HIPCHK(c, c->bt_res2.ensure(m));
+        HIPCHK(c, hipMemcpyAsync(c->bt_items2.p, t2.data(), (size_t)m * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
+        r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items2.p, m, kind, wmax, true, nullptr, 0, c->bt_res2.p);
+        if (r) return r;
+        HIPCHK(c, hipMemcpyAsync(res2.data(), c->bt_res2.p, (size_t)m * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t k = 0; k < m; k++) {
+            t2[k].out_off = r2; t2[k].out_cap = res2[k].status == ZA_BATCH_OK ? res2[k].out_len : 0;
+            r2 += t2[k].out_cap;
+        }
+        HIPCHK(c, c->bt_out2.ensure(r2 + 64));
+        HIPCHK(c, hipMemcpyAsync(c->bt_items2.p, t2.data(), (size_t)m * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
+        r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items2.p, m, kind, wmax, false, c->bt_out2.p, r2, c->bt_res2.p);
+        if (r) return r;
+        std::vector<ZaBatchResult> res3(m);
+        HIPCHK(c, hipMemcpyAsync(res3.data(), c->bt_res2.p, (size_t)m * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint32_t k = 0; k < m; k++) {
+            const uint32_t i = full[k];
+            results[i] = res2[k].status == ZA_BATCH_OK ? *(const zngamd_batch_result *)&res3[k] : *(const zngamd_batch_result *)&res2[k];
+            items[i].out_off = r1 + t2[k].out_off; items[i].out_cap = t2[k].out_cap;
+        }
+    }
+    uint8_t *dst = (uint8_t *)alloc(user, r1 + r2);
+    if (!dst && r1 + r2) return fail(c, ZNGAMD_MEM_ERROR, "cannot allocate the output");
+    if (r1) { const int rc_ = d2h_payload(c, dst, c->bt_out.p, r1); if (rc_) return rc_; }
+    if (r2) { const int rc_ = d2h_payload(c, dst + r1, c->bt_out2.p, r2); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// one deflate block per item (FINAL; units of 16 KiB up to 128 KiB, as zngamd_deflate_stream cuts a one-shot call), the packed stream
+// into bt_def, then the framing kernel into d_out.  items: host table (in_off, in_len read; out_off written).
+static int deflate_batch_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                                int strategy, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res, uint64_t *total)
+{
+    *total = 0;
+    int kind, wb;
+    if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (batch_deflate_container(wbits, &kind, &wb)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (strategy < ZNGAMD_STRATEGY_DEFAULT || strategy > ZNGAMD_STRATEGY_FIXED) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression strategy");
+    if (n == 0) return ZNGAMD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<zngamd_block> blocks(n);
+    for (uint32_t i = 0; i < n; i++) {
+        zngamd_block &B = blocks[i];
+        B.off = items[i].in_off; B.len = items[i].in_len; B.dict_len = 0; B.reserved = 0;
+        B.flags = ZNGAMD_FLAG_FINAL | ZNGAMD_FLAG_STRATEGY(strategy) | (B.len <= ZA_MAX_UNIT ? ZNGAMD_FLAG_UNITS16K : 0u);
+    }
+    std::vector<ZaUnit> hu;
+    int r = build_units(c, blocks.data(), n, in_len, hu);
+    if (r) return r;
+    const uint32_t nu = (uint32_t)hu.size();
+    std::vector<uint32_t> first(n + 1, nu);
+    for (uint32_t u = nu; u-- > 0;) first[hu[u].block] = u;
+    uint64_t bound = 64;
+    for (const ZaUnit &u : hu) bound += (uint64_t)u.in_len + 32u;
+    HIPCHK(c, c->bt_def.ensure(bound)); HIPCHK(c, c->bt_uoff.ensure(nu)); HIPCHK(c, c->bt_ulen.ensure(nu)); HIPCHK(c, c->bt_ucrc.ensure(nu));
+    HIPCHK(c, c->bt_total.ensure(1)); HIPCHK(c, c->bt_first.ensure(n + 1)); HIPCHK(c, c->bt_items.ensure(n));
+    HIPCHK(c, hipMemcpyAsync(c->bt_first.p, first.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->bt_items.p, items, (size_t)n * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
+    PackedDst pd; pd.d_dst = c->bt_def.p; pd.cap = bound; pd.d_unit_off = c->bt_uoff.p; pd.d_total = c->bt_total.p;
+    r = deflate_units_dev(c, d_in, in_len, hu, level, nullptr, c->bt_ulen.p, c->bt_ucrc.p, 1 << wb, &pd, strategy);
+    if (r) return r;
+    uint64_t def_total = 0;
+    std::vector<uint32_t> st(nu);
+    HIPCHK(c, hipMemcpyAsync(&def_total, c->bt_total.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, (size_t)nu * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->up_busy = false;
+    for (uint32_t v : st) if (v) return fail(c, ZNGAMD_E_HIP, "packed deflate: a unit's size differs from its plan");
+    if (def_total > bound) return fail(c, ZNGAMD_E_HIP, "packed deflate: stream larger than its bound");
+    ZaBatchFrameHdr head;
+    const uint32_t hl = batch_header(kind, level, wb, &head);
+    *total = def_total + (uint64_t)n * (hl + batch_trailer(kind));
+    if (*total > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    {
+        ProfScope ps(c, ZNGAMD_K_GATHER);
+        hipLaunchKernelGGL(za_k_batch_frame, dim3(n), dim3(64), 0, c->stream, d_in, c->bt_items.p, n, c->bt_first.p, nu, c->bt_uoff.p, c->bt_ucrc.p,
+                           c->bt_total.p, c->bt_def.p, kind, head, hl, d_out, out_cap, d_res);
+    }
+    HIPCHK(c, hipGetLastError());
+    std::vector<ZaBatchItem> back(n);
+    HIPCHK(c, hipMemcpyAsync(back.data(), c->bt_items.p, (size_t)n * sizeof(ZaBatchItem), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n; i++) items[i].out_off = back[i].out_off;
+    return ZNGAMD_OK;
+}
+
+int zngamd_deflate_batch_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                             int strategy, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results, uint64_t *total)
+try {
+    if (!c || !total || (n && (!d_in || !items || !d_out || !d_results))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    const int r = deflate_batch_locked(c, (const uint8_t *)d_in, in_len, items, n, level, wbits, strategy, (uint8_t *)d_out, out_cap,
+                                       (ZaBatchResult *)d_results, total);
+    if (r) return r;
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_deflate_batch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                         int strategy, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results, uint64_t *total)
+try {
+    if (!c || (!in && in_len) || !total || (n && (!items || !results || !alloc))) return ZNGAMD_E_ARG;
+    *total = 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    int kind, wb;
+    if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (batch_deflate_container(wbits, &kind, &wb)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (n == 0) return ZNGAMD_OK;
+    int r = stage_in(c, in, in_len);
+    if (r) return r;
+    uint64_t cap = 64 + (uint64_t)n * 18;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t U = items[i].in_len <= ZA_MAX_UNIT ? ZA_SMALL_UNIT : ZA_MAX_UNIT;
+        cap += items[i].in_len + 32 * std::max<uint64_t>(1, (items[i].in_len + U - 1) / U);
+    }
+    HIPCHK(c, c->bt_out.ensure(cap)); HIPCHK(c, c->bt_res.ensure(n));
+    r = deflate_batch_locked(c, c->st_in.p, in_len, items, n, level, wbits, strategy, c->bt_out.p, cap, c->bt_res.p, total);
+    if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(results, c->bt_res.p, (size_t)n * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
+    uint8_t *dst = (uint8_t *)alloc(user, *total);
+    if (!dst && *total) { (void)hipStreamSynchronize(c->stream); return fail(c, ZNGAMD_MEM_ERROR, "cannot allocate the output"); }
+    if (*total) { const int rc_ = d2h_payload(c, dst, c->bt_out.p, *total); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
 

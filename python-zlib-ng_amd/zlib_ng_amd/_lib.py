@@ -77,6 +77,7 @@ SYMBOLS = [
     "zngamd_gunzip", "zngamd_gunzip_partial", "zngamd_gunzip_stream", "zngamd_gzip_members", "zngamd_gzip_members_dev", "zngamd_profiling",
     "zngamd_kernel_times", "zngamd_kernel_class_count", "zngamd_abi", "zngamd_decode_paths", "zngamd_deflate_index_dev", "zngamd_inflate_units_indexed_dev", "zngamd_index_create", "zngamd_index_destroy", "zngamd_deflate_index", "zngamd_deflate_blocks_packed_indexed", "zngamd_indexed_units", "zngamd_debug_fetch", "zngamd_debug_keep", "zngamd_d2d", "zngamd_dmemset", "zngamd_mem_info",
     "zngamd_inflate_spans_dev", "zngamd_inflate_spans", "zngamd_span_stats",
+    "zngamd_inflate_batch_dev", "zngamd_inflate_batch", "zngamd_deflate_batch_dev", "zngamd_deflate_batch",
 ]
 
 
@@ -92,6 +93,22 @@ class Span(C.Structure):                       # zngamd_span
 
 SPAN_OK, SPAN_DATA, SPAN_LENGTH, SPAN_CRC = 0, 1, 2, 3
 SPAN_PAD = 64
+
+
+class BatchItem(C.Structure):                  # zngamd_batch_item
+    _fields_ = [("in_off", C.c_uint64), ("out_off", C.c_uint64), ("in_len", C.c_uint32), ("out_cap", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class BatchResult(C.Structure):                # zngamd_batch_result
+    _fields_ = [("status", C.c_int32), ("out_len", C.c_uint32), ("in_used", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# ZNGAMD_BATCH_*: the verdict per item of the batch API
+(BATCH_OK, BATCH_TRUNCATED, BATCH_OUTFULL, BATCH_NEED_DICT, BATCH_HEADER, BATCH_WINDOW, BATCH_METHOD, BATCH_FLAGS, BATCH_HCRC,
+ BATCH_DATA, BATCH_CHECK, BATCH_LENGTH, BATCH_TABLE) = range(13)
+BATCH_PAD = 64
+ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_uint64)      # zngamd_alloc_fn
 
 
 class Block(C.Structure):
@@ -172,6 +189,12 @@ def load():
         L.zngamd_inflate_spans_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp]
         L.zngamd_inflate_spans.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, u8p, C.c_uint64, u8p, C.c_uint64, vp]
         L.zngamd_span_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        L.zngamd_inflate_batch_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint64, vp]
+        L.zngamd_inflate_batch.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, ALLOC_FN, vp, vp]
+        L.zngamd_deflate_batch_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, vp,
+                                               C.POINTER(C.c_uint64)]
+        L.zngamd_deflate_batch.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, ALLOC_FN, vp, vp,
+                                           C.POINTER(C.c_uint64)]
         L.zngamd_compare_dev.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.zngamd_crc32_fold_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
         L.zngamd_gunzip.argtypes = [vp, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64),
@@ -857,6 +880,56 @@ class Context:
         m = (C.c_uint64 * 2)()
         self._chk(self.L.zngamd_span_stats(self.h, m, 1 if reset else 0))
         return int(m[0]), int(m[1])
+
+    # ---- the batch API (batch.py)
+    def inflate_batch(self, data, items, n, wbits):
+        """zngamd_inflate_batch: data = the items back to back (bytes-like), items = a ctypes array of BatchItem (out_off / out_cap are
+        written).  -> (output bytes object, ctypes array of BatchResult)"""
+        p, keep = _addr(data)
+        res = (BatchResult * max(n, 1))()
+        box = []
+
+        def alloc(_user, nbytes):
+            obj, addr = _new_bytes(nbytes)
+            box.append(obj)
+            return addr.value
+
+        fn = ALLOC_FN(alloc)
+        self._chk(self.L.zngamd_inflate_batch(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, wbits, fn, None,
+                                              C.cast(res, C.c_void_p)))
+        return (box[0] if box else b""), res
+
+    def deflate_batch(self, data, items, n, level, wbits, strategy=STRATEGY_DEFAULT):
+        """zngamd_deflate_batch -> (output bytes object, ctypes array of BatchResult, total); items[i].out_off is written"""
+        p, keep = _addr(data)
+        res = (BatchResult * max(n, 1))()
+        box = []
+
+        def alloc(_user, nbytes):
+            obj, addr = _new_bytes(nbytes)
+            box.append(obj)
+            return addr.value
+
+        fn = ALLOC_FN(alloc)
+        total = C.c_uint64(0)
+        self._chk(self.L.zngamd_deflate_batch(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, level, wbits, strategy,
+                                              fn, None, C.cast(res, C.c_void_p), C.byref(total)))
+        return (box[0] if box else b""), res, total.value
+
+    def inflate_batch_dev(self, d_in, in_len, d_items, n, wbits, count_only, d_out, out_cap, d_results):
+        """zngamd_inflate_batch_dev on device pointers (ints or c_void_p); the results stay in d_results."""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        self._chk(self.L.zngamd_inflate_batch_dev(self.h, v(d_in), in_len, v(d_items), n, wbits, 1 if count_only else 0, v(d_out), out_cap,
+                                                  v(d_results)))
+
+    def deflate_batch_dev(self, d_in, in_len, items, n, level, wbits, strategy, d_out, out_cap, d_results):
+        """zngamd_deflate_batch_dev: items = a HOST ctypes array of BatchItem (out_off written) -> (code, total); code OK or BUF_ERROR
+        (total = the size needed)"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        total = C.c_uint64(0)
+        r = self._chk(self.L.zngamd_deflate_batch_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy, v(d_out),
+                                                      out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
+        return r, total.value
 
     # ---- measurement
     def profiling(self, on):

@@ -1,0 +1,253 @@
+"""Batch API: compress and decompress many independent buffers in one call.
+
+    batch.compress(items, level=-1, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY) -> list[bytes]
+    batch.decompress(items, wbits=MAX_WBITS, *, errors="raise") -> list[bytes]
+    batch.compress_dev(ctx, d_in, offsets, lengths, ...) -> (DeviceBuffer, out_offsets, out_lengths)
+    batch.decompress_dev(ctx, d_in, offsets, lengths, ...) -> (DeviceBuffer, out_offsets, out_lengths, statuses)
+
+`compress(items, level, wbits)[i] == zlib_ng.compress(items[i], level, wbits)` byte for byte, and `decompress(items, wbits)[i] ==
+zlib_ng.decompress(items[i], wbits)`; where the one-shot raises, the batch raises the same type with the same message for the first
+failing item in index order (its index in the exception's `index` attribute), or with errors="return" puts the exception in that
+item's slot.  One wavefront per item, all items of a call in one launch set (za_batch.hip).
+"""
+
+import numpy as np
+
+from . import _lib
+from . import zlib_ng as _z
+
+MAX_WBITS = _z.MAX_WBITS
+Z_DEFAULT_COMPRESSION = _z.Z_DEFAULT_COMPRESSION
+Z_DEFAULT_STRATEGY = _z.Z_DEFAULT_STRATEGY
+
+# A compressed item of at least this many bytes is decoded by the single-stream path (zlib_ng.decompress: chunk-parallel where the
+# stream allows it) instead of on one wavefront: one wave decodes about 58 MB/s, so an item of 256 KiB (about 1 MB of text) keeps its
+# wave busy ~15 ms, longer than a whole batch of 10 000 small items takes, while the single-stream path needs a few ms for it
+# (DESIGN.md section 5c).
+LARGE_ITEM = 256 << 10
+# Bytes of input per engine call: a larger batch runs as consecutive sub-batches of about this size, so that the staging buffers
+# (input, first-guess output room) stay bounded.  The results are the same.
+SUB_BATCH_BYTES = 256 << 20
+
+W = "while decompressing data"
+# the one-shot's exception for each item status (zlib_ng.decompress)
+_MESSAGES = {
+    _lib.BATCH_TRUNCATED: (_lib.BUF_ERROR, None),
+    _lib.BATCH_NEED_DICT: (_lib.NEED_DICT, None),
+    _lib.BATCH_HEADER: (_lib.DATA_ERROR, "incorrect header check"),
+    _lib.BATCH_WINDOW: (_lib.DATA_ERROR, "invalid window size"),
+    _lib.BATCH_METHOD: (_lib.DATA_ERROR, "unknown compression method"),
+    _lib.BATCH_FLAGS: (_lib.DATA_ERROR, "unknown header flags set"),
+    _lib.BATCH_HCRC: (_lib.DATA_ERROR, "header crc mismatch"),
+    _lib.BATCH_DATA: (_lib.DATA_ERROR, None),
+    _lib.BATCH_CHECK: (_lib.DATA_ERROR, "incorrect data check"),
+    _lib.BATCH_LENGTH: (_lib.DATA_ERROR, "incorrect length check"),
+}
+
+
+def status_error(status):
+    """The exception zlib_ng.decompress raises for an item with this ZNGAMD_BATCH_* status (None for BATCH_OK)."""
+    if status == _lib.BATCH_OK:
+        return None
+    if status in _MESSAGES:
+        code, detail = _MESSAGES[status]
+        return _z._zerr(code, W, detail)
+    if status == _lib.BATCH_TABLE:
+        return ValueError("batch item lies outside the buffers")
+    return _lib.EngineError(status, "unexpected batch status")
+
+
+def _check_errors(errors):
+    if errors not in ("raise", "return"):
+        raise ValueError(f"errors must be 'raise' or 'return', not {errors!r}")
+
+
+def _inflate_kind(wbits):
+    if not isinstance(wbits, int):
+        raise TypeError(f"an integer is required (got type {type(wbits).__name__})")
+    if not (wbits == 0 or 8 <= wbits <= 15 or -15 <= wbits <= -8 or 24 <= wbits <= 31 or wbits == 16 or 40 <= wbits <= 47 or wbits == 32):
+        raise _z._zerr(_lib.STREAM_ERROR, "while preparing to decompress data")
+
+
+def _check_strategy(strategy):
+    if not isinstance(strategy, int):
+        raise TypeError(f"an integer is required (got type {type(strategy).__name__})")
+    if not _lib.STRATEGY_DEFAULT <= strategy <= _lib.STRATEGY_FIXED:
+        raise ValueError("Invalid initialization option")
+
+
+def _views(items):
+    return [_z._view(x) for x in items]
+
+
+def _sub_batches(sizes, budget):
+    """[a, b) index ranges whose sizes add up to at most `budget` (an item larger than that goes alone)"""
+    out, a, acc = [], 0, 0
+    for i, s in enumerate(sizes):
+        if i > a and acc + s > budget:
+            out.append((a, i))
+            a, acc = i, 0
+        acc += s
+    if a < len(sizes):
+        out.append((a, len(sizes)))
+    return out
+
+
+def _table(lengths):
+    """-> (numpy view of the item table: rows of in_off, out_off, in_len | out_cap << 32, reserved; the ctypes array over it)"""
+    n = len(lengths)
+    ln = np.asarray(lengths, dtype=np.uint64)
+    if n and int(ln.max()) > 0xFFFFFFFF:
+        raise OverflowError("a batch item is limited to 4 GiB - 1")
+    tab = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    if n:
+        tab[1:n, 0] = np.cumsum(ln)[:-1]
+        tab[:n, 2] = ln
+    return tab, (_lib.BatchItem * max(n, 1)).from_buffer(tab)
+
+
+def _results(rs, n):
+    r = np.frombuffer(rs, dtype=np.uint32, count=4 * max(n, 1)).reshape(-1, 4)[:n]
+    return r[:, 0].view(np.int32).tolist(), r[:, 1].tolist()
+
+
+def compress(items, level=Z_DEFAULT_COMPRESSION, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY):
+    """Compress every item of `items` (buffer-protocol objects) on its own: the i-th result equals zlib_ng.compress(items[i], level,
+    wbits).  With a strategy, each result is the stream compressobj(level, DEFLATED, wbits, strategy=...) would write."""
+    views = _views(items)
+    _z._check_level(level)
+    _z._container(wbits)
+    _check_strategy(strategy)
+    if not views:
+        return []
+    ctx = _z._ctx()
+    sizes = [v.nbytes for v in views]
+    res = [None] * len(views)
+    for a, b in _sub_batches(sizes, SUB_BATCH_BYTES):
+        data = b"".join(views[a:b])
+        tab, items_c = _table(sizes[a:b])
+        out, rs, total = ctx.deflate_batch(data, items_c, b - a, level, wbits, strategy)
+        mv = memoryview(out)
+        _, lens = _results(rs, b - a)
+        for k, (o, ln) in enumerate(zip(tab[:b - a, 1].tolist(), lens)):
+            res[a + k] = bytes(mv[o:o + ln])
+    return res
+
+
+def _raise_first(res, errors):
+    if errors == "raise":
+        for r in res:
+            if isinstance(r, BaseException):
+                raise r
+    return res
+
+
+def _with_index(exc, i):
+    exc.index = i
+    return exc
+
+
+def decompress(items, wbits=MAX_WBITS, *, errors="raise"):
+    """Decompress every item of `items` on its own: the i-th result equals zlib_ng.decompress(items[i], wbits).  errors="raise" raises
+    the one-shot's exception for the first failing item (its index in the exception's `index` attribute); errors="return" puts the
+    exception in the failing items' slots instead."""
+    _check_errors(errors)
+    views = _views(items)
+    _inflate_kind(wbits)
+    if not views:
+        return []
+    ctx = _z._ctx()
+    res = [None] * len(views)
+    small = [i for i, v in enumerate(views) if v.nbytes < LARGE_ITEM]
+    sizes = [views[i].nbytes for i in small]
+    for a, b in _sub_batches(sizes, SUB_BATCH_BYTES):
+        idx = small[a:b]
+        data = b"".join(views[i] for i in idx)
+        tab, items_c = _table(sizes[a:b])
+        out, rs = ctx.inflate_batch(data, items_c, b - a, wbits)
+        mv = memoryview(out)
+        sts, lens = _results(rs, b - a)
+        for i, o, st, ln in zip(idx, tab[:b - a, 1].tolist(), sts, lens):
+            res[i] = bytes(mv[o:o + ln]) if st == _lib.BATCH_OK else _with_index(status_error(st), i)
+    for i, v in enumerate(views):
+        if v.nbytes >= LARGE_ITEM:
+            try:
+                res[i] = _z.decompress(v, wbits)
+            except Exception as e:          # the single-stream path's own verdict, as the one-shot gives it
+                res[i] = _with_index(e, i)
+    return _raise_first(res, errors)
+
+
+# ---- device-resident forms
+def _frame_bound(lengths, wbits):
+    kind, _ = _z._container(wbits)
+    ovh = 6 if kind == "zlib" else 18 if kind == "gzip" else 0
+    total = 64
+    for ln in lengths:
+        u = 16384 if ln <= 131072 else 131072
+        total += ln + 32 * max(1, -(-ln // u)) + ovh
+    return total
+
+
+def compress_dev(ctx, d_in, offsets, lengths, level=Z_DEFAULT_COMPRESSION, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY):
+    """Items that lie in device memory (d_in: a DeviceBuffer holding BATCH_PAD readable bytes behind the last item) compressed into
+    one new DeviceBuffer.  -> (buffer, out_offsets, out_lengths) (numpy uint64 arrays)."""
+    from . import devmem
+    _z._check_level(level)
+    _z._container(wbits)
+    _check_strategy(strategy)
+    offsets = np.asarray(offsets, dtype=np.uint64)
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    n = len(offsets)
+    if len(lengths) != n:
+        raise ValueError("offsets and lengths differ in length")
+    in_len = max(0, d_in.nbytes - _lib.BATCH_PAD)
+    items = (_lib.BatchItem * max(n, 1))()
+    for i in range(n):
+        items[i].in_off = int(offsets[i])
+        items[i].in_len = int(lengths[i])
+    cap = _frame_bound([int(x) for x in lengths], wbits)
+    out = devmem.DeviceBuffer(ctx, cap)
+    d_res = devmem.DeviceBuffer(ctx, 16 * max(n, 1))
+    r, total = ctx.deflate_batch_dev(d_in.ptr, in_len, items, n, level, wbits, strategy, out.ptr, cap, d_res.ptr)
+    if r != _lib.OK:
+        raise _lib.EngineError(r, ctx.err())
+    res = d_res.cpu().view(np.uint32).reshape(-1, 4)[:n]
+    offs = np.array([items[i].out_off for i in range(n)], dtype=np.uint64)
+    return out, offs, res[:, 1].astype(np.uint64)
+
+
+def decompress_dev(ctx, d_in, offsets, lengths, wbits=MAX_WBITS):
+    """Items that lie in device memory (d_in: a DeviceBuffer holding BATCH_PAD readable bytes behind the last item) decompressed into
+    one new DeviceBuffer: a count pass sizes every item, one decode writes it.  -> (buffer, out_offsets, out_lengths, statuses)
+    (numpy arrays; statuses are ZNGAMD_BATCH_* codes, see status_error)."""
+    from . import devmem
+    _inflate_kind(wbits)
+    offsets = np.asarray(offsets, dtype=np.uint64)
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    n = len(offsets)
+    if len(lengths) != n:
+        raise ValueError("offsets and lengths differ in length")
+    in_len = max(0, d_in.nbytes - _lib.BATCH_PAD)
+    tab = np.zeros((max(n, 1), 4), dtype=np.uint64)            # in_off, out_off, (in_len | out_cap << 32), reserved
+    tab[:n, 0] = offsets
+    tab[:n, 2] = lengths & 0xFFFFFFFF
+    d_tab = devmem.from_host(ctx, tab.view(np.uint8).reshape(-1))
+    d_res = devmem.DeviceBuffer(ctx, 16 * max(n, 1))
+    ctx.inflate_batch_dev(d_in.ptr, in_len, d_tab.ptr, n, wbits, True, None, 0, d_res.ptr)
+    res = d_res.cpu().view(np.uint32).reshape(-1, 4)[:n]
+    ok = res[:, 0] == _lib.BATCH_OK
+    sizes = np.where(ok, res[:, 1], 0).astype(np.uint64)
+    offs = np.zeros(n, dtype=np.uint64)
+    if n:
+        offs[1:] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    tab[:n, 1] = offs
+    tab[:n, 2] = (lengths & 0xFFFFFFFF) | (sizes << np.uint64(32))
+    d_tab[:] = tab.view(np.uint8).reshape(-1)
+    out = devmem.DeviceBuffer(ctx, total + 64)
+    ctx.inflate_batch_dev(d_in.ptr, in_len, d_tab.ptr, n, wbits, False, out.ptr, total, d_res.ptr)
+    res2 = d_res.cpu().view(np.uint32).reshape(-1, 4)[:n]
+    statuses = np.where(ok, res2[:, 0], res[:, 0]).astype(np.int32)
+    lens = np.where(statuses == _lib.BATCH_OK, res2[:, 1], 0).astype(np.uint64)
+    return out, offs, lens, statuses
