@@ -310,6 +310,27 @@ int zngamd_deflate_batch_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len,
                              int strategy, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results, uint64_t *total);
 int zngamd_deflate_batch(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
                          int strategy, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results, uint64_t *total);
+/* The batch API with one preset dictionary shared by every item of the call (zdict).  dict: HOST memory, dict_len bytes; the library
+ * works out its Adler-32 once and keeps its last 32 KiB, as zngamd_stream_*_set_dictionary do.
+ * Decode: a zlib item with FDICT decodes with the dictionary when its DICTID is the dictionary's Adler-32 (else ZNGAMD_ZDICT_MISMATCH;
+ * an item that ends inside its DICTID is ZNGAMD_BATCH_TRUNCATED), a raw item has it as history from its first byte, a gzip item or a
+ * zlib item without FDICT ignores it.  dict_len == 0: the call is zngamd_inflate_batch[_dev] (FDICT items get ZNGAMD_BATCH_NEED_DICT).
+ * Encode: every item becomes the stream zngamd_stream_deflate_* writes for it after zngamd_stream_deflate_set_dictionary (one block,
+ * FDICT + DICTID in a zlib header, the Adler-32 of the item's own bytes); dict == NULL: the call is zngamd_deflate_batch[_dev];
+ * dict_len == 0 with a non-NULL dict is an empty dictionary (FDICT is written).  A gzip wbits is ZNGAMD_STREAM_ERROR ("Invalid
+ * dictionary").  Every item is primed with the tail in a staging buffer: the device form runs its items in ranges of at most
+ * 256 MiB of (tail + item) each, whatever n is. */
+#define ZNGAMD_ZDICT_MISMATCH  13   /* a zlib item's DICTID is not the Adler-32 of the dictionary ("Error -3 while setting zdict") */
+int zngamd_inflate_batch_dict_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n, int wbits,
+                                  const uint8_t *dict, uint32_t dict_len, int count_only, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results);
+int zngamd_inflate_batch_dict(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
+                              const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results);
+int zngamd_deflate_batch_dict_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                                  int strategy, const uint8_t *dict, uint32_t dict_len, void *d_out, uint64_t out_cap,
+                                  zngamd_batch_result *d_results, uint64_t *total);
+int zngamd_deflate_batch_dict(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                              int strategy, const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user,
+                              zngamd_batch_result *results, uint64_t *total);
 
 /* One raw deflate stream that lies in device memory (d_in must be readable 64 bytes past in_len), decoded into device
  * memory: chunk-parallel where the stream offers block boundaries (sync-flush points, dynamic block headers), else on one

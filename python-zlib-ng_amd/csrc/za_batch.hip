@@ -4,6 +4,11 @@
 //                              za_inflate_serial_core (the decoder of za_k_inflate_serial_members, same LDS layout and occupancy)
 //                              and checks its trailer on the wave.  COUNT = 1: the same walk and checks, nothing stored; the
 //                              result's out_len is the exact output size (items whose first decode ran out of room).
+//   za_k_inflate_batch_dict<COUNT>  the same with one shared preset dictionary (zdict): a zlib item with FDICT whose DICTID is the
+//                              dictionary's Adler-32 and every raw item decode with its tail as history; a wrong DICTID is
+//                              ZA_ZDICT_MISMATCH.  Same body (za_inflate_batch_item<COUNT, true>), same LDS, occupancy and scratch.
+//   za_k_batch_prime           compress side with a dictionary: [dictionary tail][item] for every item into a staging buffer, so
+//                              that the deflate pipeline runs one block per item with the tail as its dict_len.
 //   za_k_batch_frame           compress side, after za_k_pack: header, the item's deflate bytes, Adler-32 (worked out from the
 //                              item's input) or CRC-32 (folded from its units' CRCs) and ISIZE, at the item's place in one output.
 // The item table is untrusted (device callers pass device tables): every offset and length is checked before a byte is read or
@@ -33,6 +38,7 @@ struct ZaBatchResult {               // zngamd_batch_result
 #define ZA_BATCH_CHECK     10        // incorrect data check (Adler-32 / CRC-32)
 #define ZA_BATCH_LENGTH    11        // incorrect length check (ISIZE)
 #define ZA_BATCH_TABLE     12        // the table entry lies outside the buffers
+#define ZA_ZDICT_MISMATCH  13        // a zlib item's DICTID is not the Adler-32 of the call's dictionary
 #define ZA_BATCH_PAD       64        // readable bytes the input buffer must hold behind in_len
 
 // containers (the host maps the call's wbits onto these)
@@ -98,14 +104,16 @@ __device__ __forceinline__ uint64_t za_wave_find_nul(const uint8_t *p, uint64_t 
     return n;
 }
 
-template <int COUNT>
-__global__ __launch_bounds__(64) void za_k_inflate_batch(const uint8_t *__restrict__ in, uint64_t in_len,
-                                                         const ZaBatchItem *__restrict__ items,
-                                                         uint8_t *__restrict__ out, uint64_t out_cap,
-                                                         const uint32_t *__restrict__ crc_table,
-                                                         const uint32_t *__restrict__ x8k_table,
-                                                         int kind0, int wmax,
-                                                         ZaBatchResult *__restrict__ results)
+// One item of za_k_inflate_batch[_dict].  DICT: dict / dict_len = the dictionary's kept tail (device), dictid = its Adler-32.
+template <int COUNT, bool DICT>
+__device__ __forceinline__ void za_inflate_batch_item(const uint8_t *__restrict__ in, uint64_t in_len,
+                                                      const ZaBatchItem *__restrict__ items,
+                                                      uint8_t *__restrict__ out, uint64_t out_cap,
+                                                      const uint32_t *__restrict__ crc_table,
+                                                      const uint32_t *__restrict__ x8k_table,
+                                                      int kind0, int wmax,
+                                                      ZaBatchResult *__restrict__ results,
+                                                      const uint8_t *__restrict__ dict, uint32_t dict_len, uint32_t dictid)
 {
     __shared__ ZaInfTabsT<ZA_MEMBER_LBITS, ZA_MEMBER_DBITS> T;
     __shared__ uint8_t win[ZA_MEMBER_RING];
@@ -126,6 +134,7 @@ __global__ __launch_bounds__(64) void za_k_inflate_batch(const uint8_t *__restri
     // ---- the container's header (the order of checks is zlib_ng.decompress's)
     int st = ZA_BATCH_OK;
     uint64_t hdr = 0;
+    bool use_dict = DICT && kind == ZA_BATCH_RAW;     // a raw item has the dictionary as history from its first byte, a gzip item never
     if (kind == ZA_BATCH_ZLIB) {
         if (n < 2) st = ZA_BATCH_TRUNCATED;
         else {
@@ -133,8 +142,15 @@ __global__ __launch_bounds__(64) void za_k_inflate_batch(const uint8_t *__restri
             const uint32_t win_bits = (cmf >> 4) + 8;
             if ((cmf & 15u) != 8u || ((cmf << 8) | flg) % 31u) st = ZA_BATCH_HEADER;
             else if (win_bits > 15 || (wmax != 0 && win_bits > (uint32_t)wmax)) st = ZA_BATCH_WINDOW;
-            else if (flg & 0x20u) st = ZA_BATCH_NEED_DICT;
+            else if (flg & 0x20u) {
+                if constexpr (DICT) {
+                    if (n < 6) st = ZA_BATCH_TRUNCATED;              // the item ends inside its DICTID
+                    else if (((uint32_t)src[2] << 24 | (uint32_t)src[3] << 16 | (uint32_t)src[4] << 8 | src[5]) != dictid) st = ZA_ZDICT_MISMATCH;
+                    else use_dict = true;
+                } else st = ZA_BATCH_NEED_DICT;
+            }
             hdr = 2;
+            if constexpr (DICT) if (use_dict) hdr = 6;
         }
     } else if (kind == ZA_BATCH_GZIP) {
         if (n < 10) st = ZA_BATCH_TRUNCATED;
@@ -180,11 +196,14 @@ __global__ __launch_bounds__(64) void za_k_inflate_batch(const uint8_t *__restri
     // ---- the deflate data: only the item's own bytes (a stream that needs more is truncated, whatever follows in the buffer)
     uint64_t bits = 0, op = 0;
     int status;
+    const uint8_t *hd = nullptr;
+    uint32_t hl = 0;
+    if constexpr (DICT) if (use_dict) { hd = dict; hl = dict_len; }
     if (COUNT)
-        status = za_inflate_serial_core<1, uint8_t, ZA_MEMBER_RING, ZaParBufT<ZA_MEMBER_BITS, ZA_MEMBER_Q>>(src + hdr, n - hdr, nullptr, 0, nullptr, 0xFFFFFFFFull, T, nullptr, scratch, P.stage,
+        status = za_inflate_serial_core<1, uint8_t, ZA_MEMBER_RING, ZaParBufT<ZA_MEMBER_BITS, ZA_MEMBER_Q>>(src + hdr, n - hdr, hd, hl, nullptr, 0xFFFFFFFFull, T, nullptr, scratch, P.stage,
                                                                        bits, op, 0, nullptr, nullptr, 0xFFFFFFFFu, false, nullptr, nullptr, 0, 0, &P);
     else
-        status = za_inflate_serial_core<0, uint8_t, ZA_MEMBER_RING, ZaParBufT<ZA_MEMBER_BITS, ZA_MEMBER_Q>>(src + hdr, n - hdr, nullptr, 0, out + it.out_off, it.out_cap, T, win, scratch, P.stage,
+        status = za_inflate_serial_core<0, uint8_t, ZA_MEMBER_RING, ZaParBufT<ZA_MEMBER_BITS, ZA_MEMBER_Q>>(src + hdr, n - hdr, hd, hl, out + it.out_off, it.out_cap, T, win, scratch, P.stage,
                                                                        bits, op, 0, nullptr, nullptr, 0xFFFFFFFFu, false, nullptr, nullptr, 0, 0, &P);
     res.out_len = (uint32_t)op;
     if (status == ZA_I_END) {
@@ -210,6 +229,70 @@ __global__ __launch_bounds__(64) void za_k_inflate_batch(const uint8_t *__restri
     } else st = status == ZA_I_OUTFULL ? ZA_BATCH_OUTFULL : status == ZA_I_INPUT ? ZA_BATCH_TRUNCATED : ZA_BATCH_DATA;
     res.status = st;
     if (lane == 0) results[blockIdx.x] = res;
+}
+
+template <int COUNT>
+__global__ __launch_bounds__(64) void za_k_inflate_batch(const uint8_t *__restrict__ in, uint64_t in_len,
+                                                         const ZaBatchItem *__restrict__ items,
+                                                         uint8_t *__restrict__ out, uint64_t out_cap,
+                                                         const uint32_t *__restrict__ crc_table,
+                                                         const uint32_t *__restrict__ x8k_table,
+                                                         int kind0, int wmax,
+                                                         ZaBatchResult *__restrict__ results)
+{
+    za_inflate_batch_item<COUNT, false>(in, in_len, items, out, out_cap, crc_table, x8k_table, kind0, wmax, results, nullptr, 0u, 0u);
+}
+
+template <int COUNT>
+__global__ __launch_bounds__(64) void za_k_inflate_batch_dict(const uint8_t *__restrict__ in, uint64_t in_len,
+                                                              const ZaBatchItem *__restrict__ items,
+                                                              uint8_t *__restrict__ out, uint64_t out_cap,
+                                                              const uint32_t *__restrict__ crc_table,
+                                                              const uint32_t *__restrict__ x8k_table,
+                                                              int kind0, int wmax,
+                                                              ZaBatchResult *__restrict__ results,
+                                                              const uint8_t *__restrict__ dict, uint32_t dict_len, uint32_t dictid)
+{
+    za_inflate_batch_item<COUNT, true>(in, in_len, items, out, out_cap, crc_table, x8k_table, kind0, wmax, results, dict, dict_len, dictid);
+}
+
+// n bytes from src to dst on one wavefront: the stores are whole aligned 16-byte pieces of dst (a few single bytes in front of the
+// first and behind the last), each lane assembling its piece from five aligned dwords of src (v_alignbyte).  src must be readable
+// up to 20 bytes past n (ZA_BATCH_PAD behind the input, 64 behind the dictionary).
+__device__ __forceinline__ void za_wave_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint64_t n)
+{
+    const int lane = za_lane();
+    const uint64_t h0 = (16u - ((uintptr_t)dst & 15u)) & 15u, h = h0 < n ? h0 : n;
+    if ((uint64_t)lane < h) dst[lane] = src[lane];
+    dst += h; src += h; n -= h;
+    const uint32_t sh = (uint32_t)((uintptr_t)src & 3u);
+    const uint32_t *s4 = (const uint32_t *)(src - sh);
+    const uint64_t nv = n >> 4;
+    for (uint64_t k = (uint64_t)lane; k < nv; k += 64) {
+        const uint32_t *p = s4 + 4 * k;
+        const uint32_t w0 = p[0], w1 = p[1], w2 = p[2], w3 = p[3], w4 = p[4];
+        uint4 v;
+        v.x = __builtin_amdgcn_alignbyte(w1, w0, sh); v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
+        v.z = __builtin_amdgcn_alignbyte(w3, w2, sh); v.w = __builtin_amdgcn_alignbyte(w4, w3, sh);
+        *(uint4 *)(dst + 16 * k) = v;
+    }
+    for (uint64_t k = (nv << 4) + (uint64_t)lane; k < n; k += 64) dst[k] = src[k];
+}
+
+// Compress side with a dictionary: item i (in_off, in_len of the host-built table; out_off = the place of its record in `prime`)
+// becomes [the tail's tl bytes][the item] at out_off.  The records start on 64-byte boundaries, as a stream's staged buffer does.
+__global__ __launch_bounds__(64) void za_k_batch_prime(const uint8_t *__restrict__ in, uint64_t in_len, const ZaBatchItem *__restrict__ items,
+                                                       uint32_t n, const uint8_t *__restrict__ tail, uint32_t tl,
+                                                       uint8_t *__restrict__ prime, uint64_t prime_cap)
+{
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    const ZaBatchItem it = items[i];
+    // (the host checked the table; a record outside the buffers is left alone, and the deflate of that block is garbage, not a fault)
+    if (it.in_off > in_len || in_len - it.in_off < it.in_len || it.out_off > prime_cap || prime_cap - it.out_off < (uint64_t)tl + it.in_len) return;
+    uint8_t *dst = prime + it.out_off;
+    za_wave_copy(dst, tail, tl);
+    za_wave_copy(dst + tl, in + it.in_off, it.in_len);
 }
 
 // The compress side's framing.  Items are packed by za_k_pack unit after unit, so item i's deflate bytes run from the offset of its

@@ -26,6 +26,7 @@ static_assert(sizeof(zngamd_member) == sizeof(ZaMember), "member layout");
 static_assert(sizeof(zngamd_span) == sizeof(ZaSpan) && ZNGAMD_SPAN_PAD == ZA_SPAN_PAD && ZNGAMD_SPAN_CRC == ZA_SPAN_CRC, "span layout");
 static_assert(sizeof(zngamd_batch_item) == sizeof(ZaBatchItem) && sizeof(zngamd_batch_result) == sizeof(ZaBatchResult) &&
               ZNGAMD_BATCH_PAD == ZA_BATCH_PAD && ZNGAMD_BATCH_TABLE == ZA_BATCH_TABLE && ZNGAMD_BATCH_OUTFULL == ZA_BATCH_OUTFULL, "batch layout");
+static_assert(ZNGAMD_ZDICT_MISMATCH == ZA_ZDICT_MISMATCH, "zdict status");
 static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT + 32, "slot stride");
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
@@ -108,6 +109,7 @@ struct zngamd_ctx {
     DevBuf<uint8_t> sp_in, sp_win, sp_out; DevBuf<ZaSpan> sp_tab; DevBuf<int32_t> sp_status;      // staging of zngamd_inflate_spans
     DevBuf<uint8_t> bt_out, bt_out2, bt_def; DevBuf<ZaBatchItem> bt_items, bt_items2; DevBuf<ZaBatchResult> bt_res, bt_res2;    // the batch API (za_batch.hip)
     DevBuf<uint32_t> bt_first, bt_ulen, bt_ucrc; DevBuf<uint64_t> bt_uoff, bt_total;
+    DevBuf<uint8_t> bt_dict, bt_prime;           // the batch API with a dictionary: its kept tail, the primed items ([tail][item] each)
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
     uint8_t *h_tab = nullptr; size_t h_tab_cap = 0;
@@ -246,6 +248,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->sp_in.release(); c->sp_win.release(); c->sp_out.release(); c->sp_tab.release(); c->sp_status.release();
     c->bt_out.release(); c->bt_out2.release(); c->bt_def.release(); c->bt_items.release(); c->bt_items2.release(); c->bt_res.release(); c->bt_res2.release();
     c->bt_first.release(); c->bt_ulen.release(); c->bt_ucrc.release(); c->bt_uoff.release(); c->bt_total.release();
+    c->bt_dict.release(); c->bt_prime.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -1592,10 +1595,53 @@ static uint32_t batch_header(int kind, int level, int wb, ZaBatchFrameHdr *h)
 
 static uint32_t batch_trailer(int kind) { return kind == ZA_BATCH_ZLIB ? 4u : kind == ZA_BATCH_GZIP ? 8u : 0u; }
 
-static int inflate_batch_launch(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaBatchItem *d_items, uint32_t n, int kind, int wmax,
-                                bool count_only, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res)
+// One preset dictionary for a whole call (zdict): its kept tail (the last 32 KiB, as zngamd_stream_*_set_dictionary keep) in device
+// memory with 64 readable bytes behind it, and its Adler-32 (the DICTID of a zlib header)
+struct BatchDict { const uint8_t *d_tail = nullptr; uint32_t tl = 0, dictid = 1; };
+
+// the zlib header of compressobj(zdict=...): FDICT set, FCHECK worked out again, DICTID behind it (zs_zlib_header in zng_stream.hip)
+static uint32_t batch_header_dict(int kind, int level, int wb, uint32_t dictid, ZaBatchFrameHdr *h)
 {
-    if (n) {
+    memset(h, 0, sizeof(*h));
+    if (kind != ZA_BATCH_ZLIB) return 0;
+    const int lv = level == -1 ? 6 : level;
+    const uint32_t flevel = lv < 2 ? 0 : lv < 6 ? 1 : lv == 6 ? 2 : 3;
+    uint32_t head = ((((uint32_t)(wb - 8) << 4) | 8u) << 8) | (flevel << 6) | 0x20u;
+    head += 31u - head % 31u;
+    h->b[0] = (uint8_t)(head >> 8); h->b[1] = (uint8_t)head;
+    for (int k = 0; k < 4; k++) h->b[2 + k] = (uint8_t)(dictid >> (24 - 8 * k));
+    return 6;
+}
+
+// the dictionary's Adler-32: zngamd_adler32 takes the context's lock and its input staging, so this runs before the caller's
+static int batch_dict_id(zngamd_ctx *c, const uint8_t *dict, uint32_t len, uint32_t *id)
+{
+    *id = 1;
+    return len ? zngamd_adler32(c, 1, dict, len, id) : ZNGAMD_OK;
+}
+
+// (under the lock) the kept tail into bt_dict
+static int batch_dict_upload(zngamd_ctx *c, const uint8_t *dict, uint32_t len, uint32_t dictid, BatchDict *bd)
+{
+    const uint32_t keep = len > ZA_WIN ? (uint32_t)ZA_WIN : len;
+    HIPCHK(c, c->bt_dict.ensure(ZA_WIN + 64));
+    if (keep) HIPCHK(c, hipMemcpyAsync(c->bt_dict.p, dict + (len - keep), keep, hipMemcpyHostToDevice, c->stream));
+    bd->d_tail = c->bt_dict.p; bd->tl = keep; bd->dictid = dictid;
+    return ZNGAMD_OK;
+}
+
+static int inflate_batch_launch(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaBatchItem *d_items, uint32_t n, int kind, int wmax,
+                                bool count_only, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res, const BatchDict *bd = nullptr)
+{
+    if (n && bd) {
+        ProfScope ps(c, ZNGAMD_K_INFLATE);
+        if (count_only)
+            hipLaunchKernelGGL(za_k_inflate_batch_dict<1>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res,
+                               bd->d_tail, bd->tl, bd->dictid);
+        else
+            hipLaunchKernelGGL(za_k_inflate_batch_dict<0>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res,
+                               bd->d_tail, bd->tl, bd->dictid);
+    } else if (n) {
         ProfScope ps(c, ZNGAMD_K_INFLATE);
         if (count_only)
             hipLaunchKernelGGL(za_k_inflate_batch<1>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res);
@@ -1637,16 +1683,22 @@ static uint32_t batch_guess(const uint8_t *in, uint64_t in_len, const zngamd_bat
     return (uint32_t)std::min<uint64_t>(4ull * it.in_len + 1024, hi);
 }
 
-int zngamd_inflate_batch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
-                         zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results)
-try {
-    if (!c || (!in && in_len) || (n && (!items || !results || !alloc))) return ZNGAMD_E_ARG;
+// the host form of zngamd_inflate_batch[_dict]: dict / dict_len = NULL / 0 without a dictionary
+static int inflate_batch_host(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
+                              const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results)
+{
+    if (!c || (!in && in_len) || (n && (!items || !results || !alloc)) || (!dict && dict_len)) return ZNGAMD_E_ARG;
     int kind, wmax;
     if (batch_inflate_container(wbits, &kind, &wmax)) return fail(c, ZNGAMD_STREAM_ERROR, "invalid wbits");
     if (n == 0) return ZNGAMD_OK;
+    uint32_t dictid = 1;
+    if (dict_len) { const int rd = batch_dict_id(c, dict, dict_len, &dictid); if (rd) return rd; }
     std::lock_guard<std::mutex> g(c->mu);
     int r = stage_in(c, in, in_len);                    // (64 zero bytes behind the input: ZA_BATCH_PAD)
     if (r) return r;
+    BatchDict bdv;
+    const BatchDict *bd = nullptr;
+    if (dict_len) { r = batch_dict_upload(c, dict, dict_len, dictid, &bdv); if (r) return r; bd = &bdv; }
     // first decode: every item with its guessed room, back to back
     std::vector<ZaBatchItem> t1(n);
     uint64_t r1 = 0;
@@ -1658,7 +1710,7 @@ try {
     }
     HIPCHK(c, c->bt_items.ensure(n)); HIPCHK(c, c->bt_res.ensure(n)); HIPCHK(c, c->bt_out.ensure(r1 + 64));
     HIPCHK(c, hipMemcpyAsync(c->bt_items.p, t1.data(), (size_t)n * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
-    r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items.p, n, kind, wmax, false, c->bt_out.p, r1, c->bt_res.p);
+    r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items.p, n, kind, wmax, false, c->bt_out.p, r1, c->bt_res.p, bd);
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(results, c->bt_res.p, (size_t)n * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1675,7 +1727,7 @@ try {
         for (uint32_t k = 0; k < m; k++) { t2[k] = t1[full[k]]; t2[k].out_off = 0; t2[k].out_cap = 0; }
         HIPCHK(c, c->bt_items2.ensure(m)); HIPCHK(c, c->bt_res2.ensure(m));
         HIPCHK(c, hipMemcpyAsync(c->bt_items2.p, t2.data(), (size_t)m * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
-        r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items2.p, m, kind, wmax, true, nullptr, 0, c->bt_res2.p);
+        r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items2.p, m, kind, wmax, true, nullptr, 0, c->bt_res2.p, bd);
         if (r) return r;
         HIPCHK(c, hipMemcpyAsync(res2.data(), c->bt_res2.p, (size_t)m * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1685,7 +1737,7 @@ try {
         }
         HIPCHK(c, c->bt_out2.ensure(r2 + 64));
         HIPCHK(c, hipMemcpyAsync(c->bt_items2.p, t2.data(), (size_t)m * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
-        r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items2.p, m, kind, wmax, false, c->bt_out2.p, r2, c->bt_res2.p);
+        r = inflate_batch_launch(c, c->st_in.p, in_len, c->bt_items2.p, m, kind, wmax, false, c->bt_out2.p, r2, c->bt_res2.p, bd);
         if (r) return r;
         std::vector<ZaBatchResult> res3(m);
         HIPCHK(c, hipMemcpyAsync(res3.data(), c->bt_res2.p, (size_t)m * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
@@ -1700,6 +1752,41 @@ try {
     if (!dst && r1 + r2) return fail(c, ZNGAMD_MEM_ERROR, "cannot allocate the output");
     if (r1) { const int rc_ = d2h_payload(c, dst, c->bt_out.p, r1); if (rc_) return rc_; }
     if (r2) { const int rc_ = d2h_payload(c, dst + r1, c->bt_out2.p, r2); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+}
+
+int zngamd_inflate_batch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
+                         zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results)
+try {
+    return inflate_batch_host(c, in, in_len, items, n, wbits, nullptr, 0, alloc, user, results);
+} ZA_ABI_GUARD
+
+int zngamd_inflate_batch_dict(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
+                              const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results)
+try {
+    return inflate_batch_host(c, in, in_len, items, n, wbits, dict, dict_len, alloc, user, results);
+} ZA_ABI_GUARD
+
+int zngamd_inflate_batch_dict_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n, int wbits,
+                                  const uint8_t *dict, uint32_t dict_len, int count_only, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results)
+try {
+    if (!c || (n && (!d_in || !d_items || !d_results)) || (!d_out && out_cap) || (!dict && dict_len)) return ZNGAMD_E_ARG;
+    if (!dict_len) return zngamd_inflate_batch_dev(c, d_in, in_len, d_items, n, wbits, count_only, d_out, out_cap, d_results);
+    int kind, wmax;
+    if (batch_inflate_container(wbits, &kind, &wmax)) return fail(c, ZNGAMD_STREAM_ERROR, "invalid wbits");
+    uint32_t dictid = 1;
+    int r = batch_dict_id(c, dict, dict_len, &dictid);
+    if (r) return r;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    BatchDict bd;
+    r = batch_dict_upload(c, dict, dict_len, dictid, &bd);
+    if (r) return r;
+    r = inflate_batch_launch(c, (const uint8_t *)d_in, in_len, (const ZaBatchItem *)d_items, n, kind, wmax, count_only != 0, (uint8_t *)d_out,
+                             d_out ? out_cap : 0, (ZaBatchResult *)d_results, &bd);
+    if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     return ZNGAMD_OK;
@@ -1794,6 +1881,161 @@ try {
     }
     HIPCHK(c, c->bt_out.ensure(cap)); HIPCHK(c, c->bt_res.ensure(n));
     r = deflate_batch_locked(c, c->st_in.p, in_len, items, n, level, wbits, strategy, c->bt_out.p, cap, c->bt_res.p, total);
+    if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(results, c->bt_res.p, (size_t)n * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
+    uint8_t *dst = (uint8_t *)alloc(user, *total);
+    if (!dst && *total) { (void)hipStreamSynchronize(c->stream); return fail(c, ZNGAMD_MEM_ERROR, "cannot allocate the output"); }
+    if (*total) { const int rc_ = d2h_payload(c, dst, c->bt_out.p, *total); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// Compress with a dictionary: every item is the stream compressobj(level, DEFLATED, wbits, strategy=..., zdict=...) writes for it.
+// za_k_batch_prime writes [tail][item] per item into bt_prime (records on 64-byte boundaries, as the stream's staged buffer), the
+// pipeline runs ONE block per item -- FINAL, 128 KiB units, dict_len = the tail, as zs_deflate_pending -- and za_k_batch_frame adds
+// the FDICT header and the Adler-32 of the item's own bytes.  Every item carries up to 32 KiB of history, so the staging and the
+// deflate workspace grow with (tail + item): the items run in ranges whose records stay under ZA_BATCH_PRIME_BUDGET.
+#define ZA_BATCH_PRIME_BUDGET (256ull << 20)
+static int deflate_batch_dict_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                                     int strategy, const BatchDict &bd, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res, uint64_t *total)
+{
+    *total = 0;
+    int kind, wb;
+    if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (batch_deflate_container(wbits, &kind, &wb)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
+    if (strategy < ZNGAMD_STRATEGY_DEFAULT || strategy > ZNGAMD_STRATEGY_FIXED) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression strategy");
+    if (n == 0) return ZNGAMD_OK;
+    for (uint32_t i = 0; i < n; i++)
+        if (items[i].in_off > in_len || in_len - items[i].in_off < items[i].in_len) return fail(c, ZNGAMD_E_ARG, "block outside the input buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    ZaBatchFrameHdr head;
+    const uint32_t hl = batch_header_dict(kind, level, wb, bd.dictid, &head), ovh = hl + batch_trailer(kind);
+    HIPCHK(c, c->bt_items.ensure(n));
+    HIPCHK(c, hipMemcpyAsync(c->bt_items.p, items, (size_t)n * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));  // (the frame's table: the items' own bytes)
+    std::vector<ZaBatchItem> pt(n), back(n);
+    uint64_t base = 0;
+    bool fits = true;
+    for (uint32_t a = 0; a < n;) {
+        // the range [a, b): records of (tail + item) rounded up to 64 bytes, under the budget (a larger item goes alone)
+        uint64_t plen = 0;
+        uint32_t b = a;
+        for (; b < n; b++) {
+            const uint64_t rl = ((uint64_t)bd.tl + items[b].in_len + 63) & ~63ull;
+            if (b > a && plen + rl > ZA_BATCH_PRIME_BUDGET) break;
+            pt[b].in_off = items[b].in_off; pt[b].in_len = items[b].in_len; pt[b].out_off = plen; pt[b].out_cap = 0;
+            pt[b].reserved[0] = pt[b].reserved[1] = 0;
+            plen += rl;
+        }
+        const uint32_t m = b - a;
+        HIPCHK(c, c->bt_prime.ensure(plen + 64)); HIPCHK(c, c->bt_items2.ensure(m));
+        HIPCHK(c, hipMemcpyAsync(c->bt_items2.p, pt.data() + a, (size_t)m * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
+        {
+            ProfScope ps(c, ZNGAMD_K_GATHER);
+            hipLaunchKernelGGL(za_k_batch_prime, dim3(m), dim3(64), 0, c->stream, d_in, in_len, c->bt_items2.p, m, bd.d_tail, bd.tl, c->bt_prime.p, plen + 64);
+        }
+        HIPCHK(c, hipGetLastError());
+        std::vector<zngamd_block> blocks(m);
+        for (uint32_t k = 0; k < m; k++) {
+            zngamd_block &B = blocks[k];
+            B.off = pt[a + k].out_off + bd.tl; B.len = items[a + k].in_len; B.dict_len = bd.tl; B.reserved = 0;
+            B.flags = ZNGAMD_FLAG_FINAL | ZNGAMD_FLAG_WBITS(wb) | ZNGAMD_FLAG_STRATEGY(strategy);
+        }
+        std::vector<ZaUnit> hu;
+        int r = build_units(c, blocks.data(), m, plen, hu);
+        if (r) return r;
+        const uint32_t nu = (uint32_t)hu.size();
+        std::vector<uint32_t> first(m + 1, nu);
+        for (uint32_t u = nu; u-- > 0;) first[hu[u].block] = u;
+        uint64_t bound = 64;
+        for (const ZaUnit &u : hu) bound += (uint64_t)u.in_len + 32u;
+        HIPCHK(c, c->bt_def.ensure(bound)); HIPCHK(c, c->bt_uoff.ensure(nu)); HIPCHK(c, c->bt_ulen.ensure(nu)); HIPCHK(c, c->bt_ucrc.ensure(nu));
+        HIPCHK(c, c->bt_total.ensure(1)); HIPCHK(c, c->bt_first.ensure(m + 1));
+        HIPCHK(c, hipMemcpyAsync(c->bt_first.p, first.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        PackedDst pd; pd.d_dst = c->bt_def.p; pd.cap = bound; pd.d_unit_off = c->bt_uoff.p; pd.d_total = c->bt_total.p;
+        r = deflate_units_dev(c, c->bt_prime.p, plen, hu, level, nullptr, c->bt_ulen.p, c->bt_ucrc.p, 1 << wb, &pd, strategy);
+        if (r) return r;
+        uint64_t def_total = 0;
+        std::vector<uint32_t> st(nu);
+        HIPCHK(c, hipMemcpyAsync(&def_total, c->bt_total.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, (size_t)nu * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->up_busy = false;
+        for (uint32_t v : st) if (v) return fail(c, ZNGAMD_E_HIP, "packed deflate: a unit's size differs from its plan");
+        if (def_total > bound) return fail(c, ZNGAMD_E_HIP, "packed deflate: stream larger than its bound");
+        const uint64_t need = def_total + (uint64_t)m * ovh;
+        fits = fits && base + need <= out_cap;
+        if (fits) {
+            {
+                ProfScope ps(c, ZNGAMD_K_GATHER);
+                hipLaunchKernelGGL(za_k_batch_frame, dim3(m), dim3(64), 0, c->stream, d_in, c->bt_items.p + a, m, c->bt_first.p, nu, c->bt_uoff.p, c->bt_ucrc.p,
+                                   c->bt_total.p, c->bt_def.p, kind, head, hl, d_out + base, out_cap - base, d_res + a);
+            }
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(back.data() + a, c->bt_items.p + a, (size_t)m * sizeof(ZaBatchItem), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (uint32_t k = a; k < b; k++) items[k].out_off = base + back[k].out_off;
+        }
+        base += need;
+        a = b;
+    }
+    *total = base;
+    if (!fits) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    return ZNGAMD_OK;
+}
+
+int zngamd_deflate_batch_dict_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                                  int strategy, const uint8_t *dict, uint32_t dict_len, void *d_out, uint64_t out_cap,
+                                  zngamd_batch_result *d_results, uint64_t *total)
+try {
+    if (!c || !total || (n && (!d_in || !items || !d_out || !d_results)) || (!dict && dict_len)) return ZNGAMD_E_ARG;
+    if (!dict) return zngamd_deflate_batch_dev(c, d_in, in_len, items, n, level, wbits, strategy, d_out, out_cap, d_results, total);
+    *total = 0;
+    int kind, wb;
+    if (batch_deflate_container(wbits, &kind, &wb) == ZNGAMD_OK && kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
+    uint32_t dictid = 1;
+    int r = batch_dict_id(c, dict, dict_len, &dictid);
+    if (r) return r;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    BatchDict bd;
+    r = batch_dict_upload(c, dict, dict_len, dictid, &bd);
+    if (r) return r;
+    r = deflate_batch_dict_locked(c, (const uint8_t *)d_in, in_len, items, n, level, wbits, strategy, bd, (uint8_t *)d_out, out_cap, (ZaBatchResult *)d_results, total);
+    if (r) return r;
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_deflate_batch_dict(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                              int strategy, const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user,
+                              zngamd_batch_result *results, uint64_t *total)
+try {
+    if (!c || (!in && in_len) || !total || (n && (!items || !results || !alloc)) || (!dict && dict_len)) return ZNGAMD_E_ARG;
+    if (!dict) return zngamd_deflate_batch(c, in, in_len, items, n, level, wbits, strategy, alloc, user, results, total);
+    *total = 0;
+    int kind, wb;
+    if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (batch_deflate_container(wbits, &kind, &wb)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    if (kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
+    if (n == 0) return ZNGAMD_OK;
+    uint32_t dictid = 1;
+    int r = batch_dict_id(c, dict, dict_len, &dictid);
+    if (r) return r;
+    std::lock_guard<std::mutex> g(c->mu);
+    r = stage_in(c, in, in_len);
+    if (r) return r;
+    BatchDict bd;
+    r = batch_dict_upload(c, dict, dict_len, dictid, &bd);
+    if (r) return r;
+    uint64_t cap = 64 + (uint64_t)n * 18;               // (zngamd_deflate_batch's bound: 32 bytes a 16 KiB unit, more than 128 KiB units need)
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t U = items[i].in_len <= ZA_MAX_UNIT ? ZA_SMALL_UNIT : ZA_MAX_UNIT;
+        cap += items[i].in_len + 32 * std::max<uint64_t>(1, (items[i].in_len + U - 1) / U);
+    }
+    HIPCHK(c, c->bt_out.ensure(cap)); HIPCHK(c, c->bt_res.ensure(n));
+    r = deflate_batch_dict_locked(c, c->st_in.p, in_len, items, n, level, wbits, strategy, bd, c->bt_out.p, cap, c->bt_res.p, total);
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(results, c->bt_res.p, (size_t)n * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
     uint8_t *dst = (uint8_t *)alloc(user, *total);

@@ -78,6 +78,7 @@ SYMBOLS = [
     "zngamd_kernel_times", "zngamd_kernel_class_count", "zngamd_abi", "zngamd_decode_paths", "zngamd_deflate_index_dev", "zngamd_inflate_units_indexed_dev", "zngamd_index_create", "zngamd_index_destroy", "zngamd_deflate_index", "zngamd_deflate_blocks_packed_indexed", "zngamd_indexed_units", "zngamd_debug_fetch", "zngamd_debug_keep", "zngamd_d2d", "zngamd_dmemset", "zngamd_mem_info",
     "zngamd_inflate_spans_dev", "zngamd_inflate_spans", "zngamd_span_stats",
     "zngamd_inflate_batch_dev", "zngamd_inflate_batch", "zngamd_deflate_batch_dev", "zngamd_deflate_batch",
+    "zngamd_inflate_batch_dict_dev", "zngamd_inflate_batch_dict", "zngamd_deflate_batch_dict_dev", "zngamd_deflate_batch_dict",
 ]
 
 
@@ -108,6 +109,7 @@ class BatchResult(C.Structure):                # zngamd_batch_result
 (BATCH_OK, BATCH_TRUNCATED, BATCH_OUTFULL, BATCH_NEED_DICT, BATCH_HEADER, BATCH_WINDOW, BATCH_METHOD, BATCH_FLAGS, BATCH_HCRC,
  BATCH_DATA, BATCH_CHECK, BATCH_LENGTH, BATCH_TABLE) = range(13)
 BATCH_PAD = 64
+ZDICT_MISMATCH = 13                            # ZNGAMD_ZDICT_MISMATCH: a zlib item's DICTID is not the dictionary's Adler-32
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_uint64)      # zngamd_alloc_fn
 
 
@@ -195,6 +197,12 @@ def load():
                                                C.POINTER(C.c_uint64)]
         L.zngamd_deflate_batch.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, ALLOC_FN, vp, vp,
                                            C.POINTER(C.c_uint64)]
+        L.zngamd_inflate_batch_dict_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp]
+        L.zngamd_inflate_batch_dict.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, C.c_uint32, ALLOC_FN, vp, vp]
+        L.zngamd_deflate_batch_dict_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, vp, C.c_uint64,
+                                                    vp, C.POINTER(C.c_uint64)]
+        L.zngamd_deflate_batch_dict.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, ALLOC_FN, vp,
+                                                vp, C.POINTER(C.c_uint64)]
         L.zngamd_compare_dev.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.zngamd_crc32_fold_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
         L.zngamd_gunzip.argtypes = [vp, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64),
@@ -260,6 +268,16 @@ class _Pinned:
         if getattr(self, "ok", False):
             C.pythonapi.PyBuffer_Release(C.byref(self.view))
             self.ok = False
+
+
+def _dict_arg(zdict):
+    """(pointer, keep-alive, length) of a batch call's dictionary: never a NULL pointer, even for an empty one (NULL is "no dictionary")"""
+    n = memoryview(zdict).nbytes
+    if n == 0:
+        b = b"\0"
+        return C.cast(C.c_char_p(b), C.c_void_p), b, 0
+    p, keep = _addr(zdict)
+    return p, keep, n
 
 
 def _addr(buf):
@@ -881,10 +899,10 @@ class Context:
         self._chk(self.L.zngamd_span_stats(self.h, m, 1 if reset else 0))
         return int(m[0]), int(m[1])
 
-    # ---- the batch API (batch.py)
-    def inflate_batch(self, data, items, n, wbits):
-        """zngamd_inflate_batch: data = the items back to back (bytes-like), items = a ctypes array of BatchItem (out_off / out_cap are
-        written).  -> (output bytes object, ctypes array of BatchResult)"""
+    # ---- the batch API (batch.py); zdict: None = no dictionary, else a bytes-like shared by every item (the _dict entry points)
+    def inflate_batch(self, data, items, n, wbits, zdict=None):
+        """zngamd_inflate_batch[_dict]: data = the items back to back (bytes-like), items = a ctypes array of BatchItem (out_off / out_cap
+        are written).  -> (output bytes object, ctypes array of BatchResult)"""
         p, keep = _addr(data)
         res = (BatchResult * max(n, 1))()
         box = []
@@ -895,12 +913,17 @@ class Context:
             return addr.value
 
         fn = ALLOC_FN(alloc)
-        self._chk(self.L.zngamd_inflate_batch(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, wbits, fn, None,
-                                              C.cast(res, C.c_void_p)))
+        if zdict is None:
+            self._chk(self.L.zngamd_inflate_batch(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, wbits, fn, None,
+                                                  C.cast(res, C.c_void_p)))
+        else:
+            dp, dkeep, dlen = _dict_arg(zdict)
+            self._chk(self.L.zngamd_inflate_batch_dict(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, wbits, dp, dlen, fn,
+                                                       None, C.cast(res, C.c_void_p)))
         return (box[0] if box else b""), res
 
-    def deflate_batch(self, data, items, n, level, wbits, strategy=STRATEGY_DEFAULT):
-        """zngamd_deflate_batch -> (output bytes object, ctypes array of BatchResult, total); items[i].out_off is written"""
+    def deflate_batch(self, data, items, n, level, wbits, strategy=STRATEGY_DEFAULT, zdict=None):
+        """zngamd_deflate_batch[_dict] -> (output bytes object, ctypes array of BatchResult, total); items[i].out_off is written"""
         p, keep = _addr(data)
         res = (BatchResult * max(n, 1))()
         box = []
@@ -912,23 +935,38 @@ class Context:
 
         fn = ALLOC_FN(alloc)
         total = C.c_uint64(0)
-        self._chk(self.L.zngamd_deflate_batch(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, level, wbits, strategy,
-                                              fn, None, C.cast(res, C.c_void_p), C.byref(total)))
+        if zdict is None:
+            self._chk(self.L.zngamd_deflate_batch(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, level, wbits, strategy,
+                                                  fn, None, C.cast(res, C.c_void_p), C.byref(total)))
+        else:
+            dp, dkeep, dlen = _dict_arg(zdict)
+            self._chk(self.L.zngamd_deflate_batch_dict(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, level, wbits,
+                                                       strategy, dp, dlen, fn, None, C.cast(res, C.c_void_p), C.byref(total)))
         return (box[0] if box else b""), res, total.value
 
-    def inflate_batch_dev(self, d_in, in_len, d_items, n, wbits, count_only, d_out, out_cap, d_results):
-        """zngamd_inflate_batch_dev on device pointers (ints or c_void_p); the results stay in d_results."""
+    def inflate_batch_dev(self, d_in, in_len, d_items, n, wbits, count_only, d_out, out_cap, d_results, zdict=None):
+        """zngamd_inflate_batch[_dict]_dev on device pointers (ints or c_void_p); the results stay in d_results."""
         v = lambda x: C.c_void_p(int(x)) if x else None
-        self._chk(self.L.zngamd_inflate_batch_dev(self.h, v(d_in), in_len, v(d_items), n, wbits, 1 if count_only else 0, v(d_out), out_cap,
-                                                  v(d_results)))
+        if zdict is None:
+            self._chk(self.L.zngamd_inflate_batch_dev(self.h, v(d_in), in_len, v(d_items), n, wbits, 1 if count_only else 0, v(d_out),
+                                                      out_cap, v(d_results)))
+        else:
+            dp, dkeep, dlen = _dict_arg(zdict)
+            self._chk(self.L.zngamd_inflate_batch_dict_dev(self.h, v(d_in), in_len, v(d_items), n, wbits, dp, dlen, 1 if count_only else 0,
+                                                           v(d_out), out_cap, v(d_results)))
 
-    def deflate_batch_dev(self, d_in, in_len, items, n, level, wbits, strategy, d_out, out_cap, d_results):
-        """zngamd_deflate_batch_dev: items = a HOST ctypes array of BatchItem (out_off written) -> (code, total); code OK or BUF_ERROR
-        (total = the size needed)"""
+    def deflate_batch_dev(self, d_in, in_len, items, n, level, wbits, strategy, d_out, out_cap, d_results, zdict=None):
+        """zngamd_deflate_batch[_dict]_dev: items = a HOST ctypes array of BatchItem (out_off written) -> (code, total); code OK or
+        BUF_ERROR (total = the size needed)"""
         v = lambda x: C.c_void_p(int(x)) if x else None
         total = C.c_uint64(0)
-        r = self._chk(self.L.zngamd_deflate_batch_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy, v(d_out),
-                                                      out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
+        if zdict is None:
+            r = self._chk(self.L.zngamd_deflate_batch_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy,
+                                                          v(d_out), out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
+        else:
+            dp, dkeep, dlen = _dict_arg(zdict)
+            r = self._chk(self.L.zngamd_deflate_batch_dict_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy,
+                                                               dp, dlen, v(d_out), out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
         return r, total.value
 
     # ---- measurement

@@ -1,7 +1,7 @@
 """Batch API: compress and decompress many independent buffers in one call.
 
-    batch.compress(items, level=-1, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY) -> list[bytes]
-    batch.decompress(items, wbits=MAX_WBITS, *, errors="raise") -> list[bytes]
+    batch.compress(items, level=-1, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY, zdict=None) -> list[bytes]
+    batch.decompress(items, wbits=MAX_WBITS, *, errors="raise", zdict=None) -> list[bytes]
     batch.compress_dev(ctx, d_in, offsets, lengths, ...) -> (DeviceBuffer, out_offsets, out_lengths)
     batch.decompress_dev(ctx, d_in, offsets, lengths, ...) -> (DeviceBuffer, out_offsets, out_lengths, statuses)
 
@@ -9,6 +9,11 @@
 zlib_ng.decompress(items[i], wbits)`; where the one-shot raises, the batch raises the same type with the same message for the first
 failing item in index order (its index in the exception's `index` attribute), or with errors="return" puts the exception in that
 item's slot.  One wavefront per item, all items of a call in one launch set (za_batch.hip).
+
+With a preset dictionary (zdict, one for the whole call) the yardsticks are the stream objects: compress(items, level, wbits,
+strategy=s, zdict=d)[i] is what compressobj(level, DEFLATED, wbits, DEF_MEM_LEVEL, s, d) writes for items[i] (compress + flush), and
+decompress(items, wbits, zdict=d)[i] is decompressobj(wbits, zdict=d).decompress(items[i]), an unfinished stream being the error
+"incomplete or truncated stream".
 """
 
 import numpy as np
@@ -28,6 +33,10 @@ LARGE_ITEM = 256 << 10
 # Bytes of input per engine call: a larger batch runs as consecutive sub-batches of about this size, so that the staging buffers
 # (input, first-guess output room) stay bounded.  The results are the same.
 SUB_BATCH_BYTES = 256 << 20
+# With a dictionary, an item of at least this many bytes is compressed by compressobj itself: the stream compresses a piece of 32 MiB
+# or more where it lies (zs_deflate_batch in zng_stream.hip), in other blocks than the single one of a batch item, and byte identity
+# with the stream needs its cut.
+ZS_BATCH = 32 << 20
 
 W = "while decompressing data"
 # the one-shot's exception for each item status (zlib_ng.decompress)
@@ -43,10 +52,18 @@ _MESSAGES = {
     _lib.BATCH_CHECK: (_lib.DATA_ERROR, "incorrect data check"),
     _lib.BATCH_LENGTH: (_lib.DATA_ERROR, "incorrect length check"),
 }
+WZ = "while setting zdict"
 
 
 def status_error(status):
-    """The exception zlib_ng.decompress raises for an item with this ZNGAMD_BATCH_* status (None for BATCH_OK)."""
+    """The exception zlib_ng.decompress raises for an item with this ZNGAMD_BATCH_* status (None for BATCH_OK); for
+    ZNGAMD_ZDICT_MISMATCH the one decompressobj(zdict=...) raises for a stream written with another dictionary."""
+    if status == _lib.ZDICT_MISMATCH:
+        return _z._zerr(_lib.DATA_ERROR, WZ)
+    return _status_error(status)
+
+
+def _status_error(status):
     if status == _lib.BATCH_OK:
         return None
     if status in _MESSAGES:
@@ -74,6 +91,45 @@ def _check_strategy(strategy):
         raise TypeError(f"an integer is required (got type {type(strategy).__name__})")
     if not _lib.STRATEGY_DEFAULT <= strategy <= _lib.STRATEGY_FIXED:
         raise ValueError("Invalid initialization option")
+
+
+_INFLATE_WBITS = lambda w: w == 0 or 8 <= w <= 15 or -15 <= w <= -8 or 24 <= w <= 31 or w == 16 or 40 <= w <= 47 or w == 32
+
+
+def _zdict_compress_args(level, wbits, strategy, zdict):
+    """compressobj(level, DEFLATED, wbits, DEF_MEM_LEVEL, strategy, zdict)'s checks in its order -> the dictionary as bytes"""
+    for v in (level, wbits, strategy):
+        if not isinstance(v, int):
+            raise TypeError(f"an integer is required (got type {type(v).__name__})")
+    try:
+        kind, _ = _z._container(wbits)
+    except _z.error:
+        kind = None
+    if kind is None or not -1 <= level <= 9 or not _lib.STRATEGY_DEFAULT <= strategy <= _lib.STRATEGY_FIXED:
+        raise ValueError("Invalid initialization option")
+    z = bytes(_z._view(zdict))
+    if kind == "gzip":                   # no gzip decoder could supply it (deflateSetDictionary: Z_STREAM_ERROR)
+        raise ValueError("Invalid dictionary")
+    return z
+
+
+def _zdict_decompress_args(wbits, zdict):
+    """decompressobj(wbits, zdict)'s checks in its order -> the dictionary as bytes"""
+    if not isinstance(wbits, int):
+        raise TypeError(f"'{type(wbits).__name__}' object cannot be interpreted as an integer")
+    z = bytes(_z._view(zdict))
+    if not _INFLATE_WBITS(wbits):
+        raise ValueError("Invalid initialization option")
+    return z
+
+
+def _zdict_reference(view, wbits, zdict):
+    """decompress with a dictionary on the single-stream path: decompressobj, and an unfinished stream is an error"""
+    o = _z.decompressobj(wbits, zdict=zdict)
+    out = o.decompress(view)
+    if not o.eof:
+        raise _z._zerr(_lib.BUF_ERROR, W)
+    return out
 
 
 def _views(items):
@@ -111,10 +167,14 @@ def _results(rs, n):
     return r[:, 0].view(np.int32).tolist(), r[:, 1].tolist()
 
 
-def compress(items, level=Z_DEFAULT_COMPRESSION, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY):
+def compress(items, level=Z_DEFAULT_COMPRESSION, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY, zdict=None):
     """Compress every item of `items` (buffer-protocol objects) on its own: the i-th result equals zlib_ng.compress(items[i], level,
-    wbits).  With a strategy, each result is the stream compressobj(level, DEFLATED, wbits, strategy=...) would write."""
+    wbits).  With a strategy, each result is the stream compressobj(level, DEFLATED, wbits, strategy=...) would write.  With zdict
+    (a bytes-like; its last 32 KiB are the history of every item) each result is what compressobj(level, DEFLATED, wbits,
+    DEF_MEM_LEVEL, strategy, zdict) writes for the item."""
     views = _views(items)
+    if zdict is not None:
+        return _compress_zdict(views, level, wbits, strategy, _zdict_compress_args(level, wbits, strategy, zdict))
     _z._check_level(level)
     _z._container(wbits)
     _check_strategy(strategy)
@@ -134,6 +194,31 @@ def compress(items, level=Z_DEFAULT_COMPRESSION, wbits=MAX_WBITS, *, strategy=Z_
     return res
 
 
+def _compress_zdict(views, level, wbits, strategy, zb):
+    if not views:
+        return []
+    ctx = _z._ctx()
+    res = [None] * len(views)
+    tl = min(len(zb), 32768)
+    small = [i for i, v in enumerate(views) if v.nbytes < ZS_BATCH]
+    lens = [views[i].nbytes for i in small]
+    # every item is staged behind its own copy of the dictionary's tail: a sub-batch is bounded by its primed bytes
+    for a, b in _sub_batches([ln + tl for ln in lens], SUB_BATCH_BYTES):
+        idx = small[a:b]
+        data = b"".join(views[i] for i in idx)
+        tab, items_c = _table(lens[a:b])
+        out, rs, total = ctx.deflate_batch(data, items_c, b - a, level, wbits, strategy, zdict=zb)
+        mv = memoryview(out)
+        _, olens = _results(rs, b - a)
+        for i, o, ln in zip(idx, tab[:b - a, 1].tolist(), olens):
+            res[i] = bytes(mv[o:o + ln])
+    for i, v in enumerate(views):
+        if v.nbytes >= ZS_BATCH:
+            c = _z.compressobj(level, _z.DEFLATED, wbits, _z.DEF_MEM_LEVEL, strategy, zb)
+            res[i] = c.compress(v) + c.flush()
+    return res
+
+
 def _raise_first(res, errors):
     if errors == "raise":
         for r in res:
@@ -147,12 +232,15 @@ def _with_index(exc, i):
     return exc
 
 
-def decompress(items, wbits=MAX_WBITS, *, errors="raise"):
+def decompress(items, wbits=MAX_WBITS, *, errors="raise", zdict=None):
     """Decompress every item of `items` on its own: the i-th result equals zlib_ng.decompress(items[i], wbits).  errors="raise" raises
     the one-shot's exception for the first failing item (its index in the exception's `index` attribute); errors="return" puts the
-    exception in the failing items' slots instead."""
+    exception in the failing items' slots instead.  With zdict, the i-th result is decompressobj(wbits, zdict=zdict)'s for the item
+    (a zlib item with FDICT and a raw item decode with the dictionary; an unfinished stream is "incomplete or truncated stream")."""
     _check_errors(errors)
     views = _views(items)
+    if zdict is not None:
+        return _raise_first(_decompress_zdict(views, wbits, _zdict_decompress_args(wbits, zdict)), errors)
     _inflate_kind(wbits)
     if not views:
         return []
@@ -178,10 +266,35 @@ def decompress(items, wbits=MAX_WBITS, *, errors="raise"):
     return _raise_first(res, errors)
 
 
+def _decompress_zdict(views, wbits, zb):
+    if not views:
+        return []
+    ctx = _z._ctx()
+    res = [None] * len(views)
+    small = [i for i, v in enumerate(views) if v.nbytes < LARGE_ITEM]
+    sizes = [views[i].nbytes for i in small]
+    for a, b in _sub_batches(sizes, SUB_BATCH_BYTES):
+        idx = small[a:b]
+        data = b"".join(views[i] for i in idx)
+        tab, items_c = _table(sizes[a:b])
+        out, rs = ctx.inflate_batch(data, items_c, b - a, wbits, zdict=zb)
+        mv = memoryview(out)
+        sts, lens = _results(rs, b - a)
+        for i, o, st, ln in zip(idx, tab[:b - a, 1].tolist(), sts, lens):
+            res[i] = bytes(mv[o:o + ln]) if st == _lib.BATCH_OK else _with_index(status_error(st), i)
+    for i, v in enumerate(views):
+        if v.nbytes >= LARGE_ITEM:
+            try:
+                res[i] = _zdict_reference(v, wbits, zb)
+            except Exception as e:
+                res[i] = _with_index(e, i)
+    return res
+
+
 # ---- device-resident forms
-def _frame_bound(lengths, wbits):
+def _frame_bound(lengths, wbits, zdict=None):
     kind, _ = _z._container(wbits)
-    ovh = 6 if kind == "zlib" else 18 if kind == "gzip" else 0
+    ovh = (6 if zdict is None else 10) if kind == "zlib" else 18 if kind == "gzip" else 0
     total = 64
     for ln in lengths:
         u = 16384 if ln <= 131072 else 131072
@@ -189,10 +302,13 @@ def _frame_bound(lengths, wbits):
     return total
 
 
-def compress_dev(ctx, d_in, offsets, lengths, level=Z_DEFAULT_COMPRESSION, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY):
+def compress_dev(ctx, d_in, offsets, lengths, level=Z_DEFAULT_COMPRESSION, wbits=MAX_WBITS, *, strategy=Z_DEFAULT_STRATEGY, zdict=None):
     """Items that lie in device memory (d_in: a DeviceBuffer holding BATCH_PAD readable bytes behind the last item) compressed into
-    one new DeviceBuffer.  -> (buffer, out_offsets, out_lengths) (numpy uint64 arrays)."""
+    one new DeviceBuffer.  -> (buffer, out_offsets, out_lengths) (numpy uint64 arrays).  zdict: as compress (host bytes-like); the
+    engine primes and compresses the items in ranges of bounded size."""
     from . import devmem
+    if zdict is not None:
+        zdict = _zdict_compress_args(level, wbits, strategy, zdict)
     _z._check_level(level)
     _z._container(wbits)
     _check_strategy(strategy)
@@ -206,10 +322,10 @@ def compress_dev(ctx, d_in, offsets, lengths, level=Z_DEFAULT_COMPRESSION, wbits
     for i in range(n):
         items[i].in_off = int(offsets[i])
         items[i].in_len = int(lengths[i])
-    cap = _frame_bound([int(x) for x in lengths], wbits)
+    cap = _frame_bound([int(x) for x in lengths], wbits, zdict)
     out = devmem.DeviceBuffer(ctx, cap)
     d_res = devmem.DeviceBuffer(ctx, 16 * max(n, 1))
-    r, total = ctx.deflate_batch_dev(d_in.ptr, in_len, items, n, level, wbits, strategy, out.ptr, cap, d_res.ptr)
+    r, total = ctx.deflate_batch_dev(d_in.ptr, in_len, items, n, level, wbits, strategy, out.ptr, cap, d_res.ptr, zdict=zdict)
     if r != _lib.OK:
         raise _lib.EngineError(r, ctx.err())
     res = d_res.cpu().view(np.uint32).reshape(-1, 4)[:n]
@@ -217,11 +333,13 @@ def compress_dev(ctx, d_in, offsets, lengths, level=Z_DEFAULT_COMPRESSION, wbits
     return out, offs, res[:, 1].astype(np.uint64)
 
 
-def decompress_dev(ctx, d_in, offsets, lengths, wbits=MAX_WBITS):
+def decompress_dev(ctx, d_in, offsets, lengths, wbits=MAX_WBITS, *, zdict=None):
     """Items that lie in device memory (d_in: a DeviceBuffer holding BATCH_PAD readable bytes behind the last item) decompressed into
     one new DeviceBuffer: a count pass sizes every item, one decode writes it.  -> (buffer, out_offsets, out_lengths, statuses)
-    (numpy arrays; statuses are ZNGAMD_BATCH_* codes, see status_error)."""
+    (numpy arrays; statuses are ZNGAMD_BATCH_* codes or ZDICT_MISMATCH, see status_error).  zdict: as decompress."""
     from . import devmem
+    if zdict is not None:
+        zdict = _zdict_decompress_args(wbits, zdict)
     _inflate_kind(wbits)
     offsets = np.asarray(offsets, dtype=np.uint64)
     lengths = np.asarray(lengths, dtype=np.uint64)
@@ -234,7 +352,7 @@ def decompress_dev(ctx, d_in, offsets, lengths, wbits=MAX_WBITS):
     tab[:n, 2] = lengths & 0xFFFFFFFF
     d_tab = devmem.from_host(ctx, tab.view(np.uint8).reshape(-1))
     d_res = devmem.DeviceBuffer(ctx, 16 * max(n, 1))
-    ctx.inflate_batch_dev(d_in.ptr, in_len, d_tab.ptr, n, wbits, True, None, 0, d_res.ptr)
+    ctx.inflate_batch_dev(d_in.ptr, in_len, d_tab.ptr, n, wbits, True, None, 0, d_res.ptr, zdict=zdict)
     res = d_res.cpu().view(np.uint32).reshape(-1, 4)[:n]
     ok = res[:, 0] == _lib.BATCH_OK
     sizes = np.where(ok, res[:, 1], 0).astype(np.uint64)
@@ -246,7 +364,7 @@ def decompress_dev(ctx, d_in, offsets, lengths, wbits=MAX_WBITS):
     tab[:n, 2] = (lengths & 0xFFFFFFFF) | (sizes << np.uint64(32))
     d_tab[:] = tab.view(np.uint8).reshape(-1)
     out = devmem.DeviceBuffer(ctx, total + 64)
-    ctx.inflate_batch_dev(d_in.ptr, in_len, d_tab.ptr, n, wbits, False, out.ptr, total, d_res.ptr)
+    ctx.inflate_batch_dev(d_in.ptr, in_len, d_tab.ptr, n, wbits, False, out.ptr, total, d_res.ptr, zdict=zdict)
     res2 = d_res.cpu().view(np.uint32).reshape(-1, 4)[:n]
     statuses = np.where(ok, res2[:, 0], res[:, 0]).astype(np.int32)
     lens = np.where(statuses == _lib.BATCH_OK, res2[:, 1], 0).astype(np.uint64)
