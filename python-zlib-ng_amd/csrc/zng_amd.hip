@@ -1573,21 +1573,24 @@ static int batch_deflate_container(int wbits, int *kind, int *wb)
     return ZNGAMD_STREAM_ERROR;
 }
 
-// the one-shot's header bytes (_zlib_header / _gzip_header in zlib_ng.py)
-static uint32_t batch_header(int kind, int level, int wb, ZaBatchFrameHdr *h)
+// The container header the one-shot and the stream objects write (_zlib_header / _gzip_header in zlib_ng.py, zs_zlib_header in
+// zng_stream.hip): zlib 2 bytes, 6 with FDICT and the DICTID behind them when `dictid` is given; gzip 10; raw none.  h: 10 bytes of
+// room.  -> the header's length
+static uint32_t container_header(int kind, int level, int wb, const uint32_t *dictid, uint8_t *h)
 {
-    memset(h, 0, sizeof(*h));
     const int lv = level == -1 ? 6 : level;
     if (kind == ZA_BATCH_ZLIB) {
-        const int flevel = lv < 2 ? 0 : lv < 6 ? 1 : lv == 6 ? 2 : 3;
-        uint32_t head = ((((uint32_t)(wb - 8) << 4) | 8u) << 8) | ((uint32_t)flevel << 6);
+        const uint32_t flevel = lv < 2 ? 0 : lv < 6 ? 1 : lv == 6 ? 2 : 3;
+        uint32_t head = ((((uint32_t)(wb - 8) << 4) | 8u) << 8) | (flevel << 6) | (dictid ? 0x20u : 0u);
         head += 31u - head % 31u;
-        h->b[0] = (uint8_t)(head >> 8); h->b[1] = (uint8_t)head;
-        return 2;
+        h[0] = (uint8_t)(head >> 8); h[1] = (uint8_t)head;
+        if (!dictid) return 2;
+        for (int k = 0; k < 4; k++) h[2 + k] = (uint8_t)(*dictid >> (24 - 8 * k));
+        return 6;
     }
     if (kind == ZA_BATCH_GZIP) {
         const uint8_t g[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, (uint8_t)(lv == 9 ? 2 : lv == 1 ? 4 : 0), 3};
-        memcpy(h->b, g, 10);
+        memcpy(h, g, 10);
         return 10;
     }
     return 0;
@@ -1598,20 +1601,6 @@ static uint32_t batch_trailer(int kind) { return kind == ZA_BATCH_ZLIB ? 4u : ki
 // One preset dictionary for a whole call (zdict): its kept tail (the last 32 KiB, as zngamd_stream_*_set_dictionary keep) in device
 // memory with 64 readable bytes behind it, and its Adler-32 (the DICTID of a zlib header)
 struct BatchDict { const uint8_t *d_tail = nullptr; uint32_t tl = 0, dictid = 1; };
-
-// the zlib header of compressobj(zdict=...): FDICT set, FCHECK worked out again, DICTID behind it (zs_zlib_header in zng_stream.hip)
-static uint32_t batch_header_dict(int kind, int level, int wb, uint32_t dictid, ZaBatchFrameHdr *h)
-{
-    memset(h, 0, sizeof(*h));
-    if (kind != ZA_BATCH_ZLIB) return 0;
-    const int lv = level == -1 ? 6 : level;
-    const uint32_t flevel = lv < 2 ? 0 : lv < 6 ? 1 : lv == 6 ? 2 : 3;
-    uint32_t head = ((((uint32_t)(wb - 8) << 4) | 8u) << 8) | (flevel << 6) | 0x20u;
-    head += 31u - head % 31u;
-    h->b[0] = (uint8_t)(head >> 8); h->b[1] = (uint8_t)head;
-    for (int k = 0; k < 4; k++) h->b[2 + k] = (uint8_t)(dictid >> (24 - 8 * k));
-    return 6;
-}
 
 // the dictionary's Adler-32: zngamd_adler32 takes the context's lock and its input staging, so this runs before the caller's
 static int batch_dict_id(zngamd_ctx *c, const uint8_t *dict, uint32_t len, uint32_t *id)
@@ -1630,43 +1619,23 @@ static int batch_dict_upload(zngamd_ctx *c, const uint8_t *dict, uint32_t len, u
     return ZNGAMD_OK;
 }
 
+// one launch of the batch decoder (count_only: the count pass, sizes only); with a dictionary (bd), the kernel that decodes behind its tail
 static int inflate_batch_launch(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaBatchItem *d_items, uint32_t n, int kind, int wmax,
-                                bool count_only, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res, const BatchDict *bd = nullptr)
+                                bool count_only, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res, const BatchDict *bd)
 {
     if (n && bd) {
         ProfScope ps(c, ZNGAMD_K_INFLATE);
-        if (count_only)
-            hipLaunchKernelGGL(za_k_inflate_batch_dict<1>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res,
-                               bd->d_tail, bd->tl, bd->dictid);
-        else
-            hipLaunchKernelGGL(za_k_inflate_batch_dict<0>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res,
-                               bd->d_tail, bd->tl, bd->dictid);
+        const auto kernel = count_only ? za_k_inflate_batch_dict<1> : za_k_inflate_batch_dict<0>;
+        hipLaunchKernelGGL(kernel, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res,
+                           bd->d_tail, bd->tl, bd->dictid);
     } else if (n) {
         ProfScope ps(c, ZNGAMD_K_INFLATE);
-        if (count_only)
-            hipLaunchKernelGGL(za_k_inflate_batch<1>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res);
-        else
-            hipLaunchKernelGGL(za_k_inflate_batch<0>, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res);
+        const auto kernel = count_only ? za_k_inflate_batch<1> : za_k_inflate_batch<0>;
+        hipLaunchKernelGGL(kernel, dim3(n), dim3(64), 0, c->stream, d_in, in_len, d_items, d_out, out_cap, c->d_crc_table, c->d_x8k, kind, wmax, d_res);
     }
     HIPCHK(c, hipGetLastError());
     return ZNGAMD_OK;
 }
-
-int zngamd_inflate_batch_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n, int wbits,
-                             int count_only, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results)
-try {
-    if (!c || (n && (!d_in || !d_items || !d_results)) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
-    int kind, wmax;
-    if (batch_inflate_container(wbits, &kind, &wmax)) return fail(c, ZNGAMD_STREAM_ERROR, "invalid wbits");
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    int r = inflate_batch_launch(c, (const uint8_t *)d_in, in_len, (const ZaBatchItem *)d_items, n, kind, wmax, count_only != 0, (uint8_t *)d_out,
-                                 d_out ? out_cap : 0, (ZaBatchResult *)d_results);
-    if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
-} ZA_ABI_GUARD
 
 // The first decode's room for an item the caller left at out_cap 0: a gzip member's ISIZE (bounded by deflate's largest ratio),
 // else a multiple of its compressed size.  An item that does not fit is sized exactly by the count pass.
@@ -1683,18 +1652,20 @@ static uint32_t batch_guess(const uint8_t *in, uint64_t in_len, const zngamd_bat
     return (uint32_t)std::min<uint64_t>(4ull * it.in_len + 1024, hi);
 }
 
-// the host form of zngamd_inflate_batch[_dict]: dict / dict_len = NULL / 0 without a dictionary
-static int inflate_batch_host(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
+// The batch entry points without a dictionary are these with none: NULL / 0 on deflate, dict_len == 0 on inflate (an empty dictionary
+// decodes like none; on deflate a non-NULL empty one writes FDICT with DICTID 1, as compressobj(zdict=b"") does).
+int zngamd_inflate_batch_dict(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
                               const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results)
-{
+try {
     if (!c || (!in && in_len) || (n && (!items || !results || !alloc)) || (!dict && dict_len)) return ZNGAMD_E_ARG;
     int kind, wmax;
     if (batch_inflate_container(wbits, &kind, &wmax)) return fail(c, ZNGAMD_STREAM_ERROR, "invalid wbits");
     if (n == 0) return ZNGAMD_OK;
-    uint32_t dictid = 1;
-    if (dict_len) { const int rd = batch_dict_id(c, dict, dict_len, &dictid); if (rd) return rd; }
+    uint32_t dictid;
+    int r = batch_dict_id(c, dict, dict_len, &dictid);
+    if (r) return r;
     std::lock_guard<std::mutex> g(c->mu);
-    int r = stage_in(c, in, in_len);                    // (64 zero bytes behind the input: ZA_BATCH_PAD)
+    r = stage_in(c, in, in_len);                        // (64 zero bytes behind the input: ZA_BATCH_PAD)
     if (r) return r;
     BatchDict bdv;
     const BatchDict *bd = nullptr;
@@ -1755,195 +1726,107 @@ static int inflate_batch_host(zngamd_ctx *c, const uint8_t *in, uint64_t in_len,
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     return ZNGAMD_OK;
-}
+} ZA_ABI_GUARD
 
 int zngamd_inflate_batch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
                          zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results)
-try {
-    return inflate_batch_host(c, in, in_len, items, n, wbits, nullptr, 0, alloc, user, results);
-} ZA_ABI_GUARD
-
-int zngamd_inflate_batch_dict(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int wbits,
-                              const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results)
-try {
-    return inflate_batch_host(c, in, in_len, items, n, wbits, dict, dict_len, alloc, user, results);
-} ZA_ABI_GUARD
+{
+    return zngamd_inflate_batch_dict(c, in, in_len, items, n, wbits, nullptr, 0, alloc, user, results);
+}
 
 int zngamd_inflate_batch_dict_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n, int wbits,
                                   const uint8_t *dict, uint32_t dict_len, int count_only, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results)
 try {
     if (!c || (n && (!d_in || !d_items || !d_results)) || (!d_out && out_cap) || (!dict && dict_len)) return ZNGAMD_E_ARG;
-    if (!dict_len) return zngamd_inflate_batch_dev(c, d_in, in_len, d_items, n, wbits, count_only, d_out, out_cap, d_results);
     int kind, wmax;
     if (batch_inflate_container(wbits, &kind, &wmax)) return fail(c, ZNGAMD_STREAM_ERROR, "invalid wbits");
-    uint32_t dictid = 1;
+    uint32_t dictid;
     int r = batch_dict_id(c, dict, dict_len, &dictid);
     if (r) return r;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     BatchDict bd;
-    r = batch_dict_upload(c, dict, dict_len, dictid, &bd);
-    if (r) return r;
+    if (dict_len) { r = batch_dict_upload(c, dict, dict_len, dictid, &bd); if (r) return r; }
     r = inflate_batch_launch(c, (const uint8_t *)d_in, in_len, (const ZaBatchItem *)d_items, n, kind, wmax, count_only != 0, (uint8_t *)d_out,
-                             d_out ? out_cap : 0, (ZaBatchResult *)d_results, &bd);
+                             d_out ? out_cap : 0, (ZaBatchResult *)d_results, dict_len ? &bd : nullptr);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
 
-// one deflate block per item (FINAL; units of 16 KiB up to 128 KiB, as zngamd_deflate_stream cuts a one-shot call), the packed stream
-// into bt_def, then the framing kernel into d_out.  items: host table (in_off, in_len read; out_off written).
-static int deflate_batch_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
-                                int strategy, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res, uint64_t *total)
+int zngamd_inflate_batch_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n, int wbits,
+                             int count_only, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results)
 {
-    *total = 0;
-    int kind, wb;
-    if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
-    if (batch_deflate_container(wbits, &kind, &wb)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
-    if (strategy < ZNGAMD_STRATEGY_DEFAULT || strategy > ZNGAMD_STRATEGY_FIXED) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression strategy");
-    if (n == 0) return ZNGAMD_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<zngamd_block> blocks(n);
-    for (uint32_t i = 0; i < n; i++) {
-        zngamd_block &B = blocks[i];
-        B.off = items[i].in_off; B.len = items[i].in_len; B.dict_len = 0; B.reserved = 0;
-        B.flags = ZNGAMD_FLAG_FINAL | ZNGAMD_FLAG_STRATEGY(strategy) | (B.len <= ZA_MAX_UNIT ? ZNGAMD_FLAG_UNITS16K : 0u);
-    }
-    std::vector<ZaUnit> hu;
-    int r = build_units(c, blocks.data(), n, in_len, hu);
-    if (r) return r;
-    const uint32_t nu = (uint32_t)hu.size();
-    std::vector<uint32_t> first(n + 1, nu);
-    for (uint32_t u = nu; u-- > 0;) first[hu[u].block] = u;
-    uint64_t bound = 64;
-    for (const ZaUnit &u : hu) bound += (uint64_t)u.in_len + 32u;
-    HIPCHK(c, c->bt_def.ensure(bound)); HIPCHK(c, c->bt_uoff.ensure(nu)); HIPCHK(c, c->bt_ulen.ensure(nu)); HIPCHK(c, c->bt_ucrc.ensure(nu));
-    HIPCHK(c, c->bt_total.ensure(1)); HIPCHK(c, c->bt_first.ensure(n + 1)); HIPCHK(c, c->bt_items.ensure(n));
-    HIPCHK(c, hipMemcpyAsync(c->bt_first.p, first.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->bt_items.p, items, (size_t)n * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
-    PackedDst pd; pd.d_dst = c->bt_def.p; pd.cap = bound; pd.d_unit_off = c->bt_uoff.p; pd.d_total = c->bt_total.p;
-    r = deflate_units_dev(c, d_in, in_len, hu, level, nullptr, c->bt_ulen.p, c->bt_ucrc.p, 1 << wb, &pd, strategy);
-    if (r) return r;
-    uint64_t def_total = 0;
-    std::vector<uint32_t> st(nu);
-    HIPCHK(c, hipMemcpyAsync(&def_total, c->bt_total.p, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, (size_t)nu * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->up_busy = false;
-    for (uint32_t v : st) if (v) return fail(c, ZNGAMD_E_HIP, "packed deflate: a unit's size differs from its plan");
-    if (def_total > bound) return fail(c, ZNGAMD_E_HIP, "packed deflate: stream larger than its bound");
-    ZaBatchFrameHdr head;
-    const uint32_t hl = batch_header(kind, level, wb, &head);
-    *total = def_total + (uint64_t)n * (hl + batch_trailer(kind));
-    if (*total > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    {
-        ProfScope ps(c, ZNGAMD_K_GATHER);
-        hipLaunchKernelGGL(za_k_batch_frame, dim3(n), dim3(64), 0, c->stream, d_in, c->bt_items.p, n, c->bt_first.p, nu, c->bt_uoff.p, c->bt_ucrc.p,
-                           c->bt_total.p, c->bt_def.p, kind, head, hl, d_out, out_cap, d_res);
-    }
-    HIPCHK(c, hipGetLastError());
-    std::vector<ZaBatchItem> back(n);
-    HIPCHK(c, hipMemcpyAsync(back.data(), c->bt_items.p, (size_t)n * sizeof(ZaBatchItem), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint32_t i = 0; i < n; i++) items[i].out_off = back[i].out_off;
-    return ZNGAMD_OK;
+    return zngamd_inflate_batch_dict_dev(c, d_in, in_len, d_items, n, wbits, nullptr, 0, count_only, d_out, out_cap, d_results);
 }
 
-int zngamd_deflate_batch_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
-                             int strategy, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results, uint64_t *total)
-try {
-    if (!c || !total || (n && (!d_in || !items || !d_out || !d_results))) return ZNGAMD_E_ARG;
-    std::lock_guard<std::mutex> g(c->mu);
-    const int r = deflate_batch_locked(c, (const uint8_t *)d_in, in_len, items, n, level, wbits, strategy, (uint8_t *)d_out, out_cap,
-                                       (ZaBatchResult *)d_results, total);
-    if (r) return r;
-    prof_collect(c);
-    return ZNGAMD_OK;
-} ZA_ABI_GUARD
-
-int zngamd_deflate_batch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
-                         int strategy, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results, uint64_t *total)
-try {
-    if (!c || (!in && in_len) || !total || (n && (!items || !results || !alloc))) return ZNGAMD_E_ARG;
-    *total = 0;
-    std::lock_guard<std::mutex> g(c->mu);
-    int kind, wb;
-    if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
-    if (batch_deflate_container(wbits, &kind, &wb)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
-    if (n == 0) return ZNGAMD_OK;
-    int r = stage_in(c, in, in_len);
-    if (r) return r;
-    uint64_t cap = 64 + (uint64_t)n * 18;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint64_t U = items[i].in_len <= ZA_MAX_UNIT ? ZA_SMALL_UNIT : ZA_MAX_UNIT;
-        cap += items[i].in_len + 32 * std::max<uint64_t>(1, (items[i].in_len + U - 1) / U);
-    }
-    HIPCHK(c, c->bt_out.ensure(cap)); HIPCHK(c, c->bt_res.ensure(n));
-    r = deflate_batch_locked(c, c->st_in.p, in_len, items, n, level, wbits, strategy, c->bt_out.p, cap, c->bt_res.p, total);
-    if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(results, c->bt_res.p, (size_t)n * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
-    uint8_t *dst = (uint8_t *)alloc(user, *total);
-    if (!dst && *total) { (void)hipStreamSynchronize(c->stream); return fail(c, ZNGAMD_MEM_ERROR, "cannot allocate the output"); }
-    if (*total) { const int rc_ = d2h_payload(c, dst, c->bt_out.p, *total); if (rc_) return rc_; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
-} ZA_ABI_GUARD
-
-// Compress with a dictionary: every item is the stream compressobj(level, DEFLATED, wbits, strategy=..., zdict=...) writes for it.
-// za_k_batch_prime writes [tail][item] per item into bt_prime (records on 64-byte boundaries, as the stream's staged buffer), the
-// pipeline runs ONE block per item -- FINAL, 128 KiB units, dict_len = the tail, as zs_deflate_pending -- and za_k_batch_frame adds
-// the FDICT header and the Adler-32 of the item's own bytes.  Every item carries up to 32 KiB of history, so the staging and the
-// deflate workspace grow with (tail + item): the items run in ranges whose records stay under ZA_BATCH_PRIME_BUDGET.
+// One deflate block per item, the packed stream into bt_def, then the framing kernel into d_out.  items: host table (in_off, in_len
+// read; out_off written).
+//   bd == nullptr: every item is zlib_ng.compress's stream -- its block is the one zngamd_deflate_stream cuts for a one-shot call
+//     (FINAL; units of 16 KiB up to 128 KiB) and lies where the item does in d_in; the whole call is one range.
+//   bd: every item is the stream compressobj(level, DEFLATED, wbits, strategy=..., zdict=...) writes for it.  za_k_batch_prime writes
+//     [tail][item] per item into bt_prime (records on 64-byte boundaries, as the stream's staged buffer), the block is the one
+//     zs_deflate_pending runs -- FINAL, 128 KiB units, dict_len = the tail -- and the frame carries the FDICT header and the Adler-32
+//     of the item's own bytes.  Every item carries up to 32 KiB of history, so the staging and the deflate workspace grow with
+//     (tail + item): the items run in ranges whose records stay under ZA_BATCH_PRIME_BUDGET.
 #define ZA_BATCH_PRIME_BUDGET (256ull << 20)
-static int deflate_batch_dict_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
-                                     int strategy, const BatchDict &bd, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res, uint64_t *total)
+static int deflate_batch_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                                int strategy, const BatchDict *bd, uint8_t *d_out, uint64_t out_cap, ZaBatchResult *d_res, uint64_t *total)
 {
     *total = 0;
     int kind, wb;
     if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
     if (batch_deflate_container(wbits, &kind, &wb)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
-    if (kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
+    if (bd && kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
     if (strategy < ZNGAMD_STRATEGY_DEFAULT || strategy > ZNGAMD_STRATEGY_FIXED) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression strategy");
     if (n == 0) return ZNGAMD_OK;
-    for (uint32_t i = 0; i < n; i++)
-        if (items[i].in_off > in_len || in_len - items[i].in_off < items[i].in_len) return fail(c, ZNGAMD_E_ARG, "block outside the input buffer");
+    if (bd)         // (build_units sees the primed records, not the items)
+        for (uint32_t i = 0; i < n; i++)
+            if (items[i].in_off > in_len || in_len - items[i].in_off < items[i].in_len) return fail(c, ZNGAMD_E_ARG, "block outside the input buffer");
     HIPCHK(c, hipSetDevice(c->device));
-    ZaBatchFrameHdr head;
-    const uint32_t hl = batch_header_dict(kind, level, wb, bd.dictid, &head), ovh = hl + batch_trailer(kind);
-    HIPCHK(c, c->bt_items.ensure(n));
-    HIPCHK(c, hipMemcpyAsync(c->bt_items.p, items, (size_t)n * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));  // (the frame's table: the items' own bytes)
-    std::vector<ZaBatchItem> pt(n), back(n);
+    ZaBatchFrameHdr head = {};
+    const uint32_t hl = container_header(kind, level, wb, bd ? &bd->dictid : nullptr, head.b), ovh = hl + batch_trailer(kind);
+    const uint32_t tl = bd ? bd->tl : 0;
+    const uint32_t flags = ZNGAMD_FLAG_FINAL | ZNGAMD_FLAG_STRATEGY(strategy) | (bd ? ZNGAMD_FLAG_WBITS(wb) : 0u);
+    std::vector<ZaBatchItem> pt(bd ? n : 0);        // the prime kernel's table: where each record lies in bt_prime
     uint64_t base = 0;
     bool fits = true;
     for (uint32_t a = 0; a < n;) {
-        // the range [a, b): records of (tail + item) rounded up to 64 bytes, under the budget (a larger item goes alone)
-        uint64_t plen = 0;
-        uint32_t b = a;
-        for (; b < n; b++) {
-            const uint64_t rl = ((uint64_t)bd.tl + items[b].in_len + 63) & ~63ull;
-            if (b > a && plen + rl > ZA_BATCH_PRIME_BUDGET) break;
-            pt[b].in_off = items[b].in_off; pt[b].in_len = items[b].in_len; pt[b].out_off = plen; pt[b].out_cap = 0;
-            pt[b].reserved[0] = pt[b].reserved[1] = 0;
-            plen += rl;
+        // the range [a, b) and the buffer its blocks lie in
+        uint32_t b = n;
+        const uint8_t *src = d_in;
+        uint64_t src_len = in_len;
+        if (bd) {
+            // records of (tail + item) rounded up to 64 bytes, under the budget (a larger item goes alone)
+            src_len = 0;
+            for (b = a; b < n; b++) {
+                const uint64_t rl = ((uint64_t)tl + items[b].in_len + 63) & ~63ull;
+                if (b > a && src_len + rl > ZA_BATCH_PRIME_BUDGET) break;
+                pt[b].in_off = items[b].in_off; pt[b].in_len = items[b].in_len; pt[b].out_off = src_len; pt[b].out_cap = 0;
+                pt[b].reserved[0] = pt[b].reserved[1] = 0;
+                src_len += rl;
+            }
+            HIPCHK(c, c->bt_prime.ensure(src_len + 64)); HIPCHK(c, c->bt_items2.ensure(b - a));
+            HIPCHK(c, hipMemcpyAsync(c->bt_items2.p, pt.data() + a, (size_t)(b - a) * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
+            {
+                ProfScope ps(c, ZNGAMD_K_GATHER);
+                hipLaunchKernelGGL(za_k_batch_prime, dim3(b - a), dim3(64), 0, c->stream, d_in, in_len, c->bt_items2.p, b - a, bd->d_tail, tl, c->bt_prime.p,
+                                   src_len + 64);
+            }
+            HIPCHK(c, hipGetLastError());
+            src = c->bt_prime.p;
         }
         const uint32_t m = b - a;
-        HIPCHK(c, c->bt_prime.ensure(plen + 64)); HIPCHK(c, c->bt_items2.ensure(m));
-        HIPCHK(c, hipMemcpyAsync(c->bt_items2.p, pt.data() + a, (size_t)m * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
-        {
-            ProfScope ps(c, ZNGAMD_K_GATHER);
-            hipLaunchKernelGGL(za_k_batch_prime, dim3(m), dim3(64), 0, c->stream, d_in, in_len, c->bt_items2.p, m, bd.d_tail, bd.tl, c->bt_prime.p, plen + 64);
-        }
-        HIPCHK(c, hipGetLastError());
         std::vector<zngamd_block> blocks(m);
         for (uint32_t k = 0; k < m; k++) {
             zngamd_block &B = blocks[k];
-            B.off = pt[a + k].out_off + bd.tl; B.len = items[a + k].in_len; B.dict_len = bd.tl; B.reserved = 0;
-            B.flags = ZNGAMD_FLAG_FINAL | ZNGAMD_FLAG_WBITS(wb) | ZNGAMD_FLAG_STRATEGY(strategy);
+            B.off = bd ? pt[a + k].out_off + tl : items[a + k].in_off; B.len = items[a + k].in_len; B.dict_len = tl; B.reserved = 0;
+            // (the one-shot's 16 KiB units without a dictionary, the stream's 128 KiB ones with it: each is what byte identity needs)
+            B.flags = flags | (!bd && B.len <= ZA_MAX_UNIT ? ZNGAMD_FLAG_UNITS16K : 0u);
         }
         std::vector<ZaUnit> hu;
-        int r = build_units(c, blocks.data(), m, plen, hu);
+        int r = build_units(c, blocks.data(), m, src_len, hu);
         if (r) return r;
         const uint32_t nu = (uint32_t)hu.size();
         std::vector<uint32_t> first(m + 1, nu);
@@ -1951,10 +1834,12 @@ static int deflate_batch_dict_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_
         uint64_t bound = 64;
         for (const ZaUnit &u : hu) bound += (uint64_t)u.in_len + 32u;
         HIPCHK(c, c->bt_def.ensure(bound)); HIPCHK(c, c->bt_uoff.ensure(nu)); HIPCHK(c, c->bt_ulen.ensure(nu)); HIPCHK(c, c->bt_ucrc.ensure(nu));
-        HIPCHK(c, c->bt_total.ensure(1)); HIPCHK(c, c->bt_first.ensure(m + 1));
+        HIPCHK(c, c->bt_total.ensure(1)); HIPCHK(c, c->bt_first.ensure(m + 1)); HIPCHK(c, c->bt_items.ensure(n));
         HIPCHK(c, hipMemcpyAsync(c->bt_first.p, first.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (a == 0)     // the frame's table (the items' own bytes), for every range at once
+            HIPCHK(c, hipMemcpyAsync(c->bt_items.p, items, (size_t)n * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
         PackedDst pd; pd.d_dst = c->bt_def.p; pd.cap = bound; pd.d_unit_off = c->bt_uoff.p; pd.d_total = c->bt_total.p;
-        r = deflate_units_dev(c, c->bt_prime.p, plen, hu, level, nullptr, c->bt_ulen.p, c->bt_ucrc.p, 1 << wb, &pd, strategy);
+        r = deflate_units_dev(c, src, src_len, hu, level, nullptr, c->bt_ulen.p, c->bt_ucrc.p, 1 << wb, &pd, strategy);
         if (r) return r;
         uint64_t def_total = 0;
         std::vector<uint32_t> st(nu);
@@ -1973,9 +1858,10 @@ static int deflate_batch_dict_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_
                                    c->bt_total.p, c->bt_def.p, kind, head, hl, d_out + base, out_cap - base, d_res + a);
             }
             HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(back.data() + a, c->bt_items.p + a, (size_t)m * sizeof(ZaBatchItem), hipMemcpyDeviceToHost, c->stream));
+            std::vector<ZaBatchItem> back(m);
+            HIPCHK(c, hipMemcpyAsync(back.data(), c->bt_items.p + a, (size_t)m * sizeof(ZaBatchItem), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            for (uint32_t k = a; k < b; k++) items[k].out_off = base + back[k].out_off;
+            for (uint32_t k = 0; k < m; k++) items[a + k].out_off = base + back[k].out_off;
         }
         base += need;
         a = b;
@@ -1990,52 +1876,59 @@ int zngamd_deflate_batch_dict_dev(zngamd_ctx *c, const void *d_in, uint64_t in_l
                                   zngamd_batch_result *d_results, uint64_t *total)
 try {
     if (!c || !total || (n && (!d_in || !items || !d_out || !d_results)) || (!dict && dict_len)) return ZNGAMD_E_ARG;
-    if (!dict) return zngamd_deflate_batch_dev(c, d_in, in_len, items, n, level, wbits, strategy, d_out, out_cap, d_results, total);
     *total = 0;
     int kind, wb;
-    if (batch_deflate_container(wbits, &kind, &wb) == ZNGAMD_OK && kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
-    uint32_t dictid = 1;
+    if (dict && batch_deflate_container(wbits, &kind, &wb) == ZNGAMD_OK && kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
+    uint32_t dictid;
     int r = batch_dict_id(c, dict, dict_len, &dictid);
     if (r) return r;
     std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
     BatchDict bd;
-    r = batch_dict_upload(c, dict, dict_len, dictid, &bd);
-    if (r) return r;
-    r = deflate_batch_dict_locked(c, (const uint8_t *)d_in, in_len, items, n, level, wbits, strategy, bd, (uint8_t *)d_out, out_cap, (ZaBatchResult *)d_results, total);
+    if (dict) {
+        HIPCHK(c, hipSetDevice(c->device));
+        r = batch_dict_upload(c, dict, dict_len, dictid, &bd);
+        if (r) return r;
+    }
+    r = deflate_batch_locked(c, (const uint8_t *)d_in, in_len, items, n, level, wbits, strategy, dict ? &bd : nullptr, (uint8_t *)d_out, out_cap,
+                             (ZaBatchResult *)d_results, total);
     if (r) return r;
     prof_collect(c);
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
+
+int zngamd_deflate_batch_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                             int strategy, void *d_out, uint64_t out_cap, zngamd_batch_result *d_results, uint64_t *total)
+{
+    return zngamd_deflate_batch_dict_dev(c, d_in, in_len, items, n, level, wbits, strategy, nullptr, 0, d_out, out_cap, d_results, total);
+}
 
 int zngamd_deflate_batch_dict(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
                               int strategy, const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user,
                               zngamd_batch_result *results, uint64_t *total)
 try {
     if (!c || (!in && in_len) || !total || (n && (!items || !results || !alloc)) || (!dict && dict_len)) return ZNGAMD_E_ARG;
-    if (!dict) return zngamd_deflate_batch(c, in, in_len, items, n, level, wbits, strategy, alloc, user, results, total);
     *total = 0;
     int kind, wb;
     if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
     if (batch_deflate_container(wbits, &kind, &wb)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
-    if (kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
+    if (dict && kind == ZA_BATCH_GZIP) return fail(c, ZNGAMD_STREAM_ERROR, "Invalid dictionary");
     if (n == 0) return ZNGAMD_OK;
-    uint32_t dictid = 1;
+    uint32_t dictid;
     int r = batch_dict_id(c, dict, dict_len, &dictid);
     if (r) return r;
     std::lock_guard<std::mutex> g(c->mu);
     r = stage_in(c, in, in_len);
     if (r) return r;
     BatchDict bd;
-    r = batch_dict_upload(c, dict, dict_len, dictid, &bd);
-    if (r) return r;
-    uint64_t cap = 64 + (uint64_t)n * 18;               // (zngamd_deflate_batch's bound: 32 bytes a 16 KiB unit, more than 128 KiB units need)
+    if (dict) { r = batch_dict_upload(c, dict, dict_len, dictid, &bd); if (r) return r; }
+    // the output's bound: every item's packed deflate (32 bytes a 16 KiB unit, more than 128 KiB units need) and its framing
+    uint64_t cap = 64 + (uint64_t)n * 18;
     for (uint32_t i = 0; i < n; i++) {
         const uint64_t U = items[i].in_len <= ZA_MAX_UNIT ? ZA_SMALL_UNIT : ZA_MAX_UNIT;
         cap += items[i].in_len + 32 * std::max<uint64_t>(1, (items[i].in_len + U - 1) / U);
     }
     HIPCHK(c, c->bt_out.ensure(cap)); HIPCHK(c, c->bt_res.ensure(n));
-    r = deflate_batch_dict_locked(c, c->st_in.p, in_len, items, n, level, wbits, strategy, bd, c->bt_out.p, cap, c->bt_res.p, total);
+    r = deflate_batch_locked(c, c->st_in.p, in_len, items, n, level, wbits, strategy, dict ? &bd : nullptr, c->bt_out.p, cap, c->bt_res.p, total);
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(results, c->bt_res.p, (size_t)n * sizeof(ZaBatchResult), hipMemcpyDeviceToHost, c->stream));
     uint8_t *dst = (uint8_t *)alloc(user, *total);
@@ -2045,6 +1938,12 @@ try {
     prof_collect(c);
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
+
+int zngamd_deflate_batch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
+                         int strategy, zngamd_alloc_fn alloc, void *user, zngamd_batch_result *results, uint64_t *total)
+{
+    return zngamd_deflate_batch_dict(c, in, in_len, items, n, level, wbits, strategy, nullptr, 0, alloc, user, results, total);
+}
 
 int zngamd_inflate_raw_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, void *d_out, uint64_t out_cap, uint64_t *out_len,
                            uint64_t *in_used)

@@ -85,22 +85,19 @@ static bool zs_drain(zngamd_stream *s)
 static void zs_put(zngamd_stream_state *st, const void *p, size_t n) { const uint8_t *b = (const uint8_t *)p; st->outq.insert(st->outq.end(), b, b + n); }
 
 // ---- deflate ---------------------------------------------------------------------------------------------------------
+// (the bytes come from container_header in zng_amd.hip, which the batch API frames its items with)
 static void zs_zlib_header(zngamd_stream_state *st)
 {
     const ZsDeflate &d = st->d;
-    const int lv = d.level == -1 ? 6 : d.level;
-    const unsigned flevel = lv < 2 ? 0 : lv < 6 ? 1 : lv == 6 ? 2 : 3;
-    unsigned head = ((((unsigned)d.wb - 8u) << 4) | 8u) << 8 | (flevel << 6) | (d.has_dict ? 0x20u : 0u);
-    head += 31 - head % 31;
-    const uint8_t h[2] = {(uint8_t)(head >> 8), (uint8_t)head};
-    zs_put(st, h, 2);
-    if (d.has_dict) { const uint8_t id[4] = {(uint8_t)(d.dictid >> 24), (uint8_t)(d.dictid >> 16), (uint8_t)(d.dictid >> 8), (uint8_t)d.dictid}; zs_put(st, id, 4); }
+    uint8_t h[10];
+    const uint32_t hl = container_header(ZA_BATCH_ZLIB, d.level, d.wb, d.has_dict ? &d.dictid : nullptr, h);
+    zs_put(st, h, hl);
 }
 static void zs_gzip_header(zngamd_stream_state *st)
 {
-    const int lv = st->d.level == -1 ? 6 : st->d.level;
-    const uint8_t h[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, (uint8_t)(lv == 9 ? 2 : lv == 1 ? 4 : 0), 3};
-    zs_put(st, h, 10);
+    uint8_t h[10];
+    const uint32_t hl = container_header(ZA_BATCH_GZIP, st->d.level, st->d.wb, nullptr, h);
+    zs_put(st, h, hl);
 }
 // one engine batch: `data` primed with the 32 KiB tail; appends the raw deflate bytes to the output queue
 static int zs_deflate_batch(zngamd_stream *s, const uint8_t *data, size_t n, bool final)

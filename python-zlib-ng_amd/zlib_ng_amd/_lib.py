@@ -271,7 +271,10 @@ class _Pinned:
 
 
 def _dict_arg(zdict):
-    """(pointer, keep-alive, length) of a batch call's dictionary: never a NULL pointer, even for an empty one (NULL is "no dictionary")"""
+    """(pointer, keep-alive, length) of a batch call's dictionary: NULL and 0 for None ("no dictionary"), and never a NULL pointer for
+    an empty one"""
+    if zdict is None:
+        return None, None, 0
     n = memoryview(zdict).nbytes
     if n == 0:
         b = b"\0"
@@ -899,11 +902,13 @@ class Context:
         self._chk(self.L.zngamd_span_stats(self.h, m, 1 if reset else 0))
         return int(m[0]), int(m[1])
 
-    # ---- the batch API (batch.py); zdict: None = no dictionary, else a bytes-like shared by every item (the _dict entry points)
+    # ---- the batch API (batch.py): always the _dict entry points; zdict None = no dictionary (NULL, 0), else a bytes-like shared
+    # by every item
     def inflate_batch(self, data, items, n, wbits, zdict=None):
-        """zngamd_inflate_batch[_dict]: data = the items back to back (bytes-like), items = a ctypes array of BatchItem (out_off / out_cap
+        """zngamd_inflate_batch_dict: data = the items back to back (bytes-like), items = a ctypes array of BatchItem (out_off / out_cap
         are written).  -> (output bytes object, ctypes array of BatchResult)"""
         p, keep = _addr(data)
+        dp, dkeep, dlen = _dict_arg(zdict)
         res = (BatchResult * max(n, 1))()
         box = []
 
@@ -913,18 +918,14 @@ class Context:
             return addr.value
 
         fn = ALLOC_FN(alloc)
-        if zdict is None:
-            self._chk(self.L.zngamd_inflate_batch(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, wbits, fn, None,
-                                                  C.cast(res, C.c_void_p)))
-        else:
-            dp, dkeep, dlen = _dict_arg(zdict)
-            self._chk(self.L.zngamd_inflate_batch_dict(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, wbits, dp, dlen, fn,
-                                                       None, C.cast(res, C.c_void_p)))
+        self._chk(self.L.zngamd_inflate_batch_dict(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, wbits, dp, dlen, fn, None,
+                                                   C.cast(res, C.c_void_p)))
         return (box[0] if box else b""), res
 
     def deflate_batch(self, data, items, n, level, wbits, strategy=STRATEGY_DEFAULT, zdict=None):
-        """zngamd_deflate_batch[_dict] -> (output bytes object, ctypes array of BatchResult, total); items[i].out_off is written"""
+        """zngamd_deflate_batch_dict -> (output bytes object, ctypes array of BatchResult, total); items[i].out_off is written"""
         p, keep = _addr(data)
+        dp, dkeep, dlen = _dict_arg(zdict)
         res = (BatchResult * max(n, 1))()
         box = []
 
@@ -935,38 +936,25 @@ class Context:
 
         fn = ALLOC_FN(alloc)
         total = C.c_uint64(0)
-        if zdict is None:
-            self._chk(self.L.zngamd_deflate_batch(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, level, wbits, strategy,
-                                                  fn, None, C.cast(res, C.c_void_p), C.byref(total)))
-        else:
-            dp, dkeep, dlen = _dict_arg(zdict)
-            self._chk(self.L.zngamd_deflate_batch_dict(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, level, wbits,
-                                                       strategy, dp, dlen, fn, None, C.cast(res, C.c_void_p), C.byref(total)))
+        self._chk(self.L.zngamd_deflate_batch_dict(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, level, wbits, strategy,
+                                                   dp, dlen, fn, None, C.cast(res, C.c_void_p), C.byref(total)))
         return (box[0] if box else b""), res, total.value
 
     def inflate_batch_dev(self, d_in, in_len, d_items, n, wbits, count_only, d_out, out_cap, d_results, zdict=None):
-        """zngamd_inflate_batch[_dict]_dev on device pointers (ints or c_void_p); the results stay in d_results."""
+        """zngamd_inflate_batch_dict_dev on device pointers (ints or c_void_p); the results stay in d_results."""
         v = lambda x: C.c_void_p(int(x)) if x else None
-        if zdict is None:
-            self._chk(self.L.zngamd_inflate_batch_dev(self.h, v(d_in), in_len, v(d_items), n, wbits, 1 if count_only else 0, v(d_out),
-                                                      out_cap, v(d_results)))
-        else:
-            dp, dkeep, dlen = _dict_arg(zdict)
-            self._chk(self.L.zngamd_inflate_batch_dict_dev(self.h, v(d_in), in_len, v(d_items), n, wbits, dp, dlen, 1 if count_only else 0,
-                                                           v(d_out), out_cap, v(d_results)))
+        dp, dkeep, dlen = _dict_arg(zdict)
+        self._chk(self.L.zngamd_inflate_batch_dict_dev(self.h, v(d_in), in_len, v(d_items), n, wbits, dp, dlen, 1 if count_only else 0,
+                                                       v(d_out), out_cap, v(d_results)))
 
     def deflate_batch_dev(self, d_in, in_len, items, n, level, wbits, strategy, d_out, out_cap, d_results, zdict=None):
-        """zngamd_deflate_batch[_dict]_dev: items = a HOST ctypes array of BatchItem (out_off written) -> (code, total); code OK or
+        """zngamd_deflate_batch_dict_dev: items = a HOST ctypes array of BatchItem (out_off written) -> (code, total); code OK or
         BUF_ERROR (total = the size needed)"""
         v = lambda x: C.c_void_p(int(x)) if x else None
+        dp, dkeep, dlen = _dict_arg(zdict)
         total = C.c_uint64(0)
-        if zdict is None:
-            r = self._chk(self.L.zngamd_deflate_batch_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy,
-                                                          v(d_out), out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
-        else:
-            dp, dkeep, dlen = _dict_arg(zdict)
-            r = self._chk(self.L.zngamd_deflate_batch_dict_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy,
-                                                               dp, dlen, v(d_out), out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
+        r = self._chk(self.L.zngamd_deflate_batch_dict_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy,
+                                                           dp, dlen, v(d_out), out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
         return r, total.value
 
     # ---- measurement

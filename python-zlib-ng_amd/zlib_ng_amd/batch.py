@@ -79,10 +79,15 @@ def _check_errors(errors):
         raise ValueError(f"errors must be 'raise' or 'return', not {errors!r}")
 
 
+def _inflate_wbits(w):
+    """wbits zlib_ng.decompress / decompressobj accept"""
+    return w == 0 or 8 <= w <= 15 or -15 <= w <= -8 or 24 <= w <= 31 or w == 16 or 40 <= w <= 47 or w == 32
+
+
 def _inflate_kind(wbits):
     if not isinstance(wbits, int):
         raise TypeError(f"an integer is required (got type {type(wbits).__name__})")
-    if not (wbits == 0 or 8 <= wbits <= 15 or -15 <= wbits <= -8 or 24 <= wbits <= 31 or wbits == 16 or 40 <= wbits <= 47 or wbits == 32):
+    if not _inflate_wbits(wbits):
         raise _z._zerr(_lib.STREAM_ERROR, "while preparing to decompress data")
 
 
@@ -91,9 +96,6 @@ def _check_strategy(strategy):
         raise TypeError(f"an integer is required (got type {type(strategy).__name__})")
     if not _lib.STRATEGY_DEFAULT <= strategy <= _lib.STRATEGY_FIXED:
         raise ValueError("Invalid initialization option")
-
-
-_INFLATE_WBITS = lambda w: w == 0 or 8 <= w <= 15 or -15 <= w <= -8 or 24 <= w <= 31 or w == 16 or 40 <= w <= 47 or w == 32
 
 
 def _zdict_compress_args(level, wbits, strategy, zdict):
@@ -118,7 +120,7 @@ def _zdict_decompress_args(wbits, zdict):
     if not isinstance(wbits, int):
         raise TypeError(f"'{type(wbits).__name__}' object cannot be interpreted as an integer")
     z = bytes(_z._view(zdict))
-    if not _INFLATE_WBITS(wbits):
+    if not _inflate_wbits(wbits):
         raise ValueError("Invalid initialization option")
     return z
 
@@ -134,6 +136,15 @@ def _zdict_reference(view, wbits, zdict):
 
 def _views(items):
     return [_z._view(x) for x in items]
+
+
+def _split(views, limit):
+    """the items the engine takes -- all of them (limit None), else those under `limit` bytes -> (their indices, views, sizes)"""
+    if limit is None:
+        return range(len(views)), views, [v.nbytes for v in views]
+    idx = [i for i, v in enumerate(views) if v.nbytes < limit]
+    sv = [views[i] for i in idx]
+    return idx, sv, [v.nbytes for v in sv]
 
 
 def _sub_batches(sizes, budget):
@@ -173,49 +184,32 @@ def compress(items, level=Z_DEFAULT_COMPRESSION, wbits=MAX_WBITS, *, strategy=Z_
     (a bytes-like; its last 32 KiB are the history of every item) each result is what compressobj(level, DEFLATED, wbits,
     DEF_MEM_LEVEL, strategy, zdict) writes for the item."""
     views = _views(items)
-    if zdict is not None:
-        return _compress_zdict(views, level, wbits, strategy, _zdict_compress_args(level, wbits, strategy, zdict))
-    _z._check_level(level)
-    _z._container(wbits)
-    _check_strategy(strategy)
+    if zdict is None:
+        _z._check_level(level)
+        _z._container(wbits)
+        _check_strategy(strategy)
+    else:
+        zdict = _zdict_compress_args(level, wbits, strategy, zdict)
     if not views:
         return []
     ctx = _z._ctx()
-    sizes = [v.nbytes for v in views]
     res = [None] * len(views)
-    for a, b in _sub_batches(sizes, SUB_BATCH_BYTES):
-        data = b"".join(views[a:b])
+    # with a dictionary an item of ZS_BATCH bytes or more is compressobj's, and every item is staged behind its own copy of the
+    # dictionary's tail: a sub-batch is bounded by its primed bytes
+    idx, sv, sizes = _split(views, None if zdict is None else ZS_BATCH)
+    tl = 0 if zdict is None else min(len(zdict), 32768)
+    for a, b in _sub_batches([s + tl for s in sizes] if tl else sizes, SUB_BATCH_BYTES):
         tab, items_c = _table(sizes[a:b])
-        out, rs, total = ctx.deflate_batch(data, items_c, b - a, level, wbits, strategy)
+        out, rs, _ = ctx.deflate_batch(b"".join(sv[a:b]), items_c, b - a, level, wbits, strategy, zdict=zdict)
         mv = memoryview(out)
         _, lens = _results(rs, b - a)
-        for k, (o, ln) in enumerate(zip(tab[:b - a, 1].tolist(), lens)):
-            res[a + k] = bytes(mv[o:o + ln])
-    return res
-
-
-def _compress_zdict(views, level, wbits, strategy, zb):
-    if not views:
-        return []
-    ctx = _z._ctx()
-    res = [None] * len(views)
-    tl = min(len(zb), 32768)
-    small = [i for i, v in enumerate(views) if v.nbytes < ZS_BATCH]
-    lens = [views[i].nbytes for i in small]
-    # every item is staged behind its own copy of the dictionary's tail: a sub-batch is bounded by its primed bytes
-    for a, b in _sub_batches([ln + tl for ln in lens], SUB_BATCH_BYTES):
-        idx = small[a:b]
-        data = b"".join(views[i] for i in idx)
-        tab, items_c = _table(lens[a:b])
-        out, rs, total = ctx.deflate_batch(data, items_c, b - a, level, wbits, strategy, zdict=zb)
-        mv = memoryview(out)
-        _, olens = _results(rs, b - a)
-        for i, o, ln in zip(idx, tab[:b - a, 1].tolist(), olens):
+        for i, o, ln in zip(idx[a:b], tab[:b - a, 1].tolist(), lens):
             res[i] = bytes(mv[o:o + ln])
-    for i, v in enumerate(views):
-        if v.nbytes >= ZS_BATCH:
-            c = _z.compressobj(level, _z.DEFLATED, wbits, _z.DEF_MEM_LEVEL, strategy, zb)
-            res[i] = c.compress(v) + c.flush()
+    if zdict is not None:
+        for i, v in enumerate(views):
+            if v.nbytes >= ZS_BATCH:
+                c = _z.compressobj(level, _z.DEFLATED, wbits, _z.DEF_MEM_LEVEL, strategy, zdict)
+                res[i] = c.compress(v) + c.flush()
     return res
 
 
@@ -239,56 +233,31 @@ def decompress(items, wbits=MAX_WBITS, *, errors="raise", zdict=None):
     (a zlib item with FDICT and a raw item decode with the dictionary; an unfinished stream is "incomplete or truncated stream")."""
     _check_errors(errors)
     views = _views(items)
-    if zdict is not None:
-        return _raise_first(_decompress_zdict(views, wbits, _zdict_decompress_args(wbits, zdict)), errors)
-    _inflate_kind(wbits)
+    if zdict is None:
+        _inflate_kind(wbits)
+        large = lambda v: _z.decompress(v, wbits)
+    else:
+        zdict = _zdict_decompress_args(wbits, zdict)
+        large = lambda v: _zdict_reference(v, wbits, zdict)
     if not views:
         return []
     ctx = _z._ctx()
     res = [None] * len(views)
-    small = [i for i, v in enumerate(views) if v.nbytes < LARGE_ITEM]
-    sizes = [views[i].nbytes for i in small]
+    idx, sv, sizes = _split(views, LARGE_ITEM)
     for a, b in _sub_batches(sizes, SUB_BATCH_BYTES):
-        idx = small[a:b]
-        data = b"".join(views[i] for i in idx)
         tab, items_c = _table(sizes[a:b])
-        out, rs = ctx.inflate_batch(data, items_c, b - a, wbits)
+        out, rs = ctx.inflate_batch(b"".join(sv[a:b]), items_c, b - a, wbits, zdict=zdict)
         mv = memoryview(out)
         sts, lens = _results(rs, b - a)
-        for i, o, st, ln in zip(idx, tab[:b - a, 1].tolist(), sts, lens):
+        for i, o, st, ln in zip(idx[a:b], tab[:b - a, 1].tolist(), sts, lens):
             res[i] = bytes(mv[o:o + ln]) if st == _lib.BATCH_OK else _with_index(status_error(st), i)
     for i, v in enumerate(views):
         if v.nbytes >= LARGE_ITEM:
             try:
-                res[i] = _z.decompress(v, wbits)
+                res[i] = large(v)
             except Exception as e:          # the single-stream path's own verdict, as the one-shot gives it
                 res[i] = _with_index(e, i)
     return _raise_first(res, errors)
-
-
-def _decompress_zdict(views, wbits, zb):
-    if not views:
-        return []
-    ctx = _z._ctx()
-    res = [None] * len(views)
-    small = [i for i, v in enumerate(views) if v.nbytes < LARGE_ITEM]
-    sizes = [views[i].nbytes for i in small]
-    for a, b in _sub_batches(sizes, SUB_BATCH_BYTES):
-        idx = small[a:b]
-        data = b"".join(views[i] for i in idx)
-        tab, items_c = _table(sizes[a:b])
-        out, rs = ctx.inflate_batch(data, items_c, b - a, wbits, zdict=zb)
-        mv = memoryview(out)
-        sts, lens = _results(rs, b - a)
-        for i, o, st, ln in zip(idx, tab[:b - a, 1].tolist(), sts, lens):
-            res[i] = bytes(mv[o:o + ln]) if st == _lib.BATCH_OK else _with_index(status_error(st), i)
-    for i, v in enumerate(views):
-        if v.nbytes >= LARGE_ITEM:
-            try:
-                res[i] = _zdict_reference(v, wbits, zb)
-            except Exception as e:
-                res[i] = _with_index(e, i)
-    return res
 
 
 # ---- device-resident forms

@@ -230,3 +230,117 @@ def test_sub_batches_give_the_same_results(mods, monkeypatch):
     monkeypatch.setattr(batch, "SUB_BATCH_BYTES", 100000)
     assert batch.compress(items, 6, 31) == c_whole
     assert batch.decompress(c_whole, 31) == d_whole == items
+
+
+def test_plain_entry_points_are_the_dict_forms_without_one(mods):
+    """zngamd_{inflate,deflate}_batch[_dev] (the binding calls only the _dict forms) give what the _dict forms give with NULL / 0:
+    the same return code and message, output bytes, results, item table and total, on a small mixed set and on refused calls"""
+    _lib, batch, corpus, devmem, zlib_ng = mods
+    ctx = _lib.default_context()
+    L, h = ctx.L, ctx.h
+    vp = lambda b: C.cast(C.c_char_p(b), C.c_void_p)
+    items = _mixed(corpus, 100, seed=13)
+    lens = [len(x) for x in items]
+    flat = b"".join(items)
+    n = len(items)
+
+    def host(call, data, lens):
+        """-> (code, message, item table, per item (status, out_len, its output if OK), total)"""
+        tab, items_c = batch._table(lens)
+        res = (_lib.BatchResult * max(len(lens), 1))()
+        box = []
+
+        def alloc(_user, nbytes):
+            obj, addr = _lib._new_bytes(nbytes)
+            box.append(obj)
+            return addr.value
+
+        fn = _lib.ALLOC_FN(alloc)
+        total = C.c_uint64(7)
+        r = call(vp(data), len(data), C.cast(items_c, C.c_void_p), len(lens), fn, C.cast(res, C.c_void_p), C.byref(total))
+        out = box[0] if box else b""
+        per = [(res[k].status, res[k].out_len,
+                out[int(tab[k, 1]):int(tab[k, 1]) + res[k].out_len] if r == _lib.OK and res[k].status == _lib.BATCH_OK else None)
+               for k in range(len(lens))]
+        return r, ctx.err() if r else "", tab[:len(lens)].tolist(), per, total.value
+
+    # host deflate: good calls, a bad level, a bad strategy, a bad wbits
+    for level, wbits, strategy in ((6, 15, 0), (1, 31, zlib.Z_RLE), (9, -15, 0), (10, 15, 0), (6, 15, 9), (6, 17, 0)):
+        plain = host(lambda d, dl, it, k, fn, res, tot: L.zngamd_deflate_batch(h, d, dl, it, k, level, wbits, strategy, fn, None, res, tot),
+                     flat, lens)
+        nulld = host(lambda d, dl, it, k, fn, res, tot: L.zngamd_deflate_batch_dict(h, d, dl, it, k, level, wbits, strategy, None, 0, fn, None,
+                                                                                     res, tot), flat, lens)
+        assert plain == nulld, (level, wbits, strategy)
+        assert (plain[0] == _lib.OK) == (level <= 9 and strategy <= zlib.Z_FIXED and wbits != 17)
+
+    # host inflate: good and broken items, automatic detection, a bad wbits
+    comp = batch.compress(items, 6, 31)
+    comp[3] = comp[3][:-5]
+    comp[7] = comp[7][:20] + bytes([comp[7][20] ^ 0x55]) + comp[7][21:]
+    comp[11] = b"\x00" * 30
+    cflat = b"".join(comp)
+    clens = [len(x) for x in comp]
+    for wbits in (31, 47, 15, 7):
+        plain = host(lambda d, dl, it, k, fn, res, tot: L.zngamd_inflate_batch(h, d, dl, it, k, wbits, fn, None, res), cflat, clens)
+        nulld = host(lambda d, dl, it, k, fn, res, tot: L.zngamd_inflate_batch_dict(h, d, dl, it, k, wbits, None, 0, fn, None, res),
+                     cflat, clens)
+        assert plain == nulld, wbits
+    assert plain[0] == _lib.STREAM_ERROR and nulld[1] == "invalid wbits"
+
+    # device deflate: fitting and too small an output, a bad strategy
+    d_in = devmem.from_host(ctx, np.frombuffer(flat + bytes(_lib.BATCH_PAD), np.uint8))
+    cap = batch._frame_bound(lens, 15)
+
+    def dev_deflate(call, out_cap, strategy):
+        items_c = (_lib.BatchItem * n)()
+        for k, (o, ln) in enumerate(zip(np.cumsum([0] + lens[:-1]).tolist(), lens)):
+            items_c[k].in_off, items_c[k].in_len = o, ln
+        d_out = devmem.DeviceBuffer(ctx, cap)
+        d_out[:] = 0
+        d_res = devmem.DeviceBuffer(ctx, 16 * n)
+        d_res[:] = 0
+        total = C.c_uint64(7)
+        r = call(C.c_void_p(d_in.ptr), len(flat), C.cast(items_c, C.c_void_p), C.c_void_p(d_out.ptr), out_cap, C.c_void_p(d_res.ptr),
+                 strategy, C.byref(total))
+        return (r, ctx.err() if r else "", d_out.cpu().tobytes(), d_res.cpu().tobytes(), [items_c[k].out_off for k in range(n)],
+                total.value)
+
+    codes = []
+    for out_cap, strategy in ((cap, 0), (cap, zlib.Z_FILTERED), (100, 0), (cap, 9)):
+        plain = dev_deflate(lambda d, dl, it, o, oc, res, s, tot: L.zngamd_deflate_batch_dev(h, d, dl, it, n, 6, 15, s, o, oc, res, tot),
+                            out_cap, strategy)
+        nulld = dev_deflate(lambda d, dl, it, o, oc, res, s, tot: L.zngamd_deflate_batch_dict_dev(h, d, dl, it, n, 6, 15, s, None, 0, o, oc,
+                                                                                                 res, tot), out_cap, strategy)
+        assert plain == nulld, (out_cap, strategy)
+        codes.append(plain[0])
+    assert codes == [_lib.OK, _lib.OK, _lib.BUF_ERROR, _lib.STREAM_ERROR]
+
+    # device inflate: the count pass, then a decode into exactly the counted room
+    d_c = devmem.from_host(ctx, np.frombuffer(cflat + bytes(_lib.BATCH_PAD), np.uint8))
+    sizes = [len(zlib_ng.decompress(x, 31)) if k not in (3, 7, 11) else 0 for k, x in enumerate(comp)]
+    tab = np.zeros((n, 4), dtype=np.uint64)
+    tab[:, 0] = np.cumsum([0] + clens[:-1])
+    tab[:, 1] = np.cumsum([0] + sizes[:-1])
+    tab[:, 2] = np.array(clens, dtype=np.uint64) | (np.array(sizes, dtype=np.uint64) << np.uint64(32))
+    d_tab = devmem.from_host(ctx, tab.view(np.uint8).reshape(-1))
+    room = sum(sizes)
+
+    def dev_inflate(call, count_only, wbits):
+        d_out = devmem.DeviceBuffer(ctx, room + 64)
+        d_out[:] = 0
+        d_res = devmem.DeviceBuffer(ctx, 16 * n)
+        d_res[:] = 0
+        r = call(C.c_void_p(d_c.ptr), len(cflat), C.c_void_p(d_tab.ptr), wbits, count_only,
+                 None if count_only else C.c_void_p(d_out.ptr), 0 if count_only else room, C.c_void_p(d_res.ptr))
+        return r, ctx.err() if r else "", d_out.cpu().tobytes(), d_res.cpu().tobytes()
+
+    for count_only, wbits in ((1, 31), (0, 31), (0, 47), (0, 3)):
+        plain = dev_inflate(lambda d, dl, t, w, co, o, oc, res: L.zngamd_inflate_batch_dev(h, d, dl, t, n, w, co, o, oc, res), count_only, wbits)
+        nulld = dev_inflate(lambda d, dl, t, w, co, o, oc, res: L.zngamd_inflate_batch_dict_dev(h, d, dl, t, n, w, None, 0, co, o, oc, res),
+                            count_only, wbits)
+        assert plain == nulld, (count_only, wbits)
+        if (count_only, wbits) == (0, 31):
+            st = np.frombuffer(plain[3], np.uint32).reshape(-1, 4)[:, 0]
+            assert [k for k in range(n) if st[k] != _lib.BATCH_OK] == [3, 7, 11]
+            assert plain[2][:room] == b"".join(x for k, x in enumerate(items) if k not in (3, 7, 11))
+    assert plain[0] == _lib.STREAM_ERROR and plain[1] == "invalid wbits"
