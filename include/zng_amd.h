@@ -331,6 +331,16 @@ int zngamd_deflate_batch_dict_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in
 int zngamd_deflate_batch_dict(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, zngamd_batch_item *items, uint32_t n, int level, int wbits,
                               int strategy, const uint8_t *dict, uint32_t dict_len, zngamd_alloc_fn alloc, void *user,
                               zngamd_batch_result *results, uint64_t *total);
+/* A preset dictionary trained from sample records (a deterministic FastCOVER variant; segments of k bytes
+ * scored by the d-mers, 4 <= d <= 8, they share with all samples).  The samples are the items in table order (in_off, in_len read);
+ * d_in holds ZNGAMD_BATCH_PAD readable bytes behind in_len, d_items lies in device memory.  dict: HOST memory of dict_size bytes, the
+ * result fills dict[0 .. *dict_len), *dict_len <= dict_size; it depends only on the sample bytes, their order and the parameters.
+ * ZNGAMD_E_ARG before any device work unless n >= 1, d <= dict_size <= 32768, 4 <= d <= 8 and d <= k <= 16384; ZNGAMD_E_ARG also for an
+ * item outside [0, in_len) or samples that add up to fewer than k bytes or to 4 GiB or more (nothing written to dict). */
+int zngamd_train_dict_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n,
+                          uint32_t dict_size, uint32_t k, uint32_t d, uint8_t *dict, uint32_t *dict_len);
+int zngamd_train_dict(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_batch_item *items, uint32_t n,
+                      uint32_t dict_size, uint32_t k, uint32_t d, uint8_t *dict, uint32_t *dict_len);
 
 /* One raw deflate stream that lies in device memory (d_in must be readable 64 bytes past in_len), decoded into device
  * memory: chunk-parallel where the stream offers block boundaries (sync-flush points, dynamic block headers), else on one

@@ -9,6 +9,7 @@
 #include "za_inflate_units.hip"
 #include "za_inflate_spans.hip"
 #include "za_batch.hip"
+#include "za_dict.hip"
 #include "za_checksum.hip"
 #include "../../include/zng_amd.h"
 
@@ -110,6 +111,8 @@ struct zngamd_ctx {
     DevBuf<uint8_t> bt_out, bt_out2, bt_def; DevBuf<ZaBatchItem> bt_items, bt_items2; DevBuf<ZaBatchResult> bt_res, bt_res2;    // the batch API (za_batch.hip)
     DevBuf<uint32_t> bt_first, bt_ulen, bt_ucrc; DevBuf<uint64_t> bt_uoff, bt_total;
     DevBuf<uint8_t> bt_dict, bt_prime;           // the batch API with a dictionary: its kept tail, the primed items ([tail][item] each)
+    DevBuf<uint8_t> dt_data, dt_dict; DevBuf<uint32_t> dt_hash, dt_freq; DevBuf<uint16_t> dt_shadow;      // the dictionary trainer (za_dict.hip)
+    DevBuf<ZaBatchItem> dt_items; DevBuf<ZaDictBest> dt_best; DevBuf<ZaDictState> dt_state;
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
     uint8_t *h_tab = nullptr; size_t h_tab_cap = 0;
@@ -249,6 +252,8 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->bt_out.release(); c->bt_out2.release(); c->bt_def.release(); c->bt_items.release(); c->bt_items2.release(); c->bt_res.release(); c->bt_res2.release();
     c->bt_first.release(); c->bt_ulen.release(); c->bt_ucrc.release(); c->bt_uoff.release(); c->bt_total.release();
     c->bt_dict.release(); c->bt_prime.release();
+    c->dt_data.release(); c->dt_dict.release(); c->dt_hash.release(); c->dt_freq.release(); c->dt_shadow.release();
+    c->dt_items.release(); c->dt_best.release(); c->dt_state.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -1944,6 +1949,121 @@ int zngamd_deflate_batch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, znga
 {
     return zngamd_deflate_batch_dict(c, in, in_len, items, n, level, wbits, strategy, nullptr, 0, alloc, user, results, total);
 }
+
+// ---- the batch API's dictionary trainer (za_dict.hip)
+static bool train_args_ok(uint32_t n, uint32_t dict_size, uint32_t k, uint32_t d)
+{
+    return n && d >= 4 && d <= 8 && k >= d && k <= 16384 && dict_size >= d && dict_size <= ZA_WIN;
+}
+
+// items: a HOST copy of the table.  Every entry must lie inside [0, in_len) and the samples must add up to [k, 4 GiB); out_off
+// becomes each one's place in the joined samples, *total their sum.
+static int train_table(zngamd_ctx *c, std::vector<ZaBatchItem> &items, uint64_t in_len, uint32_t k, uint64_t *total)
+{
+    uint64_t t = 0;
+    for (auto &it : items) {
+        if (it.in_off > in_len || in_len - it.in_off < it.in_len) return fail(c, ZNGAMD_E_ARG, "a sample lies outside the input buffer");
+        it.out_off = t;
+        t += it.in_len;
+    }
+    if (t < k || t >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "the samples must hold at least k and less than 4 GiB bytes");
+    *total = t;
+    return ZNGAMD_OK;
+}
+
+// (under the lock) d_in: device, ZNGAMD_BATCH_PAD readable bytes behind in_len; items: the checked table (train_table)
+static int train_dict_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const std::vector<ZaBatchItem> &items, uint64_t total,
+                             uint32_t dict_size, uint32_t k, uint32_t d, uint8_t *dict, uint32_t *dict_len)
+{
+    const uint32_t n_items = (uint32_t)items.size(), n = (uint32_t)(total - d + 1), K = k - d + 1;
+    uint32_t E = std::max(1u, dict_size / k / 4), S = n / E;                     // the epochs (step 4)
+    if (S < 10u * k) { E = std::max(1u, n / (10u * k)); S = n / E; }
+    if (S < K) return ZNGAMD_OK;
+    const uint32_t ntiles = (S - K + 1 + ZA_DICT_TILE - 1) / ZA_DICT_TILE;
+    HIPCHK(c, c->dt_items.ensure(n_items)); HIPCHK(c, c->dt_data.ensure(total + 64)); HIPCHK(c, c->dt_hash.ensure(n));
+    HIPCHK(c, c->dt_shadow.ensure(n)); HIPCHK(c, c->dt_freq.ensure(1u << ZA_DICT_HASH_BITS)); HIPCHK(c, c->dt_best.ensure(ntiles));
+    HIPCHK(c, c->dt_state.ensure(1)); HIPCHK(c, c->dt_dict.ensure(dict_size));
+    HIPCHK(c, hipMemcpyAsync(c->dt_items.p, items.data(), (size_t)n_items * sizeof(ZaBatchItem), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->dt_data.p + total, 0, 64, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->dt_freq.p, 0, sizeof(uint32_t) << ZA_DICT_HASH_BITS, c->stream));
+    ZaDictState hs = {dict_size, 0, 0, 0, 0, {0, 0, 0}};
+    HIPCHK(c, hipMemcpyAsync(c->dt_state.p, &hs, sizeof hs, hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, ZNGAMD_K_OTHER);
+        const uint32_t hb = (uint32_t)(((uint64_t)n + 4095) / 4096), lim = E * S;
+        hipLaunchKernelGGL(za_k_dict_gather, dim3(n_items), dim3(64), 0, c->stream, d_in, in_len, c->dt_items.p, n_items, c->dt_data.p, total);
+        hipLaunchKernelGGL(za_k_dict_hash, dim3(hb), dim3(256), 0, c->stream, c->dt_data.p, n, d, c->dt_hash.p);
+        hipLaunchKernelGGL(za_k_dict_mark, dim3((n_items + 255) / 256), dim3(256), 0, c->stream, c->dt_items.p, n_items, n, d, c->dt_hash.p);
+        hipLaunchKernelGGL(za_k_dict_count, dim3(hb), dim3(256), 0, c->stream, c->dt_hash.p, n, c->dt_freq.p);
+        const bool lds = K - 1 + ZA_DICT_SH_TILE <= ZA_DICT_SH_LDS;
+        hipLaunchKernelGGL(lds ? za_k_dict_shadow<true> : za_k_dict_shadow<false>, dim3((lim + ZA_DICT_SH_TILE - 1) / ZA_DICT_SH_TILE), dim3(256),
+                           lds ? (K - 1 + ZA_DICT_SH_TILE) * sizeof(uint32_t) : 0, c->stream, c->dt_hash.p, lim, S, K, c->dt_shadow.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    // the pick loop (step 6) in groups of launches; a pick after the last returns at once.  Every pick but the last shortens the tail
+    // by at least d bytes or is one of at most E - 1 zero picks in a row: the loop ends within (dict_size / d + 1) E picks.
+    const uint64_t bound = ((uint64_t)dict_size / d + 1) * E;
+    uint64_t launched = 0;
+    for (uint32_t group = 32;; group = std::min(group * 2, 512u)) {
+        ProfScope ps(c, ZNGAMD_K_OTHER);
+        for (uint32_t g = 0; g < group; g++) {
+            hipLaunchKernelGGL(za_k_dict_score, dim3(ntiles), dim3(256), 0, c->stream, c->dt_hash.p, c->dt_shadow.p, c->dt_freq.p, S, K,
+                               c->dt_state.p, c->dt_best.p);
+            hipLaunchKernelGGL(za_k_dict_pick, dim3(1), dim3(256), 0, c->stream, c->dt_data.p, c->dt_hash.p, c->dt_freq.p, c->dt_best.p,
+                               ntiles, S, K, E, d, c->dt_state.p, c->dt_dict.p);
+        }
+        HIPCHK(c, hipGetLastError());
+        launched += group;
+        HIPCHK(c, hipMemcpyAsync(&hs, c->dt_state.p, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (hs.done) break;
+        if (launched > bound) return fail(c, ZNGAMD_E_HIP, "the dictionary trainer's pick loop did not end");
+    }
+    if (hs.tail > dict_size) return fail(c, ZNGAMD_E_HIP, "the dictionary trainer's state is corrupt");
+    if (trace_on()) fprintf(stderr, "[zngamd] train_dict: %u positions, %u epochs of %u, %u picks, %u bytes\n", n, E, S, hs.picks, dict_size - hs.tail);
+    if (hs.tail < dict_size) HIPCHK(c, hipMemcpyAsync(dict, c->dt_dict.p + hs.tail, dict_size - hs.tail, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *dict_len = dict_size - hs.tail;
+    return ZNGAMD_OK;
+}
+
+int zngamd_train_dict_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_batch_item *d_items, uint32_t n, uint32_t dict_size,
+                          uint32_t k, uint32_t d, uint8_t *dict, uint32_t *dict_len)
+try {
+    if (!c || !d_in || !d_items || !dict || !dict_len || !train_args_ok(n, dict_size, k, d)) return ZNGAMD_E_ARG;
+    *dict_len = 0;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<ZaBatchItem> items(n);
+    HIPCHK(c, hipMemcpyAsync(items.data(), d_items, (size_t)n * sizeof(ZaBatchItem), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint64_t total;
+    int r = train_table(c, items, in_len, k, &total);
+    if (r) return r;
+    r = train_dict_locked(c, (const uint8_t *)d_in, in_len, items, total, dict_size, k, d, dict, dict_len);
+    if (r) return r;
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_train_dict(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_batch_item *items, uint32_t n, uint32_t dict_size,
+                      uint32_t k, uint32_t d, uint8_t *dict, uint32_t *dict_len)
+try {
+    if (!c || !in || !items || !dict || !dict_len || !train_args_ok(n, dict_size, k, d)) return ZNGAMD_E_ARG;
+    *dict_len = 0;
+    std::vector<ZaBatchItem> tab(n);
+    memcpy(tab.data(), items, (size_t)n * sizeof(ZaBatchItem));
+    uint64_t total;
+    int r = train_table(c, tab, in_len, k, &total);
+    if (r) return r;
+    std::lock_guard<std::mutex> g(c->mu);
+    r = stage_in(c, in, in_len);
+    if (r) return r;
+    r = train_dict_locked(c, c->st_in.p, in_len, tab, total, dict_size, k, d, dict, dict_len);
+    if (r) return r;
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
 
 int zngamd_inflate_raw_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, void *d_out, uint64_t out_cap, uint64_t *out_len,
                            uint64_t *in_used)

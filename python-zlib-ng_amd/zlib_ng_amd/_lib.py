@@ -79,6 +79,7 @@ SYMBOLS = [
     "zngamd_inflate_spans_dev", "zngamd_inflate_spans", "zngamd_span_stats",
     "zngamd_inflate_batch_dev", "zngamd_inflate_batch", "zngamd_deflate_batch_dev", "zngamd_deflate_batch",
     "zngamd_inflate_batch_dict_dev", "zngamd_inflate_batch_dict", "zngamd_deflate_batch_dict_dev", "zngamd_deflate_batch_dict",
+    "zngamd_train_dict_dev", "zngamd_train_dict",
 ]
 
 
@@ -203,6 +204,10 @@ def load():
                                                     vp, C.POINTER(C.c_uint64)]
         L.zngamd_deflate_batch_dict.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, ALLOC_FN, vp,
                                                 vp, C.POINTER(C.c_uint64)]
+        L.zngamd_train_dict_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u8p,
+                                            C.POINTER(C.c_uint32)]
+        L.zngamd_train_dict.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u8p,
+                                        C.POINTER(C.c_uint32)]
         L.zngamd_compare_dev.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.zngamd_crc32_fold_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
         L.zngamd_gunzip.argtypes = [vp, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64),
@@ -956,6 +961,26 @@ class Context:
         r = self._chk(self.L.zngamd_deflate_batch_dict_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy,
                                                            dp, dlen, v(d_out), out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
         return r, total.value
+
+    def train_dict(self, data, items, n, dict_size, k, d):
+        """zngamd_train_dict: data = the samples' buffer (bytes-like), items = a ctypes array of BatchItem (in_off, in_len read)
+        -> the dictionary (bytes)"""
+        p, keep = _addr(data)
+        out = (C.c_uint8 * dict_size)()
+        ln = C.c_uint32(0)
+        self._chk(self.L.zngamd_train_dict(self.h, p, memoryview(data).nbytes, C.cast(items, C.c_void_p), n, dict_size, k, d,
+                                           C.cast(out, C.c_void_p), C.byref(ln)))
+        return bytes(out[:ln.value])
+
+    def train_dict_dev(self, d_in, in_len, d_items, n, dict_size, k, d):
+        """zngamd_train_dict_dev on device pointers (ints or c_void_p): the samples and the item table in device memory -> (code, the
+        dictionary as bytes); code OK or E_ARG (an item outside the buffer, samples outside [k, 4 GiB): no bytes)"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        out = (C.c_uint8 * dict_size)()
+        ln = C.c_uint32(0)
+        r = self._chk(self.L.zngamd_train_dict_dev(self.h, v(d_in), in_len, v(d_items), n, dict_size, k, d, C.cast(out, C.c_void_p),
+                                                   C.byref(ln)), (OK, E_ARG))
+        return r, bytes(out[:ln.value])
 
     # ---- measurement
     def profiling(self, on):

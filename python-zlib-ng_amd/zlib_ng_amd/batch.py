@@ -4,6 +4,8 @@
     batch.decompress(items, wbits=MAX_WBITS, *, errors="raise", zdict=None) -> list[bytes]
     batch.compress_dev(ctx, d_in, offsets, lengths, ...) -> (DeviceBuffer, out_offsets, out_lengths)
     batch.decompress_dev(ctx, d_in, offsets, lengths, ...) -> (DeviceBuffer, out_offsets, out_lengths, statuses)
+    batch.train_dict(samples, dict_size=32768, *, k=256, d=8) -> bytes
+    batch.train_dict_dev(ctx, d_in, offsets, lengths, dict_size=32768, *, k=256, d=8) -> bytes
 
 `compress(items, level, wbits)[i] == zlib_ng.compress(items[i], level, wbits)` byte for byte, and `decompress(items, wbits)[i] ==
 zlib_ng.decompress(items[i], wbits)`; where the one-shot raises, the batch raises the same type with the same message for the first
@@ -14,6 +16,9 @@ With a preset dictionary (zdict, one for the whole call) the yardsticks are the 
 strategy=s, zdict=d)[i] is what compressobj(level, DEFLATED, wbits, DEF_MEM_LEVEL, s, d) writes for items[i] (compress + flush), and
 decompress(items, wbits, zdict=d)[i] is decompressobj(wbits, zdict=d).decompress(items[i]), an unfinished stream being the error
 "incomplete or truncated stream".
+
+train_dict makes such a dictionary from sample records (za_dict.hip): the k-byte segments whose d-mers recur
+most across the samples, the best nearest the end.  Pass it unchanged as zdict= here, to compressobj / decompressobj or to CPython's zlib.
 """
 
 import numpy as np
@@ -338,3 +343,59 @@ def decompress_dev(ctx, d_in, offsets, lengths, wbits=MAX_WBITS, *, zdict=None):
     statuses = np.where(ok, res2[:, 0], res[:, 0]).astype(np.int32)
     lens = np.where(statuses == _lib.BATCH_OK, res2[:, 1], 0).astype(np.uint64)
     return out, offs, lens, statuses
+
+
+# ---- dictionary training
+def _train_args(lengths, dict_size, k, d):
+    """the trainer's argument checks, made before any device call"""
+    for v in (dict_size, k, d):
+        if not isinstance(v, int):
+            raise TypeError(f"an integer is required (got type {type(v).__name__})")
+    if len(lengths) == 0:
+        raise ValueError("no samples to train from")
+    if not 4 <= d <= 8:
+        raise ValueError(f"d must lie in [4, 8], not {d}")
+    if not d <= k <= 16384:
+        raise ValueError(f"k must lie in [d, 16384], not {k}")
+    if not d <= dict_size <= 32768:
+        raise ValueError(f"dict_size must lie in [d, 32768], not {dict_size}")
+    total = int(sum(int(x) for x in lengths))
+    if total < k:
+        raise ValueError(f"the samples hold {total} bytes, fewer than k = {k}")
+    if total >= 1 << 32:
+        raise ValueError("the samples hold 4 GiB or more")
+
+
+def train_dict(samples, dict_size=32768, *, k=256, d=8):
+    """A preset dictionary of at most dict_size bytes trained from `samples` (buffer-protocol objects, taken in order): segments of
+    k bytes chosen by the d-mers they share with all samples, the most useful last (shortest match distances).  The bytes depend
+    only on the samples, their order and the parameters."""
+    views = _views(samples)
+    lengths = [v.nbytes for v in views]
+    _train_args(lengths, dict_size, k, d)
+    ctx = _z._ctx()
+    _, items_c = _table(lengths)
+    return ctx.train_dict(b"".join(views), items_c, len(views), dict_size, k, d)
+
+
+def train_dict_dev(ctx, d_in, offsets, lengths, dict_size=32768, *, k=256, d=8):
+    """train_dict on samples that lie in device memory (d_in: a DeviceBuffer holding BATCH_PAD readable bytes behind the last sample;
+    offsets, lengths: the samples in it, in order).  -> the dictionary as bytes."""
+    from . import devmem
+    offsets = np.asarray(offsets, dtype=np.uint64)
+    lengths = np.asarray(lengths, dtype=np.uint64)
+    n = len(offsets)
+    if len(lengths) != n:
+        raise ValueError("offsets and lengths differ in length")
+    _train_args(lengths, dict_size, k, d)
+    in_len = max(0, d_in.nbytes - _lib.BATCH_PAD)
+    if n and (int(offsets.max()) > in_len or bool(np.any(lengths > in_len - np.minimum(offsets, in_len)))):
+        raise ValueError("a sample lies outside the device buffer")
+    tab = np.zeros((n, 4), dtype=np.uint64)                    # in_off, out_off, in_len, reserved
+    tab[:, 0] = offsets
+    tab[:, 2] = lengths
+    d_tab = devmem.from_host(ctx, tab.view(np.uint8).reshape(-1))
+    r, out = ctx.train_dict_dev(d_in.ptr, in_len, d_tab.ptr, n, dict_size, k, d)
+    if r != _lib.OK:
+        raise ValueError(ctx.err())
+    return out
