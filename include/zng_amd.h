@@ -425,6 +425,68 @@ int zngamd_gzip_members_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, 
                             int level, void *d_out, uint64_t out_cap, uint64_t *out_len,
                             uint32_t *n_members);
 
+/* ---- BGZF (SAM specification section 4.1; zlib_ng_amd/bgzf.py): gzip members of at most 64 KiB, each with its
+ * own size in a 'B','C' extra subfield, each a deflate stream of its own; a file ends with an empty block of 28 fixed bytes.  A
+ * position is a virtual offset, coffset << 16 | uoffset: the file offset of a block and a byte offset inside its output. */
+#define ZNGAMD_E_BGZF          (-107)    /* zngamd_bgzf_scan: the buffer does not start with a BGZF block */
+#define ZNGAMD_BGZF_MAX_INPUT  65280u    /* input bytes per block (htslib's 0xff00) */
+#define ZNGAMD_BGZF_MAX_BLOCK  65536u
+#define ZNGAMD_BGZF_EOF_BYTES  28u
+typedef struct {
+    uint64_t coffset;      /* offset of the block's first byte in the compressed stream */
+    uint64_t uoffset;      /* offset of its first output byte in the uncompressed data  */
+    uint32_t csize;        /* the block's bytes, header and trailer included (BSIZE + 1) */
+    uint32_t isize;        /* its output bytes (ISIZE)                                   */
+} zngamd_bgzf_block;       /* 24 B */
+/* The writer.  The input is cut into blocks of block_size bytes (1 .. ZNGAMD_BGZF_MAX_INPUT; the last one shorter; no block for no
+ * input); each is compressed on its own by the deflate kernels, one final deflate block sequence with ordinary dynamic headers, and
+ * framed by one workgroup of the assemble kernel.  A payload of more than 65 510 bytes (it would not fit a block) is replaced by one
+ * stored deflate block of the input.  eof != 0: the EOF block follows the data blocks.  d_out / d_table: device memory; d_table (may
+ * be NULL) receives one row per block written, the EOF block's included (room for ceil(in_len / block_size) + 1 rows); *n_blocks =
+ * the rows.  *out_len = the stream's bytes; ZNGAMD_BUF_ERROR with *out_len = the size needed when out_cap is too small (nothing is
+ * written then).  Levels as zngamd_level_ok; level 0 writes stored blocks. */
+int zngamd_bgzf_compress_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, uint32_t block_size, int level, int eof,
+                             void *d_out, uint64_t out_cap, uint64_t *out_len, zngamd_bgzf_block *d_table, uint32_t *n_blocks);
+/* Host-buffer form: table (may be NULL) is host memory of max_blocks rows (ZNGAMD_BUF_ERROR when it has fewer than *n_blocks). */
+int zngamd_bgzf_compress(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t block_size, int level, int eof,
+                         uint8_t *out, uint64_t out_cap, uint64_t *out_len, zngamd_bgzf_block *table, uint32_t max_blocks,
+                         uint32_t *n_blocks);
+/* The walk from block to block through BSIZE, on the host: no GPU, no context (ctx-free, like zngamd_crc32_combine).  Every complete
+ * block of `in` gets a row of `table` (NULL: the blocks are only counted; else the walk stops after max_blocks rows, *consumed says
+ * where); *n_blocks = blocks walked, *consumed = offset of the first byte behind them, *total_out = the sum of their ISIZE.
+ *   ZNGAMD_OK          the walk ended at in_len, at a full table, or in front of an incomplete last block (a cut header, or a BSIZE
+ *                      that reaches beyond in_len) that follows at least one complete block: the tail starts at *consumed
+ *   ZNGAMD_E_BGZF      `in` does not start with a BGZF block: other magic bytes, or a gzip member without the 'B','C' subfield
+ *   ZNGAMD_DATA_ERROR  a BSIZE smaller than the block's own header and trailer; an ISIZE above 65 536; an extra field whose
+ *                      subfields overrun it; behind the first block: bytes that are no BGZF header; and a FIRST block whose
+ *                      header or BSIZE reaches beyond in_len (no complete block vouches for the stream: a reader that holds at
+ *                      least 64 KiB, or the whole file, never sees this for a sound file).  The outputs describe the blocks in
+ *                      front of the bad one. */
+int zngamd_bgzf_scan(const uint8_t *in, uint64_t in_len, zngamd_bgzf_block *table, uint32_t max_blocks, uint32_t *n_blocks,
+                     uint64_t *consumed, uint64_t *total_out);
+/* Ranged reads.  d_in holds compressed blocks (any selection of a file's blocks, packed in any way; 64 readable bytes behind in_len),
+ * d_members names them as zngamd_gzip_inflate_plain_members_dev takes it (in_off / in_len = a block's deflate payload, the trailer
+ * behind it; out_off / out_len = where its output goes in d_scratch), in ascending order of out_off.  One launch of that decoder
+ * decodes all of them into d_scratch, CRC-32 and ISIZE verified, d_status[m] = the verdict per block (0 = good).  Then one workgroup
+ * per row of d_slices copies scratch[src_off, src_off + len) to d_out + dst_off -- only when blocks that decoded cover those bytes
+ * without a gap: d_slice_status[i] = ZNGAMD_BGZF_SLICE_OK, _BLOCK (a block the slice touches failed or is missing; the slice's
+ * bytes in d_out are zeros) or _TABLE (the row points outside scratch_cap / out_cap; nothing is written).  The tables are
+ * untrusted: no entry makes a kernel read or write outside the buffers. */
+typedef struct { uint64_t src_off, dst_off; uint32_t len, reserved; } zngamd_bgzf_slice;      /* 24 B */
+#define ZNGAMD_BGZF_SLICE_OK    0
+#define ZNGAMD_BGZF_SLICE_BLOCK 1
+#define ZNGAMD_BGZF_SLICE_TABLE 2
+int zngamd_bgzf_read_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                         const zngamd_bgzf_slice *d_slices, uint32_t n_slices, void *d_scratch, uint64_t scratch_cap,
+                         void *d_out, uint64_t out_cap, int32_t *d_status, int32_t *d_slice_status);
+/* Host-buffer form: stages in and the tables, keeps the decoded blocks on the device and copies back the statuses and the packed
+ * result only (out[0 .. the end of the last slice)). */
+int zngamd_bgzf_read(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                     const zngamd_bgzf_slice *slices, uint32_t n_slices, uint8_t *out, uint64_t out_cap, int32_t *status,
+                     int32_t *slice_status);
+/* what the ranged reads did since the last reset: out[0] decode launches, out[1] blocks decoded, out[2] slices gathered */
+int zngamd_bgzf_stats(zngamd_ctx *ctx, uint64_t *out /*[3]*/, int reset);
+
 /* ---- streaming: the zng_stream calling convention ------------------------------------------------
  * What a binding of the reference swaps in for zng_deflateInit2 / zng_deflate / zng_deflateSetDictionary / zng_deflateCopy /
  * zng_deflateEnd (zlib_ngmodule.c:394, :552, :743, :401, :811) and zng_inflateInit2 / zng_inflate / zng_inflateSetDictionary /

@@ -8,6 +8,7 @@
 #include "za_inflate.hip"
 #include "za_inflate_units.hip"
 #include "za_inflate_spans.hip"
+#include "za_bgzf.hip"
 #include "za_batch.hip"
 #include "za_dict.hip"
 #include "za_checksum.hip"
@@ -28,6 +29,8 @@ static_assert(sizeof(zngamd_span) == sizeof(ZaSpan) && ZNGAMD_SPAN_PAD == ZA_SPA
 static_assert(sizeof(zngamd_batch_item) == sizeof(ZaBatchItem) && sizeof(zngamd_batch_result) == sizeof(ZaBatchResult) &&
               ZNGAMD_BATCH_PAD == ZA_BATCH_PAD && ZNGAMD_BATCH_TABLE == ZA_BATCH_TABLE && ZNGAMD_BATCH_OUTFULL == ZA_BATCH_OUTFULL, "batch layout");
 static_assert(ZNGAMD_ZDICT_MISMATCH == ZA_ZDICT_MISMATCH, "zdict status");
+static_assert(sizeof(zngamd_bgzf_block) == sizeof(ZaBgzfBlock) && sizeof(zngamd_bgzf_slice) == sizeof(ZaBgzfSlice) && ZNGAMD_BGZF_MAX_INPUT == ZA_BGZF_MAX_IN &&
+              ZNGAMD_BGZF_SLICE_BLOCK == ZA_SLICE_BLOCK && ZNGAMD_BGZF_SLICE_TABLE == ZA_SLICE_TABLE, "bgzf layout");
 static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT + 32, "slot stride");
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
@@ -113,6 +116,8 @@ struct zngamd_ctx {
     DevBuf<uint8_t> bt_dict, bt_prime;           // the batch API with a dictionary: its kept tail, the primed items ([tail][item] each)
     DevBuf<uint8_t> dt_data, dt_dict; DevBuf<uint32_t> dt_hash, dt_freq; DevBuf<uint16_t> dt_shadow;      // the dictionary trainer (za_dict.hip)
     DevBuf<ZaBatchItem> dt_items; DevBuf<ZaDictBest> dt_best; DevBuf<ZaDictState> dt_state;
+    DevBuf<uint32_t> bg_len; DevBuf<ZaBgzfBlock> bg_table; DevBuf<ZaBgzfSlice> bg_slices; DevBuf<int32_t> bg_sstat; DevBuf<uint8_t> bg_out;      // BGZF (za_bgzf.hip): block sizes, block table, slices of a ranged read
+    uint64_t bgzf_stats[3] = {0, 0, 0};          // ranged reads: decode launches, blocks decoded, slices gathered (zngamd_bgzf_stats)
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
     uint8_t *h_tab = nullptr; size_t h_tab_cap = 0;
@@ -254,6 +259,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->bt_dict.release(); c->bt_prime.release();
     c->dt_data.release(); c->dt_dict.release(); c->dt_hash.release(); c->dt_freq.release(); c->dt_shadow.release();
     c->dt_items.release(); c->dt_best.release(); c->dt_state.release();
+    c->bg_len.release(); c->bg_table.release(); c->bg_slices.release(); c->bg_sstat.release(); c->bg_out.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -3189,6 +3195,214 @@ try {
     *out_len = total;
     if (total > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
     if (total) { const int rc_ = d2h_payload(c, out, c->st_aux.p, total); if (rc_) return rc_; }
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- BGZF (za_bgzf.hip) --------------------------------------------------
+// The BSIZE walk over a host buffer: no GPU, no context.  Like hop_bgzf above (which zngamd_gunzip keeps, with its own rules for
+// when to hand a stream to the general reader), but with a verdict for every way the walk can end.
+int zngamd_bgzf_scan(const uint8_t *in, uint64_t in_len, zngamd_bgzf_block *table, uint32_t max_blocks, uint32_t *n_blocks,
+                     uint64_t *consumed, uint64_t *total_out)
+{
+    if ((!in && in_len) || !n_blocks || !consumed || !total_out) return ZNGAMD_E_ARG;
+    auto le16 = [&](uint64_t o) { return (uint32_t)in[o] | ((uint32_t)in[o + 1] << 8); };
+    auto le32 = [&](uint64_t o) { return (uint32_t)in[o] | ((uint32_t)in[o + 1] << 8) | ((uint32_t)in[o + 2] << 16) | ((uint32_t)in[o + 3] << 24); };
+    static const uint8_t magic[4] = {0x1f, 0x8b, 8, 4};
+    uint64_t pos = 0, outp = 0;
+    uint32_t n = 0;
+    int ret = ZNGAMD_OK;
+    while (pos < in_len && (!table || n < max_blocks)) {
+        const uint64_t left = in_len - pos;
+        // what is there of the four fixed bytes decides between "not a block" and "the start of one"
+        bool is_block = true;
+        for (uint64_t i = 0; i < std::min<uint64_t>(left, 4); i++) if (in[pos + i] != magic[i]) is_block = false;
+        if (!is_block) { ret = pos == 0 ? ZNGAMD_E_BGZF : ZNGAMD_DATA_ERROR; break; }
+        if (left < 12) { if (n == 0) ret = ZNGAMD_E_BGZF; break; }                   // a cut header: the tail (nothing but a stump is no BGZF)
+        const uint64_t end = pos + 12 + le16(pos + 10);                               // end of the extra field
+        if (end > in_len) { if (n == 0) ret = ZNGAMD_DATA_ERROR; break; }
+        long bsize = -1;
+        bool bad = false;
+        for (uint64_t cur = pos + 12; cur + 4 <= end;) {
+            const uint32_t sl = le16(cur + 2);
+            if (cur + 4 + sl > end) { bad = true; break; }
+            if (in[cur] == 'B' && in[cur + 1] == 'C' && sl == 2) bsize = (long)le16(cur + 4);
+            cur += 4 + sl;
+        }
+        if (bad) { ret = ZNGAMD_DATA_ERROR; break; }
+        if (bsize < 0) { ret = pos == 0 ? ZNGAMD_E_BGZF : ZNGAMD_DATA_ERROR; break; }    // a gzip member without the 'B','C' subfield
+        const uint64_t msize = (uint64_t)bsize + 1;
+        if (msize < (end - pos) + 8) { ret = ZNGAMD_DATA_ERROR; break; }             // smaller than its own header and trailer
+        // A block that runs past the buffer: the incomplete tail of a longer file once a complete block stands in front of it (what
+        // hop_bgzf allows too); with none in front of it nothing vouches for this BSIZE
+        if (msize > left) { if (n == 0) ret = ZNGAMD_DATA_ERROR; break; }
+        const uint32_t isize = le32(pos + msize - 4);
+        if (isize > 65536u) { ret = ZNGAMD_DATA_ERROR; break; }
+        if (table) { zngamd_bgzf_block r; r.coffset = pos; r.uoffset = outp; r.csize = (uint32_t)msize; r.isize = isize; table[n] = r; }
+        n++; pos += msize; outp += isize;
+    }
+    *n_blocks = n; *consumed = pos; *total_out = outp;
+    return ret;
+}
+
+static int bgzf_compress_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, uint32_t block_size, int level, int eof, uint8_t *d_out,
+                             uint64_t out_cap, uint64_t *out_len, ZaBgzfBlock *d_table, uint32_t *n_blocks)
+{
+    if (block_size == 0 || block_size > ZA_BGZF_MAX_IN) return fail(c, ZNGAMD_E_ARG, "block_size must be 1..65280");
+    if (!zngamd_level_ok(level)) return fail(c, ZNGAMD_STREAM_ERROR, "Bad compression level");
+    const uint64_t nb64 = (in_len + block_size - 1) / block_size;
+    if (nb64 > (1u << 26)) return fail(c, ZNGAMD_E_ARG, "too many blocks");
+    const uint32_t nb = (uint32_t)nb64;
+    *out_len = 0;
+    if (n_blocks) *n_blocks = 0;
+    if (nb == 0 && !eof) return ZNGAMD_OK;
+    uint64_t total = 0;
+    uint64_t *d_total = (uint64_t *)c->d_small;
+    if (nb) {
+        std::vector<ZaUnit> hu(nb);
+        for (uint32_t b = 0; b < nb; b++) {
+            ZaUnit u; u.in_off = (uint64_t)b * block_size; u.in_len = (uint32_t)std::min<uint64_t>(block_size, in_len - u.in_off);
+            u.dict_len = 0; u.flags = ZA_FLAG_FINAL; u.flags |= (uint32_t)za_seg_shift_for(u.in_len, u.flags) << 8; u.block = b; hu[b] = u;
+        }
+        HIPCHK(c, c->st_slots.ensure((size_t)nb * ZNGAMD_SLOT_STRIDE)); HIPCHK(c, c->st_len.ensure(nb)); HIPCHK(c, c->st_crc.ensure(nb));
+        HIPCHK(c, c->bg_len.ensure(nb)); HIPCHK(c, c->st_off.ensure(nb));
+        int r = deflate_units_dev(c, d_in, in_len, hu, level, c->st_slots.p, c->st_len.p, c->st_crc.p);
+        if (r) return r;
+        { ProfScope ps(c, ZNGAMD_K_GATHER);
+          hipLaunchKernelGGL(za_k_bgzf_lengths, dim3((nb + 255u) / 256u), dim3(256), 0, c->stream, c->st_len.p, c->units.p, nb, c->bg_len.p);
+          hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(nb <= 64 ? 64 : 1024), 0, c->stream, c->bg_len.p, nb, 0u, 0ull, c->st_off.p, d_total,
+                             (const ZaUnit *)nullptr); }
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else HIPCHK(c, hipMemsetAsync(d_total, 0, 8, c->stream));
+    const uint64_t need = total + (eof ? ZA_BGZF_EOF_BYTES : 0u);
+    *out_len = need;
+    if (need > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_assemble_bgzf, dim3(nb + (eof ? 1u : 0u)), dim3(256), 0, c->stream, d_in, c->st_slots.p, (uint32_t)ZNGAMD_SLOT_STRIDE,
+                         c->st_len.p, c->st_crc.p, c->units.p, c->bg_len.p, c->st_off.p, d_total, nb, in_len, d_out, d_table); }
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint32_t> st(nb);
+    if (nb) HIPCHK(c, hipMemcpyAsync(st.data(), c->status.p, nb * 4ull, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    for (uint32_t i = 0; i < nb; i++) if (st[i]) return fail(c, ZNGAMD_E_OVERFLOW, "unit overflowed its slot");
+    if (n_blocks) *n_blocks = nb + (eof ? 1u : 0u);
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_compress_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, uint32_t block_size, int level, int eof, void *d_out,
+                             uint64_t out_cap, uint64_t *out_len, zngamd_bgzf_block *d_table, uint32_t *n_blocks)
+try {
+    if (!c || (!d_in && in_len) || (!d_out && out_cap) || !out_len) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return bgzf_compress_dev(c, (const uint8_t *)d_in, in_len, block_size, level, eof, (uint8_t *)d_out, out_cap, out_len, (ZaBgzfBlock *)d_table, n_blocks);
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_compress(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, uint32_t block_size, int level, int eof, uint8_t *out,
+                         uint64_t out_cap, uint64_t *out_len, zngamd_bgzf_block *table, uint32_t max_blocks, uint32_t *n_blocks)
+try {
+    if (!c || (!in && in_len) || (!out && out_cap) || !out_len) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (block_size == 0 || block_size > ZA_BGZF_MAX_IN) return fail(c, ZNGAMD_E_ARG, "block_size must be 1..65280");
+    int r = stage_in(c, in, in_len);
+    if (r) return r;
+    const uint64_t nb = (in_len + block_size - 1) / block_size;
+    const uint64_t bound = in_len + in_len / 32 + nb * (ZA_BGZF_FIXED + 600) + ZA_BGZF_EOF_BYTES;      // (what the pipeline writes for a unit that does not compress, with room to spare)
+    HIPCHK(c, c->st_aux.ensure(bound)); HIPCHK(c, c->bg_table.ensure(nb + 1));
+    uint64_t total = 0; uint32_t rows = 0;
+    r = bgzf_compress_dev(c, c->st_in.p, in_len, block_size, level, eof, c->st_aux.p, bound, &total, c->bg_table.p, &rows);
+    *out_len = total;
+    if (r) return r;
+    if (n_blocks) *n_blocks = rows;
+    if (total > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    if (table) {
+        if (rows > max_blocks) return fail(c, ZNGAMD_BUF_ERROR, "block table too small");
+        if (rows) HIPCHK(c, hipMemcpyAsync(table, c->bg_table.p, (size_t)rows * sizeof(ZaBgzfBlock), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if (total) { const int rc_ = d2h_payload(c, out, c->st_aux.p, total); if (rc_) return rc_; }
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// Ranged reads: the blocks in ONE launch of the plain-member decoder (CRC-32 and ISIZE checked there, a status per block), then the
+// slice kernel.  Nothing is copied to the host here.
+static int bgzf_read_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members,
+                         const ZaBgzfSlice *d_slices, uint32_t n_slices, uint8_t *d_scratch, uint64_t scratch_cap, uint8_t *d_out,
+                         uint64_t out_cap, int32_t *d_status, int32_t *d_slice_status)
+{
+    if (n_members) {
+        ProfScope ps(c, ZNGAMD_K_INFLATE);
+        hipLaunchKernelGGL(za_k_inflate_serial_members, dim3(n_members), dim3(64), 0, c->stream, d_in, in_len, d_members, d_scratch, scratch_cap,
+                           c->d_crc_table, c->d_x8k, d_status);
+        c->bgzf_stats[0]++; c->bgzf_stats[1] += n_members;
+    }
+    if (n_slices) {
+        ProfScope ps(c, ZNGAMD_K_GATHER);
+        hipLaunchKernelGGL(za_k_slice_gather, dim3(n_slices), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, d_slices,
+                           d_out, out_cap, d_slice_status);
+        c->bgzf_stats[2] += n_slices;
+    }
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_read_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                         const zngamd_bgzf_slice *d_slices, uint32_t n_slices, void *d_scratch, uint64_t scratch_cap, void *d_out,
+                         uint64_t out_cap, int32_t *d_status, int32_t *d_slice_status)
+try {
+    if (!c || (n_members && (!d_in || !d_members || !d_status || (!d_scratch && scratch_cap))) ||
+        (n_slices && (!d_slices || !d_slice_status || (!d_out && out_cap)))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_read_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, (const ZaBgzfSlice *)d_slices, n_slices,
+                          (uint8_t *)d_scratch, scratch_cap, (uint8_t *)d_out, out_cap, d_status, d_slice_status);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_read(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                     const zngamd_bgzf_slice *slices, uint32_t n_slices, uint8_t *out, uint64_t out_cap, int32_t *status, int32_t *slice_status)
+try {
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (n_slices && (!slices || !slice_status)) || (!out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    // the decoded scratch is as long as the members say; a member that lies outside the input gets its verdict from the kernel
+    uint64_t scratch = 0;
+    for (uint32_t i = 0; i < n_members; i++) {
+        if (members[i].out_off > (1ull << 40)) return fail(c, ZNGAMD_E_ARG, "member table: output offset out of range");
+        scratch = std::max<uint64_t>(scratch, members[i].out_off + members[i].out_len);
+    }
+    int r = stage_in(c, in, in_len);
+    if (r) return r;
+    HIPCHK(c, c->st_out.ensure(scratch + 64)); HIPCHK(c, c->bg_out.ensure(out_cap + 64));
+    HIPCHK(c, c->members.ensure(n_members + 1)); HIPCHK(c, c->mstatus.ensure(n_members + 1));
+    HIPCHK(c, c->bg_slices.ensure(n_slices + 1)); HIPCHK(c, c->bg_sstat.ensure(n_slices + 1));
+    if (n_members) HIPCHK(c, hipMemcpyAsync(c->members.p, members, (size_t)n_members * sizeof(ZaMember), hipMemcpyHostToDevice, c->stream));
+    if (n_slices) HIPCHK(c, hipMemcpyAsync(c->bg_slices.p, slices, (size_t)n_slices * sizeof(ZaBgzfSlice), hipMemcpyHostToDevice, c->stream));
+    r = bgzf_read_dev(c, c->st_in.p, in_len, c->members.p, n_members, c->bg_slices.p, n_slices, c->st_out.p, scratch, c->bg_out.p, out_cap,
+                      c->mstatus.p, c->bg_sstat.p);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_slices) HIPCHK(c, hipMemcpyAsync(slice_status, c->bg_sstat.p, (size_t)n_slices * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (the uploads read the caller's pageable tables: drained before it may touch them again)
+    // only the packed result crosses the link: as far as the slices reach
+    uint64_t used = 0;
+    for (uint32_t i = 0; i < n_slices; i++)
+        if (slice_status[i] != ZA_SLICE_TABLE) used = std::max<uint64_t>(used, slices[i].dst_off + slices[i].len);
+    if (used) { const int rc_ = d2h_payload(c, out, c->bg_out.p, std::min(used, out_cap)); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_stats(zngamd_ctx *c, uint64_t *out, int reset)
+try {
+    if (!c || !out) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int i = 0; i < 3; i++) { out[i] = c->bgzf_stats[i]; if (reset) c->bgzf_stats[i] = 0; }
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
 

@@ -80,6 +80,7 @@ SYMBOLS = [
     "zngamd_inflate_batch_dev", "zngamd_inflate_batch", "zngamd_deflate_batch_dev", "zngamd_deflate_batch",
     "zngamd_inflate_batch_dict_dev", "zngamd_inflate_batch_dict", "zngamd_deflate_batch_dict_dev", "zngamd_deflate_batch_dict",
     "zngamd_train_dict_dev", "zngamd_train_dict",
+    "zngamd_bgzf_compress_dev", "zngamd_bgzf_compress", "zngamd_bgzf_scan", "zngamd_bgzf_read_dev", "zngamd_bgzf_read", "zngamd_bgzf_stats",
 ]
 
 
@@ -123,6 +124,17 @@ class Member(C.Structure):
     _fields_ = [("in_off", C.c_uint64), ("in_len", C.c_uint64), ("out_off", C.c_uint64),
                 ("out_len", C.c_uint32), ("crc", C.c_uint32), ("index_off", C.c_uint32), ("nseg", C.c_uint32)]
 
+
+class BgzfBlock(C.Structure):                  # zngamd_bgzf_block
+    _fields_ = [("coffset", C.c_uint64), ("uoffset", C.c_uint64), ("csize", C.c_uint32), ("isize", C.c_uint32)]
+
+
+class BgzfSlice(C.Structure):                  # zngamd_bgzf_slice
+    _fields_ = [("src_off", C.c_uint64), ("dst_off", C.c_uint64), ("len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+E_BGZF = -107                                  # ZNGAMD_E_BGZF: zngamd_bgzf_scan on data that is not BGZF
+BGZF_SLICE_OK, BGZF_SLICE_BLOCK, BGZF_SLICE_TABLE = 0, 1, 2
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -208,6 +220,15 @@ def load():
                                             C.POINTER(C.c_uint32)]
         L.zngamd_train_dict.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u8p,
                                         C.POINTER(C.c_uint32)]
+        if hasattr(L, "zngamd_bgzf_scan"):           # (a variant build of an earlier revision under ZNGAMD_LIB has no BGZF entry points)
+            L.zngamd_bgzf_compress_dev.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint64, C.POINTER(C.c_uint64), vp,
+                                                   C.POINTER(C.c_uint32)]
+            L.zngamd_bgzf_compress.argtypes = [vp, u8p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, u8p, C.c_uint64, C.POINTER(C.c_uint64), vp,
+                                               C.c_uint32, C.POINTER(C.c_uint32)]
+            L.zngamd_bgzf_scan.argtypes = [u8p, C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+            L.zngamd_bgzf_read_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+            L.zngamd_bgzf_read.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, u8p, C.c_uint64, vp, vp]
+            L.zngamd_bgzf_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         L.zngamd_compare_dev.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.zngamd_crc32_fold_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
         L.zngamd_gunzip.argtypes = [vp, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64),
@@ -557,6 +578,18 @@ def parse_index_tail(fp, start, end):
             fp.seek(here)
         except (OSError, ValueError):
             pass
+
+
+def bgzf_scan(data, max_blocks=None):
+    """zngamd_bgzf_scan (no GPU) -> (code, [(coffset, uoffset, block bytes, isize), ...], consumed, total_out)"""
+    L = load()
+    p, keep = _addr(data)
+    n = memoryview(data).nbytes
+    cap = n // 26 + 1 if max_blocks is None else int(max_blocks)
+    tab = (BgzfBlock * max(cap, 1))()
+    nb, used, tot = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    r = L.zngamd_bgzf_scan(p, n, tab, cap, C.byref(nb), C.byref(used), C.byref(tot))
+    return r, [(t.coffset, t.uoffset, t.csize, t.isize) for t in tab[:nb.value]], used.value, tot.value
 
 
 def block_table(blocks):
@@ -983,6 +1016,69 @@ class Context:
         return r, bytes(out[:ln.value])
 
     # ---- measurement
+    # ---- BGZF (bgzf.py)
+    @staticmethod
+    def bgzf_room(n, block_size):
+        """Bytes that always hold the BGZF stream of n bytes of input (EOF block included)."""
+        nb = (n + block_size - 1) // max(block_size, 1)
+        return n + n // 32 + nb * 626 + 28
+
+    def bgzf_compress(self, data, block_size, level, eof=True):
+        """zngamd_bgzf_compress -> (stream bytes, [(coffset, uoffset, block bytes, isize), ...] with the EOF block's row)"""
+        p, keep = _addr(data)
+        n = memoryview(data).nbytes
+        cap = self.bgzf_room(n, block_size)
+        rows = (n + block_size - 1) // max(block_size, 1) + 1
+        tab = (BgzfBlock * rows)()
+        out = _Out(cap)
+        ol, nb = C.c_uint64(0), C.c_uint32(0)
+        self._chk(self.L.zngamd_bgzf_compress(self.h, p, n, block_size, level, 1 if eof else 0, out.addr(), cap, C.byref(ol), tab, rows, C.byref(nb)))
+        return out.take(ol.value), [(t.coffset, t.uoffset, t.csize, t.isize) for t in tab[:nb.value]]
+
+    def bgzf_compress_dev(self, d_in, n, block_size, level, eof, d_out, out_cap, d_table):
+        """zngamd_bgzf_compress_dev on device pointers -> (stream bytes, rows written to d_table)"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        ol, nb = C.c_uint64(0), C.c_uint32(0)
+        self._chk(self.L.zngamd_bgzf_compress_dev(self.h, v(d_in), n, block_size, level, 1 if eof else 0, v(d_out), out_cap, C.byref(ol), v(d_table),
+                                                  C.byref(nb)))
+        return ol.value, nb.value
+
+    def gunzip_into(self, data, addr, out_cap):
+        """zngamd_gunzip into memory of the caller's (an address from take_window(): a reader that decodes window after window
+        into the same warm buffer) -> (code, bytes produced, n_members)"""
+        p, keep = _addr(data)
+        ol, nm = C.c_uint64(0), C.c_uint32(0)
+        r = self.L.zngamd_gunzip(self.h, p, memoryview(data).nbytes, addr, out_cap, C.byref(ol), C.byref(nm))
+        if r in (E_HIP, E_ARG):
+            raise EngineError(r, self.err())
+        return r, min(ol.value, out_cap), nm.value
+
+    def bgzf_read(self, data, members, slices, out_cap):
+        """zngamd_bgzf_read: data = packed compressed blocks, members / slices = tables of Member / BgzfSlice rows (ctypes arrays, or
+        numpy arrays of the same layout).  -> (block statuses, slice statuses, packed result)"""
+        nm, ns = len(members), len(slices)
+        ptr = lambda t: C.c_void_p(t.ctypes.data) if isinstance(t, np.ndarray) else C.cast(t, C.c_void_p)
+        p, keep = _addr(data)
+        out, op = _new_bytes(out_cap)
+        st = (C.c_int32 * max(1, nm))()
+        ss = (C.c_int32 * max(1, ns))()
+        self._chk(self.L.zngamd_bgzf_read(self.h, p, memoryview(data).nbytes, ptr(members) if nm else None, nm,
+                                          ptr(slices) if ns else None, ns, op, out_cap, st, ss))
+        return list(st[:nm]), list(ss[:ns]), _take(out, out_cap)
+
+    def bgzf_read_dev(self, d_in, in_len, d_members, n_members, d_slices, n_slices, d_scratch, scratch_cap, d_out, out_cap, d_status,
+                      d_slice_status):
+        """zngamd_bgzf_read_dev on device pointers (ints or c_void_p); statuses and result stay on the device."""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        self._chk(self.L.zngamd_bgzf_read_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_slices), n_slices, v(d_scratch), scratch_cap,
+                                              v(d_out), out_cap, v(d_status), v(d_slice_status)))
+
+    def bgzf_stats(self, reset=True):
+        """(decode launches, blocks decoded, slices gathered) of the ranged reads since the last reset"""
+        m = (C.c_uint64 * 3)()
+        self._chk(self.L.zngamd_bgzf_stats(self.h, m, 1 if reset else 0))
+        return int(m[0]), int(m[1]), int(m[2])
+
     def profiling(self, on):
         self._chk(self.L.zngamd_profiling(self.h, 1 if on else 0))
 
