@@ -484,8 +484,55 @@ int zngamd_bgzf_read_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, con
 int zngamd_bgzf_read(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
                      const zngamd_bgzf_slice *slices, uint32_t n_slices, uint8_t *out, uint64_t out_cap, int32_t *status,
                      int32_t *slice_status);
-/* what the ranged reads did since the last reset: out[0] decode launches, out[1] blocks decoded, out[2] slices gathered */
+/* what the ranged reads and the line calls below did since the last reset: out[0] decode launches, out[1] blocks decoded, out[2]
+ * slices gathered */
 int zngamd_bgzf_stats(zngamd_ctx *ctx, uint64_t *out /*[3]*/, int reset);
+
+/* ---- BGZF by line (zlib_ng_amd/bgzf.py: LineIndex, BgzfReader.read_lines).  A line ends with one delimiter
+ * byte (delim, 0 .. 255; anything else is ZNGAMD_E_ARG).  All three calls take the compressed blocks and the member table as
+ * zngamd_bgzf_read_dev takes them (64 readable bytes behind in_len in d_in), decode all of them in one launch into the scratch and
+ * leave the decoded bytes on the device.  d_status[m] = the decoder's verdict per block (0 = good).  The tables are untrusted: no
+ * entry makes a kernel read or write outside the buffers. */
+typedef struct { uint32_t count, flags; } zngamd_bgzf_count_row;      /* 8 B (12 per block with its status) */
+#define ZNGAMD_BGZF_COUNT_LAST  1u           /* flags: the block's last output byte is the delimiter */
+/* Counting: d_rows[m] = the delimiter bytes in block m's output and ZNGAMD_BGZF_COUNT_LAST; a block that failed, or whose output
+ * lies outside scratch_cap, gets {0, 0}. */
+int zngamd_bgzf_count_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                          int delim, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_count_row *d_rows);
+/* Host-buffer form: stages in and the table, copies back the statuses and the rows only. */
+int zngamd_bgzf_count(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                      int delim, int32_t *status, zngamd_bgzf_count_row *rows);
+/* A position query: the scratch offset of the byte BEHIND the rank-th delimiter (counted from 1) of block `member`'s output.  rank 0
+ * is the block's first byte, ZNGAMD_BGZF_RANK_END one past its last.  Verdict per query: ZNGAMD_BGZF_SLICE_OK; _TABLE (member outside
+ * the table, a block outside scratch_cap or of more than 65 536 bytes); _BLOCK (the block failed); _RANK (the block has fewer
+ * delimiters than rank: the index that made the query was built for another file).  Only _OK comes with a position (0 otherwise). */
+typedef struct { uint32_t member, rank; } zngamd_bgzf_pos;              /* 8 B */
+#define ZNGAMD_BGZF_RANK_END    0xFFFFFFFFu
+#define ZNGAMD_BGZF_SLICE_RANK  3
+int zngamd_bgzf_line_positions_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members,
+                                   uint32_t n_members, const zngamd_bgzf_pos *d_queries, uint32_t n_queries, int delim,
+                                   void *d_scratch, uint64_t scratch_cap, int32_t *d_status, uint64_t *d_pos, int32_t *d_pos_status);
+int zngamd_bgzf_line_positions(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                               const zngamd_bgzf_pos *queries, uint32_t n_queries, int delim, int32_t *status, uint64_t *pos,
+                               int32_t *pos_status);
+/* Reading lines: a range is two positions, from (m0, r0) up to (m1, r1); the bytes between them are packed into d_out in the order
+ * of the table, d_range_len[i] bytes each, *out_len in all.  d_range_status[i]: the verdict of the range's positions if one is not
+ * _OK, _TABLE for a second position below the first or a range of 4 GiB or more, else what the slice kernel of the ranged reads
+ * says (_BLOCK: a block between the two positions failed or is missing).  A range without the verdict _OK has length 0 or zeros
+ * for bytes.  ZNGAMD_BUF_ERROR with *out_len = the size needed when out_cap is too small: no line is written then, d_range_len is
+ * valid, d_range_status is NOT written (the slice kernel, which has the last word on it, has not run).  Fewer than 2^30 ranges. */
+typedef struct { uint32_t m0, r0, m1, r1; } zngamd_bgzf_line_range;    /* 16 B */
+int zngamd_bgzf_read_lines_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                               const zngamd_bgzf_line_range *d_ranges, uint32_t n_ranges, int delim, void *d_scratch,
+                               uint64_t scratch_cap, void *d_out, uint64_t out_cap, uint64_t *out_len, uint32_t *d_range_len,
+                               int32_t *d_status, int32_t *d_range_status);
+/* Host-buffer form: the lengths and the verdicts are copied back in either case, the packed lines when they fit out_cap.  A caller
+ * that cannot bound the lines passes out = NULL, out_cap = 0 and alloc: once the size is known, alloc(user, *out_len) is asked for
+ * the memory the lines go to (not called for no bytes; NULL from it: ZNGAMD_MEM_ERROR), as in the batch API's host forms. */
+int zngamd_bgzf_read_lines(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                           const zngamd_bgzf_line_range *ranges, uint32_t n_ranges, int delim, uint8_t *out, uint64_t out_cap,
+                           zngamd_alloc_fn alloc, void *user, uint64_t *out_len, uint32_t *range_len, int32_t *status,
+                           int32_t *range_status);
 
 /* ---- streaming: the zng_stream calling convention ------------------------------------------------
  * What a binding of the reference swaps in for zng_deflateInit2 / zng_deflate / zng_deflateSetDictionary / zng_deflateCopy /

@@ -5,6 +5,7 @@
 //                         the input), CRC-32, ISIZE, and the block's row of the block table; one more workgroup writes the EOF block
 //   za_k_slice_gather     ranged reads: one workgroup per slice copies the requested bytes of the decoded blocks into a packed
 //                         result, after it has made sure that every block the slice touches decoded and checked out
+//   za_k_bgzf_count, za_k_bgzf_select and their helpers: lines by number (at the end of this file)
 // Included by zng_amd.hip behind za_inflate.hip (ZaMember, ZA_I_OK).
 #include "za_common.h"
 
@@ -128,4 +129,150 @@ __global__ __launch_bounds__(256) void za_k_slice_gather(const uint8_t *__restri
     uint8_t *d = out + s.dst_off;
     if (verdict == ZA_SLICE_OK) za_wg_copy(d, scratch + s.src_off, s.len);
     else for (uint32_t i = threadIdx.x; i < s.len; i += blockDim.x) d[i] = 0;      // never the bytes of a block that failed
+}
+
+// ---- lines: counting a delimiter in the decoded blocks, and finding the r-th one of a block ------------
+//   za_k_bgzf_count        one workgroup per block: how many of its output bytes equal the delimiter, and whether its last one does
+//   za_k_bgzf_select       one workgroup per position query (block m, rank r): the scratch offset of the byte behind the r-th delimiter
+//   za_k_bgzf_line_slices  pairs of positions become the slices of za_k_slice_gather (placed by za_k_offsets, za_k_bgzf_place)
+//   za_k_bgzf_line_verdicts  a range keeps the verdict of its positions where the gather kernel had nothing to object to
+#define ZA_SLICE_RANK  3             // a rank beyond the block's count: the index was built for another file
+#define ZA_RANK_END    0xFFFFFFFFu   // the reserved rank: one past the block's last byte
+#define ZA_COUNT_LAST  1u            // flags of a count row: the block's last output byte is the delimiter
+
+struct ZaBgzfCount { uint32_t count, flags; };       // mirrors zngamd_bgzf_count_row
+struct ZaBgzfPos { uint32_t m, r; };                 // mirrors zngamd_bgzf_pos; a zngamd_bgzf_line_range is two of them
+
+// 0x80 in exactly the bytes of x that equal the byte `pat` repeats.  Exact per byte: no carry leaves a byte, unlike
+// (y - 0x01010101) & ~y & 0x80808080, whose borrow marks a 0x01 byte above a zero one (a test, not a count).
+__device__ __forceinline__ uint32_t za_eq_mask(uint32_t x, uint32_t pat)
+{
+    const uint32_t y = x ^ pat;
+    const uint32_t t = (y & 0x7f7f7f7fu) + 0x7f7f7f7fu;
+    return ~(t | y | 0x7f7f7f7fu);
+}
+__device__ __forceinline__ uint32_t za_eq_count16(uint32_t x, uint32_t y, uint32_t z, uint32_t w, uint32_t pat)
+{
+    return (uint32_t)(__popc(za_eq_mask(x, pat)) + __popc(za_eq_mask(y, pat)) + __popc(za_eq_mask(z, pat)) + __popc(za_eq_mask(w, pat)));
+}
+
+// the member's output lies inside the scratch (the tables are untrusted; no sum that could wrap)
+__device__ __forceinline__ bool za_member_in_scratch(const ZaMember &m, uint64_t scratch_cap)
+{
+    return m.out_off <= scratch_cap && scratch_cap - m.out_off >= m.out_len;
+}
+
+// grid: one workgroup per member.  16-byte loads on the aligned body (out_off is not aligned in general), bytes in front and behind.
+__global__ __launch_bounds__(256) void za_k_bgzf_count(const uint8_t *__restrict__ scratch, uint64_t scratch_cap, const ZaMember *__restrict__ members,
+                                                       const int32_t *__restrict__ member_status, uint32_t delim, ZaBgzfCount *__restrict__ rows)
+{
+    __shared__ uint32_t part[4];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const ZaMember m = members[b];
+    if (member_status[b] != ZA_I_OK || !za_member_in_scratch(m, scratch_cap)) {       // (the same for every thread)
+        if (tid == 0) { ZaBgzfCount r; r.count = 0; r.flags = 0; rows[b] = r; }
+        return;
+    }
+    const uint8_t *p = scratch + m.out_off;
+    const uint32_t len = m.out_len, pat = delim * 0x01010101u;
+    uint32_t head = (uint32_t)((16u - ((uintptr_t)p & 15u)) & 15u);
+    if (head > len) head = len;
+    uint32_t n = 0;
+    if (tid < head) n += p[tid] == delim;
+    const uint4 *body = (const uint4 *)(p + head);
+    const uint32_t nv = (len - head) >> 4;
+    for (uint32_t i = tid; i < nv; i += 256u) { const uint4 v = body[i]; n += za_eq_count16(v.x, v.y, v.z, v.w, pat); }
+    const uint32_t done = head + 16u * nv;
+    if (tid < len - done) n += p[done + tid] == delim;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
+    if ((tid & 63u) == 0) part[tid >> 6] = n;
+    __syncthreads();
+    if (tid == 0) {
+        ZaBgzfCount r; r.count = part[0] + part[1] + part[2] + part[3];
+        r.flags = (len && p[len - 1u] == delim) ? ZA_COUNT_LAST : 0u;
+        rows[b] = r;
+    }
+}
+
+// grid: one workgroup per query.  Every thread counts its stretch of 256 bytes, a scan over the 256 counts finds the stretch that
+// holds the r-th delimiter, and its thread walks it.  Whatever the tables say, nothing outside [scratch, scratch + scratch_cap) is read.
+__global__ __launch_bounds__(256) void za_k_bgzf_select(const uint8_t *__restrict__ scratch, uint64_t scratch_cap, const ZaMember *__restrict__ members,
+                                                        const int32_t *__restrict__ member_status, uint32_t n_members,
+                                                        const ZaBgzfPos *__restrict__ queries, uint32_t delim, uint64_t *__restrict__ pos_out,
+                                                        int32_t *__restrict__ pos_status)
+{
+    __shared__ uint32_t wave_sum[4];
+    __shared__ uint32_t found;
+    const uint32_t tid = threadIdx.x;
+    const ZaBgzfPos q = queries[blockIdx.x];
+    int verdict = ZA_SLICE_OK;                        // (everything up to the scan is the same for every thread)
+    uint64_t pos = 0;
+    ZaMember m = {};
+    if (q.m >= n_members) verdict = ZA_SLICE_TABLE;
+    else {
+        m = members[q.m];
+        if (!za_member_in_scratch(m, scratch_cap) || m.out_len > 65536u) verdict = ZA_SLICE_TABLE;      // (256 threads x 256 bytes)
+        else if (member_status[q.m] != ZA_I_OK) verdict = ZA_SLICE_BLOCK;
+    }
+    if (verdict == ZA_SLICE_OK) {
+        if (q.r == 0) pos = m.out_off;
+        else if (q.r == ZA_RANK_END) pos = m.out_off + m.out_len;
+        else {
+            const uint8_t *p = scratch + m.out_off;
+            const uint32_t len = m.out_len, pat = delim * 0x01010101u;
+            const uint32_t b = tid * 256u < len ? tid * 256u : len, e = b + 256u < len ? b + 256u : len;
+            uint32_t n = 0, i = b;
+            for (; i + 16u <= e; i += 16u) { const ZaU4u v = *(const ZaU4u *)(p + i); n += za_eq_count16(v.x, v.y, v.z, v.w, pat); }
+            for (; i < e; i++) n += p[i] == delim;
+            const uint32_t incl = za_wave_incl_scan(n);
+            if ((tid & 63u) == 63u) wave_sum[tid >> 6] = incl;
+            if (tid == 0) found = 0xFFFFFFFFu;
+            __syncthreads();
+            uint32_t base = 0, total = 0;
+            for (uint32_t w = 0; w < 4u; w++) { const uint32_t s = wave_sum[w]; if (w < (tid >> 6)) base += s; total += s; }
+            if (q.r > total) verdict = ZA_SLICE_RANK;
+            else {
+                const uint32_t excl = base + incl - n;
+                if (excl < q.r && q.r <= excl + n) {           // exactly one thread
+                    uint32_t left = q.r - excl, j = b;
+                    for (; j < e; j++) if (p[j] == delim && --left == 0) break;
+                    found = j + 1u;
+                }
+                __syncthreads();
+                pos = m.out_off + found;
+            }
+        }
+    }
+    if (tid == 0) { pos_out[blockIdx.x] = verdict == ZA_SLICE_OK ? pos : 0ull; pos_status[blockIdx.x] = verdict; }
+}
+
+// One thread per range: positions 2 i and 2 i + 1 become slice i.  A range whose positions have no verdict of 0, whose second
+// position lies below its first, or that is 4 GiB long or longer, is an empty slice with a verdict in `pre`.
+__global__ __launch_bounds__(256) void za_k_bgzf_line_slices(const uint64_t *__restrict__ pos, const int32_t *__restrict__ pos_status, uint32_t n,
+                                                             ZaBgzfSlice *__restrict__ slices, uint32_t *__restrict__ lens, int32_t *__restrict__ pre)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t p0 = pos[2u * i], p1 = pos[2u * i + 1u];
+    int v = pos_status[2u * i] ? pos_status[2u * i] : pos_status[2u * i + 1u];
+    uint32_t len = 0;
+    if (v == ZA_SLICE_OK) {
+        if (p1 < p0 || p1 - p0 >= (1ull << 32)) v = ZA_SLICE_TABLE;
+        else len = (uint32_t)(p1 - p0);
+    }
+    ZaBgzfSlice s; s.src_off = v == ZA_SLICE_OK ? p0 : 0ull; s.dst_off = 0; s.len = len; s.reserved = 0;
+    slices[i] = s; lens[i] = len; pre[i] = v;
+}
+
+__global__ __launch_bounds__(256) void za_k_bgzf_place(const uint64_t *__restrict__ offs, uint32_t n, ZaBgzfSlice *__restrict__ slices)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) slices[i].dst_off = offs[i];
+}
+
+__global__ __launch_bounds__(256) void za_k_bgzf_line_verdicts(const int32_t *__restrict__ pre, uint32_t n, int32_t *__restrict__ range_status)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && pre[i] != ZA_SLICE_OK) range_status[i] = pre[i];
 }

@@ -31,6 +31,8 @@ static_assert(sizeof(zngamd_batch_item) == sizeof(ZaBatchItem) && sizeof(zngamd_
 static_assert(ZNGAMD_ZDICT_MISMATCH == ZA_ZDICT_MISMATCH, "zdict status");
 static_assert(sizeof(zngamd_bgzf_block) == sizeof(ZaBgzfBlock) && sizeof(zngamd_bgzf_slice) == sizeof(ZaBgzfSlice) && ZNGAMD_BGZF_MAX_INPUT == ZA_BGZF_MAX_IN &&
               ZNGAMD_BGZF_SLICE_BLOCK == ZA_SLICE_BLOCK && ZNGAMD_BGZF_SLICE_TABLE == ZA_SLICE_TABLE, "bgzf layout");
+static_assert(sizeof(zngamd_bgzf_count_row) == sizeof(ZaBgzfCount) && sizeof(zngamd_bgzf_pos) == sizeof(ZaBgzfPos) && sizeof(zngamd_bgzf_line_range) == 2 * sizeof(ZaBgzfPos) &&
+              ZNGAMD_BGZF_SLICE_RANK == ZA_SLICE_RANK && ZNGAMD_BGZF_RANK_END == ZA_RANK_END && ZNGAMD_BGZF_COUNT_LAST == ZA_COUNT_LAST, "bgzf line layout");
 static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT + 32, "slot stride");
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
@@ -118,6 +120,7 @@ struct zngamd_ctx {
     DevBuf<ZaBatchItem> dt_items; DevBuf<ZaDictBest> dt_best; DevBuf<ZaDictState> dt_state;
     DevBuf<uint32_t> bg_len; DevBuf<ZaBgzfBlock> bg_table; DevBuf<ZaBgzfSlice> bg_slices; DevBuf<int32_t> bg_sstat; DevBuf<uint8_t> bg_out;      // BGZF (za_bgzf.hip): block sizes, block table, slices of a ranged read
     uint64_t bgzf_stats[3] = {0, 0, 0};          // ranged reads: decode launches, blocks decoded, slices gathered (zngamd_bgzf_stats)
+    DevBuf<ZaBgzfCount> bg_rows; DevBuf<ZaBgzfPos> bg_q; DevBuf<uint64_t> bg_pos; DevBuf<int32_t> bg_pstat, bg_pre; DevBuf<uint32_t> bg_rlen;      // lines (section 5e): count rows, position queries, positions and their verdicts, range lengths
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
     uint8_t *h_tab = nullptr; size_t h_tab_cap = 0;
@@ -260,6 +263,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->dt_data.release(); c->dt_dict.release(); c->dt_hash.release(); c->dt_freq.release(); c->dt_shadow.release();
     c->dt_items.release(); c->dt_best.release(); c->dt_state.release();
     c->bg_len.release(); c->bg_table.release(); c->bg_slices.release(); c->bg_sstat.release(); c->bg_out.release();
+    c->bg_rows.release(); c->bg_q.release(); c->bg_pos.release(); c->bg_pstat.release(); c->bg_pre.release(); c->bg_rlen.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -3395,6 +3399,230 @@ try {
     if (used) { const int rc_ = d2h_payload(c, out, c->bg_out.p, std::min(used, out_cap)); if (rc_) return rc_; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- lines: the decode launch of the ranged reads, then the count kernel or the select kernel on the decoded
+// scratch.  Nothing here copies decoded bytes to the host.
+static void bgzf_decode_launch(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint8_t *d_scratch,
+                               uint64_t scratch_cap, int32_t *d_status)
+{
+    ProfScope ps(c, ZNGAMD_K_INFLATE);
+    hipLaunchKernelGGL(za_k_inflate_serial_members, dim3(n_members), dim3(64), 0, c->stream, d_in, in_len, d_members, d_scratch, scratch_cap,
+                       c->d_crc_table, c->d_x8k, d_status);
+    c->bgzf_stats[0]++; c->bgzf_stats[1] += n_members;
+}
+
+static int bgzf_count_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint32_t delim,
+                          uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status, ZaBgzfCount *d_rows)
+{
+    if (!n_members) return ZNGAMD_OK;
+    bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_bgzf_count, dim3(n_members), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, delim, d_rows); }
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+static int bgzf_positions_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members,
+                              const ZaBgzfPos *d_queries, uint32_t n_queries, uint32_t delim, uint8_t *d_scratch, uint64_t scratch_cap,
+                              int32_t *d_status, uint64_t *d_pos, int32_t *d_pos_status)
+{
+    if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+    if (n_queries) {
+        ProfScope ps(c, ZNGAMD_K_GATHER);
+        hipLaunchKernelGGL(za_k_bgzf_select, dim3(n_queries), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, d_queries,
+                           delim, d_pos, d_pos_status);
+    }
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+// decode, select (two positions per range), pairs into slices, scan, [the host waits for the packed total], gather, verdicts
+static int bgzf_read_lines_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members,
+                               const ZaBgzfPos *d_ranges, uint32_t n_ranges, uint32_t delim, uint8_t *d_scratch, uint64_t scratch_cap,
+                               uint8_t *d_out, uint64_t out_cap, bool own_out, uint64_t *out_len, uint32_t *d_range_len, int32_t *d_status,
+                               int32_t *d_range_status)
+{
+    *out_len = 0;
+    if (n_ranges >= (1u << 30)) return fail(c, ZNGAMD_E_ARG, "too many ranges");      // (two workgroups of the select launch per range)
+    if (!n_ranges) {
+        if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+        HIPCHK(c, hipGetLastError());
+        return ZNGAMD_OK;
+    }
+    HIPCHK(c, c->bg_pos.ensure(2ull * n_ranges)); HIPCHK(c, c->bg_pstat.ensure(2ull * n_ranges)); HIPCHK(c, c->bg_pre.ensure(n_ranges));
+    HIPCHK(c, c->bg_slices.ensure(n_ranges + 1)); HIPCHK(c, c->st_off.ensure(n_ranges));
+    int r = bgzf_positions_dev(c, d_in, in_len, d_members, n_members, d_ranges, 2u * n_ranges, delim, d_scratch, scratch_cap, d_status, c->bg_pos.p,
+                               c->bg_pstat.p);
+    if (r) return r;
+    uint64_t *d_total = (uint64_t *)c->d_small;
+    uint64_t total = 0;
+    const uint32_t grid = (n_ranges + 255u) / 256u;
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_bgzf_line_slices, dim3(grid), dim3(256), 0, c->stream, c->bg_pos.p, c->bg_pstat.p, n_ranges, c->bg_slices.p, d_range_len,
+                         c->bg_pre.p);
+      hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n_ranges <= 64 ? 64 : 1024), 0, c->stream, d_range_len, n_ranges, 0u, 0ull, c->st_off.p, d_total,
+                         (const ZaUnit *)nullptr);
+      hipLaunchKernelGGL(za_k_bgzf_place, dim3(grid), dim3(256), 0, c->stream, c->st_off.p, n_ranges, c->bg_slices.p); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *out_len = total;
+    if (own_out) { HIPCHK(c, c->bg_out.ensure(total + 64)); d_out = c->bg_out.p; }      // (the host form: the packed result is as long as the lines are)
+    else if (total > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_slice_gather, dim3(n_ranges), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, c->bg_slices.p,
+                         d_out, total, d_range_status);
+      hipLaunchKernelGGL(za_k_bgzf_line_verdicts, dim3(grid), dim3(256), 0, c->stream, c->bg_pre.p, n_ranges, d_range_status); }
+    c->bgzf_stats[2] += n_ranges;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+// host forms: the member table decides the scratch; a row whose offsets could wrap the kernels' sums is refused here
+static int bgzf_host_scratch(zngamd_ctx *c, const zngamd_member *members, uint32_t n_members, uint64_t *scratch)
+{
+    uint64_t need = 0;
+    for (uint32_t i = 0; i < n_members; i++) {
+        if (members[i].out_off > (1ull << 40)) return fail(c, ZNGAMD_E_ARG, "member table: output offset out of range");
+        if (members[i].in_off > (1ull << 48) || members[i].in_len > (1ull << 48)) return fail(c, ZNGAMD_E_ARG, "member table: input offset out of range");
+        need = std::max<uint64_t>(need, members[i].out_off + members[i].out_len);
+    }
+    *scratch = need;
+    return ZNGAMD_OK;
+}
+
+static int bgzf_host_stage(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t *scratch)
+{
+    int r = bgzf_host_scratch(c, members, n_members, scratch);
+    if (r) return r;
+    r = stage_in(c, in, in_len);
+    if (r) return r;
+    HIPCHK(c, c->st_out.ensure(*scratch + 64)); HIPCHK(c, c->members.ensure(n_members + 1)); HIPCHK(c, c->mstatus.ensure(n_members + 1));
+    if (n_members) HIPCHK(c, hipMemcpyAsync(c->members.p, members, (size_t)n_members * sizeof(ZaMember), hipMemcpyHostToDevice, c->stream));
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_count_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, int delim,
+                          void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_count_row *d_rows)
+try {
+    if (!c || delim < 0 || delim > 255 || (n_members && (!d_in || !d_members || !d_status || !d_rows || (!d_scratch && scratch_cap)))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_count_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, (uint32_t)delim, (uint8_t *)d_scratch, scratch_cap,
+                           d_status, (ZaBgzfCount *)d_rows);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_count(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, int delim,
+                      int32_t *status, zngamd_bgzf_count_row *rows)
+try {
+    if (!c || delim < 0 || delim > 255 || (!in && in_len) || (n_members && (!members || !status || !rows))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    HIPCHK(c, c->bg_rows.ensure(n_members + 1));
+    r = bgzf_count_dev(c, c->st_in.p, in_len, c->members.p, n_members, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p, c->bg_rows.p);
+    if (r) return r;
+    if (n_members) {
+        HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rows, c->bg_rows.p, (size_t)n_members * sizeof(ZaBgzfCount), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_line_positions_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                   const zngamd_bgzf_pos *d_queries, uint32_t n_queries, int delim, void *d_scratch, uint64_t scratch_cap,
+                                   int32_t *d_status, uint64_t *d_pos, int32_t *d_pos_status)
+try {
+    if (!c || delim < 0 || delim > 255 || (n_members && (!d_in || !d_members || !d_status || (!d_scratch && scratch_cap))) ||
+        (n_queries && (!d_queries || !d_pos || !d_pos_status))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_positions_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, (const ZaBgzfPos *)d_queries, n_queries,
+                               (uint32_t)delim, (uint8_t *)d_scratch, scratch_cap, d_status, d_pos, d_pos_status);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_line_positions(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                               const zngamd_bgzf_pos *queries, uint32_t n_queries, int delim, int32_t *status, uint64_t *pos, int32_t *pos_status)
+try {
+    if (!c || delim < 0 || delim > 255 || (!in && in_len) || (n_members && (!members || !status)) || (n_queries && (!queries || !pos || !pos_status)))
+        return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    HIPCHK(c, c->bg_q.ensure(n_queries + 1)); HIPCHK(c, c->bg_pos.ensure(n_queries + 1)); HIPCHK(c, c->bg_pstat.ensure(n_queries + 1));
+    if (n_queries) HIPCHK(c, hipMemcpyAsync(c->bg_q.p, queries, (size_t)n_queries * sizeof(ZaBgzfPos), hipMemcpyHostToDevice, c->stream));
+    r = bgzf_positions_dev(c, c->st_in.p, in_len, c->members.p, n_members, c->bg_q.p, n_queries, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p,
+                           c->bg_pos.p, c->bg_pstat.p);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_queries) {
+        HIPCHK(c, hipMemcpyAsync(pos, c->bg_pos.p, (size_t)n_queries * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(pos_status, c->bg_pstat.p, (size_t)n_queries * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_read_lines_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                               const zngamd_bgzf_line_range *d_ranges, uint32_t n_ranges, int delim, void *d_scratch, uint64_t scratch_cap,
+                               void *d_out, uint64_t out_cap, uint64_t *out_len, uint32_t *d_range_len, int32_t *d_status, int32_t *d_range_status)
+try {
+    if (!c || !out_len || delim < 0 || delim > 255 || (n_members && (!d_in || !d_members || !d_status || (!d_scratch && scratch_cap))) ||
+        (n_ranges && (!d_ranges || !d_range_len || !d_range_status || (!d_out && out_cap)))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_read_lines_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, (const ZaBgzfPos *)d_ranges, n_ranges,
+                                (uint32_t)delim, (uint8_t *)d_scratch, scratch_cap, (uint8_t *)d_out, out_cap, false, out_len, d_range_len, d_status,
+                                d_range_status);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_read_lines(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                           const zngamd_bgzf_line_range *ranges, uint32_t n_ranges, int delim, uint8_t *out, uint64_t out_cap,
+                           zngamd_alloc_fn alloc, void *user, uint64_t *out_len, uint32_t *range_len, int32_t *status, int32_t *range_status)
+try {
+    if (!c || !out_len || delim < 0 || delim > 255 || (!in && in_len) || (n_members && (!members || !status)) ||
+        (n_ranges && (!ranges || !range_len || !range_status)) || (!out && out_cap) || (out && alloc)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    HIPCHK(c, c->bg_q.ensure(2ull * n_ranges + 2)); HIPCHK(c, c->bg_rlen.ensure(n_ranges + 1)); HIPCHK(c, c->bg_sstat.ensure(n_ranges + 1));
+    if (n_ranges) HIPCHK(c, hipMemcpyAsync(c->bg_q.p, ranges, (size_t)n_ranges * 2 * sizeof(ZaBgzfPos), hipMemcpyHostToDevice, c->stream));
+    r = bgzf_read_lines_dev(c, c->st_in.p, in_len, c->members.p, n_members, c->bg_q.p, n_ranges, (uint32_t)delim, c->st_out.p, scratch, nullptr, 0, true,
+                            out_len, c->bg_rlen.p, c->mstatus.p, c->bg_sstat.p);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_ranges) {
+        HIPCHK(c, hipMemcpyAsync(range_len, c->bg_rlen.p, (size_t)n_ranges * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(range_status, c->bg_sstat.p, (size_t)n_ranges * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (alloc) {                                          // the size is known: the caller's memory is asked for now
+        if (!*out_len) return ZNGAMD_OK;
+        out = (uint8_t *)alloc(user, *out_len);
+        if (!out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (*out_len > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");      // (lengths and verdicts are there; only the lines are not)
+    if (*out_len) { const int rc_ = d2h_payload(c, out, c->bg_out.p, *out_len); if (rc_) return rc_; }
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
 

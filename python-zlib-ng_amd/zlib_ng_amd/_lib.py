@@ -81,6 +81,8 @@ SYMBOLS = [
     "zngamd_inflate_batch_dict_dev", "zngamd_inflate_batch_dict", "zngamd_deflate_batch_dict_dev", "zngamd_deflate_batch_dict",
     "zngamd_train_dict_dev", "zngamd_train_dict",
     "zngamd_bgzf_compress_dev", "zngamd_bgzf_compress", "zngamd_bgzf_scan", "zngamd_bgzf_read_dev", "zngamd_bgzf_read", "zngamd_bgzf_stats",
+    "zngamd_bgzf_count_dev", "zngamd_bgzf_count", "zngamd_bgzf_line_positions_dev", "zngamd_bgzf_line_positions", "zngamd_bgzf_read_lines_dev",
+    "zngamd_bgzf_read_lines",
 ]
 
 
@@ -135,6 +137,9 @@ class BgzfSlice(C.Structure):                  # zngamd_bgzf_slice
 
 E_BGZF = -107                                  # ZNGAMD_E_BGZF: zngamd_bgzf_scan on data that is not BGZF
 BGZF_SLICE_OK, BGZF_SLICE_BLOCK, BGZF_SLICE_TABLE = 0, 1, 2
+BGZF_SLICE_RANK = 3                            # ZNGAMD_BGZF_SLICE_RANK: a rank beyond the block's delimiter count (a stale line index)
+BGZF_RANK_END = 0xFFFFFFFF                     # ZNGAMD_BGZF_RANK_END: the position one past a block's last byte
+BGZF_COUNT_LAST = 1                            # ZNGAMD_BGZF_COUNT_LAST
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -229,6 +234,15 @@ def load():
             L.zngamd_bgzf_read_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
             L.zngamd_bgzf_read.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, u8p, C.c_uint64, vp, vp]
             L.zngamd_bgzf_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        if hasattr(L, "zngamd_bgzf_count"):
+            L.zngamd_bgzf_count_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, vp]
+            L.zngamd_bgzf_count.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_int, vp, vp]
+            L.zngamd_bgzf_line_positions_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, vp, vp]
+            L.zngamd_bgzf_line_positions.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int, vp, vp, vp]
+            L.zngamd_bgzf_read_lines_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, C.c_uint64,
+                                                     C.POINTER(C.c_uint64), vp, vp, vp]
+            L.zngamd_bgzf_read_lines.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int, u8p, C.c_uint64, ALLOC_FN, vp,
+                                                 C.POINTER(C.c_uint64), vp, vp, vp]
         L.zngamd_compare_dev.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.zngamd_crc32_fold_dev.argtypes = [vp, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]
         L.zngamd_gunzip.argtypes = [vp, u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint64),
@@ -1072,6 +1086,87 @@ class Context:
         v = lambda x: C.c_void_p(int(x)) if x else None
         self._chk(self.L.zngamd_bgzf_read_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_slices), n_slices, v(d_scratch), scratch_cap,
                                               v(d_out), out_cap, v(d_status), v(d_slice_status)))
+
+    def bgzf_count(self, data, members, delim):
+        """zngamd_bgzf_count: data = packed compressed blocks, members = numpy table of MEMBER rows -> (block statuses int32[n],
+        rows uint32[n, 2] of (count, flags)); the decoded bytes stay on the device"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        rows = np.zeros((max(1, nm), 2), np.uint32)
+        self._chk(self.L.zngamd_bgzf_count(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm, delim,
+                                           C.c_void_p(st.ctypes.data), C.c_void_p(rows.ctypes.data)))
+        return st[:nm], rows[:nm]
+
+    def bgzf_line_positions(self, data, members, queries, delim):
+        """zngamd_bgzf_line_positions: queries = uint32[n, 2] of (member, rank) -> (block statuses, scratch offsets uint64[n], verdicts
+        int32[n])"""
+        nm, nq = len(members), len(queries)
+        p, keep = _addr(data)
+        queries = np.ascontiguousarray(queries, np.uint32)
+        st = np.zeros(max(1, nm), np.int32)
+        pos = np.zeros(max(1, nq), np.uint64)
+        ps = np.zeros(max(1, nq), np.int32)
+        self._chk(self.L.zngamd_bgzf_line_positions(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                    C.c_void_p(queries.ctypes.data) if nq else None, nq, delim, C.c_void_p(st.ctypes.data),
+                                                    C.c_void_p(pos.ctypes.data), C.c_void_p(ps.ctypes.data)))
+        return st[:nm], pos[:nq], ps[:nq]
+
+    def bgzf_read_lines(self, data, members, ranges, delim, out_cap=None):
+        """zngamd_bgzf_read_lines: ranges = uint32[n, 4] of (m0, r0, m1, r1) -> (code, block statuses, range verdicts, range lengths,
+        packed lines, bytes needed).  out_cap None: the result is allocated once the engine knows its size; a number: a buffer of that
+        size, and code is BUF_ERROR (no lines) when the lines need more"""
+        nm, nr = len(members), len(ranges)
+        p, keep = _addr(data)
+        ranges = np.ascontiguousarray(ranges, np.uint32)
+        st = np.zeros(max(1, nm), np.int32)
+        rs = np.zeros(max(1, nr), np.int32)
+        rl = np.zeros(max(1, nr), np.uint32)
+        ol = C.c_uint64(0)
+        box = []
+
+        def alloc(_user, nbytes):
+            obj, addr = _new_bytes(nbytes)
+            box.append(obj)
+            return addr.value
+
+        if out_cap is None:
+            op, cap, fn = None, 0, ALLOC_FN(alloc)
+        else:
+            out, op = _new_bytes(out_cap)
+            cap, fn = out_cap, ALLOC_FN()
+        r = self._chk(self.L.zngamd_bgzf_read_lines(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                    C.c_void_p(ranges.ctypes.data) if nr else None, nr, delim, op, cap, fn, None, C.byref(ol),
+                                                    C.c_void_p(rl.ctypes.data), C.c_void_p(st.ctypes.data), C.c_void_p(rs.ctypes.data)),
+                      (OK, BUF_ERROR))
+        if out_cap is None:
+            packed = box[0] if box else b""
+        else:
+            packed = _take(out, ol.value) if r == OK else b""
+        return r, st[:nm], rs[:nr], rl[:nr], packed, ol.value
+
+    def bgzf_count_dev(self, d_in, in_len, d_members, n_members, delim, d_scratch, scratch_cap, d_status, d_rows):
+        """zngamd_bgzf_count_dev on device pointers; statuses and rows stay on the device."""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        self._chk(self.L.zngamd_bgzf_count_dev(self.h, v(d_in), in_len, v(d_members), n_members, delim, v(d_scratch), scratch_cap, v(d_status),
+                                               v(d_rows)))
+
+    def bgzf_line_positions_dev(self, d_in, in_len, d_members, n_members, d_queries, n_queries, delim, d_scratch, scratch_cap, d_status, d_pos,
+                                d_pos_status):
+        """zngamd_bgzf_line_positions_dev on device pointers."""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        self._chk(self.L.zngamd_bgzf_line_positions_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_queries), n_queries, delim,
+                                                        v(d_scratch), scratch_cap, v(d_status), v(d_pos), v(d_pos_status)))
+
+    def bgzf_read_lines_dev(self, d_in, in_len, d_members, n_members, d_ranges, n_ranges, delim, d_scratch, scratch_cap, d_out, out_cap,
+                            d_range_len, d_status, d_range_status):
+        """zngamd_bgzf_read_lines_dev on device pointers -> (code, packed bytes, or the bytes needed when code is BUF_ERROR)"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        ol = C.c_uint64(0)
+        r = self._chk(self.L.zngamd_bgzf_read_lines_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_ranges), n_ranges, delim,
+                                                        v(d_scratch), scratch_cap, v(d_out), out_cap, C.byref(ol), v(d_range_len), v(d_status),
+                                                        v(d_range_status)), (OK, BUF_ERROR))
+        return r, ol.value
 
     def bgzf_stats(self, reset=True):
         """(decode launches, blocks decoded, slices gathered) of the ranged reads since the last reset"""

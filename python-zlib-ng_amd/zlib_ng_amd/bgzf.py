@@ -15,6 +15,11 @@ offset inside that block's output -- what .bai, .tbi and .csi indexes store, and
         pieces = r.read_ranges([(v0, 100), (v1, 4096)])      # every needed block decoded once, one launch; only the bytes asked
                                                              # for come back from the device
 
+    idx = bgzf.LineIndex.build("reads.fastq.gz")     # delimiters counted on the GPU, 32 bytes per block; idx.save(path) / load(path)
+    with bgzf.open("reads.fastq.gz") as r:
+        recs = r.read_lines(idx, [(40_000_000, 4000)])       # lines by number: planned on the index, one launch
+        cuts = idx.shards(r, 8, lines_per_record=4)          # nine virtual offsets: eight parts that differ by at most one record
+
 The .gzi index (`GziIndex`) maps uncompressed offsets to blocks.  On disk, little-endian: a u64 count, then for every data block
 AFTER the first a pair of u64 (compressed offset, uncompressed offset).  save() writes no entry for the EOF block; load() accepts a
 file whose last entry points at it.  An index is untrusted: load() and the reader check it before it steers a read.
@@ -29,7 +34,7 @@ import numpy as np
 from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
-           "GziIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT"]
+           "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT"]
 
 BadGzipFile = zlib_ng.BadGzipFile
 MAX_BLOCK_INPUT = 65280                       # htslib's 0xff00
@@ -230,6 +235,292 @@ class GziIndex:
         return len(self.entries)
 
 
+def _bsize_of(buf, start, end):
+    """BSIZE + 1 of the header in buf[start:end) (the walk over the extra field's subfields); -1 without a 'B','C' subfield"""
+    cur = start + 12
+    while cur + 4 <= end:
+        sl = int(buf[cur + 2]) | int(buf[cur + 3]) << 8
+        if buf[cur] == 0x42 and buf[cur + 1] == 0x43 and sl == 2 and cur + 6 <= end:
+            return (int(buf[cur + 4]) | int(buf[cur + 5]) << 8) + 1
+        cur += 4 + sl
+    return -1
+
+
+def _member_table(buf, starts, csizes, isizes):
+    """-> (member table (MEMBER_DTYPE) of the blocks that lie at `starts` in `buf`, a uint8 array, with their outputs packed in table
+    order; -1, or the first row whose bytes are not a block of that size and ISIZE: no room in `buf`, no gzip header with the FEXTRA
+    flag that fits the block, a BSIZE or an ISIZE that says otherwise)"""
+    n = len(starts)
+    members = np.zeros(n, MEMBER_DTYPE)
+    if not n:
+        return members, -1
+    starts, csizes = starts.astype(np.int64), csizes.astype(np.int64)
+    ends = starts + csizes
+    ok = (csizes >= 26) & (starts >= 0) & (ends <= len(buf))
+    at = np.where(ok, starts, 0)                             # (rows without room are judged already: they read the buffer's first bytes)
+    if len(buf) < 26:
+        return members, 0
+    hdrs = 12 + buf[at + 10].astype(np.int64) + (buf[at + 11].astype(np.int64) << 8)
+    ok &= (buf[at] == 0x1F) & (buf[at + 1] == 0x8B) & (buf[at + 2] == 8) & (buf[at + 3] & 4 != 0) & (csizes - hdrs >= 8)
+    last = np.where(ok, ends, 26)
+    trailer = buf[(last - 8)[:, None] + np.arange(8)].astype(np.uint32)
+    ok &= (trailer[:, 4] | trailer[:, 5] << 8 | trailer[:, 6] << 16 | trailer[:, 7] << 24) == isizes.astype(np.uint32)
+    # BSIZE: where the 'B','C' subfield is the only one (every writer's blocks), one gather; other headers are walked one by one
+    plain = ok & (hdrs == 18) & (buf[at + 12] == 0x42) & (buf[at + 13] == 0x43) & (buf[at + 14] == 2) & (buf[at + 15] == 0)
+    bsize = buf[at + 16].astype(np.int64) + (buf[at + 17].astype(np.int64) << 8) + 1
+    ok &= ~plain | (bsize == csizes)
+    for i in np.nonzero(ok & ~plain)[0].tolist():
+        ok[i] = _bsize_of(buf, int(starts[i]), int(starts[i] + hdrs[i])) == int(csizes[i])
+    if not bool(ok.all()):
+        return members, int(np.argmin(ok))
+    members["in_off"] = starts + hdrs
+    members["in_len"] = csizes - hdrs - 8
+    members["out_len"] = isizes
+    members["out_off"] = np.cumsum(isizes, dtype=np.uint64) - isizes.astype(np.uint64)
+    members["crc"] = trailer[:, 0] | trailer[:, 1] << 8 | trailer[:, 2] << 16 | trailer[:, 3] << 24
+    return members, -1
+
+
+def _block_error(offset, code, suffix=""):
+    what = {-104: "CRC check failed", -105: "Incorrect length of data produced"}.get(int(code), "invalid deflate data")
+    return BadGzipFile(f"BGZF block at offset {offset}: {what}{suffix}")
+
+
+LINE_INDEX_MAGIC = b"ZNGLIDX\x01"              # the last byte is the format's version
+LINE_ROW_DTYPE = np.dtype([("coffset", "<u8"), ("uoffset", "<u8"), ("before", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])
+_LINE_HEAD = struct.Struct("<8sIIQQQQQ")      # magic, delimiter, reserved, blocks, file size, end of the blocks, data bytes, delimiters
+_STALE = "line index does not match the file"
+
+
+class LineIndex:
+    """Where the lines of a BGZF file are: per block (empty ones in the middle included, the EOF block at the end not) its offset in
+    the file, the offset of its output in the data, the number of delimiter bytes in front of it and whether its last output byte is
+    a delimiter.  A line number becomes a block and the ordinal of a delimiter inside it by arithmetic on these (locate); the
+    delimiters themselves are counted, and found, on the GPU.  On disk (little-endian): LINE_INDEX_MAGIC, u32 delimiter, u32 0, u64
+    blocks, u64 file size, u64 offset of the first byte behind the indexed blocks, u64 data bytes, u64 delimiters; then per block u64
+    coffset, u64 uoffset, u64 delimiters in front, u32 flags (bit 0: the last byte is a delimiter), u32 0.  An index is untrusted:
+    from_bytes() checks it, and a reader checks what it says against the file."""
+
+    def __init__(self, rows, delimiter, file_size, cend, usize, delimiters):
+        self._rows = np.ascontiguousarray(rows, LINE_ROW_DTYPE)
+        self.delimiter = bytes(delimiter)
+        self.file_size, self.cend, self.usize, self.delimiters = int(file_size), int(cend), int(usize), int(delimiters)
+        self.validate()
+        r, n = self._rows, len(self._rows)
+        self._c = np.append(r["coffset"], np.uint64(self.cend)).astype(np.int64)
+        self._u = np.append(r["uoffset"], np.uint64(self.usize)).astype(np.int64)
+        self._before = r["before"].astype(np.int64)
+        self._count = np.diff(np.append(self._before, self.delimiters))
+        self._last = (r["flags"] & 1).astype(bool)
+        self._isize = np.diff(self._u)
+        nxt = np.where(self._isize > 0, np.arange(n), n)          # the first block at or behind i that holds data (n: none)
+        self._next = np.append(np.minimum.accumulate(nxt[::-1])[::-1], n) if n else np.array([0])
+        full = np.nonzero(self._isize > 0)[0]
+        self._tail = int(full[-1]) if len(full) else -1           # the last block that holds data
+        self.lines = self.delimiters + (1 if self._tail >= 0 and not self._last[self._tail] else 0)
+
+    def validate(self, file_size=None):
+        """ValueError unless the rows describe blocks that follow each other inside the file (and, file_size given, inside a file of
+        exactly that size: an index is for one file)."""
+        r, n = self._rows, len(self._rows)
+        if len(self.delimiter) != 1:
+            raise ValueError("line index: the delimiter is exactly one byte")
+        if file_size is not None and int(file_size) != self.file_size:
+            raise ValueError(f"line index: built for a file of {self.file_size} bytes, not {int(file_size)}")
+        if not 0 <= self.cend <= self.file_size < 1 << 48 or not 0 <= self.delimiters <= self.usize < 1 << 62:
+            raise ValueError("line index: totals out of range")
+        c = np.append(r["coffset"], np.uint64(self.cend)).astype(np.int64)
+        u = np.append(r["uoffset"], np.uint64(self.usize)).astype(np.int64)
+        b = np.append(r["before"], np.uint64(self.delimiters)).astype(np.int64)
+        if c[0] != (0 if n else self.cend) or u[0] != (0 if n else self.usize) or b[0] != (0 if n else self.delimiters):
+            raise ValueError("line index: the first block does not start at 0")
+        dc, du, db = np.diff(c), np.diff(u), np.diff(b)
+        if n and (int(dc.min()) < 26 or int(dc.max()) > MAX_BLOCK):
+            raise ValueError("line index: compressed offsets do not ascend by a block's size")
+        if n and (int(du.min()) < 0 or int(du.max()) > MAX_BLOCK):
+            raise ValueError("line index: uncompressed offsets do not ascend by a block's size")
+        if n and (int(db.min()) < 0 or bool((db > du).any())):
+            raise ValueError("line index: delimiter counts descend or exceed a block's bytes")
+        flagged = (r["flags"] & 1).astype(bool)
+        if n and (bool((r["flags"] > 1).any()) or bool(r["reserved"].any()) or bool((flagged & (db == 0)).any())):
+            raise ValueError("line index: bad flags")
+
+    def __len__(self):
+        return len(self._rows)
+
+    def __eq__(self, other):
+        return (isinstance(other, LineIndex) and self.delimiter == other.delimiter and
+                (self.file_size, self.cend, self.usize, self.delimiters) == (other.file_size, other.cend, other.usize, other.delimiters) and
+                np.array_equal(self._rows, other._rows))
+
+    __hash__ = None
+
+    @property
+    def blocks(self):
+        """[(coffset, uoffset, delimiters in front, last byte is a delimiter), ...]"""
+        r = self._rows
+        return [(int(c), int(u), int(b), bool(f & 1)) for c, u, b, f in zip(r["coffset"], r["uoffset"], r["before"], r["flags"])]
+
+    @classmethod
+    def from_counts(cls, blocks, delimiter=b"\n", file_size=None):
+        """From [(coffset, block bytes, isize, delimiters, last byte is a delimiter), ...] of blocks that follow each other from
+        offset 0; a final empty block (the EOF block) gets no row.  file_size: the end of the last block unless given."""
+        tab = np.asarray(blocks, np.int64).reshape(-1, 5)         # (an array of that shape is taken as it is)
+        end = int(tab[-1, 0] + tab[-1, 1]) if len(tab) else 0
+        if len(tab) and tab[-1, 2] == 0:
+            tab = tab[:-1]
+        rows = np.zeros(len(tab), LINE_ROW_DTYPE)
+        if len(tab):
+            rows["coffset"], rows["flags"] = tab[:, 0], tab[:, 4] != 0
+            rows["uoffset"] = np.cumsum(tab[:, 2]) - tab[:, 2]
+            rows["before"] = np.cumsum(tab[:, 3]) - tab[:, 3]
+            cend, usize, total = int(tab[-1, 0] + tab[-1, 1]), int(tab[:, 2].sum()), int(tab[:, 3].sum())
+        else:
+            cend = usize = total = 0
+        return cls(rows, delimiter, end if file_size is None else file_size, cend, usize, total)
+
+    @classmethod
+    def build(cls, file, delimiter=b"\n"):
+        """Count `delimiter` (one byte) in every block of a BGZF file on the GPU: the file is read in windows as BgzfReader reads it,
+        every window's blocks are decoded in one launch and counted where they lie, and 12 bytes per block come back.  BadGzipFile
+        for a file that is not BGZF, or for a block that does not decode (with its offset)."""
+        delimiter = bytes(delimiter)
+        if len(delimiter) != 1:
+            raise ValueError("the delimiter is exactly one byte")
+        if _is_path(file):
+            with _builtin_open(file, "rb") as f:
+                return cls.build(f, delimiter)
+        ctx = zlib_ng._ctx()
+        file.seek(0)
+        into = getattr(file, "readinto", None)
+        buf = _lib.take_buffer(_READ_WINDOW + MAX_BLOCK)
+        mv = memoryview(buf)
+        parts, base, have, nblocks = [], 0, 0, 0
+        try:
+            while True:
+                if into is not None:
+                    got = into(mv[have:have + _READ_WINDOW]) or 0
+                else:
+                    chunk = file.read(_READ_WINDOW)
+                    got = len(chunk)
+                    mv[have:have + got] = chunk
+                have += got
+                if not have:
+                    break
+                data = mv[:have]
+                code, tab, used, total = _lib.bgzf_scan(data)
+                if not got and used < have and _cut_block(data[used:]):
+                    raise BadGzipFile(f"BGZF block {nblocks + len(tab)} at offset {base + used}: the file ends inside the block")
+                if code != _lib.OK and not (code == _lib.DATA_ERROR and not tab and got and have < MAX_BLOCK):
+                    raise _scan_error(code if base + used == 0 else _lib.DATA_ERROR, nblocks + len(tab), base + used)
+                if tab:
+                    t = np.array(tab, np.int64)
+                    members, bad = _member_table(np.frombuffer(data, np.uint8), t[:, 0], t[:, 2], t[:, 3])
+                    if bad >= 0:
+                        raise BadGzipFile(f"BGZF block {nblocks + bad} at offset {base + int(t[bad, 0])}: bad block header or block size")
+                    status, rows = ctx.bgzf_count(data[:used], members, delimiter[0])
+                    bad = np.nonzero(status)[0]
+                    if len(bad):
+                        raise _block_error(base + int(t[bad[0], 0]), status[bad[0]])
+                    t[:, 0] += base
+                    parts.append(np.column_stack([t[:, 0], t[:, 2], t[:, 3], rows[:, 0].astype(np.int64),
+                                                  (rows[:, 1] & _lib.BGZF_COUNT_LAST).astype(np.int64)]))
+                    nblocks += len(tab)
+                tail = have - used
+                if tail and used:
+                    mv[:tail] = bytes(data[used:have])
+                base, have = base + used, tail
+                if not got:
+                    break
+        finally:
+            del mv
+            _lib.give_buffer(buf)
+        return cls.from_counts(np.concatenate(parts) if parts else [], delimiter, base)
+
+    # ---- on disk
+    def to_bytes(self):
+        return _LINE_HEAD.pack(LINE_INDEX_MAGIC, self.delimiter[0], 0, len(self._rows), self.file_size, self.cend, self.usize,
+                               self.delimiters) + self._rows.tobytes()
+
+    def save(self, path_or_file):
+        if hasattr(path_or_file, "write"):
+            path_or_file.write(self.to_bytes())
+        else:
+            with _builtin_open(path_or_file, "wb") as f:
+                f.write(self.to_bytes())
+
+    @classmethod
+    def from_bytes(cls, blob, file_size=None):
+        """ValueError for a truncated blob, another magic or version, rows that validate() refuses, or (file_size given) an index that
+        was built for a file of another size."""
+        blob = bytes(blob)
+        if len(blob) < _LINE_HEAD.size:
+            raise ValueError("line index: too short")
+        magic, delim, zero, n, fsize, cend, usize, total = _LINE_HEAD.unpack_from(blob)
+        if magic != LINE_INDEX_MAGIC:
+            raise ValueError("line index: wrong magic or version")
+        if delim > 255 or zero:
+            raise ValueError("line index: bad header")
+        if n > len(blob) or _LINE_HEAD.size + LINE_ROW_DTYPE.itemsize * n != len(blob):
+            raise ValueError("line index: block count and length disagree")
+        idx = cls(np.frombuffer(blob, LINE_ROW_DTYPE, n, _LINE_HEAD.size), bytes([delim]), fsize, cend, usize, total)
+        if file_size is not None:
+            idx.validate(file_size)
+        return idx
+
+    @classmethod
+    def load(cls, path_or_file, file_size=None):
+        if hasattr(path_or_file, "read"):
+            return cls.from_bytes(path_or_file.read(), file_size)
+        with _builtin_open(path_or_file, "rb") as f:
+            return cls.from_bytes(f.read(), file_size)
+
+    # ---- line numbers
+    def _locate_many(self, lines, normalise=True):
+        """-> (block numbers, ranks).  normalise: the position is where the line STARTS (behind a delimiter that ends a block: the
+        next block that holds data, rank 0; the end of the data: block len(self), rank 0); else it is where the line in front of it
+        ENDS (behind that delimiter, in its own block; the end of data that lacks a last delimiter: the last block, BGZF_RANK_END)."""
+        L = np.asarray(lines, np.int64).reshape(-1)
+        if len(L) and int(L.min()) < 0:
+            raise ValueError("negative line number")
+        if len(L) and int(L.max()) > self.lines:
+            raise IndexError(f"line {int(L.max())} beyond the file's {self.lines} lines")
+        n = len(self._rows)
+        if not n:
+            return np.zeros(len(L), np.int64), np.zeros(len(L), np.int64)
+        inside = (L >= 1) & (L <= self.delimiters)
+        b = np.clip(np.searchsorted(self._before, L, "left") - 1, 0, n - 1)        # the last block with fewer delimiters in front than L
+        r = np.where(inside, L - self._before[b], 0)
+        if normalise:
+            step = inside & (r == self._count[b]) & self._last[b]
+            b = np.where(step, self._next[np.minimum(b + 1, n)], b)
+            r = np.where(step, 0, r)
+            b = np.where(L == 0, self._next[0], b)
+            b = np.where(L > self.delimiters, n, b)
+        else:
+            b = np.where(L == 0, self._next[0], b)
+            over = L > self.delimiters
+            b = np.where(over, max(self._tail, 0), b)
+            r = np.where(over, _lib.BGZF_RANK_END, r)
+        return b, r
+
+    def locate(self, line):
+        """-> (block number, rank): line `line` (from 0) starts behind the rank-th delimiter of that block's output, rank 0 being the
+        block's first byte.  A line that starts behind a block's last byte starts in the next block that holds data.  line == lines
+        is the end of the data: (len(self), 0) unless it lies inside a block.  IndexError beyond it."""
+        b, r = self._locate_many([int(line)])
+        return int(b[0]), int(r[0])
+
+    def shards(self, reader, n, lines_per_record=1):
+        """n + 1 virtual offsets (of `reader`, a BgzfReader on the file) that cut the file into n parts at record boundaries, a
+        record being lines_per_record lines: adjacent parts differ by at most one record."""
+        n, k = int(n), int(lines_per_record)
+        if n < 1 or k < 1:
+            raise ValueError("shards: n and lines_per_record are at least 1")
+        records = (self.lines + k - 1) // k
+        return reader.line_voffsets(self, [min(i * records // n * k, self.lines) for i in range(n + 1)])
+
+
 def _scan_file(f):
     """-> (block table of the whole file, file size); BadGzipFile for anything that is not a complete run of BGZF blocks"""
     f.seek(0)
@@ -340,6 +631,15 @@ class BgzfWriter(io.BufferedIOBase):
     def write_gzi(self, path_or_file):
         """Save the .gzi index of the blocks written so far."""
         GziIndex.from_blocks(self.blocks).save(path_or_file)
+
+    def write_line_index(self, path_or_file, delimiter=b"\n"):
+        """After close(), for a writer that was given a path: build the LineIndex of the finished file (LineIndex.build: the file is
+        read back and counted on the GPU), save it and return it."""
+        if not self._done or not self._own:
+            raise ValueError("write_line_index() needs a closed writer that was opened on a path")
+        idx = LineIndex.build(self._fp.name, delimiter)
+        idx.save(path_or_file)
+        return idx
 
 
 class BgzfReader(io.BufferedIOBase):
@@ -627,3 +927,111 @@ class BgzfReader(io.BufferedIOBase):
                 raise BadGzipFile(f"BGZF block {at}: {what} (range {i})")
         mv = memoryview(out)
         return [bytes(mv[a:a + ln]) for a, ln in spans]
+
+    # ---- lines
+    def _load_indexed(self, index, need):
+        """the blocks `need` (ascending block numbers of `index`) read from the file, one read per run of adjacent ones -> (their
+        bytes packed, member table); ValueError where the file does not hold what the index says"""
+        c, csize = index._c[need], index._c[need + 1] - index._c[need]
+        first = np.nonzero(np.append(True, need[1:] != need[:-1] + 1))[0]           # where a run starts
+        last = np.append(first[1:], len(need)) - 1
+        pieces = []
+        for a, b in zip(first.tolist(), last.tolist()):
+            self._fp.seek(int(c[a]))
+            want = int(c[b] + csize[b] - c[a])
+            piece = self._fp.read(want)
+            if len(piece) != want:
+                raise ValueError(_STALE)
+            pieces.append(piece)
+        data = pieces[0] if len(pieces) == 1 else b"".join(pieces)
+        run_len = c[last] + csize[last] - c[first]
+        run_at = np.cumsum(run_len) - run_len                                           # where each run lies in `data`
+        run_of = np.cumsum(np.append(True, need[1:] != need[:-1] + 1)) - 1
+        starts = run_at[run_of] + (c - c[first][run_of])
+        members, bad = _member_table(np.frombuffer(data, np.uint8), starts, csize, index._isize[need])
+        if bad >= 0:
+            raise ValueError(_STALE)
+        return data, members
+
+    def _check_index(self, index):
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        if index.file_size != self._fsize:
+            raise ValueError(_STALE)
+
+    def read_lines(self, index, ranges):
+        """[the lines first_line .. first_line + n_lines - 1 of (first_line, n_lines) for each range], lines counted from 0, each with
+        its delimiter, as one bytes per range (short where the file ends, empty at or behind index.lines).  `index` is a LineIndex of
+        this file.  The blocks are planned from the index alone, read with one file read per run of adjacent blocks and decoded once,
+        in one launch; the select kernel finds where the lines start and end, and only the lines come back.  BadGzipFile if a block
+        that a range touches does not check out; ValueError if the index does not match the file."""
+        self._check_index(index)
+        ranges = [(int(a), int(n)) for a, n in ranges]
+        if any(a < 0 or n < 0 for a, n in ranges):
+            raise ValueError("line numbers and counts must not be negative")
+        out = [b""] * len(ranges)
+        lo = np.fromiter((min(a, index.lines) for a, n in ranges), np.int64, len(ranges))
+        hi = np.fromiter((min(a + n, index.lines) for a, n in ranges), np.int64, len(ranges))
+        live = np.nonzero(hi > lo)[0]
+        if not len(live):
+            return out
+        m0, r0 = index._locate_many(lo[live])
+        m1, r1 = index._locate_many(hi[live], normalise=False)
+        nb = len(index)
+        cover = np.zeros(nb + 1, np.int64)                       # how many ranges reach over each block
+        np.add.at(cover, m0, 1)
+        np.add.at(cover, m1 + 1, -1)
+        need = np.nonzero((np.cumsum(cover[:nb]) > 0) & (index._isize > 0))[0]
+        here = self._fp.tell()
+        try:
+            data, members = self._load_indexed(index, need)
+        finally:
+            self._fp.seek(here)
+        member_of = np.full(nb, -1, np.int64)
+        member_of[need] = np.arange(len(need))
+        table = np.column_stack([member_of[m0], r0, member_of[m1], r1]).astype(np.uint32)
+        code, status, verdicts, lens, packed, _ = self._ctx.bgzf_read_lines(data, members, table, index.delimiter[0])
+        for j in np.nonzero(verdicts)[0].tolist():
+            if verdicts[j] == _lib.BGZF_SLICE_BLOCK:
+                span = need[(need >= m0[j]) & (need <= m1[j])]
+                bad = span[status[member_of[span]] != 0]
+                if len(bad):
+                    raise _block_error(int(index._c[bad[0]]), status[member_of[bad[0]]], f" (range {int(live[j])})")
+            raise ValueError(_STALE)
+        if code != _lib.OK:
+            raise ValueError(_STALE)
+        mv, at = memoryview(packed), 0
+        for j, ln in zip(live.tolist(), lens.tolist()):
+            out[j] = bytes(mv[at:at + ln])
+            at += ln
+        return out
+
+    def line_voffsets(self, index, lines):
+        """[the virtual offset at which each of `lines` starts] -- what seek() takes.  Normalised: the offset inside the block is below
+        the block's ISIZE; the end of the data (line == index.lines) is the offset of the first byte behind the indexed blocks.
+        Lines that start where a block starts cost nothing; the others are found by the select kernel in one launch."""
+        self._check_index(index)
+        lines = [int(x) for x in lines]
+        b, r = index._locate_many(lines)
+        within = np.zeros(len(b), np.int64)
+        ask = np.nonzero(r > 0)[0]
+        if len(ask):
+            need = np.unique(b[ask])
+            here = self._fp.tell()
+            try:
+                data, members = self._load_indexed(index, need)
+            finally:
+                self._fp.seek(here)
+            member_of = np.full(len(index), -1, np.int64)
+            member_of[need] = np.arange(len(need))
+            q = np.column_stack([member_of[b[ask]], r[ask]]).astype(np.uint32)
+            status, pos, verdicts = self._ctx.bgzf_line_positions(data, members, q, index.delimiter[0])
+            for j in np.nonzero(verdicts)[0].tolist():
+                blk = int(b[ask[j]])
+                if verdicts[j] == _lib.BGZF_SLICE_BLOCK:
+                    raise _block_error(int(index._c[blk]), status[member_of[blk]], f" (line {lines[int(ask[j])]})")
+                raise ValueError(_STALE)
+            within[ask] = pos.astype(np.int64) - members["out_off"][q[:, 0]].astype(np.int64)
+            if bool((within[ask] >= index._isize[b[ask]]).any()):
+                raise ValueError(_STALE)
+        return [make_virtual_offset(int(c), int(w)) for c, w in zip(index._c[b].tolist(), within.tolist())]
