@@ -534,6 +534,50 @@ int zngamd_bgzf_read_lines(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, 
                            zngamd_alloc_fn alloc, void *user, uint64_t *out_len, uint32_t *range_len, int32_t *status,
                            int32_t *range_status);
 
+/* ---- BGZF by content (zlib_ng_amd/bgzf.py: grep).  The blocks and the member table as the line calls take
+ * them; one decode launch; then the text scratch[text_off, text_end) (text_off: the first byte of a line; text_end <= scratch_cap;
+ * fewer than 4 GiB) is searched on the device for fixed byte strings.  A line is selected when one of the patterns occurs in it (with
+ * _LINE_START: stands at its first byte; with _INVERT: when none does).  Lines end with `delim` and are returned with it; with
+ * _FINAL the bytes behind the last delimiter are a line too, without it they are the open tail, which the next call takes up again
+ * at totals->tail_off.  Patterns: host memory in both forms, n_patterns (1 .. 64) rows {off, len} into `patterns` (patterns_len
+ * bytes), each 1 .. 255 bytes without the delimiter byte; anything else is ZNGAMD_E_ARG, found before anything is launched.
+ * Results: one row per selected line in ascending order (src_off: where it starts in the scratch; number: line_base + the lines of
+ * the text in front of it; len: its bytes, delimiter included) and the lines packed in that order.  *totals is always valid on
+ * ZNGAMD_OK and ZNGAMD_BUF_ERROR.  covered = 0: the member rows do not tile the text in ascending order without a gap or an
+ * overlap, or a block that touches the text did not decode (d_status says which): nothing is counted and no line is emitted.
+ * ZNGAMD_BUF_ERROR: rows_cap < totals->matched or out_cap < totals->bytes; nothing is written.  _COUNT_ONLY: the totals alone, no
+ * buffers needed.  The tables are untrusted: no entry makes a kernel read or write outside the buffers. */
+typedef struct { uint32_t off, len; } zngamd_bgzf_pattern;                                        /* 8 B */
+typedef struct { uint64_t src_off, number; uint32_t len, reserved; } zngamd_bgzf_grep_row;        /* 24 B */
+typedef struct {
+    uint64_t seen;         /* lines of the text that were decided (the open tail is not one of them) */
+    uint64_t matched;      /* of them, selected */
+    uint64_t bytes;        /* bytes of the selected lines */
+    uint64_t tail_off;     /* scratch offset where the open line starts; text_end when there is none */
+    uint32_t covered;      /* 1: decoded blocks cover the text and the figures above describe it */
+    uint32_t reserved;
+} zngamd_bgzf_grep_totals;                                                                        /* 40 B */
+#define ZNGAMD_BGZF_GREP_INVERT      1u
+#define ZNGAMD_BGZF_GREP_LINE_START  2u
+#define ZNGAMD_BGZF_GREP_FINAL       4u
+#define ZNGAMD_BGZF_GREP_COUNT_ONLY  8u
+#define ZNGAMD_BGZF_GREP_MAX_PATTERNS 64u
+#define ZNGAMD_BGZF_GREP_MAX_PATTERN  255u
+int zngamd_bgzf_grep_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                         uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                         const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint64_t line_base,
+                         void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap,
+                         void *d_out, uint64_t out_cap, zngamd_bgzf_grep_totals *totals);
+/* Host-buffer form: stages in and the member table; the scratch is as long as the table says; status, rows and the packed lines come
+ * back.  A caller that cannot bound the result passes rows = out = NULL, the capacities 0 and alloc: once the sizes are known it is
+ * asked first for the rows (matched * 24 bytes), then for the lines (bytes); it is not asked for an empty array; NULL from it:
+ * ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_grep(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                     uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                     const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint64_t line_base,
+                     int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap,
+                     zngamd_alloc_fn alloc, void *user, zngamd_bgzf_grep_totals *totals);
+
 /* ---- streaming: the zng_stream calling convention ------------------------------------------------
  * What a binding of the reference swaps in for zng_deflateInit2 / zng_deflate / zng_deflateSetDictionary / zng_deflateCopy /
  * zng_deflateEnd (zlib_ngmodule.c:394, :552, :743, :401, :811) and zng_inflateInit2 / zng_inflate / zng_inflateSetDictionary /

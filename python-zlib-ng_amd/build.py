@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "zlib_ng_amd", "libzng_amd.so")
 SOURCES = ["zng_amd.hip"]
-DEPS = ["zng_amd.hip", "zng_stream.hip", "za_common.h", "za_crc.h", "za_deflate.hip", "za_inflate.hip", "za_inflate_units.hip", "za_inflate_spans.hip", "za_bgzf.hip", "za_batch.hip", "za_dict.hip", "za_checksum.hip",
+DEPS = ["zng_amd.hip", "zng_stream.hip", "za_common.h", "za_crc.h", "za_deflate.hip", "za_inflate.hip", "za_inflate_units.hip", "za_inflate_spans.hip", "za_bgzf.hip", "za_grep.hip", "za_batch.hip", "za_dict.hip", "za_checksum.hip",
         os.path.join("..", "..", "include", "zng_amd.h")]
 
 
@@ -39,11 +39,11 @@ def build(force=False, verbose=False):
 
 def build_host_asan(out):
     """The library with its HOST side under AddressSanitizer + UndefinedBehaviorSanitizer (hipcc applies -fsanitize to the host
-    compilation only for a plain gfx950 target and says so; the device code is the ordinary one), for the entry points that need
+    compilation only for a plain gfx950 target and says so, and -fno-gpu-sanitize makes that explicit; the device code is the ordinary one), for the entry points that need
     no GPU (tests/test_cpu_sanitizers.py; the reference's tox.ini:23-30 does the same for its extension).  GPU-side sanitizers
     are not available on this pool."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "--offload-arch=gfx950", "-Wno-option-ignored", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-fsanitize=address,undefined",
+    cmd = [hipcc, "--offload-arch=gfx950", "-Wno-option-ignored", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
            "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-o", out] + [os.path.join(CSRC, s) for s in SOURCES]
     subprocess.check_call(cmd)
     return out

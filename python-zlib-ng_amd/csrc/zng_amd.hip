@@ -9,6 +9,7 @@
 #include "za_inflate_units.hip"
 #include "za_inflate_spans.hip"
 #include "za_bgzf.hip"
+#include "za_grep.hip"
 #include "za_batch.hip"
 #include "za_dict.hip"
 #include "za_checksum.hip"
@@ -33,6 +34,11 @@ static_assert(sizeof(zngamd_bgzf_block) == sizeof(ZaBgzfBlock) && sizeof(zngamd_
               ZNGAMD_BGZF_SLICE_BLOCK == ZA_SLICE_BLOCK && ZNGAMD_BGZF_SLICE_TABLE == ZA_SLICE_TABLE, "bgzf layout");
 static_assert(sizeof(zngamd_bgzf_count_row) == sizeof(ZaBgzfCount) && sizeof(zngamd_bgzf_pos) == sizeof(ZaBgzfPos) && sizeof(zngamd_bgzf_line_range) == 2 * sizeof(ZaBgzfPos) &&
               ZNGAMD_BGZF_SLICE_RANK == ZA_SLICE_RANK && ZNGAMD_BGZF_RANK_END == ZA_RANK_END && ZNGAMD_BGZF_COUNT_LAST == ZA_COUNT_LAST, "bgzf line layout");
+static_assert(sizeof(zngamd_bgzf_pattern) == sizeof(ZaGrepPat) && sizeof(zngamd_bgzf_grep_row) == sizeof(ZaGrepRow) && sizeof(ZaGrepRow) == sizeof(ZaBgzfSlice) &&
+              sizeof(zngamd_bgzf_grep_totals) == 40 && offsetof(ZaGrepTotals, covered) == offsetof(zngamd_bgzf_grep_totals, covered) && sizeof(ZaGrepTotals) <= 64 &&
+              ZNGAMD_BGZF_GREP_INVERT == ZA_GREP_INVERT && ZNGAMD_BGZF_GREP_LINE_START == ZA_GREP_LINE_START && ZNGAMD_BGZF_GREP_FINAL == ZA_GREP_FINAL &&
+              ZNGAMD_BGZF_GREP_COUNT_ONLY == ZA_GREP_COUNT_ONLY && ZNGAMD_BGZF_GREP_MAX_PATTERNS == ZA_GREP_MAX_PAT && ZNGAMD_BGZF_GREP_MAX_PATTERN == ZA_GREP_MAX_LEN,
+              "bgzf grep layout");
 static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT + 32, "slot stride");
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
@@ -121,6 +127,8 @@ struct zngamd_ctx {
     DevBuf<uint32_t> bg_len; DevBuf<ZaBgzfBlock> bg_table; DevBuf<ZaBgzfSlice> bg_slices; DevBuf<int32_t> bg_sstat; DevBuf<uint8_t> bg_out;      // BGZF (za_bgzf.hip): block sizes, block table, slices of a ranged read
     uint64_t bgzf_stats[3] = {0, 0, 0};          // ranged reads: decode launches, blocks decoded, slices gathered (zngamd_bgzf_stats)
     DevBuf<ZaBgzfCount> bg_rows; DevBuf<ZaBgzfPos> bg_q; DevBuf<uint64_t> bg_pos; DevBuf<int32_t> bg_pstat, bg_pre; DevBuf<uint32_t> bg_rlen;      // lines (section 5e): count rows, position queries, positions and their verdicts, range lengths
+    DevBuf<uint8_t> gp_par; DevBuf<ulonglong2> gp_bits; DevBuf<ZaGrepTile> gp_tiles; DevBuf<ZaGrepCarry> gp_carry; DevBuf<ZaGrepRow> gp_rows; DevBuf<uint32_t> gp_lens;      // lines by content (za_grep.hip, section 5f): prefilter + pattern table + patterns, bits / summary / carry per tile, rows and their lengths
+    std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
     uint8_t *h_tab = nullptr; size_t h_tab_cap = 0;
@@ -264,6 +272,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->dt_items.release(); c->dt_best.release(); c->dt_state.release();
     c->bg_len.release(); c->bg_table.release(); c->bg_slices.release(); c->bg_sstat.release(); c->bg_out.release();
     c->bg_rows.release(); c->bg_q.release(); c->bg_pos.release(); c->bg_pstat.release(); c->bg_pre.release(); c->bg_rlen.release();
+    c->gp_par.release(); c->gp_bits.release(); c->gp_tiles.release(); c->gp_carry.release(); c->gp_rows.release(); c->gp_lens.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -3624,6 +3633,135 @@ try {
     } else if (*out_len > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");      // (lengths and verdicts are there; only the lines are not)
     if (*out_len) { const int rc_ = d2h_payload(c, out, c->bg_out.p, *out_len); if (rc_) return rc_; }
     return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- lines by content (za_grep.hip)
+// The patterns as the caller gave them: judged on the host, before a context is touched or anything is launched.
+static bool grep_patterns_ok(const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim)
+{
+    if (!patterns || !table || n_patterns < 1 || n_patterns > ZNGAMD_BGZF_GREP_MAX_PATTERNS || delim < 0 || delim > 255) return false;
+    for (uint32_t i = 0; i < n_patterns; i++) {
+        const uint32_t off = table[i].off, len = table[i].len;
+        if (len < 1 || len > ZNGAMD_BGZF_GREP_MAX_PATTERN || off > patterns_len || patterns_len - off < len) return false;
+        if (memchr(patterns + off, delim, len)) return false;
+    }
+    return true;
+}
+
+#define ZA_GREP_PAR_TABLE (ZA_GREP_PAIR_WORDS * 4u)                                // the parameter block: prefilter bits, pattern table, patterns
+#define ZA_GREP_PAR_BLOB  (ZA_GREP_PAR_TABLE + ZA_GREP_MAX_PAT * (uint32_t)sizeof(ZaGrepPat))
+
+// decode, cover, mark, scan, [the host waits for the totals], emit, offsets, place, gather.  own: the host form (rows and lines go to
+// the context's buffers, as long as the totals say).
+static int bgzf_grep_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
+                         uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                         uint32_t delim, uint32_t flags, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                         ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own, zngamd_bgzf_grep_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    if (text_off > text_end || text_end > scratch_cap) return fail(c, ZNGAMD_E_ARG, "the text lies outside the scratch");
+    if (text_end - text_off >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "a text of 4 GiB or more");
+    const uint64_t tile0 = text_off / ZA_GREP_TILE;
+    const uint32_t ntiles = text_end > text_off ? (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull) : 0u;
+    // the parameter block: a bit per pair of bytes that opens a pattern (a one-byte pattern: every pair with that first byte)
+    std::vector<uint8_t> &par = c->gp_host;
+    par.assign((size_t)ZA_GREP_PAR_BLOB + patterns_len + 1u, 0);
+    uint32_t *pairs = (uint32_t *)par.data();
+    for (uint32_t i = 0; i < n_patterns; i++) {
+        const uint8_t *p = patterns + table[i].off;
+        if (table[i].len == 1) for (uint32_t b = 0; b < 256u; b++) { const uint32_t pr = p[0] | b << 8; pairs[pr >> 5] |= 1u << (pr & 31u); }
+        else { const uint32_t pr = p[0] | (uint32_t)p[1] << 8; pairs[pr >> 5] |= 1u << (pr & 31u); }
+    }
+    memcpy(par.data() + ZA_GREP_PAR_TABLE, table, (size_t)n_patterns * sizeof(ZaGrepPat));
+    memcpy(par.data() + ZA_GREP_PAR_BLOB, patterns, patterns_len);
+    HIPCHK(c, c->gp_par.ensure(par.size())); HIPCHK(c, c->gp_bits.ensure((size_t)ntiles * 256u + 1u)); HIPCHK(c, c->gp_tiles.ensure(ntiles + 1u));
+    HIPCHK(c, c->gp_carry.ensure(ntiles + 1u));
+    HIPCHK(c, hipMemcpyAsync(c->gp_par.p, par.data(), par.size(), hipMemcpyHostToDevice, c->stream));
+    ZaGrepTotals *d_tot = (ZaGrepTotals *)c->d_small;
+    unsigned long long *d_cover = (unsigned long long *)((uint8_t *)c->d_small + 64);
+    uint64_t *d_bytes = (uint64_t *)((uint8_t *)c->d_small + 128);
+    HIPCHK(c, hipMemsetAsync(d_cover, 0, 16, c->stream));
+    if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      if (n_members) hipLaunchKernelGGL(za_k_grep_cover, dim3((n_members + 255u) / 256u), dim3(256), 0, c->stream, d_members, d_status, n_members, scratch_cap,
+                                        text_off, text_end, d_cover);
+      if (ntiles) hipLaunchKernelGGL(za_k_grep_mark, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
+                                     (const uint32_t *)c->gp_par.p, (const ZaGrepPat *)(c->gp_par.p + ZA_GREP_PAR_TABLE), c->gp_par.p + ZA_GREP_PAR_BLOB, n_patterns,
+                                     delim, flags, c->gp_bits.p, c->gp_tiles.p);
+      hipLaunchKernelGGL(za_k_grep_scan, dim3(1), dim3(ZA_GREP_SCAN_THREADS), 0, c->stream, c->gp_tiles.p, ntiles, tile0, text_off, text_end, flags, line_base,
+                         d_cover, c->gp_carry.p, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    totals->reserved = 0;
+    if (!totals->covered || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !totals->matched) return ZNGAMD_OK;
+    const uint64_t n = totals->matched;
+    if (own) {
+        HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(totals->bytes + 64));
+        d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; out_cap = totals->bytes;
+    } else if (n > rows_cap || totals->bytes > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
+    const uint32_t grid = (uint32_t)((n + 255u) / 256u);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_grep_emit, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_tot, tile0, line_base, text_end,
+                         d_rows, n, c->gp_lens.p);
+      hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n <= 64 ? 64 : 1024), 0, c->stream, c->gp_lens.p, (uint32_t)n, 0u, 0ull, c->st_off.p, d_bytes,
+                         (const ZaUnit *)nullptr);
+      hipLaunchKernelGGL(za_k_grep_place, dim3(grid), dim3(256), 0, c->stream, d_rows, c->st_off.p, n, c->bg_slices.p);
+      hipLaunchKernelGGL(za_k_slice_gather, dim3((uint32_t)n), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, c->bg_slices.p,
+                         d_out, totals->bytes, c->bg_sstat.p); }
+    c->bgzf_stats[2] += n;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_grep_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                         uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                         int delim, uint32_t flags, uint64_t line_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                         zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_grep_totals *totals)
+try {
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (flags & ~15u) || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) ||
+        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_grep_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, patterns, patterns_len, table,
+                          n_patterns, (uint32_t)delim, flags, line_base, (uint8_t *)d_scratch, scratch_cap, d_status, (ZaGrepRow *)d_rows, rows_cap,
+                          (uint8_t *)d_out, out_cap, false, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_grep(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                     uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim,
+                     uint32_t flags, uint64_t line_base, int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap,
+                     zngamd_alloc_fn alloc, void *user, zngamd_bgzf_grep_totals *totals)
+try {
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (flags & ~15u) || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!out && out_cap) ||
+        (alloc && (rows || out))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    r = bgzf_grep_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, (uint32_t)delim, flags,
+                      line_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, true, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t n = totals->matched;
+    if (!totals->covered || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !n) return ZNGAMD_OK;
+    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
+        rows = (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow));
+        out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr;
+        if (!rows || !out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (n > rows_cap || totals->bytes > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return d2h_payload(c, out, c->bg_out.p, totals->bytes);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_stats(zngamd_ctx *c, uint64_t *out, int reset)

@@ -82,7 +82,7 @@ SYMBOLS = [
     "zngamd_train_dict_dev", "zngamd_train_dict",
     "zngamd_bgzf_compress_dev", "zngamd_bgzf_compress", "zngamd_bgzf_scan", "zngamd_bgzf_read_dev", "zngamd_bgzf_read", "zngamd_bgzf_stats",
     "zngamd_bgzf_count_dev", "zngamd_bgzf_count", "zngamd_bgzf_line_positions_dev", "zngamd_bgzf_line_positions", "zngamd_bgzf_read_lines_dev",
-    "zngamd_bgzf_read_lines",
+    "zngamd_bgzf_read_lines", "zngamd_bgzf_grep_dev", "zngamd_bgzf_grep",
 ]
 
 
@@ -140,6 +140,24 @@ BGZF_SLICE_OK, BGZF_SLICE_BLOCK, BGZF_SLICE_TABLE = 0, 1, 2
 BGZF_SLICE_RANK = 3                            # ZNGAMD_BGZF_SLICE_RANK: a rank beyond the block's delimiter count (a stale line index)
 BGZF_RANK_END = 0xFFFFFFFF                     # ZNGAMD_BGZF_RANK_END: the position one past a block's last byte
 BGZF_COUNT_LAST = 1                            # ZNGAMD_BGZF_COUNT_LAST
+BGZF_GREP_INVERT, BGZF_GREP_LINE_START, BGZF_GREP_FINAL, BGZF_GREP_COUNT_ONLY = 1, 2, 4, 8      # ZNGAMD_BGZF_GREP_*
+BGZF_GREP_MAX_PATTERNS, BGZF_GREP_MAX_PATTERN = 64, 255
+GREP_ROW_DTYPE = np.dtype([("src_off", "<u8"), ("number", "<u8"), ("len", "<u4"), ("reserved", "<u4")])      # zngamd_bgzf_grep_row
+
+
+class BgzfGrepTotals(C.Structure):             # zngamd_bgzf_grep_totals
+    _fields_ = [("seen", C.c_uint64), ("matched", C.c_uint64), ("bytes", C.c_uint64), ("tail_off", C.c_uint64),
+                ("covered", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def grep_pattern_table(patterns):
+    """the patterns (bytes objects) as zngamd_bgzf_grep takes them -> (blob, uint32[n, 2] of (off, len))"""
+    blob = b"".join(patterns)
+    lens = np.array([len(p) for p in patterns], np.uint32)
+    tab = np.empty((len(patterns), 2), np.uint32)
+    tab[:, 1] = lens
+    tab[:, 0] = np.cumsum(lens, dtype=np.uint64) - lens
+    return blob, tab
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -234,6 +252,11 @@ def load():
             L.zngamd_bgzf_read_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
             L.zngamd_bgzf_read.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, u8p, C.c_uint64, vp, vp]
             L.zngamd_bgzf_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        if hasattr(L, "zngamd_bgzf_grep"):
+            L.zngamd_bgzf_grep_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int,
+                                               C.c_uint32, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_grep.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int,
+                                           C.c_uint32, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
         if hasattr(L, "zngamd_bgzf_count"):
             L.zngamd_bgzf_count_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, vp]
             L.zngamd_bgzf_count.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_int, vp, vp]
@@ -1167,6 +1190,63 @@ class Context:
                                                         v(d_scratch), scratch_cap, v(d_out), out_cap, C.byref(ol), v(d_range_len), v(d_status),
                                                         v(d_range_status)), (OK, BUF_ERROR))
         return r, ol.value
+
+    def bgzf_grep(self, data, members, text_off, text_end, blob, table, delim, flags, line_base=0, caps=None):
+        """zngamd_bgzf_grep: data = packed compressed blocks, members = numpy table of MEMBER rows, (blob, table) as
+        grep_pattern_table gives them -> (code, block statuses, totals, rows (GREP_ROW_DTYPE), packed lines).  caps None: rows and
+        lines are allocated once the engine knows their sizes; (rows, bytes): buffers of those sizes, and code is BUF_ERROR (nothing
+        written) when the result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        table = np.ascontiguousarray(table, np.uint32)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfGrepTotals()
+        box = []
+
+        def alloc(_user, nbytes):
+            if not box:
+                arr = np.empty(nbytes // GREP_ROW_DTYPE.itemsize, GREP_ROW_DTYPE)
+                box.append(arr)
+                return arr.ctypes.data
+            obj, addr = _new_bytes(nbytes)
+            box.append(obj)
+            return addr.value
+
+        if caps is None:
+            rp, rcap, op, ocap, fn = None, 0, None, 0, ALLOC_FN(alloc)
+        else:
+            rows = np.zeros(max(1, caps[0]), GREP_ROW_DTYPE)
+            out, op = _new_bytes(caps[1])
+            rp, rcap, ocap, fn = C.c_void_p(rows.ctypes.data), caps[0], caps[1], ALLOC_FN()
+            if not ocap:
+                op = None
+            if not rcap:
+                rp = None
+        bp, bkeep = _addr(blob)
+        r = self._chk(self.L.zngamd_bgzf_grep(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                              text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table), delim, flags,
+                                              line_base, C.c_void_p(st.ctypes.data), rp, rcap, op, ocap, fn, None, C.byref(tot)),
+                      (OK, BUF_ERROR))
+        got = r == OK and tot.covered and tot.matched and not flags & BGZF_GREP_COUNT_ONLY
+        if caps is None:
+            rows_out = box[0] if got else np.empty(0, GREP_ROW_DTYPE)
+            packed = box[1] if got else b""
+        else:
+            rows_out = rows[:tot.matched] if got else np.empty(0, GREP_ROW_DTYPE)
+            packed = _take(out, tot.bytes) if got else b""
+        return r, st[:nm], tot, rows_out, packed
+
+    def bgzf_grep_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, line_base, d_scratch,
+                      scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap):
+        """zngamd_bgzf_grep_dev on device pointers (the patterns: host memory) -> (code, totals); rows and lines stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        table = np.ascontiguousarray(table, np.uint32)
+        tot = BgzfGrepTotals()
+        bp, bkeep = _addr(blob)
+        r = self._chk(self.L.zngamd_bgzf_grep_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob),
+                                                  C.c_void_p(table.ctypes.data), len(table), delim, flags, line_base, v(d_scratch), scratch_cap,
+                                                  v(d_status), v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
 
     def bgzf_stats(self, reset=True):
         """(decode launches, blocks decoded, slices gathered) of the ranged reads since the last reset"""

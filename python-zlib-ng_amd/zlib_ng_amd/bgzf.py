@@ -20,6 +20,11 @@ offset inside that block's output -- what .bai, .tbi and .csi indexes store, and
         recs = r.read_lines(idx, [(40_000_000, 4000)])       # lines by number: planned on the index, one launch
         cuts = idx.shards(r, 8, lines_per_record=4)          # nine virtual offsets: eight parts that differ by at most one record
 
+    hits = bgzf.grep("calls.vcf.gz", b"chr7\t", line_start=True)      # lines by content: matched on the GPU where the blocks were
+    for number, voffset, line in zip(hits.numbers, hits.voffsets, hits):      # decoded; only the matching lines come back
+        ...
+    n = bgzf.grep("reads.fastq.gz", [b"ACGTTGCA", b"TGCAACGT"], count=True, start=cuts[2], stop=cuts[3])
+
 The .gzi index (`GziIndex`) maps uncompressed offsets to blocks.  On disk, little-endian: a u64 count, then for every data block
 AFTER the first a pair of u64 (compressed offset, uncompressed offset).  save() writes no entry for the EOF block; load() accepts a
 file whose last entry points at it.  An index is untrusted: load() and the reader check it before it steers a read.
@@ -34,7 +39,7 @@ import numpy as np
 from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
-           "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT"]
+           "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "GrepResult"]
 
 BadGzipFile = zlib_ng.BadGzipFile
 MAX_BLOCK_INPUT = 65280                       # htslib's 0xff00
@@ -46,6 +51,7 @@ SLICE_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("len", "<u4"), 
 BLOCK_DTYPE = np.dtype([("coffset", "<u8"), ("uoffset", "<u8"), ("csize", "<u4"), ("isize", "<u4")])      # zngamd_bgzf_block
 _WRITE_BATCH = (64 << 20) // MAX_BLOCK_INPUT * MAX_BLOCK_INPUT      # input bytes per engine call of the writer: about 64 MiB
 _READ_WINDOW = 32 << 20                       # compressed bytes per window of the sequential reader
+_GREP_TEXT = 1 << 30                          # decoded bytes per window of grep at most (one engine call searches less than 4 GiB)
 _builtin_open = open
 
 
@@ -519,6 +525,237 @@ class LineIndex:
             raise ValueError("shards: n and lines_per_record are at least 1")
         records = (self.lines + k - 1) // k
         return reader.line_voffsets(self, [min(i * records // n * k, self.lines) for i in range(n + 1)])
+
+
+# ---- lines by content
+class GrepResult:
+    """What grep() found: len() lines; numbers (int64, ascending), voffsets (uint64, the normalised virtual offset of each line's first
+    byte: seek() goes there), offsets (int64, n + 1 of them) into data (the lines packed, each with its delimiter); result[i], slices
+    and iteration yield bytes.  searched: the lines that were looked at."""
+
+    def __init__(self, numbers, voffsets, offsets, data, searched):
+        self.numbers = np.asarray(numbers, np.int64)
+        self.voffsets = np.asarray(voffsets, np.uint64)
+        self.offsets = np.asarray(offsets, np.int64)
+        self.data = data
+        self.searched = int(searched)
+        if len(self.offsets) != len(self.numbers) + 1 or len(self.voffsets) != len(self.numbers):
+            raise ValueError("GrepResult: arrays of different lengths")
+
+    def __len__(self):
+        return len(self.numbers)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(len(self)))]
+        n = len(self)
+        k = int(i)
+        if not -n <= k < n:
+            raise IndexError("GrepResult index out of range")
+        k %= n
+        return bytes(self.data[int(self.offsets[k]):int(self.offsets[k + 1])])
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+    def __repr__(self):
+        return f"<GrepResult: {len(self)} of {self.searched} lines, {int(self.offsets[-1])} bytes>"
+
+
+def _grep_patterns(patterns, delimiter):
+    """-> (list of bytes, delimiter as bytes); ValueError as grep() documents it"""
+    delimiter = bytes(delimiter)
+    if len(delimiter) != 1:
+        raise ValueError("the delimiter is exactly one byte")
+    if isinstance(patterns, (bytes, bytearray, memoryview)):
+        patterns = [patterns]
+    pats = [bytes(p) for p in patterns]
+    if not 1 <= len(pats) <= _lib.BGZF_GREP_MAX_PATTERNS:
+        raise ValueError(f"grep takes 1 to {_lib.BGZF_GREP_MAX_PATTERNS} patterns, not {len(pats)}")
+    for p in pats:
+        if not 1 <= len(p) <= _lib.BGZF_GREP_MAX_PATTERN:
+            raise ValueError(f"a pattern has 1 to {_lib.BGZF_GREP_MAX_PATTERN} bytes, not {len(p)}")
+        if delimiter in p:
+            raise ValueError("a pattern cannot contain the delimiter")
+    return pats, delimiter
+
+
+def _grep_window(coffs, isizes, text_off, stop, ended, text_cap):
+    """Which part of a window is searched.  coffs / isizes: file offset and ISIZE of the window's blocks, in file order; text_off: where
+    the first line starts in the first block's output; stop: None or (coffset, uoffset), the line start in front of which the search
+    ends; ended: the file holds nothing behind these blocks; text_cap: decoded bytes per engine call at most.
+    -> (blocks to decode, text_end as an offset into their packed output, final: the bytes behind the last delimiter are a line)"""
+    n = len(coffs)
+    ends = np.cumsum(isizes, dtype=np.int64)
+    if n and int(ends[-1]) > text_cap:                       # (at least one block; what is cut off comes with the next window)
+        n, ended = max(1, int(np.searchsorted(ends, text_cap, "right"))), False
+    text_end, final = (int(ends[n - 1]) if n else 0), ended
+    if stop is not None and n:
+        c, u = stop
+        k = int(np.searchsorted(coffs[:n], c))
+        if k < n:
+            if int(coffs[k]) != c:
+                raise ValueError(f"stop: no block starts at compressed offset {c}")
+            if u > int(isizes[k]):
+                raise ValueError(f"stop: virtual offset points {u} bytes into a block of {int(isizes[k])}")
+            n, text_end, final = k + (1 if u else 0), int(ends[k]) - int(isizes[k]) + u, True
+    if text_end < text_off:
+        raise ValueError("stop lies in front of start")
+    return n, text_end, final
+
+
+def _grep_advance(isizes, n_use, text_off, text_end, tail_off, final, window, max_line):
+    """Where the next window begins.  tail_off: where the engine says the open line starts (text_end: there is none).
+    -> None when the search is over, else (index of the block the next window starts with -- n_use: the block behind this window --,
+    text_off in that block's output, compressed bytes to read).  The blocks from the open line's first one on are decoded again with
+    the next window; a window in which no line ended is read again twice as large.  ValueError (with the index of the block and the
+    offset in it where the line starts) for a line that has not ended after max_line bytes."""
+    if final:
+        return None
+    if tail_off >= text_end:
+        return n_use, 0, window
+    starts = np.cumsum(isizes[:n_use], dtype=np.int64) - isizes[:n_use]
+    b = int(np.searchsorted(starts, tail_off, "right")) - 1
+    off = tail_off - int(starts[b])
+    if text_end - tail_off > max_line:
+        raise _LongLine(b, off)
+    if b == 0 and off == text_off:
+        window *= 2
+    return b, off, window
+
+
+class _LongLine(ValueError):
+    def __init__(self, block, offset):
+        super().__init__(block, offset)
+        self.block, self.offset = block, offset
+
+
+def _read_full(fp, mv):
+    """fill mv from fp's position; fewer bytes only at the end of the file"""
+    into, got = getattr(fp, "readinto", None), 0
+    while got < len(mv):
+        if into is not None:
+            n = into(mv[got:]) or 0
+        else:
+            chunk = fp.read(len(mv) - got)
+            n = len(chunk)
+            mv[got:got + n] = chunk
+        if not n:
+            break
+        got += n
+    return got
+
+
+def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line):
+    pats, delimiter = _grep_patterns(patterns, delimiter)
+    max_line = int(max_line)
+    if not 1 <= max_line <= 1 << 31:
+        raise ValueError("max_line lies between 1 and 2**31")
+    if max_count is not None and int(max_count) < 0:
+        raise ValueError("max_count is not negative")
+    ctx = ctx or zlib_ng._ctx()                              # (the arguments are judged before a context is asked for)
+    blob, table = _lib.grep_pattern_table(pats)
+    flags = (_lib.BGZF_GREP_INVERT if invert else 0) | (_lib.BGZF_GREP_LINE_START if line_start else 0) | (_lib.BGZF_GREP_COUNT_ONLY if count else 0)
+    c_next, text_off = split_virtual_offset(start) if start is not None else (0, 0)
+    stop = split_virtual_offset(stop) if stop is not None else None
+    text_cap = max(_GREP_TEXT, max_line + 2 * MAX_BLOCK)
+    window, first, nblocks, line_base, searched, matched = _READ_WINDOW, True, 0, int(first_line), 0, 0
+    numbers, voffsets, lengths, pieces = [], [], [], []
+    buf = mv = None
+    try:
+        while (stop is None or stop > (c_next, text_off)) and (max_count is None or matched < max_count):
+            if buf is None or len(buf) < window + MAX_BLOCK:
+                if buf is not None:
+                    del mv
+                    _lib.give_buffer(buf)
+                buf = _lib.take_buffer(window + MAX_BLOCK)
+                mv = memoryview(buf)
+            fp.seek(c_next)
+            got = _read_full(fp, mv[:window + MAX_BLOCK])
+            if not got:
+                break
+            data = mv[:got]
+            ended = got < window + MAX_BLOCK
+            code, tab, used, total = _lib.bgzf_scan(data)
+            if ended and used < got and _cut_block(data[used:]):
+                raise EOFError(f"BGZF block {nblocks + len(tab)} at offset {c_next + used}: the file ends inside the block")
+            if code != _lib.OK or not tab:
+                raise _scan_error(code if c_next + used == 0 else _lib.DATA_ERROR, nblocks + len(tab), c_next + used)
+            t = np.array(tab, np.int64)
+            coffs, csizes, isizes = t[:, 0], t[:, 2], t[:, 3]
+            if first and text_off > int(isizes[0]):
+                raise ValueError(f"virtual offset points {text_off} bytes into a block of {int(isizes[0])}")
+            first = False
+            n_use, text_end, final = _grep_window(coffs + c_next, isizes, text_off, stop, ended and used == got, text_cap)
+            members, bad = _member_table(np.frombuffer(data, np.uint8), coffs[:n_use], csizes[:n_use], isizes[:n_use])
+            if bad >= 0:
+                raise BadGzipFile(f"BGZF block {nblocks + bad} at offset {c_next + int(coffs[bad])}: bad block header or block size")
+            cend = int(coffs[n_use - 1] + csizes[n_use - 1]) if n_use else 0
+            _, status, tot, rows, packed = ctx.bgzf_grep(data[:cend], members, text_off, text_end, blob, table, delimiter[0],
+                                                         flags | (_lib.BGZF_GREP_FINAL if final else 0), line_base)
+            bad = np.nonzero(status)[0]
+            if len(bad):
+                raise _block_error(c_next + int(coffs[bad[0]]), status[bad[0]])
+            if not tot.covered:
+                raise BadGzipFile(f"BGZF blocks at offset {c_next}: the decoded blocks do not cover the text")
+            searched, line_base, matched = searched + tot.seen, line_base + tot.seen, matched + tot.matched
+            if len(rows):
+                src = rows["src_off"].astype(np.int64)
+                at = np.searchsorted(members["out_off"].astype(np.int64), src, "right") - 1
+                numbers.append(rows["number"].astype(np.int64))
+                voffsets.append((coffs[at] + c_next).astype(np.uint64) << np.uint64(16) | (src - members["out_off"][at].astype(np.int64)).astype(np.uint64))
+                lengths.append(rows["len"].astype(np.int64))
+                pieces.append(packed)
+            try:
+                nxt = _grep_advance(isizes, n_use, text_off, text_end, int(tot.tail_off), final, window, max_line)
+            except _LongLine as e:
+                v = make_virtual_offset(c_next + int(coffs[e.block]), e.offset)
+                raise ValueError(f"the line at virtual offset {v} has not ended after {max_line} bytes (max_line)") from None
+            if nxt is None:
+                break
+            b, text_off, window = nxt
+            nblocks += b
+            c_next += int(coffs[b]) if b < len(coffs) else used
+    finally:
+        if buf is not None:
+            del mv
+            _lib.give_buffer(buf)
+    if count:
+        return matched if max_count is None else min(matched, int(max_count))
+    numbers = np.concatenate(numbers) if numbers else np.empty(0, np.int64)
+    voffsets = np.concatenate(voffsets) if voffsets else np.empty(0, np.uint64)
+    offsets = np.zeros(len(numbers) + 1, np.int64)
+    if lengths:
+        np.cumsum(np.concatenate(lengths), out=offsets[1:])
+    data = pieces[0] if len(pieces) == 1 else b"".join(pieces)
+    if max_count is not None and len(numbers) > max_count:
+        n = int(max_count)
+        numbers, voffsets, offsets = numbers[:n], voffsets[:n], offsets[:n + 1]
+        data = data[:int(offsets[-1])]
+    return GrepResult(numbers, voffsets, offsets, data, searched)
+
+
+def grep(file, patterns, *, delimiter=b"\n", invert=False, line_start=False, count=False, max_count=None, start=None, stop=None,
+         first_line=0, max_line=64 << 20):
+    """The lines of a BGZF file (a path or a seekable binary file) that contain one of `patterns`: fixed byte strings, one bytes-like
+    object or 1 to 64 of them, 1 to 255 bytes each, none holding the delimiter byte (ValueError).  The file is read in windows; each
+    window's blocks are decoded in one launch and searched where they lie on the GPU, and only the matching lines, their numbers and
+    their places come back: a GrepResult.
+      line_start   the pattern must stand at the line's first byte      invert      the lines without a match
+      count        -> int, the number of matching lines; no line leaves the device
+      max_count    at most the first N matching lines; no window behind the one that reaches N is read
+      start, stop  virtual offsets of line starts (LineIndex.shards, BgzfReader.line_voffsets): the part of the file to search
+      first_line   the number of the first line searched
+      max_line     ValueError (naming the line's virtual offset) for a line that is still open after this many bytes of a window:
+                   the bound on the memory a file without delimiters can claim (at most 2**31)
+    A line ends with `delimiter` (one byte) and is returned with it; a non-empty remainder behind the last one is the last line.
+    BadGzipFile for a file that is not BGZF or a block that does not decode (with its offset; no partial result), EOFError for a
+    file that ends inside a block."""
+    if _is_path(file):
+        with _builtin_open(file, "rb") as f:
+            return grep(f, patterns, delimiter=delimiter, invert=invert, line_start=line_start, count=count, max_count=max_count,
+                        start=start, stop=stop, first_line=first_line, max_line=max_line)
+    return _grep_file(file, None, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line)
 
 
 def _scan_file(f):
@@ -1005,6 +1242,20 @@ class BgzfReader(io.BufferedIOBase):
             out[j] = bytes(mv[at:at + ln])
             at += ln
         return out
+
+    def grep(self, patterns, *, delimiter=b"\n", invert=False, line_start=False, count=False, max_count=None, start=None, stop=None,
+             first_line=0, max_line=64 << 20):
+        """bgzf.grep() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("grep() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _grep_file(self._fp, self._ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line,
+                              max_line)
+        finally:
+            self._fp.seek(at)
 
     def line_voffsets(self, index, lines):
         """[the virtual offset at which each of `lines` starts] -- what seek() takes.  Normalised: the offset inside the block is below
