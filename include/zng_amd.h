@@ -578,6 +578,91 @@ int zngamd_bgzf_grep(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const 
                      int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap,
                      zngamd_alloc_fn alloc, void *user, zngamd_bgzf_grep_totals *totals);
 
+/* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
+ * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM
+ * preset, is ZNGAMD_E_ARG), the columns of the name, the start and the end (from 1; col_end 0: none), the byte that opens a comment
+ * line, the lines at the top to skip.  A line ends with `delim`; one CR in front of it belongs to no field.  A line is skipped when
+ * its number is below conf.skip, its first byte is conf.meta or it is empty.  The interval [beg, end), zero-based: generic, beg =
+ * col_beg - 1 (with 0x10000: col_beg) and end = col_end, or beg + 1 without one; VCF, beg = POS - 1, end = beg + the length of
+ * column 4, or the value of the first END= that opens column 8 or follows a ';' in it, if digits follow it up to ';' or the column's
+ * end and it lies above beg; end <= beg becomes beg + 1.  A coordinate is 1 to 10 digits and nothing else.  A data line is bad,
+ * checked in this order, when (1) a needed column is missing (VCF: 1, 2 and 4), (2) a coordinate is not digits, (3) beg < 0 or end >
+ * 2^29, (4) its name equals the previous data line's and its beg is smaller.
+ *
+ * zngamd_bgzf_tabix: what an index of the text scratch[text_off, text_end) is made of.  Blocks, member table, text, delimiter,
+ * _FINAL, line_base and the cover contract (covered = 0: nothing is reported) are those of zngamd_bgzf_grep.  Data lines are counted
+ * from 0 in the order of the text (their ordinal).  Three tables come back:
+ *   names  one row per maximal run of data lines with the same name: where the name stands in the scratch, its length, the ordinal
+ *          and the line number of the run's first line; the names themselves packed in that order into `blob`
+ *   bins   one row per maximal run of data lines with the same name and the same bin (reg2bin, SAM specification 5.3): the scratch
+ *          offset of its first line and of the byte behind its last line, its name run, the bin, its first ordinal, its lines
+ *   wins   one row per data line that raises the running maximum of (end - 1) >> 14 within its name run: name run, that window, the
+ *          scratch offset of the line -- the windows between the previous row's and this one are first overlapped by this line
+ * Skipped lines break no run.  The totals first: with a bad line (bad_kind 1 .. 4, bad_line the smallest such line number, bad_src its
+ * scratch offset) the tables describe the data lines without those that are bad by (1) to (3): a caller that wants to know whether a
+ * name came back earlier than the bad line still can; an index is not to be built from them.  ZNGAMD_BUF_ERROR: a capacity is below
+ * its count; nothing is written.  *totals is always valid on ZNGAMD_OK and ZNGAMD_BUF_ERROR.  The tables are untrusted: no entry makes a kernel read or
+ * write outside the buffers. */
+typedef struct { int32_t format, col_seq, col_beg, col_end, meta, skip; } zngamd_tabix_conf;                  /* 24 B */
+typedef struct { uint64_t src_off, first, line; uint32_t len, reserved; } zngamd_tabix_name;                  /* 32 B */
+typedef struct { uint64_t src_beg, src_end, first, lines; uint32_t name, bin; } zngamd_tabix_bin;             /* 40 B */
+typedef struct { uint64_t src_off; uint32_t name, window; } zngamd_tabix_win;                                 /* 16 B */
+typedef struct {
+    uint64_t seen;         /* lines of the text that were decided (the open tail is not one of them) */
+    uint64_t data;         /* of them, data lines */
+    uint64_t tail_off;     /* scratch offset where the open line starts; text_end when there is none */
+    uint64_t bad_line;     /* bad_kind != 0: the smallest number of a bad line */
+    uint64_t bad_src;      /*                where that line starts in the scratch */
+    uint64_t n_names, name_bytes, n_bins, n_wins;      /* rows of the three tables, bytes of the packed names */
+    uint64_t first_line;   /* data != 0: the number of the first data line, */
+    uint64_t first_src;    /*            where it starts, */
+    uint32_t first_beg;    /*            its beg, */
+    uint32_t last_beg;     /*            and the last data line's (the caller compares across two calls) */
+    uint32_t covered;      /* 1: decoded blocks cover the text and the figures above describe it */
+    uint32_t bad_kind;     /* 0, or 1 .. 4 as numbered above */
+} zngamd_bgzf_tabix_totals;                                                                                    /* 104 B */
+#define ZNGAMD_BGZF_TABIX_FINAL      4u
+#define ZNGAMD_TABIX_MAX_POS         536870912      /* 2^29: the largest end a .tbi can hold */
+int zngamd_bgzf_tabix_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                          uint64_t text_off, uint64_t text_end, const zngamd_tabix_conf *conf, int delim, uint32_t flags,
+                          uint64_t line_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_tabix_name *d_names,
+                          uint64_t names_cap, void *d_blob, uint64_t blob_cap, zngamd_tabix_bin *d_bins, uint64_t bins_cap,
+                          zngamd_tabix_win *d_wins, uint64_t wins_cap, zngamd_bgzf_tabix_totals *totals);
+/* Host-buffer form: stages in and the member table; status and the tables come back.  A caller that cannot bound the tables passes
+ * NULL pointers, the capacities 0 and alloc: once the sizes are known it is asked for names, blob, bins and wins in this order; it is
+ * not asked for an empty one; NULL from it: ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_tabix(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                      uint64_t text_off, uint64_t text_end, const zngamd_tabix_conf *conf, int delim, uint32_t flags,
+                      uint64_t line_base, int32_t *status, zngamd_tabix_name *names, uint64_t names_cap, uint8_t *blob,
+                      uint64_t blob_cap, zngamd_tabix_bin *bins, uint64_t bins_cap, zngamd_tabix_win *wins, uint64_t wins_cap,
+                      zngamd_alloc_fn alloc, void *user, zngamd_bgzf_tabix_totals *totals);
+/* zngamd_bgzf_fetch: the lines of a region.  The blocks a plan needs and their member rows as zngamd_bgzf_read takes them, decoded
+ * once in one launch.  regions (host memory in both forms): 1 .. ZNGAMD_BGZF_FETCH_MAX_REGIONS rows {name_off, name_len, beg, end}
+ * into `names` (names_len bytes); anything else is ZNGAMD_E_ARG, found before anything is launched.  spans: rows {text_off, text_end,
+ * region} of the scratch; a span begins where a line begins and ends behind a delimiter or at the end of the decoded text (the bytes
+ * behind its last delimiter are a line); spans of different regions may overlap.  span_status[s]: ZNGAMD_BGZF_SLICE_OK; _TABLE (the
+ * span lies outside the scratch, is 4 GiB or longer or names no region); _BLOCK (blocks that decoded do not cover it): such a span
+ * selects nothing.  span_rows[s]: the lines span s selects.  A data line is selected when its name equals the region's, beg <
+ * region.end and end > region.beg; bad and skipped lines are never selected and are no error.  rows: {src_off, len, region} of the
+ * selected lines in span order, then in the order of the text; the lines packed in that order into out.  Totals, ZNGAMD_BUF_ERROR and
+ * alloc (rows, then lines) as for zngamd_bgzf_grep; _COUNT_ONLY: the totals, span_status and span_rows alone. */
+typedef struct { uint32_t name_off, name_len, beg, end; } zngamd_tabix_region;                                 /* 16 B */
+typedef struct { uint64_t text_off, text_end; uint32_t region, reserved; } zngamd_tabix_span;                 /* 24 B */
+typedef struct { uint64_t src_off; uint32_t len, region; } zngamd_tabix_row;                                  /* 16 B */
+typedef struct { uint64_t matched, bytes; } zngamd_bgzf_fetch_totals;                                         /* 16 B */
+#define ZNGAMD_BGZF_FETCH_COUNT_ONLY  8u
+#define ZNGAMD_BGZF_FETCH_MAX_REGIONS 4096u
+int zngamd_bgzf_fetch_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                          const zngamd_tabix_conf *conf, int delim, uint32_t flags, const uint8_t *names, uint32_t names_len,
+                          const zngamd_tabix_region *regions, uint32_t n_regions, const zngamd_tabix_span *d_spans, uint32_t n_spans,
+                          void *d_scratch, uint64_t scratch_cap, int32_t *d_status, int32_t *d_span_status, uint32_t *d_span_rows,
+                          zngamd_tabix_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_fetch_totals *totals);
+int zngamd_bgzf_fetch(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                      const zngamd_tabix_conf *conf, int delim, uint32_t flags, const uint8_t *names, uint32_t names_len,
+                      const zngamd_tabix_region *regions, uint32_t n_regions, const zngamd_tabix_span *spans, uint32_t n_spans,
+                      int32_t *status, int32_t *span_status, uint32_t *span_rows, zngamd_tabix_row *rows, uint64_t rows_cap,
+                      uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_fetch_totals *totals);
+
 /* ---- streaming: the zng_stream calling convention ------------------------------------------------
  * What a binding of the reference swaps in for zng_deflateInit2 / zng_deflate / zng_deflateSetDictionary / zng_deflateCopy /
  * zng_deflateEnd (zlib_ngmodule.c:394, :552, :743, :401, :811) and zng_inflateInit2 / zng_inflate / zng_inflateSetDictionary /

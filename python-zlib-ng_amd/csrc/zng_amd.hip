@@ -10,6 +10,7 @@
 #include "za_inflate_spans.hip"
 #include "za_bgzf.hip"
 #include "za_grep.hip"
+#include "za_tabix.hip"
 #include "za_batch.hip"
 #include "za_dict.hip"
 #include "za_checksum.hip"
@@ -39,6 +40,10 @@ static_assert(sizeof(zngamd_bgzf_pattern) == sizeof(ZaGrepPat) && sizeof(zngamd_
               ZNGAMD_BGZF_GREP_INVERT == ZA_GREP_INVERT && ZNGAMD_BGZF_GREP_LINE_START == ZA_GREP_LINE_START && ZNGAMD_BGZF_GREP_FINAL == ZA_GREP_FINAL &&
               ZNGAMD_BGZF_GREP_COUNT_ONLY == ZA_GREP_COUNT_ONLY && ZNGAMD_BGZF_GREP_MAX_PATTERNS == ZA_GREP_MAX_PAT && ZNGAMD_BGZF_GREP_MAX_PATTERN == ZA_GREP_MAX_LEN,
               "bgzf grep layout");
+static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_tabix_name) == sizeof(ZaTbxName) && sizeof(zngamd_tabix_bin) == sizeof(ZaTbxBin) &&
+              sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
+              sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
+              ZNGAMD_BGZF_TABIX_FINAL == ZA_TBX_FINAL && ZNGAMD_BGZF_FETCH_COUNT_ONLY == ZA_TBX_COUNT_ONLY && ZNGAMD_TABIX_MAX_POS == ZA_TBX_MAX_POS, "bgzf tabix layout");
 static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT + 32, "slot stride");
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
@@ -128,6 +133,12 @@ struct zngamd_ctx {
     uint64_t bgzf_stats[3] = {0, 0, 0};          // ranged reads: decode launches, blocks decoded, slices gathered (zngamd_bgzf_stats)
     DevBuf<ZaBgzfCount> bg_rows; DevBuf<ZaBgzfPos> bg_q; DevBuf<uint64_t> bg_pos; DevBuf<int32_t> bg_pstat, bg_pre; DevBuf<uint32_t> bg_rlen;      // lines (section 5e): count rows, position queries, positions and their verdicts, range lengths
     DevBuf<uint8_t> gp_par; DevBuf<ulonglong2> gp_bits; DevBuf<ZaGrepTile> gp_tiles; DevBuf<ZaGrepCarry> gp_carry; DevBuf<ZaGrepRow> gp_rows; DevBuf<uint32_t> gp_lens;      // lines by content (za_grep.hip, section 5f): prefilter + pattern table + patterns, bits / summary / carry per tile, rows and their lengths
+    // fields of a line (za_tabix.hip, section 5g): delimiter bits / number / delimiters in front per tile, the line records, the ordinals of
+    // the data lines, the five scanned arrays and the scans' partial results, state and totals; the tables; the region filter's tables
+    DevBuf<unsigned long long> tb_bits, tb_data, tb_name, tb_bin, tb_key, tb_raise, tb_blk, tb_tot; DevBuf<uint32_t> tb_tcnt, tb_di, tb_lens; DevBuf<uint64_t> tb_tbase;
+    DevBuf<ZaTbxLine> tb_lines; DevBuf<ZaTbxName> tb_names; DevBuf<ZaTbxBin> tb_bins; DevBuf<ZaTbxWin> tb_wins;
+    DevBuf<uint8_t> tb_par; DevBuf<ZaTbxSpan> tb_spans; DevBuf<ZaTbxRow> tb_rows; DevBuf<uint32_t> tb_srows; DevBuf<int32_t> tb_sstat; DevBuf<uint64_t> tb_sbase;
+    std::vector<uint8_t> tb_host;
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -272,6 +283,9 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->dt_items.release(); c->dt_best.release(); c->dt_state.release();
     c->bg_len.release(); c->bg_table.release(); c->bg_slices.release(); c->bg_sstat.release(); c->bg_out.release();
     c->bg_rows.release(); c->bg_q.release(); c->bg_pos.release(); c->bg_pstat.release(); c->bg_pre.release(); c->bg_rlen.release();
+    c->tb_bits.release(); c->tb_data.release(); c->tb_name.release(); c->tb_bin.release(); c->tb_key.release(); c->tb_raise.release(); c->tb_blk.release();
+    c->tb_tot.release(); c->tb_tcnt.release(); c->tb_di.release(); c->tb_lens.release(); c->tb_tbase.release(); c->tb_lines.release(); c->tb_names.release();
+    c->tb_bins.release(); c->tb_wins.release(); c->tb_par.release(); c->tb_spans.release(); c->tb_rows.release(); c->tb_srows.release(); c->tb_sstat.release(); c->tb_sbase.release();
     c->gp_par.release(); c->gp_bits.release(); c->gp_tiles.release(); c->gp_carry.release(); c->gp_rows.release(); c->gp_lens.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
@@ -3760,6 +3774,291 @@ try {
         if (!rows || !out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
     } else if (n > rows_cap || totals->bytes > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
     HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return d2h_payload(c, out, c->bg_out.p, totals->bytes);
+} ZA_ABI_GUARD
+
+// ---- fields of a line (za_tabix.hip)
+// The configuration as the caller gave it: judged on the host, before a context is touched or anything is launched.
+static bool tabix_conf_ok(const zngamd_tabix_conf *cf, int delim)
+{
+    if (!cf || delim < 0 || delim > 255) return false;
+    const int f = cf->format & 0xFFFF;
+    if ((cf->format & ~0x1FFFF) || (f != 0 && f != 2)) return false;              // (1 is the SAM preset: it needs CIGAR)
+    return cf->col_seq >= 1 && cf->col_beg >= 1 && cf->col_end >= 0 && cf->meta >= 0 && cf->meta <= 255 && cf->skip >= 0;
+}
+
+// one inclusive scan of v[0, n) in place (n >= 1); *d_total = the sum or the maximum of all
+static void tbx_scan(zngamd_ctx *c, unsigned long long *v, uint64_t n, int op, unsigned long long *d_total)
+{
+    const uint32_t nb = (uint32_t)((n + ZA_TBX_SCAN_ITEMS - 1u) / ZA_TBX_SCAN_ITEMS);
+    hipLaunchKernelGGL(za_k_tbx_reduce, dim3(nb), dim3(256), 0, c->stream, v, n, op, c->tb_blk.p);
+    hipLaunchKernelGGL(za_k_tbx_scan_blocks, dim3(1), dim3(1024), 0, c->stream, c->tb_blk.p, nb, op, d_total);
+    hipLaunchKernelGGL(za_k_tbx_apply, dim3(nb), dim3(256), 0, c->stream, v, n, op, c->tb_blk.p);
+}
+
+// tb_tot, in u64: [0, 8) ZaTbxState, [8, 10) the cover, [10] delimiters, [11] data lines, [12] name runs, [13] bin runs, [14] window rows,
+// [15] (the largest key), [16] bytes of the packed names
+// decode, cover, mark, offsets, [the host waits for the delimiter count], parse, the scans, [the host waits for the totals], emit,
+// finish, offsets, place, gather.  own: the host form (the tables go to the context's buffers, as long as the totals say).
+static int bgzf_tabix_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
+                          uint64_t text_end, const zngamd_tabix_conf *conf, uint32_t delim, uint32_t flags, uint64_t line_base, uint8_t *d_scratch,
+                          uint64_t scratch_cap, int32_t *d_status, ZaTbxName *d_names, uint64_t names_cap, uint8_t *d_blob, uint64_t blob_cap,
+                          ZaTbxBin *d_bins, uint64_t bins_cap, ZaTbxWin *d_wins, uint64_t wins_cap, bool own, zngamd_bgzf_tabix_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    if (text_off > text_end || text_end > scratch_cap) return fail(c, ZNGAMD_E_ARG, "the text lies outside the scratch");
+    if (text_end - text_off >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "a text of 4 GiB or more");
+    if (line_base >= (1ull << 60)) return fail(c, ZNGAMD_E_ARG, "line_base out of range");
+    const uint64_t tile0 = text_off / ZA_TBX_TILE;
+    const uint32_t ntiles = text_end > text_off ? (uint32_t)((text_end - 1ull) / ZA_TBX_TILE - tile0 + 1ull) : 0u;
+    ZaTbxConf cf;
+    memcpy(&cf, conf, sizeof cf);
+    HIPCHK(c, c->tb_tot.ensure(32)); HIPCHK(c, c->tb_bits.ensure((size_t)ntiles * 256u + 1u)); HIPCHK(c, c->tb_tcnt.ensure(ntiles + 1u));
+    HIPCHK(c, c->tb_tbase.ensure(ntiles + 1u));
+    unsigned long long *T = c->tb_tot.p;
+    ZaTbxState *d_st = (ZaTbxState *)T;
+    c->tb_host.assign(256, 0);
+    { ZaTbxState *h = (ZaTbxState *)c->tb_host.data(); h->bad_key = ~0ull; h->tail_off = text_end; }
+    HIPCHK(c, hipMemcpyAsync(T, c->tb_host.data(), 256, hipMemcpyHostToDevice, c->stream));
+    if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      if (n_members) hipLaunchKernelGGL(za_k_grep_cover, dim3((n_members + 255u) / 256u), dim3(256), 0, c->stream, d_members, d_status, n_members, scratch_cap,
+                                        text_off, text_end, T + 8);
+      if (ntiles) {
+          hipLaunchKernelGGL(za_k_tbx_mark, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0, delim, c->tb_bits.p,
+                             c->tb_tcnt.p);
+          hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(ntiles <= 64 ? 64 : 1024), 0, c->stream, c->tb_tcnt.p, ntiles, 0u, 0ull, c->tb_tbase.p,
+                             (uint64_t *)(T + 10), (const ZaUnit *)nullptr);
+      } }
+    HIPCHK(c, hipGetLastError());
+    unsigned long long h3[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h3, T + 8, sizeof h3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h3[0] != text_end - text_off || h3[1] != 0) { totals->tail_off = text_off; return ZNGAMD_OK; }      // not covered: nothing is reported
+    const uint64_t ndelim = h3[2], nl = ndelim + 1ull;
+    HIPCHK(c, c->tb_lines.ensure(nl)); HIPCHK(c, c->tb_data.ensure(nl)); HIPCHK(c, c->tb_name.ensure(nl)); HIPCHK(c, c->tb_bin.ensure(nl));
+    HIPCHK(c, c->tb_key.ensure(nl)); HIPCHK(c, c->tb_raise.ensure(nl)); HIPCHK(c, c->tb_di.ensure(nl)); HIPCHK(c, c->tb_blk.ensure(nl / ZA_TBX_SCAN_ITEMS + 2u));
+    HIPCHK(c, hipMemsetAsync(c->tb_data.p + ndelim, 0, 8, c->stream));
+    const uint32_t grid_l = (uint32_t)((nl + 255u) / 256u);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      if (ntiles) hipLaunchKernelGGL(za_k_tbx_parse, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, text_off, text_end, tile0, delim, flags, line_base, cf,
+                                     c->tb_bits.p, c->tb_tbase.p, nl, c->tb_lines.p, c->tb_data.p, d_st);
+      tbx_scan(c, c->tb_data.p, nl, ZA_TBX_SUM, T + 11);
+      hipLaunchKernelGGL(za_k_tbx_compact, dim3(grid_l), dim3(256), 0, c->stream, c->tb_data.p, nl, c->tb_di.p);
+      hipLaunchKernelGGL(za_k_tbx_edges, dim3(grid_l), dim3(256), 0, c->stream, d_scratch, c->tb_lines.p, c->tb_di.p, T + 11, nl, line_base, c->tb_name.p,
+                         c->tb_bin.p, d_st);
+      tbx_scan(c, c->tb_name.p, nl, ZA_TBX_SUM, T + 12);
+      tbx_scan(c, c->tb_bin.p, nl, ZA_TBX_SUM, T + 13);
+      hipLaunchKernelGGL(za_k_tbx_keys, dim3(grid_l), dim3(256), 0, c->stream, c->tb_lines.p, c->tb_di.p, T + 11, nl, c->tb_name.p, c->tb_key.p);
+      tbx_scan(c, c->tb_key.p, nl, ZA_TBX_MAX, T + 15);
+      hipLaunchKernelGGL(za_k_tbx_raise, dim3(grid_l), dim3(256), 0, c->stream, c->tb_key.p, T + 11, nl, c->tb_raise.p);
+      tbx_scan(c, c->tb_raise.p, nl, ZA_TBX_SUM, T + 14); }
+    HIPCHK(c, hipGetLastError());
+    unsigned long long H[16];
+    HIPCHK(c, hipMemcpyAsync(H, T, sizeof H, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ZaTbxState st;
+    memcpy(&st, H, sizeof st);
+    totals->covered = 1; totals->seen = ndelim + st.final_line; totals->data = H[11]; totals->tail_off = st.tail_off;
+    if (st.bad_key != ~0ull) {                            // a bad line: where it starts
+        totals->bad_kind = (uint32_t)(st.bad_key & 7u); totals->bad_line = st.bad_key >> 3;
+        const uint64_t k = totals->bad_line - line_base;
+        if (k >= nl) return fail(c, ZNGAMD_E_ARG, "bad line out of range");
+        HIPCHK(c, hipMemcpyAsync(&totals->bad_src, &c->tb_lines.p[k].start, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    const uint64_t nd = H[11];
+    if (!nd) return ZNGAMD_OK;
+    totals->first_line = st.first_line; totals->first_src = st.first_src; totals->first_beg = st.first_beg; totals->last_beg = st.last_beg;
+    totals->n_names = H[12]; totals->name_bytes = st.name_bytes; totals->n_bins = H[13]; totals->n_wins = H[14];
+    const uint64_t nn = H[12], nb = H[13], nw = H[14];
+    if (own) {
+        HIPCHK(c, c->tb_names.ensure(nn)); HIPCHK(c, c->tb_bins.ensure(nb)); HIPCHK(c, c->tb_wins.ensure(nw)); HIPCHK(c, c->bg_out.ensure(st.name_bytes + 64));
+        d_names = c->tb_names.p; names_cap = nn; d_bins = c->tb_bins.p; bins_cap = nb; d_wins = c->tb_wins.p; wins_cap = nw; d_blob = c->bg_out.p; blob_cap = st.name_bytes;
+    } else if (nn > names_cap || nb > bins_cap || nw > wins_cap || st.name_bytes > blob_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    HIPCHK(c, c->tb_lens.ensure(nn)); HIPCHK(c, c->st_off.ensure(nn)); HIPCHK(c, c->bg_slices.ensure(nn + 1)); HIPCHK(c, c->bg_sstat.ensure(nn + 1));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_tbx_emit, dim3((uint32_t)((nd + 255u) / 256u)), dim3(256), 0, c->stream, c->tb_lines.p, c->tb_di.p, nd, line_base, c->tb_name.p,
+                         c->tb_bin.p, c->tb_key.p, c->tb_raise.p, d_names, nn, c->tb_lens.p, d_bins, nb, d_wins, nw);
+      hipLaunchKernelGGL(za_k_tbx_finish, dim3((uint32_t)((nb + 255u) / 256u)), dim3(256), 0, c->stream, d_bins, nb, c->tb_lines.p, c->tb_di.p, nd);
+      hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(nn <= 64 ? 64 : 1024), 0, c->stream, c->tb_lens.p, (uint32_t)nn, 0u, 0ull, c->st_off.p, (uint64_t *)(T + 16),
+                         (const ZaUnit *)nullptr);
+      hipLaunchKernelGGL(za_k_tbx_place, dim3((uint32_t)((nn + 255u) / 256u)), dim3(256), 0, c->stream, d_names, c->st_off.p, nn, c->bg_slices.p);
+      if (st.name_bytes) hipLaunchKernelGGL(za_k_slice_gather, dim3((uint32_t)nn), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members,
+                                            c->bg_slices.p, d_blob, st.name_bytes, c->bg_sstat.p); }
+    c->bgzf_stats[2] += nn;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_tabix_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                          uint64_t text_end, const zngamd_tabix_conf *conf, int delim, uint32_t flags, uint64_t line_base, void *d_scratch,
+                          uint64_t scratch_cap, int32_t *d_status, zngamd_tabix_name *d_names, uint64_t names_cap, void *d_blob, uint64_t blob_cap,
+                          zngamd_tabix_bin *d_bins, uint64_t bins_cap, zngamd_tabix_win *d_wins, uint64_t wins_cap, zngamd_bgzf_tabix_totals *totals)
+try {
+    if (!tabix_conf_ok(conf, delim)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (flags & ~ZNGAMD_BGZF_TABIX_FINAL) || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) ||
+        (!d_names && names_cap) || (!d_blob && blob_cap) || (!d_bins && bins_cap) || (!d_wins && wins_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_tabix_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, conf, (uint32_t)delim, flags, line_base,
+                           (uint8_t *)d_scratch, scratch_cap, d_status, (ZaTbxName *)d_names, names_cap, (uint8_t *)d_blob, blob_cap, (ZaTbxBin *)d_bins, bins_cap,
+                           (ZaTbxWin *)d_wins, wins_cap, false, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_tabix(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                      uint64_t text_end, const zngamd_tabix_conf *conf, int delim, uint32_t flags, uint64_t line_base, int32_t *status,
+                      zngamd_tabix_name *names, uint64_t names_cap, uint8_t *blob, uint64_t blob_cap, zngamd_tabix_bin *bins, uint64_t bins_cap,
+                      zngamd_tabix_win *wins, uint64_t wins_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_tabix_totals *totals)
+try {
+    if (!tabix_conf_ok(conf, delim)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (flags & ~ZNGAMD_BGZF_TABIX_FINAL) || (!in && in_len) || (n_members && (!members || !status)) || (!names && names_cap) ||
+        (!blob && blob_cap) || (!bins && bins_cap) || (!wins && wins_cap) || (alloc && (names || blob || bins || wins))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    r = bgzf_tabix_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, conf, (uint32_t)delim, flags, line_base, c->st_out.p, scratch,
+                       c->mstatus.p, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, true, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t nn = totals->n_names, nb = totals->n_bins, nw = totals->n_wins, by = totals->name_bytes;
+    if (!totals->covered || !nn) return ZNGAMD_OK;
+    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now
+        names = (zngamd_tabix_name *)alloc(user, nn * sizeof(ZaTbxName));
+        blob = names && by ? (uint8_t *)alloc(user, by) : nullptr;
+        bins = names && (blob || !by) ? (zngamd_tabix_bin *)alloc(user, nb * sizeof(ZaTbxBin)) : nullptr;
+        wins = bins ? (zngamd_tabix_win *)alloc(user, nw * sizeof(ZaTbxWin)) : nullptr;
+        if (!names || (by && !blob) || !bins || !wins) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (nn > names_cap || nb > bins_cap || nw > wins_cap || by > blob_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    HIPCHK(c, hipMemcpyAsync(names, c->tb_names.p, (size_t)nn * sizeof(ZaTbxName), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(bins, c->tb_bins.p, (size_t)nb * sizeof(ZaTbxBin), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(wins, c->tb_wins.p, (size_t)nw * sizeof(ZaTbxWin), hipMemcpyDeviceToHost, c->stream));
+    if (by) HIPCHK(c, hipMemcpyAsync(blob, c->bg_out.p, by, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+static bool fetch_regions_ok(const uint8_t *names, uint32_t names_len, const zngamd_tabix_region *regions, uint32_t n_regions)
+{
+    if (!regions || (!names && names_len) || n_regions < 1 || n_regions > ZNGAMD_BGZF_FETCH_MAX_REGIONS) return false;
+    for (uint32_t i = 0; i < n_regions; i++)
+        if (regions[i].name_off > names_len || names_len - regions[i].name_off < regions[i].name_len) return false;
+    return true;
+}
+
+// decode, count per span, offsets, [the host waits for the totals], emit, offsets, place, gather
+static int bgzf_fetch_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, const zngamd_tabix_conf *conf,
+                          uint32_t delim, uint32_t flags, const uint8_t *names, uint32_t names_len, const zngamd_tabix_region *regions, uint32_t n_regions,
+                          const ZaTbxSpan *d_spans, uint32_t n_spans, uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status, int32_t *d_span_status,
+                          uint32_t *d_span_rows, ZaTbxRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own, zngamd_bgzf_fetch_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    if (n_spans >= (1u << 31)) return fail(c, ZNGAMD_E_ARG, "too many spans");
+    ZaTbxConf cf;
+    memcpy(&cf, conf, sizeof cf);
+    const size_t tab = (size_t)n_regions * sizeof(ZaTbxRegion);
+    c->tb_host.assign(tab + names_len + 1u, 0);
+    memcpy(c->tb_host.data(), regions, tab);
+    if (names_len) memcpy(c->tb_host.data() + tab, names, names_len);
+    HIPCHK(c, c->tb_par.ensure(c->tb_host.size())); HIPCHK(c, c->tb_tot.ensure(32)); HIPCHK(c, c->tb_sbase.ensure(n_spans + 1u));
+    HIPCHK(c, hipMemcpyAsync(c->tb_par.p, c->tb_host.data(), c->tb_host.size(), hipMemcpyHostToDevice, c->stream));
+    unsigned long long *T = c->tb_tot.p;                 // [0] bytes, [1] rows, [2] bytes again (the offsets of the lines)
+    HIPCHK(c, hipMemsetAsync(T, 0, 256, c->stream));
+    if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+    const ZaTbxRegion *d_reg = (const ZaTbxRegion *)c->tb_par.p;
+    const uint8_t *d_nm = c->tb_par.p + tab;
+    if (n_spans) {
+        ProfScope ps(c, ZNGAMD_K_GATHER);
+        hipLaunchKernelGGL(za_k_tbx_fetch<false>, dim3(n_spans), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, d_spans, d_reg,
+                           n_regions, d_nm, cf, delim, d_span_status, d_span_rows, T, (const uint64_t *)nullptr, (ZaTbxRow *)nullptr, 0ull, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n_spans <= 64 ? 64 : 1024), 0, c->stream, d_span_rows, n_spans, 0u, 0ull, c->tb_sbase.p,
+                           (uint64_t *)(T + 1), (const ZaUnit *)nullptr);
+    }
+    HIPCHK(c, hipGetLastError());
+    unsigned long long H[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(H, T, sizeof H, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    totals->bytes = H[0]; totals->matched = H[1];
+    const uint64_t n = H[1];
+    if ((flags & ZNGAMD_BGZF_FETCH_COUNT_ONLY) || !n) return ZNGAMD_OK;
+    if (n >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "2^32 rows or more");
+    if (own) {
+        HIPCHK(c, c->tb_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(H[0] + 64));
+        d_rows = c->tb_rows.p; rows_cap = n; d_out = c->bg_out.p; out_cap = H[0];
+    } else if (n > rows_cap || H[0] > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    HIPCHK(c, c->tb_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_tbx_fetch<true>, dim3(n_spans), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, d_spans, d_reg,
+                         n_regions, d_nm, cf, delim, d_span_status, d_span_rows, T, (const uint64_t *)c->tb_sbase.p, d_rows, n, c->tb_lens.p);
+      hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n <= 64 ? 64 : 1024), 0, c->stream, c->tb_lens.p, (uint32_t)n, 0u, 0ull, c->st_off.p, (uint64_t *)(T + 2),
+                         (const ZaUnit *)nullptr);
+      hipLaunchKernelGGL(za_k_tbx_place_rows, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, c->stream, d_rows, c->st_off.p, n, c->bg_slices.p);
+      hipLaunchKernelGGL(za_k_slice_gather, dim3((uint32_t)n), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, c->bg_slices.p,
+                         d_out, H[0], c->bg_sstat.p); }
+    c->bgzf_stats[2] += n;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_fetch_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, const zngamd_tabix_conf *conf,
+                          int delim, uint32_t flags, const uint8_t *names, uint32_t names_len, const zngamd_tabix_region *regions, uint32_t n_regions,
+                          const zngamd_tabix_span *d_spans, uint32_t n_spans, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, int32_t *d_span_status,
+                          uint32_t *d_span_rows, zngamd_tabix_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_fetch_totals *totals)
+try {
+    if (!tabix_conf_ok(conf, delim) || !fetch_regions_ok(names, names_len, regions, n_regions)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (flags & ~ZNGAMD_BGZF_FETCH_COUNT_ONLY) || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) ||
+        (n_spans && (!d_spans || !d_span_status || !d_span_rows)) || (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_fetch_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, conf, (uint32_t)delim, flags, names, names_len, regions,
+                           n_regions, (const ZaTbxSpan *)d_spans, n_spans, (uint8_t *)d_scratch, scratch_cap, d_status, d_span_status, d_span_rows,
+                           (ZaTbxRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_fetch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, const zngamd_tabix_conf *conf,
+                      int delim, uint32_t flags, const uint8_t *names, uint32_t names_len, const zngamd_tabix_region *regions, uint32_t n_regions,
+                      const zngamd_tabix_span *spans, uint32_t n_spans, int32_t *status, int32_t *span_status, uint32_t *span_rows, zngamd_tabix_row *rows,
+                      uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_fetch_totals *totals)
+try {
+    if (!tabix_conf_ok(conf, delim) || !fetch_regions_ok(names, names_len, regions, n_regions)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (flags & ~ZNGAMD_BGZF_FETCH_COUNT_ONLY) || (!in && in_len) || (n_members && (!members || !status)) ||
+        (n_spans && (!spans || !span_status || !span_rows)) || (!rows && rows_cap) || (!out && out_cap) || (alloc && (rows || out))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    HIPCHK(c, c->tb_spans.ensure(n_spans + 1u)); HIPCHK(c, c->tb_sstat.ensure(n_spans + 1u)); HIPCHK(c, c->tb_srows.ensure(n_spans + 1u));
+    if (n_spans) HIPCHK(c, hipMemcpyAsync(c->tb_spans.p, spans, (size_t)n_spans * sizeof(ZaTbxSpan), hipMemcpyHostToDevice, c->stream));
+    r = bgzf_fetch_dev(c, c->st_in.p, in_len, c->members.p, n_members, conf, (uint32_t)delim, flags, names, names_len, regions, n_regions, c->tb_spans.p, n_spans,
+                       c->st_out.p, scratch, c->mstatus.p, c->tb_sstat.p, c->tb_srows.p, nullptr, 0, nullptr, 0, true, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_spans) {
+        HIPCHK(c, hipMemcpyAsync(span_status, c->tb_sstat.p, (size_t)n_spans * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(span_rows, c->tb_srows.p, (size_t)n_spans * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t n = totals->matched;
+    if ((flags & ZNGAMD_BGZF_FETCH_COUNT_ONLY) || !n) return ZNGAMD_OK;
+    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
+        rows = (zngamd_tabix_row *)alloc(user, n * sizeof(ZaTbxRow));
+        out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr;
+        if (!rows || !out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (n > rows_cap || totals->bytes > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    HIPCHK(c, hipMemcpyAsync(rows, c->tb_rows.p, (size_t)n * sizeof(ZaTbxRow), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return d2h_payload(c, out, c->bg_out.p, totals->bytes);
 } ZA_ABI_GUARD

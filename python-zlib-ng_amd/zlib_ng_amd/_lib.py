@@ -83,6 +83,7 @@ SYMBOLS = [
     "zngamd_bgzf_compress_dev", "zngamd_bgzf_compress", "zngamd_bgzf_scan", "zngamd_bgzf_read_dev", "zngamd_bgzf_read", "zngamd_bgzf_stats",
     "zngamd_bgzf_count_dev", "zngamd_bgzf_count", "zngamd_bgzf_line_positions_dev", "zngamd_bgzf_line_positions", "zngamd_bgzf_read_lines_dev",
     "zngamd_bgzf_read_lines", "zngamd_bgzf_grep_dev", "zngamd_bgzf_grep",
+    "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
 ]
 
 
@@ -148,6 +149,32 @@ GREP_ROW_DTYPE = np.dtype([("src_off", "<u8"), ("number", "<u8"), ("len", "<u4")
 class BgzfGrepTotals(C.Structure):             # zngamd_bgzf_grep_totals
     _fields_ = [("seen", C.c_uint64), ("matched", C.c_uint64), ("bytes", C.c_uint64), ("tail_off", C.c_uint64),
                 ("covered", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+BGZF_TABIX_FINAL, BGZF_FETCH_COUNT_ONLY, BGZF_FETCH_MAX_REGIONS = 4, 8, 4096      # ZNGAMD_BGZF_TABIX_FINAL, ZNGAMD_BGZF_FETCH_*
+TABIX_MAX_POS = 1 << 29                        # ZNGAMD_TABIX_MAX_POS
+TABIX_NAME_DTYPE = np.dtype([("src_off", "<u8"), ("first", "<u8"), ("line", "<u8"), ("len", "<u4"), ("reserved", "<u4")])      # zngamd_tabix_name
+TABIX_BIN_DTYPE = np.dtype([("src_beg", "<u8"), ("src_end", "<u8"), ("first", "<u8"), ("lines", "<u8"), ("name", "<u4"), ("bin", "<u4")])      # zngamd_tabix_bin
+TABIX_WIN_DTYPE = np.dtype([("src_off", "<u8"), ("name", "<u4"), ("window", "<u4")])                      # zngamd_tabix_win
+TABIX_REGION_DTYPE = np.dtype([("name_off", "<u4"), ("name_len", "<u4"), ("beg", "<u4"), ("end", "<u4")])   # zngamd_tabix_region
+TABIX_SPAN_DTYPE = np.dtype([("text_off", "<u8"), ("text_end", "<u8"), ("region", "<u4"), ("reserved", "<u4")])      # zngamd_tabix_span
+TABIX_ROW_DTYPE = np.dtype([("src_off", "<u8"), ("len", "<u4"), ("region", "<u4")])                        # zngamd_tabix_row
+
+
+class TabixConf(C.Structure):                  # zngamd_tabix_conf
+    _fields_ = [("format", C.c_int32), ("col_seq", C.c_int32), ("col_beg", C.c_int32), ("col_end", C.c_int32), ("meta", C.c_int32),
+                ("skip", C.c_int32)]
+
+
+class BgzfTabixTotals(C.Structure):            # zngamd_bgzf_tabix_totals
+    _fields_ = [("seen", C.c_uint64), ("data", C.c_uint64), ("tail_off", C.c_uint64), ("bad_line", C.c_uint64), ("bad_src", C.c_uint64),
+                ("n_names", C.c_uint64), ("name_bytes", C.c_uint64), ("n_bins", C.c_uint64), ("n_wins", C.c_uint64),
+                ("first_line", C.c_uint64), ("first_src", C.c_uint64), ("first_beg", C.c_uint32), ("last_beg", C.c_uint32),
+                ("covered", C.c_uint32), ("bad_kind", C.c_uint32)]
+
+
+class BgzfFetchTotals(C.Structure):            # zngamd_bgzf_fetch_totals
+    _fields_ = [("matched", C.c_uint64), ("bytes", C.c_uint64)]
 
 
 def grep_pattern_table(patterns):
@@ -257,6 +284,15 @@ def load():
                                                C.c_uint32, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
             L.zngamd_bgzf_grep.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int,
                                            C.c_uint32, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
+        if hasattr(L, "zngamd_bgzf_tabix"):
+            L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
+                                                C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_tabix.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
+                                            vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
+            L.zngamd_bgzf_fetch_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_int, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp,
+                                                C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_fetch.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, vp, C.c_int, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp,
+                                            C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
         if hasattr(L, "zngamd_bgzf_count"):
             L.zngamd_bgzf_count_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, vp]
             L.zngamd_bgzf_count.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_int, vp, vp]
@@ -1246,6 +1282,123 @@ class Context:
         r = self._chk(self.L.zngamd_bgzf_grep_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob),
                                                   C.c_void_p(table.ctypes.data), len(table), delim, flags, line_base, v(d_scratch), scratch_cap,
                                                   v(d_status), v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def bgzf_tabix(self, data, members, text_off, text_end, conf, delim, flags, line_base=0, caps=None):
+        """zngamd_bgzf_tabix: conf = (format, col_seq, col_beg, col_end, meta, skip) -> (code, block statuses, totals, names
+        (TABIX_NAME_DTYPE), the names packed, bins (TABIX_BIN_DTYPE), wins (TABIX_WIN_DTYPE)).  caps None: the tables are allocated once
+        the engine knows their sizes; (names, name bytes, bins, wins): buffers of those sizes, and code is BUF_ERROR (nothing written)
+        when a table needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfTabixTotals()
+        cf = TabixConf(*[int(x) for x in conf])
+        dts = (TABIX_NAME_DTYPE, np.dtype("u1"), TABIX_BIN_DTYPE, TABIX_WIN_DTYPE)
+        box = []
+
+        def alloc(_user, nbytes):
+            k = len(box) + (1 if box and not tot.name_bytes else 0)      # (no call for names that are all empty)
+            arr = np.empty(nbytes // dts[k].itemsize, dts[k])
+            box.append(arr)
+            return arr.ctypes.data
+
+        if caps is None:
+            ptrs, fn = [None, 0] * 4, ALLOC_FN(alloc)
+        else:
+            bufs = [np.zeros(max(1, n), dt) for n, dt in zip(caps, dts)]
+            ptrs, fn = [], ALLOC_FN()
+            for b, n in zip(bufs, caps):
+                ptrs += [C.c_void_p(b.ctypes.data) if n else None, n]
+        r = self._chk(self.L.zngamd_bgzf_tabix(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm, text_off,
+                                               text_end, C.byref(cf), delim, flags, line_base, C.c_void_p(st.ctypes.data), *ptrs, fn, None,
+                                               C.byref(tot)), (OK, BUF_ERROR))
+        counts = (tot.n_names, tot.name_bytes, tot.n_bins, tot.n_wins)
+        if r != OK or not tot.covered or not tot.n_names:
+            out = [np.empty(0, dt) for dt in dts]
+        elif caps is None:
+            if not tot.name_bytes:
+                box.insert(1, np.empty(0, np.uint8))
+            out = box
+        else:
+            out = [b[:n] for b, n in zip(bufs, counts)]
+        return r, st[:nm], tot, out[0], out[1].tobytes(), out[2], out[3]
+
+    def bgzf_tabix_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, conf, delim, flags, line_base, d_scratch, scratch_cap,
+                       d_status, d_names, names_cap, d_blob, blob_cap, d_bins, bins_cap, d_wins, wins_cap):
+        """zngamd_bgzf_tabix_dev on device pointers -> (code, totals); the tables stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfTabixTotals()
+        cf = TabixConf(*[int(x) for x in conf])
+        r = self._chk(self.L.zngamd_bgzf_tabix_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, C.byref(cf), delim, flags,
+                                                   line_base, v(d_scratch), scratch_cap, v(d_status), v(d_names), names_cap, v(d_blob), blob_cap,
+                                                   v(d_bins), bins_cap, v(d_wins), wins_cap, C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def bgzf_fetch(self, data, members, conf, delim, flags, names, regions, spans, caps=None):
+        """zngamd_bgzf_fetch: names = the regions' names packed, regions = TABIX_REGION_DTYPE rows, spans = TABIX_SPAN_DTYPE rows ->
+        (code, block statuses, span verdicts, rows per span, totals, rows (TABIX_ROW_DTYPE), packed lines).  caps None: rows and lines
+        are allocated once the engine knows their sizes; (rows, bytes): buffers of those sizes, and code is BUF_ERROR when the result
+        needs more"""
+        nm, ns = len(members), len(spans)
+        p, keep = _addr(data)
+        regions = np.ascontiguousarray(regions, TABIX_REGION_DTYPE)
+        spans = np.ascontiguousarray(spans, TABIX_SPAN_DTYPE)
+        st = np.zeros(max(1, nm), np.int32)
+        ss = np.zeros(max(1, ns), np.int32)
+        sr = np.zeros(max(1, ns), np.uint32)
+        tot = BgzfFetchTotals()
+        cf = TabixConf(*[int(x) for x in conf])
+        box = []
+
+        def alloc(_user, nbytes):
+            if not box:
+                arr = np.empty(nbytes // TABIX_ROW_DTYPE.itemsize, TABIX_ROW_DTYPE)
+                box.append(arr)
+                return arr.ctypes.data
+            obj, addr = _new_bytes(nbytes)
+            box.append(obj)
+            return addr.value
+
+        if caps is None:
+            rp, rcap, op, ocap, fn = None, 0, None, 0, ALLOC_FN(alloc)
+        else:
+            rows = np.zeros(max(1, caps[0]), TABIX_ROW_DTYPE)
+            out, op = _new_bytes(caps[1])
+            rp, rcap, ocap, fn = C.c_void_p(rows.ctypes.data), caps[0], caps[1], ALLOC_FN()
+            if not ocap:
+                op = None
+            if not rcap:
+                rp = None
+        names = bytes(names)
+        bp, bkeep = _addr(names) if names else (None, None)
+        r = self._chk(self.L.zngamd_bgzf_fetch(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                               C.byref(cf), delim, flags, bp, len(names), C.c_void_p(regions.ctypes.data), len(regions),
+                                               C.c_void_p(spans.ctypes.data) if ns else None, ns, C.c_void_p(st.ctypes.data),
+                                               C.c_void_p(ss.ctypes.data), C.c_void_p(sr.ctypes.data), rp, rcap, op, ocap, fn, None,
+                                               C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and tot.matched and not flags & BGZF_FETCH_COUNT_ONLY
+        if caps is None:
+            rows_out = box[0] if got else np.empty(0, TABIX_ROW_DTYPE)
+            packed = box[1] if got else b""
+        else:
+            rows_out = rows[:tot.matched] if got else np.empty(0, TABIX_ROW_DTYPE)
+            packed = _take(out, tot.bytes) if got else b""
+        return r, st[:nm], ss[:ns], sr[:ns], tot, rows_out, packed
+
+    def bgzf_fetch_dev(self, d_in, in_len, d_members, n_members, conf, delim, flags, names, regions, d_spans, n_spans, d_scratch, scratch_cap,
+                       d_status, d_span_status, d_span_rows, d_rows, rows_cap, d_out, out_cap):
+        """zngamd_bgzf_fetch_dev on device pointers (the regions: host memory) -> (code, totals)"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        regions = np.ascontiguousarray(regions, TABIX_REGION_DTYPE)
+        tot = BgzfFetchTotals()
+        cf = TabixConf(*[int(x) for x in conf])
+        names = bytes(names)
+        bp, bkeep = _addr(names) if names else (None, None)
+        r = self._chk(self.L.zngamd_bgzf_fetch_dev(self.h, v(d_in), in_len, v(d_members), n_members, C.byref(cf), delim, flags, bp, len(names),
+                                                   C.c_void_p(regions.ctypes.data), len(regions), v(d_spans), n_spans, v(d_scratch), scratch_cap,
+                                                   v(d_status), v(d_span_status), v(d_span_rows), v(d_rows), rows_cap, v(d_out), out_cap,
+                                                   C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_stats(self, reset=True):

@@ -25,6 +25,10 @@ offset inside that block's output -- what .bai, .tbi and .csi indexes store, and
         ...
     n = bgzf.grep("reads.fastq.gz", [b"ACGTTGCA", b"TGCAACGT"], count=True, start=cuts[2], stop=cuts[3])
 
+    tbi = bgzf.TabixIndex.build("calls.vcf.gz", "vcf")                # lines by region: the fields of every line are read on the GPU, a
+    tbi.save("calls.vcf.gz.tbi")                                      # standard .tbi comes out; fetch() plans on it, decodes the blocks
+    rows = bgzf.fetch("calls.vcf.gz", tbi, "chr7:55,000,000-55,200,000")      # of the region's chunks and filters their lines on the GPU
+
 The .gzi index (`GziIndex`) maps uncompressed offsets to blocks.  On disk, little-endian: a u64 count, then for every data block
 AFTER the first a pair of u64 (compressed offset, uncompressed offset).  save() writes no entry for the EOF block; load() accepts a
 file whose last entry points at it.  An index is untrusted: load() and the reader check it before it steers a read.
@@ -39,7 +43,8 @@ import numpy as np
 from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
-           "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "GrepResult"]
+           "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "GrepResult",
+           "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins"]
 
 BadGzipFile = zlib_ng.BadGzipFile
 MAX_BLOCK_INPUT = 65280                       # htslib's 0xff00
@@ -758,6 +763,603 @@ def grep(file, patterns, *, delimiter=b"\n", invert=False, line_start=False, cou
     return _grep_file(file, None, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line)
 
 
+# ---- lines by region: a tabix index built on the GPU, and the rows of a region filtered there
+TABIX_MAGIC = b"TBI\x01"
+TABIX_PRESETS = {"gff": (0, 1, 4, 5, 35, 0), "bed": (0x10000, 1, 2, 3, 35, 0), "vcf": (2, 1, 2, 0, 35, 0)}
+TABIX_MAX_POS = 1 << 29                       # the largest end a .tbi can hold
+_TABIX_PSEUDO_BIN = 37450                     # htslib's bin of per-name statistics: read and dropped, never written
+_TABIX_MAX_LINE = 64 << 20                    # a line that is still open after this many bytes of a window: ValueError
+_TABIX_LEVELS = ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681))
+_TABIX_KINDS = {1: "a needed column is missing", 2: "a coordinate is not 1 to 10 digits", 3: "the interval leaves [0, 2**29]",
+                4: "its start lies below the previous line's of the same name", "contig": "its name came before, with other names in between"}
+
+
+def reg2bin(beg, end):
+    """the bin of [beg, end) (SAM specification section 5.3: five levels, 16 KiB leaves)"""
+    end -= 1
+    for shift, first in reversed(_TABIX_LEVELS):
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def reg2bins(beg, end):
+    """the bins that may hold a feature overlapping [beg, end)"""
+    end -= 1
+    out = [0]
+    for shift, first in _TABIX_LEVELS:
+        out.extend(range(first + (beg >> shift), first + (end >> shift) + 1))
+    return out
+
+
+def parse_region(region):
+    """"chr1:1,000-2,000" -> (b"chr1", 999, 2000): tabix's 1-based inclusive convention, commas ignored; "chr1" is the whole name and
+    "chr1:1000" reaches to the end.  A tuple (name, beg0, end0) is taken as zero-based half-open."""
+    if isinstance(region, tuple):
+        if len(region) != 3:
+            raise ValueError("a region tuple is (name, beg, end)")
+        name, beg, end = region
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        beg, end = int(beg), int(end)
+        if beg < 0 or end < 0:
+            raise ValueError("region coordinates are not negative")
+        return name, beg, end
+    text = region.encode() if isinstance(region, str) else bytes(region)
+    if not text:
+        raise ValueError("empty region")
+    name, sep, rest = text.rpartition(b":")
+    if sep:
+        rest = rest.replace(b",", b"")
+        lo, dash, hi = rest.partition(b"-")
+        if lo.isdigit() and (not dash or hi.isdigit()) and name:
+            a, b = int(lo), int(hi) if dash else TABIX_MAX_POS
+            if b < a:
+                raise ValueError(f"region {text!r}: the end lies below the start")
+            return name, max(a - 1, 0), b
+    return text, 0, TABIX_MAX_POS
+
+
+def _tabix_conf(preset, seq_col, start_col, end_col, zero_based, meta, skip):
+    """-> (format, col_seq, col_beg, col_end, meta, skip); ValueError as TabixIndex.build documents it"""
+    meta = bytes(meta)
+    skip = int(skip)
+    if len(meta) != 1:
+        raise ValueError("meta is exactly one byte")
+    if not 0 <= skip < 1 << 31:
+        raise ValueError("skip lies between 0 and 2**31 - 1")
+    if preset is not None:
+        if seq_col is not None or start_col is not None or end_col is not None or zero_based:
+            raise ValueError("a preset or columns, not both")
+        if preset == "sam":
+            raise ValueError("the SAM preset needs CIGAR: not supported")
+        if preset not in TABIX_PRESETS:
+            raise ValueError(f"unknown preset {preset!r}: gff, bed or vcf")
+        fmt, cs, cb, ce = TABIX_PRESETS[preset][:4]
+    else:
+        if seq_col is None or start_col is None:
+            raise ValueError("a preset, or seq_col and start_col")
+        fmt, cs, cb, ce = (0x10000 if zero_based else 0), int(seq_col), int(start_col), int(end_col or 0)
+        if not 1 <= cs < 1 << 31 or not 1 <= cb < 1 << 31 or not 0 <= ce < 1 << 31:
+            raise ValueError("columns are counted from 1")
+    return fmt, cs, cb, ce, meta[0], skip
+
+
+class _TabixBad(ValueError):
+    def __init__(self, line, kind, voffset):
+        super().__init__(f"line {line} at virtual offset {voffset} cannot be indexed: {_TABIX_KINDS[kind]}")
+        self.line, self.kind, self.voffset = line, kind, voffset
+
+
+class _TabixMerge:
+    """The tables of the windows become one index (pure host code).  Per window: names [(name, line, voffset)] per name run, bins
+    [(name run, bin, v_beg, v_end)] (v_end None: the run ends where the window's text ends), wins [(name run, window, voffset)],
+    the first and last beg of its data lines, head: the virtual offset of its first text byte (None: no text)."""
+
+    def __init__(self):
+        self.names, self.ids, self.bins, self.linear = [], {}, [], []
+        self.last = self.prev = self.open_end = None
+
+    def add(self, names, bins, wins, first_beg, last_beg, head=None, bad=None):
+        if self.open_end is not None and head is not None:
+            self.open_end[1], self.open_end = head, None
+        errs = [bad] if bad is not None else []
+        if names and self.prev is not None and names[0][0] == self.prev[0] and first_beg < self.prev[1]:
+            errs.append((names[0][1], 4, names[0][2]))        # out of order across the cut
+        run_ids = []
+        for name, line, v in names:
+            if self.names and self.names[-1] == name:
+                run_ids.append(len(self.names) - 1)
+            elif name in self.ids:
+                errs.append((line, "contig", v))
+                break
+            else:
+                self.ids[name] = len(self.names)
+                run_ids.append(len(self.names))
+                self.names.append(name)
+                self.bins.append({})
+                self.linear.append([])
+        if errs:
+            raise _TabixBad(*min(errs, key=lambda e: e[0]))
+        for run, b, vb, ve in bins:
+            i = run_ids[run]
+            if self.last == (i, b):
+                chunk = self.bins[i][b][-1]
+                chunk[1] = ve
+            else:
+                chunk = [vb, ve]
+                self.bins[i].setdefault(b, []).append(chunk)
+                self.last = (i, b)
+            self.open_end = chunk if ve is None else None
+        for run, w, v in wins:
+            lin = self.linear[run_ids[run]]
+            if w >= len(lin):                               # this line is the first to reach the windows up to w
+                lin.extend([v] * (w + 1 - len(lin)))
+        if names:
+            self.prev = (names[-1][0], last_beg)
+
+    def finish(self, conf, end_v):
+        """end_v: the virtual offset behind the file's last data byte"""
+        if self.open_end is not None:
+            self.open_end[1], self.open_end = end_v, None
+        return TabixIndex(conf, self.names, [{b: [tuple(c) for c in cs] for b, cs in d.items()} for d in self.bins], self.linear)
+
+
+def _tabix_voffsets(src, out_offs, isizes, coffs):
+    """scratch offsets -> (normalised virtual offsets, mask: the offset lies at or behind the end of the decoded blocks).  out_offs /
+    isizes / coffs: where each decoded block's output lies, its length, the block's offset in the file."""
+    src = np.asarray(src, np.int64)
+    full = np.nonzero(isizes > 0)[0]
+    if not len(full):
+        return np.zeros(len(src), np.uint64), np.ones(len(src), bool)
+    offs, cs = out_offs[full].astype(np.int64), coffs[full].astype(np.int64)
+    beyond = src >= int(offs[-1] + isizes[full[-1]])
+    at = np.clip(np.searchsorted(offs, src, "right") - 1, 0, len(offs) - 1)
+    return (cs[at].astype(np.uint64) << np.uint64(16)) | (src - offs[at]).astype(np.uint64), beyond
+
+
+class TabixIndex:
+    """A tabix index (.tbi) of a BGZF file of tab-separated lines sorted by name and start: names in order of first appearance; per
+    name, per bin (SAM specification section 5.3) the chunks (v_beg, v_end) of virtual offsets that hold its lines, and the linear
+    index, the smallest virtual offset of a line overlapping each 16 KiB window.  build() makes one on the GPU; chunks() answers a
+    region on the host; BgzfReader.fetch() reads a region's lines.  On disk the standard layout, BGZF-compressed; what this project
+    writes has no pseudo-bin 37450 and no trailing n_no_coor; load() accepts both, and a plain blob that starts with the magic."""
+
+    def __init__(self, conf, names, bins, linear):
+        self.conf = tuple(int(x) for x in conf)
+        self._names = [bytes(n) for n in names]
+        self.bins = [{int(b): [(int(x), int(y)) for x, y in cs] for b, cs in d.items()} for d in bins]
+        self.linear = [[int(v) for v in lin] for lin in linear]
+        if len(self.conf) != 6 or not len(self._names) == len(self.bins) == len(self.linear):
+            raise ValueError("tabix index: tables of different lengths")
+        self._ids = {n: i for i, n in enumerate(self._names)}
+        if len(self._ids) != len(self._names):
+            raise ValueError("tabix index: a name appears twice")
+        self._keys = [np.array(sorted(d), np.int64) for d in self.bins]
+
+    @property
+    def names(self):
+        return list(self._names)
+
+    def __len__(self):
+        return len(self._names)
+
+    def __eq__(self, other):
+        return (isinstance(other, TabixIndex) and self.conf == other.conf and self._names == other._names and self.bins == other.bins and
+                self.linear == other.linear)
+
+    __hash__ = None
+
+    def validate(self, file_size):
+        """ValueError unless every chunk satisfies v_beg < v_end and lies inside a file of file_size bytes"""
+        file_size = int(file_size)
+        for name, d in zip(self._names, self.bins):
+            for b, cs in d.items():
+                for vb, ve in cs:
+                    if not 0 <= vb < ve < 1 << 64 or vb >> 16 >= file_size or ve >> 16 > file_size:
+                        raise ValueError(f"tabix index: chunk ({vb}, {ve}) of {name!r}, bin {b}, does not fit a file of {file_size} bytes")
+
+    # ---- regions
+    def chunks(self, name, beg, end):
+        """[(v_beg, v_end), ...], sorted and merged where they overlap or touch: every line of `name` that overlaps [beg, end)
+        (zero-based, half-open; an empty interval is [beg, beg + 1)) starts inside one of them.  An unknown name: []."""
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        i = self._ids.get(name)
+        beg, end = max(int(beg), 0), int(end)
+        if end <= beg:
+            end = beg + 1
+        end = min(end, TABIX_MAX_POS)
+        if i is None or beg >= end:
+            return []
+        lin = self.linear[i]
+        if beg >> 14 >= len(lin):                            # no line of the name reaches this window
+            return []
+        floor, keys, found = lin[beg >> 14], self._keys[i], []
+        levels = [(0, 0)] + [(first + (beg >> shift), first + ((end - 1) >> shift)) for shift, first in _TABIX_LEVELS]
+        for lo, hi in levels:
+            for b in keys[np.searchsorted(keys, lo, "left"):np.searchsorted(keys, hi, "right")].tolist():
+                found.extend(c for c in self.bins[i][b] if c[1] > floor)
+        found.sort()
+        out = []
+        for vb, ve in found:
+            if out and vb <= out[-1][1]:
+                out[-1] = (out[-1][0], max(out[-1][1], ve))
+            else:
+                out.append((vb, ve))
+        return out
+
+    # ---- on disk
+    def to_bytes(self, compressed=True):
+        """the .tbi bytes; compressed=False: the plain layout, not BGZF-compressed"""
+        blob = b"".join(n + b"\0" for n in self._names)
+        parts = [TABIX_MAGIC, struct.pack("<8i", len(self._names), *self.conf, len(blob)), blob]
+        for d, lin in zip(self.bins, self.linear):
+            parts.append(struct.pack("<i", len(d)))
+            for b in sorted(d):
+                parts.append(struct.pack("<Ii", b, len(d[b])))
+                parts.append(np.array(d[b], np.uint64).reshape(-1, 2).astype("<u8").tobytes())
+            parts.append(struct.pack("<i", len(lin)))
+            parts.append(np.array(lin, np.uint64).astype("<u8").tobytes())
+        raw = b"".join(parts)
+        return compress(raw) if compressed else raw
+
+    def save(self, path_or_file):
+        if hasattr(path_or_file, "write"):
+            path_or_file.write(self.to_bytes())
+        else:
+            with _builtin_open(path_or_file, "wb") as f:
+                f.write(self.to_bytes())
+
+    @classmethod
+    def from_bytes(cls, blob):
+        """ValueError (with the offset) for a blob that is not a .tbi: counts that overrun it, negative counts, names that do not end
+        in NUL.  A BGZF-compressed blob is decompressed first; one that starts with the magic is taken as it is."""
+        blob = bytes(blob)
+        if not blob.startswith(TABIX_MAGIC):
+            if not blob.startswith(b"\x1f\x8b"):
+                raise ValueError("tabix index: neither BGZF nor the magic at offset 0")
+            try:
+                blob = bytes(decompress(blob))
+            except (BadGzipFile, EOFError) as e:
+                raise ValueError(f"tabix index: {e}") from None
+            if not blob.startswith(TABIX_MAGIC):
+                raise ValueError("tabix index: wrong magic at offset 0")
+        at = 4
+
+        def take(fmt, what):
+            nonlocal at
+            size = struct.calcsize(fmt)
+            if len(blob) - at < size:
+                raise ValueError(f"tabix index: {what} at offset {at} overruns the {len(blob)} bytes")
+            vals = struct.unpack_from(fmt, blob, at)
+            at += size
+            return vals
+
+        def count(what, unit):
+            n, = take("<i", what)
+            if n < 0 or n * unit > len(blob) - at:
+                raise ValueError(f"tabix index: {what} {n} at offset {at - 4} is negative or overruns the {len(blob)} bytes")
+            return n
+
+        n_ref = count("n_ref", 1)
+        conf = take("<6i", "the configuration")
+        l_nm = count("l_nm", 1)
+        names = blob[at:at + l_nm]
+        if l_nm and not names.endswith(b"\0"):
+            raise ValueError(f"tabix index: the names at offset {at} do not end in NUL")
+        names = names.split(b"\0")[:-1] if l_nm else []
+        if len(names) != n_ref:
+            raise ValueError(f"tabix index: {len(names)} names at offset {at} for n_ref = {n_ref}")
+        at += l_nm
+        bins, linear = [], []
+        for _ in range(n_ref):
+            d = {}
+            for _ in range(count("n_bin", 8)):
+                b, = take("<I", "a bin")
+                n = count("n_chunk", 16)
+                if b > _TABIX_PSEUDO_BIN or b in d:
+                    raise ValueError(f"tabix index: bin {b} at offset {at - 8} is out of range or repeated")
+                cs = np.frombuffer(blob, "<u8", 2 * n, at).reshape(-1, 2).tolist()
+                at += 16 * n
+                if b != _TABIX_PSEUDO_BIN:
+                    d[b] = cs
+            n = count("n_intv", 8)
+            linear.append(np.frombuffer(blob, "<u8", n, at).tolist())
+            at += 8 * n
+            bins.append(d)
+        if len(blob) - at not in (0, 8):                     # (8: htslib's n_no_coor)
+            raise ValueError(f"tabix index: {len(blob) - at} bytes behind the last name's tables at offset {at}")
+        return cls(conf, names, bins, linear)
+
+    @classmethod
+    def load(cls, path_or_file):
+        if hasattr(path_or_file, "read"):
+            return cls.from_bytes(path_or_file.read())
+        with _builtin_open(path_or_file, "rb") as f:
+            return cls.from_bytes(f.read())
+
+    # ---- building
+    @classmethod
+    def build(cls, file, preset=None, *, seq_col=None, start_col=None, end_col=None, zero_based=False, meta=b"#", skip=0):
+        """Index a BGZF file (a path or a seekable binary file) on the GPU.  preset: "gff", "bed" or "vcf" (tabix's); or columns by
+        keyword, counted from 1: seq_col, start_col, end_col (none: features of one base), zero_based (half-open, as BED).  meta: lines
+        that start with this byte are skipped, and so are the first `skip` lines and empty ones.  The file is read in windows as grep()
+        reads it; each window's blocks are decoded in one launch, the fields of every line are read where they lie, and name runs, bin
+        runs and the window records of the linear index come back -- nothing per line.  ValueError, naming the smallest such line
+        number and its virtual offset, for a line with a needed column missing, a coordinate that is not 1 to 10 digits, an interval
+        outside [0, 2**29] or a start below the previous line's of the same name, and for a name that comes back after another;
+        BadGzipFile for a file that is not BGZF or a block that does not decode."""
+        conf = _tabix_conf(preset, seq_col, start_col, end_col, zero_based, meta, skip)
+        if _is_path(file):
+            with _builtin_open(file, "rb") as f:
+                return _tabix_build(f, None, conf)
+        return _tabix_build(file, None, conf)
+
+
+def _tabix_window(tot, names, blob, bins, wins, out_offs, isizes, coffs):
+    """one engine call's tables -> the arguments of _TabixMerge.add (pure host code)"""
+    nv, _ = _tabix_voffsets(names["src_off"], out_offs, isizes, coffs)
+    ends = np.cumsum(names["len"].astype(np.int64))
+    nm = [(blob[int(e - ln):int(e)], int(line), int(v)) for e, ln, line, v in zip(ends, names["len"], names["line"], nv)]
+    vb, _ = _tabix_voffsets(bins["src_beg"], out_offs, isizes, coffs)
+    ve, beyond = _tabix_voffsets(bins["src_end"], out_offs, isizes, coffs)
+    bn = [(int(r), int(b), int(x), None if o else int(y)) for r, b, x, y, o in zip(bins["name"], bins["bin"], vb, ve, beyond)]
+    wv, _ = _tabix_voffsets(wins["src_off"], out_offs, isizes, coffs)
+    wn = [(int(r), int(w), int(v)) for r, w, v in zip(wins["name"], wins["window"], wv)]
+    bad = None
+    if tot.bad_kind:
+        v, _ = _tabix_voffsets([tot.bad_src], out_offs, isizes, coffs)
+        bad = (int(tot.bad_line), int(tot.bad_kind), int(v[0]))
+    return nm, bn, wn, int(tot.first_beg), int(tot.last_beg), bad
+
+
+def _tabix_build(fp, ctx, conf):
+    ctx = ctx or zlib_ng._ctx()                              # (the arguments are judged before a context is asked for)
+    merge = _TabixMerge()
+    c_next, text_off, text_cap = 0, 0, max(_GREP_TEXT, _TABIX_MAX_LINE + 2 * MAX_BLOCK)
+    window, nblocks, line_base, after = _READ_WINDOW, 0, 0, 0
+    buf = mv = None
+    try:
+        while True:
+            if buf is None or len(buf) < window + MAX_BLOCK:
+                if buf is not None:
+                    del mv
+                    _lib.give_buffer(buf)
+                buf = _lib.take_buffer(window + MAX_BLOCK)
+                mv = memoryview(buf)
+            fp.seek(c_next)
+            got = _read_full(fp, mv[:window + MAX_BLOCK])
+            if not got:
+                break
+            data = mv[:got]
+            ended = got < window + MAX_BLOCK
+            code, tab, used, total = _lib.bgzf_scan(data)
+            if ended and used < got and _cut_block(data[used:]):
+                raise EOFError(f"BGZF block {nblocks + len(tab)} at offset {c_next + used}: the file ends inside the block")
+            if code != _lib.OK or not tab:
+                raise _scan_error(code if c_next + used == 0 else _lib.DATA_ERROR, nblocks + len(tab), c_next + used)
+            t = np.array(tab, np.int64)
+            coffs, csizes, isizes = t[:, 0], t[:, 2], t[:, 3]
+            n_use, text_end, final = _grep_window(coffs + c_next, isizes, text_off, None, ended and used == got, text_cap)
+            members, bad = _member_table(np.frombuffer(data, np.uint8), coffs[:n_use], csizes[:n_use], isizes[:n_use])
+            if bad >= 0:
+                raise BadGzipFile(f"BGZF block {nblocks + bad} at offset {c_next + int(coffs[bad])}: bad block header or block size")
+            cend = int(coffs[n_use - 1] + csizes[n_use - 1]) if n_use else 0
+            _, status, tot, names, blob, bins, wins = ctx.bgzf_tabix(data[:cend], members, text_off, text_end, conf, 10,
+                                                                     _lib.BGZF_TABIX_FINAL if final else 0, line_base)
+            bad = np.nonzero(status)[0]
+            if len(bad):
+                raise _block_error(c_next + int(coffs[bad[0]]), status[bad[0]])
+            if not tot.covered:
+                raise BadGzipFile(f"BGZF blocks at offset {c_next}: the decoded blocks do not cover the text")
+            out_offs, abs_c = members["out_off"].astype(np.int64), coffs[:n_use] + c_next
+            full = np.nonzero(isizes[:n_use] > 0)[0]
+            if len(full):
+                after = max(after, int(abs_c[full[-1]] + csizes[full[-1]]))
+            head = None
+            if text_end > text_off:
+                hv, _ = _tabix_voffsets([text_off], out_offs, isizes[:n_use], abs_c)
+                head = int(hv[0])
+            nm, bn, wn, first_beg, last_beg, bad = _tabix_window(tot, names, blob, bins, wins, out_offs, isizes[:n_use], abs_c)
+            merge.add(nm, bn, wn, first_beg, last_beg, head=head, bad=bad)
+            line_base += tot.seen
+            try:
+                nxt = _grep_advance(isizes, n_use, text_off, text_end, int(tot.tail_off), final, window, _TABIX_MAX_LINE)
+            except _LongLine as e:
+                v = make_virtual_offset(c_next + int(coffs[e.block]), e.offset)
+                raise ValueError(f"the line at virtual offset {v} has not ended after {_TABIX_MAX_LINE} bytes") from None
+            if nxt is None:
+                break
+            b, text_off, window = nxt
+            nblocks += b
+            c_next += int(coffs[b]) if b < len(coffs) else used
+    finally:
+        if buf is not None:
+            del mv
+            _lib.give_buffer(buf)
+    return merge.finish(conf, after << 16)
+
+
+class FetchResult:
+    """What fetch() found: len() lines; region (int64: the index into `regions` of each row, ascending), voffsets (uint64, the
+    normalised virtual offset of each line's first byte), offsets (int64, n + 1 of them) into data (the lines packed, each with its
+    delimiter); result[i], slices and iteration yield bytes; of(i): the lines of region i."""
+
+    def __init__(self, region, voffsets, offsets, data, n_regions):
+        self.region = np.asarray(region, np.int64)
+        self.voffsets = np.asarray(voffsets, np.uint64)
+        self.offsets = np.asarray(offsets, np.int64)
+        self.data = data
+        self.n_regions = int(n_regions)
+        if len(self.offsets) != len(self.region) + 1 or len(self.voffsets) != len(self.region):
+            raise ValueError("FetchResult: arrays of different lengths")
+
+    def __len__(self):
+        return len(self.region)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(len(self)))]
+        n = len(self)
+        k = int(i)
+        if not -n <= k < n:
+            raise IndexError("FetchResult index out of range")
+        k %= n
+        return bytes(self.data[int(self.offsets[k]):int(self.offsets[k + 1])])
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+    def of(self, i):
+        """the lines of region i"""
+        if not 0 <= int(i) < self.n_regions:
+            raise IndexError("FetchResult.of: no such region")
+        a, b = np.searchsorted(self.region, [int(i), int(i) + 1])
+        return [self[k] for k in range(int(a), int(b))]
+
+    def __repr__(self):
+        return f"<FetchResult: {len(self)} lines of {self.n_regions} regions, {int(self.offsets[-1])} bytes>"
+
+
+def _fetch_regions(regions):
+    """-> ([(name, beg, end)], whether one region was given rather than a list)"""
+    single = isinstance(regions, (str, bytes, tuple))
+    out = []
+    for r in ([regions] if single else list(regions)):
+        name, beg, end = parse_region(r)
+        if end <= beg:
+            end = beg + 1
+        out.append((name, min(beg, TABIX_MAX_POS), min(end, TABIX_MAX_POS)))
+    return out, single
+
+
+def _fetch_groups(spans, chains, isize_of, text_cap, max_regions):
+    """Cut the spans [(region, v_beg, v_end)] (in order) into engine calls: each decodes the blocks of its spans once, at most text_cap
+    bytes of them (one span may exceed it) for at most max_regions regions.  chains: per span its blocks' file offsets.
+    -> [(first span, behind the last span)] (pure host code)"""
+    groups, start, blocks, regs, size = [], 0, set(), set(), 0
+    for k, (span, chain) in enumerate(zip(spans, chains)):
+        new = [c for c in chain if c not in blocks]
+        add = sum(isize_of[c] for c in new)
+        if k > start and (size + add > text_cap or (span[0] not in regs and len(regs) >= max_regions)):
+            groups.append((start, k))
+            start, blocks, regs, size = k, set(), set(), 0
+            new, add = list(chain), sum(isize_of[c] for c in chain)
+        blocks.update(new)
+        regs.add(span[0])
+        size += add
+    if len(spans) > start:
+        groups.append((start, len(spans)))
+    return groups
+
+
+_STALE_TBI = "tabix index does not match the file"
+
+
+def _fetch_file(fp, fsize, ctx, index, regions, count, load_block):
+    regs, single = _fetch_regions(regions)
+    if not isinstance(index, TabixIndex):
+        raise TypeError("fetch() takes a TabixIndex")
+    if index.conf[0] & 0xFFFF not in (0, 2) or index.conf[0] & ~0x1FFFF or index.conf[1] < 1 or index.conf[2] < 1 or index.conf[3] < 0 or \
+            not 0 <= index.conf[4] <= 255 or index.conf[5] < 0:
+        raise ValueError("fetch(): the index's configuration is not one of generic, BED-like or VCF")
+    index.validate(fsize)
+    spans = [(i, vb, ve) for i, (name, beg, end) in enumerate(regs) for vb, ve in index.chunks(name, beg, end)]
+    counts = [0] * len(regs)
+    empty = FetchResult([], [], [0], b"", len(regs))
+    if not spans:
+        return (counts[0] if single else counts) if count else empty
+    ctx = ctx or zlib_ng._ctx()                              # (the arguments are judged before a context is asked for)
+    cache, chains = {}, []
+    for _, vb, ve in spans:                                  # the blocks of a chunk: from its first one through BSIZE
+        (c, ub), (ce, ue) = split_virtual_offset(vb), split_virtual_offset(ve)
+        chain = []
+        while c < ce or (c == ce and ue > 0):
+            blk = load_block(c, cache) if c < fsize else None
+            if blk is None or (not chain and ub >= blk[2]) or (c == ce and ue > blk[2]):
+                raise ValueError(_STALE_TBI)
+            chain.append(c)
+            c += len(blk[0])
+        if not chain or (c != ce and ue == 0) or (ue and chain[-1] != ce):
+            raise ValueError(_STALE_TBI)
+        chains.append(chain)
+    isize_of = {c: b[2] for c, b in cache.items() if b is not None}
+    region_parts, voff_parts, len_parts, pieces = [], [], [], []
+    for a, b in _fetch_groups(spans, chains, isize_of, _GREP_TEXT, _lib.BGZF_FETCH_MAX_REGIONS):
+        need = sorted({c for chain in chains[a:b] for c in chain})
+        raws = [cache[c][0] for c in need]
+        members = np.zeros(len(need), MEMBER_DTYPE)
+        lens = np.fromiter((len(r) for r in raws), np.uint64, len(need))
+        hdrs = np.fromiter((cache[c][1] for c in need), np.uint64, len(need))
+        members["out_len"] = np.fromiter((cache[c][2] for c in need), np.uint32, len(need))
+        members["crc"] = np.fromiter((struct.unpack_from("<I", r, len(r) - 8)[0] for r in raws), np.uint32, len(need))
+        members["in_off"] = np.cumsum(lens) - lens + hdrs
+        members["in_len"] = lens - hdrs - 8
+        opos = np.cumsum(members["out_len"], dtype=np.uint64) - members["out_len"]
+        members["out_off"] = opos
+        where = dict(zip(need, opos.tolist()))
+        local = {}                                           # the regions of this call, numbered from 0
+        for i, _, _ in spans[a:b]:
+            local.setdefault(i, len(local))
+        glob = np.fromiter(local, np.int64, len(local))
+        rtab = np.zeros(len(local), _lib.TABIX_REGION_DTYPE)
+        blob = b"".join(regs[i][0] for i in local)
+        nlen = np.fromiter((len(regs[i][0]) for i in local), np.uint32, len(local))
+        rtab["name_len"], rtab["name_off"] = nlen, np.cumsum(nlen, dtype=np.uint64) - nlen
+        rtab["beg"], rtab["end"] = [regs[i][1] for i in local], [regs[i][2] for i in local]
+        stab = np.zeros(b - a, _lib.TABIX_SPAN_DTYPE)
+        for k, ((i, vb, ve), chain) in enumerate(zip(spans[a:b], chains[a:b])):
+            ue = ve & 0xFFFF
+            stab[k] = (where[chain[0]] + (vb & 0xFFFF), where[chain[-1]] + (ue if ue else cache[chain[-1]][2]), local[i], 0)
+        _, status, sstat, srows, tot, rows, packed = ctx.bgzf_fetch(b"".join(raws), members, index.conf, 10,
+                                                                    _lib.BGZF_FETCH_COUNT_ONLY if count else 0, blob, rtab, stab)
+        bad = np.nonzero(status)[0]
+        if len(bad):
+            raise _block_error(need[int(bad[0])], status[bad[0]])
+        if bool(sstat.any()):
+            raise ValueError(_STALE_TBI)
+        for k, n in enumerate(srows.tolist()):
+            counts[spans[a + k][0]] += n
+        if len(rows):
+            v, _ = _tabix_voffsets(rows["src_off"], opos.astype(np.int64), members["out_len"].astype(np.int64), np.array(need, np.int64))
+            region_parts.append(glob[rows["region"]])
+            voff_parts.append(v)
+            len_parts.append(rows["len"].astype(np.int64))
+            pieces.append(packed)
+    if count:
+        return counts[0] if single else counts
+    if not region_parts:
+        return empty
+    lens = np.concatenate(len_parts)
+    offsets = np.zeros(len(lens) + 1, np.int64)
+    np.cumsum(lens, out=offsets[1:])
+    return FetchResult(np.concatenate(region_parts), np.concatenate(voff_parts), offsets, pieces[0] if len(pieces) == 1 else b"".join(pieces),
+                       len(regs))
+
+
+def fetch(file, index, regions, *, count=False):
+    """The lines of a BGZF file (a path or a seekable binary file) that overlap `regions`: one region or a list of them, each a
+    string as parse_region() reads it or a tuple (name, beg, end), zero-based and half-open.  `index`: the file's TabixIndex.  The
+    plan is made on the index alone (chunks() per region); every needed block is read and decoded once, the lines of each chunk are
+    filtered on the GPU by name and interval, and only the matching lines come back: a FetchResult, in the order of the regions and
+    then of the file.  count=True: the number of lines per region (a list; an int for one region); no line leaves the device.
+    ValueError for an index that does not fit the file, BadGzipFile (with its offset; no partial result) for a block that fails."""
+    if _is_path(file):
+        with _builtin_open(file, "rb") as f:
+            return fetch(f, index, regions, count=count)
+    fsize = file.seek(0, 2)
+
+    def load_block(c, cache):                                # (as BgzfReader._load_block)
+        if c not in cache:
+            file.seek(c)
+            raw = file.read(MAX_BLOCK)
+            code, tab, used, total = _lib.bgzf_scan(raw, 1) if raw else (_lib.OK, [], 0, 0)
+            if raw and (code != _lib.OK or not tab):
+                raise BadGzipFile(f"BGZF block at offset {c}: bad block header or block size")
+            cache[c] = (raw[:used], 12 + struct.unpack_from("<H", raw, 10)[0], tab[0][3]) if raw else None
+        return cache[c]
+    return _fetch_file(file, fsize, None, index, regions, count, load_block)
+
+
 def _scan_file(f):
     """-> (block table of the whole file, file size); BadGzipFile for anything that is not a complete run of BGZF blocks"""
     f.seek(0)
@@ -1254,6 +1856,18 @@ class BgzfReader(io.BufferedIOBase):
         try:
             return _grep_file(self._fp, self._ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line,
                               max_line)
+        finally:
+            self._fp.seek(at)
+
+    def fetch(self, index, regions, *, count=False):
+        """bgzf.fetch() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("fetch() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _fetch_file(self._fp, self._fsize, self._ctx, index, regions, count, self._load_block)
         finally:
             self._fp.seek(at)
 
