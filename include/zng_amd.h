@@ -663,6 +663,84 @@ int zngamd_bgzf_fetch(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const
                       int32_t *status, int32_t *span_status, uint32_t *span_rows, zngamd_tabix_row *rows, uint64_t rows_cap,
                       uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_fetch_totals *totals);
 
+/* ---- BGZF by sequence (zlib_ng_amd/bgzf.py: FaidxIndex, fetch_seq).  Both calls read a FASTA.
+ * The line model.  The text is cut into lines by '\n' (delim must be 10; anything else, and flags other than _FINAL, is ZNGAMD_E_ARG,
+ * found before the context is touched).  One CR directly in front of the '\n' belongs to the terminator.  A line's bases are the bytes
+ * of its body, without the terminator; its width is the body plus the terminator bytes.  With _FINAL, non-empty bytes behind the last
+ * '\n' are a line whose width equals its bases.  A line whose first byte is '>' is a header: its name runs from the byte behind '>'
+ * to the first space, tab or CR, or to the end of the body, and it opens a sequence.  Every other line is a sequence line of the open
+ * sequence; one with 0 bases is empty.  Per sequence: bases, the sum of the bases of its lines; seq_src, the first byte behind the
+ * header line (also when no sequence line follows); line_bases and line_width, those of its first non-empty line, or 0 and 0.
+ * A line is bad, smallest kind first, when (1) it is a header with an empty name, (2) a sequence line with a byte outside 0x21 ..
+ * 0x7E in its body, (3) a non-empty sequence line that is not the last non-empty line of its sequence and whose bases or width
+ * differ from the first one's, or the last non-empty line with more bases than the first (its width is free), (4) an empty line that
+ * a non-empty line follows inside the same sequence, (5) a non-empty sequence line while no sequence is open (empty lines in front
+ * of the first header are skipped).  Of several faults the smallest line number is reported, and of one line's the smallest kind.
+ *
+ * zngamd_bgzf_faidx: the records of the text scratch[text_off, text_end).  Blocks, member table, text, _FINAL, line_base, tail_off
+ * and the cover contract (covered = 0: nothing is reported, the carry comes back as it went in) are those of zngamd_bgzf_tabix.
+ * carry (NULL: nothing is open) describes the sequence that is open at text_off: its first non-empty line (first_width 0: none yet),
+ * its last non-empty line so far and that line's number (without one: 0, 0 and the header's number), flags ZNGAMD_FAIDX_OPEN and
+ * ZNGAMD_FAIDX_GAP (an empty line follows last_line).  With it every line of the text is judged by the rules above, the lines in
+ * front of the text's first header too; head_bases is the sum of their bases, to be added to the open sequence by the caller.  One
+ * judgement waits for the next call, whether the text's last non-empty line is a middle line or its sequence's last: a call that
+ * meets a non-empty line in front of its first header applies (3) to carry.last_line as a middle line and (4) to last_line + 1 with
+ * _GAP; one that meets a header, or has _FINAL, applies (3) as to a last line.  A bad line in front of line_base has bad_src ~0;
+ * carry.reserved of the carry that comes back says where it starts: the scratch offset, from text_off, of the line behind last_line,
+ * valid while last_line >= line_base (bad_line == last_line starts last_width bytes in front of it).  totals.carry is what the next
+ * call takes; with _FINAL it is zero.  rows: one per header line, in text order: where the name stands and its length, seq_src, the
+ * header's line number, and bases, line_bases, line_width as far as this text shows them (the record the text ends in is continued
+ * by the next call's head); the names packed in that order into blob.  Nothing per line leaves the device.  ZNGAMD_BUF_ERROR: a
+ * capacity is below its count; nothing is written.  *totals is always valid on ZNGAMD_OK and ZNGAMD_BUF_ERROR.  The member table is
+ * untrusted: no entry makes a kernel read or write outside the buffers. */
+typedef struct { uint64_t last_line; uint32_t first_bases, first_width, last_bases, last_width, flags, reserved; } zngamd_faidx_carry;   /* 32 B */
+typedef struct { uint64_t name_src, seq_src, line, bases; uint32_t name_len, line_bases, line_width, reserved; } zngamd_faidx_row;       /* 48 B */
+typedef struct {
+    uint64_t seen;         /* lines of the text that were decided (the open tail is not one of them) */
+    uint64_t records;      /* of them, headers: the rows */
+    uint64_t tail_off;     /* scratch offset where the open line starts; text_end when there is none */
+    uint64_t head_bases;   /* bases of the lines in front of the text's first header when the carry that came in is open */
+    uint64_t name_bytes;   /* bytes of the packed names */
+    uint64_t bad_line;     /* bad_kind != 0: the smallest number of a bad line */
+    uint64_t bad_src;      /*                where that line starts in the scratch; ~0 for a line in front of line_base */
+    uint32_t covered;      /* 1: decoded blocks cover the text and the figures above describe it */
+    uint32_t bad_kind;     /* 0, or 1 .. 5 as numbered above */
+    zngamd_faidx_carry carry;
+    uint32_t head_line_bases, head_line_width;      /* the first non-empty line in front of the text's first header when the carry that
+                                                       came in is open and has none: the open sequence's line_bases and line_width */
+} zngamd_bgzf_faidx_totals;                                                                                    /* 104 B */
+#define ZNGAMD_BGZF_FAIDX_FINAL 4u
+#define ZNGAMD_FAIDX_OPEN       1u
+#define ZNGAMD_FAIDX_GAP        2u
+int zngamd_bgzf_faidx_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                          uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, uint64_t line_base,
+                          const zngamd_faidx_carry *carry, void *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                          zngamd_faidx_row *d_rows, uint64_t rows_cap, void *d_blob, uint64_t blob_cap, zngamd_bgzf_faidx_totals *totals);
+/* Host-buffer form: stages in and the member table; status, rows and names come back.  alloc as for zngamd_bgzf_tabix: rows, then
+ * blob; it is not asked for an empty one. */
+int zngamd_bgzf_faidx(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                      uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, uint64_t line_base,
+                      const zngamd_faidx_carry *carry, int32_t *status, zngamd_faidx_row *rows, uint64_t rows_cap, uint8_t *blob,
+                      uint64_t blob_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_faidx_totals *totals);
+/* zngamd_bgzf_faidx_fetch: bases without their line terminators.  Blocks and member rows as zngamd_bgzf_read takes them, decoded
+ * once in one launch; then one workgroup per span.  src_off: the scratch offset of the span's first base; col: that base's position
+ * in its line; n: bases, at most ZNGAMD_FAIDX_MAX_SPAN.  Base k, with q = col + k, comes from src_off - col + (q / line_bases) *
+ * line_width + q % line_bases and goes to dst_off + k; with ZNGAMD_FAIDX_SPAN_RC to dst_off + n - 1 - k, complemented (A<->T, C<->G,
+ * U->A, R<->Y, K<->M, B<->V, D<->H, in both letter cases; everything else unchanged).  span_status[s]: ZNGAMD_BGZF_SLICE_OK; _TABLE
+ * (the span lies outside scratch_cap or out_cap, line_bases == 0, line_width < line_bases, col >= line_bases, src_off < col or n >
+ * 65 536: nothing is written); _BLOCK (blocks that decoded do not cover its bytes: zeros are written); _STALE (a gathered byte lies
+ * outside 0x21 .. 0x7E: the index belongs to another file).  The spans are untrusted as the member table is. */
+typedef struct { uint64_t src_off, dst_off; uint32_t n, col, line_bases, line_width, flags, reserved; } zngamd_faidx_span;   /* 40 B */
+#define ZNGAMD_BGZF_SLICE_STALE 4
+#define ZNGAMD_FAIDX_SPAN_RC    1u
+#define ZNGAMD_FAIDX_MAX_SPAN   65536u
+int zngamd_bgzf_faidx_fetch_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                const zngamd_faidx_span *d_spans, uint32_t n_spans, void *d_scratch, uint64_t scratch_cap, void *d_out,
+                                uint64_t out_cap, int32_t *d_status, int32_t *d_span_status);
+int zngamd_bgzf_faidx_fetch(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                            const zngamd_faidx_span *spans, uint32_t n_spans, uint8_t *out, uint64_t out_cap, int32_t *status,
+                            int32_t *span_status);
+
 /* ---- streaming: the zng_stream calling convention ------------------------------------------------
  * What a binding of the reference swaps in for zng_deflateInit2 / zng_deflate / zng_deflateSetDictionary / zng_deflateCopy /
  * zng_deflateEnd (zlib_ngmodule.c:394, :552, :743, :401, :811) and zng_inflateInit2 / zng_inflate / zng_inflateSetDictionary /

@@ -11,6 +11,7 @@
 #include "za_bgzf.hip"
 #include "za_grep.hip"
 #include "za_tabix.hip"
+#include "za_faidx.hip"
 #include "za_batch.hip"
 #include "za_dict.hip"
 #include "za_checksum.hip"
@@ -44,6 +45,10 @@ static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_ta
               sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
               sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
               ZNGAMD_BGZF_TABIX_FINAL == ZA_TBX_FINAL && ZNGAMD_BGZF_FETCH_COUNT_ONLY == ZA_TBX_COUNT_ONLY && ZNGAMD_TABIX_MAX_POS == ZA_TBX_MAX_POS, "bgzf tabix layout");
+static_assert(sizeof(zngamd_faidx_carry) == sizeof(ZaFaiCarry) && sizeof(ZaFaiCarry) == 32 && sizeof(zngamd_faidx_row) == sizeof(ZaFaiRow) && sizeof(ZaFaiRow) == 48 &&
+              sizeof(zngamd_faidx_span) == sizeof(ZaFaiSpan) && sizeof(ZaFaiSpan) == 40 && sizeof(zngamd_bgzf_faidx_totals) == 104 && sizeof(ZaFaiState) == 88 &&
+              ZNGAMD_BGZF_FAIDX_FINAL == ZA_FAI_FINAL && ZNGAMD_FAIDX_SPAN_RC == ZA_FAI_RC && ZNGAMD_FAIDX_MAX_SPAN == ZA_FAI_MAX_SPAN &&
+              ZNGAMD_BGZF_SLICE_STALE == ZA_SLICE_STALE && ZNGAMD_FAIDX_OPEN == ZA_FAI_OPEN && ZNGAMD_FAIDX_GAP == ZA_FAI_GAP, "bgzf faidx layout");
 static_assert(ZNGAMD_SLOT_STRIDE % 4 == 0 && ZNGAMD_SLOT_STRIDE >= ZA_MAX_UNIT + 32, "slot stride");
 static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants");
 
@@ -139,6 +144,9 @@ struct zngamd_ctx {
     DevBuf<ZaTbxLine> tb_lines; DevBuf<ZaTbxName> tb_names; DevBuf<ZaTbxBin> tb_bins; DevBuf<ZaTbxWin> tb_wins;
     DevBuf<uint8_t> tb_par; DevBuf<ZaTbxSpan> tb_spans; DevBuf<ZaTbxRow> tb_rows; DevBuf<uint32_t> tb_srows; DevBuf<int32_t> tb_sstat; DevBuf<uint64_t> tb_sbase;
     std::vector<uint8_t> tb_host;
+    // records of a FASTA (za_faidx.hip, section 5h; the bits, the tile counts, three scanned arrays and the totals are those of 5g): bad-byte
+    // bits, line starts, bases | width per line, where header r stands, first / last non-empty line per record, rows, spans
+    DevBuf<unsigned long long> fa_x, fa_bw; DevBuf<uint64_t> fa_start; DevBuf<uint32_t> fa_hline, fa_first, fa_last; DevBuf<ZaFaiRow> fa_rows; DevBuf<ZaFaiSpan> fa_spans;
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -286,6 +294,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->tb_bits.release(); c->tb_data.release(); c->tb_name.release(); c->tb_bin.release(); c->tb_key.release(); c->tb_raise.release(); c->tb_blk.release();
     c->tb_tot.release(); c->tb_tcnt.release(); c->tb_di.release(); c->tb_lens.release(); c->tb_tbase.release(); c->tb_lines.release(); c->tb_names.release();
     c->tb_bins.release(); c->tb_wins.release(); c->tb_par.release(); c->tb_spans.release(); c->tb_rows.release(); c->tb_srows.release(); c->tb_sstat.release(); c->tb_sbase.release();
+    c->fa_x.release(); c->fa_bw.release(); c->fa_start.release(); c->fa_hline.release(); c->fa_first.release(); c->fa_last.release(); c->fa_rows.release(); c->fa_spans.release();
     c->gp_par.release(); c->gp_bits.release(); c->gp_tiles.release(); c->gp_carry.release(); c->gp_rows.release(); c->gp_lens.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
@@ -4061,6 +4070,226 @@ try {
     HIPCHK(c, hipMemcpyAsync(rows, c->tb_rows.p, (size_t)n * sizeof(ZaTbxRow), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return d2h_payload(c, out, c->bg_out.p, totals->bytes);
+} ZA_ABI_GUARD
+
+// ---- records of a FASTA (za_faidx.hip)
+// tb_tot, in u64: [0, 11) ZaFaiState, [12, 14) the cover, [14] '\n', [15] records, [16] non-empty sequence lines, [17] bases, [18] bytes of
+// the packed names, [20, 24) the carry that came in
+// decode, cover, mark, offsets, [the host waits for the '\n' count], starts, bytes, classify, three scans, heads, ends, judge, close,
+// [the host waits for the totals], emit, offsets, place, gather.  own: the host form (rows and names go to the context's buffers).
+static int bgzf_faidx_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
+                          uint64_t text_end, uint32_t flags, uint64_t line_base, const zngamd_faidx_carry *carry, uint8_t *d_scratch, uint64_t scratch_cap,
+                          int32_t *d_status, ZaFaiRow *d_rows, uint64_t rows_cap, uint8_t *d_blob, uint64_t blob_cap, bool own, zngamd_bgzf_faidx_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    if (text_off > text_end || text_end > scratch_cap) return fail(c, ZNGAMD_E_ARG, "the text lies outside the scratch");
+    if (text_end - text_off >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "a text of 4 GiB or more");
+    if (line_base >= (1ull << 60)) return fail(c, ZNGAMD_E_ARG, "line_base out of range");
+    const uint64_t tile0 = text_off / ZA_TBX_TILE;
+    const uint32_t ntiles = text_end > text_off ? (uint32_t)((text_end - 1ull) / ZA_TBX_TILE - tile0 + 1ull) : 0u;
+    HIPCHK(c, c->tb_tot.ensure(32)); HIPCHK(c, c->tb_bits.ensure((size_t)ntiles * 256u + 1u)); HIPCHK(c, c->fa_x.ensure((size_t)ntiles * 256u + 1u));
+    HIPCHK(c, c->tb_tcnt.ensure(ntiles + 1u)); HIPCHK(c, c->tb_tbase.ensure(ntiles + 1u));
+    unsigned long long *T = c->tb_tot.p;
+    ZaFaiState *d_st = (ZaFaiState *)T;
+    const ZaFaiCarry *d_cin = (const ZaFaiCarry *)(T + 20);
+    c->tb_host.assign(256, 0);
+    { ZaFaiState *h = (ZaFaiState *)c->tb_host.data(); h->bad_key = ~0ull; h->tail_off = text_end;
+      if (carry) memcpy(c->tb_host.data() + 160, carry, sizeof *carry); }
+    HIPCHK(c, hipMemcpyAsync(T, c->tb_host.data(), 256, hipMemcpyHostToDevice, c->stream));
+    if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      if (n_members) hipLaunchKernelGGL(za_k_grep_cover, dim3((n_members + 255u) / 256u), dim3(256), 0, c->stream, d_members, d_status, n_members, scratch_cap,
+                                        text_off, text_end, T + 12);
+      if (ntiles) {
+          hipLaunchKernelGGL(za_k_fai_mark, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0, c->tb_bits.p, c->fa_x.p,
+                             c->tb_tcnt.p);
+          hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(ntiles <= 64 ? 64 : 1024), 0, c->stream, c->tb_tcnt.p, ntiles, 0u, 0ull, c->tb_tbase.p,
+                             (uint64_t *)(T + 14), (const ZaUnit *)nullptr);
+      } }
+    HIPCHK(c, hipGetLastError());
+    unsigned long long h3[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h3, T + 12, sizeof h3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h3[0] != text_end - text_off || h3[1] != 0) { totals->tail_off = text_off; if (carry) memcpy(&totals->carry, carry, sizeof *carry); return ZNGAMD_OK; }      // not covered: nothing is reported
+    const uint64_t ndelim = h3[2], nl = ndelim + 1ull;
+    if (nl >= 0xFFFFFFF0ull) return fail(c, ZNGAMD_E_ARG, "2^32 lines or more");
+    HIPCHK(c, c->fa_start.ensure(nl + 2u)); HIPCHK(c, c->fa_bw.ensure(nl)); HIPCHK(c, c->tb_data.ensure(nl)); HIPCHK(c, c->tb_name.ensure(nl)); HIPCHK(c, c->tb_bin.ensure(nl));
+    HIPCHK(c, c->fa_hline.ensure(nl + 2u)); HIPCHK(c, c->fa_first.ensure(nl + 2u)); HIPCHK(c, c->fa_last.ensure(nl + 2u)); HIPCHK(c, c->tb_lens.ensure(nl + 2u));
+    HIPCHK(c, c->tb_blk.ensure(nl / ZA_TBX_SCAN_ITEMS + 2u));
+    HIPCHK(c, hipMemsetAsync(c->fa_first.p, 0xFF, (nl + 2u) * 4u, c->stream)); HIPCHK(c, hipMemsetAsync(c->fa_last.p, 0xFF, (nl + 2u) * 4u, c->stream));
+    const uint32_t grid_l = (uint32_t)((nl + 255u) / 256u);
+    uint64_t nj = ndelim;                                 // the lines this call judges: with _FINAL the bytes behind the last '\n' are one
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      if (ntiles) hipLaunchKernelGGL(za_k_fai_starts, dim3(ntiles), dim3(256), 0, c->stream, text_off, text_end, tile0, c->tb_bits.p, c->tb_tbase.p, ndelim,
+                                     c->fa_start.p); }
+    if ((flags & ZA_FAI_FINAL) && ntiles) {               // (is there a byte behind the last '\n'?  one u64 more)
+        uint64_t last_start = 0;
+        HIPCHK(c, hipMemcpyAsync(&last_start, c->fa_start.p + ndelim, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (last_start < text_end) nj = ndelim + 1ull;
+    }
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      if (nj) {
+          hipLaunchKernelGGL(za_k_fai_bytes, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, text_end, c->tb_bits.p, c->fa_x.p, c->tb_tbase.p, c->fa_start.p, nj,
+                             line_base, d_st);
+          hipLaunchKernelGGL(za_k_fai_classify, dim3(grid_l), dim3(256), 0, c->stream, d_scratch, text_off, text_end, c->fa_start.p, ndelim, nj, nl, line_base,
+                             c->tb_data.p, c->tb_name.p, c->tb_bin.p, c->fa_bw.p, d_st);
+          tbx_scan(c, c->tb_data.p, nl, ZA_TBX_SUM, T + 15);
+          tbx_scan(c, c->tb_name.p, nl, ZA_TBX_SUM, T + 16);
+          tbx_scan(c, c->tb_bin.p, nl, ZA_TBX_SUM, T + 17);
+          hipLaunchKernelGGL(za_k_fai_heads, dim3(grid_l), dim3(256), 0, c->stream, d_scratch, c->fa_start.p, c->tb_data.p, c->fa_bw.p, nj, c->fa_hline.p,
+                             c->tb_lens.p, d_st);
+          hipLaunchKernelGGL(za_k_fai_ends, dim3(grid_l), dim3(256), 0, c->stream, c->tb_data.p, c->tb_name.p, c->fa_hline.p, nj, T + 15, c->fa_first.p,
+                             c->fa_last.p);
+          hipLaunchKernelGGL(za_k_fai_judge, dim3(grid_l), dim3(256), 0, c->stream, c->tb_data.p, c->tb_name.p, c->fa_bw.p, c->fa_hline.p, c->fa_first.p, nj,
+                             line_base, flags, T + 15, d_cin, d_st);
+      }
+      hipLaunchKernelGGL(za_k_fai_close, dim3(1), dim3(64), 0, c->stream, c->tb_name.p, c->tb_bin.p, c->fa_bw.p, c->fa_start.p, c->fa_hline.p, c->fa_first.p,
+                         c->fa_last.p, ndelim, nj, text_off, text_end, line_base, flags, T + 15, d_cin, d_st); }
+    HIPCHK(c, hipGetLastError());
+    unsigned long long H[18];
+    HIPCHK(c, hipMemcpyAsync(H, T, sizeof H, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ZaFaiState st;
+    memcpy(&st, H, sizeof st);
+    totals->covered = 1; totals->seen = st.seen; totals->records = st.records; totals->tail_off = st.tail_off; totals->head_bases = st.head_bases;
+    totals->name_bytes = st.name_bytes; totals->head_line_bases = st.head_fb; totals->head_line_width = st.head_fw;
+    memcpy(&totals->carry, &st.out, sizeof st.out);
+    if (st.bad_key != ~0ull) {                            // a bad line: where it starts (a line of a window in front: ~0, the caller knows)
+        totals->bad_kind = (uint32_t)(st.bad_key & 7u); totals->bad_line = st.bad_key >> 3; totals->bad_src = ~0ull;
+        if (totals->bad_line >= line_base) {
+            const uint64_t k = totals->bad_line - line_base;
+            if (k >= nl) return fail(c, ZNGAMD_E_ARG, "bad line out of range");
+            HIPCHK(c, hipMemcpyAsync(&totals->bad_src, c->fa_start.p + k, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+    }
+    const uint64_t nr = st.records;
+    if (!nr) return ZNGAMD_OK;
+    if (nr > nl) return fail(c, ZNGAMD_E_ARG, "records out of range");
+    if (own) {
+        HIPCHK(c, c->fa_rows.ensure(nr)); HIPCHK(c, c->bg_out.ensure(st.name_bytes + 64));
+        d_rows = c->fa_rows.p; rows_cap = nr; d_blob = c->bg_out.p; blob_cap = st.name_bytes;
+    } else if (nr > rows_cap || st.name_bytes > blob_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    HIPCHK(c, c->st_off.ensure(nr)); HIPCHK(c, c->bg_slices.ensure(nr + 1)); HIPCHK(c, c->bg_sstat.ensure(nr + 1));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_fai_emit, dim3((uint32_t)((nr + 255u) / 256u)), dim3(256), 0, c->stream, c->fa_start.p, c->tb_bin.p, c->fa_bw.p, c->fa_hline.p,
+                         c->fa_first.p, c->tb_lens.p, nr, nj, text_end, line_base, H[17], d_rows, nr);
+      hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(nr <= 64 ? 64 : 1024), 0, c->stream, c->tb_lens.p, (uint32_t)nr, 0u, 0ull, c->st_off.p, (uint64_t *)(T + 18),
+                         (const ZaUnit *)nullptr);
+      hipLaunchKernelGGL(za_k_fai_place, dim3((uint32_t)((nr + 255u) / 256u)), dim3(256), 0, c->stream, d_rows, c->st_off.p, nr, c->bg_slices.p);
+      if (st.name_bytes) hipLaunchKernelGGL(za_k_slice_gather, dim3((uint32_t)nr), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members,
+                                            c->bg_slices.p, d_blob, st.name_bytes, c->bg_sstat.p); }
+    c->bgzf_stats[2] += nr;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_faidx_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                          uint64_t text_end, int delim, uint32_t flags, uint64_t line_base, const zngamd_faidx_carry *carry, void *d_scratch,
+                          uint64_t scratch_cap, int32_t *d_status, zngamd_faidx_row *d_rows, uint64_t rows_cap, void *d_blob, uint64_t blob_cap,
+                          zngamd_bgzf_faidx_totals *totals)
+try {
+    if (delim != 10 || (flags & ~ZNGAMD_BGZF_FAIDX_FINAL)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) ||
+        (!d_blob && blob_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_faidx_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, flags, line_base, carry,
+                           (uint8_t *)d_scratch, scratch_cap, d_status, (ZaFaiRow *)d_rows, rows_cap, (uint8_t *)d_blob, blob_cap, false, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_faidx(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                      uint64_t text_end, int delim, uint32_t flags, uint64_t line_base, const zngamd_faidx_carry *carry, int32_t *status,
+                      zngamd_faidx_row *rows, uint64_t rows_cap, uint8_t *blob, uint64_t blob_cap, zngamd_alloc_fn alloc, void *user,
+                      zngamd_bgzf_faidx_totals *totals)
+try {
+    if (delim != 10 || (flags & ~ZNGAMD_BGZF_FAIDX_FINAL)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!blob && blob_cap) ||
+        (alloc && (rows || blob))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    r = bgzf_faidx_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, flags, line_base, carry, c->st_out.p, scratch, c->mstatus.p,
+                       nullptr, 0, nullptr, 0, true, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t nr = totals->records, by = totals->name_bytes;
+    if (!totals->covered || !nr) return ZNGAMD_OK;
+    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
+        rows = (zngamd_faidx_row *)alloc(user, nr * sizeof(ZaFaiRow));
+        blob = rows && by ? (uint8_t *)alloc(user, by) : nullptr;
+        if (!rows || (by && !blob)) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (nr > rows_cap || by > blob_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    HIPCHK(c, hipMemcpyAsync(rows, c->fa_rows.p, (size_t)nr * sizeof(ZaFaiRow), hipMemcpyDeviceToHost, c->stream));
+    if (by) HIPCHK(c, hipMemcpyAsync(blob, c->bg_out.p, by, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// the blocks in one launch, then one workgroup per span
+static int bgzf_faidx_fetch_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, const ZaFaiSpan *d_spans,
+                                uint32_t n_spans, uint8_t *d_scratch, uint64_t scratch_cap, uint8_t *d_out, uint64_t out_cap, int32_t *d_status,
+                                int32_t *d_span_status)
+{
+    if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+    if (n_spans) {
+        ProfScope ps(c, ZNGAMD_K_GATHER);
+        hipLaunchKernelGGL(za_k_fai_gather, dim3(n_spans), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, d_spans, d_out,
+                           out_cap, d_span_status);
+        c->bgzf_stats[2] += n_spans;
+    }
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_faidx_fetch_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                const zngamd_faidx_span *d_spans, uint32_t n_spans, void *d_scratch, uint64_t scratch_cap, void *d_out, uint64_t out_cap,
+                                int32_t *d_status, int32_t *d_span_status)
+try {
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) ||
+        (n_spans && (!d_spans || !d_span_status || (!d_out && out_cap))) || n_spans >= (1u << 31)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_faidx_fetch_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, (const ZaFaiSpan *)d_spans, n_spans,
+                                 (uint8_t *)d_scratch, scratch_cap, (uint8_t *)d_out, out_cap, d_status, d_span_status);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_faidx_fetch(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                            const zngamd_faidx_span *spans, uint32_t n_spans, uint8_t *out, uint64_t out_cap, int32_t *status, int32_t *span_status)
+try {
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (n_spans && (!spans || !span_status)) || (!out && out_cap) ||
+        n_spans >= (1u << 31)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    HIPCHK(c, c->bg_out.ensure(out_cap + 64)); HIPCHK(c, c->fa_spans.ensure(n_spans + 1u)); HIPCHK(c, c->bg_sstat.ensure(n_spans + 1u));
+    if (n_spans) HIPCHK(c, hipMemcpyAsync(c->fa_spans.p, spans, (size_t)n_spans * sizeof(ZaFaiSpan), hipMemcpyHostToDevice, c->stream));
+    r = bgzf_faidx_fetch_dev(c, c->st_in.p, in_len, c->members.p, n_members, c->fa_spans.p, n_spans, c->st_out.p, scratch, c->bg_out.p, out_cap,
+                             c->mstatus.p, c->bg_sstat.p);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    if (n_spans) HIPCHK(c, hipMemcpyAsync(span_status, c->bg_sstat.p, (size_t)n_spans * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (the uploads read the caller's pageable tables: drained before it may touch them again)
+    uint64_t used = 0;                                    // only the packed bases cross the link: as far as the spans reach
+    for (uint32_t i = 0; i < n_spans; i++)
+        if (span_status[i] != ZA_SLICE_TABLE) used = std::max<uint64_t>(used, spans[i].dst_off + spans[i].n);
+    if (used) { const int rc_ = d2h_payload(c, out, c->bg_out.p, std::min(used, out_cap)); if (rc_) return rc_; }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_stats(zngamd_ctx *c, uint64_t *out, int reset)

@@ -84,6 +84,7 @@ SYMBOLS = [
     "zngamd_bgzf_count_dev", "zngamd_bgzf_count", "zngamd_bgzf_line_positions_dev", "zngamd_bgzf_line_positions", "zngamd_bgzf_read_lines_dev",
     "zngamd_bgzf_read_lines", "zngamd_bgzf_grep_dev", "zngamd_bgzf_grep",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
+    "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
 
 
@@ -175,6 +176,25 @@ class BgzfTabixTotals(C.Structure):            # zngamd_bgzf_tabix_totals
 
 class BgzfFetchTotals(C.Structure):            # zngamd_bgzf_fetch_totals
     _fields_ = [("matched", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+BGZF_FAIDX_FINAL, BGZF_SLICE_STALE = 4, 4      # ZNGAMD_BGZF_FAIDX_FINAL, ZNGAMD_BGZF_SLICE_STALE
+FAIDX_OPEN, FAIDX_GAP, FAIDX_SPAN_RC, FAIDX_MAX_SPAN = 1, 2, 1, 65536      # ZNGAMD_FAIDX_*
+FAIDX_ROW_DTYPE = np.dtype([("name_src", "<u8"), ("seq_src", "<u8"), ("line", "<u8"), ("bases", "<u8"), ("name_len", "<u4"), ("line_bases", "<u4"),
+                            ("line_width", "<u4"), ("reserved", "<u4")])                                    # zngamd_faidx_row
+FAIDX_SPAN_DTYPE = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("n", "<u4"), ("col", "<u4"), ("line_bases", "<u4"), ("line_width", "<u4"),
+                             ("flags", "<u4"), ("reserved", "<u4")])                                        # zngamd_faidx_span
+
+
+class FaidxCarry(C.Structure):                 # zngamd_faidx_carry
+    _fields_ = [("last_line", C.c_uint64), ("first_bases", C.c_uint32), ("first_width", C.c_uint32), ("last_bases", C.c_uint32),
+                ("last_width", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class BgzfFaidxTotals(C.Structure):            # zngamd_bgzf_faidx_totals
+    _fields_ = [("seen", C.c_uint64), ("records", C.c_uint64), ("tail_off", C.c_uint64), ("head_bases", C.c_uint64), ("name_bytes", C.c_uint64),
+                ("bad_line", C.c_uint64), ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("bad_kind", C.c_uint32), ("carry", FaidxCarry),
+                ("head_line_bases", C.c_uint32), ("head_line_width", C.c_uint32)]
 
 
 def grep_pattern_table(patterns):
@@ -293,6 +313,13 @@ def load():
                                                 C.c_uint32, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
             L.zngamd_bgzf_fetch.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, vp, C.c_int, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp,
                                             C.c_uint32, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
+        if hasattr(L, "zngamd_bgzf_faidx"):
+            L.zngamd_bgzf_faidx_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, vp, vp,
+                                                C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_faidx.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, vp, vp,
+                                            vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
+            L.zngamd_bgzf_faidx_fetch_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+            L.zngamd_bgzf_faidx_fetch.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, u8p, C.c_uint64, vp, vp]
         if hasattr(L, "zngamd_bgzf_count"):
             L.zngamd_bgzf_count_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, vp, C.c_uint64, vp, vp]
             L.zngamd_bgzf_count.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_int, vp, vp]
@@ -1400,6 +1427,70 @@ class Context:
                                                    v(d_status), v(d_span_status), v(d_span_rows), v(d_rows), rows_cap, v(d_out), out_cap,
                                                    C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
+
+    def bgzf_faidx(self, data, members, text_off, text_end, delim, flags, line_base=0, carry=None, caps=None):
+        """zngamd_bgzf_faidx: carry = None (nothing is open) or a FaidxCarry -> (code, block statuses, totals (with the carry for the
+        next call), rows (FAIDX_ROW_DTYPE), the names packed).  caps None: the tables are allocated once the engine knows their sizes;
+        (rows, name bytes): buffers of those sizes, and code is BUF_ERROR (nothing written) when a table needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfFaidxTotals()
+        dts = (FAIDX_ROW_DTYPE, np.dtype("u1"))
+        box = []
+
+        def alloc(_user, nbytes):
+            arr = np.empty(nbytes // dts[len(box)].itemsize, dts[len(box)])
+            box.append(arr)
+            return arr.ctypes.data
+
+        if caps is None:
+            ptrs, fn = [None, 0] * 2, ALLOC_FN(alloc)
+        else:
+            bufs = [np.zeros(max(1, n), dt) for n, dt in zip(caps, dts)]
+            ptrs, fn = [], ALLOC_FN()
+            for b, n in zip(bufs, caps):
+                ptrs += [C.c_void_p(b.ctypes.data) if n else None, n]
+        r = self._chk(self.L.zngamd_bgzf_faidx(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm, text_off,
+                                               text_end, delim, flags, line_base, C.byref(carry) if carry is not None else None,
+                                               C.c_void_p(st.ctypes.data), *ptrs, fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        if r != OK or not tot.covered or not tot.records:
+            out = [np.empty(0, dt) for dt in dts]
+        elif caps is None:
+            out = box + [np.empty(0, np.uint8)] * (2 - len(box))
+        else:
+            out = [b[:n] for b, n in zip(bufs, (tot.records, tot.name_bytes))]
+        return r, st[:nm], tot, out[0], out[1].tobytes()
+
+    def bgzf_faidx_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, line_base, carry, d_scratch, scratch_cap,
+                       d_status, d_rows, rows_cap, d_blob, blob_cap):
+        """zngamd_bgzf_faidx_dev on device pointers (the carry: host memory) -> (code, totals); rows and names stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfFaidxTotals()
+        r = self._chk(self.L.zngamd_bgzf_faidx_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags, line_base,
+                                                   C.byref(carry) if carry is not None else None, v(d_scratch), scratch_cap, v(d_status),
+                                                   v(d_rows), rows_cap, v(d_blob), blob_cap, C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def bgzf_faidx_fetch(self, data, members, spans, out_cap):
+        """zngamd_bgzf_faidx_fetch: spans = FAIDX_SPAN_DTYPE rows -> (block statuses int32[n], span verdicts int32[n], packed bases)"""
+        nm, ns = len(members), len(spans)
+        p, keep = _addr(data)
+        spans = np.ascontiguousarray(spans, FAIDX_SPAN_DTYPE)
+        out, op = _new_bytes(out_cap)
+        st = np.zeros(max(1, nm), np.int32)
+        ss = np.zeros(max(1, ns), np.int32)
+        self._chk(self.L.zngamd_bgzf_faidx_fetch(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                 C.c_void_p(spans.ctypes.data) if ns else None, ns, op if out_cap else None, out_cap,
+                                                 C.c_void_p(st.ctypes.data), C.c_void_p(ss.ctypes.data)))
+        return st[:nm], ss[:ns], _take(out, out_cap)
+
+    def bgzf_faidx_fetch_dev(self, d_in, in_len, d_members, n_members, d_spans, n_spans, d_scratch, scratch_cap, d_out, out_cap, d_status,
+                             d_span_status):
+        """zngamd_bgzf_faidx_fetch_dev on device pointers; statuses and bases stay on the device."""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        self._chk(self.L.zngamd_bgzf_faidx_fetch_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_spans), n_spans, v(d_scratch),
+                                                     scratch_cap, v(d_out), out_cap, v(d_status), v(d_span_status)))
 
     def bgzf_stats(self, reset=True):
         """(decode launches, blocks decoded, slices gathered) of the ranged reads since the last reset"""

@@ -29,6 +29,10 @@ offset inside that block's output -- what .bai, .tbi and .csi indexes store, and
     tbi.save("calls.vcf.gz.tbi")                                      # standard .tbi comes out; fetch() plans on it, decodes the blocks
     rows = bgzf.fetch("calls.vcf.gz", tbi, "chr7:55,000,000-55,200,000")      # of the region's chunks and filters their lines on the GPU
 
+    fai = bgzf.FaidxIndex.build("ref.fa.gz")                          # bases by sequence: the records of a FASTA are read on the GPU;
+    fai.save("ref.fa.gz.fai", "ref.fa.gz.gzi")                        # the standard pair of indexes comes out
+    seqs = bgzf.fetch_seq("ref.fa.gz", fai, ["chr7:55,000,000-55,200,000", ("chrM", 0, 300)], reverse_complement=True)
+
 The .gzi index (`GziIndex`) maps uncompressed offsets to blocks.  On disk, little-endian: a u64 count, then for every data block
 AFTER the first a pair of u64 (compressed offset, uncompressed offset).  save() writes no entry for the EOF block; load() accepts a
 file whose last entry points at it.  An index is untrusted: load() and the reader check it before it steers a read.
@@ -44,7 +48,7 @@ from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "GrepResult",
-           "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins"]
+           "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
 BadGzipFile = zlib_ng.BadGzipFile
 MAX_BLOCK_INPUT = 65280                       # htslib's 0xff00
@@ -1360,6 +1364,366 @@ def fetch(file, index, regions, *, count=False):
     return _fetch_file(file, fsize, None, index, regions, count, load_block)
 
 
+# ---- bases by sequence: a FASTA index built on the GPU, and subsequences gathered there
+_FAIDX_MAX_LINE = 512 << 20                   # a line that is still open after this many bytes of a window: ValueError.  Twice the longest
+                                              # human chromosome on one line; with two blocks it still fits the 1 GiB text of one engine call
+_FAIDX_KINDS = {1: "a header with an empty name", 2: "a sequence line holds a byte outside 0x21..0x7E",
+                3: "its length differs from the first line of its sequence", 4: "an empty line inside a sequence",
+                5: "sequence in front of the first header"}
+_STALE_FAI = "faidx index does not match the file"
+
+
+class _FaidxBad(ValueError):
+    def __init__(self, line, kind, voffset):
+        super().__init__(f"line {line} at virtual offset {voffset} cannot be indexed: {_FAIDX_KINDS[kind]}")
+        self.line, self.kind, self.voffset = line, kind, voffset
+
+
+class FaidxIndex:
+    """The .fai index of a FASTA file: per sequence, in file order, its name and (LENGTH, OFFSET, LINEBASES, LINEWIDTH) -- bases, the
+    uncompressed offset of its first base, bases and bytes per line.  For a BGZF file it goes with a GziIndex (`gzi`, None when it
+    was loaded without one).  build() makes both on the GPU; fetch_seq() reads subsequences with them."""
+
+    def __init__(self, rows, gzi=None):
+        self._names, self._rows = [], {}
+        for name, length, offset, lb, lw in rows:
+            name = bytes(name)
+            vals = (int(length), int(offset), int(lb), int(lw))
+            if not name or min(vals) < 0 or vals[3] < vals[2] or max(vals) >= 1 << 63:
+                raise ValueError(f"fai row {len(self._names)}: not a name and four numbers with LINEWIDTH >= LINEBASES")
+            if name in self._rows:
+                raise ValueError(f"fai row {len(self._names)}: the name {name!r} occurs twice")
+            self._names.append(name)
+            self._rows[name] = vals
+        self.gzi = gzi
+
+    @property
+    def names(self):
+        return list(self._names)
+
+    def __len__(self):
+        return len(self._names)
+
+    def __contains__(self, name):
+        return (name.encode() if isinstance(name, str) else bytes(name)) in self._rows
+
+    def __getitem__(self, name):
+        """-> (length, offset, line_bases, line_width); KeyError for a name the index does not hold"""
+        return self._rows[name.encode() if isinstance(name, str) else bytes(name)]
+
+    def __eq__(self, other):
+        return isinstance(other, FaidxIndex) and self._names == other._names and self._rows == other._rows
+
+    def to_bytes(self):
+        """the five-column .fai text"""
+        return b"".join(b"%s\t%d\t%d\t%d\t%d\n" % ((n,) + self._rows[n]) for n in self._names)
+
+    @classmethod
+    def from_bytes(cls, blob, gzi=None):
+        rows = []
+        for i, line in enumerate(bytes(blob).split(b"\n")):
+            if line.endswith(b"\r"):
+                line = line[:-1]
+            if not line:
+                continue
+            cols = line.split(b"\t")
+            if len(cols) == 6:
+                raise ValueError(f"fai line {i}: six columns, a FASTQ index (fqidx) -- not supported")
+            if len(cols) != 5 or not all(c.isdigit() for c in cols[1:]):
+                raise ValueError(f"fai line {i}: not a name and four numbers")
+            rows.append((cols[0],) + tuple(int(c) for c in cols[1:]))
+        return cls(rows, gzi)
+
+    def save(self, fai_path, gzi_path=None):
+        """the .fai text, and with gzi_path the .gzi next to it"""
+        if hasattr(fai_path, "write"):
+            fai_path.write(self.to_bytes())
+        else:
+            with _builtin_open(fai_path, "wb") as f:
+                f.write(self.to_bytes())
+        if gzi_path is not None:
+            if self.gzi is None:
+                raise ValueError("this index holds no gzi")
+            self.gzi.save(gzi_path)
+
+    @classmethod
+    def load(cls, fai_path, gzi_path=None):
+        """without gzi_path, `gzi` is None and fetch_seq() walks the file's block headers for one (GziIndex.build)"""
+        if hasattr(fai_path, "read"):
+            blob = fai_path.read()
+        else:
+            with _builtin_open(fai_path, "rb") as f:
+                blob = f.read()
+        return cls.from_bytes(blob, GziIndex.load(gzi_path) if gzi_path is not None else None)
+
+    @classmethod
+    def build(cls, file):
+        """Index a bgzipped FASTA (a path or a seekable binary file) on the GPU.  The file is read in windows as grep() reads it; each
+        window's blocks are decoded in one launch, the record structure is read where the text lies, and one row per header comes
+        back -- nothing per line.  ValueError with .line, .kind and .voffset for the smallest bad line (the line model: INTEGRATION.md),
+        ValueError for a name that occurs twice (it names both header lines); BadGzipFile for a file that is not BGZF or a block that
+        does not decode.  The GziIndex of the blocks that were walked is kept as `gzi`."""
+        if _is_path(file):
+            with _builtin_open(file, "rb") as f:
+                return _faidx_build(f, None)
+        return _faidx_build(file, None)
+
+
+def _faidx_build(fp, ctx):
+    ctx = ctx or zlib_ng._ctx()
+    recs, blocks = [], []                                    # [name, line, length, offset, line_bases, line_width]; (coffset, uoffset, csize, isize)
+    carry, last_v = None, (0, 0)                             # last_v: where carry.last_line and the line behind it start
+    c_next, u_next, text_off, text_cap = 0, 0, 0, max(_GREP_TEXT, _FAIDX_MAX_LINE + 2 * MAX_BLOCK)
+    window, nblocks, line_base, final = _READ_WINDOW, 0, 0, False
+    buf = mv = None
+    try:
+        while True:
+            if buf is None or len(buf) < window + MAX_BLOCK:
+                if buf is not None:
+                    del mv
+                    _lib.give_buffer(buf)
+                buf = _lib.take_buffer(window + MAX_BLOCK)
+                mv = memoryview(buf)
+            fp.seek(c_next)
+            got = _read_full(fp, mv[:window + MAX_BLOCK])
+            if not got:
+                break
+            data = mv[:got]
+            ended = got < window + MAX_BLOCK
+            code, tab, used, total = _lib.bgzf_scan(data)
+            if ended and used < got and _cut_block(data[used:]):
+                raise EOFError(f"BGZF block {nblocks + len(tab)} at offset {c_next + used}: the file ends inside the block")
+            if code != _lib.OK or not tab:
+                raise _scan_error(code if c_next + used == 0 else _lib.DATA_ERROR, nblocks + len(tab), c_next + used)
+            t = np.array(tab, np.int64)
+            coffs, csizes, isizes = t[:, 0], t[:, 2], t[:, 3]
+            ustarts = np.cumsum(isizes) - isizes
+            for k in range(len(tab)):                        # the gzi: every block once, in file order
+                if not blocks or c_next + int(coffs[k]) > blocks[-1][0]:
+                    blocks.append((c_next + int(coffs[k]), u_next + int(ustarts[k]), int(csizes[k]), int(isizes[k])))
+            n_use, text_end, final = _grep_window(coffs + c_next, isizes, text_off, None, ended and used == got, text_cap)
+            members, bad = _member_table(np.frombuffer(data, np.uint8), coffs[:n_use], csizes[:n_use], isizes[:n_use])
+            if bad >= 0:
+                raise BadGzipFile(f"BGZF block {nblocks + bad} at offset {c_next + int(coffs[bad])}: bad block header or block size")
+            cend = int(coffs[n_use - 1] + csizes[n_use - 1]) if n_use else 0
+            _, status, tot, rows, blob = ctx.bgzf_faidx(data[:cend], members, text_off, text_end, 10, _lib.BGZF_FAIDX_FINAL if final else 0,
+                                                        line_base, carry)
+            bad = np.nonzero(status)[0]
+            if len(bad):
+                raise _block_error(c_next + int(coffs[bad[0]]), status[bad[0]])
+            if not tot.covered:
+                raise BadGzipFile(f"BGZF blocks at offset {c_next}: the decoded blocks do not cover the text")
+            out_offs, abs_c = members["out_off"].astype(np.int64), coffs[:n_use] + c_next
+
+            def voffset(src):
+                v, beyond = _tabix_voffsets([src], out_offs, isizes[:n_use], abs_c)
+                return int(abs_c[-1] + csizes[n_use - 1]) << 16 if beyond[0] else int(v[0])
+            if tot.bad_kind:
+                if tot.bad_line >= line_base:
+                    raise _FaidxBad(int(tot.bad_line), int(tot.bad_kind), voffset(int(tot.bad_src)))
+                raise _FaidxBad(int(tot.bad_line), int(tot.bad_kind), last_v[0] if tot.bad_kind == 3 else last_v[1])
+            if recs:                                         # the lines in front of the window's first header belong to the open sequence
+                recs[-1][2] += int(tot.head_bases)
+                if not recs[-1][5] and tot.head_line_width:
+                    recs[-1][4], recs[-1][5] = int(tot.head_line_bases), int(tot.head_line_width)
+            ends = np.cumsum(rows["name_len"].astype(np.int64))
+            for r, e in zip(rows, ends.tolist()):
+                recs.append([blob[e - int(r["name_len"]):e], int(r["line"]), int(r["bases"]), u_next + int(r["seq_src"]), int(r["line_bases"]),
+                             int(r["line_width"])])
+            carry = tot.carry
+            if carry.flags & _lib.FAIDX_OPEN and carry.last_line >= line_base and n_use:
+                nxt = text_off + int(carry.reserved)
+                last_v = (voffset(nxt - int(carry.last_width)), voffset(nxt))
+            line_base += tot.seen
+            try:
+                nxt = _grep_advance(isizes, n_use, text_off, text_end, int(tot.tail_off), final, window, _FAIDX_MAX_LINE)
+            except _LongLine as e:
+                v = make_virtual_offset(c_next + int(coffs[e.block]), e.offset)
+                raise ValueError(f"the line at virtual offset {v} has not ended after {_FAIDX_MAX_LINE} bytes") from None
+            if nxt is None:
+                break
+            b, text_off, window = nxt
+            nblocks += b
+            u_next += int(ustarts[b]) if b < len(coffs) else total
+            c_next += int(coffs[b]) if b < len(coffs) else used
+    finally:
+        if buf is not None:
+            del mv
+            _lib.give_buffer(buf)
+    if not final and carry is not None and carry.flags & _lib.FAIDX_OPEN and carry.first_width and carry.last_bases > carry.first_bases:
+        raise _FaidxBad(int(carry.last_line), 3, last_v[0])  # (a file that ends exactly where a read ended: no call had _FINAL)
+    seen = {}
+    for name, line, *_ in recs:
+        if name in seen:
+            raise ValueError(f"the name {name!r} occurs twice: header lines {seen[name]} and {line}")
+        seen[name] = line
+    return FaidxIndex([(r[0], r[2], r[3], r[4], r[5]) for r in recs], GziIndex.from_blocks(blocks))
+
+
+class SeqResult:
+    """What fetch_seq() found: len() regions; offsets (int64, n + 1 of them) into data (the bases packed, without line terminators);
+    result[i], slices and iteration yield bytes."""
+
+    def __init__(self, offsets, data):
+        self.offsets = np.asarray(offsets, np.int64)
+        self.data = data
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(len(self)))]
+        n = len(self)
+        k = int(i)
+        if not -n <= k < n:
+            raise IndexError("SeqResult index out of range")
+        k %= n
+        return bytes(self.data[int(self.offsets[k]):int(self.offsets[k + 1])])
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+    def __repr__(self):
+        return f"<SeqResult: {len(self)} regions, {int(self.offsets[-1])} bases>"
+
+
+def _seq_regions(index, regions):
+    """-> ([(row, beg, end)] clipped to the sequences, whether one region was given); KeyError for a name the index does not hold"""
+    single = isinstance(regions, (str, bytes, tuple))
+    out = []
+    for r in ([regions] if single else list(regions)):
+        if isinstance(r, tuple):
+            open_end = len(r) == 3 and r[2] is None
+            name, beg, end = parse_region((r[0], r[1], 0) if open_end else r)
+        else:
+            text = r.encode() if isinstance(r, str) else bytes(r)
+            name, beg, end = parse_region(text)
+            open_end = name == text or b"-" not in text.rpartition(b":")[2]
+        row = index[name]
+        end = row[0] if open_end else min(end, row[0])
+        out.append((row, beg, end) if beg < end else (row, 0, 0))
+    return out, single
+
+
+def _seq_spans(regs, rc, text_cap=1 << 62):
+    """Cut the regions into spans of at most FAIDX_MAX_SPAN bases and (with lines of that many bases at most) about text_cap bytes
+    that begin at line starts behind a region's first.
+    -> [(region, first byte, last byte, bases, col, line_bases, line_width, place in the region's output)] (pure host code)"""
+    spans = []
+    for i, ((length, offset, lb, lw), beg, end) in enumerate(regs):
+        if end <= beg:
+            continue
+        if not lb:
+            raise ValueError(_STALE_FAI)
+        step = min(_lib.FAIDX_MAX_SPAN // lb, max(1, text_cap // lw)) * lb if lb <= _lib.FAIDX_MAX_SPAN else _lib.FAIDX_MAX_SPAN
+        b0 = beg
+        while b0 < end:
+            b1 = min(end, (b0 // lb * lb if lb <= _lib.FAIDX_MAX_SPAN else b0) + step)
+            first, last = offset + b0 // lb * lw + b0 % lb, offset + (b1 - 1) // lb * lw + (b1 - 1) % lb
+            spans.append((i, first, last, b1 - b0, b0 % lb, lb, lw, end - b1 if rc else b0 - beg))
+            b0 = b1
+    return spans
+
+
+def _fetch_seq_file(fp, fsize, ctx, index, regions, rc, load_block):
+    if not isinstance(index, FaidxIndex):
+        raise TypeError("fetch_seq() takes a FaidxIndex")
+    regs, single = _seq_regions(index, regions)             # (KeyError before anything is read or decoded)
+    offsets = np.zeros(len(regs) + 1, np.int64)
+    np.cumsum([e - b for _, b, e in regs], out=offsets[1:])
+    spans = _seq_spans(regs, rc, _GREP_TEXT)
+    if not spans:
+        return SeqResult(offsets, b"")
+    gzi = index.gzi if index.gzi is not None else GziIndex.build(fp)
+    gzi.validate(fsize)
+    cs, us = [0] + [c for c, _ in gzi.entries], [0] + [u for _, u in gzi.entries]
+    ctx = ctx or zlib_ng._ctx()
+    cache, chains, ubase = {}, [], {}
+    for _, first, last, *_ in spans:                         # byte spans -> blocks, through the gzi
+        i0, i1 = bisect.bisect_right(us, first) - 1, bisect.bisect_right(us, last) - 1
+        chain = cs[i0:i1 + 1]
+        for k, c in enumerate(chain, i0):
+            blk = load_block(c, cache) if c < fsize else None
+            if blk is None or (k + 1 < len(us) and us[k + 1] - us[k] != blk[2]):
+                raise ValueError(_STALE_FAI)
+            ubase[c] = us[k]
+        if last - us[i1] >= cache[chain[-1]][2]:
+            raise ValueError(f"a region's bytes end at uncompressed offset {last}: does not fit the file's data")
+        chains.append(chain)
+    isize_of = {c: b[2] for c, b in cache.items() if b is not None}
+    out = bytearray(int(offsets[-1]))
+    for a, b in _fetch_groups(spans, chains, isize_of, _GREP_TEXT, 1 << 62):
+        need = sorted({c for chain in chains[a:b] for c in chain})
+        raws = [cache[c][0] for c in need]
+        members = np.zeros(len(need), MEMBER_DTYPE)
+        lens = np.fromiter((len(r) for r in raws), np.uint64, len(need))
+        hdrs = np.fromiter((cache[c][1] for c in need), np.uint64, len(need))
+        members["out_len"] = np.fromiter((cache[c][2] for c in need), np.uint32, len(need))
+        members["crc"] = np.fromiter((struct.unpack_from("<I", r, len(r) - 8)[0] for r in raws), np.uint32, len(need))
+        members["in_off"] = np.cumsum(lens) - lens + hdrs
+        members["in_len"] = lens - hdrs - 8
+        opos = np.cumsum(members["out_len"], dtype=np.uint64) - members["out_len"]
+        members["out_off"] = opos
+        where = dict(zip(need, opos.tolist()))
+        stab = np.zeros(b - a, _lib.FAIDX_SPAN_DTYPE)
+        # a region's spans of this call lie together in the call's output, in the order of the region's output (reversed under
+        # reverse_complement); runs that follow each other there and in the result are copied as one
+        runs, k = [], a
+        while k < b:
+            e = k
+            while e < b and spans[e][0] == spans[k][0]:
+                e += 1
+            lo = min(spans[j][7] for j in range(k, e))
+            at = runs[-1][0] + runs[-1][2] if runs else 0
+            g = int(offsets[spans[k][0]]) + lo
+            for j in range(k, e):
+                i, first, last, n, col, lb, lw, place = spans[j]
+                stab[j - a] = (where[chains[j][0]] + first - ubase[chains[j][0]], at + place - lo, n, col, lb, lw, 1 if rc else 0, 0)
+            n_run = sum(spans[j][3] for j in range(k, e))
+            if runs and runs[-1][1] + runs[-1][2] == g:
+                runs[-1][2] += n_run
+            else:
+                runs.append([at, g, n_run])
+            k = e
+        status, sstat, packed = ctx.bgzf_faidx_fetch(b"".join(raws), members, stab, runs[-1][0] + runs[-1][2])
+        bad = np.nonzero(status)[0]
+        if len(bad):
+            raise _block_error(need[int(bad[0])], status[bad[0]])
+        if bool(np.any(sstat)):
+            raise ValueError(_STALE_FAI)
+        pm = memoryview(packed)
+        for at, g, n in runs:
+            out[g:g + n] = pm[at:at + n]
+    return SeqResult(offsets, bytes(out))
+
+
+def fetch_seq(file, index, regions, *, reverse_complement=False):
+    """The bases of `regions` of a bgzipped FASTA (a path or a seekable binary file): one region or a list of them, each a string as
+    parse_region() reads it ("chr7:55,000,000-55,200,000", 1-based inclusive; without an end: to the sequence's end) or a tuple (name,
+    beg, end), zero-based and half-open (end None: the sequence's end).  `index`: the file's FaidxIndex.  An end beyond the sequence is
+    clipped, a start at or beyond it gives an empty result; a name the index does not hold is a KeyError, raised before anything is
+    decoded.  The plan is made on the two indexes alone; every needed block is read and decoded once, the bases are gathered on the
+    GPU without their line terminators (reverse_complement: reversed and complemented there, IUPAC codes in both cases), and only they
+    come back: a SeqResult, in the order of the regions.  ValueError for an index that does not fit the file, BadGzipFile (with its
+    offset) for a block that fails."""
+    if _is_path(file):
+        with _builtin_open(file, "rb") as f:
+            return fetch_seq(f, index, regions, reverse_complement=reverse_complement)
+    fsize = file.seek(0, 2)
+
+    def load_block(c, cache):                                # (as BgzfReader._load_block)
+        if c not in cache:
+            file.seek(c)
+            raw = file.read(MAX_BLOCK)
+            code, tab, used, total = _lib.bgzf_scan(raw, 1) if raw else (_lib.OK, [], 0, 0)
+            if raw and (code != _lib.OK or not tab):
+                raise BadGzipFile(f"BGZF block at offset {c}: bad block header or block size")
+            cache[c] = (raw[:used], 12 + struct.unpack_from("<H", raw, 10)[0], tab[0][3]) if raw else None
+        return cache[c]
+    return _fetch_seq_file(file, fsize, None, index, regions, bool(reverse_complement), load_block)
+
+
 def _scan_file(f):
     """-> (block table of the whole file, file size); BadGzipFile for anything that is not a complete run of BGZF blocks"""
     f.seek(0)
@@ -1868,6 +2232,18 @@ class BgzfReader(io.BufferedIOBase):
         at = self._fp.tell()
         try:
             return _fetch_file(self._fp, self._fsize, self._ctx, index, regions, count, self._load_block)
+        finally:
+            self._fp.seek(at)
+
+    def fetch_seq(self, index, regions, *, reverse_complement=False):
+        """bgzf.fetch_seq() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("fetch_seq() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _fetch_seq_file(self._fp, self._fsize, self._ctx, index, regions, bool(reverse_complement), self._load_block)
         finally:
             self._fp.seek(at)
 
