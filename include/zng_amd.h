@@ -578,6 +578,50 @@ int zngamd_bgzf_grep(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const 
                      int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap,
                      zngamd_alloc_fn alloc, void *user, zngamd_bgzf_grep_totals *totals);
 
+/* ---- BGZF by record (zlib_ng_amd/bgzf.py: grep_records).  zngamd_bgzf_grep on records of record_lines
+ * (k, 1 .. 64) lines each: FASTQ 4, two-line FASTA 2, interleaved pairs 8; k = 1 is zngamd_bgzf_grep.  Blocks, member table, text,
+ * patterns, delimiter, the lines, _FINAL, _LINE_START, _COUNT_ONLY, the cover contract, ZNGAMD_BUF_ERROR and alloc are those of
+ * zngamd_bgzf_grep.  The record model:
+ *   - text_off is a record start.  Record r of the call is its lines [k r, k r + k).
+ *   - A record is hit when one of the patterns occurs in one of its lines; with match_line = j (0 <= j < k; -1: any line) only line j
+ *     of the record counts; with _LINE_START the pattern must stand at that line's first byte.
+ *   - A record is selected when hit != _INVERT: invert works on records, the line verdicts are computed without it.
+ *   - A record whose last line has not ended in the text is the open tail: tail_off is where its FIRST line starts, and the next
+ *     call takes it up there.
+ *   - With _FINAL the lines left over (lines % k != 0) form one short last record, judged like any other on the lines it has;
+ *     short_lines says how many it has (0: the last record is whole).
+ *   - first_byte (0 .. 255; -1: no check): a record whose first byte differs is bad.  bad = 1: bad_record is the smallest such record's
+ *     number and bad_src its scratch offset; no row and no byte is written, the other totals are valid.
+ * Results: one row per selected record in ascending order (src_off: where its first line starts in the scratch; number: record_base +
+ * r; len: the bytes of its lines, delimiters included) and the records packed whole in that order.  record_lines, match_line or
+ * first_byte out of range: ZNGAMD_E_ARG, found before the context is touched, like everything zngamd_bgzf_grep refuses.  Device
+ * memory beside the tiles of zngamd_bgzf_grep: 8 bytes per line and 17 bytes per record of the text. */
+typedef struct {
+    uint64_t seen;         /* records of the text that were decided (the open tail is not one of them) */
+    uint64_t selected;     /* of them, selected */
+    uint64_t bytes;        /* bytes of the selected records */
+    uint64_t tail_off;     /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;   /* bad = 1: the number of the first record whose first byte is not first_byte */
+    uint64_t bad_src;      /*          and where it starts in the scratch */
+    uint32_t covered;      /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;  /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;
+    uint32_t reserved;
+} zngamd_bgzf_grep_records_totals;                                                                /* 64 B */
+#define ZNGAMD_BGZF_GREP_MAX_RECORD_LINES 64u
+int zngamd_bgzf_grep_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                 uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                                 const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t record_lines,
+                                 int32_t match_line, int32_t first_byte, uint64_t record_base, void *d_scratch, uint64_t scratch_cap,
+                                 int32_t *d_status, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap,
+                                 zngamd_bgzf_grep_records_totals *totals);
+int zngamd_bgzf_grep_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                             uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                             const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t record_lines,
+                             int32_t match_line, int32_t first_byte, uint64_t record_base, int32_t *status, zngamd_bgzf_grep_row *rows,
+                             uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user,
+                             zngamd_bgzf_grep_records_totals *totals);
+
 /* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
  * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM
  * preset, is ZNGAMD_E_ARG), the columns of the name, the start and the end (from 1; col_end 0: none), the byte that opens a comment

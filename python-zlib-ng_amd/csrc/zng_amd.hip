@@ -10,6 +10,7 @@
 #include "za_inflate_spans.hip"
 #include "za_bgzf.hip"
 #include "za_grep.hip"
+#include "za_grep_records.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
 #include "za_batch.hip"
@@ -41,6 +42,9 @@ static_assert(sizeof(zngamd_bgzf_pattern) == sizeof(ZaGrepPat) && sizeof(zngamd_
               ZNGAMD_BGZF_GREP_INVERT == ZA_GREP_INVERT && ZNGAMD_BGZF_GREP_LINE_START == ZA_GREP_LINE_START && ZNGAMD_BGZF_GREP_FINAL == ZA_GREP_FINAL &&
               ZNGAMD_BGZF_GREP_COUNT_ONLY == ZA_GREP_COUNT_ONLY && ZNGAMD_BGZF_GREP_MAX_PATTERNS == ZA_GREP_MAX_PAT && ZNGAMD_BGZF_GREP_MAX_PATTERN == ZA_GREP_MAX_LEN,
               "bgzf grep layout");
+static_assert(sizeof(zngamd_bgzf_grep_records_totals) == sizeof(ZaGrepRecTotals) && sizeof(ZaGrepRecTotals) == 64 &&
+              offsetof(ZaGrepRecTotals, covered) == offsetof(zngamd_bgzf_grep_records_totals, covered) && sizeof(ZaGrepTotals) == 56 &&
+              ZNGAMD_BGZF_GREP_MAX_RECORD_LINES == ZA_GREP_REC_MAX, "bgzf grep records layout");
 static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_tabix_name) == sizeof(ZaTbxName) && sizeof(zngamd_tabix_bin) == sizeof(ZaTbxBin) &&
               sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
               sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
@@ -147,6 +151,7 @@ struct zngamd_ctx {
     // records of a FASTA (za_faidx.hip, section 5h; the bits, the tile counts, three scanned arrays and the totals are those of 5g): bad-byte
     // bits, line starts, bases | width per line, where header r stands, first / last non-empty line per record, rows, spans
     DevBuf<unsigned long long> fa_x, fa_bw; DevBuf<uint64_t> fa_start; DevBuf<uint32_t> fa_hline, fa_first, fa_last; DevBuf<ZaFaiRow> fa_rows; DevBuf<ZaFaiSpan> fa_spans;
+    DevBuf<unsigned long long> gr_start, gr_sel, gr_len; DevBuf<uint8_t> gr_hit;      // records by content (za_grep_records.hip, section 5f.1): line starts; per record selected / bytes (scanned in place) and hit
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -296,6 +301,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->tb_bins.release(); c->tb_wins.release(); c->tb_par.release(); c->tb_spans.release(); c->tb_rows.release(); c->tb_srows.release(); c->tb_sstat.release(); c->tb_sbase.release();
     c->fa_x.release(); c->fa_bw.release(); c->fa_start.release(); c->fa_hline.release(); c->fa_first.release(); c->fa_last.release(); c->fa_rows.release(); c->fa_spans.release();
     c->gp_par.release(); c->gp_bits.release(); c->gp_tiles.release(); c->gp_carry.release(); c->gp_rows.release(); c->gp_lens.release();
+    c->gr_start.release(); c->gr_sel.release(); c->gr_len.release(); c->gr_hit.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -3674,14 +3680,13 @@ static bool grep_patterns_ok(const uint8_t *patterns, uint32_t patterns_len, con
 #define ZA_GREP_PAR_TABLE (ZA_GREP_PAIR_WORDS * 4u)                                // the parameter block: prefilter bits, pattern table, patterns
 #define ZA_GREP_PAR_BLOB  (ZA_GREP_PAR_TABLE + ZA_GREP_MAX_PAT * (uint32_t)sizeof(ZaGrepPat))
 
-// decode, cover, mark, scan, [the host waits for the totals], emit, offsets, place, gather.  own: the host form (rows and lines go to
-// the context's buffers, as long as the totals say).
-static int bgzf_grep_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
-                         uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
-                         uint32_t delim, uint32_t flags, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status,
-                         ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own, zngamd_bgzf_grep_totals *totals)
+// decode, cover, mark, scan, and the host waits for the scan's totals: the first `totals_len` bytes of ZaGrepTotals go to `totals`.
+// After it every tile has its bits, its summary and its carry (gp_bits, gp_tiles, gp_carry), unless covered is 0.
+static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
+                                uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                                uint32_t delim, uint32_t flags, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                                void *totals, size_t totals_len)
 {
-    memset(totals, 0, sizeof *totals);
     if (text_off > text_end || text_end > scratch_cap) return fail(c, ZNGAMD_E_ARG, "the text lies outside the scratch");
     if (text_end - text_off >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "a text of 4 GiB or more");
     const uint64_t tile0 = text_off / ZA_GREP_TILE;
@@ -3702,7 +3707,6 @@ static int bgzf_grep_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, co
     HIPCHK(c, hipMemcpyAsync(c->gp_par.p, par.data(), par.size(), hipMemcpyHostToDevice, c->stream));
     ZaGrepTotals *d_tot = (ZaGrepTotals *)c->d_small;
     unsigned long long *d_cover = (unsigned long long *)((uint8_t *)c->d_small + 64);
-    uint64_t *d_bytes = (uint64_t *)((uint8_t *)c->d_small + 128);
     HIPCHK(c, hipMemsetAsync(d_cover, 0, 16, c->stream));
     if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
     { ProfScope ps(c, ZNGAMD_K_GATHER);
@@ -3714,8 +3718,36 @@ static int bgzf_grep_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, co
       hipLaunchKernelGGL(za_k_grep_scan, dim3(1), dim3(ZA_GREP_SCAN_THREADS), 0, c->stream, c->gp_tiles.p, ntiles, tile0, text_off, text_end, flags, line_base,
                          d_cover, c->gp_carry.p, d_tot); }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, totals_len, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+// offsets, place, gather: the n rows' bytes packed into d_out in the order of the rows (gp_lens holds their lengths)
+static void bgzf_grep_pack(zngamd_ctx *c, const ZaMember *d_members, uint32_t n_members, const uint8_t *d_scratch, uint64_t scratch_cap, const int32_t *d_status,
+                           const ZaGrepRow *d_rows, uint64_t n, uint8_t *d_out, uint64_t bytes)
+{
+    uint64_t *d_bytes = (uint64_t *)((uint8_t *)c->d_small + 128);
+    hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n <= 64 ? 64 : 1024), 0, c->stream, c->gp_lens.p, (uint32_t)n, 0u, 0ull, c->st_off.p, d_bytes,
+                       (const ZaUnit *)nullptr);
+    hipLaunchKernelGGL(za_k_grep_place, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, c->stream, d_rows, c->st_off.p, n, c->bg_slices.p);
+    hipLaunchKernelGGL(za_k_slice_gather, dim3((uint32_t)n), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, c->bg_slices.p,
+                       d_out, bytes, c->bg_sstat.p);
+}
+
+// the lines pass, emit, pack.  own: the host form (rows and lines go to the context's buffers, as long as the totals say).
+static int bgzf_grep_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
+                         uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                         uint32_t delim, uint32_t flags, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                         ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own, zngamd_bgzf_grep_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, flags,
+                                       line_base, d_scratch, scratch_cap, d_status, totals, sizeof *totals);
+    if (r) return r;
+    const uint64_t tile0 = text_off / ZA_GREP_TILE;
+    const uint32_t ntiles = text_end > text_off ? (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull) : 0u;
+    const ZaGrepTotals *d_tot = (const ZaGrepTotals *)c->d_small;
     totals->reserved = 0;
     if (!totals->covered || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !totals->matched) return ZNGAMD_OK;
     const uint64_t n = totals->matched;
@@ -3724,15 +3756,10 @@ static int bgzf_grep_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, co
         d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; out_cap = totals->bytes;
     } else if (n > rows_cap || totals->bytes > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
     HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
-    const uint32_t grid = (uint32_t)((n + 255u) / 256u);
     { ProfScope ps(c, ZNGAMD_K_GATHER);
       hipLaunchKernelGGL(za_k_grep_emit, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_tot, tile0, line_base, text_end,
                          d_rows, n, c->gp_lens.p);
-      hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n <= 64 ? 64 : 1024), 0, c->stream, c->gp_lens.p, (uint32_t)n, 0u, 0ull, c->st_off.p, d_bytes,
-                         (const ZaUnit *)nullptr);
-      hipLaunchKernelGGL(za_k_grep_place, dim3(grid), dim3(256), 0, c->stream, d_rows, c->st_off.p, n, c->bg_slices.p);
-      hipLaunchKernelGGL(za_k_slice_gather, dim3((uint32_t)n), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, c->bg_slices.p,
-                         d_out, totals->bytes, c->bg_sstat.p); }
+      bgzf_grep_pack(c, d_members, n_members, d_scratch, scratch_cap, d_status, d_rows, n, d_out, totals->bytes); }
     c->bgzf_stats[2] += n;
     HIPCHK(c, hipGetLastError());
     return ZNGAMD_OK;
@@ -3777,6 +3804,125 @@ try {
     prof_collect(c);
     const uint64_t n = totals->matched;
     if (!totals->covered || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !n) return ZNGAMD_OK;
+    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
+        rows = (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow));
+        out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr;
+        if (!rows || !out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (n > rows_cap || totals->bytes > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return d2h_payload(c, out, c->bg_out.p, totals->bytes);
+} ZA_ABI_GUARD
+
+// ---- records by content (za_grep_records.hip)
+static void tbx_scan(zngamd_ctx *c, unsigned long long *v, uint64_t n, int op, unsigned long long *d_total);
+
+static bool grep_records_ok(uint32_t record_lines, int32_t match_line, int32_t first_byte)
+{
+    return record_lines >= 1 && record_lines <= ZNGAMD_BGZF_GREP_MAX_RECORD_LINES && match_line >= -1 && match_line < (int32_t)record_lines &&
+           first_byte >= -1 && first_byte <= 255;
+}
+
+// the lines pass without INVERT, [the host waits for the line count], lines, eval, the two scans, close, [the host waits for the totals],
+// emit, pack.  own: the host form (rows and records go to the context's buffers, as long as the totals say).
+static int bgzf_grep_records_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
+                                 uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                                 uint32_t delim, uint32_t flags, uint32_t k, int32_t match_line, int32_t first_byte, uint64_t record_base,
+                                 uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status, ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out,
+                                 uint64_t out_cap, bool own, zngamd_bgzf_grep_records_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    ZaGrepTotals lt;
+    const uint32_t lflags = flags & (ZA_GREP_LINE_START | ZA_GREP_FINAL);
+    const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, lflags,
+                                       0, d_scratch, scratch_cap, d_status, &lt, sizeof lt);
+    if (r) return r;
+    totals->tail_off = text_off;
+    if (!lt.covered) return ZNGAMD_OK;
+    totals->covered = 1;
+    const bool fin = (flags & ZA_GREP_FINAL) != 0;
+    const uint64_t lines = lt.seen, nrec = fin ? (lines + k - 1u) / k : lines / k;
+    if (fin) totals->tail_off = text_end;
+    if (!nrec) return ZNGAMD_OK;                                  // (without FINAL: fewer than k lines have ended, the open record starts at text_off)
+    const uint64_t tile0 = text_off / ZA_GREP_TILE;
+    const uint32_t ntiles = (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull);      // (a line was decided: the text is not empty)
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->gr_hit.ensure(nrec)); HIPCHK(c, c->gr_sel.ensure(nrec)); HIPCHK(c, c->gr_len.ensure(nrec));
+    HIPCHK(c, c->tb_blk.ensure(nrec / ZA_TBX_SCAN_ITEMS + 2u));
+    const ZaGrepTotals *d_lt = (const ZaGrepTotals *)c->d_small;
+    unsigned long long *d_sums = (unsigned long long *)((uint8_t *)c->d_small + 80);       // the two scans' totals, the first bad record
+    ZaGrepRecTotals *d_tot = (ZaGrepRecTotals *)((uint8_t *)c->d_small + 192);
+    HIPCHK(c, hipMemsetAsync(c->gr_hit.p, 0, nrec, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_sums + 2, 0xFF, 8, c->stream));
+    const uint32_t grid = (uint32_t)((nrec + 255u) / 256u);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_grep_rec_lines, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_lt, ntiles, tile0, text_off,
+                         text_end, lflags, k, match_line, c->gr_start.p, lines + 1u, c->gr_hit.p, nrec);
+      hipLaunchKernelGGL(za_k_grep_rec_eval, dim3(grid), dim3(256), 0, c->stream, d_scratch, text_off, text_end, c->gr_start.p, lines, c->gr_hit.p, nrec, k,
+                         flags & ZA_GREP_INVERT, first_byte, c->gr_sel.p, c->gr_len.p, d_sums + 2);
+      tbx_scan(c, c->gr_sel.p, nrec, ZA_TBX_SUM, d_sums);
+      tbx_scan(c, c->gr_len.p, nrec, ZA_TBX_SUM, d_sums + 1);
+      hipLaunchKernelGGL(za_k_grep_rec_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, text_end, record_base, d_sums, d_sums + 1,
+                         d_sums + 2, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (totals->bad || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !totals->selected) return ZNGAMD_OK;
+    const uint64_t n = totals->selected;
+    if (own) {
+        HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(totals->bytes + 64));
+        d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; out_cap = totals->bytes;
+    } else if (n > rows_cap || totals->bytes > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_grep_rec_emit, dim3(grid), dim3(256), 0, c->stream, c->gr_sel.p, c->gr_start.p, lines, nrec, k, record_base, d_rows, n, c->gp_lens.p);
+      bgzf_grep_pack(c, d_members, n_members, d_scratch, scratch_cap, d_status, d_rows, n, d_out, totals->bytes); }
+    c->bgzf_stats[2] += n;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_grep_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                 uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                                 int delim, uint32_t flags, uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base,
+                                 void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out,
+                                 uint64_t out_cap, zngamd_bgzf_grep_records_totals *totals)
+try {
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim) || !grep_records_ok(record_lines, match_line, first_byte)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (flags & ~15u) || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) ||
+        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_grep_records_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, patterns, patterns_len, table,
+                                  n_patterns, (uint32_t)delim, flags, record_lines, match_line, first_byte, record_base, (uint8_t *)d_scratch, scratch_cap,
+                                  d_status, (ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_grep_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                             uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                             int delim, uint32_t flags, uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base,
+                             int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc,
+                             void *user, zngamd_bgzf_grep_records_totals *totals)
+try {
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim) || !grep_records_ok(record_lines, match_line, first_byte)) return ZNGAMD_E_ARG;
+    if (!c || !totals || (flags & ~15u) || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!out && out_cap) ||
+        (alloc && (rows || out))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    r = bgzf_grep_records_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, (uint32_t)delim,
+                              flags, record_lines, match_line, first_byte, record_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, true,
+                              totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t n = totals->selected;
+    if (!totals->covered || totals->bad || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !n) return ZNGAMD_OK;
     if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
         rows = (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow));
         out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr;

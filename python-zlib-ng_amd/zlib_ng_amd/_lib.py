@@ -82,7 +82,7 @@ SYMBOLS = [
     "zngamd_train_dict_dev", "zngamd_train_dict",
     "zngamd_bgzf_compress_dev", "zngamd_bgzf_compress", "zngamd_bgzf_scan", "zngamd_bgzf_read_dev", "zngamd_bgzf_read", "zngamd_bgzf_stats",
     "zngamd_bgzf_count_dev", "zngamd_bgzf_count", "zngamd_bgzf_line_positions_dev", "zngamd_bgzf_line_positions", "zngamd_bgzf_read_lines_dev",
-    "zngamd_bgzf_read_lines", "zngamd_bgzf_grep_dev", "zngamd_bgzf_grep",
+    "zngamd_bgzf_read_lines", "zngamd_bgzf_grep_dev", "zngamd_bgzf_grep", "zngamd_bgzf_grep_records_dev", "zngamd_bgzf_grep_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
@@ -150,6 +150,18 @@ GREP_ROW_DTYPE = np.dtype([("src_off", "<u8"), ("number", "<u8"), ("len", "<u4")
 class BgzfGrepTotals(C.Structure):             # zngamd_bgzf_grep_totals
     _fields_ = [("seen", C.c_uint64), ("matched", C.c_uint64), ("bytes", C.c_uint64), ("tail_off", C.c_uint64),
                 ("covered", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+BGZF_GREP_MAX_RECORD_LINES = 64                # ZNGAMD_BGZF_GREP_MAX_RECORD_LINES
+
+
+class BgzfGrepRecordsTotals(C.Structure):      # zngamd_bgzf_grep_records_totals
+    _fields_ = [("seen", C.c_uint64), ("selected", C.c_uint64), ("bytes", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64),
+                ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads)
+        return self.selected
 
 
 BGZF_TABIX_FINAL, BGZF_FETCH_COUNT_ONLY, BGZF_FETCH_MAX_REGIONS = 4, 8, 4096      # ZNGAMD_BGZF_TABIX_FINAL, ZNGAMD_BGZF_FETCH_*
@@ -304,6 +316,13 @@ def load():
                                                C.c_uint32, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
             L.zngamd_bgzf_grep.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int,
                                            C.c_uint32, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
+        if hasattr(L, "zngamd_bgzf_grep_records"):
+            L.zngamd_bgzf_grep_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int,
+                                                       C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
+                                                       C.c_uint64, vp]
+            L.zngamd_bgzf_grep_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int,
+                                                   C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN,
+                                                   vp, vp]
         if hasattr(L, "zngamd_bgzf_tabix"):
             L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
                                                 C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1259,11 +1278,20 @@ class Context:
         grep_pattern_table gives them -> (code, block statuses, totals, rows (GREP_ROW_DTYPE), packed lines).  caps None: rows and
         lines are allocated once the engine knows their sizes; (rows, bytes): buffers of those sizes, and code is BUF_ERROR (nothing
         written) when the result needs more"""
+        return self._bgzf_grep(self.L.zngamd_bgzf_grep, BgzfGrepTotals(), data, members, text_off, text_end, blob, table, delim, flags, (line_base,), caps)
+
+    def bgzf_grep_records(self, data, members, text_off, text_end, blob, table, delim, flags, record_lines, match_line=-1, first_byte=-1,
+                          record_base=0, caps=None):
+        """zngamd_bgzf_grep_records: bgzf_grep on records of record_lines lines (match_line, first_byte: -1 for none) -> (code, block
+        statuses, totals (BgzfGrepRecordsTotals), rows, the records packed); nothing comes back when totals.bad is set"""
+        return self._bgzf_grep(self.L.zngamd_bgzf_grep_records, BgzfGrepRecordsTotals(), data, members, text_off, text_end, blob, table, delim, flags,
+                               (record_lines, match_line, first_byte, record_base), caps)
+
+    def _bgzf_grep(self, fn_c, tot, data, members, text_off, text_end, blob, table, delim, flags, extra, caps):
         nm = len(members)
         p, keep = _addr(data)
         table = np.ascontiguousarray(table, np.uint32)
         st = np.zeros(max(1, nm), np.int32)
-        tot = BgzfGrepTotals()
         box = []
 
         def alloc(_user, nbytes):
@@ -1286,11 +1314,10 @@ class Context:
             if not rcap:
                 rp = None
         bp, bkeep = _addr(blob)
-        r = self._chk(self.L.zngamd_bgzf_grep(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
-                                              text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table), delim, flags,
-                                              line_base, C.c_void_p(st.ctypes.data), rp, rcap, op, ocap, fn, None, C.byref(tot)),
-                      (OK, BUF_ERROR))
-        got = r == OK and tot.covered and tot.matched and not flags & BGZF_GREP_COUNT_ONLY
+        r = self._chk(fn_c(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm, text_off, text_end, bp, len(blob),
+                           C.c_void_p(table.ctypes.data), len(table), delim, flags, *extra, C.c_void_p(st.ctypes.data), rp, rcap, op, ocap, fn, None,
+                           C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and tot.covered and tot.matched and not flags & BGZF_GREP_COUNT_ONLY and not getattr(tot, "bad", 0)
         if caps is None:
             rows_out = box[0] if got else np.empty(0, GREP_ROW_DTYPE)
             packed = box[1] if got else b""
@@ -1309,6 +1336,19 @@ class Context:
         r = self._chk(self.L.zngamd_bgzf_grep_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob),
                                                   C.c_void_p(table.ctypes.data), len(table), delim, flags, line_base, v(d_scratch), scratch_cap,
                                                   v(d_status), v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def bgzf_grep_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, record_lines, match_line,
+                              first_byte, record_base, d_scratch, scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap):
+        """zngamd_bgzf_grep_records_dev on device pointers (the patterns: host memory) -> (code, totals); rows and records stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        table = np.ascontiguousarray(table, np.uint32)
+        tot = BgzfGrepRecordsTotals()
+        bp, bkeep = _addr(blob)
+        r = self._chk(self.L.zngamd_bgzf_grep_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob),
+                                                          C.c_void_p(table.ctypes.data), len(table), delim, flags, record_lines, match_line, first_byte,
+                                                          record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap, v(d_out), out_cap,
+                                                          C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_tabix(self, data, members, text_off, text_end, conf, delim, flags, line_base=0, caps=None):

@@ -24,6 +24,8 @@ offset inside that block's output -- what .bai, .tbi and .csi indexes store, and
     for number, voffset, line in zip(hits.numbers, hits.voffsets, hits):      # decoded; only the matching lines come back
         ...
     n = bgzf.grep("reads.fastq.gz", [b"ACGTTGCA", b"TGCAACGT"], count=True, start=cuts[2], stop=cuts[3])
+    reads = bgzf.grep_records("reads.fastq.gz", b"ACGTTGCA", 4, match_line=1, first_byte=b"@")      # records by content: the reads whose
+                                                                      # bases hold the barcode, all four lines of each, in the same one pass
 
     tbi = bgzf.TabixIndex.build("calls.vcf.gz", "vcf")                # lines by region: the fields of every line are read on the GPU, a
     tbi.save("calls.vcf.gz.tbi")                                      # standard .tbi comes out; fetch() plans on it, decodes the blocks
@@ -47,7 +49,7 @@ import numpy as np
 from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
-           "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "GrepResult",
+           "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
 BadGzipFile = zlib_ng.BadGzipFile
@@ -655,11 +657,37 @@ def _read_full(fp, mv):
     return got
 
 
-def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line):
+def _grep_record_args(record_lines, match_line, first_byte):
+    """-> (k, match_line or -1, first_byte or -1) as zngamd_bgzf_grep_records takes them; ValueError as grep_records() documents it"""
+    k = int(record_lines)
+    if not 1 <= k <= _lib.BGZF_GREP_MAX_RECORD_LINES:
+        raise ValueError(f"a record has 1 to {_lib.BGZF_GREP_MAX_RECORD_LINES} lines, not {k}")
+    j = -1 if match_line is None else int(match_line)
+    if match_line is not None and not 0 <= j < k:
+        raise ValueError(f"match_line lies between 0 and {k - 1}, not {j}")
+    if first_byte is None:
+        b = -1
+    elif isinstance(first_byte, (bytes, bytearray, memoryview)):
+        if len(bytes(first_byte)) != 1:
+            raise ValueError("first_byte is exactly one byte")
+        b = bytes(first_byte)[0]
+    else:
+        b = int(first_byte)
+        if not 0 <= b <= 255:
+            raise ValueError("first_byte lies between 0 and 255")
+    return k, j, b
+
+
+def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line, records=None):
+    """The window loop of grep() and, with records = (record_lines, match_line, first_byte, allow_short), of grep_records(): then the
+    unit that is counted, numbered, carried over a window's end and bounded by max_line is the record."""
     pats, delimiter = _grep_patterns(patterns, delimiter)
+    unit, bound = ("record", "max_record") if records is not None else ("line", "max_line")
+    if records is not None:
+        rec_k, rec_j, rec_b = _grep_record_args(*records[:3])
     max_line = int(max_line)
     if not 1 <= max_line <= 1 << 31:
-        raise ValueError("max_line lies between 1 and 2**31")
+        raise ValueError(f"{bound} lies between 1 and 2**31")
     if max_count is not None and int(max_count) < 0:
         raise ValueError("max_count is not negative")
     ctx = ctx or zlib_ng._ctx()                              # (the arguments are judged before a context is asked for)
@@ -700,26 +728,39 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
             if bad >= 0:
                 raise BadGzipFile(f"BGZF block {nblocks + bad} at offset {c_next + int(coffs[bad])}: bad block header or block size")
             cend = int(coffs[n_use - 1] + csizes[n_use - 1]) if n_use else 0
-            _, status, tot, rows, packed = ctx.bgzf_grep(data[:cend], members, text_off, text_end, blob, table, delimiter[0],
-                                                         flags | (_lib.BGZF_GREP_FINAL if final else 0), line_base)
+            wflags = flags | (_lib.BGZF_GREP_FINAL if final else 0)
+            if records is None:
+                _, status, tot, rows, packed = ctx.bgzf_grep(data[:cend], members, text_off, text_end, blob, table, delimiter[0], wflags, line_base)
+            else:
+                _, status, tot, rows, packed = ctx.bgzf_grep_records(data[:cend], members, text_off, text_end, blob, table, delimiter[0], wflags,
+                                                                     rec_k, rec_j, rec_b, line_base)
             bad = np.nonzero(status)[0]
             if len(bad):
                 raise _block_error(c_next + int(coffs[bad[0]]), status[bad[0]])
             if not tot.covered:
                 raise BadGzipFile(f"BGZF blocks at offset {c_next}: the decoded blocks do not cover the text")
+
+            def voffsets_of(src):                            # scratch offsets -> normalised virtual offsets
+                at = np.searchsorted(members["out_off"].astype(np.int64), src, "right") - 1
+                return (coffs[at] + c_next).astype(np.uint64) << np.uint64(16) | (src - members["out_off"][at].astype(np.int64)).astype(np.uint64)
+
+            if records is not None:
+                if tot.bad:
+                    v = int(voffsets_of(np.array([tot.bad_src], np.int64))[0])
+                    raise ValueError(f"record {tot.bad_record} at virtual offset {v} does not start with {bytes([rec_b])!r} (first_byte)")
+                if tot.short_lines and not records[3]:
+                    raise ValueError(f"record {line_base + tot.seen - 1}, the last one, has {tot.short_lines} of {rec_k} lines (allow_short)")
             searched, line_base, matched = searched + tot.seen, line_base + tot.seen, matched + tot.matched
             if len(rows):
-                src = rows["src_off"].astype(np.int64)
-                at = np.searchsorted(members["out_off"].astype(np.int64), src, "right") - 1
                 numbers.append(rows["number"].astype(np.int64))
-                voffsets.append((coffs[at] + c_next).astype(np.uint64) << np.uint64(16) | (src - members["out_off"][at].astype(np.int64)).astype(np.uint64))
+                voffsets.append(voffsets_of(rows["src_off"].astype(np.int64)))
                 lengths.append(rows["len"].astype(np.int64))
                 pieces.append(packed)
             try:
                 nxt = _grep_advance(isizes, n_use, text_off, text_end, int(tot.tail_off), final, window, max_line)
             except _LongLine as e:
                 v = make_virtual_offset(c_next + int(coffs[e.block]), e.offset)
-                raise ValueError(f"the line at virtual offset {v} has not ended after {max_line} bytes (max_line)") from None
+                raise ValueError(f"the {unit} at virtual offset {v} has not ended after {max_line} bytes ({bound})") from None
             if nxt is None:
                 break
             b, text_off, window = nxt
@@ -765,6 +806,32 @@ def grep(file, patterns, *, delimiter=b"\n", invert=False, line_start=False, cou
             return grep(f, patterns, delimiter=delimiter, invert=invert, line_start=line_start, count=count, max_count=max_count,
                         start=start, stop=stop, first_line=first_line, max_line=max_line)
     return _grep_file(file, None, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line)
+
+
+def grep_records(file, patterns, record_lines, *, match_line=None, first_byte=None, delimiter=b"\n", invert=False, line_start=False,
+                 count=False, max_count=None, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+    """grep() on records of `record_lines` (1 to 64) lines each -- FASTQ 4, two-line FASTA 2, interleaved pairs 8 -- in one pass: the
+    records of which one line contains one of `patterns` come back WHOLE, as `grep -B1 -A2` or `seqkit grep -s -p` give them.  The
+    file (or its part from `start`) begins with a record; record r is its lines [k r, k r + k).  -> a GrepResult whose numbers are
+    record numbers, whose voffsets point at each record's first byte, whose data holds the records packed, and whose searched
+    counts records.  patterns, delimiter, start, stop and the errors of the file are those of grep().
+      match_line    only this line of a record (0 .. record_lines - 1) is looked at: 1 for the bases of a FASTQ read
+      first_byte    every record starts with this byte (b"@"): ValueError naming the first record that does not and its virtual
+                    offset -- what a stray blank line or a multi-line FASTQ, which shift every record behind them, turn into
+      line_start    the pattern must stand at the first byte of the line       invert      the records without a match
+      count         -> int, the number of selected records                      max_count   at most the first N selected records
+      start, stop   virtual offsets of record starts: the cuts of LineIndex.shards(reader, n, lines_per_record=record_lines)
+      first_record  the number of the first record searched
+      max_record    ValueError (naming the record's virtual offset) for a record that is still open after this many bytes of a window
+      allow_short   the lines left over at the end (fewer than record_lines) are a last record; without it they are a ValueError
+                    that names the record and how many lines it has"""
+    if _is_path(file):
+        with _builtin_open(file, "rb") as f:
+            return grep_records(f, patterns, record_lines, match_line=match_line, first_byte=first_byte, delimiter=delimiter, invert=invert,
+                                line_start=line_start, count=count, max_count=max_count, start=start, stop=stop, first_record=first_record,
+                                max_record=max_record, allow_short=allow_short)
+    return _grep_file(file, None, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_record, max_record,
+                      (record_lines, match_line, first_byte, allow_short))
 
 
 # ---- lines by region (DESIGN.md section 5g): a tabix index built on the GPU, and the rows of a region filtered there
@@ -2220,6 +2287,20 @@ class BgzfReader(io.BufferedIOBase):
         try:
             return _grep_file(self._fp, self._ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line,
                               max_line)
+        finally:
+            self._fp.seek(at)
+
+    def grep_records(self, patterns, record_lines, *, match_line=None, first_byte=None, delimiter=b"\n", invert=False, line_start=False,
+                     count=False, max_count=None, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+        """bgzf.grep_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("grep_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _grep_file(self._fp, self._ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_record,
+                              max_record, (record_lines, match_line, first_byte, allow_short))
         finally:
             self._fp.seek(at)
 
