@@ -87,6 +87,25 @@ def test_stored_fixed_empty_and_tiny_units(ctx):
     assert zlib.decompressobj(-15).decompress(stream) == buf
     r, n, back = _decode(ctx, stream, [len(c) for c in outs], [b[1] for b in blocks], d_index)
     assert r == _lib.STREAM_END and back == buf
+    # units of their own that end one byte around a segment's end and a unit's, and one whose last segment is 7 bytes that begin
+    # with literals (2 KiB pieces: 300 bytes drawn from 16 values, then text): a refused index would come back as E_INDEX
+    from zlib_ng_amd import corpus
+    text = corpus.text(B, seed=9).tobytes()
+    vals = rng.integers(0, 256, 16, dtype=np.uint8)
+    edge = b"".join(vals[rng.integers(0, 16, 300)].tobytes() + text[i * 1748:(i + 1) * 1748] for i in range(60))[:59 * 2048 + 7]
+    assert len(edge) % 16 == 7
+    for data in [text[:k] for k in (2047, 2048, 2049, 4097, 131071, 131072)] + [edge]:
+        stream, uin, uout, d_index = _compress_indexed(ctx, data, 6)
+        assert zlib.decompressobj(-15).decompress(stream) == data
+        r, n, back = _decode(ctx, stream, uin, uout, d_index)
+        assert r == _lib.STREAM_END and n == len(data) and back == data, len(data)
+    # a dictionary of exactly 32 768 bytes whose first bytes open the first unit: a match that reaches back all of the history
+    d = _mix(32768, 13)
+    data = d[:300] + text[:5000]
+    stream, uin, uout, d_index = _compress_indexed(ctx, data, 6, dict_first=d)
+    assert zlib.decompressobj(-15, zdict=d).decompress(stream) == data
+    r, n, back = _decode(ctx, stream, uin, uout, d_index, dict_first=d)
+    assert r == _lib.STREAM_END and n == len(data) and back == data
 
 
 def test_dictionary_in_front_of_the_stream(ctx):

@@ -112,6 +112,18 @@ def test_indexed_members_round_trip(ctx, fastq, level):
     ctx.decode_paths(True)
     code, out, nm = ctx.gunzip(stream, len(mix))
     assert code == 0 and out == mix and ctx.decode_paths(True)["indexed"] == nm == 3
+    # the edges of what the member decoder shares with the unit decoder: members that end one byte around a segment's end and
+    # a member's, and a last segment of 7 bytes that begins with literals -- its open block of literals ends less than 16 bytes
+    # before the end of the output and must leave byte by byte (2 KiB pieces: 300 bytes drawn from 16 values, then text)
+    vals = rng.integers(0, 256, 16, dtype=np.uint8)
+    edge = b"".join(vals[rng.integers(0, 16, 300)].tobytes() + fastq[i * 1748:(i + 1) * 1748] for i in range(70))[:69 * 2048 + 7]
+    assert len(edge) % 16 == 7
+    for data in [fastq[:n] for n in (2047, 2048, 2049, 4097, 131071, 131072)] + [edge]:
+        stream = ctx.gzip_members(data, 131072, level)
+        ctx.decode_paths(True)
+        code, out, nm = ctx.gunzip(stream, len(data))
+        assert code == 0 and out == data and nm == -(-len(data) // 131072)
+        assert ctx.decode_paths(True)["indexed"] == nm, len(data)
     # corrupt one payload byte of an indexed stream: CRC / data error must surface
     stream = bytearray(ctx.gzip_members(fastq[:400000], 131072, level))
     stream[5000] ^= 0x10
