@@ -4,7 +4,12 @@
  * state machine GzipReader_read_into_buffer (zlib_ngmodule.c:2426-2637).
  * Decoder: canonical-Huffman decode with a 10-bit lookup table and a bit-serial slow path for
  * longer codes.  Error rules follow the published zlib behaviour the reference's tests rely on
- * (over-subscribed / incomplete sets, missing end-of-block, distance too far back, ...). */
+ * (over-subscribed / incomplete sets, missing end-of-block, distance too far back, ...).
+ * Invalid code against out of input: the referee is zlib fed the whole input in one call.  Bits that match no code of a set are
+ * a data error as soon as as many bits are present as the set's longest code has (one bit for a set of one code or of none: its
+ * unused code is one bit long), and "out of input" only when fewer are.  The fixed distance code has all 32 five-bit codes, the
+ * fixed literal/length code all 288: the symbols no stream may use (30, 31; 286, 287) are decoded like any other and then refused,
+ * so they too are a data error once their own bits are there -- never a walk to 15 bits that runs off the end of the input. */
 #include "oracle.h"
 #include <string.h>
 
@@ -68,7 +73,7 @@ static int build(hufftab *h, const uint8_t *lens, int n)
     return left;
 }
 
-/* decode one symbol; -1 = invalid code / out of input */
+/* decode one symbol; -1 = invalid code (no code of the set's longest length matches) / out of input (overrun set) */
 static inline int decode(bitrd *b, const hufftab *h)
 {
     if (b->bitcnt < 15) refill(b);
@@ -82,7 +87,8 @@ static inline int decode(bitrd *b, const hufftab *h)
     /* slow path: bit-serial canonical decode */
     int code = 0, first = 0, index = 0;
     uint64_t bb = b->bitbuf;
-    for (int l = 1; l <= 15; l++) {
+    const int maxlen = h->maxlen > 0 ? h->maxlen : 1;
+    for (int l = 1; l <= maxlen; l++) {
         if (l > b->bitcnt) { b->overrun = 1; return -1; }
         code |= (int)(bb & 1); bb >>= 1;
         int count = h->count[l];
@@ -118,8 +124,8 @@ int za_o_inflate_raw(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_
         for (; i < 280; i++) l[i] = 7;
         for (; i < 288; i++) l[i] = 8;
         build(&fixl, l, 288);
-        for (i = 0; i < 30; i++) l[i] = 5;
-        build(&fixd, l, 30);
+        for (i = 0; i < 32; i++) l[i] = 5;
+        build(&fixd, l, 32);
         fixed_ready = 1;
     }
     for (;;) {
@@ -187,6 +193,7 @@ int za_o_inflate_raw(const uint8_t *in, size_t in_len, uint8_t *out, size_t out_
                     sym -= 257;
                     if (sym >= 29) { ret = ZA_DATA_ERROR; goto done; }
                     uint32_t len = len_base[sym] + getbits(&b, len_extra[sym]);
+                    if (b.overrun) { ret = ZA_BUF_ERROR; goto done; }
                     int ds = decode(&b, hd);
                     if (ds < 0) { ret = b.overrun ? ZA_BUF_ERROR : ZA_DATA_ERROR; goto done; }
                     if (ds >= 30) { ret = ZA_DATA_ERROR; goto done; }

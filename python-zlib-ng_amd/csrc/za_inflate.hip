@@ -241,9 +241,11 @@ __device__ int za_read_tables(const uint8_t *in, uint64_t in_bits, uint64_t &bit
     if (type == 1) {
         za_wave_sync();
         for (int i = lane; i < 320; i += 64)
-            T.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : i < 318 ? 5 : 0);
+            T.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5);
+        // (all 32 distance codes, like all 288 literal/length codes: 30 and 31 are decoded and then refused -- with 30 symbols their
+        // five bits matched no code, and "no code" within 15 bits of the end of the input was taken for the end of the input)
         za_build_table(T.lens, 288, T.cnt_l, T.sym_l, T.lut_l, TT::kLBits, &scratch[0], &scratch[1], T.fst_l, T.idx_l);
-        za_build_table(T.lens + 288, 30, T.cnt_d, T.sym_d, T.lut_d, TT::kDBits, &scratch[0], &scratch[1], T.fst_d, T.idx_d);
+        za_build_table(T.lens + 288, 32, T.cnt_d, T.sym_d, T.lut_d, TT::kDBits, &scratch[0], &scratch[1], T.fst_d, T.idx_d);
         return ZA_I_OK;
     }
     if (bitpos + 14 > in_bits) return ZA_I_INPUT;
@@ -1237,7 +1239,10 @@ __device__ int za_inflate_serial_core(const uint8_t *__restrict__ in, uint64_t i
                     if (o > 64u - 15u) break;                                        // next code may be cut: new window
                     uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)eL, (int)o);
                     if (!e) e = za_long_decode((uint32_t)(W >> o), T.cnt_l, T.fst_l, T.idx_l, T.sym_l, TT::kLBits + 1);         // o <= 49: 15 bits are there
-                    if (!e) { status = (bitpos + o + 15 > in_bits) ? ZA_I_INPUT : ZA_I_DATA; break; }
+                    // bits that match no code: only a set of one code (or of none) has such, and its unused code is ONE bit long
+                    // (za_read_tables refuses every other incomplete set: `st > 0 && maxl != 1`; the fixed tables are complete) --
+                    // a data error as soon as that bit is there (zlib's verdict), "out of input" only at the very end
+                    if (!e) { status = (bitpos + o + 1 > in_bits) ? ZA_I_INPUT : ZA_I_DATA; break; }
                     int sym = (int)(e >> 4);
                     const uint32_t l = e & 15u;
                     if (bitpos + o + l > in_bits) { status = ZA_I_INPUT; break; }
@@ -1257,7 +1262,8 @@ __device__ int za_inflate_serial_core(const uint8_t *__restrict__ in, uint64_t i
                     if (nx) len += (int)((W >> (o + l)) & ((1u << nx) - 1u));       // o + l < 64 here
                     uint32_t e2 = (uint32_t)__builtin_amdgcn_readlane((int)eD, (int)o2);
                     if (!e2) e2 = za_long_decode((uint32_t)(W >> o2), T.cnt_d, T.fst_d, T.idx_d, T.sym_d, TT::kDBits + 1);
-                    if (!e2) { status = (bitpos + o2 + 15 > in_bits) ? ZA_I_INPUT : ZA_I_DATA; break; }
+                    if (!e2) { status = (bitpos + o2 + 1 > in_bits) ? ZA_I_INPUT : ZA_I_DATA; break; }       // (one bit: as above, by za_read_tables)
+                    if (bitpos + o2 + (e2 & 15u) > in_bits) { status = ZA_I_INPUT; break; }     // (a code read from what lies behind the input is no verdict on the stream)
                     const int ds = (int)(e2 >> 4);
                     if (ds >= 30) { status = ZA_I_DATA; break; }
                     int dnx;

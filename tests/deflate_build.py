@@ -1,0 +1,548 @@
+"""A small DEFLATE (RFC 1951) stream BUILDER for the inflate tests: streams are written bit by bit from an explicit description, so a
+test can feed the decoders what no ordinary encoder writes -- 15-bit codes, one-code and empty distance sets, length 258 spelled as
+code 284 + 31, references that reach exactly the first byte of the history, hundreds of tiny blocks -- and headers that are INVALID
+for one chosen reason.  The builder computes the plaintext itself, by replaying its own tokens over zdict + output; it never asks a
+decoder.  tests/test_cpu_handbuilt_streams.py proves every vector against the system zlib (the referee) before any GPU test uses it.
+Holds no test and no GPU code.  Not a conftest: imported by the test files that use it, like deflate_walk.
+
+A stream is a list of blocks: Stored, Fixed or Dynamic.  A block of the two compressed kinds carries a token list:
+    an int 0..255               a literal
+    M(length, dist[, code])     a match; `code` chooses the spelling of the length (258 is code 285, or code 284 with extra bits 31)
+    Sym(s) / DSym(s)            the literal/length (distance) code of symbol s, nothing else: for defects such as symbol 286
+    Code(code, nbits)           a raw Huffman code, first bit first (the unused code of a one-code set)
+    Raw(value, nbits)           raw bits, least significant first
+assemble() sets BFINAL on the last block, or on none: any vector's blocks can also be embedded in a longer stream."""
+from collections import namedtuple
+
+LBASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+LEXT = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
+DBASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
+         8193, 12289, 16385, 24577]
+DEXT = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
+CLORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
+FIXED_L = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8       # all 288: the fixed code has codes for 286 and 287, which no stream may use
+FIXED_D = [5] * 32                                         # likewise 30 and 31
+
+DATA = "DATA"         # `expect` of a stream that zlib must refuse with a data error
+
+M = namedtuple("M", "length dist code", defaults=(None,))
+Sym = namedtuple("Sym", "sym")
+DSym = namedtuple("DSym", "sym")
+Code = namedtuple("Code", "code nbits")
+Raw = namedtuple("Raw", "value nbits")
+
+
+class BitWriter:
+    """Fields least significant bit first, Huffman codes most significant bit first, both packed from bit 0 of each byte."""
+
+    def __init__(self):
+        self.buf, self.acc, self.n = bytearray(), 0, 0
+
+    def bits(self, value, nbits):
+        assert 0 <= value < (1 << nbits) or nbits == 0
+        self.acc |= value << self.n
+        self.n += nbits
+        while self.n >= 8:
+            self.buf.append(self.acc & 0xFF)
+            self.acc >>= 8
+            self.n -= 8
+
+    def code(self, code, nbits):
+        self.bits(int(format(code & ((1 << nbits) - 1), "0%db" % nbits)[::-1], 2) if nbits else 0, nbits)
+
+    def align(self):
+        if self.n:
+            self.bits(0, 8 - self.n)
+
+    def raw_bytes(self, data):
+        assert self.n == 0
+        self.buf += data
+
+    @property
+    def bitlen(self):
+        return 8 * len(self.buf) + self.n
+
+    def getvalue(self):
+        return bytes(self.buf) + (bytes([self.acc]) if self.n else b"")
+
+
+def canonical(lengths):
+    """Canonical Huffman codes of a length list -> [(code, nbits) or None per symbol].  An over-subscribed list gives codes that do
+    not fit their length; they are cut to it (such a header is refused before any code is read)."""
+    mx = max(lengths) if lengths else 0
+    count = [0] * (mx + 2)
+    for ln in lengths:
+        count[ln] += 1
+    count[0] = 0
+    code, nxt = 0, [0] * (mx + 2)
+    for b in range(1, mx + 1):
+        code = (code + count[b - 1]) << 1
+        nxt[b] = code
+    out = []
+    for ln in lengths:
+        if ln:
+            out.append((nxt[ln], ln))
+            nxt[ln] += 1
+        else:
+            out.append(None)
+    return out
+
+
+def kraft(lengths):
+    """Sum of 2^-len over the coded symbols, as a fraction of 2^15: 32768 = complete."""
+    return sum(1 << (15 - ln) for ln in lengths if ln)
+
+
+def complete_lengths(k):
+    """Lengths of a complete code of k >= 2 symbols, as flat as possible, shortest first."""
+    assert k >= 2
+    top = (k - 1).bit_length()
+    short = (1 << top) - k
+    return [top - 1] * short + [top] * (k - short)
+
+
+def length_code(length, code=None):
+    """-> (symbol, extra value, extra bits) of a match length; code = force this length code (257..285)"""
+    if code is None:
+        code = 285 if length == 258 else 257 + max(i for i in range(28) if LBASE[i] <= length)
+    i = code - 257
+    extra = length - LBASE[i]
+    assert 0 <= extra < (1 << LEXT[i]) or (extra == 0 and LEXT[i] == 0), (length, code)
+    return code, extra, LEXT[i]
+
+
+def dist_code(dist):
+    i = max(i for i in range(30) if DBASE[i] <= dist)
+    return i, dist - DBASE[i], DEXT[i]
+
+
+class Stored:
+    btype = 0
+
+    def __init__(self, data, nlen=None):
+        self.data, self.nlen = bytes(data), nlen         # nlen: the one's complement field as written (a defect), or None
+
+    def write(self, w, final):
+        w.bits(1 if final else 0, 1)
+        w.bits(0, 2)
+        w.align()
+        w.bits(len(self.data), 16)
+        w.bits(len(self.data) ^ 0xFFFF if self.nlen is None else self.nlen, 16)
+        w.raw_bytes(self.data)
+
+
+class _Coded:
+    def __init__(self, tokens, eob=True):
+        self.tokens, self.eob = list(tokens), eob
+
+    def _codes(self):
+        raise NotImplementedError
+
+    def _write_tokens(self, w):
+        lc, dc = self._codes()
+        for t in self.tokens + ([Sym(256)] if self.eob else []):
+            if isinstance(t, int):
+                w.code(*lc[t])
+            elif isinstance(t, M):
+                s, ev, eb = length_code(t.length, t.code)
+                w.code(*lc[s])
+                w.bits(ev, eb)
+                d, dv, db = dist_code(t.dist)
+                w.code(*dc[d])
+                w.bits(dv, db)
+            elif isinstance(t, Sym):
+                w.code(*lc[t.sym])
+            elif isinstance(t, DSym):
+                w.code(*dc[t.sym])
+            elif isinstance(t, Code):
+                w.code(t.code, t.nbits)
+            elif isinstance(t, Raw):
+                w.bits(t.value, t.nbits)
+            else:
+                raise TypeError(t)
+
+
+class Fixed(_Coded):
+    btype = 1
+
+    def _codes(self):
+        return canonical(FIXED_L), canonical(FIXED_D)
+
+    def write(self, w, final):
+        w.bits(1 if final else 0, 1)
+        w.bits(1, 2)
+        self._write_tokens(w)
+
+
+def rle_lengths(lens):
+    """The code-length sequence of a length list with the repeat codes, greedily: [(symbol, extra value)]"""
+    out, i = [], 0
+    while i < len(lens):
+        v, j = lens[i], i
+        while j < len(lens) and lens[j] == v:
+            j += 1
+        run = j - i
+        if v == 0 and run >= 3:
+            r = min(run, 138)
+            out.append((18, r - 11) if r >= 11 else (17, r - 3))
+            i += r
+        elif v and run >= 4:
+            out.append((v, 0))
+            r = min(run - 1, 6)
+            out.append((16, r - 3))
+            i += 1 + r
+        else:
+            out.append((v, 0))
+            i += 1
+    return out
+
+
+class Dynamic(_Coded):
+    """ll / d: the literal/length and the distance code lengths (HLIT + 257 and HDIST + 1 of them).  Everything else has a default
+    and can be forced: hlit / hdist / hclen = the header fields as written; clseq = the code-length sequence [(symbol, extra)], by
+    default the lengths one by one (rle=False) or with repeat codes (rle=True); cl = the 19 lengths of the code-length code, by
+    default a complete code over the symbols of clseq.  eob=False: no end-of-block code behind the tokens."""
+    btype = 2
+
+    def __init__(self, ll, d, tokens=(), eob=True, rle=False, clseq=None, cl=None, hlit=None, hdist=None, hclen=None):
+        _Coded.__init__(self, tokens, eob)
+        self.ll, self.d = list(ll), list(d)
+        self.clseq = list(clseq) if clseq is not None else (rle_lengths(self.ll + self.d) if rle else [(v, 0) for v in self.ll + self.d])
+        if cl is None:
+            used = sorted({s for s, _ in self.clseq})
+            if len(used) == 1:
+                used = sorted(used + [0 if used[0] else 8])        # (a one-code code-length code is refused: a second, unused code)
+            cl = [0] * 19
+            for s, ln in zip(used, complete_lengths(len(used))):
+                cl[s] = ln
+        self.cl = list(cl)
+        self.hlit = len(self.ll) - 257 if hlit is None else hlit
+        self.hdist = len(self.d) - 1 if hdist is None else hdist
+        if hclen is None:
+            hclen = max([4] + [i + 1 for i, s in enumerate(CLORDER) if self.cl[s]])
+        self.hclen = hclen
+
+    def _codes(self):
+        return canonical(self.ll), canonical(self.d)
+
+    def write(self, w, final):
+        w.bits(1 if final else 0, 1)
+        w.bits(2, 2)
+        w.bits(self.hlit, 5)
+        w.bits(self.hdist, 5)
+        w.bits(self.hclen - 4, 4)
+        for s in CLORDER[:self.hclen]:
+            w.bits(self.cl[s], 3)
+        cc = canonical(self.cl)
+        for s, ev in self.clseq:
+            w.code(*cc[s])
+            w.bits(ev, {16: 2, 17: 3, 18: 7}.get(s, 0))
+        self._write_tokens(w)
+
+
+class RawBlock:
+    """A block given as bare bits behind BFINAL: (value, nbits) pairs.  For headers that no class above can spell (BTYPE 3)."""
+    btype = None
+
+    def __init__(self, fields):
+        self.fields = list(fields)
+
+    def write(self, w, final):
+        w.bits(1 if final else 0, 1)
+        for v, n in self.fields:
+            w.bits(v, n)
+
+
+def assemble(blocks, final=True, writer=None):
+    """The stream of `blocks`; final: BFINAL on the last one.  With a writer, the blocks are appended to it (at any bit position)."""
+    w = writer or BitWriter()
+    for i, b in enumerate(blocks):
+        b.write(w, final and i == len(blocks) - 1)
+    return w if writer else w.getvalue()
+
+
+def end_bit(blocks, final=True):
+    w = BitWriter()
+    assemble(blocks, final, w)
+    return w.bitlen
+
+
+def replay(blocks, zdict=b""):
+    """The plaintext of VALID blocks, from the tokens alone, and the matches [(length, distance)] in order."""
+    out = bytearray(zdict)
+    matches = []
+    for b in blocks:
+        if isinstance(b, Stored):
+            out += b.data
+            continue
+        for t in b.tokens:
+            if isinstance(t, int):
+                out.append(t)
+            elif isinstance(t, M):
+                assert 3 <= t.length <= 258 and 1 <= t.dist <= min(32768, len(out)), (t, len(out))
+                matches.append((t.length, t.dist))
+                for _ in range(t.length):
+                    out.append(out[-t.dist])
+            else:
+                raise ValueError("replay of a defect token: %r" % (t,))
+    return bytes(out[len(zdict):]), matches
+
+
+Vector = namedtuple("Vector", "name blob zdict expect blocks")
+
+
+def _vec(name, blocks, zdict=b"", invalid=False):
+    return Vector(name, assemble(blocks), zdict, DATA if invalid else replay(blocks, zdict)[0], blocks)
+
+
+def is_valid(v):
+    return v.expect is not DATA
+
+
+def spread(symbols, lengths, n):
+    """A length list of n entries in which symbols[i] has lengths[i]"""
+    out = [0] * n
+    for s, ln in zip(symbols, lengths):
+        out[s] = ln
+    return out
+
+
+SKEW = list(range(1, 16)) + [15]                      # sixteen codes, complete: 1/2 + 1/4 + ... + 2^-15 + 2^-15
+_SKEW_SYMS = [97, 256, 285, 98, 99, 100, 101, 284, 102, 103, 104, 105, 106, 257, 107, 108]         # 107 and 108 get the 15-bit codes
+
+
+def _pattern(n, seed):
+    """n bytes that no deflate-style shortcut produces: a 32-bit multiplicative generator (no match of three bytes worth taking)"""
+    out, x = bytearray(), seed * 2654435761 % (1 << 32) or 1
+    for _ in range(n):
+        x = (x * 1664525 + 1013904223) % (1 << 32)
+        out.append(x >> 24)
+    return bytes(out)
+
+
+def valid_vectors():
+    v = []
+    skew_ll = spread(_SKEW_SYMS, SKEW, 286)
+    text = [97, 98, 107, 108, 99, 106]
+    # 15-bit literal codes, a 258-match at distance 1 (code 285, 3 bits) and a one-code distance set (one code of one bit: incomplete)
+    v.append(_vec("skew_ll_onecode_dist", [Dynamic(skew_ll, [1], text + [M(258, 1), 108, 107, M(3, 1), M(258, 1, 284), 105])]))
+    # ... the same with sixteen distance codes of 1..15,15 bits: distances 1 and 2 have the 15-bit codes, 24577.. the one-bit code
+    skew_d = SKEW[::-1] + [0] * 13 + [1]
+    skew_d[15] = 0                                                                    # (code 29 takes the one-bit code instead of code 15)
+    v.append(_vec("skew_ll_skew_dist", [Dynamic(skew_ll, skew_d, text + [M(258, 1), 108, M(3, 2), M(258, 2, 284), M(3, 3), M(240, 8), 107, M(3, 1)])]))
+    # codes one bit longer than each first-level table, and two bits: literal codes of 10 and 11 bits (tables of 9 and 10 index bits),
+    # distance codes of 9 and 10 bits (tables of 8 and 9) -- every code of the block is used
+    ll = spread([97, 98, 99, 256, 257, 100, 101, 102, 103, 104, 105, 106], list(range(1, 11)) + [11, 11], 258)
+    d = spread([0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10], list(range(1, 9)) + [9, 10, 10], 11)
+    toks = [97, 98, 99, 100, 101, 102, 103, 104, 105, 106] + [M(3, dd) for dd in (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33)] + [104, 105, 106, M(3, 46), 103]
+    v.append(_vec("one_bit_past_the_tables", [Dynamic(ll, d, toks)]))
+    # ... and with the long codes in bulk: 286 codes of 8..10 bits, 30 distance codes of 4 and 5 bits (nlen = 286, ndist = 30)
+    ll = [8] * 240 + [9] * 18 + [10] * 28                                             # 960 + 36 + 28 = 1024 / 1024: complete
+    assert kraft(ll) == 32768 and len(ll) == 286
+    d30 = [4, 4] + [5] * 28
+    toks = list(range(230, 256)) + [M(3 + i, 1 + i) for i in range(20)] + [M(258, 26), M(257, 25), M(130, 24), 255, 240]
+    v.append(_vec("nlen286_ndist30", [Dynamic(ll, d30, toks, rle=True)]))
+    # no distance code at all (HDIST = 1, its one length 0): literals only
+    ll = spread([104, 105, 256], [1, 2, 2], 257)
+    v.append(_vec("no_distance_code", [Dynamic(ll, [0], [104, 105, 104, 104, 105], rle=True)]))
+    # two blocks that hold an end-of-block and nothing else, their code one code of one bit
+    eob_only = spread([256], [1], 257)
+    v.append(_vec("two_eob_only_blocks", [Dynamic(eob_only, [0], rle=True), Dynamic(eob_only, [0], rle=True)]))
+    # HCLEN: 5 is the smallest a valid header can have (with 4, only 16, 17, 18 and 0 have codes: every length is 0, no end-of-block;
+    # that header is among the invalid vectors); 19 = symbol 15 is used
+    ll = [8] * 255 + [0, 8]                                                           # 256 codes of 8 bits; nlen = 257
+    b = Dynamic(ll, [0], [1, 2, 3, 254, 0], clseq=[(8, 0)] * 255 + [(0, 0), (8, 0), (0, 0)])
+    assert b.hclen == 5
+    v.append(_vec("hclen5", [b]))
+    b = Dynamic(skew_ll, [1], [97, M(3, 1), 108], rle=True)
+    assert b.hclen == 19
+    v.append(_vec("hclen19", [b]))
+    # a code-length 16 whose run starts at the last literal/length entry's value and ends in the distance entries; an 18 with 138 zeros
+    ll = spread([97, 98, 256, 257], [1, 3, 3, 2], 258)
+    seq = [(18, 97 - 11), (1, 0), (3, 0), (18, 138 - 11), (18, 19 - 11), (3, 0), (2, 0), (16, 4 - 3)]
+    v.append(_vec("repeat_across_the_sets", [Dynamic(ll, [2, 2, 2, 2], [97, 98, M(3, 2), M(3, 4), M(3, 1), M(3, 3)], clseq=seq)]))
+    ll = spread([0, 139, 256], [1, 2, 2], 257)
+    seq = [(1, 0), (18, 127), (2, 0), (18, 116 - 11), (2, 0), (0, 0)]
+    v.append(_vec("zeros_138", [Dynamic(ll, [0], [0, 139, 139, 0], clseq=seq)]))
+    # ndist = 1, its one code used (nlen = 257 has no length code: the vectors above without a distance code have it)
+    v.append(_vec("nlen258_ndist1", [Dynamic(spread([120, 256, 257], [1, 2, 2], 258), [1], [120, M(3, 1), 120])]))
+    # length 258 both ways, in the fixed code; every length code with its extra bits all ones
+    v.append(_vec("len258_both_spellings", [Fixed([7, M(258, 1), M(258, 1, 284), 8, M(258, 259), M(258, 2, 284)])]))
+    toks = [65, 66, 67]
+    for i in range(29):
+        toks += [M(LBASE[i] + (1 << LEXT[i]) - 1, 1 + i % 3, 257 + i), 48 + i]
+    v.append(_vec("length_codes_extra_all_ones", [Fixed(toks)]))
+    v.append(_vec("length_codes_extra_all_ones_dynamic", [Dynamic([9] * 60 + [8] * 226, [4, 4] + [5] * 28, toks, rle=True)]))
+    # distance 32768 with exactly 32768 bytes produced (code 29, its 13 extra bits all ones), then 24577 (extra bits 0)
+    hist = _pattern(32768, 1)
+    v.append(_vec("dist32768_at_32768", [Stored(hist), Fixed([M(258, 32768), M(3, 24577), M(4, 32768)])]))
+    # a distance that reaches exactly the first byte of the dictionary: zdict of 1 byte and of 32768 bytes
+    v.append(_vec("reach_start_zdict1", [Fixed([M(4, 1), 9, M(3, 6)])], zdict=b"\x5a"))
+    big = _pattern(32768, 2)
+    v.append(_vec("reach_start_zdict32768", [Fixed([M(258, 32768), M(3, 32768)])], zdict=big))
+    v.append(_vec("reach_start_zdict100", [Fixed([200, 201, M(9, 102), M(3, 111)])], zdict=_pattern(100, 3)))
+    # the fixed code's 9-bit literals 144..255, and distance code 29 with 13 extra bits (into a dictionary, to keep the vector small)
+    v.append(_vec("fixed_9bit_literals_dist29", [Fixed(list(range(144, 256)) + [M(7, 24577 + 112), M(200, 32768), M(3, 30000)])], zdict=big))
+    # a stored block of length 0 between two compressed blocks that end off a byte boundary
+    b1, b2 = Fixed([1, 2, 3]), Dynamic(spread([50, 51, 256, 258], [1, 2, 3, 3], 259), [1], [50, 51, M(4, 1)], rle=True)
+    assert end_bit([b1], False) % 8 and end_bit([b1, Stored(b""), b2]) % 8
+    v.append(_vec("empty_stored_between", [b1, Stored(b""), b2]))
+    v.append(_vec("stored_65535", [Stored(_pattern(65535, 4))]))
+    v.append(_vec("stored_then_match", [Stored(b"abcdefgh"), Fixed([M(8, 8), M(3, 16)]), Stored(b"xyz"), Fixed([M(5, 3)])]))
+    # final blocks that end on each of the eight bit positions of the last byte (a 9-bit literal moves the end by one bit)
+    ends = set()
+    for k in range(8):
+        b = Fixed([33] + [200] * k)
+        ends.add(end_bit([b]) % 8)
+        v.append(_vec("ends_on_bit_%d" % (end_bit([b]) % 8), [b]))
+    assert len(ends) == 8
+    # 1500 blocks of one byte each: fixed, dynamic with a 15-bit code for the byte, stored, in turn; then an empty final block
+    blocks = []
+    for i in range(1500):
+        c = 32 + i % 90
+        if i % 3 == 0:
+            blocks.append(Fixed([c]))
+        elif i % 3 == 1:
+            syms = [256] + [s for s in range(1, 17) if s != c][:14] + [c]
+            blocks.append(Dynamic(spread(syms, SKEW, 257), [0], [c], rle=True))
+        else:
+            blocks.append(Stored(bytes([c])))
+    blocks.append(Fixed([]))
+    v.append(_vec("blocks_1500", blocks))
+    return v
+
+
+def invalid_vectors():
+    """(vector, the phrase of zlib's message) -- every stream is invalid for exactly the reason its name gives"""
+    v = []
+    tail = [Raw(0x5A5A5A5A, 32)] * 4                   # bits behind a defect, so that it is not the end of the input that is met
+
+    def add(name, blocks, phrase, zdict=b""):
+        v.append((_vec(name, blocks, zdict, invalid=True), phrase))
+
+    ok_ll = spread([97, 98, 256], [1, 2, 2], 257)
+    add("block_type_3", [Fixed([1, 2]), RawBlock([(3, 2), (0x1234, 16)])], "invalid block type")
+    add("stored_len_nlen_mismatch", [Stored(b"hello", nlen=0xFFFA ^ 1)], "invalid stored block lengths")
+    for hlit in (30, 31):
+        add("hlit_%d" % (hlit + 257), [Dynamic(ok_ll + [0] * 29, [1], hlit=hlit, eob=False, tokens=[97] + tail)], "too many length or distance symbols")
+    for hdist in (30, 31):
+        add("hdist_%d" % (hdist + 1), [Dynamic(ok_ll, [5] * 30, hdist=hdist, eob=False, tokens=[97] + tail)], "too many length or distance symbols")
+    cl = [0] * 19
+    cl[0], cl[1], cl[2] = 2, 2, 2                                                     # three codes of two bits: one missing
+    add("incomplete_code_length_code", [Dynamic(ok_ll, [1], cl=cl, eob=False, tokens=tail)], "invalid code lengths set")
+    cl = [0] * 19
+    cl[0], cl[1], cl[2] = 1, 1, 1
+    add("oversubscribed_code_length_code", [Dynamic(ok_ll, [1], cl=cl, eob=False, tokens=tail)], "invalid code lengths set")
+    add("hclen4_all_lengths_zero", [Dynamic([0] * 257, [0], clseq=[(18, 127), (18, 120 - 11)], cl=spread([18, 0], [1, 1], 19), hclen=4, eob=False, tokens=tail)],
+        "missing end-of-block")
+    add("oversubscribed_literal_set", [Dynamic(spread([97, 98, 99, 256], [1, 2, 2, 2], 257), [1], eob=False, tokens=tail)], "invalid literal/lengths set")
+    add("incomplete_literal_set", [Dynamic(spread([97, 256], [2, 2], 257), [1], eob=False, tokens=tail)], "invalid literal/lengths set")
+    add("incomplete_distance_set", [Dynamic(ok_ll, [2, 2], eob=False, tokens=tail)], "invalid distances set")
+    add("incomplete_distance_set_3", [Dynamic(ok_ll, [1, 2, 3], eob=False, tokens=tail)], "invalid distances set")
+    add("oversubscribed_distance_set", [Dynamic(ok_ll, [1, 1, 1], eob=False, tokens=tail)], "invalid distances set")
+    add("no_end_of_block_code", [Dynamic(spread([97, 98, 99], [1, 2, 2], 257), [1], eob=False, tokens=[97] + tail)], "missing end-of-block")
+    add("repeat_as_first_length", [Dynamic(ok_ll, [1], clseq=[(16, 0), (1, 0), (2, 0)], cl=spread([16, 1, 2, 0], [2, 2, 2, 2], 19), eob=False, tokens=tail)],
+        "invalid bit length repeat")
+    seq = [(18, 86), (1, 0), (2, 0), (18, 127), (18, 8), (2, 0), (17, 0)]             # 257 lengths, then three zeros where one entry is left
+    add("repeat_overruns_the_lengths", [Dynamic(ok_ll, [1], clseq=seq, eob=False, tokens=tail)], "invalid bit length repeat")
+    seq = [(18, 86), (1, 0), (2, 0), (18, 127), (18, 8), (2, 0), (16, 0)]             # a 16 of three where one entry is left
+    add("repeat_16_overruns_the_lengths", [Dynamic(ok_ll, [1], clseq=seq, eob=False, tokens=tail)], "invalid bit length repeat")
+    for s in (286, 287):
+        add("fixed_symbol_%d" % s, [Fixed([1, Sym(s)] + tail, eob=False)], "invalid literal/length code")
+    for s in (30, 31):
+        add("fixed_distance_code_%d" % s, [Fixed([1, Sym(257), DSym(s)] + tail, eob=False)], "invalid distance code")
+        # ... as the last bits of the input: `literal, length 257, distance code 30, end-of-block` and nothing behind
+        add("fixed_distance_code_%d_at_the_end" % s, [Fixed([1, Sym(257), DSym(s)])], "invalid distance code")
+    # (the same with exactly the five bits of the code present and not one more: 3 + 8 + 8 + 8 + 8 + 7 + 5 + 1 bits = six bytes)
+    b = Fixed([1, 2, 3, 4, Sym(257), DSym(30), Raw(0, 1)], eob=False)
+    assert end_bit([b]) == 48
+    add("fixed_distance_code_30_five_bits_left", [b], "invalid distance code")
+    one = spread([97, 256, 257], [1, 2, 2], 258)
+    add("unused_code_of_one_code_distance_set", [Dynamic(one, [1], [97, Sym(257), Code(1, 1)] + tail, eob=False)], "invalid distance code")
+    add("unused_code_of_one_code_distance_set_at_the_end", [Dynamic(one, [1], [97, Sym(257), Code(1, 1)], eob=False)], "invalid distance code")
+    add("length_code_without_distance_codes", [Dynamic(one, [0], [97, Sym(257)] + tail, eob=False)], "invalid distance code")
+    add("distance_beyond_start", [Fixed([1, 2, 3, Sym(257), DSym(3)] + tail, eob=False)], "too far back")
+    add("distance_beyond_start_at_0", [Fixed([Sym(257), DSym(0)] + tail, eob=False)], "too far back")
+    add("distance_beyond_zdict1", [Fixed([9, Sym(257), DSym(2)] + tail, eob=False)], "too far back", zdict=b"\x5a")
+    big = _pattern(32768, 2)
+    add("distance_beyond_zdict32767", [Fixed([Sym(258), DSym(29), Raw(8191, 13)] + tail, eob=False)], "too far back", zdict=big[1:])
+    hist = _pattern(32767, 1)
+    add("distance_32768_at_32767", [Stored(hist), Fixed([Sym(285), DSym(29), Raw(8191, 13)] + tail, eob=False)], "too far back")
+    return v
+
+
+def vectors():
+    """Every vector, the valid ones first: records (name, blob, zdict, expect, blocks); expect = the plaintext, or DATA"""
+    return valid_vectors() + [x for x, _ in invalid_vectors()]
+
+
+# ---- random valid streams ----------------------------------------------------------------------------------------------------------
+
+def random_complete_lengths(rng, n, maxlen):
+    """n >= 2 code lengths of a complete code, none longer than maxlen: the Kraft budget split at random (a leaf of the code tree is
+    split in two until there are n), with a taste for the deepest leaf so that long codes do occur"""
+    assert 2 <= n <= (1 << maxlen)
+    leaves = [1, 1]
+    while len(leaves) < n:
+        can = [i for i, d in enumerate(leaves) if d < maxlen]
+        deep = max(leaves[i] for i in can)
+        pick = [i for i in can if leaves[i] == deep] if rng.random() < 0.5 else can
+        i = pick[int(rng.integers(0, len(pick)))]
+        leaves[i] += 1
+        leaves.append(leaves[i])
+    rng.shuffle(leaves)
+    return [int(x) for x in leaves]
+
+
+def random_stream(rng):
+    """A valid stream of 1..12 blocks of random kind -> (blob, expect).  Output <= 40 KiB, input <= 8 KiB."""
+    while True:
+        blocks, out = [], 0
+        for _ in range(int(rng.integers(1, 13))):
+            kind = int(rng.integers(0, 4))
+            if kind == 0:
+                data = rng.bytes(int(rng.integers(0, 300)))
+                blocks.append(Stored(data))
+                out += len(data)
+                continue
+            ntok = int(rng.integers(0, 100))
+            if kind == 1:
+                lits, lens, dists = list(range(256)), list(range(257, 286)), list(range(30))
+            else:
+                maxlen = int(rng.integers(1, 16))
+                nl = int(min(rng.integers(1, 80), 1 << maxlen))
+                lsyms = [256] + [int(s) for s in rng.choice([s for s in range(286) if s != 256], nl - 1, replace=False)]
+                lits, lens = [s for s in lsyms if s < 256], [s for s in lsyms if s > 256]
+                ll = spread(lsyms, [1] if nl == 1 else random_complete_lengths(rng, nl, maxlen), int(rng.integers(max(lsyms) + 1, 287)) if max(lsyms) < 286 else 286)
+                maxd = int(rng.integers(1, 16))
+                nd = int(min(rng.integers(0, 31), 1 << maxd)) if lens else 0
+                dists = sorted(int(s) for s in rng.choice(30, nd, replace=False))
+                d = spread(dists, [1] if nd == 1 else random_complete_lengths(rng, nd, maxd), max(dists) + 1) if nd else [0]
+            toks = []
+            for _ in range(ntok):
+                feas = [s for s in dists if DBASE[s] <= out]
+                if lens and feas and out < 40 * 1024 - 258 and (not lits or rng.random() < 0.4):
+                    ls = lens[int(rng.integers(0, len(lens)))] - 257
+                    length = LBASE[ls] + int(rng.integers(0, 1 << LEXT[ls]))
+                    ds = feas[int(rng.integers(0, len(feas)))]
+                    dist = DBASE[ds] + int(rng.integers(0, min(1 << DEXT[ds], out - DBASE[ds] + 1)))
+                    toks.append(M(length, dist, ls + 257))
+                    out += length
+                elif lits:
+                    toks.append(lits[int(rng.integers(0, len(lits)))])
+                    out += 1
+            blocks.append(Fixed(toks) if kind == 1 else Dynamic(ll, d, toks, rle=bool(rng.integers(0, 2))))
+        blob = assemble(blocks)
+        if len(blob) <= 8192 and out <= 40 * 1024:
+            return blob, replay(blocks)[0]
+
+
+def random_streams(seed=1951, n=300):
+    """n random_stream cases from a fixed seed -> [(blob, expect)]"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    return [random_stream(rng) for _ in range(n)]
+
+
+def match_count(blocks):
+    return sum(isinstance(t, M) for b in blocks if not isinstance(b, Stored) for t in b.tokens)
