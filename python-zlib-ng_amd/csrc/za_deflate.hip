@@ -1974,65 +1974,14 @@ __device__ void za_sort_syms(ZaPlanLds &S, const uint32_t *freq, int nsym)
     __syncthreads();
 }
 
-// lane 0 only: Moffat-Katajainen in-place lengths on S.key[0..m) + count-based limiting.
-__device__ void za_lengths_serial(ZaPlanLds &S, int nsym, int limit, uint8_t *lens)
-{
-    const int m = S.m;
-    for (int i = 0; i < nsym; i++) lens[i] = 0;
-    if (m == 0) return;
-    if (m == 1) { lens[S.key[0] & 511u] = 1; return; }
-    uint32_t *A = S.A;
-    for (int i = 0; i < m; i++) A[i] = S.key[i] >> 9;
-    int root, leaf, next, avbl, used, dpth;
-    A[0] += A[1]; root = 0; leaf = 2;
-    for (next = 1; next < m - 1; next++) {
-        if (leaf >= m || A[root] < A[leaf]) { A[next] = A[root]; A[root++] = (uint32_t)next; }
-        else A[next] = A[leaf++];
-        if (leaf >= m || (root < next && A[root] < A[leaf])) { A[next] += A[root]; A[root++] = (uint32_t)next; }
-        else A[next] += A[leaf++];
-    }
-    A[m - 2] = 0;
-    for (next = m - 3; next >= 0; next--) A[next] = A[A[next]] + 1;
-    avbl = 1; used = dpth = 0; root = m - 2; next = m - 1;
-    while (avbl > 0 && dpth < 320) {
-        while (root >= 0 && (int)A[root] == dpth) { used++; root--; }
-        while (avbl > used && next >= 0) { A[next--] = (uint32_t)dpth; avbl--; }
-        if (next < 0) break;
-        avbl = 2 * used; dpth++; used = 0;
-    }
-    int *cnt = (int *)(S.A + 256);                 // (LDS, behind the at most 256 symbols this lane-0 form is used for: a local array
-                                                   // indexed by a variable would live in scratch memory)
-    for (int i = 0; i < 17; i++) cnt[i] = 0;
-    bool over = false;
-    for (int i = 0; i < m; i++) {
-        int d = (int)A[i];
-        if (d > limit) { d = limit; over = true; }
-        cnt[d]++;
-    }
-    if (over) {
-        uint32_t total = 0;
-        for (int i = 1; i <= limit; i++) total += (uint32_t)cnt[i] << (limit - i);
-        // every step removes one unit of the Kraft sum; the guard only bounds a corrupted state
-        for (int guard = 0; total != (1u << limit) && guard < (1 << 17); guard++) {
-            cnt[limit]--;
-            for (int i = limit - 1; i > 0; i--)
-                if (cnt[i]) { cnt[i]--; cnt[i + 1] += 2; break; }
-            total--;
-        }
-    }
-    int idx = 0;
-    for (int l = limit; l >= 1; l--)
-        for (int k = 0; k < cnt[l] && idx < m; k++) lens[S.key[idx++] & 511u] = (uint8_t)l;
-}
-
-// The same lengths with the wave: only the two-queue merge that builds the tree (phase 1 of Moffat-Katajainen) is a chain of
-// dependent steps, and it stays on lane 0 -- with the heads of its two queues kept in registers and the next two leaves fetched
-// ahead, so that a step waits for one LDS round trip at most instead of four.  Everything behind it is done by all lanes: the
-// depths of the internal nodes by pointer jumping (depth += depth of the parent, parent = the parent's parent: nine rounds at
-// most for 285 nodes) instead of a walk down the array, the leaves per depth from the internal nodes per depth (a level holds
-// twice the internal nodes of the level above it: leaves = 2 x inner[d - 1] - inner[d]) instead of the third pass, the lengths
-// by rank.  S.cltok and S.clf are scratch here (the header is built later).  125 -> 50 us for the literal/length tree of a text
-// unit: the latency of every batch too small to fill the device, and of every small call.
+// Code lengths of the symbols in S.key[0..m): Moffat-Katajainen's in-place tree + count-based limiting, by the wave.  Only the
+// two-queue merge that builds the tree (phase 1) is a chain of dependent steps, and it stays on lane 0 -- with the heads of its
+// two queues kept in registers and the next two leaves fetched ahead, so that a step waits for one LDS round trip at most.
+// Everything behind it is done by all lanes: the depths of the internal nodes by pointer jumping (depth += depth of the parent,
+// parent = the parent's parent: nine rounds at most for 285 nodes), the leaves per depth from the internal nodes per depth (a
+// level holds twice the internal nodes of the level above it: leaves = 2 x inner[d - 1] - inner[d]), the lengths by rank.
+// S.cltok and S.clf are scratch here (the header is built later).  50 us for the literal/length tree of a text unit (125 with
+// lane 0 alone): the latency of every batch too small to fill the device, and of every small call.
 __device__ void za_lengths_wave(ZaPlanLds &S, int nsym, int limit, uint8_t *lens)
 {
     const int lane = za_lane();
@@ -2138,9 +2087,10 @@ __device__ void za_lengths_wave(ZaPlanLds &S, int nsym, int limit, uint8_t *lens
     __syncthreads();
 }
 
-// The same lengths for an alphabet of at most 32 symbols (the code-length code's 19) without a single LDS round trip inside the
-// algorithm: the array lives in ONE register across the lanes (lane i holds A[i]); every index is wave-uniform, so a read is a
-// v_readlane, a write a compare and a select, and the control flow scalar.  (Lane 0 alone, through LDS: 15 us of the plan kernel's 105.)
+// The lengths of za_lengths_wave for an alphabet of at most 32 symbols (the code-length code's 19, the distance code's 30)
+// without a single LDS round trip inside the algorithm: the array lives in ONE register across the lanes (lane i holds A[i]);
+// every index is wave-uniform, so a read is a v_readlane, a write a compare and a select, and the control flow scalar.
+// (Lane 0 alone, through LDS: 15 us of the plan kernel's 105.)
 __device__ void za_lengths_small(ZaPlanLds &S, int nsym, int limit, uint8_t *lens)
 {
     const int lane = za_lane();
@@ -2205,25 +2155,9 @@ __device__ void za_lengths_small(ZaPlanLds &S, int nsym, int limit, uint8_t *len
     __syncthreads();
 }
 
-// lane 0 only: canonical codes, bit-reversed for LSB-first emission
-__device__ void za_canon_serial(const uint8_t *lens, int n, uint16_t *codes, uint32_t *scratch32 /* 32 dwords of LDS */)
-{
-    uint32_t *bl = scratch32, *nc = scratch32 + 16;
-    for (int i = 0; i < 16; i++) bl[i] = 0;
-    for (int i = 0; i < n; i++) bl[lens[i]]++;
-    bl[0] = 0;
-    uint32_t code = 0;
-    for (int b = 1; b <= 15; b++) { code = (code + bl[b - 1]) << 1; nc[b] = code; }
-    for (int i = 0; i < n; i++) {
-        const int l = lens[i];
-        uint32_t r = 0;
-        if (l) { const uint32_t c = nc[l]++; r = __brev(c) >> (32 - l); }
-        codes[i] = (uint16_t)r;
-    }
-}
-
-// all lanes: the same canonical codes, without lane 0 walking every symbol -- lengths counted with LDS atomics, the first code of
-// every length by lane (15 steps each), a symbol's place among the symbols of its length from ballots (symbols in index order)
+// Canonical codes (RFC 1951 3.2.2), bit-reversed for LSB-first emission, by all lanes: lengths counted with LDS atomics, the
+// first code of every length by lane (15 steps each), a symbol's place among the symbols of its length from ballots (symbols
+// in index order)
 __device__ void za_canon_wave(const uint8_t *lens, int n, uint16_t *codes, uint32_t *scratch32 /* 32 dwords of LDS */)
 {
     const int lane = za_lane();

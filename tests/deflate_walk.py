@@ -67,10 +67,26 @@ _FIXED_D = _table([5] * 32)
 
 class Walk:
     """Result of walk(): btypes = BTYPE of every block in order, matches = [(length, distance)], out = the decoded bytes (without
-    the preset window), final = whether a block with BFINAL was seen, end_bit = bit position behind the last block walked."""
+    the preset window), final = whether a block with BFINAL was seen, end_bit = bit position behind the last block walked,
+    tokens = the stream's tokens in order over all blocks (an int per literal, (length, distance) per match; end-of-block codes and
+    stored bytes are not tokens), blocks = one Block per block."""
 
     def __init__(self):
         self.btypes, self.matches, self.out, self.final, self.end_bit = [], [], b"", False, 0
+        self.tokens, self.blocks = [], []
+
+
+class Block:
+    """One block as walked: btype, final; ll_lens / d_lens = the code lengths read from a dynamic header (hlit / hdist of them; the
+    fixed code's 288 / 32 for BTYPE 1, empty for stored), cl_lens = the 19 code-length code lengths (by symbol), hlit, hdist, hclen;
+    start_bit = offset of the block's three header bits, header_bits = bits from there to the first token, first_token_bit and
+    eob_bit = bit offsets of the first token and of the end-of-block code (stored: of the first data byte and behind the last),
+    ntokens = tokens of this block."""
+
+    def __init__(self):
+        self.btype, self.final, self.ll_lens, self.d_lens, self.cl_lens = 0, False, [], [], []
+        self.hlit = self.hdist = self.hclen = 0
+        self.start_bit = self.header_bits = self.first_token_bit = self.eob_bit = self.ntokens = 0
 
 
 def walk(data, window=b"", stop_at_final=True):
@@ -82,8 +98,12 @@ def walk(data, window=b"", stop_at_final=True):
     while True:
         if br.n - br.pos < 3:
             break
+        blk = Block()
+        blk.start_bit = br.pos
         bfinal, btype = br.get(1), br.get(2)
         w.btypes.append(btype)
+        w.blocks.append(blk)
+        blk.btype, blk.final = btype, bool(bfinal)
         if btype == 0:
             br.align()
             ln, nln = br.get(16), br.get(16)
@@ -93,10 +113,14 @@ def walk(data, window=b"", stop_at_final=True):
             if start + ln > len(data):
                 raise WalkError("stored block truncated")
             out += bytes(data[start:start + ln])
+            blk.first_token_bit = br.pos
             br.pos += 8 * ln
+            blk.eob_bit = br.pos
+            blk.header_bits = blk.first_token_bit - blk.start_bit
         elif btype in (1, 2):
             if btype == 1:
                 lt, dt = _FIXED_L, _FIXED_D
+                blk.ll_lens, blk.d_lens = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8, [5] * 32
             else:
                 hlit, hdist, hclen = br.get(5) + 257, br.get(5) + 1, br.get(4) + 4
                 cl = [0] * 19
@@ -119,11 +143,20 @@ def walk(data, window=b"", stop_at_final=True):
                 if len(lens) > hlit + hdist:
                     raise WalkError("code lengths overrun")
                 lt, dt = _table(lens[:hlit]), _table(lens[hlit:])
+                blk.ll_lens, blk.d_lens, blk.cl_lens = lens[:hlit], lens[hlit:], cl
+                blk.hlit, blk.hdist, blk.hclen = hlit, hdist, hclen
+            blk.first_token_bit = br.pos
+            blk.header_bits = br.pos - blk.start_bit
+            ntok0 = len(w.tokens)
             while True:
+                at = br.pos
                 s = _sym(br, lt)
                 if s < 256:
                     out.append(s)
+                    w.tokens.append(s)
                 elif s == 256:
+                    blk.eob_bit = at
+                    blk.ntokens = len(w.tokens) - ntok0
                     break
                 else:
                     s -= 257
@@ -137,6 +170,7 @@ def walk(data, window=b"", stop_at_final=True):
                     if dist > len(out):
                         raise WalkError("distance too far back")
                     w.matches.append((ln, dist))
+                    w.tokens.append((ln, dist))
                     for _ in range(ln):
                         out.append(out[-dist])
         else:
