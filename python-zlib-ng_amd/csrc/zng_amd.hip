@@ -59,6 +59,7 @@ static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants
 // the level table (the same numbers as the oracle's): chain steps over table A, nice, cap, table C, dynamic programme,
 // too_far3, too_far4, shortest match (6 under Z_FILTERED, set per call), fixed-code costs (Z_FIXED, set per call).  Within 2 % of zlib 1.2.11 at the same level on held-out real files, at least zlib on the synthetic corpora.
 #define ZA_CH_STREAMS_PER_CU (ZA_HASH_BITS >= 14 ? 2u : 3u)     // what the chain kernel's LDS (table + 14 KiB) lets a CU hold
+#define ZA_WS_SHARE_DIV 4u          // ZA_WS_SHARE = 1 / 4: the most of the free device memory that the deflate workspace of a call without ZNGAMD_CHUNK_UNITS takes
 static const ZaLevel ZA_LEVELS[10] = {
     {0, 0, ZA_WIN, 0, 0, 0, 0, 0, 3, 0},
     {1, 16, ZA_WIN, 16, 0, 0, 256, 4096, 3, 0}, {2, 16, ZA_WIN, 16, 0, 0, 256, 4096, 3, 0}, {3, 16, ZA_WIN, 16, 0, 0, 256, 4096, 3, 0},
@@ -102,13 +103,14 @@ struct zngamd_ctx {
     uint32_t *d_crc_table = nullptr, *d_x8k = nullptr;
     uint32_t *d_crc_slice4 = nullptr;                                         // CRC slice-by-4 table of za_k_inflate_members
     // deflate workspaces (per chunk of units)
-    // units per launch (ZNGAMD_CHUNK_UNITS).  Workspace per unit (r06): link tables 3 x 320 KiB (two below level 5), entries 512 KiB,
-    // about 5 KiB of small arrays -- 1.44 MiB; the token words (512 KiB) live IN the link tables' memory, which nobody reads once the
-    // search is through (r05: 1.94 MiB with an eighth of slack on top).  16 384 units = 24 GB: a 4 GiB shard takes two launches per
-    // kernel and 2.1 % longer than in one (32 768: 47 GB; measured on the r06 kernels: deflate 64.5 -> 65.9 ms, the device holds
-    // 58.7 instead of 83.5 GB during the bench; 8 192: 68.4 ms, 46.3 GB) -- the default since r06, the review's choice.  A chunk
-    // that does not fit the device's free memory is halved until it does.
-    uint32_t chunk_units = 16384;
+    // units per launch set (ZNGAMD_CHUNK_UNITS; 0 = not set: the whole call).  Workspace per unit (r06): link tables 3 x 320 KiB (two
+    // below level 5), entries 512 KiB, about 5 KiB of small arrays -- 1.44 MiB; the token words (512 KiB) live IN the link tables'
+    // memory, which nobody reads once the search is through (r05: 1.94 MiB with an eighth of slack on top).  Every launch set drains
+    // the device once per kernel: a 4 GiB shard in two sets of 16 384 units (24 GB, the default of r06) took 2.1 % longer than in
+    // one of 32 768 (47 GB; measured on the r06 kernels: deflate 64.5 -> 65.9 ms; 8 192: 68.4 ms).  So a call is ONE set unless
+    // memory forbids: a set whose workspace would take more than ZA_WS_SHARE of the memory that is free (what these buffers hold
+    // already counted as free), or that does not fit what is free at all, is halved until it does.
+    uint32_t chunk_units = 0;
     DevBuf<uint16_t> links; DevBuf<uint32_t> best, tok, segtok, hist, codes; DevBuf<ZaPlan> plan;
     uint16_t *prev_p = nullptr, *linkb_p = nullptr, *linkc_p = nullptr; uint32_t *tok_p = nullptr;     // where the current chunk size puts the tables inside `links`, and the token words (inside `links` too unless zngamd_debug_keep asked for all stages to stay)
     bool debug_keep = false, last_kept = false; DevBuf<uint32_t> best_keep, dpcost;
@@ -120,7 +122,8 @@ struct zngamd_ctx {
     std::vector<ZaUnit> last_hu;                 // the units of the last deflate call as the kernels saw them (zngamd_debug_fetch)
     std::vector<ZaUnit> plan_in; std::vector<uint32_t> plan_runs; uint32_t plan_ch = 0;     // the unit table the device holds was planned from this one: a caller that compresses batch after batch of the same shape pays for the planning once
     std::vector<zngamd_block> blocks_in; std::vector<ZaUnit> blocks_hu; uint64_t blocks_len = 0;
-    uint32_t chain_slots = 512;                  // chain-kernel workgroups the device holds at once: CUs x ZA_CH_STREAMS_PER_CU (two with the 64 KiB table)
+    uint32_t chain_slots = 512;                  // chain-kernel workgroups the device holds at once: CUs x ZA_CH_STREAMS_PER_CU (two with the 64 KiB table); ZNGAMD_CHAIN_SLOTS overrides
+    uint32_t search_slots = 256;                 // search workgroups the device holds at once: one per CU (its LDS)
     uint32_t chain_run = 0;                      // ZNGAMD_CHAIN_RUN: fixed run length of the chain kernel (0 = sized to the device)
     // staging
     DevBuf<uint8_t> st_in, st_out, st_slots, st_aux, hdr; DevBuf<uint32_t> st_len, st_crc; DevBuf<uint64_t> st_off;
@@ -230,7 +233,9 @@ try {
     c->stream = c->own_stream;
     if (const char *e = getenv("ZNGAMD_CHUNK_UNITS")) { long v = atol(e); if (v >= 1 && v <= (1 << 20)) c->chunk_units = (uint32_t)v; }
     if (const char *e = getenv("ZNGAMD_CHAIN_RUN")) { long v = atol(e); if (v >= 1 && v <= (1 << 20)) c->chain_run = (uint32_t)v; }
-    { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) c->chain_slots = (uint32_t)cus * ZA_CH_STREAMS_PER_CU; }
+    { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) { c->chain_slots = (uint32_t)cus * ZA_CH_STREAMS_PER_CU; c->search_slots = (uint32_t)cus; } }
+    // (tests and sweeps: a device of v / ZA_CH_STREAMS_PER_CU CUs as far as the run plan is concerned -- all tiers within a few dozen units)
+    if (const char *e = getenv("ZNGAMD_CHAIN_SLOTS")) { long v = atol(e); if (v >= 1 && v <= (1 << 20)) { c->chain_slots = (uint32_t)v; c->search_slots = std::max<uint32_t>(1u, (uint32_t)v / ZA_CH_STREAMS_PER_CU); } }
     // tables: CRC-32 byte table and x^(8*2048*k) mod P
     uint32_t tab[256], x8k[64];
     for (uint32_t i = 0; i < 256; i++) { uint32_t v = i; for (int k = 0; k < 8; k++) v = (v & 1) ? (0xEDB88320u ^ (v >> 1)) : (v >> 1); tab[i] = v; }
@@ -612,29 +617,28 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
     const uint32_t n = (uint32_t)hu.size();
     if (n == 0) return ZNGAMD_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    uint32_t ch = std::min(n, c->chunk_units);
+    uint32_t ch = c->chunk_units ? std::min(n, c->chunk_units) : n;
     const size_t ntab = ZA_LEVELS[level].use_c ? 3 : 2;
-    if (search) {
-        // a chunk's workspaces must fit what the device has free (plus what these buffers hold already): halve it until they do
-        // (a hipMalloc failure further down is still a hard error, but no longer the first thing a smaller device or a second
-        // context on this one meets)
-        const size_t held = c->links.cap * 2 + c->best.cap * 4 + c->tok.cap * 4 + c->best_keep.cap * 4;
+    // a set's workspaces (`per_unit` bytes a unit) must fit what the device has free (plus `held`, what these buffers hold already):
+    // halve it until they do (a hipMalloc failure further down is still a hard error, but no longer the first thing a smaller
+    // device or a second context on this one meets).  A set that nobody sized (no ZNGAMD_CHUNK_UNITS) also stays within
+    // ZA_WS_SHARE of that memory: the caller's own buffers and a second context want room too.  `held` counts as free on both
+    // sides, so a call of the same shape gets the same set size every time and the kept plan stays valid.
+    auto fit_set = [&](size_t per_unit, size_t held) {
         size_t free_b = 0, total_b = 0;
-        if (ch > 64 && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {       // (a driver call: tens of microseconds, and a small call has nothing to halve)
-            auto need = [&](uint32_t k) { return (size_t)k * (ntab * ZA_PREV_STRIDE * 2 + ZA_BEST_STRIDE * 4 + (c->debug_keep ? (ZA_BEST_STRIDE + ZA_TOK_STRIDE) * 4 : 0) + 8192); };
-            while (ch > 64 && need(ch) > held && need(ch) - held > free_b - free_b / 16) ch = (ch + 1) / 2;
-        }
-    }
+        if (ch <= 64 || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return;       // (a driver call: tens of microseconds, and a small call has nothing to halve)
+        auto need = [&](uint32_t k) { return (size_t)k * per_unit; };
+        while (ch > 64 && need(ch) > held && need(ch) - held > free_b - free_b / 16) ch = (ch + 1) / 2;
+        if (!c->chunk_units) while (ch > 64 && need(ch) > (free_b + held) / ZA_WS_SHARE_DIV) ch = (ch + 1) / 2;
+    };
+    if (search)
+        fit_set(ntab * ZA_PREV_STRIDE * 2 + ZA_BEST_STRIDE * 4 + (c->debug_keep ? (ZA_BEST_STRIDE + ZA_TOK_STRIDE) * 4 : 0) + 8192,
+                c->links.cap * 2 + c->best.cap * 4 + c->tok.cap * 4 + c->best_keep.cap * 4);
     HIPCHK(c, c->units.ensure(n)); HIPCHK(c, c->segbits.ensure((size_t)n * ZA_SEGB_STRIDE)); HIPCHK(c, c->cidx.ensure((size_t)n * ZA_CIDX_STRIDE)); HIPCHK(c, c->status.ensure(n));
     if (runs_only) {
         // only the token words: in the link tables' buffer (grown to 512 KiB a unit if a search never made it larger), or, when the
         // debug copies are kept, in their own
-        const size_t held = c->links.cap * 2 + (c->debug_keep ? c->tok.cap * 4 : 0);
-        size_t free_b = 0, total_b = 0;
-        if (ch > 64 && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            auto need = [&](uint32_t k) { return (size_t)k * (ZA_TOK_STRIDE * 4 + 8192); };
-            while (ch > 64 && need(ch) > held && need(ch) - held > free_b - free_b / 16) ch = (ch + 1) / 2;
-        }
+        fit_set(ZA_TOK_STRIDE * 4 + 8192, c->links.cap * 2 + (c->debug_keep ? c->tok.cap * 4 : 0));
         if (c->debug_keep) { HIPCHK(c, c->tok.ensure((size_t)ch * ZA_TOK_STRIDE)); c->tok_p = c->tok.p; }
         else { HIPCHK(c, c->links.ensure((size_t)ch * ZA_TOK_STRIDE * 2)); c->tok_p = (uint32_t *)c->links.p; }
     }
@@ -669,8 +673,14 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
     // Runs of the chain kernel: one workgroup walks a run of consecutive units and carries its tables from unit to unit where
     // the next unit's dictionary is the tail of the one before (ZA_FLAG_CARRY); a run costs its first unit's dictionary
     // again, so longer runs save more (a quarter of the positions at most) -- but workgroups are handed out in order, and a
-    // launch ends with its last workgroup: runs of L units for the first four fifths of a launch, short ones behind them to
-    // fill the tail, and L bounded by what keeps every slot of the device busy at least twice.  Runs never cross a launch.
+    // launch ends with its last workgroup -- of the chain kernel, and of the search, which walks the same runs with half as
+    // many workgroups at once and spends three times as long on a unit.  Hence three tiers: runs of L units (L bounded by what
+    // keeps every slot of the device busy at least twice), runs of L / 4 behind them, single units at the end.  When the last
+    // run of a tier is handed out, every slot holds a run of that tier with anything between nothing and all of it left: the
+    // tiers behind it hold `slots` x the tier's run length in units to even the slots out -- all that the search's slots can
+    // have left, and what the chain kernel's twice as many slots have left on average.  (Measured at 32 768 units against a
+    // whole run length for every slot of the chain kernel: chains 13.81 / 13.92 ms, search 29.05 / 29.04; until the search was
+    // looked at, short runs simply took the last fifth: 14.07 and 29.45.)  Runs never cross a launch set.
     const bool same_plan = c->plan_ch == ch && c->plan_in.size() == hu.size() && c->last_hu.size() == hu.size() &&
                            memcmp(c->plan_in.data(), hu.data(), hu.size() * sizeof(ZaUnit)) == 0;
     if (!same_plan) {
@@ -683,12 +693,15 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
             const uint32_t m = std::min(ch, n - c0);
             const uint32_t L = c->chain_run ? c->chain_run : std::min<uint32_t>(8u, std::max<uint32_t>(1u, m / (2u * c->chain_slots)));
             const uint32_t Ls = c->chain_run ? c->chain_run : std::max<uint32_t>(1u, L / 4u);
-            const uint32_t big_end = c->chain_run ? m : (uint32_t)((uint64_t)m * 4 / 5 / L * L);
+            const uint64_t slots = std::max<uint32_t>(c->search_slots, (c->chain_slots + 1u) / 2u);
+            const uint32_t n_single = (c->chain_run || Ls == 1u) ? 0u : (uint32_t)std::min<uint64_t>(m, slots * Ls);       // (Ls = 1: the middle tier IS single units)
+            const uint32_t n_mid = c->chain_run ? 0u : (uint32_t)std::min<uint64_t>(m - n_single, slots * L);
+            const uint32_t big_end = (m - n_single - n_mid) / L * L, mid_end = m - n_single;
             uint32_t next_cut = 0;
             for (uint32_t i = 0; i < m; i++) {
                 ZaUnit &u = hv[c0 + i];
                 const bool cut = i == next_cut || !(u.flags & ZA_FLAG_CARRY);
-                if (cut) { u.flags |= ZA_FLAG_RUNHEAD; run_start.push_back(i); next_cut = i + (i < big_end ? L : Ls); }
+                if (cut) { u.flags |= ZA_FLAG_RUNHEAD; run_start.push_back(i); next_cut = i + (i < big_end ? L : i < mid_end ? Ls : 1u); }
             }
             run_start.push_back(m);                                  // (the runs of one launch: starts relative to the launch, then its end)
         }
