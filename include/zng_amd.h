@@ -578,6 +578,29 @@ int zngamd_bgzf_grep(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const 
                      int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap,
                      zngamd_alloc_fn alloc, void *user, zngamd_bgzf_grep_totals *totals);
 
+/* ---- BGZF by content, with mismatches (zlib_ng_amd/bgzf.py: grep(..., mismatches=k)).  The four calls above
+ * with max_mismatch (k) directly behind flags; every other parameter, the results, the totals and the errors are those of the call
+ * without _approx, and max_mismatch = 0 selects exactly what that call selects.  Hamming distance, that is substitutions only: a
+ * pattern of L bytes matches a line when the line's body (the line without its delimiter) has L consecutive bytes that differ from it
+ * in at most k positions.  The window lies wholly inside the body: one that holds the delimiter byte never matches, though the count
+ * would fit (a pattern holds no delimiter, so it would be one mismatch); one that would need a byte at or behind text_end never
+ * matches; a line shorter than L cannot match.  With _LINE_START the window starts at the line's first byte.  One k for all patterns
+ * of a call, 0 .. ZNGAMD_BGZF_GREP_MAX_MISMATCH and less than the length of the shortest pattern; anything else is ZNGAMD_E_ARG, found
+ * before the context is touched, like everything the exact calls refuse.  Not reported: which pattern matched, and at what distance
+ * (the row's reserved word stays 0).  Cost: there is no prefilter, every text byte is compared with every pattern byte until a window's
+ * count passes k -- 64 x 255 pattern bytes per text byte at the worst; the exact calls do not pay for it. */
+#define ZNGAMD_BGZF_GREP_MAX_MISMATCH 16u
+int zngamd_bgzf_grep_approx_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                                const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t max_mismatch,
+                                uint64_t line_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_grep_row *d_rows,
+                                uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_grep_totals *totals);
+int zngamd_bgzf_grep_approx(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                            uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                            const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t max_mismatch,
+                            uint64_t line_base, int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out,
+                            uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_grep_totals *totals);
+
 /* ---- BGZF by record (zlib_ng_amd/bgzf.py: grep_records).  zngamd_bgzf_grep on records of record_lines
  * (k, 1 .. 64) lines each: FASTQ 4, two-line FASTA 2, interleaved pairs 8; k = 1 is zngamd_bgzf_grep.  Blocks, member table, text,
  * patterns, delimiter, the lines, _FINAL, _LINE_START, _COUNT_ONLY, the cover contract, ZNGAMD_BUF_ERROR and alloc are those of
@@ -621,6 +644,21 @@ int zngamd_bgzf_grep_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len
                              int32_t match_line, int32_t first_byte, uint64_t record_base, int32_t *status, zngamd_bgzf_grep_row *rows,
                              uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user,
                              zngamd_bgzf_grep_records_totals *totals);
+/* With mismatches: max_mismatch directly behind flags, the matching rule of zngamd_bgzf_grep_approx on the lines that count for a
+ * record; match_line, first_byte and _INVERT on records mean what they mean above. */
+int zngamd_bgzf_grep_records_approx_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members,
+                                        uint32_t n_members, uint64_t text_off, uint64_t text_end, const uint8_t *patterns,
+                                        uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim,
+                                        uint32_t flags, uint32_t max_mismatch, uint32_t record_lines, int32_t match_line,
+                                        int32_t first_byte, uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                                        zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap,
+                                        zngamd_bgzf_grep_records_totals *totals);
+int zngamd_bgzf_grep_records_approx(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                                    uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                                    const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t max_mismatch,
+                                    uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base, int32_t *status,
+                                    zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc,
+                                    void *user, zngamd_bgzf_grep_records_totals *totals);
 
 /* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
  * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM

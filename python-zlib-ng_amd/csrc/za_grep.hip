@@ -4,6 +4,7 @@
 //   za_k_grep_cover   one thread per member row: do rows that decoded tile the text without a gap?  (a byte count and a flag)
 //   za_k_grep_mark    one workgroup per tile: a bit per delimiter, a bit per position where a pattern starts, then per line that
 //                     BEGINS AND ENDS in the tile its verdict; per tile a summary for the lines that cross its edges
+//   za_k_grep_mark_approx   the same with "starts" meaning "stands there with at most k bytes substituted" (section 5f.2)
 //   za_k_grep_scan    one workgroup: the scan over the tile summaries (delimiters in front, where the open line began, whether it
 //                     has matched), the verdict of every tile's first line, rows in front of every tile, the totals
 //   za_k_grep_emit    one workgroup per tile: the rows of the matching lines that end in it, in order
@@ -22,6 +23,9 @@
 #define ZA_GREP_TAIL        2u           //             a pattern starts behind the tile's last delimiter
 #define ZA_GREP_PAIR_WORDS  2048u        // the prefilter: a bit per pair of bytes (first, second) that opens a pattern
 #define ZA_GREP_SCAN_THREADS 512u
+#define ZA_GREP_MAX_MISMATCH 16u         // za_k_grep_mark_approx: mismatches at most (mirrors ZNGAMD_BGZF_GREP_MAX_MISMATCH)
+#define ZA_GREP_AP_WORDS    ((ZA_GREP_TILE + 256u) / 4u)      // what it stages: the tile and 256 bytes behind it, as dwords
+#define ZA_GREP_AP_BITS     ((ZA_GREP_TILE + 256u) / 32u)     //                 and a bit per staged byte, as dwords
 
 struct ZaGrepPat { uint32_t off, len; };                                   // mirrors zngamd_bgzf_pattern
 struct ZaGrepRow { uint64_t src_off, number; uint32_t len, reserved; };    // mirrors zngamd_bgzf_grep_row (and lies like a ZaBgzfSlice)
@@ -82,6 +86,89 @@ __device__ __forceinline__ bool za_grep_verify(const uint8_t *__restrict__ scrat
     return false;
 }
 
+// What both mark kernels end with.  s_d / s_m: a bit per byte of the tile (a delimiter; a position where a pattern starts), complete
+// behind a barrier; v.first = 0xFFFFFFFF and v.last = 0 were set in front of that barrier.  Every thread of the workgroup calls it
+// (it holds barriers): bits[tile][thread] and the tile's summary are written.
+struct ZaGrepVerdictLds {
+    uint32_t first, last;
+    uint32_t w[4], wl[4];          // per wave: 1 = has a delimiter, 2 = head, 4 = tail; its last delimiter
+    uint32_t cnt[4][3];
+};
+__device__ __forceinline__ void za_grep_tile_verdicts(const uint32_t *s_d, const uint32_t *s_m, ZaGrepVerdictLds &v, uint32_t flags,
+                                                      ulonglong2 *__restrict__ bits, ZaGrepTile *__restrict__ tiles)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    // ---- per line: thread tid owns bytes [64 tid, 64 tid + 64) of the tile
+    const uint64_t D = (uint64_t)s_d[2u * tid + 1u] << 32 | s_d[2u * tid], M = (uint64_t)s_m[2u * tid + 1u] << 32 | s_m[2u * tid];
+    const bool hasd = D != 0;
+    const uint32_t fb = hasd ? (uint32_t)__builtin_ctzll(D) : 0u, lb = hasd ? 63u - (uint32_t)__builtin_clzll(D) : 0u;
+    const bool headm = hasd ? (M & za_mask_le(fb)) != 0 : M != 0;
+    const bool tailm = hasd && lb < 63u && (M >> (lb + 1u)) != 0;
+    const uint64_t Dm = __ballot(hasd), Hm = __ballot(headm), Tm = __ballot(tailm);
+    const uint32_t mylast = tid * 64u + lb;
+    const uint64_t below = (1ull << lane) - 1ull, pd = Dm & below;
+    const uint32_t j = pd ? 63u - (uint32_t)__builtin_clzll(pd) : 0u;
+    const uint32_t lane_prev = (uint32_t)__shfl((int)mylast, (int)j, 64);
+    const uint32_t wave_last = (uint32_t)__shfl((int)mylast, Dm ? 63 - __builtin_clzll(Dm) : 0, 64);
+    if (lane == 0) {
+        uint32_t s = 0;
+        if (Dm) {
+            const uint32_t fl = (uint32_t)__builtin_ctzll(Dm), ll = 63u - (uint32_t)__builtin_clzll(Dm);
+            s = 1u | ((Hm & za_mask_le(fl)) != 0 ? 2u : 0u) | (((Tm >> ll) & 1ull) != 0 || (Hm & ~za_mask_le(ll)) != 0 ? 4u : 0u);
+        } else s = Hm != 0 ? 2u : 0u;
+        v.w[wave] = s; v.wl[wave] = wave_last;
+    }
+    if (hasd) { atomicMin(&v.first, tid * 64u + fb); atomicMax(&v.last, mylast); }
+    __syncthreads();
+    uint32_t win = 0, prevpos = 0;                    // in front of this wave: has the open line matched, is there a delimiter, where
+    bool prevd = false;
+    for (uint32_t x = 0; x < wave; x++) {
+        const uint32_t s = v.w[x];
+        if (s & 1u) { win = s >> 2 & 1u; prevd = true; prevpos = v.wl[x]; } else win |= s >> 1 & 1u;
+    }
+    uint32_t carry;
+    if (pd) { carry = (uint32_t)(Tm >> j & 1ull) | ((Hm & below & ~za_mask_le(j)) != 0 ? 1u : 0u); prevd = true; prevpos = lane_prev; }
+    else carry = win | ((Hm & below) != 0 ? 1u : 0u);
+    const uint32_t inv = flags & ZA_GREP_INVERT;
+    uint64_t L = 0, d = D;
+    uint32_t rows = 0, bytes = 0;
+    int pb = -1;
+    while (d) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(d);
+        d &= d - 1ull;
+        const uint64_t seg = M & za_mask_le(b) & ~(pb >= 0 ? za_mask_le((uint32_t)pb) : 0ull);
+        const uint32_t m = (pb >= 0 ? 0u : carry) | (seg != 0 ? 1u : 0u);
+        if ((pb >= 0 || prevd) && (m ^ inv)) {        // (the tile's first delimiter ends a line that began in front of the tile: the scan decides it)
+            L |= 1ull << b; rows++;
+            bytes += tid * 64u + b - (pb >= 0 ? tid * 64u + (uint32_t)pb : prevpos);
+        }
+        pb = (int)b;
+    }
+    bits[(size_t)blockIdx.x * 256u + tid] = make_ulonglong2(D, L);
+    uint32_t nd = (uint32_t)__popcll(D);
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) { nd += __shfl_xor(nd, x, 64); rows += __shfl_xor(rows, x, 64); bytes += __shfl_xor(bytes, x, 64); }
+    if (lane == 0) { v.cnt[wave][0] = nd; v.cnt[wave][1] = rows; v.cnt[wave][2] = bytes; }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t head = 0, tail = 0;
+        bool seen = false;
+        for (uint32_t x = 0; x < 4u; x++) {
+            const uint32_t s = v.w[x];
+            if (!seen) { head |= s >> 1 & 1u; if (s & 1u) { seen = true; tail = s >> 2 & 1u; } }
+            else if (s & 1u) tail = s >> 2 & 1u;
+            else tail |= s >> 1 & 1u;
+        }
+        ZaGrepTile t;
+        t.ndelim = v.cnt[0][0] + v.cnt[1][0] + v.cnt[2][0] + v.cnt[3][0];
+        t.first = t.ndelim ? v.first : 0u; t.last = v.last;
+        t.flags = (head ? ZA_GREP_HEAD : 0u) | (seen && tail ? ZA_GREP_TAIL : 0u);
+        t.rows = v.cnt[0][1] + v.cnt[1][1] + v.cnt[2][1] + v.cnt[3][1];
+        t.bytes = v.cnt[0][2] + v.cnt[1][2] + v.cnt[2][2] + v.cnt[3][2];
+        tiles[blockIdx.x] = t;
+    }
+}
+
 // grid: one workgroup per tile, tile0 + blockIdx.x.  bits[tile][thread] = {delimiter bits, verdict bits} of the thread's 64 bytes: a
 // verdict bit stands at the delimiter of a line that begins and ends in the tile and is selected (INVERT applied).  With LINE_START
 // a pattern counts only at a line's first byte, so "a pattern starts in the line" is the test in both modes.
@@ -93,10 +180,8 @@ __global__ __launch_bounds__(256) void za_k_grep_mark(const uint8_t *__restrict_
     __shared__ uint32_t s_pairs[ZA_GREP_PAIR_WORDS];
     __shared__ uint32_t s_d[512], s_m[512];
     __shared__ uint32_t s_key[ZA_GREP_MAX_PAT], s_off[ZA_GREP_MAX_PAT];
-    __shared__ uint32_t s_first, s_last;
-    __shared__ uint32_t s_w[4], s_wl[4];          // per wave: 1 = has a delimiter, 2 = head, 4 = tail; its last delimiter
-    __shared__ uint32_t s_cnt[4][3];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    __shared__ ZaGrepVerdictLds s_v;
+    const uint32_t tid = threadIdx.x;
     const uint64_t base = (tile0 + blockIdx.x) * (uint64_t)ZA_GREP_TILE;
     for (uint32_t i = tid; i < ZA_GREP_PAIR_WORDS; i += 256u) s_pairs[i] = pairs[i];
     s_d[tid] = 0; s_d[tid + 256u] = 0; s_m[tid] = 0; s_m[tid + 256u] = 0;
@@ -105,7 +190,7 @@ __global__ __launch_bounds__(256) void za_k_grep_mark(const uint8_t *__restrict_
         s_off[tid] = pt.off;
         s_key[tid] = pt.len | (uint32_t)blob[pt.off] << 8 | (pt.len > 1u ? (uint32_t)blob[pt.off + 1u] << 16 : 0u);
     }
-    if (tid == 0) { s_first = 0xFFFFFFFFu; s_last = 0; }
+    if (tid == 0) { s_v.first = 0xFFFFFFFFu; s_v.last = 0; }
     __syncthreads();
     const uint32_t pat = delim * 0x01010101u;
     for (uint32_t it = 0; it < 4u; it++) {            // 16 bytes per thread and round: 4 KiB per round
@@ -148,75 +233,128 @@ __global__ __launch_bounds__(256) void za_k_grep_mark(const uint8_t *__restrict_
         if (mm) atomicOr(&s_m[rel >> 5], mm << (rel & 31u));
     }
     __syncthreads();
-    // ---- per line: thread tid owns bytes [64 tid, 64 tid + 64) of the tile
-    const uint64_t D = (uint64_t)s_d[2u * tid + 1u] << 32 | s_d[2u * tid], M = (uint64_t)s_m[2u * tid + 1u] << 32 | s_m[2u * tid];
-    const bool hasd = D != 0;
-    const uint32_t fb = hasd ? (uint32_t)__builtin_ctzll(D) : 0u, lb = hasd ? 63u - (uint32_t)__builtin_clzll(D) : 0u;
-    const bool headm = hasd ? (M & za_mask_le(fb)) != 0 : M != 0;
-    const bool tailm = hasd && lb < 63u && (M >> (lb + 1u)) != 0;
-    const uint64_t Dm = __ballot(hasd), Hm = __ballot(headm), Tm = __ballot(tailm);
-    const uint32_t mylast = tid * 64u + lb;
-    const uint64_t below = (1ull << lane) - 1ull, pd = Dm & below;
-    const uint32_t j = pd ? 63u - (uint32_t)__builtin_clzll(pd) : 0u;
-    const uint32_t lane_prev = (uint32_t)__shfl((int)mylast, (int)j, 64);
-    const uint32_t wave_last = (uint32_t)__shfl((int)mylast, Dm ? 63 - __builtin_clzll(Dm) : 0, 64);
-    if (lane == 0) {
-        uint32_t s = 0;
-        if (Dm) {
-            const uint32_t fl = (uint32_t)__builtin_ctzll(Dm), ll = 63u - (uint32_t)__builtin_clzll(Dm);
-            s = 1u | ((Hm & za_mask_le(fl)) != 0 ? 2u : 0u) | (((Tm >> ll) & 1ull) != 0 || (Hm & ~za_mask_le(ll)) != 0 ? 4u : 0u);
-        } else s = Hm != 0 ? 2u : 0u;
-        s_w[wave] = s; s_wl[wave] = wave_last;
-    }
-    if (hasd) { atomicMin(&s_first, tid * 64u + fb); atomicMax(&s_last, mylast); }
+    za_grep_tile_verdicts(s_d, s_m, s_v, flags, bits, tiles);
+}
+
+// ---- up to k mismatches
+// the non-zero bytes of x as their 0x80 bits (no carry leaves a byte: 0x7f + 0x7f = 0xfe)
+__device__ __forceinline__ uint32_t za_nonzero_bytes(uint32_t x) { return ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x; }
+
+// grid, bits[] and tiles[] as za_k_grep_mark; what differs is how a match bit comes about: a pattern of len bytes starts at p when
+// scratch[p, p + len) differs from it in at most k bytes, holds no delimiter and ends at or in front of text_end (so the window lies in
+// one line's body).  No prefilter: every position is compared with every pattern, four pattern bytes a step.
+//   - The tile and the 255 bytes behind it (a window that starts in its last byte) are staged in LDS as dwords; nothing at or behind
+//     text_end is read, and so nothing at or behind scratch_cap.
+//   - s_stop has a bit per staged byte that no window may hold: a delimiter, or a byte at or behind text_end.  s_before[w] counts the
+//     stop bits in front of bitmap word w, so "no stop bit in [p, p + len)" is two counts that are equal.  It is asked of the positions
+//     whose count stayed within k only.
+//   - A thread takes four adjacent positions a round, so a wave reads 64 adjacent dwords of the text per pattern dword; the loops over
+//     patterns and pattern dwords are the same for a whole wave (they end on ballots), which leaves the pattern words in scalar registers.
+// ptab[q] = {off, len}: the pattern's first DWORD in words[] and its length in bytes; the last dword is padded with zeros.
+__global__ __launch_bounds__(256) void za_k_grep_mark_approx(const uint8_t *__restrict__ scratch, uint64_t scratch_cap, uint64_t text_off, uint64_t text_end,
+                                                             uint64_t tile0, const ZaGrepPat *__restrict__ ptab, const uint32_t *__restrict__ words,
+                                                             uint32_t np, uint32_t delim, uint32_t flags, uint32_t k,
+                                                             ulonglong2 *__restrict__ bits, ZaGrepTile *__restrict__ tiles)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_t[ZA_GREP_AP_WORDS];
+    __shared__ uint32_t s_d[512], s_m[512];
+    __shared__ uint32_t s_stop[ZA_GREP_AP_BITS], s_before[ZA_GREP_AP_BITS];
+    __shared__ uint32_t s_wsum[4];
+    __shared__ ZaGrepVerdictLds s_v;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t base = (tile0 + blockIdx.x) * (uint64_t)ZA_GREP_TILE;
+    s_d[tid] = 0; s_d[tid + 256u] = 0; s_m[tid] = 0; s_m[tid + 256u] = 0;
+    for (uint32_t i = tid; i < ZA_GREP_AP_BITS; i += 256u) s_stop[i] = 0;
+    if (tid == 0) { s_v.first = 0xFFFFFFFFu; s_v.last = 0; }
     __syncthreads();
-    uint32_t win = 0, prevpos = 0;                    // in front of this wave: has the open line matched, is there a delimiter, where
-    bool prevd = false;
-    for (uint32_t x = 0; x < wave; x++) {
-        const uint32_t s = s_w[x];
-        if (s & 1u) { win = s >> 2 & 1u; prevd = true; prevpos = s_wl[x]; } else win |= s >> 1 & 1u;
-    }
-    uint32_t carry;
-    if (pd) { carry = (uint32_t)(Tm >> j & 1ull) | ((Hm & below & ~za_mask_le(j)) != 0 ? 1u : 0u); prevd = true; prevpos = lane_prev; }
-    else carry = win | ((Hm & below) != 0 ? 1u : 0u);
-    const uint32_t inv = flags & ZA_GREP_INVERT;
-    uint64_t L = 0, d = D;
-    uint32_t rows = 0, bytes = 0;
-    int pb = -1;
-    while (d) {
-        const uint32_t b = (uint32_t)__builtin_ctzll(d);
-        d &= d - 1ull;
-        const uint64_t seg = M & za_mask_le(b) & ~(pb >= 0 ? za_mask_le((uint32_t)pb) : 0ull);
-        const uint32_t m = (pb >= 0 ? 0u : carry) | (seg != 0 ? 1u : 0u);
-        if ((pb >= 0 || prevd) && (m ^ inv)) {        // (the tile's first delimiter ends a line that began in front of the tile: the scan decides it)
-            L |= 1ull << b; rows++;
-            bytes += tid * 64u + b - (pb >= 0 ? tid * 64u + (uint32_t)pb : prevpos);
+    const uint32_t pat = delim * 0x01010101u;
+    for (uint32_t ch = tid; ch < ZA_GREP_AP_WORDS / 4u; ch += 256u) {       // 16 bytes per thread and round (no barrier in this loop)
+        const uint32_t rel = ch * 16u;
+        const uint64_t g = base + rel;
+        uint32_t w[4] = {0, 0, 0, 0}, dm = 0, stop = 0xFFFFu;
+        if (g < text_end && !(text_off > g && text_off - g >= 16u)) {
+            if (scratch_cap - g >= 16u) { const ZaU4u v = *(const ZaU4u *)(scratch + g); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+            else {                                                                    // the scratch ends inside these 16 bytes
+                uint64_t a = 0, b = 0;
+                for (uint32_t i = 0; i < (uint32_t)(scratch_cap - g); i++) { const uint64_t x = scratch[g + i]; if (i < 8u) a |= x << (8u * i); else b |= x << (8u * (i - 8u)); }
+                w[0] = (uint32_t)a; w[1] = (uint32_t)(a >> 32); w[2] = (uint32_t)b; w[3] = (uint32_t)(b >> 32);
+            }
+            const uint32_t lo = text_off > g ? (uint32_t)(text_off - g) : 0u, hi = text_end - g >= 16u ? 16u : (uint32_t)(text_end - g);
+            const uint32_t dmraw = za_mask_nibble(za_eq_mask(w[0], pat)) | za_mask_nibble(za_eq_mask(w[1], pat)) << 4 |
+                                   za_mask_nibble(za_eq_mask(w[2], pat)) << 8 | za_mask_nibble(za_eq_mask(w[3], pat)) << 12;
+            dm = dmraw & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+            stop = (dmraw | ~((1u << hi) - 1u)) & 0xFFFFu;
         }
-        pb = (int)b;
+        *(uint4 *)&s_t[ch * 4u] = make_uint4(w[0], w[1], w[2], w[3]);
+        if (dm && rel < ZA_GREP_TILE) atomicOr(&s_d[rel >> 5], dm << (rel & 31u));
+        atomicOr(&s_stop[rel >> 5], stop << (rel & 31u));
     }
-    bits[(size_t)blockIdx.x * 256u + tid] = make_ulonglong2(D, L);
-    uint32_t nd = (uint32_t)__popcll(D);
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) { nd += __shfl_xor(nd, x, 64); rows += __shfl_xor(rows, x, 64); bytes += __shfl_xor(bytes, x, 64); }
-    if (lane == 0) { s_cnt[wave][0] = nd; s_cnt[wave][1] = rows; s_cnt[wave][2] = bytes; }
     __syncthreads();
-    if (tid == 0) {
-        uint32_t head = 0, tail = 0;
-        bool seen = false;
-        for (uint32_t x = 0; x < 4u; x++) {
-            const uint32_t s = s_w[x];
-            if (!seen) { head |= s >> 1 & 1u; if (s & 1u) { seen = true; tail = s >> 2 & 1u; } }
-            else if (s & 1u) tail = s >> 2 & 1u;
-            else tail |= s >> 1 & 1u;
+    {   // s_before: thread tid sums the bitmap words 2 tid and 2 tid + 1 of the tile; the overhang's eight words follow the tile's total
+        const uint32_t n0 = (uint32_t)__popc(s_stop[2u * tid]), n1 = (uint32_t)__popc(s_stop[2u * tid + 1u]);
+        const uint32_t incl = za_wave_incl_scan(n0 + n1);
+        if (lane == 63u) s_wsum[wave] = incl;
+        __syncthreads();
+        uint32_t ex = incl - n0 - n1;
+        for (uint32_t x = 0; x < wave; x++) ex += s_wsum[x];
+        s_before[2u * tid] = ex; s_before[2u * tid + 1u] = ex + n0;
+        if (tid < ZA_GREP_AP_BITS - 512u) {
+            uint32_t t = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+            for (uint32_t i = 0; i < tid; i++) t += (uint32_t)__popc(s_stop[512u + i]);
+            s_before[512u + tid] = t;
         }
-        ZaGrepTile t;
-        t.ndelim = s_cnt[0][0] + s_cnt[1][0] + s_cnt[2][0] + s_cnt[3][0];
-        t.first = t.ndelim ? s_first : 0u; t.last = s_last;
-        t.flags = (head ? ZA_GREP_HEAD : 0u) | (seen && tail ? ZA_GREP_TAIL : 0u);
-        t.rows = s_cnt[0][1] + s_cnt[1][1] + s_cnt[2][1] + s_cnt[3][1];
-        t.bytes = s_cnt[0][2] + s_cnt[1][2] + s_cnt[2][2] + s_cnt[3][2];
-        tiles[blockIdx.x] = t;
     }
+    __syncthreads();
+    for (uint32_t it = 0; it < 16u; it++) {            // 4 positions per thread and round: 1 KiB per round (no barrier in this loop)
+        const uint32_t w = it * 256u + tid, rel = w * 4u;
+        const uint64_t g = base + rel;
+        uint32_t alive = 0;                            // the positions of the four where a pattern may start
+        if (g < text_end) {
+            const uint32_t lo = text_off > g ? (text_off - g >= 4u ? 4u : (uint32_t)(text_off - g)) : 0u, hi = text_end - g >= 4u ? 4u : (uint32_t)(text_end - g);
+            alive = ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+        }
+        if ((flags & ZA_GREP_LINE_START) && alive) {
+            uint32_t ls = (s_d[rel >> 5] >> (rel & 31u) & 7u) << 1;
+            if (rel) ls |= s_d[(rel - 1u) >> 5] >> ((rel - 1u) & 31u) & 1u;
+            else if (g > text_off) ls |= scratch[g - 1u] == delim ? 1u : 0u;
+            if (text_off >= g && text_off - g < 4u) ls |= 1u << (uint32_t)(text_off - g);      // the text begins with a line
+            alive &= ls;
+        }
+        if (__ballot(alive != 0) == 0ull) continue;
+        const uint32_t t0 = s_t[w];
+        uint32_t mm = 0;
+        for (uint32_t q = 0; q < np; q++) {
+            const uint32_t live = alive & ~mm;         // (a position that has matched needs no further pattern)
+            if (__ballot(live != 0) == 0ull) break;
+            const ZaGrepPat pt = ptab[q];
+            const uint32_t nw = (pt.len + 3u) >> 2, last80 = 0x80808080u >> (8u * (nw * 4u - pt.len));
+            const uint32_t *__restrict__ pw = words + pt.off;
+            uint32_t c0 = live & 1u ? 0u : 256u, c1 = live & 2u ? 0u : 256u, c2 = live & 4u ? 0u : 256u, c3 = live & 8u ? 0u : 256u;
+            uint32_t lo = t0;
+            for (uint32_t j = 0; j < nw; j++) {
+                const uint32_t hi = s_t[w + j + 1u], p = pw[j], m80 = j + 1u == nw ? last80 : 0x80808080u;
+                c0 += (uint32_t)__popc(za_nonzero_bytes(lo ^ p) & m80);
+                c1 += (uint32_t)__popc(za_nonzero_bytes(__builtin_amdgcn_alignbyte(hi, lo, 1u) ^ p) & m80);
+                c2 += (uint32_t)__popc(za_nonzero_bytes(__builtin_amdgcn_alignbyte(hi, lo, 2u) ^ p) & m80);
+                c3 += (uint32_t)__popc(za_nonzero_bytes(__builtin_amdgcn_alignbyte(hi, lo, 3u) ^ p) & m80);
+                lo = hi;
+                const uint32_t c01 = c0 < c1 ? c0 : c1, c23 = c2 < c3 ? c2 : c3;
+                if (__ballot((c01 < c23 ? c01 : c23) <= k) == 0ull) break;      // every pair of this wave has left
+            }
+            uint32_t cand = (c0 <= k ? 1u : 0u) | (c1 <= k ? 2u : 0u) | (c2 <= k ? 4u : 0u) | (c3 <= k ? 8u : 0u);
+            while (cand) {
+                const uint32_t s = (uint32_t)__builtin_ctz(cand);
+                cand &= cand - 1u;
+                const uint32_t b = rel + s, e = b + pt.len;
+                const uint32_t nb = s_before[b >> 5] + (uint32_t)__popc(s_stop[b >> 5] & ((1u << (b & 31u)) - 1u));
+                const uint32_t ne = s_before[e >> 5] + (uint32_t)__popc(s_stop[e >> 5] & ((1u << (e & 31u)) - 1u));
+                if (nb == ne) mm |= 1u << s;
+            }
+        }
+        if (mm) atomicOr(&s_m[rel >> 5], mm << (rel & 31u));
+    }
+    __syncthreads();
+    za_grep_tile_verdicts(s_d, s_m, s_v, flags, bits, tiles);
 }
 
 // The scan's state in front of a tile, and its step.  The operator is associative (a segmented OR with sums beside it), so a chunk

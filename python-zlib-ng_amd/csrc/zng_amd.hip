@@ -40,7 +40,7 @@ static_assert(sizeof(zngamd_bgzf_count_row) == sizeof(ZaBgzfCount) && sizeof(zng
 static_assert(sizeof(zngamd_bgzf_pattern) == sizeof(ZaGrepPat) && sizeof(zngamd_bgzf_grep_row) == sizeof(ZaGrepRow) && sizeof(ZaGrepRow) == sizeof(ZaBgzfSlice) &&
               sizeof(zngamd_bgzf_grep_totals) == 40 && offsetof(ZaGrepTotals, covered) == offsetof(zngamd_bgzf_grep_totals, covered) && sizeof(ZaGrepTotals) <= 64 &&
               ZNGAMD_BGZF_GREP_INVERT == ZA_GREP_INVERT && ZNGAMD_BGZF_GREP_LINE_START == ZA_GREP_LINE_START && ZNGAMD_BGZF_GREP_FINAL == ZA_GREP_FINAL &&
-              ZNGAMD_BGZF_GREP_COUNT_ONLY == ZA_GREP_COUNT_ONLY && ZNGAMD_BGZF_GREP_MAX_PATTERNS == ZA_GREP_MAX_PAT && ZNGAMD_BGZF_GREP_MAX_PATTERN == ZA_GREP_MAX_LEN,
+              ZNGAMD_BGZF_GREP_COUNT_ONLY == ZA_GREP_COUNT_ONLY && ZNGAMD_BGZF_GREP_MAX_PATTERNS == ZA_GREP_MAX_PAT && ZNGAMD_BGZF_GREP_MAX_PATTERN == ZA_GREP_MAX_LEN && ZNGAMD_BGZF_GREP_MAX_MISMATCH == ZA_GREP_MAX_MISMATCH,
               "bgzf grep layout");
 static_assert(sizeof(zngamd_bgzf_grep_records_totals) == sizeof(ZaGrepRecTotals) && sizeof(ZaGrepRecTotals) == 64 &&
               offsetof(ZaGrepRecTotals, covered) == offsetof(zngamd_bgzf_grep_records_totals, covered) && sizeof(ZaGrepTotals) == 56 &&
@@ -3679,12 +3679,15 @@ try {
 
 // ---- lines by content (za_grep.hip)
 // The patterns as the caller gave them: judged on the host, before a context is touched or anything is launched.
-static bool grep_patterns_ok(const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim)
+// max_mismatch: at most ZNGAMD_BGZF_GREP_MAX_MISMATCH and less than the shortest pattern's length.
+static bool grep_patterns_ok(const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim,
+                             uint32_t max_mismatch)
 {
-    if (!patterns || !table || n_patterns < 1 || n_patterns > ZNGAMD_BGZF_GREP_MAX_PATTERNS || delim < 0 || delim > 255) return false;
+    if (!patterns || !table || n_patterns < 1 || n_patterns > ZNGAMD_BGZF_GREP_MAX_PATTERNS || delim < 0 || delim > 255 ||
+        max_mismatch > ZNGAMD_BGZF_GREP_MAX_MISMATCH) return false;
     for (uint32_t i = 0; i < n_patterns; i++) {
         const uint32_t off = table[i].off, len = table[i].len;
-        if (len < 1 || len > ZNGAMD_BGZF_GREP_MAX_PATTERN || off > patterns_len || patterns_len - off < len) return false;
+        if (len < 1 || len > ZNGAMD_BGZF_GREP_MAX_PATTERN || off > patterns_len || patterns_len - off < len || max_mismatch >= len) return false;
         if (memchr(patterns + off, delim, len)) return false;
     }
     return true;
@@ -3692,29 +3695,44 @@ static bool grep_patterns_ok(const uint8_t *patterns, uint32_t patterns_len, con
 
 #define ZA_GREP_PAR_TABLE (ZA_GREP_PAIR_WORDS * 4u)                                // the parameter block: prefilter bits, pattern table, patterns
 #define ZA_GREP_PAR_BLOB  (ZA_GREP_PAR_TABLE + ZA_GREP_MAX_PAT * (uint32_t)sizeof(ZaGrepPat))
+#define ZA_GREP_APAR_WORDS (ZA_GREP_MAX_PAT * (uint32_t)sizeof(ZaGrepPat))         // with mismatches: pattern table, padded patterns
 
-// decode, cover, mark, scan, and the host waits for the scan's totals: the first `totals_len` bytes of ZaGrepTotals go to `totals`.
+// decode, cover, mark (max_mismatch 0: za_k_grep_mark; more: za_k_grep_mark_approx), scan, and the host waits for the scan's totals: the first `totals_len` bytes of ZaGrepTotals go to `totals`.
 // After it every tile has its bits, its summary and its carry (gp_bits, gp_tiles, gp_carry), unless covered is 0.
 static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
                                 uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
-                                uint32_t delim, uint32_t flags, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status,
-                                void *totals, size_t totals_len)
+                                uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap,
+                                int32_t *d_status, void *totals, size_t totals_len)
 {
     if (text_off > text_end || text_end > scratch_cap) return fail(c, ZNGAMD_E_ARG, "the text lies outside the scratch");
     if (text_end - text_off >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "a text of 4 GiB or more");
     const uint64_t tile0 = text_off / ZA_GREP_TILE;
     const uint32_t ntiles = text_end > text_off ? (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull) : 0u;
-    // the parameter block: a bit per pair of bytes that opens a pattern (a one-byte pattern: every pair with that first byte)
     std::vector<uint8_t> &par = c->gp_host;
-    par.assign((size_t)ZA_GREP_PAR_BLOB + patterns_len + 1u, 0);
-    uint32_t *pairs = (uint32_t *)par.data();
-    for (uint32_t i = 0; i < n_patterns; i++) {
-        const uint8_t *p = patterns + table[i].off;
-        if (table[i].len == 1) for (uint32_t b = 0; b < 256u; b++) { const uint32_t pr = p[0] | b << 8; pairs[pr >> 5] |= 1u << (pr & 31u); }
-        else { const uint32_t pr = p[0] | (uint32_t)p[1] << 8; pairs[pr >> 5] |= 1u << (pr & 31u); }
+    if (!max_mismatch) {
+        // the parameter block: a bit per pair of bytes that opens a pattern (a one-byte pattern: every pair with that first byte)
+        par.assign((size_t)ZA_GREP_PAR_BLOB + patterns_len + 1u, 0);
+        uint32_t *pairs = (uint32_t *)par.data();
+        for (uint32_t i = 0; i < n_patterns; i++) {
+            const uint8_t *p = patterns + table[i].off;
+            if (table[i].len == 1) for (uint32_t b = 0; b < 256u; b++) { const uint32_t pr = p[0] | b << 8; pairs[pr >> 5] |= 1u << (pr & 31u); }
+            else { const uint32_t pr = p[0] | (uint32_t)p[1] << 8; pairs[pr >> 5] |= 1u << (pr & 31u); }
+        }
+        memcpy(par.data() + ZA_GREP_PAR_TABLE, table, (size_t)n_patterns * sizeof(ZaGrepPat));
+        memcpy(par.data() + ZA_GREP_PAR_BLOB, patterns, patterns_len);
+    } else {
+        // the parameter block of za_k_grep_mark_approx: the table {first dword, length}, then every pattern padded with zeros to whole dwords
+        size_t nwords = 0;
+        for (uint32_t i = 0; i < n_patterns; i++) nwords += (table[i].len + 3u) / 4u;
+        par.assign(ZA_GREP_APAR_WORDS + nwords * 4u, 0);
+        ZaGrepPat *pt = (ZaGrepPat *)par.data();
+        uint32_t at = 0;
+        for (uint32_t i = 0; i < n_patterns; i++) {
+            pt[i].off = at; pt[i].len = table[i].len;
+            memcpy(par.data() + ZA_GREP_APAR_WORDS + (size_t)at * 4u, patterns + table[i].off, table[i].len);
+            at += (table[i].len + 3u) / 4u;
+        }
     }
-    memcpy(par.data() + ZA_GREP_PAR_TABLE, table, (size_t)n_patterns * sizeof(ZaGrepPat));
-    memcpy(par.data() + ZA_GREP_PAR_BLOB, patterns, patterns_len);
     HIPCHK(c, c->gp_par.ensure(par.size())); HIPCHK(c, c->gp_bits.ensure((size_t)ntiles * 256u + 1u)); HIPCHK(c, c->gp_tiles.ensure(ntiles + 1u));
     HIPCHK(c, c->gp_carry.ensure(ntiles + 1u));
     HIPCHK(c, hipMemcpyAsync(c->gp_par.p, par.data(), par.size(), hipMemcpyHostToDevice, c->stream));
@@ -3725,9 +3743,14 @@ static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_
     { ProfScope ps(c, ZNGAMD_K_GATHER);
       if (n_members) hipLaunchKernelGGL(za_k_grep_cover, dim3((n_members + 255u) / 256u), dim3(256), 0, c->stream, d_members, d_status, n_members, scratch_cap,
                                         text_off, text_end, d_cover);
-      if (ntiles) hipLaunchKernelGGL(za_k_grep_mark, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
-                                     (const uint32_t *)c->gp_par.p, (const ZaGrepPat *)(c->gp_par.p + ZA_GREP_PAR_TABLE), c->gp_par.p + ZA_GREP_PAR_BLOB, n_patterns,
-                                     delim, flags, c->gp_bits.p, c->gp_tiles.p);
+      if (ntiles && !max_mismatch)
+          hipLaunchKernelGGL(za_k_grep_mark, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
+                             (const uint32_t *)c->gp_par.p, (const ZaGrepPat *)(c->gp_par.p + ZA_GREP_PAR_TABLE), c->gp_par.p + ZA_GREP_PAR_BLOB, n_patterns,
+                             delim, flags, c->gp_bits.p, c->gp_tiles.p);
+      else if (ntiles)
+          hipLaunchKernelGGL(za_k_grep_mark_approx, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
+                             (const ZaGrepPat *)c->gp_par.p, (const uint32_t *)(c->gp_par.p + ZA_GREP_APAR_WORDS), n_patterns, delim, flags, max_mismatch,
+                             c->gp_bits.p, c->gp_tiles.p);
       hipLaunchKernelGGL(za_k_grep_scan, dim3(1), dim3(ZA_GREP_SCAN_THREADS), 0, c->stream, c->gp_tiles.p, ntiles, tile0, text_off, text_end, flags, line_base,
                          d_cover, c->gp_carry.p, d_tot); }
     HIPCHK(c, hipGetLastError());
@@ -3751,12 +3774,13 @@ static void bgzf_grep_pack(zngamd_ctx *c, const ZaMember *d_members, uint32_t n_
 // the lines pass, emit, pack.  own: the host form (rows and lines go to the context's buffers, as long as the totals say).
 static int bgzf_grep_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
                          uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
-                         uint32_t delim, uint32_t flags, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status,
-                         ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own, zngamd_bgzf_grep_totals *totals)
+                         uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap,
+                         int32_t *d_status, ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own,
+                         zngamd_bgzf_grep_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
     const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, flags,
-                                       line_base, d_scratch, scratch_cap, d_status, totals, sizeof *totals);
+                                       max_mismatch, line_base, d_scratch, scratch_cap, d_status, totals, sizeof *totals);
     if (r) return r;
     const uint64_t tile0 = text_off / ZA_GREP_TILE;
     const uint32_t ntiles = text_end > text_off ? (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull) : 0u;
@@ -3782,15 +3806,26 @@ int zngamd_bgzf_grep_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const
                          uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
                          int delim, uint32_t flags, uint64_t line_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status,
                          zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_grep_totals *totals)
+{
+    return zngamd_bgzf_grep_approx_dev(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, flags, 0,
+                                       line_base, d_scratch, scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap, totals);
+}
+
+// the exact call is this one with max_mismatch = 0
+int zngamd_bgzf_grep_approx_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                                int delim, uint32_t flags, uint32_t max_mismatch, uint64_t line_base, void *d_scratch, uint64_t scratch_cap,
+                                int32_t *d_status, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap,
+                                zngamd_bgzf_grep_totals *totals)
 try {
-    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim)) return ZNGAMD_E_ARG;
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim, max_mismatch)) return ZNGAMD_E_ARG;
     if (!c || !totals || (flags & ~15u) || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) ||
         (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     int r = bgzf_grep_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, patterns, patterns_len, table,
-                          n_patterns, (uint32_t)delim, flags, line_base, (uint8_t *)d_scratch, scratch_cap, d_status, (ZaGrepRow *)d_rows, rows_cap,
-                          (uint8_t *)d_out, out_cap, false, totals);
+                          n_patterns, (uint32_t)delim, flags, max_mismatch, line_base, (uint8_t *)d_scratch, scratch_cap, d_status, (ZaGrepRow *)d_rows,
+                          rows_cap, (uint8_t *)d_out, out_cap, false, totals);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -3801,8 +3836,17 @@ int zngamd_bgzf_grep(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zn
                      uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim,
                      uint32_t flags, uint64_t line_base, int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap,
                      zngamd_alloc_fn alloc, void *user, zngamd_bgzf_grep_totals *totals)
+{
+    return zngamd_bgzf_grep_approx(c, in, in_len, members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, flags, 0,
+                                   line_base, status, rows, rows_cap, out, out_cap, alloc, user, totals);
+}
+
+int zngamd_bgzf_grep_approx(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                            uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                            int delim, uint32_t flags, uint32_t max_mismatch, uint64_t line_base, int32_t *status, zngamd_bgzf_grep_row *rows,
+                            uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_grep_totals *totals)
 try {
-    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim)) return ZNGAMD_E_ARG;
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim, max_mismatch)) return ZNGAMD_E_ARG;
     if (!c || !totals || (flags & ~15u) || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!out && out_cap) ||
         (alloc && (rows || out))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
@@ -3810,7 +3854,7 @@ try {
     int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
     if (r) return r;
     r = bgzf_grep_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, (uint32_t)delim, flags,
-                      line_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, true, totals);
+                      max_mismatch, line_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, true, totals);
     if (r) return r;
     if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3840,7 +3884,7 @@ static bool grep_records_ok(uint32_t record_lines, int32_t match_line, int32_t f
 // emit, pack.  own: the host form (rows and records go to the context's buffers, as long as the totals say).
 static int bgzf_grep_records_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
                                  uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
-                                 uint32_t delim, uint32_t flags, uint32_t k, int32_t match_line, int32_t first_byte, uint64_t record_base,
+                                 uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint32_t k, int32_t match_line, int32_t first_byte, uint64_t record_base,
                                  uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status, ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out,
                                  uint64_t out_cap, bool own, zngamd_bgzf_grep_records_totals *totals)
 {
@@ -3848,7 +3892,7 @@ static int bgzf_grep_records_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in
     ZaGrepTotals lt;
     const uint32_t lflags = flags & (ZA_GREP_LINE_START | ZA_GREP_FINAL);
     const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, lflags,
-                                       0, d_scratch, scratch_cap, d_status, &lt, sizeof lt);
+                                       max_mismatch, 0, d_scratch, scratch_cap, d_status, &lt, sizeof lt);
     if (r) return r;
     totals->tail_off = text_off;
     if (!lt.covered) return ZNGAMD_OK;
@@ -3899,15 +3943,27 @@ int zngamd_bgzf_grep_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_le
                                  int delim, uint32_t flags, uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base,
                                  void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out,
                                  uint64_t out_cap, zngamd_bgzf_grep_records_totals *totals)
+{
+    return zngamd_bgzf_grep_records_approx_dev(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim,
+                                               flags, 0, record_lines, match_line, first_byte, record_base, d_scratch, scratch_cap, d_status, d_rows, rows_cap,
+                                               d_out, out_cap, totals);
+}
+
+int zngamd_bgzf_grep_records_approx_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                        uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                                        const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t max_mismatch,
+                                        uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base, void *d_scratch,
+                                        uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out,
+                                        uint64_t out_cap, zngamd_bgzf_grep_records_totals *totals)
 try {
-    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim) || !grep_records_ok(record_lines, match_line, first_byte)) return ZNGAMD_E_ARG;
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim, max_mismatch) || !grep_records_ok(record_lines, match_line, first_byte)) return ZNGAMD_E_ARG;
     if (!c || !totals || (flags & ~15u) || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) ||
         (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     int r = bgzf_grep_records_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, patterns, patterns_len, table,
-                                  n_patterns, (uint32_t)delim, flags, record_lines, match_line, first_byte, record_base, (uint8_t *)d_scratch, scratch_cap,
-                                  d_status, (ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false, totals);
+                                  n_patterns, (uint32_t)delim, flags, max_mismatch, record_lines, match_line, first_byte, record_base, (uint8_t *)d_scratch,
+                                  scratch_cap, d_status, (ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false, totals);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -3919,8 +3975,19 @@ int zngamd_bgzf_grep_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, 
                              int delim, uint32_t flags, uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base,
                              int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc,
                              void *user, zngamd_bgzf_grep_records_totals *totals)
+{
+    return zngamd_bgzf_grep_records_approx(c, in, in_len, members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, flags, 0,
+                                           record_lines, match_line, first_byte, record_base, status, rows, rows_cap, out, out_cap, alloc, user, totals);
+}
+
+int zngamd_bgzf_grep_records_approx(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                                    uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                                    const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t max_mismatch,
+                                    uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base, int32_t *status,
+                                    zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user,
+                                    zngamd_bgzf_grep_records_totals *totals)
 try {
-    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim) || !grep_records_ok(record_lines, match_line, first_byte)) return ZNGAMD_E_ARG;
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim, max_mismatch) || !grep_records_ok(record_lines, match_line, first_byte)) return ZNGAMD_E_ARG;
     if (!c || !totals || (flags & ~15u) || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!out && out_cap) ||
         (alloc && (rows || out))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
@@ -3928,8 +3995,8 @@ try {
     int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
     if (r) return r;
     r = bgzf_grep_records_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, (uint32_t)delim,
-                              flags, record_lines, match_line, first_byte, record_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, true,
-                              totals);
+                              flags, max_mismatch, record_lines, match_line, first_byte, record_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr,
+                              0, true, totals);
     if (r) return r;
     if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

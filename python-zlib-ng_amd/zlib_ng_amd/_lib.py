@@ -83,6 +83,7 @@ SYMBOLS = [
     "zngamd_bgzf_compress_dev", "zngamd_bgzf_compress", "zngamd_bgzf_scan", "zngamd_bgzf_read_dev", "zngamd_bgzf_read", "zngamd_bgzf_stats",
     "zngamd_bgzf_count_dev", "zngamd_bgzf_count", "zngamd_bgzf_line_positions_dev", "zngamd_bgzf_line_positions", "zngamd_bgzf_read_lines_dev",
     "zngamd_bgzf_read_lines", "zngamd_bgzf_grep_dev", "zngamd_bgzf_grep", "zngamd_bgzf_grep_records_dev", "zngamd_bgzf_grep_records",
+    "zngamd_bgzf_grep_approx_dev", "zngamd_bgzf_grep_approx", "zngamd_bgzf_grep_records_approx_dev", "zngamd_bgzf_grep_records_approx",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
@@ -144,6 +145,7 @@ BGZF_RANK_END = 0xFFFFFFFF                     # ZNGAMD_BGZF_RANK_END: the posit
 BGZF_COUNT_LAST = 1                            # ZNGAMD_BGZF_COUNT_LAST
 BGZF_GREP_INVERT, BGZF_GREP_LINE_START, BGZF_GREP_FINAL, BGZF_GREP_COUNT_ONLY = 1, 2, 4, 8      # ZNGAMD_BGZF_GREP_*
 BGZF_GREP_MAX_PATTERNS, BGZF_GREP_MAX_PATTERN = 64, 255
+BGZF_GREP_MAX_MISMATCH = 16                    # ZNGAMD_BGZF_GREP_MAX_MISMATCH
 GREP_ROW_DTYPE = np.dtype([("src_off", "<u8"), ("number", "<u8"), ("len", "<u4"), ("reserved", "<u4")])      # zngamd_bgzf_grep_row
 
 
@@ -323,6 +325,11 @@ def load():
             L.zngamd_bgzf_grep_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_int,
                                                    C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN,
                                                    vp, vp]
+        if hasattr(L, "zngamd_bgzf_grep_approx"):           # the exact calls' parameters with max_mismatch behind flags
+            for name in ("zngamd_bgzf_grep", "zngamd_bgzf_grep_records"):
+                for form in ("", "_dev"):
+                    exact = getattr(L, name + form).argtypes
+                    getattr(L, name + "_approx" + form).argtypes = exact[:13] + [C.c_uint32] + exact[13:]
         if hasattr(L, "zngamd_bgzf_tabix"):
             L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
                                                 C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1273,17 +1280,24 @@ class Context:
                                                         v(d_range_status)), (OK, BUF_ERROR))
         return r, ol.value
 
-    def bgzf_grep(self, data, members, text_off, text_end, blob, table, delim, flags, line_base=0, caps=None):
+    def bgzf_grep(self, data, members, text_off, text_end, blob, table, delim, flags, line_base=0, caps=None, mismatches=0):
         """zngamd_bgzf_grep: data = packed compressed blocks, members = numpy table of MEMBER rows, (blob, table) as
         grep_pattern_table gives them -> (code, block statuses, totals, rows (GREP_ROW_DTYPE), packed lines).  caps None: rows and
         lines are allocated once the engine knows their sizes; (rows, bytes): buffers of those sizes, and code is BUF_ERROR (nothing
-        written) when the result needs more"""
+        written) when the result needs more.  mismatches k > 0: zngamd_bgzf_grep_approx, a pattern matches with up to k bytes substituted"""
+        if mismatches:
+            return self._bgzf_grep(self.L.zngamd_bgzf_grep_approx, BgzfGrepTotals(), data, members, text_off, text_end, blob, table, delim, flags,
+                                   (mismatches, line_base), caps)
         return self._bgzf_grep(self.L.zngamd_bgzf_grep, BgzfGrepTotals(), data, members, text_off, text_end, blob, table, delim, flags, (line_base,), caps)
 
     def bgzf_grep_records(self, data, members, text_off, text_end, blob, table, delim, flags, record_lines, match_line=-1, first_byte=-1,
-                          record_base=0, caps=None):
+                          record_base=0, caps=None, mismatches=0):
         """zngamd_bgzf_grep_records: bgzf_grep on records of record_lines lines (match_line, first_byte: -1 for none) -> (code, block
-        statuses, totals (BgzfGrepRecordsTotals), rows, the records packed); nothing comes back when totals.bad is set"""
+        statuses, totals (BgzfGrepRecordsTotals), rows, the records packed); nothing comes back when totals.bad is set.  mismatches k > 0:
+        zngamd_bgzf_grep_records_approx"""
+        if mismatches:
+            return self._bgzf_grep(self.L.zngamd_bgzf_grep_records_approx, BgzfGrepRecordsTotals(), data, members, text_off, text_end, blob, table, delim,
+                                   flags, (mismatches, record_lines, match_line, first_byte, record_base), caps)
         return self._bgzf_grep(self.L.zngamd_bgzf_grep_records, BgzfGrepRecordsTotals(), data, members, text_off, text_end, blob, table, delim, flags,
                                (record_lines, match_line, first_byte, record_base), caps)
 
@@ -1327,28 +1341,31 @@ class Context:
         return r, st[:nm], tot, rows_out, packed
 
     def bgzf_grep_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, line_base, d_scratch,
-                      scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap):
-        """zngamd_bgzf_grep_dev on device pointers (the patterns: host memory) -> (code, totals); rows and lines stay on the device"""
+                      scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap, mismatches=0):
+        """zngamd_bgzf_grep_dev (mismatches > 0: zngamd_bgzf_grep_approx_dev) on device pointers (the patterns: host memory) -> (code, totals);
+        rows and lines stay on the device"""
         v = lambda x: C.c_void_p(int(x)) if x else None
         table = np.ascontiguousarray(table, np.uint32)
         tot = BgzfGrepTotals()
         bp, bkeep = _addr(blob)
-        r = self._chk(self.L.zngamd_bgzf_grep_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob),
-                                                  C.c_void_p(table.ctypes.data), len(table), delim, flags, line_base, v(d_scratch), scratch_cap,
-                                                  v(d_status), v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
+        fn, k = (self.L.zngamd_bgzf_grep_approx_dev, (mismatches,)) if mismatches else (self.L.zngamd_bgzf_grep_dev, ())
+        r = self._chk(fn(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table),
+                         delim, flags, *k, line_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
+                      (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_grep_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, record_lines, match_line,
-                              first_byte, record_base, d_scratch, scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap):
-        """zngamd_bgzf_grep_records_dev on device pointers (the patterns: host memory) -> (code, totals); rows and records stay on the device"""
+                              first_byte, record_base, d_scratch, scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap, mismatches=0):
+        """zngamd_bgzf_grep_records_dev (mismatches > 0: zngamd_bgzf_grep_records_approx_dev) on device pointers (the patterns: host memory)
+        -> (code, totals); rows and records stay on the device"""
         v = lambda x: C.c_void_p(int(x)) if x else None
         table = np.ascontiguousarray(table, np.uint32)
         tot = BgzfGrepRecordsTotals()
         bp, bkeep = _addr(blob)
-        r = self._chk(self.L.zngamd_bgzf_grep_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob),
-                                                          C.c_void_p(table.ctypes.data), len(table), delim, flags, record_lines, match_line, first_byte,
-                                                          record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap, v(d_out), out_cap,
-                                                          C.byref(tot)), (OK, BUF_ERROR))
+        fn, k = (self.L.zngamd_bgzf_grep_records_approx_dev, (mismatches,)) if mismatches else (self.L.zngamd_bgzf_grep_records_dev, ())
+        r = self._chk(fn(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table),
+                         delim, flags, *k, record_lines, match_line, first_byte, record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap,
+                         v(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_tabix(self, data, members, text_off, text_end, conf, delim, flags, line_base=0, caps=None):

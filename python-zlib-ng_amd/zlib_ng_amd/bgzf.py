@@ -26,6 +26,7 @@ offset inside that block's output -- what .bai, .tbi and .csi indexes store, and
     n = bgzf.grep("reads.fastq.gz", [b"ACGTTGCA", b"TGCAACGT"], count=True, start=cuts[2], stop=cuts[3])
     reads = bgzf.grep_records("reads.fastq.gz", b"ACGTTGCA", 4, match_line=1, first_byte=b"@")      # records by content: the reads whose
                                                                       # bases hold the barcode, all four lines of each, in the same one pass
+    reads = bgzf.grep_records("reads.fastq.gz", b"GATTACAGATTACATC", 4, match_line=1, mismatches=1)      # ... with one base substituted at most
 
     tbi = bgzf.TabixIndex.build("calls.vcf.gz", "vcf")                # lines by region: the fields of every line are read on the GPU, a
     tbi.save("calls.vcf.gz.tbi")                                      # standard .tbi comes out; fetch() plans on it, decodes the blocks
@@ -591,6 +592,18 @@ def _grep_patterns(patterns, delimiter):
     return pats, delimiter
 
 
+def _grep_mismatches(mismatches, pats):
+    """-> k as zngamd_bgzf_grep_approx takes it; ValueError as grep() documents it"""
+    if isinstance(mismatches, bool) or not isinstance(mismatches, (int, np.integer)):
+        raise ValueError("mismatches is an integer")
+    k = int(mismatches)
+    if not 0 <= k <= _lib.BGZF_GREP_MAX_MISMATCH:
+        raise ValueError(f"mismatches lies between 0 and {_lib.BGZF_GREP_MAX_MISMATCH}, not {k}")
+    if k >= min(len(p) for p in pats):
+        raise ValueError(f"mismatches is less than the length of the shortest pattern ({min(len(p) for p in pats)}), not {k}")
+    return k
+
+
 def _grep_window(coffs, isizes, text_off, stop, ended, text_cap):
     """Which part of a window is searched.  coffs / isizes: file offset and ISIZE of the window's blocks, in file order; text_off: where
     the first line starts in the first block's output; stop: None or (coffset, uoffset), the line start in front of which the search
@@ -678,10 +691,12 @@ def _grep_record_args(record_lines, match_line, first_byte):
     return k, j, b
 
 
-def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line, records=None):
+def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line, records=None, mismatches=0):
     """The window loop of grep() and, with records = (record_lines, match_line, first_byte, allow_short), of grep_records(): then the
     unit that is counted, numbered, carried over a window's end and bounded by max_line is the record."""
     pats, delimiter = _grep_patterns(patterns, delimiter)
+    mismatches = _grep_mismatches(mismatches, pats)
+    approx = {"mismatches": mismatches} if mismatches else {}      # (0: the engine is called with the arguments it always had)
     unit, bound = ("record", "max_record") if records is not None else ("line", "max_line")
     if records is not None:
         rec_k, rec_j, rec_b = _grep_record_args(*records[:3])
@@ -730,10 +745,10 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
             cend = int(coffs[n_use - 1] + csizes[n_use - 1]) if n_use else 0
             wflags = flags | (_lib.BGZF_GREP_FINAL if final else 0)
             if records is None:
-                _, status, tot, rows, packed = ctx.bgzf_grep(data[:cend], members, text_off, text_end, blob, table, delimiter[0], wflags, line_base)
+                _, status, tot, rows, packed = ctx.bgzf_grep(data[:cend], members, text_off, text_end, blob, table, delimiter[0], wflags, line_base, **approx)
             else:
                 _, status, tot, rows, packed = ctx.bgzf_grep_records(data[:cend], members, text_off, text_end, blob, table, delimiter[0], wflags,
-                                                                     rec_k, rec_j, rec_b, line_base)
+                                                                     rec_k, rec_j, rec_b, line_base, **approx)
             bad = np.nonzero(status)[0]
             if len(bad):
                 raise _block_error(c_next + int(coffs[bad[0]]), status[bad[0]])
@@ -786,7 +801,7 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
 
 
 def grep(file, patterns, *, delimiter=b"\n", invert=False, line_start=False, count=False, max_count=None, start=None, stop=None,
-         first_line=0, max_line=64 << 20):
+         first_line=0, max_line=64 << 20, mismatches=0):
     """The lines of a BGZF file (a path or a seekable binary file) that contain one of `patterns`: fixed byte strings, one bytes-like
     object or 1 to 64 of them, 1 to 255 bytes each, none holding the delimiter byte (ValueError).  The file is read in windows; each
     window's blocks are decoded in one launch and searched where they lie on the GPU, and only the matching lines, their numbers and
@@ -798,18 +813,22 @@ def grep(file, patterns, *, delimiter=b"\n", invert=False, line_start=False, cou
       first_line   the number of the first line searched
       max_line     ValueError (naming the line's virtual offset) for a line that is still open after this many bytes of a window:
                    the bound on the memory a file without delimiters can claim (at most 2**31)
+      mismatches   k: a pattern of L bytes also matches L consecutive bytes of a line's body (the line without its delimiter) that
+                   differ from it in at most k places -- substitutions only, no insertions or deletions; one k for all patterns, 0 to 16
+                   and less than the shortest pattern's length (ValueError).  Every pattern is compared at every byte: the cost grows
+                   with the patterns' total length.  0, the default, is the exact search
     A line ends with `delimiter` (one byte) and is returned with it; a non-empty remainder behind the last one is the last line.
     BadGzipFile for a file that is not BGZF or a block that does not decode (with its offset; no partial result), EOFError for a
     file that ends inside a block."""
     if _is_path(file):
         with _builtin_open(file, "rb") as f:
             return grep(f, patterns, delimiter=delimiter, invert=invert, line_start=line_start, count=count, max_count=max_count,
-                        start=start, stop=stop, first_line=first_line, max_line=max_line)
-    return _grep_file(file, None, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line)
+                        start=start, stop=stop, first_line=first_line, max_line=max_line, mismatches=mismatches)
+    return _grep_file(file, None, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line, None, mismatches)
 
 
 def grep_records(file, patterns, record_lines, *, match_line=None, first_byte=None, delimiter=b"\n", invert=False, line_start=False,
-                 count=False, max_count=None, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+                 count=False, max_count=None, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False, mismatches=0):
     """grep() on records of `record_lines` (1 to 64) lines each -- FASTQ 4, two-line FASTA 2, interleaved pairs 8 -- in one pass: the
     records of which one line contains one of `patterns` come back WHOLE, as `grep -B1 -A2` or `seqkit grep -s -p` give them.  The
     file (or its part from `start`) begins with a record; record r is its lines [k r, k r + k).  -> a GrepResult whose numbers are
@@ -824,14 +843,15 @@ def grep_records(file, patterns, record_lines, *, match_line=None, first_byte=No
       first_record  the number of the first record searched
       max_record    ValueError (naming the record's virtual offset) for a record that is still open after this many bytes of a window
       allow_short   the lines left over at the end (fewer than record_lines) are a last record; without it they are a ValueError
-                    that names the record and how many lines it has"""
+                    that names the record and how many lines it has
+      mismatches    as for grep(): a pattern matches a line of the record with up to this many bytes substituted"""
     if _is_path(file):
         with _builtin_open(file, "rb") as f:
             return grep_records(f, patterns, record_lines, match_line=match_line, first_byte=first_byte, delimiter=delimiter, invert=invert,
                                 line_start=line_start, count=count, max_count=max_count, start=start, stop=stop, first_record=first_record,
-                                max_record=max_record, allow_short=allow_short)
+                                max_record=max_record, allow_short=allow_short, mismatches=mismatches)
     return _grep_file(file, None, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_record, max_record,
-                      (record_lines, match_line, first_byte, allow_short))
+                      (record_lines, match_line, first_byte, allow_short), mismatches)
 
 
 # ---- lines by region (DESIGN.md section 5g): a tabix index built on the GPU, and the rows of a region filtered there
@@ -2277,7 +2297,7 @@ class BgzfReader(io.BufferedIOBase):
         return out
 
     def grep(self, patterns, *, delimiter=b"\n", invert=False, line_start=False, count=False, max_count=None, start=None, stop=None,
-             first_line=0, max_line=64 << 20):
+             first_line=0, max_line=64 << 20, mismatches=0):
         """bgzf.grep() on this reader's file; the read position stays where it was"""
         if self.closed:
             raise ValueError("grep() on closed BgzfReader object")
@@ -2286,12 +2306,13 @@ class BgzfReader(io.BufferedIOBase):
         at = self._fp.tell()
         try:
             return _grep_file(self._fp, self._ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line,
-                              max_line)
+                              max_line, None, mismatches)
         finally:
             self._fp.seek(at)
 
     def grep_records(self, patterns, record_lines, *, match_line=None, first_byte=None, delimiter=b"\n", invert=False, line_start=False,
-                     count=False, max_count=None, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+                     count=False, max_count=None, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False,
+                     mismatches=0):
         """bgzf.grep_records() on this reader's file; the read position stays where it was"""
         if self.closed:
             raise ValueError("grep_records() on closed BgzfReader object")
@@ -2300,7 +2321,7 @@ class BgzfReader(io.BufferedIOBase):
         at = self._fp.tell()
         try:
             return _grep_file(self._fp, self._ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_record,
-                              max_record, (record_lines, match_line, first_byte, allow_short))
+                              max_record, (record_lines, match_line, first_byte, allow_short), mismatches)
         finally:
             self._fp.seek(at)
 
