@@ -587,7 +587,7 @@ int zngamd_bgzf_grep(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const 
  * matches; a line shorter than L cannot match.  With _LINE_START the window starts at the line's first byte.  One k for all patterns
  * of a call, 0 .. ZNGAMD_BGZF_GREP_MAX_MISMATCH and less than the length of the shortest pattern; anything else is ZNGAMD_E_ARG, found
  * before the context is touched, like everything the exact calls refuse.  Not reported: which pattern matched, and at what distance
- * (the row's reserved word stays 0).  Cost: there is no prefilter, every text byte is compared with every pattern byte until a window's
+ * (the row's reserved word stays 0; zngamd_bgzf_classify_records below answers that).  Cost: there is no prefilter, every text byte is compared with every pattern byte until a window's
  * count passes k -- 64 x 255 pattern bytes per text byte at the worst; the exact calls do not pay for it. */
 #define ZNGAMD_BGZF_GREP_MAX_MISMATCH 16u
 int zngamd_bgzf_grep_approx_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
@@ -659,6 +659,68 @@ int zngamd_bgzf_grep_records_approx(zngamd_ctx *ctx, const uint8_t *in, uint64_t
                                     uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base, int32_t *status,
                                     zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc,
                                     void *user, zngamd_bgzf_grep_records_totals *totals);
+
+/* ---- BGZF by nearest pattern (zlib_ng_amd/bgzf.py: classify_records, demux).  Not "which records carry one of
+ * the patterns" but, for every record, "which of the patterns is it, and how surely": what a demultiplexer asks of its 8 to 64
+ * barcodes.  The record model is that of zngamd_bgzf_grep_records (record_lines, match_line, first_byte, _LINE_START, _FINAL, the
+ * open tail, the short last record, the cover contract), the window rule that of zngamd_bgzf_grep_approx (a window lies wholly inside
+ * a line's body, holds no delimiter, needs no byte at or behind text_end, with _LINE_START starts at the line's first byte), and
+ * max_mismatch (k) is 0 .. 16 and less than the shortest pattern's length; k = 0 is exact assignment.  The rule:
+ *   - d_i(r), for record r and pattern i, is the smallest distance <= k over all windows of the record's lines that count (all of
+ *     them, or line match_line alone); "none" when no window is within k.
+ *   - unassigned: every d_i is none.                    row {255, 255, 255, 0}
+ *   - assigned to i at distance d = min d_i when exactly one pattern reaches d.          row {i, i, d, _CLASS_ASSIGNED}
+ *   - ambiguous when two or more patterns reach the minimum: the lowest and the highest index among them.   row {lo, hi, d, _CLASS_AMBIGUOUS}
+ * The result depends on the text and the pattern list alone.  Two patterns with the same bytes are ZNGAMD_E_ARG (neither could ever
+ * be assigned); a pattern that is a prefix of another is allowed, the rule settles the pair.  Classes, for counting and grouping:
+ * i (0 .. n_patterns - 1) for the records assigned to pattern i, n_patterns for the ambiguous ones, n_patterns + 1 for the unassigned
+ * ones; n_classes = n_patterns + 2, at most 66.
+ * flags: _LINE_START, _FINAL and ZNGAMD_BGZF_CLASSIFY_GROUP; anything else, _INVERT and _COUNT_ONLY included, is ZNGAMD_E_ARG.
+ * Without _GROUP only d_class[0 .. seen), one row per record in record order, and the totals leave the kernels; d_rows and d_out may
+ * be NULL with capacity 0.  With _GROUP d_rows[0 .. seen) holds a row per record ordered by class, then by record number (src_off,
+ * number = record_base + r, len as in zngamd_bgzf_grep_records; reserved: the record's class row), and d_out the records packed whole
+ * in that order: class c has the rows [sum of class_records[< c], ... + class_records[c]) and the bytes [sum of class_bytes[< c], ...).
+ * ZNGAMD_BUF_ERROR: class_cap < seen or, with _GROUP, rows_cap < seen or out_cap < bytes; nothing is written, the totals are valid.
+ * bad / bad_record / bad_src / covered / short_lines / tail_off mean what they mean in zngamd_bgzf_grep_records_totals; with bad set
+ * no row and no byte is written.  Hostile arguments -- patterns, max_mismatch, record_lines / match_line / first_byte, flags, duplicate
+ * patterns, totals = NULL -- are ZNGAMD_E_ARG before the context is touched.  Device memory beside the tiles: 8 bytes per line and 17
+ * bytes per record of the text, and 8 bytes per class and 256 records. */
+typedef struct { uint8_t pattern, other, distance, flags; } zngamd_bgzf_class_row;               /* 4 B */
+#define ZNGAMD_BGZF_CLASS_ASSIGNED  1u   /* pattern == other: the one nearest pattern, at `distance` */
+#define ZNGAMD_BGZF_CLASS_AMBIGUOUS 2u   /* pattern < other: the lowest and the highest index at `distance` */
+/* flags == 0: unassigned; pattern = other = distance = 255 */
+#define ZNGAMD_BGZF_CLASSIFY_GROUP  16u  /* flags of the call: also return the records, grouped by class */
+#define ZNGAMD_BGZF_CLASSIFY_MAX_CLASSES 66u
+typedef struct {
+    uint64_t seen;         /* records of the text that were decided (the open tail is not one of them) */
+    uint64_t bytes;        /* their bytes: the sum of class_bytes */
+    uint64_t tail_off;     /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;   /* bad = 1: the number of the first record whose first byte is not first_byte */
+    uint64_t bad_src;      /*          and where it starts in the scratch */
+    uint32_t covered;      /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;  /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;
+    uint32_t n_classes;    /* n_patterns + 2 */
+    uint64_t class_records[ZNGAMD_BGZF_CLASSIFY_MAX_CLASSES];      /* records per class; entries from n_classes on are 0 */
+    uint64_t class_bytes[ZNGAMD_BGZF_CLASSIFY_MAX_CLASSES];        /* and their bytes */
+} zngamd_bgzf_classify_totals;                                                                    /* 1112 B */
+int zngamd_bgzf_classify_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                     uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                                     const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t max_mismatch,
+                                     uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base, void *d_scratch,
+                                     uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_class_row *d_class, uint64_t class_cap,
+                                     zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap,
+                                     zngamd_bgzf_classify_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; status, the class rows and, with _GROUP, the rows and the packed records
+ * come back.  With alloc (class_rows = rows = out = NULL, the capacities 0) the caller's memory is asked for once the sizes are known,
+ * in the order class rows (seen * 4 bytes), rows (seen * 24 bytes), bytes -- the last two with _GROUP only; NULL from it:
+ * ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_classify_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                                 uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                                 const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags, uint32_t max_mismatch,
+                                 uint32_t record_lines, int32_t match_line, int32_t first_byte, uint64_t record_base, int32_t *status,
+                                 zngamd_bgzf_class_row *class_rows, uint64_t class_cap, zngamd_bgzf_grep_row *rows, uint64_t rows_cap,
+                                 uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_classify_totals *totals);
 
 /* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
  * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM

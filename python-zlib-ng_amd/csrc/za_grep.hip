@@ -8,6 +8,7 @@
 //   za_k_grep_scan    one workgroup: the scan over the tile summaries (delimiters in front, where the open line began, whether it
 //                     has matched), the verdict of every tile's first line, rows in front of every tile, the totals
 //   za_k_grep_emit    one workgroup per tile: the rows of the matching lines that end in it, in order
+//   (za_grep_approx_stage / _compare: what za_k_grep_mark_approx and za_k_grep_classify of za_classify.hip share)
 //   za_k_grep_place   rows and the offsets of za_k_offsets become the slices of za_k_slice_gather, which packs the lines
 // Included by zng_amd.hip behind za_bgzf.hip (za_eq_mask, za_member_in_scratch, ZaBgzfSlice).
 #include "za_common.h"
@@ -240,33 +241,13 @@ __global__ __launch_bounds__(256) void za_k_grep_mark(const uint8_t *__restrict_
 // the non-zero bytes of x as their 0x80 bits (no carry leaves a byte: 0x7f + 0x7f = 0xfe)
 __device__ __forceinline__ uint32_t za_nonzero_bytes(uint32_t x) { return ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x; }
 
-// grid, bits[] and tiles[] as za_k_grep_mark; what differs is how a match bit comes about: a pattern of len bytes starts at p when
-// scratch[p, p + len) differs from it in at most k bytes, holds no delimiter and ends at or in front of text_end (so the window lies in
-// one line's body).  No prefilter: every position is compared with every pattern, four pattern bytes a step.
-//   - The tile and the 255 bytes behind it (a window that starts in its last byte) are staged in LDS as dwords; nothing at or behind
-//     text_end is read, and so nothing at or behind scratch_cap.
-//   - s_stop has a bit per staged byte that no window may hold: a delimiter, or a byte at or behind text_end.  s_before[w] counts the
-//     stop bits in front of bitmap word w, so "no stop bit in [p, p + len)" is two counts that are equal.  It is asked of the positions
-//     whose count stayed within k only.
-//   - A thread takes four adjacent positions a round, so a wave reads 64 adjacent dwords of the text per pattern dword; the loops over
-//     patterns and pattern dwords are the same for a whole wave (they end on ballots), which leaves the pattern words in scalar registers.
-// ptab[q] = {off, len}: the pattern's first DWORD in words[] and its length in bytes; the last dword is padded with zeros.
-__global__ __launch_bounds__(256) void za_k_grep_mark_approx(const uint8_t *__restrict__ scratch, uint64_t scratch_cap, uint64_t text_off, uint64_t text_end,
-                                                             uint64_t tile0, const ZaGrepPat *__restrict__ ptab, const uint32_t *__restrict__ words,
-                                                             uint32_t np, uint32_t delim, uint32_t flags, uint32_t k,
-                                                             ulonglong2 *__restrict__ bits, ZaGrepTile *__restrict__ tiles)
+// Steps 1 and 2 of za_k_grep_mark_approx, shared with za_k_grep_classify (za_classify.hip).  s_d and s_stop were zeroed in front of a
+// barrier.  Every thread of the workgroup calls it (it holds barriers): behind it s_t holds the tile and its overhang, s_d the tile's
+// delimiter bits, s_stop the stop bits and s_before[w] the stop bits in front of bitmap word w.
+__device__ __forceinline__ void za_grep_approx_stage(const uint8_t *__restrict__ scratch, uint64_t scratch_cap, uint64_t text_off, uint64_t text_end, uint64_t base,
+                                                     uint32_t delim, uint32_t *s_t, uint32_t *s_d, uint32_t *s_stop, uint32_t *s_before, uint32_t *s_wsum)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t s_t[ZA_GREP_AP_WORDS];
-    __shared__ uint32_t s_d[512], s_m[512];
-    __shared__ uint32_t s_stop[ZA_GREP_AP_BITS], s_before[ZA_GREP_AP_BITS];
-    __shared__ uint32_t s_wsum[4];
-    __shared__ ZaGrepVerdictLds s_v;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t base = (tile0 + blockIdx.x) * (uint64_t)ZA_GREP_TILE;
-    s_d[tid] = 0; s_d[tid + 256u] = 0; s_m[tid] = 0; s_m[tid + 256u] = 0;
-    for (uint32_t i = tid; i < ZA_GREP_AP_BITS; i += 256u) s_stop[i] = 0;
-    if (tid == 0) { s_v.first = 0xFFFFFFFFu; s_v.last = 0; }
-    __syncthreads();
     const uint32_t pat = delim * 0x01010101u;
     for (uint32_t ch = tid; ch < ZA_GREP_AP_WORDS / 4u; ch += 256u) {       // 16 bytes per thread and round (no barrier in this loop)
         const uint32_t rel = ch * 16u;
@@ -305,6 +286,19 @@ __global__ __launch_bounds__(256) void za_k_grep_mark_approx(const uint8_t *__re
         }
     }
     __syncthreads();
+}
+
+// Step 3: every position of the tile against every pattern.  A window that is within k and holds no stop bit is a match: hit(b, q, d)
+// is told its offset in the tile, the pattern and the distance, and once a round of four positions per thread is through
+// round(rel, mm) is told which of the four matched.  ALL = false: a position that has matched is compared with no further pattern (a
+// bit is all za_k_grep_mark_approx wants); ALL = true: every pattern is compared at every position.  No barrier in here.
+template <bool ALL, typename Hit, typename Round>
+__device__ __forceinline__ void za_grep_approx_compare(const uint8_t *__restrict__ scratch, uint64_t text_off, uint64_t text_end, uint64_t base,
+                                                       const ZaGrepPat *__restrict__ ptab, const uint32_t *__restrict__ words, uint32_t np, uint32_t delim,
+                                                       uint32_t flags, uint32_t k, const uint32_t *s_t, const uint32_t *s_d, const uint32_t *s_stop,
+                                                       const uint32_t *s_before, Hit hit, Round round)
+{
+    const uint32_t tid = threadIdx.x;
     for (uint32_t it = 0; it < 16u; it++) {            // 4 positions per thread and round: 1 KiB per round (no barrier in this loop)
         const uint32_t w = it * 256u + tid, rel = w * 4u;
         const uint64_t g = base + rel;
@@ -324,7 +318,7 @@ __global__ __launch_bounds__(256) void za_k_grep_mark_approx(const uint8_t *__re
         const uint32_t t0 = s_t[w];
         uint32_t mm = 0;
         for (uint32_t q = 0; q < np; q++) {
-            const uint32_t live = alive & ~mm;         // (a position that has matched needs no further pattern)
+            const uint32_t live = ALL ? alive : alive & ~mm;      // (a position that has matched needs no further pattern)
             if (__ballot(live != 0) == 0ull) break;
             const ZaGrepPat pt = ptab[q];
             const uint32_t nw = (pt.len + 3u) >> 2, last80 = 0x80808080u >> (8u * (nw * 4u - pt.len));
@@ -348,11 +342,43 @@ __global__ __launch_bounds__(256) void za_k_grep_mark_approx(const uint8_t *__re
                 const uint32_t b = rel + s, e = b + pt.len;
                 const uint32_t nb = s_before[b >> 5] + (uint32_t)__popc(s_stop[b >> 5] & ((1u << (b & 31u)) - 1u));
                 const uint32_t ne = s_before[e >> 5] + (uint32_t)__popc(s_stop[e >> 5] & ((1u << (e & 31u)) - 1u));
-                if (nb == ne) mm |= 1u << s;
+                if (nb == ne) { mm |= 1u << s; hit(b, q, s == 0u ? c0 : s == 1u ? c1 : s == 2u ? c2 : c3); }
             }
         }
-        if (mm) atomicOr(&s_m[rel >> 5], mm << (rel & 31u));
+        round(rel, mm);
     }
+}
+
+// grid, bits[] and tiles[] as za_k_grep_mark; what differs is how a match bit comes about: a pattern of len bytes starts at p when
+// scratch[p, p + len) differs from it in at most k bytes, holds no delimiter and ends at or in front of text_end (so the window lies in
+// one line's body).  No prefilter: every position is compared with every pattern, four pattern bytes a step.
+//   - The tile and the 255 bytes behind it (a window that starts in its last byte) are staged in LDS as dwords; nothing at or behind
+//     text_end is read, and so nothing at or behind scratch_cap.
+//   - s_stop has a bit per staged byte that no window may hold: a delimiter, or a byte at or behind text_end.  s_before[w] counts the
+//     stop bits in front of bitmap word w, so "no stop bit in [p, p + len)" is two counts that are equal.  It is asked of the positions
+//     whose count stayed within k only.
+//   - A thread takes four adjacent positions a round, so a wave reads 64 adjacent dwords of the text per pattern dword; the loops over
+//     patterns and pattern dwords are the same for a whole wave (they end on ballots), which leaves the pattern words in scalar registers.
+// ptab[q] = {off, len}: the pattern's first DWORD in words[] and its length in bytes; the last dword is padded with zeros.
+__global__ __launch_bounds__(256) void za_k_grep_mark_approx(const uint8_t *__restrict__ scratch, uint64_t scratch_cap, uint64_t text_off, uint64_t text_end,
+                                                             uint64_t tile0, const ZaGrepPat *__restrict__ ptab, const uint32_t *__restrict__ words,
+                                                             uint32_t np, uint32_t delim, uint32_t flags, uint32_t k,
+                                                             ulonglong2 *__restrict__ bits, ZaGrepTile *__restrict__ tiles)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t s_t[ZA_GREP_AP_WORDS];
+    __shared__ uint32_t s_d[512], s_m[512];
+    __shared__ uint32_t s_stop[ZA_GREP_AP_BITS], s_before[ZA_GREP_AP_BITS];
+    __shared__ uint32_t s_wsum[4];
+    __shared__ ZaGrepVerdictLds s_v;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t base = (tile0 + blockIdx.x) * (uint64_t)ZA_GREP_TILE;
+    s_d[tid] = 0; s_d[tid + 256u] = 0; s_m[tid] = 0; s_m[tid + 256u] = 0;
+    for (uint32_t i = tid; i < ZA_GREP_AP_BITS; i += 256u) s_stop[i] = 0;
+    if (tid == 0) { s_v.first = 0xFFFFFFFFu; s_v.last = 0; }
+    __syncthreads();
+    za_grep_approx_stage(scratch, scratch_cap, text_off, text_end, base, delim, s_t, s_d, s_stop, s_before, s_wsum);
+    za_grep_approx_compare<false>(scratch, text_off, text_end, base, ptab, words, np, delim, flags, k, s_t, s_d, s_stop, s_before,
+                                  [](uint32_t, uint32_t, uint32_t) {}, [&](uint32_t rel, uint32_t mm) { if (mm) atomicOr(&s_m[rel >> 5], mm << (rel & 31u)); });
     __syncthreads();
     za_grep_tile_verdicts(s_d, s_m, s_v, flags, bits, tiles);
 }

@@ -11,6 +11,7 @@
 #include "za_bgzf.hip"
 #include "za_grep.hip"
 #include "za_grep_records.hip"
+#include "za_classify.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
 #include "za_batch.hip"
@@ -45,6 +46,9 @@ static_assert(sizeof(zngamd_bgzf_pattern) == sizeof(ZaGrepPat) && sizeof(zngamd_
 static_assert(sizeof(zngamd_bgzf_grep_records_totals) == sizeof(ZaGrepRecTotals) && sizeof(ZaGrepRecTotals) == 64 &&
               offsetof(ZaGrepRecTotals, covered) == offsetof(zngamd_bgzf_grep_records_totals, covered) && sizeof(ZaGrepTotals) == 56 &&
               ZNGAMD_BGZF_GREP_MAX_RECORD_LINES == ZA_GREP_REC_MAX, "bgzf grep records layout");
+static_assert(sizeof(zngamd_bgzf_classify_totals) == sizeof(ZaClsTotals) && offsetof(ZaClsTotals, class_bytes) == offsetof(zngamd_bgzf_classify_totals, class_bytes) &&
+              sizeof(zngamd_bgzf_class_row) == 4 && ZNGAMD_BGZF_CLASSIFY_MAX_CLASSES == ZA_CLS_MAX_CLASSES && ZNGAMD_BGZF_CLASSIFY_GROUP == ZA_CLS_GROUP &&
+              ZNGAMD_BGZF_CLASS_ASSIGNED == ZA_CLS_ASSIGNED && ZNGAMD_BGZF_CLASS_AMBIGUOUS == ZA_CLS_AMBIGUOUS, "bgzf classify layout");
 static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_tabix_name) == sizeof(ZaTbxName) && sizeof(zngamd_tabix_bin) == sizeof(ZaTbxBin) &&
               sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
               sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
@@ -155,6 +159,9 @@ struct zngamd_ctx {
     // bits, line starts, bases | width per line, where header r stands, first / last non-empty line per record, rows, spans
     DevBuf<unsigned long long> fa_x, fa_bw; DevBuf<uint64_t> fa_start; DevBuf<uint32_t> fa_hline, fa_first, fa_last; DevBuf<ZaFaiRow> fa_rows; DevBuf<ZaFaiSpan> fa_spans;
     DevBuf<unsigned long long> gr_start, gr_sel, gr_len; DevBuf<uint8_t> gr_hit;      // records by content (za_grep_records.hip, section 5f.1): line starts; per record selected / bytes (scanned in place) and hit
+    // records by their nearest pattern (za_classify.hip, section 5f.3): the two minima per record; per record class row, length and class;
+    // the table of counts per (class, workgroup); the totals and the first bad record
+    DevBuf<uint32_t> cl_min, cl_row, cl_len; DevBuf<uint8_t> cl_cls, cl_tot; DevBuf<unsigned long long> cl_tab;
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -307,6 +314,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->fa_x.release(); c->fa_bw.release(); c->fa_start.release(); c->fa_hline.release(); c->fa_first.release(); c->fa_last.release(); c->fa_rows.release(); c->fa_spans.release();
     c->gp_par.release(); c->gp_bits.release(); c->gp_tiles.release(); c->gp_carry.release(); c->gp_rows.release(); c->gp_lens.release();
     c->gr_start.release(); c->gr_sel.release(); c->gr_len.release(); c->gr_hit.release();
+    c->cl_min.release(); c->cl_row.release(); c->cl_len.release(); c->cl_cls.release(); c->cl_tot.release(); c->cl_tab.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -3697,12 +3705,28 @@ static bool grep_patterns_ok(const uint8_t *patterns, uint32_t patterns_len, con
 #define ZA_GREP_PAR_BLOB  (ZA_GREP_PAR_TABLE + ZA_GREP_MAX_PAT * (uint32_t)sizeof(ZaGrepPat))
 #define ZA_GREP_APAR_WORDS (ZA_GREP_MAX_PAT * (uint32_t)sizeof(ZaGrepPat))         // with mismatches: pattern table, padded patterns
 
+// the parameter block of za_k_grep_mark_approx and za_k_grep_classify: the table {first dword, length}, then every pattern padded with zeros to whole dwords
+static void grep_approx_params(std::vector<uint8_t> &par, const uint8_t *patterns, const zngamd_bgzf_pattern *table, uint32_t n_patterns)
+{
+    size_t nwords = 0;
+    for (uint32_t i = 0; i < n_patterns; i++) nwords += (table[i].len + 3u) / 4u;
+    par.assign(ZA_GREP_APAR_WORDS + nwords * 4u, 0);
+    ZaGrepPat *pt = (ZaGrepPat *)par.data();
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < n_patterns; i++) {
+        pt[i].off = at; pt[i].len = table[i].len;
+        memcpy(par.data() + ZA_GREP_APAR_WORDS + (size_t)at * 4u, patterns + table[i].off, table[i].len);
+        at += (table[i].len + 3u) / 4u;
+    }
+}
+
 // decode, cover, mark (max_mismatch 0: za_k_grep_mark; more: za_k_grep_mark_approx), scan, and the host waits for the scan's totals: the first `totals_len` bytes of ZaGrepTotals go to `totals`.
 // After it every tile has its bits, its summary and its carry (gp_bits, gp_tiles, gp_carry), unless covered is 0.
+// marks = false (with max_mismatch 0): the delimiters alone -- za_k_grep_mark with an empty prefilter and no pattern, so no line matches.
 static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
                                 uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
                                 uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap,
-                                int32_t *d_status, void *totals, size_t totals_len)
+                                int32_t *d_status, void *totals, size_t totals_len, bool marks = true)
 {
     if (text_off > text_end || text_end > scratch_cap) return fail(c, ZNGAMD_E_ARG, "the text lies outside the scratch");
     if (text_end - text_off >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "a text of 4 GiB or more");
@@ -3713,26 +3737,14 @@ static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_
         // the parameter block: a bit per pair of bytes that opens a pattern (a one-byte pattern: every pair with that first byte)
         par.assign((size_t)ZA_GREP_PAR_BLOB + patterns_len + 1u, 0);
         uint32_t *pairs = (uint32_t *)par.data();
-        for (uint32_t i = 0; i < n_patterns; i++) {
+        for (uint32_t i = 0; i < (marks ? n_patterns : 0u); i++) {
             const uint8_t *p = patterns + table[i].off;
             if (table[i].len == 1) for (uint32_t b = 0; b < 256u; b++) { const uint32_t pr = p[0] | b << 8; pairs[pr >> 5] |= 1u << (pr & 31u); }
             else { const uint32_t pr = p[0] | (uint32_t)p[1] << 8; pairs[pr >> 5] |= 1u << (pr & 31u); }
         }
         memcpy(par.data() + ZA_GREP_PAR_TABLE, table, (size_t)n_patterns * sizeof(ZaGrepPat));
         memcpy(par.data() + ZA_GREP_PAR_BLOB, patterns, patterns_len);
-    } else {
-        // the parameter block of za_k_grep_mark_approx: the table {first dword, length}, then every pattern padded with zeros to whole dwords
-        size_t nwords = 0;
-        for (uint32_t i = 0; i < n_patterns; i++) nwords += (table[i].len + 3u) / 4u;
-        par.assign(ZA_GREP_APAR_WORDS + nwords * 4u, 0);
-        ZaGrepPat *pt = (ZaGrepPat *)par.data();
-        uint32_t at = 0;
-        for (uint32_t i = 0; i < n_patterns; i++) {
-            pt[i].off = at; pt[i].len = table[i].len;
-            memcpy(par.data() + ZA_GREP_APAR_WORDS + (size_t)at * 4u, patterns + table[i].off, table[i].len);
-            at += (table[i].len + 3u) / 4u;
-        }
-    }
+    } else grep_approx_params(par, patterns, table, n_patterns);
     HIPCHK(c, c->gp_par.ensure(par.size())); HIPCHK(c, c->gp_bits.ensure((size_t)ntiles * 256u + 1u)); HIPCHK(c, c->gp_tiles.ensure(ntiles + 1u));
     HIPCHK(c, c->gp_carry.ensure(ntiles + 1u));
     HIPCHK(c, hipMemcpyAsync(c->gp_par.p, par.data(), par.size(), hipMemcpyHostToDevice, c->stream));
@@ -3745,8 +3757,8 @@ static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_
                                         text_off, text_end, d_cover);
       if (ntiles && !max_mismatch)
           hipLaunchKernelGGL(za_k_grep_mark, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
-                             (const uint32_t *)c->gp_par.p, (const ZaGrepPat *)(c->gp_par.p + ZA_GREP_PAR_TABLE), c->gp_par.p + ZA_GREP_PAR_BLOB, n_patterns,
-                             delim, flags, c->gp_bits.p, c->gp_tiles.p);
+                             (const uint32_t *)c->gp_par.p, (const ZaGrepPat *)(c->gp_par.p + ZA_GREP_PAR_TABLE), c->gp_par.p + ZA_GREP_PAR_BLOB,
+                             marks ? n_patterns : 0u, delim, flags, c->gp_bits.p, c->gp_tiles.p);
       else if (ntiles)
           hipLaunchKernelGGL(za_k_grep_mark_approx, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
                              (const ZaGrepPat *)c->gp_par.p, (const uint32_t *)(c->gp_par.p + ZA_GREP_APAR_WORDS), n_patterns, delim, flags, max_mismatch,
@@ -4011,6 +4023,147 @@ try {
     HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return d2h_payload(c, out, c->bg_out.p, totals->bytes);
+} ZA_ABI_GUARD
+
+// ---- records by their nearest pattern (za_classify.hip)
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool classify_args_ok(const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags,
+                             uint32_t max_mismatch, uint32_t record_lines, int32_t match_line, int32_t first_byte, const zngamd_bgzf_classify_totals *totals)
+{
+    if (!totals || (flags & ~(ZNGAMD_BGZF_GREP_LINE_START | ZNGAMD_BGZF_GREP_FINAL | ZNGAMD_BGZF_CLASSIFY_GROUP))) return false;
+    if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim, max_mismatch) || !grep_records_ok(record_lines, match_line, first_byte)) return false;
+    for (uint32_t i = 1; i < n_patterns; i++)                 // two patterns with the same bytes: no record could ever be assigned to either
+        for (uint32_t j = 0; j < i; j++)
+            if (table[i].len == table[j].len && !memcmp(patterns + table[i].off, patterns + table[j].off, table[i].len)) return false;
+    return true;
+}
+
+// the lines pass for the delimiters alone, [the host waits for the line count], lines, classify, eval, hist, the scan, close, [the host
+// waits for the totals], then the class rows and, with _GROUP, scatter and pack.  own: the host form (class rows stay in cl_row; rows and
+// records go to the context's buffers, as long as the totals say).
+static int bgzf_classify_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
+                             uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                             uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint32_t k, int32_t match_line, int32_t first_byte, uint64_t record_base,
+                             uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_class_row *d_class, uint64_t class_cap, ZaGrepRow *d_rows,
+                             uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own, zngamd_bgzf_classify_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    const uint32_t ncls = n_patterns + 2u;
+    totals->n_classes = ncls;
+    ZaGrepTotals lt;
+    const uint32_t lflags = flags & (ZA_GREP_LINE_START | ZA_GREP_FINAL);
+    const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim,
+                                       flags & ZA_GREP_FINAL, 0, 0, d_scratch, scratch_cap, d_status, &lt, sizeof lt, false);
+    if (r) return r;
+    totals->tail_off = text_off;
+    if (!lt.covered) return ZNGAMD_OK;
+    totals->covered = 1;
+    const bool fin = (flags & ZA_GREP_FINAL) != 0, group = (flags & ZA_CLS_GROUP) != 0;
+    const uint64_t lines = lt.seen, nrec = fin ? (lines + k - 1u) / k : lines / k;
+    if (fin) totals->tail_off = text_end;
+    if (!nrec) return ZNGAMD_OK;                                  // (without FINAL: fewer than k lines have ended, the open record starts at text_off)
+    const uint64_t tile0 = text_off / ZA_GREP_TILE;
+    const uint32_t ntiles = (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull);      // (a line was decided: the text is not empty)
+    const uint32_t grid = (uint32_t)((nrec + 255u) / 256u), nwg = (uint32_t)((nrec + ZA_CLS_WG_RECORDS - 1u) / ZA_CLS_WG_RECORDS);
+    const uint64_t ntab = (uint64_t)ncls * nwg;
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_min.ensure(2u * nrec)); HIPCHK(c, c->cl_row.ensure(nrec)); HIPCHK(c, c->cl_len.ensure(nrec));
+    HIPCHK(c, c->cl_cls.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab)); HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u));
+    HIPCHK(c, c->cl_tot.ensure(sizeof(ZaClsTotals) + 16u));
+    std::vector<uint8_t> &par = c->gp_host;                      // (the lines pass has been waited for: its block is no longer read)
+    grep_approx_params(par, patterns, table, n_patterns);
+    HIPCHK(c, c->gp_par.ensure(par.size()));
+    HIPCHK(c, hipMemcpyAsync(c->gp_par.p, par.data(), par.size(), hipMemcpyHostToDevice, c->stream));
+    const ZaGrepTotals *d_lt = (const ZaGrepTotals *)c->d_small;
+    ZaClsTotals *d_tot = (ZaClsTotals *)c->cl_tot.p;
+    unsigned long long *d_bad = (unsigned long long *)(c->cl_tot.p + sizeof(ZaClsTotals)), *d_sum = d_bad + 1;
+    uint32_t *d_lo = c->cl_min.p, *d_hi = c->cl_min.p + nrec;
+    HIPCHK(c, hipMemsetAsync(c->cl_min.p, 0xFF, 2u * nrec * 4u, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_tot, 0, sizeof(ZaClsTotals), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_grep_rec_lines, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_lt, ntiles, tile0, text_off,
+                         text_end, lflags, k, match_line, c->gr_start.p, lines + 1u, (uint8_t *)nullptr, 0ull);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_grep_classify, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
+                         (const ZaGrepPat *)c->gp_par.p, (const uint32_t *)(c->gp_par.p + ZA_GREP_APAR_WORDS), n_patterns, delim, lflags, max_mismatch,
+                         c->gp_carry.p, k, match_line, nrec, d_lo, d_hi);
+      hipLaunchKernelGGL(za_k_cls_eval, dim3(grid), dim3(256), 0, c->stream, d_scratch, text_off, text_end, c->gr_start.p, lines, d_lo, d_hi, nrec, k,
+                         n_patterns, first_byte, c->cl_row.p, c->cl_cls.p, c->cl_len.p, d_bad);
+      hipLaunchKernelGGL(za_k_cls_hist, dim3(nwg), dim3(ZA_CLS_WG_RECORDS), 0, c->stream, c->cl_cls.p, c->cl_len.p, nrec, ncls, nwg, c->cl_tab.p, d_tot);
+      tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
+      hipLaunchKernelGGL(za_k_cls_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, text_end, record_base, ncls, d_bad, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (totals->bad) return ZNGAMD_OK;
+    const uint64_t n = totals->seen;
+    if (own) {
+        if (group) { HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(totals->bytes + 64)); d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; }
+    } else if (n > class_cap || (group && (n > rows_cap || totals->bytes > out_cap))) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    else HIPCHK(c, hipMemcpyAsync(d_class, c->cl_row.p, (size_t)n * 4u, hipMemcpyDeviceToDevice, c->stream));
+    if (!group) return ZNGAMD_OK;
+    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_cls_scatter, dim3(nwg), dim3(ZA_CLS_WG_RECORDS), 0, c->stream, c->cl_cls.p, c->cl_row.p, c->cl_len.p, c->gr_start.p, nrec, k, ncls, nwg,
+                         c->cl_tab.p, record_base, d_rows, n, c->gp_lens.p);
+      bgzf_grep_pack(c, d_members, n_members, d_scratch, scratch_cap, d_status, d_rows, n, d_out, totals->bytes); }
+    c->bgzf_stats[2] += n;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_classify_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                     uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                                     int delim, uint32_t flags, uint32_t max_mismatch, uint32_t record_lines, int32_t match_line, int32_t first_byte,
+                                     uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_class_row *d_class,
+                                     uint64_t class_cap, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap,
+                                     zngamd_bgzf_classify_totals *totals)
+try {
+    if (!classify_args_ok(patterns, patterns_len, table, n_patterns, delim, flags, max_mismatch, record_lines, match_line, first_byte, totals)) return ZNGAMD_E_ARG;
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_class && class_cap) || (!d_rows && rows_cap) ||
+        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_classify_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, patterns, patterns_len, table,
+                              n_patterns, (uint32_t)delim, flags, max_mismatch, record_lines, match_line, first_byte, record_base, (uint8_t *)d_scratch,
+                              scratch_cap, d_status, d_class, class_cap, (ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_classify_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                                 uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                                 int delim, uint32_t flags, uint32_t max_mismatch, uint32_t record_lines, int32_t match_line, int32_t first_byte,
+                                 uint64_t record_base, int32_t *status, zngamd_bgzf_class_row *cls, uint64_t class_cap, zngamd_bgzf_grep_row *rows,
+                                 uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_classify_totals *totals)
+try {
+    if (!classify_args_ok(patterns, patterns_len, table, n_patterns, delim, flags, max_mismatch, record_lines, match_line, first_byte, totals)) return ZNGAMD_E_ARG;
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!cls && class_cap) || (!rows && rows_cap) || (!out && out_cap) ||
+        (alloc && (cls || rows || out))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    r = bgzf_classify_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, (uint32_t)delim, flags,
+                          max_mismatch, record_lines, match_line, first_byte, record_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, nullptr, 0,
+                          true, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t n = totals->seen;
+    const bool group = (flags & ZNGAMD_BGZF_CLASSIFY_GROUP) != 0;
+    if (!totals->covered || totals->bad || !n) return ZNGAMD_OK;
+    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now: class rows, rows, bytes
+        cls = (zngamd_bgzf_class_row *)alloc(user, n * sizeof(zngamd_bgzf_class_row));
+        if (group) { rows = cls ? (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow)) : nullptr; out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr; }
+        if (!cls || (group && (!rows || !out))) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (n > class_cap || (group && (n > rows_cap || totals->bytes > out_cap))) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    HIPCHK(c, hipMemcpyAsync(cls, c->cl_row.p, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
+    if (group) HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return group ? d2h_payload(c, out, c->bg_out.p, totals->bytes) : ZNGAMD_OK;
 } ZA_ABI_GUARD
 
 // ---- fields of a line (za_tabix.hip)

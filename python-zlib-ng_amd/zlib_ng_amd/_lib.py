@@ -84,6 +84,7 @@ SYMBOLS = [
     "zngamd_bgzf_count_dev", "zngamd_bgzf_count", "zngamd_bgzf_line_positions_dev", "zngamd_bgzf_line_positions", "zngamd_bgzf_read_lines_dev",
     "zngamd_bgzf_read_lines", "zngamd_bgzf_grep_dev", "zngamd_bgzf_grep", "zngamd_bgzf_grep_records_dev", "zngamd_bgzf_grep_records",
     "zngamd_bgzf_grep_approx_dev", "zngamd_bgzf_grep_approx", "zngamd_bgzf_grep_records_approx_dev", "zngamd_bgzf_grep_records_approx",
+    "zngamd_bgzf_classify_records_dev", "zngamd_bgzf_classify_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
@@ -164,6 +165,21 @@ class BgzfGrepRecordsTotals(C.Structure):      # zngamd_bgzf_grep_records_totals
     @property
     def matched(self):                         # (the name the window loop of bgzf.grep reads)
         return self.selected
+
+
+BGZF_CLASSIFY_GROUP, BGZF_CLASSIFY_MAX_CLASSES = 16, 66      # ZNGAMD_BGZF_CLASSIFY_*
+BGZF_CLASS_ASSIGNED, BGZF_CLASS_AMBIGUOUS = 1, 2               # ZNGAMD_BGZF_CLASS_*: a class row's flags (0: unassigned)
+CLASS_ROW_DTYPE = np.dtype([("pattern", "u1"), ("other", "u1"), ("distance", "u1"), ("flags", "u1")])      # zngamd_bgzf_class_row
+
+
+class BgzfClassifyTotals(C.Structure):         # zngamd_bgzf_classify_totals
+    _fields_ = [("seen", C.c_uint64), ("bytes", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64), ("bad_src", C.c_uint64),
+                ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("n_classes", C.c_uint32),
+                ("class_records", C.c_uint64 * BGZF_CLASSIFY_MAX_CLASSES), ("class_bytes", C.c_uint64 * BGZF_CLASSIFY_MAX_CLASSES)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is classified)
+        return self.seen
 
 
 BGZF_TABIX_FINAL, BGZF_FETCH_COUNT_ONLY, BGZF_FETCH_MAX_REGIONS = 4, 8, 4096      # ZNGAMD_BGZF_TABIX_FINAL, ZNGAMD_BGZF_FETCH_*
@@ -330,6 +346,11 @@ def load():
                 for form in ("", "_dev"):
                     exact = getattr(L, name + form).argtypes
                     getattr(L, name + "_approx" + form).argtypes = exact[:13] + [C.c_uint32] + exact[13:]
+        if hasattr(L, "zngamd_bgzf_classify_records"):      # the records calls with mismatches, class rows in front of the rows
+            exact = L.zngamd_bgzf_grep_records_approx_dev.argtypes
+            L.zngamd_bgzf_classify_records_dev.argtypes = exact[:21] + [vp, C.c_uint64] + exact[21:]
+            exact = L.zngamd_bgzf_grep_records_approx.argtypes
+            L.zngamd_bgzf_classify_records.argtypes = exact[:19] + [vp, C.c_uint64] + exact[19:]
         if hasattr(L, "zngamd_bgzf_tabix"):
             L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
                                                 C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1300,6 +1321,74 @@ class Context:
                                    flags, (mismatches, record_lines, match_line, first_byte, record_base), caps)
         return self._bgzf_grep(self.L.zngamd_bgzf_grep_records, BgzfGrepRecordsTotals(), data, members, text_off, text_end, blob, table, delim, flags,
                                (record_lines, match_line, first_byte, record_base), caps)
+
+    def bgzf_classify_records(self, data, members, text_off, text_end, blob, table, delim, flags, mismatches, record_lines, match_line=-1,
+                              first_byte=-1, record_base=0, caps=None):
+        """zngamd_bgzf_classify_records: every record's nearest pattern -> (code, block statuses, totals (BgzfClassifyTotals), class rows
+        (CLASS_ROW_DTYPE, one per record in record order), rows (GREP_ROW_DTYPE, ordered by class then number; reserved: the class row),
+        the records packed in that order); rows and records only with BGZF_CLASSIFY_GROUP in flags; nothing comes back when totals.bad
+        is set.  caps None: the arrays are allocated once the engine knows their sizes; (class rows, rows, bytes): buffers of those sizes,
+        and code is BUF_ERROR (nothing written) when the result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        table = np.ascontiguousarray(table, np.uint32)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfClassifyTotals()
+        group = bool(flags & BGZF_CLASSIFY_GROUP)
+        box = []
+
+        def alloc(_user, nbytes):
+            if not box:
+                arr = np.empty(nbytes // CLASS_ROW_DTYPE.itemsize, CLASS_ROW_DTYPE)
+            elif len(box) == 1:
+                arr = np.empty(nbytes // GREP_ROW_DTYPE.itemsize, GREP_ROW_DTYPE)
+            else:
+                obj, addr = _new_bytes(nbytes)
+                box.append(obj)
+                return addr.value
+            box.append(arr)
+            return arr.ctypes.data
+
+        if caps is None:
+            cp, ccap, rp, rcap, op, ocap, fn = None, 0, None, 0, None, 0, ALLOC_FN(alloc)
+        else:
+            ccap, rcap, ocap = caps
+            cls, rows = np.zeros(max(1, ccap), CLASS_ROW_DTYPE), np.zeros(max(1, rcap), GREP_ROW_DTYPE)
+            out, op = _new_bytes(ocap)
+            cp, rp, fn = C.c_void_p(cls.ctypes.data) if ccap else None, C.c_void_p(rows.ctypes.data) if rcap else None, ALLOC_FN()
+            if not ocap:
+                op = None
+        bp, bkeep = _addr(blob)
+        r = self._chk(self.L.zngamd_bgzf_classify_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                          text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table), delim, flags,
+                                                          mismatches, record_lines, match_line, first_byte, record_base, C.c_void_p(st.ctypes.data),
+                                                          cp, ccap, rp, rcap, op, ocap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and tot.covered and tot.seen and not tot.bad
+        if caps is None:
+            cls_out = box[0] if got else np.empty(0, CLASS_ROW_DTYPE)
+            rows_out = box[1] if got and group else np.empty(0, GREP_ROW_DTYPE)
+            packed = box[2] if got and group else b""
+        else:
+            cls_out = cls[:tot.seen] if got else np.empty(0, CLASS_ROW_DTYPE)
+            rows_out = rows[:tot.seen] if got and group else np.empty(0, GREP_ROW_DTYPE)
+            packed = _take(out, tot.bytes) if got and group else b""
+        return r, st[:nm], tot, cls_out, rows_out, packed
+
+    def bgzf_classify_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, mismatches, record_lines,
+                                  match_line, first_byte, record_base, d_scratch, scratch_cap, d_status, d_class, class_cap, d_rows, rows_cap, d_out,
+                                  out_cap):
+        """zngamd_bgzf_classify_records_dev on device pointers (the patterns: host memory) -> (code, totals); class rows, rows and records
+        stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        table = np.ascontiguousarray(table, np.uint32)
+        tot = BgzfClassifyTotals()
+        bp, bkeep = _addr(blob)
+        r = self._chk(self.L.zngamd_bgzf_classify_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob),
+                                                              C.c_void_p(table.ctypes.data), len(table), delim, flags, mismatches, record_lines,
+                                                              match_line, first_byte, record_base, v(d_scratch), scratch_cap, v(d_status),
+                                                              v(d_class), class_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
+                      (OK, BUF_ERROR))
+        return r, tot
 
     def _bgzf_grep(self, fn_c, tot, data, members, text_off, text_end, blob, table, delim, flags, extra, caps):
         nm = len(members)

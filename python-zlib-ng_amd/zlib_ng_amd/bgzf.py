@@ -51,6 +51,7 @@ from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
+           "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
 BadGzipFile = zlib_ng.BadGzipFile
@@ -691,9 +692,12 @@ def _grep_record_args(record_lines, match_line, first_byte):
     return k, j, b
 
 
-def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line, records=None, mismatches=0):
+def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line, records=None, mismatches=0,
+               classify=None):
     """The window loop of grep() and, with records = (record_lines, match_line, first_byte, allow_short), of grep_records(): then the
-    unit that is counted, numbered, carried over a window's end and bounded by max_line is the record."""
+    unit that is counted, numbered, carried over a window's end and bounded by max_line is the record.  classify (with records): a
+    _ClassifySink -- every window's records are not selected but assigned to their nearest pattern (classify_records(), demux()), the
+    sink takes what each window gives, and what its finish() returns is the result."""
     pats, delimiter = _grep_patterns(patterns, delimiter)
     mismatches = _grep_mismatches(mismatches, pats)
     approx = {"mismatches": mismatches} if mismatches else {}      # (0: the engine is called with the arguments it always had)
@@ -744,7 +748,10 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
                 raise BadGzipFile(f"BGZF block {nblocks + bad} at offset {c_next + int(coffs[bad])}: bad block header or block size")
             cend = int(coffs[n_use - 1] + csizes[n_use - 1]) if n_use else 0
             wflags = flags | (_lib.BGZF_GREP_FINAL if final else 0)
-            if records is None:
+            if classify is not None:
+                _, status, tot, cls_rows, rows, packed = ctx.bgzf_classify_records(data[:cend], members, text_off, text_end, blob, table, delimiter[0],
+                                                                                   wflags | classify.flags, mismatches, rec_k, rec_j, rec_b, line_base)
+            elif records is None:
                 _, status, tot, rows, packed = ctx.bgzf_grep(data[:cend], members, text_off, text_end, blob, table, delimiter[0], wflags, line_base, **approx)
             else:
                 _, status, tot, rows, packed = ctx.bgzf_grep_records(data[:cend], members, text_off, text_end, blob, table, delimiter[0], wflags,
@@ -766,7 +773,9 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
                 if tot.short_lines and not records[3]:
                     raise ValueError(f"record {line_base + tot.seen - 1}, the last one, has {tot.short_lines} of {rec_k} lines (allow_short)")
             searched, line_base, matched = searched + tot.seen, line_base + tot.seen, matched + tot.matched
-            if len(rows):
+            if classify is not None:
+                classify.window(tot, cls_rows, packed)
+            elif len(rows):
                 numbers.append(rows["number"].astype(np.int64))
                 voffsets.append(voffsets_of(rows["src_off"].astype(np.int64)))
                 lengths.append(rows["len"].astype(np.int64))
@@ -785,6 +794,8 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
         if buf is not None:
             del mv
             _lib.give_buffer(buf)
+    if classify is not None:
+        return classify.finish(searched)
     if count:
         return matched if max_count is None else min(matched, int(max_count))
     numbers = np.concatenate(numbers) if numbers else np.empty(0, np.int64)
@@ -852,6 +863,160 @@ def grep_records(file, patterns, record_lines, *, match_line=None, first_byte=No
                                 max_record=max_record, allow_short=allow_short, mismatches=mismatches)
     return _grep_file(file, None, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_record, max_record,
                       (record_lines, match_line, first_byte, allow_short), mismatches)
+
+
+# ---- records by their nearest pattern
+UNASSIGNED, AMBIGUOUS = -1, -2                # ClassifyResult.pattern for a record that no pattern is near / that two patterns are equally near
+
+
+class ClassifyResult:
+    """What classify_records() found, one entry per searched record in file order: pattern (int16: the index of the one nearest
+    pattern, UNASSIGNED or AMBIGUOUS), distance (uint8: the mismatches of the nearest window, 255 for UNASSIGNED), tie (int16, (n, 2):
+    the lowest and the highest index among the nearest patterns -- they differ where the record is AMBIGUOUS, both are the pattern where
+    it is assigned and -1 where it is UNASSIGNED); counts (int64, n_patterns + 2: records per pattern, then the ambiguous, then the
+    unassigned ones); searched = len(); first_record: the number of entry 0."""
+
+    def __init__(self, pattern, distance, tie, counts, first_record=0):
+        self.pattern = np.asarray(pattern, np.int16)
+        self.distance = np.asarray(distance, np.uint8)
+        self.tie = np.asarray(tie, np.int16).reshape(-1, 2)
+        self.counts = np.asarray(counts, np.int64)
+        self.searched = len(self.pattern)
+        self.first_record = int(first_record)
+        if len(self.distance) != self.searched or len(self.tie) != self.searched:
+            raise ValueError("ClassifyResult: arrays of different lengths")
+
+    def __len__(self):
+        return self.searched
+
+    def __repr__(self):
+        return f"<ClassifyResult: {self.searched} records, {int(self.counts[:-2].sum())} assigned, {int(self.counts[-2])} ambiguous>"
+
+
+class _ClassifySink:
+    """what _grep_file hands a window's classes to: the class rows are kept (classify_records) or, with writers, every class's bytes go
+    to its writer (demux; None: the class is dropped)"""
+
+    def __init__(self, n_patterns, first_record, writers=None):
+        self.flags = _lib.BGZF_CLASSIFY_GROUP if writers is not None else 0
+        self.writers, self.first_record = writers, int(first_record)
+        self.counts = np.zeros(n_patterns + 2, np.int64)
+        self.rows = []
+
+    def window(self, tot, cls_rows, packed):
+        n = len(self.counts)
+        self.counts += np.frombuffer(tot.class_records, np.uint64, n).astype(np.int64)
+        if self.writers is None:
+            if len(cls_rows):
+                self.rows.append(cls_rows)
+            return
+        at = 0
+        with memoryview(packed) as mv:
+            for w, nbytes in zip(self.writers, np.frombuffer(tot.class_bytes, np.uint64, n).tolist()):
+                if w is not None and nbytes:
+                    w.write(mv[at:at + nbytes])
+                at += nbytes
+        if at != len(packed):
+            raise RuntimeError("classify: the classes' bytes do not add up to the records")
+
+    def finish(self, searched):
+        if self.writers is not None:
+            return self.counts
+        rows = np.concatenate(self.rows) if self.rows else np.empty(0, _lib.CLASS_ROW_DTYPE)
+        flags = rows["flags"]
+        pattern = np.where(flags == _lib.BGZF_CLASS_ASSIGNED, rows["pattern"].astype(np.int16),
+                           np.where(flags == _lib.BGZF_CLASS_AMBIGUOUS, np.int16(AMBIGUOUS), np.int16(UNASSIGNED))).astype(np.int16)
+        tie = np.stack([rows["pattern"], rows["other"]], 1).astype(np.int16)
+        tie[flags == 0] = -1
+        return ClassifyResult(pattern, rows["distance"], tie, self.counts, self.first_record)
+
+
+def _classify_patterns(patterns, delimiter):
+    """the patterns of classify_records() and demux(): those of grep(), no two of them the same (ValueError)"""
+    pats, delimiter = _grep_patterns(patterns, delimiter)
+    if len(set(pats)) != len(pats):
+        raise ValueError("two patterns are the same bytes: no record could be assigned to either (duplicate patterns)")
+    return pats
+
+
+def classify_records(file, patterns, record_lines, *, match_line=None, first_byte=None, delimiter=b"\n", line_start=False, start=None,
+                     stop=None, first_record=0, max_record=64 << 20, allow_short=False, mismatches=0):
+    """Every record's NEAREST pattern, in one pass over the file: what a demultiplexer asks of its barcodes.  Records, patterns,
+    match_line, first_byte, line_start, start, stop, first_record, max_record, allow_short and the errors are those of grep_records();
+    a window of a pattern's length counts by the rule of mismatches=k there (inside one line's body, at most k bytes substituted,
+    0 <= k <= 16 and less than the shortest pattern's length; 0 is exact assignment).  For a record the distance to a pattern is the
+    smallest over the windows of its lines that count; the record is
+      assigned     to the one pattern at the smallest distance,
+      AMBIGUOUS    when two or more patterns are at that distance (tie names the lowest and the highest of them),
+      UNASSIGNED   when no pattern is within k.
+    Two patterns with the same bytes are a ValueError; one that is a prefix of another is allowed.  -> a ClassifyResult; four bytes
+    per record leave the device.  There is no invert and no count: counts holds every class's size."""
+    if _is_path(file):
+        with _builtin_open(file, "rb") as f:
+            return classify_records(f, patterns, record_lines, match_line=match_line, first_byte=first_byte, delimiter=delimiter,
+                                    line_start=line_start, start=start, stop=stop, first_record=first_record, max_record=max_record,
+                                    allow_short=allow_short, mismatches=mismatches)
+    return _classify_file(file, None, patterns, record_lines, match_line, first_byte, delimiter, line_start, start, stop, first_record,
+                          max_record, allow_short, mismatches, None)
+
+
+def _classify_file(fp, ctx, patterns, record_lines, match_line, first_byte, delimiter, line_start, start, stop, first_record, max_record,
+                   allow_short, mismatches, writers):
+    pats = _classify_patterns(patterns, delimiter)
+    sink = _ClassifySink(len(pats), first_record, writers)
+    return _grep_file(fp, ctx, pats, delimiter, False, line_start, False, None, start, stop, first_record, max_record,
+                      (record_lines, match_line, first_byte, allow_short), mismatches, sink)
+
+
+def _demux_file(fp, ctx, patterns, outputs, record_lines, ambiguous, unassigned, compresslevel, block_size, match_line, first_byte, delimiter,
+                line_start, start, stop, first_record, max_record, allow_short, mismatches):
+    pats = _classify_patterns(patterns, delimiter)
+    if _is_path(outputs) or hasattr(outputs, "write"):
+        outputs = [outputs]
+    outputs = list(outputs)
+    if len(outputs) != len(pats):
+        raise ValueError(f"demux takes one output per pattern: {len(pats)} patterns, {len(outputs)} outputs")
+    _grep_mismatches(mismatches, pats)
+    _grep_record_args(record_lines, match_line, first_byte)
+    _check_block_size(block_size)
+    writers = []
+    try:
+        for out in outputs + [ambiguous, unassigned]:
+            writers.append(None if out is None else BgzfWriter(out, "wb", compresslevel, block_size=block_size))
+        counts = _classify_file(fp, ctx, pats, record_lines, match_line, first_byte, delimiter, line_start, start, stop, first_record,
+                                max_record, allow_short, mismatches, writers)
+    except Exception as e:
+        for w in writers:
+            if w is not None:
+                try:
+                    w.close()
+                except Exception:
+                    pass
+        note = "demux: the outputs written so far were closed and are incomplete"
+        e.args = ((f"{e.args[0]} ({note})",) + e.args[1:]) if e.args and isinstance(e.args[0], str) else e.args + (note,)
+        raise
+    for w in writers:
+        if w is not None:
+            w.close()
+    return counts
+
+
+def demux(file, patterns, outputs, record_lines=4, *, ambiguous=None, unassigned=None, compresslevel=6, block_size=MAX_BLOCK_INPUT,
+          match_line=None, first_byte=None, delimiter=b"\n", line_start=False, start=None, stop=None, first_record=0, max_record=64 << 20,
+          allow_short=False, mismatches=0):
+    """Split a BGZF file of records by their nearest pattern (the rule of classify_records(), whose keywords these are) in ONE pass:
+    outputs is one path or writable binary file per pattern (a wrong count: ValueError); ambiguous and unassigned are a path, a file, or
+    None to drop those records.  Every output is written through a BgzfWriter (compresslevel, block_size): a complete BGZF file with
+    its EOF block whose decompressed bytes are exactly the records of its class, whole, in the order of the input.  -> counts (int64,
+    n_patterns + 2: records per pattern, then the ambiguous, then the unassigned ones; dropped records are counted too).  If anything
+    is raised the outputs written so far are closed, and the error says that they are incomplete."""
+    if _is_path(file):
+        with _builtin_open(file, "rb") as f:
+            return demux(f, patterns, outputs, record_lines, ambiguous=ambiguous, unassigned=unassigned, compresslevel=compresslevel,
+                         block_size=block_size, match_line=match_line, first_byte=first_byte, delimiter=delimiter, line_start=line_start,
+                         start=start, stop=stop, first_record=first_record, max_record=max_record, allow_short=allow_short, mismatches=mismatches)
+    return _demux_file(file, None, patterns, outputs, record_lines, ambiguous, unassigned, compresslevel, block_size, match_line, first_byte,
+                       delimiter, line_start, start, stop, first_record, max_record, allow_short, mismatches)
 
 
 # ---- lines by region (DESIGN.md section 5g): a tabix index built on the GPU, and the rows of a region filtered there
@@ -2322,6 +2487,35 @@ class BgzfReader(io.BufferedIOBase):
         try:
             return _grep_file(self._fp, self._ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_record,
                               max_record, (record_lines, match_line, first_byte, allow_short), mismatches)
+        finally:
+            self._fp.seek(at)
+
+    def classify_records(self, patterns, record_lines, *, match_line=None, first_byte=None, delimiter=b"\n", line_start=False, start=None,
+                         stop=None, first_record=0, max_record=64 << 20, allow_short=False, mismatches=0):
+        """bgzf.classify_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("classify_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _classify_file(self._fp, self._ctx, patterns, record_lines, match_line, first_byte, delimiter, line_start, start, stop,
+                                  first_record, max_record, allow_short, mismatches, None)
+        finally:
+            self._fp.seek(at)
+
+    def demux(self, patterns, outputs, record_lines=4, *, ambiguous=None, unassigned=None, compresslevel=6, block_size=MAX_BLOCK_INPUT,
+              match_line=None, first_byte=None, delimiter=b"\n", line_start=False, start=None, stop=None, first_record=0, max_record=64 << 20,
+              allow_short=False, mismatches=0):
+        """bgzf.demux() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("demux() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _demux_file(self._fp, self._ctx, patterns, outputs, record_lines, ambiguous, unassigned, compresslevel, block_size, match_line,
+                               first_byte, delimiter, line_start, start, stop, first_record, max_record, allow_short, mismatches)
         finally:
             self._fp.seek(at)
 
