@@ -722,6 +722,62 @@ int zngamd_bgzf_classify_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in
                                  zngamd_bgzf_class_row *class_rows, uint64_t class_cap, zngamd_bgzf_grep_row *rows, uint64_t rows_cap,
                                  uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_classify_totals *totals);
 
+/* ---- BGZF by a label per record (zlib_ng_amd/bgzf.py: partition_records, demux_paired).  The call above
+ * without the compare: the class of record r is not computed from patterns but read from labels[r], which the caller computed --
+ * from the mate file of a paired run, from the index reads of a dual-index run, or by any rule of their own.  The record model is that
+ * of zngamd_bgzf_grep_records (record_lines, first_byte, _FINAL, the open tail, the short last record, the cover contract); there are
+ * no patterns, no match_line and no max_mismatch.  The labels:
+ *   - labels[r] (uint16_t) belongs to record record_base + r of the call: a class 0 .. n_classes - 1 (n_classes: 1 .. 1024), or
+ *     ZNGAMD_BGZF_PARTITION_DROP: the record is counted in dropped / dropped_bytes, gets no row and none of its bytes is gathered.
+ *   - Only the first min(n_labels, seen) labels are read.  seen > n_labels: labels_short = 1, no row and no byte is written, and the
+ *     totals are valid, the records without a label counted as dropped ones.  n_labels > seen is no fault: the next call takes
+ *     labels + seen.
+ *   - Any other value is a fault: bad = 2, bad_record the smallest such record's number and bad_src its scratch offset.  A first_byte
+ *     violation is bad = 1 as in zngamd_bgzf_grep_records.  Of the two faults the one at the smaller record is reported; a record
+ *     with both is reported for its first byte.  With bad set no row and no byte is written; the other totals are valid, except that
+ *     a record whose label is out of range counts in no class.
+ * flags: _FINAL and ZNGAMD_BGZF_CLASSIFY_GROUP; anything else, _LINE_START included, is ZNGAMD_E_ARG.  class_records and class_bytes
+ * are HOST arrays of n_classes entries that the caller owns, in both forms: records and bytes per class (zeros when nothing was
+ * decided).  Without _GROUP only they and the totals leave the kernels; d_rows and d_out may be NULL with capacity 0.  With _GROUP
+ * d_rows[0 .. seen - dropped) holds a row per kept record ordered by class, then by record number (src_off, number = record_base + r,
+ * len as in zngamd_bgzf_grep_records; reserved: the label), and d_out the records packed whole in that order: class c has the rows
+ * [sum of class_records[< c], ... + class_records[c]) and the bytes [sum of class_bytes[< c], ...).
+ * ZNGAMD_BUF_ERROR: with _GROUP, rows_cap < seen - dropped or out_cap < bytes; nothing is written, the totals and the counts are valid.
+ * Hostile arguments -- n_classes 0 or above 1024, labels NULL with n_labels > 0, record_lines / first_byte, delim, flags, totals or a
+ * count array NULL -- are ZNGAMD_E_ARG before the context is touched.  Device memory beside the tiles: 8 bytes per line and 6 bytes per
+ * record of the text (4 without the host form's copy of the labels), 8 bytes per class and 256 records, and 16 bytes per class. */
+#define ZNGAMD_BGZF_PARTITION_MAX_CLASSES 1024u
+#define ZNGAMD_BGZF_PARTITION_DROP        0xFFFFu
+typedef struct {
+    uint64_t seen;          /* records of the text that were decided (the open tail is not one of them) */
+    uint64_t bytes;         /* bytes of the kept records: the sum of class_bytes */
+    uint64_t dropped;       /* records labelled _DROP (or, with labels_short, without a label) */
+    uint64_t dropped_bytes; /* and their bytes */
+    uint64_t tail_off;      /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;    /* bad != 0: the number of the record at fault */
+    uint64_t bad_src;       /*           and where it starts in the scratch */
+    uint32_t covered;       /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;   /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;           /* 0; 1: the first byte is not first_byte; 2: the label is out of range */
+    uint32_t labels_short;  /* 1: the text holds more records than n_labels */
+} zngamd_bgzf_partition_totals;                                                                   /* 72 B */
+int zngamd_bgzf_partition_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                      uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, uint32_t record_lines,
+                                      int32_t first_byte, uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                                      zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap,
+                                      const uint16_t *d_labels, uint64_t n_labels, uint32_t n_classes, uint64_t *class_records,
+                                      uint64_t *class_bytes, zngamd_bgzf_partition_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; labels is host memory, of which min(n_labels, seen) entries are uploaded
+ * once the line count is known; status and, with _GROUP, the rows and the packed records come back.  With alloc (rows = out = NULL,
+ * the capacities 0) the caller's memory is asked for once the sizes are known, in the order rows ((seen - dropped) * 24 bytes),
+ * bytes -- with _GROUP and seen > dropped only; NULL from it: ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_partition_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                                  uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, uint32_t record_lines,
+                                  int32_t first_byte, uint64_t record_base, int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap,
+                                  uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc, void *user, const uint16_t *labels,
+                                  uint64_t n_labels, uint32_t n_classes, uint64_t *class_records, uint64_t *class_bytes,
+                                  zngamd_bgzf_partition_totals *totals);
+
 /* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
  * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM
  * preset, is ZNGAMD_E_ARG), the columns of the name, the start and the end (from 1; col_end 0: none), the byte that opens a comment

@@ -12,6 +12,7 @@
 #include "za_grep.hip"
 #include "za_grep_records.hip"
 #include "za_classify.hip"
+#include "za_partition.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
 #include "za_batch.hip"
@@ -49,6 +50,9 @@ static_assert(sizeof(zngamd_bgzf_grep_records_totals) == sizeof(ZaGrepRecTotals)
 static_assert(sizeof(zngamd_bgzf_classify_totals) == sizeof(ZaClsTotals) && offsetof(ZaClsTotals, class_bytes) == offsetof(zngamd_bgzf_classify_totals, class_bytes) &&
               sizeof(zngamd_bgzf_class_row) == 4 && ZNGAMD_BGZF_CLASSIFY_MAX_CLASSES == ZA_CLS_MAX_CLASSES && ZNGAMD_BGZF_CLASSIFY_GROUP == ZA_CLS_GROUP &&
               ZNGAMD_BGZF_CLASS_ASSIGNED == ZA_CLS_ASSIGNED && ZNGAMD_BGZF_CLASS_AMBIGUOUS == ZA_CLS_AMBIGUOUS, "bgzf classify layout");
+static_assert(sizeof(zngamd_bgzf_partition_totals) == sizeof(ZaPartTotals) && sizeof(ZaPartTotals) == 72 && offsetof(ZaPartTotals, covered) == offsetof(zngamd_bgzf_partition_totals, covered) &&
+              offsetof(ZaPartTotals, labels_short) == offsetof(zngamd_bgzf_partition_totals, labels_short) && ZNGAMD_BGZF_PARTITION_MAX_CLASSES == ZA_PART_MAX_CLASSES &&
+              ZNGAMD_BGZF_PARTITION_DROP == ZA_PART_DROP && ZA_PART_WG_RECORDS == ZA_CLS_WG_RECORDS, "bgzf partition layout");
 static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_tabix_name) == sizeof(ZaTbxName) && sizeof(zngamd_tabix_bin) == sizeof(ZaTbxBin) &&
               sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
               sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
@@ -162,6 +166,9 @@ struct zngamd_ctx {
     // records by their nearest pattern (za_classify.hip, section 5f.3): the two minima per record; per record class row, length and class;
     // the table of counts per (class, workgroup); the totals and the first bad record
     DevBuf<uint32_t> cl_min, cl_row, cl_len; DevBuf<uint8_t> cl_cls, cl_tot; DevBuf<unsigned long long> cl_tab;
+    // records by the caller's labels (za_partition.hip, section 5f.4; lengths and table are cl_len and cl_tab): the host form's labels; the
+    // totals, the two first faults, the scan's sum, records and bytes per class
+    DevBuf<uint16_t> pt_lab; DevBuf<unsigned long long> pt_tot;
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -314,7 +321,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->fa_x.release(); c->fa_bw.release(); c->fa_start.release(); c->fa_hline.release(); c->fa_first.release(); c->fa_last.release(); c->fa_rows.release(); c->fa_spans.release();
     c->gp_par.release(); c->gp_bits.release(); c->gp_tiles.release(); c->gp_carry.release(); c->gp_rows.release(); c->gp_lens.release();
     c->gr_start.release(); c->gr_sel.release(); c->gr_len.release(); c->gr_hit.release();
-    c->cl_min.release(); c->cl_row.release(); c->cl_len.release(); c->cl_cls.release(); c->cl_tot.release(); c->cl_tab.release();
+    c->cl_min.release(); c->cl_row.release(); c->cl_len.release(); c->cl_cls.release(); c->cl_tot.release(); c->cl_tab.release(); c->pt_lab.release(); c->pt_tot.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -4164,6 +4171,137 @@ try {
     if (group) HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return group ? d2h_payload(c, out, c->bg_out.p, totals->bytes) : ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- records by the caller's labels (za_partition.hip)
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool partition_args_ok(int delim, uint32_t flags, uint32_t record_lines, int32_t first_byte, const uint16_t *labels, uint64_t n_labels, uint32_t n_classes,
+                              const uint64_t *class_records, const uint64_t *class_bytes, const zngamd_bgzf_partition_totals *totals)
+{
+    if (!totals || !class_records || !class_bytes || (flags & ~(ZNGAMD_BGZF_GREP_FINAL | ZNGAMD_BGZF_CLASSIFY_GROUP))) return false;
+    if (delim < 0 || delim > 255 || !grep_records_ok(record_lines, -1, first_byte)) return false;
+    return n_classes >= 1 && n_classes <= ZNGAMD_BGZF_PARTITION_MAX_CLASSES && (labels || !n_labels);
+}
+
+// the lines pass for the delimiters alone, [the host waits for the line count], lines, eval, hist, with _GROUP the scan, close, [the
+// host waits for the totals and the counts], then with _GROUP scatter and pack.  own: the host form (labels is host memory and goes to
+// pt_lab once the line count says how many are needed; rows and records go to the context's buffers, as long as the totals say).
+static int bgzf_partition_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
+                              uint64_t text_end, uint32_t delim, uint32_t flags, uint32_t k, int32_t first_byte, uint64_t record_base, uint8_t *d_scratch,
+                              uint64_t scratch_cap, int32_t *d_status, ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap,
+                              const uint16_t *labels, uint64_t n_labels, uint32_t ncls, uint64_t *class_records, uint64_t *class_bytes, bool own,
+                              zngamd_bgzf_partition_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    memset(class_records, 0, (size_t)ncls * 8u); memset(class_bytes, 0, (size_t)ncls * 8u);
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL;
+    const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, no_bytes, 0, no_table, 0, delim, lflags, 0, 0, d_scratch,
+                                       scratch_cap, d_status, &lt, sizeof lt, false);
+    if (r) return r;
+    totals->tail_off = text_off;
+    if (!lt.covered) return ZNGAMD_OK;
+    totals->covered = 1;
+    const bool fin = (flags & ZA_GREP_FINAL) != 0, group = (flags & ZA_CLS_GROUP) != 0;
+    const uint64_t lines = lt.seen, nrec = fin ? (lines + k - 1u) / k : lines / k;
+    if (fin) totals->tail_off = text_end;
+    if (!nrec) return ZNGAMD_OK;                                  // (without FINAL: fewer than k lines have ended, the open record starts at text_off)
+    const uint64_t nlab = std::min<uint64_t>(n_labels, nrec);
+    const uint64_t tile0 = text_off / ZA_GREP_TILE;
+    const uint32_t ntiles = (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull);      // (a line was decided: the text is not empty)
+    const uint32_t grid = (uint32_t)((nrec + 255u) / 256u), nwg = (uint32_t)((nrec + ZA_PART_WG_RECORDS - 1u) / ZA_PART_WG_RECORDS);
+    const uint64_t ntab = (uint64_t)ncls * nwg;
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab));
+    HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u)); HIPCHK(c, c->pt_tot.ensure(12u + 2u * ZA_PART_MAX_CLASSES));
+    if (own && nlab) {
+        HIPCHK(c, c->pt_lab.ensure(nlab));
+        HIPCHK(c, hipMemcpyAsync(c->pt_lab.p, labels, (size_t)nlab * 2u, hipMemcpyHostToDevice, c->stream));
+        labels = c->pt_lab.p;
+    }
+    const ZaGrepTotals *d_lt = (const ZaGrepTotals *)c->d_small;
+    ZaPartTotals *d_tot = (ZaPartTotals *)c->pt_tot.p;                                   // 9 words; then the two faults, the scan's sum, the counts
+    unsigned long long *d_bad = c->pt_tot.p + 9, *d_sum = c->pt_tot.p + 11, *d_cnt = c->pt_tot.p + 12;
+    HIPCHK(c, hipMemsetAsync(c->pt_tot.p, 0, (12u + 2u * (size_t)ncls) * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 16, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_grep_rec_lines, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_lt, ntiles, tile0, text_off,
+                         text_end, lflags, k, -1, c->gr_start.p, lines + 1u, (uint8_t *)nullptr, 0ull);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_part_eval, dim3(grid), dim3(256), 0, c->stream, d_scratch, text_off, text_end, c->gr_start.p, lines, labels, nlab, nrec, k, ncls,
+                         first_byte, c->cl_len.p, d_bad);
+      hipLaunchKernelGGL(za_k_part_hist, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, labels, nlab, c->cl_len.p, nrec, ncls, nwg, c->cl_tab.p, d_cnt, d_tot);
+      if (group) tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
+      hipLaunchKernelGGL(za_k_part_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, nlab, k, lflags, text_end, record_base, ncls, d_cnt, d_bad,
+                         d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(class_records, d_cnt, (size_t)ncls * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(class_bytes, d_cnt + ncls, (size_t)ncls * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint64_t n = totals->seen - totals->dropped;
+    if (totals->bad || totals->labels_short || !group || !n) return ZNGAMD_OK;
+    if (own) {
+        HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(totals->bytes + 64));
+        d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; out_cap = totals->bytes;
+    } else if (n > rows_cap || totals->bytes > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_part_scatter, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, labels, nlab, c->cl_len.p, c->gr_start.p, nrec, k, ncls, nwg,
+                         c->cl_tab.p, record_base, d_rows, n, c->gp_lens.p);
+      bgzf_grep_pack(c, d_members, n_members, d_scratch, scratch_cap, d_status, d_rows, n, d_out, totals->bytes); }
+    c->bgzf_stats[2] += n;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_partition_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                      uint64_t text_end, int delim, uint32_t flags, uint32_t record_lines, int32_t first_byte, uint64_t record_base,
+                                      void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out,
+                                      uint64_t out_cap, const uint16_t *d_labels, uint64_t n_labels, uint32_t n_classes, uint64_t *class_records,
+                                      uint64_t *class_bytes, zngamd_bgzf_partition_totals *totals)
+try {
+    if (!partition_args_ok(delim, flags, record_lines, first_byte, d_labels, n_labels, n_classes, class_records, class_bytes, totals)) return ZNGAMD_E_ARG;
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = bgzf_partition_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, flags, record_lines,
+                               first_byte, record_base, (uint8_t *)d_scratch, scratch_cap, d_status, (ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap,
+                               d_labels, n_labels, n_classes, class_records, class_bytes, false, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_partition_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                                  uint64_t text_end, int delim, uint32_t flags, uint32_t record_lines, int32_t first_byte, uint64_t record_base,
+                                  int32_t *status, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc,
+                                  void *user, const uint16_t *labels, uint64_t n_labels, uint32_t n_classes, uint64_t *class_records, uint64_t *class_bytes,
+                                  zngamd_bgzf_partition_totals *totals)
+try {
+    if (!partition_args_ok(delim, flags, record_lines, first_byte, labels, n_labels, n_classes, class_records, class_bytes, totals)) return ZNGAMD_E_ARG;
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!out && out_cap) || (alloc && (rows || out))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    r = bgzf_partition_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, flags, record_lines, first_byte, record_base,
+                           c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, labels, n_labels, n_classes, class_records, class_bytes, true, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t n = totals->seen - totals->dropped;
+    if (!totals->covered || totals->bad || totals->labels_short || !(flags & ZNGAMD_BGZF_CLASSIFY_GROUP) || !n) return ZNGAMD_OK;
+    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
+        rows = (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow));
+        out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr;
+        if (!rows || !out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (n > rows_cap || totals->bytes > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return d2h_payload(c, out, c->bg_out.p, totals->bytes);
 } ZA_ABI_GUARD
 
 // ---- fields of a line (za_tabix.hip)

@@ -85,6 +85,7 @@ SYMBOLS = [
     "zngamd_bgzf_read_lines", "zngamd_bgzf_grep_dev", "zngamd_bgzf_grep", "zngamd_bgzf_grep_records_dev", "zngamd_bgzf_grep_records",
     "zngamd_bgzf_grep_approx_dev", "zngamd_bgzf_grep_approx", "zngamd_bgzf_grep_records_approx_dev", "zngamd_bgzf_grep_records_approx",
     "zngamd_bgzf_classify_records_dev", "zngamd_bgzf_classify_records",
+    "zngamd_bgzf_partition_records_dev", "zngamd_bgzf_partition_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
@@ -179,6 +180,19 @@ class BgzfClassifyTotals(C.Structure):         # zngamd_bgzf_classify_totals
 
     @property
     def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is classified)
+        return self.seen
+
+
+BGZF_PARTITION_MAX_CLASSES, BGZF_PARTITION_DROP = 1024, 0xFFFF      # ZNGAMD_BGZF_PARTITION_*
+
+
+class BgzfPartitionTotals(C.Structure):        # zngamd_bgzf_partition_totals
+    _fields_ = [("seen", C.c_uint64), ("bytes", C.c_uint64), ("dropped", C.c_uint64), ("dropped_bytes", C.c_uint64), ("tail_off", C.c_uint64),
+                ("bad_record", C.c_uint64), ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32),
+                ("labels_short", C.c_uint32)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is labelled)
         return self.seen
 
 
@@ -351,6 +365,12 @@ def load():
             L.zngamd_bgzf_classify_records_dev.argtypes = exact[:21] + [vp, C.c_uint64] + exact[21:]
             exact = L.zngamd_bgzf_grep_records_approx.argtypes
             L.zngamd_bgzf_classify_records.argtypes = exact[:19] + [vp, C.c_uint64] + exact[19:]
+        if hasattr(L, "zngamd_bgzf_partition_records"):     # the records calls without the patterns and match_line; labels and counts behind the results
+            tail = [vp, C.c_uint64, C.c_uint32, vp, vp, vp]
+            exact = L.zngamd_bgzf_grep_records_dev.argtypes
+            L.zngamd_bgzf_partition_records_dev.argtypes = exact[:7] + exact[11:14] + exact[15:-1] + tail
+            exact = L.zngamd_bgzf_grep_records.argtypes
+            L.zngamd_bgzf_partition_records.argtypes = exact[:7] + exact[11:14] + exact[15:-1] + tail
         if hasattr(L, "zngamd_bgzf_tabix"):
             L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
                                                 C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1389,6 +1409,67 @@ class Context:
                                                               v(d_class), class_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
                       (OK, BUF_ERROR))
         return r, tot
+
+    def bgzf_partition_records(self, data, members, text_off, text_end, delim, flags, record_lines, first_byte, record_base, labels, n_classes,
+                               caps=None):
+        """zngamd_bgzf_partition_records: the records split by labels (a uint16 array; entry r belongs to record record_base + r;
+        BGZF_PARTITION_DROP: the record is dropped) -> (code, block statuses, totals (BgzfPartitionTotals), records per class, bytes per class
+        (uint64[n_classes]), rows (GREP_ROW_DTYPE, ordered by class then number; reserved: the label), the kept records packed in that
+        order); rows and records only with BGZF_CLASSIFY_GROUP in flags; nothing comes back when totals.bad or totals.labels_short is set.
+        caps None: the arrays are allocated once the engine knows their sizes; (rows, bytes): buffers of those sizes, and code is
+        BUF_ERROR (nothing written) when the result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        labels = np.ascontiguousarray(labels, np.uint16)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfPartitionTotals()
+        crec, cbytes = np.zeros(max(1, n_classes), np.uint64), np.zeros(max(1, n_classes), np.uint64)
+        box = []
+
+        def alloc(_user, nbytes):
+            if not box:
+                arr = np.empty(nbytes // GREP_ROW_DTYPE.itemsize, GREP_ROW_DTYPE)
+                box.append(arr)
+                return arr.ctypes.data
+            obj, addr = _new_bytes(nbytes)
+            box.append(obj)
+            return addr.value
+
+        if caps is None:
+            rp, rcap, op, ocap, fn = None, 0, None, 0, ALLOC_FN(alloc)
+        else:
+            rcap, ocap = caps
+            rows = np.zeros(max(1, rcap), GREP_ROW_DTYPE)
+            out, op = _new_bytes(ocap)
+            rp, fn = C.c_void_p(rows.ctypes.data) if rcap else None, ALLOC_FN()
+            if not ocap:
+                op = None
+        r = self._chk(self.L.zngamd_bgzf_partition_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                           text_off, text_end, delim, flags, record_lines, first_byte, record_base,
+                                                           C.c_void_p(st.ctypes.data), rp, rcap, op, ocap, fn, None,
+                                                           C.c_void_p(labels.ctypes.data) if len(labels) else None, len(labels), n_classes,
+                                                           C.c_void_p(crec.ctypes.data), C.c_void_p(cbytes.ctypes.data), C.byref(tot)), (OK, BUF_ERROR))
+        kept = tot.seen - tot.dropped
+        got = r == OK and tot.covered and kept and not tot.bad and not tot.labels_short and bool(flags & BGZF_CLASSIFY_GROUP)
+        if caps is None:
+            rows_out, packed = (box[0], box[1]) if got else (np.empty(0, GREP_ROW_DTYPE), b"")
+        else:
+            rows_out, packed = (rows[:kept], _take(out, tot.bytes)) if got else (np.empty(0, GREP_ROW_DTYPE), b"")
+        return r, st[:nm], tot, crec[:n_classes], cbytes[:n_classes], rows_out, packed
+
+    def bgzf_partition_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, record_lines, first_byte, record_base,
+                                   d_scratch, scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap, d_labels, n_labels, n_classes):
+        """zngamd_bgzf_partition_records_dev on device pointers -> (code, totals, records per class, bytes per class); rows and records stay
+        on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfPartitionTotals()
+        crec, cbytes = np.zeros(max(1, n_classes), np.uint64), np.zeros(max(1, n_classes), np.uint64)
+        r = self._chk(self.L.zngamd_bgzf_partition_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
+                                                               record_lines, first_byte, record_base, v(d_scratch), scratch_cap, v(d_status),
+                                                               v(d_rows), rows_cap, v(d_out), out_cap, v(d_labels), n_labels, n_classes,
+                                                               C.c_void_p(crec.ctypes.data), C.c_void_p(cbytes.ctypes.data), C.byref(tot)),
+                      (OK, BUF_ERROR))
+        return r, tot, crec[:n_classes], cbytes[:n_classes]
 
     def _bgzf_grep(self, fn_c, tot, data, members, text_off, text_end, blob, table, delim, flags, extra, caps):
         nm = len(members)

@@ -41,6 +41,7 @@ AFTER the first a pair of u64 (compressed offset, uncompressed offset).  save() 
 file whose last entry points at it.  An index is untrusted: load() and the reader check it before it steers a read.
 """
 import bisect
+import contextlib
 import io
 import os
 import struct
@@ -51,7 +52,7 @@ from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
-           "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS",
+           "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
 BadGzipFile = zlib_ng.BadGzipFile
@@ -693,13 +694,17 @@ def _grep_record_args(record_lines, match_line, first_byte):
 
 
 def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_count, start, stop, first_line, max_line, records=None, mismatches=0,
-               classify=None):
+               classify=None, partition=None):
     """The window loop of grep() and, with records = (record_lines, match_line, first_byte, allow_short), of grep_records(): then the
     unit that is counted, numbered, carried over a window's end and bounded by max_line is the record.  classify (with records): a
     _ClassifySink -- every window's records are not selected but assigned to their nearest pattern (classify_records(), demux()), the
-    sink takes what each window gives, and what its finish() returns is the result."""
-    pats, delimiter = _grep_patterns(patterns, delimiter)
-    mismatches = _grep_mismatches(mismatches, pats)
+    sink takes what each window gives, and what its finish() returns is the result.  partition (with records, instead of patterns): a
+    _PartitionSink -- every window's records are split by the labels it holds (partition_records())."""
+    if partition is None:
+        pats, delimiter = _grep_patterns(patterns, delimiter)
+        mismatches = _grep_mismatches(mismatches, pats)
+    else:
+        delimiter = _partition_delimiter(delimiter)
     approx = {"mismatches": mismatches} if mismatches else {}      # (0: the engine is called with the arguments it always had)
     unit, bound = ("record", "max_record") if records is not None else ("line", "max_line")
     if records is not None:
@@ -710,7 +715,8 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
     if max_count is not None and int(max_count) < 0:
         raise ValueError("max_count is not negative")
     ctx = ctx or zlib_ng._ctx()                              # (the arguments are judged before a context is asked for)
-    blob, table = _lib.grep_pattern_table(pats)
+    if partition is None:
+        blob, table = _lib.grep_pattern_table(pats)
     flags = (_lib.BGZF_GREP_INVERT if invert else 0) | (_lib.BGZF_GREP_LINE_START if line_start else 0) | (_lib.BGZF_GREP_COUNT_ONLY if count else 0)
     c_next, text_off = split_virtual_offset(start) if start is not None else (0, 0)
     stop = split_virtual_offset(stop) if stop is not None else None
@@ -748,7 +754,9 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
                 raise BadGzipFile(f"BGZF block {nblocks + bad} at offset {c_next + int(coffs[bad])}: bad block header or block size")
             cend = int(coffs[n_use - 1] + csizes[n_use - 1]) if n_use else 0
             wflags = flags | (_lib.BGZF_GREP_FINAL if final else 0)
-            if classify is not None:
+            if partition is not None:
+                status, tot, packed = partition.call(ctx, data[:cend], members, text_off, text_end, delimiter[0], wflags, rec_k, rec_b, line_base)
+            elif classify is not None:
                 _, status, tot, cls_rows, rows, packed = ctx.bgzf_classify_records(data[:cend], members, text_off, text_end, blob, table, delimiter[0],
                                                                                    wflags | classify.flags, mismatches, rec_k, rec_j, rec_b, line_base)
             elif records is None:
@@ -767,13 +775,17 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
                 return (coffs[at] + c_next).astype(np.uint64) << np.uint64(16) | (src - members["out_off"][at].astype(np.int64)).astype(np.uint64)
 
             if records is not None:
+                if tot.bad == 2 and partition is not None:
+                    raise ValueError(f"record {tot.bad_record}: its label is neither a class nor DROP")
                 if tot.bad:
                     v = int(voffsets_of(np.array([tot.bad_src], np.int64))[0])
                     raise ValueError(f"record {tot.bad_record} at virtual offset {v} does not start with {bytes([rec_b])!r} (first_byte)")
                 if tot.short_lines and not records[3]:
                     raise ValueError(f"record {line_base + tot.seen - 1}, the last one, has {tot.short_lines} of {rec_k} lines (allow_short)")
             searched, line_base, matched = searched + tot.seen, line_base + tot.seen, matched + tot.matched
-            if classify is not None:
+            if partition is not None:
+                partition.window(tot, packed)
+            elif classify is not None:
                 classify.window(tot, cls_rows, packed)
             elif len(rows):
                 numbers.append(rows["number"].astype(np.int64))
@@ -794,6 +806,8 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
         if buf is not None:
             del mv
             _lib.give_buffer(buf)
+    if partition is not None:
+        return partition.finish(searched)
     if classify is not None:
         return classify.finish(searched)
     if count:
@@ -889,26 +903,33 @@ class ClassifyResult:
     def __len__(self):
         return self.searched
 
+    def labels(self):
+        """-> int32, one class per record in the numbering of counts: the pattern's index where assigned, n_patterns where AMBIGUOUS,
+        n_patterns + 1 where UNASSIGNED -- what partition_records() takes for a file whose records go with these"""
+        n = len(self.counts) - 2
+        p = self.pattern.astype(np.int32)
+        return np.where(p >= 0, p, np.where(p == AMBIGUOUS, np.int32(n), np.int32(n + 1))).astype(np.int32)
+
     def __repr__(self):
         return f"<ClassifyResult: {self.searched} records, {int(self.counts[:-2].sum())} assigned, {int(self.counts[-2])} ambiguous>"
 
 
 class _ClassifySink:
     """what _grep_file hands a window's classes to: the class rows are kept (classify_records) or, with writers, every class's bytes go
-    to its writer (demux; None: the class is dropped)"""
+    to its writer (demux; None: the class is dropped); keep with writers: both (demux_paired), and finish() gives the ClassifyResult"""
 
-    def __init__(self, n_patterns, first_record, writers=None):
+    def __init__(self, n_patterns, first_record, writers=None, keep=False):
         self.flags = _lib.BGZF_CLASSIFY_GROUP if writers is not None else 0
-        self.writers, self.first_record = writers, int(first_record)
+        self.writers, self.first_record, self.keep = writers, int(first_record), keep or writers is None
         self.counts = np.zeros(n_patterns + 2, np.int64)
         self.rows = []
 
     def window(self, tot, cls_rows, packed):
         n = len(self.counts)
         self.counts += np.frombuffer(tot.class_records, np.uint64, n).astype(np.int64)
+        if self.keep and len(cls_rows):
+            self.rows.append(cls_rows)
         if self.writers is None:
-            if len(cls_rows):
-                self.rows.append(cls_rows)
             return
         at = 0
         with memoryview(packed) as mv:
@@ -920,7 +941,7 @@ class _ClassifySink:
             raise RuntimeError("classify: the classes' bytes do not add up to the records")
 
     def finish(self, searched):
-        if self.writers is not None:
+        if not self.keep:
             return self.counts
         rows = np.concatenate(self.rows) if self.rows else np.empty(0, _lib.CLASS_ROW_DTYPE)
         flags = rows["flags"]
@@ -961,15 +982,15 @@ def classify_records(file, patterns, record_lines, *, match_line=None, first_byt
 
 
 def _classify_file(fp, ctx, patterns, record_lines, match_line, first_byte, delimiter, line_start, start, stop, first_record, max_record,
-                   allow_short, mismatches, writers):
+                   allow_short, mismatches, writers, keep=False):
     pats = _classify_patterns(patterns, delimiter)
-    sink = _ClassifySink(len(pats), first_record, writers)
+    sink = _ClassifySink(len(pats), first_record, writers, keep)
     return _grep_file(fp, ctx, pats, delimiter, False, line_start, False, None, start, stop, first_record, max_record,
                       (record_lines, match_line, first_byte, allow_short), mismatches, sink)
 
 
 def _demux_file(fp, ctx, patterns, outputs, record_lines, ambiguous, unassigned, compresslevel, block_size, match_line, first_byte, delimiter,
-                line_start, start, stop, first_record, max_record, allow_short, mismatches):
+                line_start, start, stop, first_record, max_record, allow_short, mismatches, keep=False):
     pats = _classify_patterns(patterns, delimiter)
     if _is_path(outputs) or hasattr(outputs, "write"):
         outputs = [outputs]
@@ -979,12 +1000,19 @@ def _demux_file(fp, ctx, patterns, outputs, record_lines, ambiguous, unassigned,
     _grep_mismatches(mismatches, pats)
     _grep_record_args(record_lines, match_line, first_byte)
     _check_block_size(block_size)
+    return _with_writers("demux", outputs + [ambiguous, unassigned], compresslevel, block_size,
+                         lambda writers: _classify_file(fp, ctx, pats, record_lines, match_line, first_byte, delimiter, line_start, start, stop,
+                                                        first_record, max_record, allow_short, mismatches, writers, keep))
+
+
+def _with_writers(who, outputs, compresslevel, block_size, run):
+    """run(writers) with a BgzfWriter per output (None stays None).  If anything is raised the writers opened so far are closed and the
+    error says that the outputs are incomplete; otherwise they are closed behind the run, whose result this returns."""
     writers = []
     try:
-        for out in outputs + [ambiguous, unassigned]:
+        for out in outputs:
             writers.append(None if out is None else BgzfWriter(out, "wb", compresslevel, block_size=block_size))
-        counts = _classify_file(fp, ctx, pats, record_lines, match_line, first_byte, delimiter, line_start, start, stop, first_record,
-                                max_record, allow_short, mismatches, writers)
+        result = run(writers)
     except Exception as e:
         for w in writers:
             if w is not None:
@@ -992,13 +1020,13 @@ def _demux_file(fp, ctx, patterns, outputs, record_lines, ambiguous, unassigned,
                     w.close()
                 except Exception:
                     pass
-        note = "demux: the outputs written so far were closed and are incomplete"
+        note = f"{who}: the outputs written so far were closed and are incomplete"
         e.args = ((f"{e.args[0]} ({note})",) + e.args[1:]) if e.args and isinstance(e.args[0], str) else e.args + (note,)
         raise
     for w in writers:
         if w is not None:
             w.close()
-    return counts
+    return result
 
 
 def demux(file, patterns, outputs, record_lines=4, *, ambiguous=None, unassigned=None, compresslevel=6, block_size=MAX_BLOCK_INPUT,
@@ -1017,6 +1045,215 @@ def demux(file, patterns, outputs, record_lines=4, *, ambiguous=None, unassigned
                          start=start, stop=stop, first_record=first_record, max_record=max_record, allow_short=allow_short, mismatches=mismatches)
     return _demux_file(file, None, patterns, outputs, record_lines, ambiguous, unassigned, compresslevel, block_size, match_line, first_byte,
                        delimiter, line_start, start, stop, first_record, max_record, allow_short, mismatches)
+
+
+# ---- records by a label per record: the mate file of a paired run, dual indexes, any rule of the caller's
+DROP = -1                                     # a label of partition_records(): the record is counted and written nowhere
+_OUT_OF_STEP = "the file holds {} records and labels has {} entries: the files are out of step"
+
+
+def _partition_delimiter(delimiter):
+    delimiter = bytes(delimiter)
+    if len(delimiter) != 1:
+        raise ValueError("the delimiter is exactly one byte")
+    return delimiter
+
+
+def _partition_labels(labels, outputs):
+    """-> (labels as int64, outputs as a list or None, n_classes); ValueError as partition_records() documents it"""
+    labels = np.asarray(labels)
+    if labels.ndim != 1 or (labels.size and labels.dtype.kind not in "iu"):
+        raise ValueError("labels is a one-dimensional array of integers")
+    labels = labels.astype(np.int64)
+    if outputs is not None:
+        if _is_path(outputs) or hasattr(outputs, "write"):
+            outputs = [outputs]
+        outputs = list(outputs)
+        n = len(outputs)
+    else:
+        n = max(1, int(labels.max()) + 1) if len(labels) else 1
+    if not 1 <= n <= _lib.BGZF_PARTITION_MAX_CLASSES:
+        raise ValueError(f"partition_records takes 1 to {_lib.BGZF_PARTITION_MAX_CLASSES} outputs (classes), not {n}")
+    wrong = np.nonzero((labels < DROP) | (labels >= n))[0]
+    if len(wrong):
+        i = int(wrong[0])
+        raise ValueError(f"labels[{i}] is {int(labels[i])}: a label is 0 .. {n - 1}, one per output, or DROP ({DROP})")
+    return labels, outputs, n
+
+
+class _PartitionSink:
+    """what _grep_file hands a window's records to when they are split by labels: labels[i] (int64, judged) belongs to record
+    first_record + i; writers: None (count only) or one per class, None where a class is written nowhere -- such a class is relabelled
+    DROP before the upload, so its records are never gathered, and counted here"""
+
+    def __init__(self, labels, n_classes, first_record, writers=None):
+        self.n, self.first_record, self.writers = n_classes, int(first_record), writers
+        self.flags = _lib.BGZF_CLASSIFY_GROUP if writers is not None and any(w is not None for w in writers) else 0
+        self.quiet = [c for c in range(n_classes) if writers is not None and writers[c] is None]
+        self.labels = labels
+        dev = np.where(labels < 0, _lib.BGZF_PARTITION_DROP, labels)
+        if self.quiet and self.flags:
+            dev[np.isin(labels, self.quiet)] = _lib.BGZF_PARTITION_DROP
+        else:
+            self.quiet = []                                  # (nothing is gathered at all: every class is counted on the device)
+        self.dev = dev.astype(np.uint16)
+        self.counts, self.dropped, self.short = np.zeros(n_classes + 1, np.int64), 0, False
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        at = record_base - self.first_record
+        lab, group = (self.dev[:0], 0) if self.short else (self.dev[at:], self.flags)      # (out of step: the records are only counted)
+        _, status, tot, self.crec, self.cbytes, rows, packed = ctx.bgzf_partition_records(data, members, text_off, text_end, delim, flags | group, k,
+                                                                                          first_byte, record_base, lab, self.n)
+        return status, tot, packed
+
+    def window(self, tot, packed):
+        self.short = self.short or bool(tot.labels_short)
+        if self.short:
+            return
+        self.counts[:self.n] += self.crec.astype(np.int64)
+        self.dropped += int(tot.dropped)
+        if not self.flags:
+            return
+        at = 0
+        with memoryview(packed) as mv:
+            for w, nbytes in zip(self.writers, self.cbytes.tolist()):
+                if w is not None and nbytes:
+                    w.write(mv[at:at + nbytes])
+                at += nbytes
+        if at != len(packed):
+            raise RuntimeError("partition: the classes' bytes do not add up to the records")
+
+    def finish(self, searched):
+        if self.short or searched != len(self.labels):
+            raise ValueError(_OUT_OF_STEP.format(searched, len(self.labels)))
+        for c in self.quiet:
+            self.counts[c] = int((self.labels == c).sum())
+        self.counts[-1] = int((self.labels == DROP).sum())
+        if self.dropped != int(self.counts[-1]) + sum(int(self.counts[c]) for c in self.quiet):
+            raise RuntimeError("partition: the dropped records do not add up")
+        return self.counts
+
+
+def _partition_file(fp, ctx, labels, outputs, record_lines, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record,
+                    allow_short):
+    labels, outputs, n = _partition_labels(labels, outputs)
+    _partition_delimiter(delimiter)
+    _grep_record_args(record_lines, None, first_byte)
+    _check_block_size(block_size)
+
+    def run(writers):
+        sink = _PartitionSink(labels, n, first_record, writers)
+        return _grep_file(fp, ctx, None, delimiter, False, False, False, None, start, stop, first_record, max_record,
+                          (record_lines, None, first_byte, allow_short), 0, None, sink)
+
+    if outputs is None:
+        return run(None)
+    return _with_writers("partition_records", outputs, compresslevel, block_size, run)
+
+
+def partition_records(file, labels, outputs, record_lines=4, *, first_byte=None, delimiter=b"\n", compresslevel=6, block_size=MAX_BLOCK_INPUT,
+                      start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+    """Split a BGZF file of records by a label per record that the caller computed: the mate file of a paired run by the classes of the
+    file that holds the barcode (ClassifyResult.labels()), a read file by the pair of its index reads (pair_labels()), or by any rule
+    at all -- quality, length, a hash for sharding.  labels[i] belongs to record first_record + i and is 0 .. len(outputs) - 1 or DROP;
+    any other value is a ValueError before anything is opened.  outputs is one path or writable binary file per class (1 to 1024); an
+    entry may be None: its records are counted and written nowhere, and like the DROP ones they are never gathered on the device.
+    outputs=None only counts (the classes are 0 .. max(labels)).  Every output is written through a BgzfWriter (compresslevel,
+    block_size): a complete BGZF file whose decompressed bytes are exactly the records of its class, whole, in the order of the input.
+    record_lines, first_byte, delimiter, start, stop, first_record, max_record, allow_short and the errors of the file are those of
+    grep_records().  -> counts (int64, len(outputs) + 1: records per class, then the DROP ones).
+    A file that holds more or fewer records than labels is a ValueError that names both counts and says that the files are out of
+    step: what protects a paired run from a mate file that lost a read.  If anything is raised the outputs written so far are closed,
+    and the error says that they are incomplete."""
+    if _is_path(file):
+        with _builtin_open(file, "rb") as f:
+            return partition_records(f, labels, outputs, record_lines, first_byte=first_byte, delimiter=delimiter, compresslevel=compresslevel,
+                                     block_size=block_size, start=start, stop=stop, first_record=first_record, max_record=max_record,
+                                     allow_short=allow_short)
+    return _partition_file(file, None, labels, outputs, record_lines, first_byte, delimiter, compresslevel, block_size, start, stop, first_record,
+                           max_record, allow_short)
+
+
+def _per_file(value, n_files, name):
+    if value is None:
+        return [None] * n_files
+    if not isinstance(value, (list, tuple)) or len(value) != n_files:
+        raise ValueError(f"demux_paired: {name} is None or one entry per file ({n_files})")
+    return list(value)
+
+
+def _demux_paired_files(fps, patterns, outputs, record_lines, barcode_file, ambiguous, unassigned, compresslevel, block_size, match_line, first_byte,
+                        delimiter, line_start, start, stop, first_record, max_record, allow_short, mismatches):
+    """fps: (path or file, context or None) per file.  Everything is judged before the first file is opened."""
+    nf = len(fps)
+    pats = _classify_patterns(patterns, delimiter)
+    if nf < 1 or isinstance(barcode_file, bool) or not isinstance(barcode_file, (int, np.integer)) or not 0 <= barcode_file < nf:
+        raise ValueError(f"demux_paired: barcode_file is the index of one of the {nf} files")
+    one = lambda o: _is_path(o) or hasattr(o, "write")       # (one output where a list of them belongs: a list of one)
+    outputs = [[outputs]] if one(outputs) else [[o] if one(o) else list(o) for o in outputs]
+    if len(outputs) != nf or any(len(o) != len(pats) for o in outputs):
+        raise ValueError(f"demux_paired takes one output per file and pattern: {nf} files, {len(pats)} patterns")
+    ambiguous, unassigned = _per_file(ambiguous, nf, "ambiguous"), _per_file(unassigned, nf, "unassigned")
+    start, stop = _per_file(start, nf, "start"), _per_file(stop, nf, "stop")
+    _grep_mismatches(mismatches, pats)
+    _grep_record_args(record_lines, match_line, first_byte)
+    _check_block_size(block_size)
+    b = int(barcode_file)
+    with contextlib.ExitStack() as stack:
+        fps = [(stack.enter_context(_builtin_open(f, "rb")) if _is_path(f) else f, c) for f, c in fps]
+        res = _demux_file(fps[b][0], fps[b][1], pats, outputs[b], record_lines, ambiguous[b], unassigned[b], compresslevel, block_size, match_line,
+                          first_byte, delimiter, line_start, start[b], stop[b], first_record, max_record, allow_short, mismatches, True)
+        labels = res.labels()
+        for f in range(nf):
+            if f != b:
+                _partition_file(fps[f][0], fps[f][1], labels, outputs[f] + [ambiguous[f], unassigned[f]], record_lines, first_byte, delimiter,
+                                compresslevel, block_size, start[f], stop[f], first_record, max_record, allow_short)
+    return res.counts
+
+
+def demux_paired(files, patterns, outputs, record_lines=4, *, barcode_file=0, ambiguous=None, unassigned=None, compresslevel=6,
+                 block_size=MAX_BLOCK_INPUT, match_line=None, first_byte=None, delimiter=b"\n", line_start=False, start=None, stop=None,
+                 first_record=0, max_record=64 << 20, allow_short=False, mismatches=0):
+    """demux() for a run of several files whose records go together -- R1 and R2 of a paired-end run -- with the barcode in ONE of them:
+    files[barcode_file] is classified and written in one pass as demux() does it, and every other file is split by those classes through
+    partition_records(), record i of it following record i of the barcode file.  files are paths or seekable binary files; outputs[f][i]
+    is the output of file f and pattern i; ambiguous and unassigned are None or one entry (a path, a file or None) per file, start and
+    stop None or one virtual offset per file; the other keywords are demux()'s and hold for every file (match_line and mismatches for
+    the barcode file alone).  -> the counts of demux().  A file whose record count differs from the barcode file's is the ValueError
+    of partition_records() that says the files are out of step; the outputs written so far are closed."""
+    files = [files] if _is_path(files) or hasattr(files, "read") else list(files)
+    return _demux_paired_files([(f, None) for f in files], patterns, outputs, record_lines, barcode_file, ambiguous, unassigned, compresslevel,
+                               block_size, match_line, first_byte, delimiter, line_start, start, stop, first_record, max_record, allow_short,
+                               mismatches)
+
+
+def pair_labels(first, second, pairs):
+    """Dual indexes, on the host alone: first and second are the ClassifyResults of the two index reads (I1 and I2) of the same records,
+    pairs the sample sheet [(i, j), ...] of pattern indices into the two.  -> int32, one label per record for partition_records():
+      s                where both are assigned and (i, j) == pairs[s]
+      len(pairs)       where either is AMBIGUOUS
+      len(pairs) + 1   where either is UNASSIGNED (which wins over AMBIGUOUS)
+      len(pairs) + 2   where both are assigned but the pair is not in the sheet: index hopping
+    Results of unequal length, a pair outside the two pattern lists and a pair that stands twice are ValueErrors."""
+    a, b = first.labels(), second.labels()
+    if len(a) != len(b):
+        raise ValueError(f"pair_labels: the two results hold {len(a)} and {len(b)} records (unequal length)")
+    na, nb = len(first.counts) - 2, len(second.counts) - 2
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    n = len(pairs)
+    sheet = np.full((na, nb), n + 2, np.int32)
+    for s_, (i, j) in enumerate(pairs):
+        if not (0 <= i < na and 0 <= j < nb):
+            raise ValueError(f"pair_labels: pair {s_} is ({i}, {j}), outside the {na} and {nb} patterns")
+        if sheet[i, j] != n + 2:
+            raise ValueError(f"pair_labels: pair {s_}, ({i}, {j}), stands twice in the sheet (duplicate pairs)")
+        sheet[i, j] = s_
+    out = np.full(len(a), n + 2, np.int32)
+    both = (a < na) & (b < nb)
+    out[both] = sheet[a[both], b[both]]
+    out[(a == na) | (b == nb)] = n
+    out[(a == na + 1) | (b == nb + 1)] = n + 1
+    return out
 
 
 # ---- lines by region (DESIGN.md section 5g): a tabix index built on the GPU, and the rows of a region filtered there
@@ -2516,6 +2753,38 @@ class BgzfReader(io.BufferedIOBase):
         try:
             return _demux_file(self._fp, self._ctx, patterns, outputs, record_lines, ambiguous, unassigned, compresslevel, block_size, match_line,
                                first_byte, delimiter, line_start, start, stop, first_record, max_record, allow_short, mismatches)
+        finally:
+            self._fp.seek(at)
+
+    def partition_records(self, labels, outputs, record_lines=4, *, first_byte=None, delimiter=b"\n", compresslevel=6, block_size=MAX_BLOCK_INPUT,
+                          start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+        """bgzf.partition_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("partition_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _partition_file(self._fp, self._ctx, labels, outputs, record_lines, first_byte, delimiter, compresslevel, block_size, start, stop,
+                                   first_record, max_record, allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def demux_paired(self, mates, patterns, outputs, record_lines=4, *, barcode_file=0, ambiguous=None, unassigned=None, compresslevel=6,
+                     block_size=MAX_BLOCK_INPUT, match_line=None, first_byte=None, delimiter=b"\n", line_start=False, start=None, stop=None,
+                     first_record=0, max_record=64 << 20, allow_short=False, mismatches=0):
+        """bgzf.demux_paired() with this reader's file as files[0] and mates (paths or seekable binary files) behind it; the read position
+        stays where it was"""
+        if self.closed:
+            raise ValueError("demux_paired() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            mates = [mates] if _is_path(mates) or hasattr(mates, "read") else list(mates)
+            return _demux_paired_files([(self._fp, self._ctx)] + [(f, self._ctx) for f in mates], patterns, outputs, record_lines, barcode_file,
+                                       ambiguous, unassigned, compresslevel, block_size, match_line, first_byte, delimiter, line_start, start, stop,
+                                       first_record, max_record, allow_short, mismatches)
         finally:
             self._fp.seek(at)
 
