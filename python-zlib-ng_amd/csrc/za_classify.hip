@@ -8,6 +8,8 @@
 //   (za_k_tbx_reduce / _scan_blocks / _apply)    the table of counts, class by class, summed: where every (class, workgroup) begins
 //   za_k_cls_close      one thread: the totals
 //   za_k_cls_scatter    one workgroup per 256 records: every record's row behind the rows of its class in front of it
+// The histogram and the scatter are za_part_hist / za_part_scatter<MAX_CLASSES, Label> below: the one stable partition, which
+// za_k_part_hist / za_k_part_scatter of za_partition.hip instantiate for 1024 classes and 16-bit labels.
 // za_k_offsets, za_k_grep_place and za_k_slice_gather pack the records as they pack lines.  The result depends on the text and the
 // pattern list alone: a minimum and a sum of integers do not depend on the order in which they are taken.
 // Included by zng_amd.hip behind za_grep_records.hip.
@@ -66,9 +68,8 @@ __global__ __launch_bounds__(256) void za_k_grep_classify(const uint8_t *__restr
                                  [](uint32_t, uint32_t) {});
 }
 
-// grid: one thread per record.  lines: entries 0 .. lines of start[] are written.  row[r]: the class row {pattern, other, distance,
-// flags} as one word; cls[r]: the class; len[r]: the record's bytes.  *bad: the smallest r whose first byte is not first_byte (~0
-// beforehand).
+// grid: one thread per record.  row[r]: the class row {pattern, other, distance, flags} as one word; cls[r]: the class; len[r]: the
+// record's bytes.  start, lines, first_byte, bad: as za_rec_extent takes them.
 __global__ __launch_bounds__(256) void za_k_cls_eval(const uint8_t *__restrict__ scratch, uint64_t text_off, uint64_t text_end,
                                                      const unsigned long long *__restrict__ start, uint64_t lines, const uint32_t *__restrict__ lo,
                                                      const uint32_t *__restrict__ hi, uint64_t nrec, uint32_t k_lines, uint32_t np, int32_t first_byte,
@@ -77,8 +78,6 @@ __global__ __launch_bounds__(256) void za_k_cls_eval(const uint8_t *__restrict__
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nrec) return;
-    const uint64_t l0 = (uint64_t)k_lines * r, l1 = lines - l0 < k_lines ? lines : l0 + k_lines;
-    const uint64_t a = start[l0], e = start[l1];
     const uint32_t vl = lo[r], vh = hi[r];
     uint32_t w = 0x00FFFFFFu, c = np + 1u;                            // unassigned: pattern = other = distance = 255, flags = 0
     if (vl != 0xFFFFFFFFu) {
@@ -88,62 +87,57 @@ __global__ __launch_bounds__(256) void za_k_cls_eval(const uint8_t *__restrict__
         c = one ? first : np;
     }
     row[r] = w; cls[r] = (uint8_t)c;
-    len[r] = e > a ? (uint32_t)(e - a) : 0u;
-    if (first_byte >= 0 && !(a >= text_off && a < text_end && scratch[a] == (uint32_t)first_byte)) atomicMin(bad, (unsigned long long)r);
+    len[r] = (uint32_t)za_rec_extent(scratch, text_off, text_end, start, lines, r, k_lines, first_byte, bad);
 }
 
-// grid: one workgroup per ZA_CLS_WG_RECORDS records.  tab[c * nwg + workgroup] = its records of class c (class by class, so that ONE
-// sum over the table gives every (class, workgroup) its first row); tot->class_records / class_bytes (zeroed) += what it holds.
-__global__ __launch_bounds__(ZA_CLS_WG_RECORDS) void za_k_cls_hist(const uint8_t *__restrict__ cls, const uint32_t *__restrict__ len, uint64_t nrec, uint32_t ncls,
-                                                                   uint32_t nwg, unsigned long long *__restrict__ tab, ZaClsTotals *__restrict__ tot)
+// The stable partition's histogram, for a workgroup of ZA_CLS_WG_RECORDS records, one per thread, and ncls <= MAX_CLASSES classes.
+// lab[r] is read below nlab; a record at or beyond nlab has the label DROP, all ones.  tab[c * nwg + workgroup] = its records of class c
+// (class by class, so that ONE sum over the table gives every (class, workgroup) its first row); crec[c] / cbytes[c] (zeroed) += its
+// records / bytes of class c; dropped[0] / dropped[1] (zeroed; or no pointer) += its records / bytes with DROP.  Any other label that
+// is no class counts nowhere.
+template <uint32_t MAX_CLASSES, typename Label>
+__device__ __forceinline__ void za_part_hist(const Label *__restrict__ lab, uint64_t nlab, const uint32_t *__restrict__ len, uint64_t nrec, uint32_t ncls, uint32_t nwg,
+                                             unsigned long long *__restrict__ tab, unsigned long long *__restrict__ crec, unsigned long long *__restrict__ cbytes,
+                                             unsigned long long *__restrict__ dropped)
 {
-    __shared__ uint32_t s_n[ZA_CLS_MAX_CLASSES], s_b[ZA_CLS_MAX_CLASSES];
+    constexpr uint32_t DROP = (Label)~(Label)0;
+    __shared__ uint32_t s_n[MAX_CLASSES], s_b[MAX_CLASSES];
+    __shared__ uint32_t s_drop[2];
     const uint32_t tid = threadIdx.x;
-    if (tid < ZA_CLS_MAX_CLASSES) { s_n[tid] = 0; s_b[tid] = 0; }
+    for (uint32_t c = tid; c < ncls; c += ZA_CLS_WG_RECORDS) { s_n[c] = 0; s_b[c] = 0; }
+    if (tid < 2u) s_drop[tid] = 0;
     __syncthreads();
     const uint64_t r = (uint64_t)blockIdx.x * ZA_CLS_WG_RECORDS + tid;
     if (r < nrec) {
-        const uint32_t c = cls[r];
+        const uint32_t c = r < nlab ? lab[r] : DROP;
         if (c < ncls) { atomicAdd(&s_n[c], 1u); atomicAdd(&s_b[c], len[r]); }      // (the text has fewer than 4 GiB: so has a workgroup's share)
+        else if (dropped && c == DROP) { atomicAdd(&s_drop[0], 1u); atomicAdd(&s_drop[1], len[r]); }
     }
     __syncthreads();
-    if (tid < ncls) {
-        tab[(size_t)tid * nwg + blockIdx.x] = s_n[tid];
-        if (s_n[tid]) { atomicAdd((unsigned long long *)&tot->class_records[tid], (unsigned long long)s_n[tid]); atomicAdd((unsigned long long *)&tot->class_bytes[tid], (unsigned long long)s_b[tid]); }
+    for (uint32_t c = tid; c < ncls; c += ZA_CLS_WG_RECORDS) {
+        tab[(size_t)c * nwg + blockIdx.x] = s_n[c];
+        if (s_n[c]) { atomicAdd(&crec[c], (unsigned long long)s_n[c]); atomicAdd(&cbytes[c], (unsigned long long)s_b[c]); }
     }
+    if (dropped && tid == 0 && s_drop[0]) { atomicAdd(&dropped[0], (unsigned long long)s_drop[0]); atomicAdd(&dropped[1], (unsigned long long)s_drop[1]); }
 }
 
-// one thread.  nrec > 0.  tot->class_records / class_bytes hold the sums of za_k_cls_hist.
-__global__ void za_k_cls_close(const unsigned long long *__restrict__ start, uint64_t lines, uint64_t nrec, uint32_t k_lines, uint32_t flags, uint64_t text_end,
-                               uint64_t record_base, uint32_t ncls, const unsigned long long *__restrict__ bad, ZaClsTotals *__restrict__ tot)
+// The stable partition's scatter, for the same workgroups and labels.  tab: the table of za_part_hist, summed inclusively in the order
+// it lies.  A record of a class below ncls gets a row, at (the rows in front of its class and workgroup) + (the records of its class in
+// front of it in the workgroup): the second is a ballot per class and a count of the bits below the lane, so the order inside a class
+// is the input's; a wave that holds 64 different classes takes 64 rounds.  rows[] and lens[] have room for rows_cap entries.
+// reserved: row[r], or without row[] the label.
+template <uint32_t MAX_CLASSES, typename Label>
+__device__ __forceinline__ void za_part_scatter(const Label *__restrict__ lab, uint64_t nlab, const uint32_t *__restrict__ row, const uint32_t *__restrict__ len,
+                                                const unsigned long long *__restrict__ start, uint64_t nrec, uint32_t k_lines, uint32_t ncls, uint32_t nwg,
+                                                const unsigned long long *__restrict__ tab, uint64_t record_base, ZaGrepRow *__restrict__ rows, uint64_t rows_cap,
+                                                uint32_t *__restrict__ lens)
 {
-    if (blockIdx.x || threadIdx.x) return;
-    uint64_t bytes = 0;
-    for (uint32_t c = 0; c < ncls; c++) bytes += tot->class_bytes[c];
-    tot->covered = 1; tot->seen = nrec; tot->bytes = bytes; tot->n_classes = ncls;
-    const uint64_t whole = (uint64_t)k_lines * (lines / k_lines);      // lines in complete records
-    tot->tail_off = (flags & ZA_GREP_FINAL) ? text_end : start[whole];
-    tot->short_lines = (flags & ZA_GREP_FINAL) ? (uint32_t)(lines - whole) : 0u;
-    const unsigned long long b = *bad;
-    tot->bad = 0; tot->bad_record = 0; tot->bad_src = 0;
-    if (b < nrec) { tot->bad = 1; tot->bad_record = record_base + b; tot->bad_src = start[(uint64_t)k_lines * b]; }
-}
-
-// grid: one workgroup per ZA_CLS_WG_RECORDS records.  tab: the table of za_k_cls_hist, summed inclusively in the order it lies.  A
-// record's row goes to (the rows in front of its class and workgroup) + (the records of its class in front of it in the workgroup):
-// the second is a ballot per class and a count of the bits below the lane, so the order inside a class is the input's.  rows[] and
-// lens[] have room for rows_cap entries.
-__global__ __launch_bounds__(ZA_CLS_WG_RECORDS) void za_k_cls_scatter(const uint8_t *__restrict__ cls, const uint32_t *__restrict__ row, const uint32_t *__restrict__ len,
-                                                                      const unsigned long long *__restrict__ start, uint64_t nrec, uint32_t k_lines, uint32_t ncls,
-                                                                      uint32_t nwg, const unsigned long long *__restrict__ tab, uint64_t record_base,
-                                                                      ZaGrepRow *__restrict__ rows, uint64_t rows_cap, uint32_t *__restrict__ lens)
-{
-    __shared__ uint32_t s_n[4][ZA_CLS_MAX_CLASSES];
+    __shared__ uint32_t s_n[4][MAX_CLASSES];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    for (uint32_t i = tid; i < 4u * ZA_CLS_MAX_CLASSES; i += ZA_CLS_WG_RECORDS) (&s_n[0][0])[i] = 0;
+    for (uint32_t c = tid; c < ncls; c += ZA_CLS_WG_RECORDS) { s_n[0][c] = 0; s_n[1][c] = 0; s_n[2][c] = 0; s_n[3][c] = 0; }
     __syncthreads();
     const uint64_t r = (uint64_t)blockIdx.x * ZA_CLS_WG_RECORDS + tid;
-    const uint32_t c = r < nrec ? cls[r] : 0xFFFFFFFFu;
+    const uint32_t c = r < nrec && r < nlab ? lab[r] : 0xFFFFFFFFu;
     const bool mine = c < ncls;
     uint32_t rank = 0;
     uint64_t left = __ballot(mine);
@@ -162,6 +156,33 @@ __global__ __launch_bounds__(ZA_CLS_WG_RECORDS) void za_k_cls_scatter(const uint
     const size_t at = (size_t)c * nwg + blockIdx.x;
     const uint64_t idx = (at ? tab[at - 1u] : 0ull) + rank;
     if (idx >= rows_cap) return;
-    ZaGrepRow w; w.src_off = start[(uint64_t)k_lines * r]; w.number = record_base + r; w.len = len[r]; w.reserved = row[r];
+    ZaGrepRow w; w.src_off = start[(uint64_t)k_lines * r]; w.number = record_base + r; w.len = len[r]; w.reserved = row ? row[r] : c;
     rows[idx] = w; lens[idx] = w.len;
+}
+
+// grid: one workgroup per ZA_CLS_WG_RECORDS records.  za_part_hist with every record's class; the sums go to tot->class_records / class_bytes (zeroed).
+__global__ __launch_bounds__(ZA_CLS_WG_RECORDS) void za_k_cls_hist(const uint8_t *__restrict__ cls, const uint32_t *__restrict__ len, uint64_t nrec, uint32_t ncls,
+                                                                   uint32_t nwg, unsigned long long *__restrict__ tab, ZaClsTotals *__restrict__ tot)
+{
+    za_part_hist<ZA_CLS_MAX_CLASSES, uint8_t>(cls, nrec, len, nrec, ncls, nwg, tab, (unsigned long long *)tot->class_records, (unsigned long long *)tot->class_bytes, nullptr);
+}
+
+// one thread.  nrec > 0.  tot->class_records / class_bytes hold the sums of za_k_cls_hist.
+__global__ void za_k_cls_close(const unsigned long long *__restrict__ start, uint64_t lines, uint64_t nrec, uint32_t k_lines, uint32_t flags, uint64_t text_end,
+                               uint64_t record_base, uint32_t ncls, const unsigned long long *__restrict__ bad, ZaClsTotals *__restrict__ tot)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    uint64_t bytes = 0;
+    for (uint32_t c = 0; c < ncls; c++) bytes += tot->class_bytes[c];
+    tot->covered = 1; tot->seen = nrec; tot->bytes = bytes; tot->n_classes = ncls;
+    za_rec_close(start, lines, nrec, k_lines, flags, text_end, record_base, *bad, 1u, tot);
+}
+
+// grid: one workgroup per ZA_CLS_WG_RECORDS records.  za_part_scatter with every record's class; the row carries the class row in `reserved`.
+__global__ __launch_bounds__(ZA_CLS_WG_RECORDS) void za_k_cls_scatter(const uint8_t *__restrict__ cls, const uint32_t *__restrict__ row, const uint32_t *__restrict__ len,
+                                                                      const unsigned long long *__restrict__ start, uint64_t nrec, uint32_t k_lines, uint32_t ncls,
+                                                                      uint32_t nwg, const unsigned long long *__restrict__ tab, uint64_t record_base,
+                                                                      ZaGrepRow *__restrict__ rows, uint64_t rows_cap, uint32_t *__restrict__ lens)
+{
+    za_part_scatter<ZA_CLS_MAX_CLASSES, uint8_t>(cls, nrec, row, len, start, nrec, k_lines, ncls, nwg, tab, record_base, rows, rows_cap, lens);
 }

@@ -4,8 +4,9 @@
 //   za_k_grep_rec_lines  one workgroup per tile: start[q + 1] = the byte behind the delimiter of line q; a line that matched and passes
 //                        the match_line test stores 1 into hit[q / k]
 //   za_k_grep_rec_eval   one thread per record: selected or not, its length, its first byte; the two arrays the scans sum
+//                        (za_rec_extent: the length and the first byte, as za_k_cls_eval and za_k_part_eval take them too)
 //   (za_k_tbx_reduce / _scan_blocks / _apply)    selected records and their bytes up to every record, inclusive
-//   za_k_grep_rec_close  one thread: the totals
+//   za_k_grep_rec_close  one thread: the totals (za_rec_close: the tail, the short last record and the fault, for the three close kernels)
 //   za_k_grep_rec_emit   one thread per record: its row where the sum of the selected ones steps
 // za_k_offsets, za_k_grep_place and za_k_slice_gather pack the records as they pack lines.  No thread walks a line or a record.
 // Included by zng_amd.hip behind za_grep.hip.
@@ -62,8 +63,31 @@ __global__ __launch_bounds__(256) void za_k_grep_rec_lines(const ulonglong2 *__r
     }
 }
 
-// grid: one thread per record.  lines: entries 0 .. lines of start[] are written.  sel[r] = 1 for a selected record, len[r] = its bytes
-// (0 when it is not selected): what the scans sum.  *bad: the smallest r whose first byte is not first_byte (~0 beforehand).
+// What the three eval kernels (here, za_classify.hip, za_partition.hip) share.  lines: entries 0 .. lines of start[] are written.  -> the
+// bytes of record r; *bad (~0 beforehand): the smallest r whose first byte is not first_byte.
+__device__ __forceinline__ uint64_t za_rec_extent(const uint8_t *__restrict__ scratch, uint64_t text_off, uint64_t text_end, const unsigned long long *__restrict__ start,
+                                                  uint64_t lines, uint64_t r, uint32_t k, int32_t first_byte, unsigned long long *__restrict__ bad)
+{
+    const uint64_t lo = (uint64_t)k * r, hi = lines - lo < k ? lines : lo + k;
+    const uint64_t a = start[lo], e = start[hi];
+    if (first_byte >= 0 && !(a >= text_off && a < text_end && scratch[a] == (uint32_t)first_byte)) atomicMin(bad, (unsigned long long)r);
+    return e > a ? e - a : 0ull;
+}
+
+// What the three close kernels share, for a totals struct of any of them: where the rest behind the complete records begins, the lines
+// of a short last record, and the fault `kind` at record b (b >= nrec: none).
+template <typename Totals>
+__device__ __forceinline__ void za_rec_close(const unsigned long long *__restrict__ start, uint64_t lines, uint64_t nrec, uint32_t k, uint32_t flags, uint64_t text_end,
+                                             uint64_t record_base, unsigned long long b, uint32_t kind, Totals *tot)
+{
+    const uint64_t whole = (uint64_t)k * (lines / k);                  // lines in complete records
+    tot->tail_off = (flags & ZA_GREP_FINAL) ? text_end : start[whole];
+    tot->short_lines = (flags & ZA_GREP_FINAL) ? (uint32_t)(lines - whole) : 0u;
+    tot->bad = 0; tot->bad_record = 0; tot->bad_src = 0;
+    if (b < nrec) { tot->bad = kind; tot->bad_record = record_base + b; tot->bad_src = start[(uint64_t)k * b]; }
+}
+
+// grid: one thread per record.  sel[r] = 1 for a selected record, len[r] = its bytes (0 when it is not selected): what the scans sum.
 __global__ __launch_bounds__(256) void za_k_grep_rec_eval(const uint8_t *__restrict__ scratch, uint64_t text_off, uint64_t text_end,
                                                           const unsigned long long *__restrict__ start, uint64_t lines, const uint8_t *__restrict__ hit,
                                                           uint64_t nrec, uint32_t k, uint32_t invert, int32_t first_byte,
@@ -72,12 +96,10 @@ __global__ __launch_bounds__(256) void za_k_grep_rec_eval(const uint8_t *__restr
 {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nrec) return;
-    const uint64_t lo = (uint64_t)k * r, hi = lines - lo < k ? lines : lo + k;
-    const uint64_t a = start[lo], e = start[hi];
+    const uint64_t n = za_rec_extent(scratch, text_off, text_end, start, lines, r, k, first_byte, bad);
     const uint32_t s = (hit[r] ? 1u : 0u) ^ invert;
     sel[r] = s;
-    len[r] = s && e > a ? e - a : 0ull;
-    if (first_byte >= 0 && !(a >= text_off && a < text_end && scratch[a] == (uint32_t)first_byte)) atomicMin(bad, (unsigned long long)r);
+    len[r] = s ? n : 0ull;
 }
 
 // one thread.  nrec > 0.  sum_sel / sum_len: the totals of the two scans.
@@ -88,11 +110,7 @@ __global__ void za_k_grep_rec_close(const unsigned long long *__restrict__ start
     if (blockIdx.x || threadIdx.x) return;
     ZaGrepRecTotals z = {};
     z.covered = 1; z.seen = nrec; z.selected = *sum_sel; z.bytes = *sum_len;
-    const uint64_t whole = (uint64_t)k * (lines / k);                  // lines in complete records
-    z.tail_off = (flags & ZA_GREP_FINAL) ? text_end : start[whole];
-    z.short_lines = (flags & ZA_GREP_FINAL) ? (uint32_t)(lines - whole) : 0u;
-    const unsigned long long b = *bad;
-    if (b < nrec) { z.bad = 1; z.bad_record = record_base + b; z.bad_src = start[(uint64_t)k * b]; }
+    za_rec_close(start, lines, nrec, k, flags, text_end, record_base, *bad, 1u, &z);
     *totals = z;
 }
 

@@ -3727,18 +3727,23 @@ static void grep_approx_params(std::vector<uint8_t> &par, const uint8_t *pattern
     }
 }
 
+// The window a content call works on, as every driver below takes it: the compressed input and its member rows, the range of the text,
+// the scratch the members decode to and their status words.  And where a call's rows and bytes go: the caller's device buffers, or
+// (own: the host form) the context's, as long as the totals say.
+struct BgzfWindow { const uint8_t *d_in; uint64_t in_len; const ZaMember *d_members; uint32_t n_members; uint64_t text_off, text_end; uint32_t delim;
+                    uint8_t *d_scratch; uint64_t scratch_cap; int32_t *d_status; };
+struct BgzfDest { ZaGrepRow *d_rows; uint64_t rows_cap; uint8_t *d_out; uint64_t out_cap; bool own; };
+
 // decode, cover, mark (max_mismatch 0: za_k_grep_mark; more: za_k_grep_mark_approx), scan, and the host waits for the scan's totals: the first `totals_len` bytes of ZaGrepTotals go to `totals`.
 // After it every tile has its bits, its summary and its carry (gp_bits, gp_tiles, gp_carry), unless covered is 0.
 // marks = false (with max_mismatch 0): the delimiters alone -- za_k_grep_mark with an empty prefilter and no pattern, so no line matches.
-static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
-                                uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
-                                uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap,
-                                int32_t *d_status, void *totals, size_t totals_len, bool marks = true)
+static int bgzf_grep_lines_pass(zngamd_ctx *c, const BgzfWindow &w, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table,
+                                uint32_t n_patterns, uint32_t flags, uint32_t max_mismatch, uint64_t line_base, void *totals, size_t totals_len, bool marks = true)
 {
-    if (text_off > text_end || text_end > scratch_cap) return fail(c, ZNGAMD_E_ARG, "the text lies outside the scratch");
-    if (text_end - text_off >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "a text of 4 GiB or more");
-    const uint64_t tile0 = text_off / ZA_GREP_TILE;
-    const uint32_t ntiles = text_end > text_off ? (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull) : 0u;
+    if (w.text_off > w.text_end || w.text_end > w.scratch_cap) return fail(c, ZNGAMD_E_ARG, "the text lies outside the scratch");
+    if (w.text_end - w.text_off >= (1ull << 32)) return fail(c, ZNGAMD_E_ARG, "a text of 4 GiB or more");
+    const uint64_t tile0 = w.text_off / ZA_GREP_TILE;
+    const uint32_t ntiles = w.text_end > w.text_off ? (uint32_t)((w.text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull) : 0u;
     std::vector<uint8_t> &par = c->gp_host;
     if (!max_mismatch) {
         // the parameter block: a bit per pair of bytes that opens a pattern (a one-byte pattern: every pair with that first byte)
@@ -3758,19 +3763,19 @@ static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_
     ZaGrepTotals *d_tot = (ZaGrepTotals *)c->d_small;
     unsigned long long *d_cover = (unsigned long long *)((uint8_t *)c->d_small + 64);
     HIPCHK(c, hipMemsetAsync(d_cover, 0, 16, c->stream));
-    if (n_members) bgzf_decode_launch(c, d_in, in_len, d_members, n_members, d_scratch, scratch_cap, d_status);
+    if (w.n_members) bgzf_decode_launch(c, w.d_in, w.in_len, w.d_members, w.n_members, w.d_scratch, w.scratch_cap, w.d_status);
     { ProfScope ps(c, ZNGAMD_K_GATHER);
-      if (n_members) hipLaunchKernelGGL(za_k_grep_cover, dim3((n_members + 255u) / 256u), dim3(256), 0, c->stream, d_members, d_status, n_members, scratch_cap,
-                                        text_off, text_end, d_cover);
+      if (w.n_members) hipLaunchKernelGGL(za_k_grep_cover, dim3((w.n_members + 255u) / 256u), dim3(256), 0, c->stream, w.d_members, w.d_status, w.n_members,
+                                          w.scratch_cap, w.text_off, w.text_end, d_cover);
       if (ntiles && !max_mismatch)
-          hipLaunchKernelGGL(za_k_grep_mark, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
+          hipLaunchKernelGGL(za_k_grep_mark, dim3(ntiles), dim3(256), 0, c->stream, w.d_scratch, w.scratch_cap, w.text_off, w.text_end, tile0,
                              (const uint32_t *)c->gp_par.p, (const ZaGrepPat *)(c->gp_par.p + ZA_GREP_PAR_TABLE), c->gp_par.p + ZA_GREP_PAR_BLOB,
-                             marks ? n_patterns : 0u, delim, flags, c->gp_bits.p, c->gp_tiles.p);
+                             marks ? n_patterns : 0u, w.delim, flags, c->gp_bits.p, c->gp_tiles.p);
       else if (ntiles)
-          hipLaunchKernelGGL(za_k_grep_mark_approx, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
-                             (const ZaGrepPat *)c->gp_par.p, (const uint32_t *)(c->gp_par.p + ZA_GREP_APAR_WORDS), n_patterns, delim, flags, max_mismatch,
+          hipLaunchKernelGGL(za_k_grep_mark_approx, dim3(ntiles), dim3(256), 0, c->stream, w.d_scratch, w.scratch_cap, w.text_off, w.text_end, tile0,
+                             (const ZaGrepPat *)c->gp_par.p, (const uint32_t *)(c->gp_par.p + ZA_GREP_APAR_WORDS), n_patterns, w.delim, flags, max_mismatch,
                              c->gp_bits.p, c->gp_tiles.p);
-      hipLaunchKernelGGL(za_k_grep_scan, dim3(1), dim3(ZA_GREP_SCAN_THREADS), 0, c->stream, c->gp_tiles.p, ntiles, tile0, text_off, text_end, flags, line_base,
+      hipLaunchKernelGGL(za_k_grep_scan, dim3(1), dim3(ZA_GREP_SCAN_THREADS), 0, c->stream, c->gp_tiles.p, ntiles, tile0, w.text_off, w.text_end, flags, line_base,
                          d_cover, c->gp_carry.p, d_tot); }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(totals, d_tot, totals_len, hipMemcpyDeviceToHost, c->stream));
@@ -3779,46 +3784,84 @@ static int bgzf_grep_lines_pass(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_
 }
 
 // offsets, place, gather: the n rows' bytes packed into d_out in the order of the rows (gp_lens holds their lengths)
-static void bgzf_grep_pack(zngamd_ctx *c, const ZaMember *d_members, uint32_t n_members, const uint8_t *d_scratch, uint64_t scratch_cap, const int32_t *d_status,
-                           const ZaGrepRow *d_rows, uint64_t n, uint8_t *d_out, uint64_t bytes)
+static void bgzf_grep_pack(zngamd_ctx *c, const BgzfWindow &w, const ZaGrepRow *d_rows, uint64_t n, uint8_t *d_out, uint64_t bytes)
 {
     uint64_t *d_bytes = (uint64_t *)((uint8_t *)c->d_small + 128);
     hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n <= 64 ? 64 : 1024), 0, c->stream, c->gp_lens.p, (uint32_t)n, 0u, 0ull, c->st_off.p, d_bytes,
                        (const ZaUnit *)nullptr);
     hipLaunchKernelGGL(za_k_grep_place, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, c->stream, d_rows, c->st_off.p, n, c->bg_slices.p);
-    hipLaunchKernelGGL(za_k_slice_gather, dim3((uint32_t)n), dim3(256), 0, c->stream, d_scratch, scratch_cap, d_members, d_status, n_members, c->bg_slices.p,
-                       d_out, bytes, c->bg_sstat.p);
+    hipLaunchKernelGGL(za_k_slice_gather, dim3((uint32_t)n), dim3(256), 0, c->stream, w.d_scratch, w.scratch_cap, w.d_members, w.d_status, w.n_members,
+                       c->bg_slices.p, d_out, bytes, c->bg_sstat.p);
 }
 
-// the lines pass, emit, pack.  own: the host form (rows and lines go to the context's buffers, as long as the totals say).
-static int bgzf_grep_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
-                         uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
-                         uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint64_t line_base, uint8_t *d_scratch, uint64_t scratch_cap,
-                         int32_t *d_status, ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own,
-                         zngamd_bgzf_grep_totals *totals)
+// n rows and `bytes` bytes are about to be written: the context's buffers are made to hold them and d names them (own), or the
+// caller's must.  The host has read the totals, so a refusal writes nothing.
+static int bgzf_dest_ready(zngamd_ctx *c, BgzfDest &d, uint64_t n, uint64_t bytes)
+{
+    if (d.own) {
+        HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(bytes + 64));
+        d.d_rows = c->gp_rows.p; d.rows_cap = n; d.d_out = c->bg_out.p; d.out_cap = bytes;
+    } else if (n > d.rows_cap || bytes > d.out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    return ZNGAMD_OK;
+}
+
+extern "C++" {
+// The last step of the four drivers below, once the host has read the totals: the destination, then emit(rows) -- the launch that
+// writes the n rows and their lengths (gp_lens) -- and the pack.
+template <typename Emit>
+static int bgzf_pack_rows(zngamd_ctx *c, const BgzfWindow &w, BgzfDest d, uint64_t n, uint64_t bytes, Emit emit)
+{
+    const int r = bgzf_dest_ready(c, d, n, bytes);
+    if (r) return r;
+    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      emit(d.d_rows);
+      bgzf_grep_pack(c, w, d.d_rows, n, d.d_out, bytes); }
+    c->bgzf_stats[2] += n;
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+// The last step of the four host forms: the n rows (gp_rows) and `bytes` bytes (bg_out) to the caller.  The sizes are known, so the
+// caller's memory is asked for now, rows first, then bytes; without an allocator its buffers must hold them.  head_ok: what the call
+// site asked for in front of the rows is there (classify's class rows), and head() starts its download; rows_too = false: that alone.
+template <typename Head>
+static int bgzf_host_fetch(zngamd_ctx *c, zngamd_alloc_fn alloc, void *user, uint64_t n, uint64_t bytes, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out,
+                           uint64_t out_cap, bool head_ok, bool rows_too, Head head)
+{
+    if (alloc) {
+        if (rows_too) { rows = head_ok ? (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow)) : nullptr; out = rows ? (uint8_t *)alloc(user, bytes) : nullptr; }
+        if (!head_ok || (rows_too && (!rows || !out))) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
+    } else if (!head_ok || (rows_too && (n > rows_cap || bytes > out_cap))) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
+    const int r = head();
+    if (r) return r;
+    if (rows_too) HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return rows_too ? d2h_payload(c, out, c->bg_out.p, bytes) : ZNGAMD_OK;
+}
+static int bgzf_host_fetch(zngamd_ctx *c, zngamd_alloc_fn alloc, void *user, uint64_t n, uint64_t bytes, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out,
+                           uint64_t out_cap)
+{
+    return bgzf_host_fetch(c, alloc, user, n, bytes, rows, rows_cap, out, out_cap, true, true, [] { return ZNGAMD_OK; });
+}
+}  // extern "C++"
+
+// the lines pass, emit, pack
+static int bgzf_grep_dev(zngamd_ctx *c, const BgzfWindow &w, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                         uint32_t flags, uint32_t max_mismatch, uint64_t line_base, const BgzfDest &dst, zngamd_bgzf_grep_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
-    const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, flags,
-                                       max_mismatch, line_base, d_scratch, scratch_cap, d_status, totals, sizeof *totals);
+    const int r = bgzf_grep_lines_pass(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, line_base, totals, sizeof *totals);
     if (r) return r;
-    const uint64_t tile0 = text_off / ZA_GREP_TILE;
-    const uint32_t ntiles = text_end > text_off ? (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull) : 0u;
+    const uint64_t tile0 = w.text_off / ZA_GREP_TILE;
+    const uint32_t ntiles = w.text_end > w.text_off ? (uint32_t)((w.text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull) : 0u;
     const ZaGrepTotals *d_tot = (const ZaGrepTotals *)c->d_small;
     totals->reserved = 0;
     if (!totals->covered || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !totals->matched) return ZNGAMD_OK;
     const uint64_t n = totals->matched;
-    if (own) {
-        HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(totals->bytes + 64));
-        d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; out_cap = totals->bytes;
-    } else if (n > rows_cap || totals->bytes > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
-    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
-    { ProfScope ps(c, ZNGAMD_K_GATHER);
-      hipLaunchKernelGGL(za_k_grep_emit, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_tot, tile0, line_base, text_end,
-                         d_rows, n, c->gp_lens.p);
-      bgzf_grep_pack(c, d_members, n_members, d_scratch, scratch_cap, d_status, d_rows, n, d_out, totals->bytes); }
-    c->bgzf_stats[2] += n;
-    HIPCHK(c, hipGetLastError());
-    return ZNGAMD_OK;
+    return bgzf_pack_rows(c, w, dst, n, totals->bytes, [&](ZaGrepRow *d_rows) {
+        hipLaunchKernelGGL(za_k_grep_emit, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_tot, tile0, line_base, w.text_end,
+                           d_rows, n, c->gp_lens.p); });
 }
 
 int zngamd_bgzf_grep_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
@@ -3842,9 +3885,10 @@ try {
         (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    int r = bgzf_grep_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, patterns, patterns_len, table,
-                          n_patterns, (uint32_t)delim, flags, max_mismatch, line_base, (uint8_t *)d_scratch, scratch_cap, d_status, (ZaGrepRow *)d_rows,
-                          rows_cap, (uint8_t *)d_out, out_cap, false, totals);
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    int r = bgzf_grep_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, line_base,
+                          {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -3872,22 +3916,15 @@ try {
     uint64_t scratch = 0;
     int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
     if (r) return r;
-    r = bgzf_grep_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, (uint32_t)delim, flags,
-                      max_mismatch, line_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, true, totals);
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    r = bgzf_grep_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, line_base, {nullptr, 0, nullptr, 0, true}, totals);
     if (r) return r;
     if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     const uint64_t n = totals->matched;
     if (!totals->covered || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !n) return ZNGAMD_OK;
-    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
-        rows = (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow));
-        out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr;
-        if (!rows || !out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
-    } else if (n > rows_cap || totals->bytes > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
-    HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return d2h_payload(c, out, c->bg_out.p, totals->bytes);
+    return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap);
 } ZA_ABI_GUARD
 
 // ---- records by content (za_grep_records.hip)
@@ -3899,62 +3936,68 @@ static bool grep_records_ok(uint32_t record_lines, int32_t match_line, int32_t f
            first_byte >= -1 && first_byte <= 255;
 }
 
+// The records of a window, once the lines pass has said how many lines its text holds: what the three record drivers below begin with.
+struct BgzfRecords {
+    uint64_t lines, nrec, tile0; uint32_t ntiles, grid;             // grid: workgroups of 256 with a thread per record
+    // lt: what the lines pass read.  covered and tail_off of the call's totals are set.  -> false: the call ends here (the member rows
+    // do not tile the text, or no record has ended).
+    bool begin(const BgzfWindow &w, const ZaGrepTotals &lt, uint32_t flags, uint32_t k, uint32_t *covered, uint64_t *tail_off)
+    {
+        *tail_off = w.text_off;
+        if (!lt.covered) return false;
+        *covered = 1;
+        const bool fin = (flags & ZA_GREP_FINAL) != 0;
+        lines = lt.seen; nrec = fin ? (lines + k - 1u) / k : lines / k;
+        if (fin) *tail_off = w.text_end;
+        if (!nrec) return false;                                  // (without FINAL: fewer than k lines have ended, the open record starts at text_off)
+        tile0 = w.text_off / ZA_GREP_TILE;
+        ntiles = (uint32_t)((w.text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull);      // (a line was decided: the text is not empty)
+        grid = (uint32_t)((nrec + 255u) / 256u);
+        return true;
+    }
+    // where every line starts (gr_start, lines + 1 entries), and a byte per record with a line that matched into hit[] (or none: no pointer, capacity 0)
+    void launch_lines(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, uint32_t k, int32_t match_line, uint8_t *hit, uint64_t hit_cap) const
+    {
+        hipLaunchKernelGGL(za_k_grep_rec_lines, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, (const ZaGrepTotals *)c->d_small,
+                           ntiles, tile0, w.text_off, w.text_end, flags, k, match_line, c->gr_start.p, lines + 1u, hit, hit_cap);
+    }
+};
+
 // the lines pass without INVERT, [the host waits for the line count], lines, eval, the two scans, close, [the host waits for the totals],
-// emit, pack.  own: the host form (rows and records go to the context's buffers, as long as the totals say).
-static int bgzf_grep_records_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
-                                 uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
-                                 uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint32_t k, int32_t match_line, int32_t first_byte, uint64_t record_base,
-                                 uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status, ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out,
-                                 uint64_t out_cap, bool own, zngamd_bgzf_grep_records_totals *totals)
+// emit, pack
+static int bgzf_grep_records_dev(zngamd_ctx *c, const BgzfWindow &w, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table,
+                                 uint32_t n_patterns, uint32_t flags, uint32_t max_mismatch, uint32_t k, int32_t match_line, int32_t first_byte, uint64_t record_base,
+                                 const BgzfDest &dst, zngamd_bgzf_grep_records_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
     ZaGrepTotals lt;
     const uint32_t lflags = flags & (ZA_GREP_LINE_START | ZA_GREP_FINAL);
-    const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim, lflags,
-                                       max_mismatch, 0, d_scratch, scratch_cap, d_status, &lt, sizeof lt);
+    const int r = bgzf_grep_lines_pass(c, w, patterns, patterns_len, table, n_patterns, lflags, max_mismatch, 0, &lt, sizeof lt);
     if (r) return r;
-    totals->tail_off = text_off;
-    if (!lt.covered) return ZNGAMD_OK;
-    totals->covered = 1;
-    const bool fin = (flags & ZA_GREP_FINAL) != 0;
-    const uint64_t lines = lt.seen, nrec = fin ? (lines + k - 1u) / k : lines / k;
-    if (fin) totals->tail_off = text_end;
-    if (!nrec) return ZNGAMD_OK;                                  // (without FINAL: fewer than k lines have ended, the open record starts at text_off)
-    const uint64_t tile0 = text_off / ZA_GREP_TILE;
-    const uint32_t ntiles = (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull);      // (a line was decided: the text is not empty)
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const uint64_t lines = R.lines, nrec = R.nrec;
     HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->gr_hit.ensure(nrec)); HIPCHK(c, c->gr_sel.ensure(nrec)); HIPCHK(c, c->gr_len.ensure(nrec));
     HIPCHK(c, c->tb_blk.ensure(nrec / ZA_TBX_SCAN_ITEMS + 2u));
-    const ZaGrepTotals *d_lt = (const ZaGrepTotals *)c->d_small;
     unsigned long long *d_sums = (unsigned long long *)((uint8_t *)c->d_small + 80);       // the two scans' totals, the first bad record
     ZaGrepRecTotals *d_tot = (ZaGrepRecTotals *)((uint8_t *)c->d_small + 192);
     HIPCHK(c, hipMemsetAsync(c->gr_hit.p, 0, nrec, c->stream));
     HIPCHK(c, hipMemsetAsync(d_sums + 2, 0xFF, 8, c->stream));
-    const uint32_t grid = (uint32_t)((nrec + 255u) / 256u);
     { ProfScope ps(c, ZNGAMD_K_GATHER);
-      hipLaunchKernelGGL(za_k_grep_rec_lines, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_lt, ntiles, tile0, text_off,
-                         text_end, lflags, k, match_line, c->gr_start.p, lines + 1u, c->gr_hit.p, nrec);
-      hipLaunchKernelGGL(za_k_grep_rec_eval, dim3(grid), dim3(256), 0, c->stream, d_scratch, text_off, text_end, c->gr_start.p, lines, c->gr_hit.p, nrec, k,
+      R.launch_lines(c, w, lflags, k, match_line, c->gr_hit.p, nrec);
+      hipLaunchKernelGGL(za_k_grep_rec_eval, dim3(R.grid), dim3(256), 0, c->stream, w.d_scratch, w.text_off, w.text_end, c->gr_start.p, lines, c->gr_hit.p, nrec, k,
                          flags & ZA_GREP_INVERT, first_byte, c->gr_sel.p, c->gr_len.p, d_sums + 2);
       tbx_scan(c, c->gr_sel.p, nrec, ZA_TBX_SUM, d_sums);
       tbx_scan(c, c->gr_len.p, nrec, ZA_TBX_SUM, d_sums + 1);
-      hipLaunchKernelGGL(za_k_grep_rec_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, text_end, record_base, d_sums, d_sums + 1,
+      hipLaunchKernelGGL(za_k_grep_rec_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_sums, d_sums + 1,
                          d_sums + 2, d_tot); }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (totals->bad || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !totals->selected) return ZNGAMD_OK;
     const uint64_t n = totals->selected;
-    if (own) {
-        HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(totals->bytes + 64));
-        d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; out_cap = totals->bytes;
-    } else if (n > rows_cap || totals->bytes > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
-    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
-    { ProfScope ps(c, ZNGAMD_K_GATHER);
-      hipLaunchKernelGGL(za_k_grep_rec_emit, dim3(grid), dim3(256), 0, c->stream, c->gr_sel.p, c->gr_start.p, lines, nrec, k, record_base, d_rows, n, c->gp_lens.p);
-      bgzf_grep_pack(c, d_members, n_members, d_scratch, scratch_cap, d_status, d_rows, n, d_out, totals->bytes); }
-    c->bgzf_stats[2] += n;
-    HIPCHK(c, hipGetLastError());
-    return ZNGAMD_OK;
+    return bgzf_pack_rows(c, w, dst, n, totals->bytes, [&](ZaGrepRow *d_rows) {
+        hipLaunchKernelGGL(za_k_grep_rec_emit, dim3(R.grid), dim3(256), 0, c->stream, c->gr_sel.p, c->gr_start.p, lines, nrec, k, record_base, d_rows, n, c->gp_lens.p); });
 }
 
 int zngamd_bgzf_grep_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
@@ -3980,9 +4023,10 @@ try {
         (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    int r = bgzf_grep_records_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, patterns, patterns_len, table,
-                                  n_patterns, (uint32_t)delim, flags, max_mismatch, record_lines, match_line, first_byte, record_base, (uint8_t *)d_scratch,
-                                  scratch_cap, d_status, (ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false, totals);
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    int r = bgzf_grep_records_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, record_lines, match_line, first_byte, record_base,
+                                  {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -4013,23 +4057,16 @@ try {
     uint64_t scratch = 0;
     int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
     if (r) return r;
-    r = bgzf_grep_records_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, (uint32_t)delim,
-                              flags, max_mismatch, record_lines, match_line, first_byte, record_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr,
-                              0, true, totals);
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    r = bgzf_grep_records_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, record_lines, match_line, first_byte, record_base,
+                              {nullptr, 0, nullptr, 0, true}, totals);
     if (r) return r;
     if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     const uint64_t n = totals->selected;
     if (!totals->covered || totals->bad || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !n) return ZNGAMD_OK;
-    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
-        rows = (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow));
-        out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr;
-        if (!rows || !out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
-    } else if (n > rows_cap || totals->bytes > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
-    HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return d2h_payload(c, out, c->bg_out.p, totals->bytes);
+    return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap);
 } ZA_ABI_GUARD
 
 // ---- records by their nearest pattern (za_classify.hip)
@@ -4046,32 +4083,23 @@ static bool classify_args_ok(const uint8_t *patterns, uint32_t patterns_len, con
 }
 
 // the lines pass for the delimiters alone, [the host waits for the line count], lines, classify, eval, hist, the scan, close, [the host
-// waits for the totals], then the class rows and, with _GROUP, scatter and pack.  own: the host form (class rows stay in cl_row; rows and
-// records go to the context's buffers, as long as the totals say).
-static int bgzf_classify_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
-                             uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
-                             uint32_t delim, uint32_t flags, uint32_t max_mismatch, uint32_t k, int32_t match_line, int32_t first_byte, uint64_t record_base,
-                             uint8_t *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_class_row *d_class, uint64_t class_cap, ZaGrepRow *d_rows,
-                             uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap, bool own, zngamd_bgzf_classify_totals *totals)
+// waits for the totals], then with _GROUP scatter and pack, and the class rows (own: they stay in cl_row).
+static int bgzf_classify_dev(zngamd_ctx *c, const BgzfWindow &w, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                             uint32_t flags, uint32_t max_mismatch, uint32_t k, int32_t match_line, int32_t first_byte, uint64_t record_base,
+                             zngamd_bgzf_class_row *d_class, uint64_t class_cap, BgzfDest dst, zngamd_bgzf_classify_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
     const uint32_t ncls = n_patterns + 2u;
     totals->n_classes = ncls;
     ZaGrepTotals lt;
     const uint32_t lflags = flags & (ZA_GREP_LINE_START | ZA_GREP_FINAL);
-    const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, delim,
-                                       flags & ZA_GREP_FINAL, 0, 0, d_scratch, scratch_cap, d_status, &lt, sizeof lt, false);
+    int r = bgzf_grep_lines_pass(c, w, patterns, patterns_len, table, n_patterns, flags & ZA_GREP_FINAL, 0, 0, &lt, sizeof lt, false);
     if (r) return r;
-    totals->tail_off = text_off;
-    if (!lt.covered) return ZNGAMD_OK;
-    totals->covered = 1;
-    const bool fin = (flags & ZA_GREP_FINAL) != 0, group = (flags & ZA_CLS_GROUP) != 0;
-    const uint64_t lines = lt.seen, nrec = fin ? (lines + k - 1u) / k : lines / k;
-    if (fin) totals->tail_off = text_end;
-    if (!nrec) return ZNGAMD_OK;                                  // (without FINAL: fewer than k lines have ended, the open record starts at text_off)
-    const uint64_t tile0 = text_off / ZA_GREP_TILE;
-    const uint32_t ntiles = (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull);      // (a line was decided: the text is not empty)
-    const uint32_t grid = (uint32_t)((nrec + 255u) / 256u), nwg = (uint32_t)((nrec + ZA_CLS_WG_RECORDS - 1u) / ZA_CLS_WG_RECORDS);
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const bool group = (flags & ZA_CLS_GROUP) != 0;
+    const uint64_t lines = R.lines, nrec = R.nrec;
+    const uint32_t nwg = (uint32_t)((nrec + ZA_CLS_WG_RECORDS - 1u) / ZA_CLS_WG_RECORDS);
     const uint64_t ntab = (uint64_t)ncls * nwg;
     HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_min.ensure(2u * nrec)); HIPCHK(c, c->cl_row.ensure(nrec)); HIPCHK(c, c->cl_len.ensure(nrec));
     HIPCHK(c, c->cl_cls.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab)); HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u));
@@ -4080,7 +4108,6 @@ static int bgzf_classify_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
     grep_approx_params(par, patterns, table, n_patterns);
     HIPCHK(c, c->gp_par.ensure(par.size()));
     HIPCHK(c, hipMemcpyAsync(c->gp_par.p, par.data(), par.size(), hipMemcpyHostToDevice, c->stream));
-    const ZaGrepTotals *d_lt = (const ZaGrepTotals *)c->d_small;
     ZaClsTotals *d_tot = (ZaClsTotals *)c->cl_tot.p;
     unsigned long long *d_bad = (unsigned long long *)(c->cl_tot.p + sizeof(ZaClsTotals)), *d_sum = d_bad + 1;
     uint32_t *d_lo = c->cl_min.p, *d_hi = c->cl_min.p + nrec;
@@ -4088,33 +4115,30 @@ static int bgzf_classify_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
     HIPCHK(c, hipMemsetAsync(d_tot, 0, sizeof(ZaClsTotals), c->stream));
     HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
     { ProfScope ps(c, ZNGAMD_K_GATHER);
-      hipLaunchKernelGGL(za_k_grep_rec_lines, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_lt, ntiles, tile0, text_off,
-                         text_end, lflags, k, match_line, c->gr_start.p, lines + 1u, (uint8_t *)nullptr, 0ull);      // (no line matched: the starts alone)
-      hipLaunchKernelGGL(za_k_grep_classify, dim3(ntiles), dim3(256), 0, c->stream, d_scratch, scratch_cap, text_off, text_end, tile0,
-                         (const ZaGrepPat *)c->gp_par.p, (const uint32_t *)(c->gp_par.p + ZA_GREP_APAR_WORDS), n_patterns, delim, lflags, max_mismatch,
+      R.launch_lines(c, w, lflags, k, match_line, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_grep_classify, dim3(R.ntiles), dim3(256), 0, c->stream, w.d_scratch, w.scratch_cap, w.text_off, w.text_end, R.tile0,
+                         (const ZaGrepPat *)c->gp_par.p, (const uint32_t *)(c->gp_par.p + ZA_GREP_APAR_WORDS), n_patterns, w.delim, lflags, max_mismatch,
                          c->gp_carry.p, k, match_line, nrec, d_lo, d_hi);
-      hipLaunchKernelGGL(za_k_cls_eval, dim3(grid), dim3(256), 0, c->stream, d_scratch, text_off, text_end, c->gr_start.p, lines, d_lo, d_hi, nrec, k,
+      hipLaunchKernelGGL(za_k_cls_eval, dim3(R.grid), dim3(256), 0, c->stream, w.d_scratch, w.text_off, w.text_end, c->gr_start.p, lines, d_lo, d_hi, nrec, k,
                          n_patterns, first_byte, c->cl_row.p, c->cl_cls.p, c->cl_len.p, d_bad);
       hipLaunchKernelGGL(za_k_cls_hist, dim3(nwg), dim3(ZA_CLS_WG_RECORDS), 0, c->stream, c->cl_cls.p, c->cl_len.p, nrec, ncls, nwg, c->cl_tab.p, d_tot);
       tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
-      hipLaunchKernelGGL(za_k_cls_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, text_end, record_base, ncls, d_bad, d_tot); }
+      hipLaunchKernelGGL(za_k_cls_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, ncls, d_bad, d_tot); }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (totals->bad) return ZNGAMD_OK;
     const uint64_t n = totals->seen;
-    if (own) {
-        if (group) { HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(totals->bytes + 64)); d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; }
-    } else if (n > class_cap || (group && (n > rows_cap || totals->bytes > out_cap))) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
-    else HIPCHK(c, hipMemcpyAsync(d_class, c->cl_row.p, (size_t)n * 4u, hipMemcpyDeviceToDevice, c->stream));
-    if (!group) return ZNGAMD_OK;
-    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
-    { ProfScope ps(c, ZNGAMD_K_GATHER);
-      hipLaunchKernelGGL(za_k_cls_scatter, dim3(nwg), dim3(ZA_CLS_WG_RECORDS), 0, c->stream, c->cl_cls.p, c->cl_row.p, c->cl_len.p, c->gr_start.p, nrec, k, ncls, nwg,
-                         c->cl_tab.p, record_base, d_rows, n, c->gp_lens.p);
-      bgzf_grep_pack(c, d_members, n_members, d_scratch, scratch_cap, d_status, d_rows, n, d_out, totals->bytes); }
-    c->bgzf_stats[2] += n;
-    HIPCHK(c, hipGetLastError());
+    // The class rows are n entries more for the caller's memory to hold: one capacity stands for both arrays; without _GROUP there
+    // are no rows and no bytes, and the class rows alone are judged.
+    if (!dst.own) dst.rows_cap = group ? std::min(dst.rows_cap, class_cap) : class_cap;
+    if (group)
+        r = bgzf_pack_rows(c, w, dst, n, totals->bytes, [&](ZaGrepRow *d_rows) {
+            hipLaunchKernelGGL(za_k_cls_scatter, dim3(nwg), dim3(ZA_CLS_WG_RECORDS), 0, c->stream, c->cl_cls.p, c->cl_row.p, c->cl_len.p, c->gr_start.p, nrec, k, ncls,
+                               nwg, c->cl_tab.p, record_base, d_rows, n, c->gp_lens.p); });
+    else if (!dst.own) r = bgzf_dest_ready(c, dst, n, 0);
+    if (r) return r;
+    if (!dst.own) HIPCHK(c, hipMemcpyAsync(d_class, c->cl_row.p, (size_t)n * 4u, hipMemcpyDeviceToDevice, c->stream));
     return ZNGAMD_OK;
 }
 
@@ -4130,9 +4154,10 @@ try {
         (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    int r = bgzf_classify_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, patterns, patterns_len, table,
-                              n_patterns, (uint32_t)delim, flags, max_mismatch, record_lines, match_line, first_byte, record_base, (uint8_t *)d_scratch,
-                              scratch_cap, d_status, d_class, class_cap, (ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false, totals);
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    int r = bgzf_classify_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, record_lines, match_line, first_byte, record_base, d_class,
+                              class_cap, {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -4152,9 +4177,9 @@ try {
     uint64_t scratch = 0;
     int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
     if (r) return r;
-    r = bgzf_classify_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, patterns, patterns_len, table, n_patterns, (uint32_t)delim, flags,
-                          max_mismatch, record_lines, match_line, first_byte, record_base, c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, nullptr, 0,
-                          true, totals);
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    r = bgzf_classify_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, record_lines, match_line, first_byte, record_base, nullptr, 0,
+                          {nullptr, 0, nullptr, 0, true}, totals);
     if (r) return r;
     if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -4162,15 +4187,9 @@ try {
     const uint64_t n = totals->seen;
     const bool group = (flags & ZNGAMD_BGZF_CLASSIFY_GROUP) != 0;
     if (!totals->covered || totals->bad || !n) return ZNGAMD_OK;
-    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now: class rows, rows, bytes
-        cls = (zngamd_bgzf_class_row *)alloc(user, n * sizeof(zngamd_bgzf_class_row));
-        if (group) { rows = cls ? (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow)) : nullptr; out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr; }
-        if (!cls || (group && (!rows || !out))) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
-    } else if (n > class_cap || (group && (n > rows_cap || totals->bytes > out_cap))) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
-    HIPCHK(c, hipMemcpyAsync(cls, c->cl_row.p, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
-    if (group) HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return group ? d2h_payload(c, out, c->bg_out.p, totals->bytes) : ZNGAMD_OK;
+    if (alloc) cls = (zngamd_bgzf_class_row *)alloc(user, n * sizeof(zngamd_bgzf_class_row));      // the caller's memory is asked for: class rows, rows, bytes
+    return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap, alloc ? cls != nullptr : n <= class_cap, group,
+                           [&] { HIPCHK(c, hipMemcpyAsync(cls, c->cl_row.p, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream)); return ZNGAMD_OK; });
 } ZA_ABI_GUARD
 
 // ---- records by the caller's labels (za_partition.hip)
@@ -4184,12 +4203,10 @@ static bool partition_args_ok(int delim, uint32_t flags, uint32_t record_lines, 
 }
 
 // the lines pass for the delimiters alone, [the host waits for the line count], lines, eval, hist, with _GROUP the scan, close, [the
-// host waits for the totals and the counts], then with _GROUP scatter and pack.  own: the host form (labels is host memory and goes to
-// pt_lab once the line count says how many are needed; rows and records go to the context's buffers, as long as the totals say).
-static int bgzf_partition_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len, const ZaMember *d_members, uint32_t n_members, uint64_t text_off,
-                              uint64_t text_end, uint32_t delim, uint32_t flags, uint32_t k, int32_t first_byte, uint64_t record_base, uint8_t *d_scratch,
-                              uint64_t scratch_cap, int32_t *d_status, ZaGrepRow *d_rows, uint64_t rows_cap, uint8_t *d_out, uint64_t out_cap,
-                              const uint16_t *labels, uint64_t n_labels, uint32_t ncls, uint64_t *class_records, uint64_t *class_bytes, bool own,
+// host waits for the totals and the counts], then with _GROUP scatter and pack.  dst.own: labels is host memory and goes to pt_lab once
+// the line count says how many are needed.
+static int bgzf_partition_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, uint32_t k, int32_t first_byte, uint64_t record_base, const BgzfDest &dst,
+                              const uint16_t *labels, uint64_t n_labels, uint32_t ncls, uint64_t *class_records, uint64_t *class_bytes,
                               zngamd_bgzf_partition_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
@@ -4198,41 +4215,32 @@ static int bgzf_partition_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_le
     static const uint8_t no_bytes[1] = {0};
     static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL;
-    const int r = bgzf_grep_lines_pass(c, d_in, in_len, d_members, n_members, text_off, text_end, no_bytes, 0, no_table, 0, delim, lflags, 0, 0, d_scratch,
-                                       scratch_cap, d_status, &lt, sizeof lt, false);
+    const int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
     if (r) return r;
-    totals->tail_off = text_off;
-    if (!lt.covered) return ZNGAMD_OK;
-    totals->covered = 1;
-    const bool fin = (flags & ZA_GREP_FINAL) != 0, group = (flags & ZA_CLS_GROUP) != 0;
-    const uint64_t lines = lt.seen, nrec = fin ? (lines + k - 1u) / k : lines / k;
-    if (fin) totals->tail_off = text_end;
-    if (!nrec) return ZNGAMD_OK;                                  // (without FINAL: fewer than k lines have ended, the open record starts at text_off)
-    const uint64_t nlab = std::min<uint64_t>(n_labels, nrec);
-    const uint64_t tile0 = text_off / ZA_GREP_TILE;
-    const uint32_t ntiles = (uint32_t)((text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull);      // (a line was decided: the text is not empty)
-    const uint32_t grid = (uint32_t)((nrec + 255u) / 256u), nwg = (uint32_t)((nrec + ZA_PART_WG_RECORDS - 1u) / ZA_PART_WG_RECORDS);
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const bool group = (flags & ZA_CLS_GROUP) != 0;
+    const uint64_t lines = R.lines, nrec = R.nrec, nlab = std::min<uint64_t>(n_labels, nrec);
+    const uint32_t nwg = (uint32_t)((nrec + ZA_PART_WG_RECORDS - 1u) / ZA_PART_WG_RECORDS);
     const uint64_t ntab = (uint64_t)ncls * nwg;
     HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab));
     HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u)); HIPCHK(c, c->pt_tot.ensure(12u + 2u * ZA_PART_MAX_CLASSES));
-    if (own && nlab) {
+    if (dst.own && nlab) {
         HIPCHK(c, c->pt_lab.ensure(nlab));
         HIPCHK(c, hipMemcpyAsync(c->pt_lab.p, labels, (size_t)nlab * 2u, hipMemcpyHostToDevice, c->stream));
         labels = c->pt_lab.p;
     }
-    const ZaGrepTotals *d_lt = (const ZaGrepTotals *)c->d_small;
     ZaPartTotals *d_tot = (ZaPartTotals *)c->pt_tot.p;                                   // 9 words; then the two faults, the scan's sum, the counts
     unsigned long long *d_bad = c->pt_tot.p + 9, *d_sum = c->pt_tot.p + 11, *d_cnt = c->pt_tot.p + 12;
     HIPCHK(c, hipMemsetAsync(c->pt_tot.p, 0, (12u + 2u * (size_t)ncls) * 8u, c->stream));
     HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 16, c->stream));
     { ProfScope ps(c, ZNGAMD_K_GATHER);
-      hipLaunchKernelGGL(za_k_grep_rec_lines, dim3(ntiles), dim3(256), 0, c->stream, c->gp_bits.p, c->gp_tiles.p, c->gp_carry.p, d_lt, ntiles, tile0, text_off,
-                         text_end, lflags, k, -1, c->gr_start.p, lines + 1u, (uint8_t *)nullptr, 0ull);      // (no line matched: the starts alone)
-      hipLaunchKernelGGL(za_k_part_eval, dim3(grid), dim3(256), 0, c->stream, d_scratch, text_off, text_end, c->gr_start.p, lines, labels, nlab, nrec, k, ncls,
-                         first_byte, c->cl_len.p, d_bad);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_part_eval, dim3(R.grid), dim3(256), 0, c->stream, w.d_scratch, w.text_off, w.text_end, c->gr_start.p, lines, labels, nlab, nrec, k,
+                         ncls, first_byte, c->cl_len.p, d_bad);
       hipLaunchKernelGGL(za_k_part_hist, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, labels, nlab, c->cl_len.p, nrec, ncls, nwg, c->cl_tab.p, d_cnt, d_tot);
       if (group) tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
-      hipLaunchKernelGGL(za_k_part_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, nlab, k, lflags, text_end, record_base, ncls, d_cnt, d_bad,
+      hipLaunchKernelGGL(za_k_part_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, nlab, k, lflags, w.text_end, record_base, ncls, d_cnt, d_bad,
                          d_tot); }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
@@ -4241,18 +4249,9 @@ static int bgzf_partition_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_le
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const uint64_t n = totals->seen - totals->dropped;
     if (totals->bad || totals->labels_short || !group || !n) return ZNGAMD_OK;
-    if (own) {
-        HIPCHK(c, c->gp_rows.ensure(n)); HIPCHK(c, c->bg_out.ensure(totals->bytes + 64));
-        d_rows = c->gp_rows.p; rows_cap = n; d_out = c->bg_out.p; out_cap = totals->bytes;
-    } else if (n > rows_cap || totals->bytes > out_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
-    HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n)); HIPCHK(c, c->bg_slices.ensure(n + 1)); HIPCHK(c, c->bg_sstat.ensure(n + 1));
-    { ProfScope ps(c, ZNGAMD_K_GATHER);
-      hipLaunchKernelGGL(za_k_part_scatter, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, labels, nlab, c->cl_len.p, c->gr_start.p, nrec, k, ncls, nwg,
-                         c->cl_tab.p, record_base, d_rows, n, c->gp_lens.p);
-      bgzf_grep_pack(c, d_members, n_members, d_scratch, scratch_cap, d_status, d_rows, n, d_out, totals->bytes); }
-    c->bgzf_stats[2] += n;
-    HIPCHK(c, hipGetLastError());
-    return ZNGAMD_OK;
+    return bgzf_pack_rows(c, w, dst, n, totals->bytes, [&](ZaGrepRow *d_rows) {
+        hipLaunchKernelGGL(za_k_part_scatter, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, labels, nlab, c->cl_len.p, c->gr_start.p, nrec, k, ncls, nwg,
+                           c->cl_tab.p, record_base, d_rows, n, c->gp_lens.p); });
 }
 
 int zngamd_bgzf_partition_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
@@ -4265,9 +4264,10 @@ try {
     if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    int r = bgzf_partition_dev(c, (const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, flags, record_lines,
-                               first_byte, record_base, (uint8_t *)d_scratch, scratch_cap, d_status, (ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap,
-                               d_labels, n_labels, n_classes, class_records, class_bytes, false, totals);
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    int r = bgzf_partition_dev(c, w, flags, record_lines, first_byte, record_base, {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, d_labels,
+                               n_labels, n_classes, class_records, class_bytes, totals);
     if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -4286,22 +4286,16 @@ try {
     uint64_t scratch = 0;
     int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
     if (r) return r;
-    r = bgzf_partition_dev(c, c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, flags, record_lines, first_byte, record_base,
-                           c->st_out.p, scratch, c->mstatus.p, nullptr, 0, nullptr, 0, labels, n_labels, n_classes, class_records, class_bytes, true, totals);
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    r = bgzf_partition_dev(c, w, flags, record_lines, first_byte, record_base, {nullptr, 0, nullptr, 0, true}, labels, n_labels, n_classes, class_records,
+                           class_bytes, totals);
     if (r) return r;
     if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
     const uint64_t n = totals->seen - totals->dropped;
     if (!totals->covered || totals->bad || totals->labels_short || !(flags & ZNGAMD_BGZF_CLASSIFY_GROUP) || !n) return ZNGAMD_OK;
-    if (alloc) {                                          // the sizes are known: the caller's memory is asked for now, rows first
-        rows = (zngamd_bgzf_grep_row *)alloc(user, n * sizeof(ZaGrepRow));
-        out = rows ? (uint8_t *)alloc(user, totals->bytes) : nullptr;
-        if (!rows || !out) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned no memory");
-    } else if (n > rows_cap || totals->bytes > out_cap) return fail(c, ZNGAMD_BUF_ERROR, "output buffer too small");
-    HIPCHK(c, hipMemcpyAsync(rows, c->gp_rows.p, (size_t)n * sizeof(ZaGrepRow), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return d2h_payload(c, out, c->bg_out.p, totals->bytes);
+    return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap);
 } ZA_ABI_GUARD
 
 // ---- fields of a line (za_tabix.hip)

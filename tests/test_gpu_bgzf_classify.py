@@ -231,12 +231,10 @@ def reads(rng, n, barcodes):
     return out
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, WG + 1, 3 * WG + 5])
-def test_grouping(ctx, n):
+def grouped(ctx, n, barcodes, recs):
+    """the _GROUP call at k = 1 on the bases line, from the line's start, against the referee: counts, class rows, rows, packed bytes"""
     from zlib_ng_amd import _lib, bgzf
-    rng = random.Random(n)
-    barcodes = [A, B, b"GGGGCCCCAAAATTTT", mutate(rng, A, 2, b"\n")]          # the last one is two off the first: ties at k = 1
-    recs = reads(rng, n, barcodes)
+    ncls = len(barcodes) + 2
     text = b"".join(recs)
     blob = bgzf.compress(text, block_size=4099)
     tab, _ = block_map(blob)
@@ -245,9 +243,9 @@ def test_grouping(ctx, n):
     v = classify_ref.classify(text, b"\n", barcodes, 1, 4, 1, True)
     G = _lib.BGZF_GREP_FINAL | _lib.BGZF_GREP_LINE_START | _lib.BGZF_CLASSIFY_GROUP
     code, status, tot, cls, rows, packed = ctx.bgzf_classify_records(blob, members, 0, len(text), *table, 10, G, 1, 4, 1, ord("@"), 500)
-    assert code == 0 and not status.any() and (tot.covered, tot.bad, tot.seen, tot.bytes, tot.n_classes) == (1, 0, n, len(text), 6)
-    assert list(tot.class_records)[:6] == v.counts.tolist() and not any(list(tot.class_records)[6:]) and not any(list(tot.class_bytes)[6:])
-    assert sum(tot.class_bytes) == len(text) and [tot.class_bytes[c] for c in range(6)] == [len(v.of_class(c)) for c in range(6)]
+    assert code == 0 and not status.any() and (tot.covered, tot.bad, tot.seen, tot.bytes, tot.n_classes) == (1, 0, n, len(text), ncls)
+    assert list(tot.class_records)[:ncls] == v.counts.tolist() and not any(list(tot.class_records)[ncls:]) and not any(list(tot.class_bytes)[ncls:])
+    assert sum(tot.class_bytes) == len(text) and [tot.class_bytes[c] for c in range(ncls)] == [len(v.of_class(c)) for c in range(ncls)]
     # the class rows, in record order
     want_flags = np.where(v.pattern >= 0, 1, np.where(v.pattern == classify_ref.AMBIGUOUS, 2, 0))
     assert cls["flags"].tolist() == want_flags.tolist() and cls["distance"].tolist() == v.distance.tolist()
@@ -259,7 +257,7 @@ def test_grouping(ctx, n):
     assert rows["src_off"].tolist() == starts[:-1][order].tolist() and rows["len"].tolist() == np.diff(starts)[order].tolist()
     assert rows["reserved"].tolist() == cls.view(np.uint32)[order].tolist()
     at = 0
-    for c in range(6):
+    for c in range(ncls):
         assert bytes(packed[at:at + tot.class_bytes[c]]) == v.of_class(c), (n, c)
         at += tot.class_bytes[c]
     assert at == len(packed) == len(text)
@@ -267,6 +265,33 @@ def test_grouping(ctx, n):
     code, status, tot2, cls2, rows2, packed2 = ctx.bgzf_classify_records(blob, members, 0, len(text), *table, 10, G & ~_lib.BGZF_CLASSIFY_GROUP, 1, 4, 1,
                                                                          ord("@"), 500)
     assert code == 0 and cls2.tobytes() == cls.tobytes() and len(rows2) == 0 and packed2 == b"" and list(tot2.class_records) == list(tot.class_records)
+    return v
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, WG + 1, 3 * WG + 5])
+def test_grouping(ctx, n):
+    rng = random.Random(n)
+    barcodes = [A, B, b"GGGGCCCCAAAATTTT", mutate(rng, A, 2, b"\n")]          # the last one is two off the first: ties at k = 1
+    grouped(ctx, n, barcodes, reads(rng, n, barcodes))
+
+
+@pytest.mark.parametrize("n", [WG + 1, 3 * WG + 5])
+def test_grouping_every_class(ctx, n):
+    """64 barcodes, 66 classes: read i begins with barcode i % 65, and 64 stands for random bases -- so every wave of the scatter holds
+    64 different classes (one round of its ballot loop each) and the class loops of both kernels run past thread 63"""
+    rng = random.Random(1000 + n)
+    barcodes = []
+    while len(barcodes) < 64:                                                 # any two at least 3 places apart: no tie at k = 1
+        p = bytes(rng.choice(b"ACGT") for _ in range(16))
+        if all(sum(x != y for x, y in zip(p, q)) >= 3 for q in barcodes):
+            barcodes.append(p)
+    recs = []
+    for i in range(n):
+        head = barcodes[i % 65] if i % 65 < 64 else bytes(rng.choice(b"ACGT") for _ in range(16))
+        s = head + bytes(rng.choice(b"ACGT") for _ in range(rng.randrange(1, 60)))
+        recs.append(b"@read%d\n%s\n+\n%s\n" % (i, s, b"F" * len(s)))
+    v = grouped(ctx, n, barcodes, recs)
+    assert len(set(v.cls.tolist())) >= 65 and all(len(set(v.cls[a:a + 64].tolist())) == 64 for a in range(0, n - 63, 64))
 
 
 @pytest.fixture(scope="module")
