@@ -778,6 +778,108 @@ int zngamd_bgzf_partition_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t i
                                   uint64_t n_labels, uint32_t n_classes, uint64_t *class_records, uint64_t *class_bytes,
                                   zngamd_bgzf_partition_totals *totals);
 
+/* ---- BGZF trimmed (zlib_ng_amd/bgzf.py: trim_records).  The first record call that changes the records it
+ * returns: the read of every record is cut as cutadapt, fastp or Trimmomatic cut it, and what is left is written.  The record model is
+ * that of zngamd_bgzf_grep_records (record_lines k, first_byte, _FINAL, the open tail, the cover contract).  conf names two lines of
+ * the record: seq_line s (0 <= s < k) and qual_line q (-1: none; otherwise 0 <= q < k, q != s).  A line's body is its bytes without
+ * the delimiter; a CR is a body byte.  A short last record under _FINAL is judged on the lines it has: a line it lacks is an empty
+ * body and is not written.  For a seq body of n bytes the rule yields a cut [a, b), 0 <= a <= b <= n, in this order, in integers:
+ *   1. fixed cut: a = min(cut_front, n); b = max(a, n - min(cut_back, n)).
+ *   2. quality (q >= 0; qual_front / qual_back 0 .. 93, 0: off; Q_i = qual[i] - quality_base, signed).  Both scans run over the [a, b)
+ *      of step 1, independently.  3' scan: s = best = 0, b' = b; for i = b - 1 down to a: s += qual_back - Q_i; s < 0 stops; s > best:
+ *      best = s, b' = i.  5' scan: s = best = 0, a' = a; for i = a up: s += qual_front - Q_i; s < 0 stops; s > best: best = s,
+ *      a' = i + 1.  Then a = a', b = max(a', b').  (BWA's rule, the one behind cutadapt -q.)  The sums are kept in 64 bits.
+ *   3. adapters (3' adapters: n_patterns 0 .. 64 of 1 .. 255 bytes, none holding the delimiter).  R = seq[a, b), m = b - a.  Adapter j of
+ *      L bytes matches at p (0 <= p < m) with overlap o = min(L, m - p) when o >= min(min_overlap, L) and R[p, p + o) differs from its
+ *      first o bytes in at most (max_mismatch * o) / L places.  max_mismatch is 0 .. 16 and less than the shortest adapter: a budget for
+ *      the whole adapter, of which a partial overlap gets its share.  min_overlap is 1 .. 255.  The smallest p at which any adapter
+ *      matches wins, there the lowest j; then b = a + p and the record counts in adapter_records[j].  Bytes are compared as they are.
+ *   4. verdict: _TRIM_DROPPED when the drop mask says so (drop[r] != 0 for record record_base + r of the call; drop = NULL: no record is
+ *      dropped; with a mask, records at or beyond n_drop are dropped ones and set drop_short, and nothing is written); otherwise
+ *      _TRIM_TOO_SHORT when b - a < min_length; otherwise _TRIM_KEPT.  Dropped records are cut and counted like the others.
+ * Written for a record: its lines in order, lines s and q with the body bytes [a, b), every other line whole, every delimiter the
+ * source has; a read cut to nothing leaves two empty lines.  Faults: bad = 1, a first_byte violation; bad = 3, q >= 0 and the two
+ * bodies differ in length (2 is the label fault of zngamd_bgzf_partition_records and is not used here).  Of the two the one at the
+ * smaller record is reported, a record with both for its first byte; with bad set nothing is written, the counts are valid except that
+ * a record whose bodies differ is cut by step 1 alone.
+ * flags: _FINAL and ZNGAMD_BGZF_CLASSIFY_GROUP; anything else is ZNGAMD_E_ARG.  Without _GROUP only d_trim[0 .. seen), one row per
+ * record in record order, and the totals leave the kernels.  With _GROUP d_rows holds a row per kept record (and, with
+ * ZNGAMD_BGZF_TRIM_KEEP_SHORT in conf.flags, behind them one per too-short record), each class in record order (src_off: where the
+ * record starts in the scratch; number = record_base + r; len: its bytes as written; reserved: 0 kept, 1 too short), and d_out the
+ * records as written in that order: `kept` rows and then `too_short` rows.  ZNGAMD_BUF_ERROR: trim_cap < seen or, with _GROUP,
+ * rows_cap or out_cap too small; nothing is written, the totals are valid.  Hostile arguments -- conf NULL or a field out of range,
+ * q == s, a quality cutoff with q = -1, a reserved word set, adapters that break the limits above, max_mismatch >= an adapter's
+ * length, drop NULL with n_drop > 0, flags, totals NULL -- are ZNGAMD_E_ARG before the context is touched.  Device memory beside the
+ * tiles: 8 bytes per line and 18 bytes per record of the text (19 with the host form's copy of the mask), and 16 bytes per 256 records. */
+#define ZNGAMD_BGZF_TRIM_KEPT       0u
+#define ZNGAMD_BGZF_TRIM_TOO_SHORT  1u
+#define ZNGAMD_BGZF_TRIM_DROPPED    2u
+#define ZNGAMD_BGZF_TRIM_KEEP_SHORT 1u   /* conf.flags: the too-short records are gathered behind the kept ones, not only counted */
+#define ZNGAMD_BGZF_TRIM_NO_ADAPTER 255u
+#define ZNGAMD_BGZF_TRIM_MAX_QUALITY 93u
+typedef struct {
+    uint32_t record_lines;  /* k, 1 .. 64 */
+    int32_t  seq_line;      /* s */
+    int32_t  qual_line;     /* q; -1: none */
+    int32_t  first_byte;    /* 0 .. 255; -1: no check */
+    uint32_t cut_front;     /* step 1 */
+    uint32_t cut_back;
+    uint32_t qual_front;    /* step 2: 0 .. 93; 0: off */
+    uint32_t qual_back;
+    uint32_t quality_base;  /* 0 .. 255; 33 for Sanger / Illumina 1.8+ */
+    uint32_t max_mismatch;  /* step 3 */
+    uint32_t min_overlap;   /* 1 .. 255 */
+    uint32_t min_length;    /* step 4 */
+    uint32_t flags;         /* ZNGAMD_BGZF_TRIM_KEEP_SHORT */
+    uint32_t reserved[3];   /* 0 */
+} zngamd_bgzf_trim_conf;                                                                          /* 64 B */
+typedef struct {
+    uint32_t begin;         /* a */
+    uint32_t end;           /* b */
+    uint8_t  adapter;       /* j; ZNGAMD_BGZF_TRIM_NO_ADAPTER: none */
+    uint8_t  verdict;       /* ZNGAMD_BGZF_TRIM_KEPT / _TOO_SHORT / _DROPPED */
+    uint8_t  steps;         /* bit 0: the fixed cut moved an end, bit 1: quality did, bit 2: an adapter did */
+    uint8_t  reserved;
+} zngamd_bgzf_trim_row;                                                                           /* 12 B */
+typedef struct {
+    uint64_t seen;            /* records of the text that were decided (the open tail is not one of them) */
+    uint64_t kept;            /* of them, per verdict */
+    uint64_t too_short;
+    uint64_t dropped;
+    uint64_t bytes_in;        /* bytes of the records as they lie in the text */
+    uint64_t bytes;           /* bytes of the records as written: the kept ones and, with _TRIM_KEEP_SHORT, the too-short ones */
+    uint64_t bases_in;        /* sum of n */
+    uint64_t bases_out;       /* sum of b - a over the kept records */
+    uint64_t quality_trimmed; /* bases step 2 took, over all records */
+    uint64_t adapter_trimmed; /* bases step 3 took, over all records */
+    uint64_t tail_off;        /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;      /* bad != 0: the number of the record at fault */
+    uint64_t bad_src;         /*           and where it starts in the scratch */
+    uint32_t covered;         /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;     /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;             /* 0; 1: the first byte is not first_byte; 3: the bodies of seq_line and qual_line differ in length */
+    uint32_t drop_short;      /* 1: the text holds more records than n_drop */
+    uint64_t adapter_records[ZNGAMD_BGZF_GREP_MAX_PATTERNS];      /* records cut at adapter j */
+} zngamd_bgzf_trim_totals;                                                                        /* 632 B */
+int zngamd_bgzf_trim_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                 uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                                 const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags,
+                                 const zngamd_bgzf_trim_conf *conf, uint64_t record_base, void *d_scratch, uint64_t scratch_cap,
+                                 int32_t *d_status, const uint8_t *d_drop, uint64_t n_drop, zngamd_bgzf_trim_row *d_trim, uint64_t trim_cap,
+                                 zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap,
+                                 zngamd_bgzf_trim_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; drop is host memory, of which min(n_drop, seen) bytes are uploaded once
+ * the line count is known; status, the trim rows and, with _GROUP, the rows and the written records come back.  With alloc (trim =
+ * rows = out = NULL, the capacities 0) the caller's memory is asked for once the sizes are known, in the order trim rows (seen * 12
+ * bytes), rows ((kept [+ too_short]) * 24 bytes), bytes -- the last two with _GROUP and a record to write only; NULL from it:
+ * ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_trim_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                             uint64_t text_off, uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len,
+                             const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags,
+                             const zngamd_bgzf_trim_conf *conf, uint64_t record_base, int32_t *status, const uint8_t *drop, uint64_t n_drop,
+                             zngamd_bgzf_trim_row *trim, uint64_t trim_cap, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out,
+                             uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_trim_totals *totals);
+
 /* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
  * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM
  * preset, is ZNGAMD_E_ARG), the columns of the name, the start and the end (from 1; col_end 0: none), the byte that opens a comment

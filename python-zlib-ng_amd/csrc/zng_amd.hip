@@ -13,6 +13,7 @@
 #include "za_grep_records.hip"
 #include "za_classify.hip"
 #include "za_partition.hip"
+#include "za_trim.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
 #include "za_batch.hip"
@@ -53,6 +54,11 @@ static_assert(sizeof(zngamd_bgzf_classify_totals) == sizeof(ZaClsTotals) && offs
 static_assert(sizeof(zngamd_bgzf_partition_totals) == sizeof(ZaPartTotals) && sizeof(ZaPartTotals) == 72 && offsetof(ZaPartTotals, covered) == offsetof(zngamd_bgzf_partition_totals, covered) &&
               offsetof(ZaPartTotals, labels_short) == offsetof(zngamd_bgzf_partition_totals, labels_short) && ZNGAMD_BGZF_PARTITION_MAX_CLASSES == ZA_PART_MAX_CLASSES &&
               ZNGAMD_BGZF_PARTITION_DROP == ZA_PART_DROP && ZA_PART_WG_RECORDS == ZA_CLS_WG_RECORDS, "bgzf partition layout");
+static_assert(sizeof(zngamd_bgzf_trim_totals) == sizeof(ZaTrimTotals) && sizeof(ZaTrimTotals) == 632 && offsetof(ZaTrimTotals, covered) == offsetof(zngamd_bgzf_trim_totals, covered) &&
+              offsetof(ZaTrimTotals, adapter_records) == offsetof(zngamd_bgzf_trim_totals, adapter_records) && sizeof(zngamd_bgzf_trim_row) == sizeof(ZaTrimRow) &&
+              sizeof(ZaTrimRow) == 12 && sizeof(zngamd_bgzf_trim_conf) == 64 && ZNGAMD_BGZF_TRIM_KEPT == ZA_TRIM_KEPT && ZNGAMD_BGZF_TRIM_TOO_SHORT == ZA_TRIM_TOO_SHORT &&
+              ZNGAMD_BGZF_TRIM_DROPPED == ZA_TRIM_DROPPED && ZNGAMD_BGZF_TRIM_KEEP_SHORT == ZA_TRIM_KEEP_SHORT && ZNGAMD_BGZF_TRIM_NO_ADAPTER == ZA_TRIM_NO_ADAPTER &&
+              ZA_TRIM_STAGE_WORDS == 16u + (ZA_GREP_MAX_LEN + 3u) / 4u, "bgzf trim layout");
 static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_tabix_name) == sizeof(ZaTbxName) && sizeof(zngamd_tabix_bin) == sizeof(ZaTbxBin) &&
               sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
               sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
@@ -169,6 +175,9 @@ struct zngamd_ctx {
     // records by the caller's labels (za_partition.hip, section 5f.4; lengths and table are cl_len and cl_tab): the host form's labels; the
     // totals, the two first faults, the scan's sum, records and bytes per class
     DevBuf<uint16_t> pt_lab; DevBuf<unsigned long long> pt_tot;
+    // records trimmed (za_trim.hip, section 5f.5; line starts, lengths, table and labels are gr_start, cl_len, cl_tab and pt_lab): the trim
+    // rows; the host form's drop mask; the totals, the two first faults, the scan's sum, the counts and what za_k_part_hist sums beside them
+    DevBuf<ZaTrimRow> tr_row; DevBuf<uint8_t> tr_drop; DevBuf<unsigned long long> tr_tot;
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -322,6 +331,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->gp_par.release(); c->gp_bits.release(); c->gp_tiles.release(); c->gp_carry.release(); c->gp_rows.release(); c->gp_lens.release();
     c->gr_start.release(); c->gr_sel.release(); c->gr_len.release(); c->gr_hit.release();
     c->cl_min.release(); c->cl_row.release(); c->cl_len.release(); c->cl_cls.release(); c->cl_tot.release(); c->cl_tab.release(); c->pt_lab.release(); c->pt_tot.release();
+    c->tr_row.release(); c->tr_drop.release(); c->tr_tot.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -4296,6 +4306,146 @@ try {
     const uint64_t n = totals->seen - totals->dropped;
     if (!totals->covered || totals->bad || totals->labels_short || !(flags & ZNGAMD_BGZF_CLASSIFY_GROUP) || !n) return ZNGAMD_OK;
     return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap);
+} ZA_ABI_GUARD
+
+// ---- records trimmed (za_trim.hip)
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool trim_args_ok(const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim, uint32_t flags,
+                         const zngamd_bgzf_trim_conf *cf, const uint8_t *drop, uint64_t n_drop, const zngamd_bgzf_trim_totals *totals)
+{
+    if (!totals || !cf || (flags & ~(ZNGAMD_BGZF_GREP_FINAL | ZNGAMD_BGZF_CLASSIFY_GROUP)) || delim < 0 || delim > 255 || (!drop && n_drop)) return false;
+    if (!grep_records_ok(cf->record_lines, -1, cf->first_byte)) return false;
+    if (cf->seq_line < 0 || cf->seq_line >= (int32_t)cf->record_lines || cf->qual_line < -1 || cf->qual_line >= (int32_t)cf->record_lines ||
+        cf->qual_line == cf->seq_line) return false;
+    if (cf->qual_front > ZNGAMD_BGZF_TRIM_MAX_QUALITY || cf->qual_back > ZNGAMD_BGZF_TRIM_MAX_QUALITY || cf->quality_base > 255u ||
+        (cf->qual_line < 0 && (cf->qual_front || cf->qual_back))) return false;
+    if (cf->max_mismatch > ZNGAMD_BGZF_GREP_MAX_MISMATCH || cf->min_overlap < 1u || cf->min_overlap > ZNGAMD_BGZF_GREP_MAX_PATTERN ||
+        (cf->flags & ~ZNGAMD_BGZF_TRIM_KEEP_SHORT) || cf->reserved[0] || cf->reserved[1] || cf->reserved[2]) return false;
+    return !n_patterns || grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim, cf->max_mismatch);
+}
+
+// the lines pass for the delimiters alone, [the host waits for the line count], lines, eval, hist, with _GROUP the scan, close, [the
+// host waits for the totals], then with _GROUP scatter, offsets and gather, and the trim rows (own: they stay in tr_row).  dst.own:
+// drop is host memory and goes to tr_drop once the line count says how many bytes are needed.
+static int bgzf_trim_dev(zngamd_ctx *c, const BgzfWindow &w, const uint8_t *patterns, const zngamd_bgzf_pattern *table, uint32_t n_patterns, uint32_t flags,
+                         const zngamd_bgzf_trim_conf &cf, uint64_t record_base, const uint8_t *drop, uint64_t n_drop, zngamd_bgzf_trim_row *d_trim,
+                         uint64_t trim_cap, BgzfDest dst, zngamd_bgzf_trim_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines, ncls = 2u;
+    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+    if (r) return r;
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const bool group = (flags & ZA_CLS_GROUP) != 0, keep_short = (cf.flags & ZA_TRIM_KEEP_SHORT) != 0;
+    const uint64_t lines = R.lines, nrec = R.nrec, ndrop = std::min<uint64_t>(n_drop, nrec);
+    const uint32_t nwg = (uint32_t)((nrec + ZA_PART_WG_RECORDS - 1u) / ZA_PART_WG_RECORDS);
+    const uint64_t ntab = (uint64_t)ncls * nwg;
+    constexpr size_t TOT_WORDS = sizeof(ZaTrimTotals) / 8u;                              // then the two faults, the scan's sum, the counts, hist's totals
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab)); HIPCHK(c, c->pt_lab.ensure(nrec));
+    HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u)); HIPCHK(c, c->tr_row.ensure(nrec));
+    HIPCHK(c, c->tr_tot.ensure(TOT_WORDS + 3u + 2u * ncls + sizeof(ZaPartTotals) / 8u));
+    if (dst.own && drop && ndrop) {
+        HIPCHK(c, c->tr_drop.ensure(ndrop));
+        HIPCHK(c, hipMemcpyAsync(c->tr_drop.p, drop, (size_t)ndrop, hipMemcpyHostToDevice, c->stream));
+        drop = c->tr_drop.p;
+    }
+    static_assert(ZA_GREP_APAR_WORDS == ZA_GREP_MAX_PAT * sizeof(ZaGrepPat), "where za_k_trim_eval finds the adapter words");
+    std::vector<uint8_t> &par = c->gp_host;                      // (the lines pass has been waited for: its block is no longer read)
+    grep_approx_params(par, patterns, table, n_patterns);
+    HIPCHK(c, c->gp_par.ensure(par.size() + 4u));
+    HIPCHK(c, hipMemcpyAsync(c->gp_par.p, par.data(), par.size(), hipMemcpyHostToDevice, c->stream));
+    ZaTrimPar P = {k, (uint32_t)cf.seq_line, cf.qual_line, cf.first_byte, cf.cut_front, cf.cut_back, cf.qual_front, cf.qual_back, cf.quality_base,
+                   cf.max_mismatch, cf.min_overlap, cf.min_length, keep_short ? 1u : 0u, w.delim, n_patterns, 0u};
+    for (uint32_t i = 0; i < n_patterns; i++) P.max_len = std::max(P.max_len, table[i].len);
+    ZaTrimTotals *d_tot = (ZaTrimTotals *)c->tr_tot.p;
+    unsigned long long *d_bad = c->tr_tot.p + TOT_WORDS, *d_sum = d_bad + 2, *d_cnt = d_bad + 3;
+    ZaPartTotals *d_ptot = (ZaPartTotals *)(d_cnt + 2u * ncls);
+    HIPCHK(c, hipMemsetAsync(c->tr_tot.p, 0, (TOT_WORDS + 3u + 2u * ncls) * 8u + sizeof(ZaPartTotals), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 16, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_trim_eval, dim3((uint32_t)((nrec + ZA_TRIM_WG_RECORDS - 1u) / ZA_TRIM_WG_RECORDS)), dim3(256), 0, c->stream, w.d_scratch,
+                         w.text_end, c->gr_start.p, lines, nrec, P, (const uint8_t *)c->gp_par.p, drop, ndrop, c->tr_row.p, c->cl_len.p, c->pt_lab.p, d_tot);
+      hipLaunchKernelGGL(za_k_part_hist, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, c->pt_lab.p, nrec, c->cl_len.p, nrec, ncls, nwg, c->cl_tab.p, d_cnt, d_ptot);
+      if (group) tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
+      hipLaunchKernelGGL(za_k_trim_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, ndrop, drop ? 1u : 0u, k, lflags, w.text_end, record_base,
+                         d_cnt, d_bad, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (totals->bad || totals->drop_short) return ZNGAMD_OK;
+    const uint64_t n = group ? totals->kept + (keep_short ? totals->too_short : 0ull) : 0ull, bytes = group ? totals->bytes : 0ull;
+    if (!dst.own && totals->seen > trim_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    r = bgzf_dest_ready(c, dst, n, bytes);
+    if (r) return r;
+    if (n) {
+        HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n));
+        uint64_t *d_bytes = (uint64_t *)((uint8_t *)c->d_small + 128);
+        { ProfScope ps(c, ZNGAMD_K_GATHER);
+          hipLaunchKernelGGL(za_k_part_scatter, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, c->pt_lab.p, nrec, c->cl_len.p, c->gr_start.p, nrec, k, ncls, nwg,
+                             c->cl_tab.p, record_base, dst.d_rows, n, c->gp_lens.p);
+          hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n <= 64 ? 64 : 1024), 0, c->stream, c->gp_lens.p, (uint32_t)n, 0u, 0ull, c->st_off.p, d_bytes,
+                             (const ZaUnit *)nullptr);
+          hipLaunchKernelGGL(za_k_trim_gather, dim3((uint32_t)((n + 3u) / 4u)), dim3(256), 0, c->stream, w.d_scratch, c->gr_start.p, lines, record_base, k,
+                             (uint32_t)cf.seq_line, cf.qual_line, w.delim, c->tr_row.p, dst.d_rows, c->st_off.p, n, dst.d_out, bytes); }
+        c->bgzf_stats[2] += n;
+        HIPCHK(c, hipGetLastError());
+    }
+    if (!dst.own) HIPCHK(c, hipMemcpyAsync(d_trim, c->tr_row.p, (size_t)totals->seen * sizeof(ZaTrimRow), hipMemcpyDeviceToDevice, c->stream));
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_trim_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                 uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns,
+                                 int delim, uint32_t flags, const zngamd_bgzf_trim_conf *conf, uint64_t record_base, void *d_scratch, uint64_t scratch_cap,
+                                 int32_t *d_status, const uint8_t *d_drop, uint64_t n_drop, zngamd_bgzf_trim_row *d_trim, uint64_t trim_cap,
+                                 zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_trim_totals *totals)
+try {
+    if (!trim_args_ok(patterns, patterns_len, table, n_patterns, delim, flags, conf, d_drop, n_drop, totals)) return ZNGAMD_E_ARG;
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_trim && trim_cap) || (!d_rows && rows_cap) ||
+        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    int r = bgzf_trim_dev(c, w, patterns, table, n_patterns, flags, *conf, record_base, d_drop, n_drop, d_trim, trim_cap,
+                          {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_trim_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                             uint64_t text_end, const uint8_t *patterns, uint32_t patterns_len, const zngamd_bgzf_pattern *table, uint32_t n_patterns, int delim,
+                             uint32_t flags, const zngamd_bgzf_trim_conf *conf, uint64_t record_base, int32_t *status, const uint8_t *drop, uint64_t n_drop,
+                             zngamd_bgzf_trim_row *trim, uint64_t trim_cap, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap,
+                             zngamd_alloc_fn alloc, void *user, zngamd_bgzf_trim_totals *totals)
+try {
+    if (!trim_args_ok(patterns, patterns_len, table, n_patterns, delim, flags, conf, drop, n_drop, totals)) return ZNGAMD_E_ARG;
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!trim && trim_cap) || (!rows && rows_cap) || (!out && out_cap) ||
+        (alloc && (trim || rows || out))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    r = bgzf_trim_dev(c, w, patterns, table, n_patterns, flags, *conf, record_base, drop, n_drop, nullptr, 0, {nullptr, 0, nullptr, 0, true}, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t seen = totals->seen;
+    const bool group = (flags & ZNGAMD_BGZF_CLASSIFY_GROUP) != 0;
+    if (!totals->covered || totals->bad || totals->drop_short || !seen) return ZNGAMD_OK;
+    const uint64_t n = group ? totals->kept + ((conf->flags & ZNGAMD_BGZF_TRIM_KEEP_SHORT) ? totals->too_short : 0ull) : 0ull;
+    if (alloc) trim = (zngamd_bgzf_trim_row *)alloc(user, seen * sizeof(zngamd_bgzf_trim_row));      // the caller's memory is asked for: trim rows, rows, bytes
+    return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap, alloc ? trim != nullptr : seen <= trim_cap, n != 0,
+                           [&] { HIPCHK(c, hipMemcpyAsync(trim, c->tr_row.p, (size_t)seen * sizeof(ZaTrimRow), hipMemcpyDeviceToHost, c->stream)); return ZNGAMD_OK; });
 } ZA_ABI_GUARD
 
 // ---- fields of a line (za_tabix.hip)

@@ -86,6 +86,7 @@ SYMBOLS = [
     "zngamd_bgzf_grep_approx_dev", "zngamd_bgzf_grep_approx", "zngamd_bgzf_grep_records_approx_dev", "zngamd_bgzf_grep_records_approx",
     "zngamd_bgzf_classify_records_dev", "zngamd_bgzf_classify_records",
     "zngamd_bgzf_partition_records_dev", "zngamd_bgzf_partition_records",
+    "zngamd_bgzf_trim_records_dev", "zngamd_bgzf_trim_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
@@ -193,6 +194,30 @@ class BgzfPartitionTotals(C.Structure):        # zngamd_bgzf_partition_totals
 
     @property
     def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is labelled)
+        return self.seen
+
+
+BGZF_TRIM_KEPT, BGZF_TRIM_TOO_SHORT, BGZF_TRIM_DROPPED = 0, 1, 2      # ZNGAMD_BGZF_TRIM_*: a trim row's verdict
+BGZF_TRIM_KEEP_SHORT, BGZF_TRIM_NO_ADAPTER, BGZF_TRIM_MAX_QUALITY = 1, 255, 93
+TRIM_ROW_DTYPE = np.dtype([("begin", "<u4"), ("end", "<u4"), ("adapter", "u1"), ("verdict", "u1"), ("steps", "u1"), ("reserved", "u1")])      # zngamd_bgzf_trim_row
+
+
+class BgzfTrimConf(C.Structure):               # zngamd_bgzf_trim_conf
+    _fields_ = [("record_lines", C.c_uint32), ("seq_line", C.c_int32), ("qual_line", C.c_int32), ("first_byte", C.c_int32), ("cut_front", C.c_uint32),
+                ("cut_back", C.c_uint32), ("qual_front", C.c_uint32), ("qual_back", C.c_uint32), ("quality_base", C.c_uint32),
+                ("max_mismatch", C.c_uint32), ("min_overlap", C.c_uint32), ("min_length", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class BgzfTrimTotals(C.Structure):             # zngamd_bgzf_trim_totals
+    _fields_ = [("seen", C.c_uint64), ("kept", C.c_uint64), ("too_short", C.c_uint64), ("dropped", C.c_uint64), ("bytes_in", C.c_uint64),
+                ("bytes", C.c_uint64), ("bases_in", C.c_uint64), ("bases_out", C.c_uint64), ("quality_trimmed", C.c_uint64),
+                ("adapter_trimmed", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64), ("bad_src", C.c_uint64),
+                ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("drop_short", C.c_uint32),
+                ("adapter_records", C.c_uint64 * BGZF_GREP_MAX_PATTERNS)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is judged)
         return self.seen
 
 
@@ -371,6 +396,11 @@ def load():
             L.zngamd_bgzf_partition_records_dev.argtypes = exact[:7] + exact[11:14] + exact[15:-1] + tail
             exact = L.zngamd_bgzf_grep_records.argtypes
             L.zngamd_bgzf_partition_records.argtypes = exact[:7] + exact[11:14] + exact[15:-1] + tail
+        if hasattr(L, "zngamd_bgzf_trim_records"):          # the records calls with a conf for record_lines .. first_byte; mask and trim rows in front of the rows
+            exact = L.zngamd_bgzf_grep_records_dev.argtypes
+            L.zngamd_bgzf_trim_records_dev.argtypes = exact[:13] + [vp] + exact[16:20] + [vp, C.c_uint64, vp, C.c_uint64] + exact[20:]
+            exact = L.zngamd_bgzf_grep_records.argtypes
+            L.zngamd_bgzf_trim_records.argtypes = exact[:13] + [vp] + exact[16:18] + [vp, C.c_uint64, vp, C.c_uint64] + exact[18:]
         if hasattr(L, "zngamd_bgzf_tabix"):
             L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
                                                 C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1470,6 +1500,80 @@ class Context:
                                                                C.c_void_p(crec.ctypes.data), C.c_void_p(cbytes.ctypes.data), C.byref(tot)),
                       (OK, BUF_ERROR))
         return r, tot, crec[:n_classes], cbytes[:n_classes]
+
+    def bgzf_trim_records(self, data, members, text_off, text_end, blob, table, delim, flags, conf, record_base=0, drop=None, caps=None):
+        """zngamd_bgzf_trim_records: every record cut by the rule of conf (a BgzfTrimConf) and the adapters (blob, table: as bgzf_grep takes
+        patterns; the table may be empty) -> (code, block statuses, totals (BgzfTrimTotals), trim rows (TRIM_ROW_DTYPE, one per record in
+        record order), rows (GREP_ROW_DTYPE: the kept records, then with BGZF_TRIM_KEEP_SHORT the too-short ones; len: the bytes as
+        written), the records as written in that order); rows and records only with BGZF_CLASSIFY_GROUP in flags; nothing comes back
+        when totals.bad or totals.drop_short is set.  drop: None or a uint8 array, entry r belongs to record record_base + r.  caps None:
+        the arrays are allocated once the engine knows their sizes; (trim rows, rows, bytes): buffers of those sizes, and code is
+        BUF_ERROR (nothing written) when the result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        table = np.ascontiguousarray(table, np.uint32).reshape(-1, 2)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfTrimTotals()
+        group = bool(flags & BGZF_CLASSIFY_GROUP)
+        box = []
+
+        def alloc(_user, nbytes):
+            if not box:
+                arr = np.empty(nbytes // TRIM_ROW_DTYPE.itemsize, TRIM_ROW_DTYPE)
+            elif len(box) == 1:
+                arr = np.empty(nbytes // GREP_ROW_DTYPE.itemsize, GREP_ROW_DTYPE)
+            else:
+                obj, addr = _new_bytes(nbytes)
+                box.append(obj)
+                return addr.value
+            box.append(arr)
+            return arr.ctypes.data
+
+        if caps is None:
+            tp, tcap, rp, rcap, op, ocap, fn = None, 0, None, 0, None, 0, ALLOC_FN(alloc)
+        else:
+            tcap, rcap, ocap = caps
+            trim, rows = np.zeros(max(1, tcap), TRIM_ROW_DTYPE), np.zeros(max(1, rcap), GREP_ROW_DTYPE)
+            out, op = _new_bytes(ocap)
+            tp, rp, fn = C.c_void_p(trim.ctypes.data) if tcap else None, C.c_void_p(rows.ctypes.data) if rcap else None, ALLOC_FN()
+            if not ocap:
+                op = None
+        if drop is not None:                               # (an empty mask is still a mask: every record lies beyond it)
+            drop = np.ascontiguousarray(drop, np.uint8)
+            mask = drop if len(drop) else np.zeros(1, np.uint8)
+            dp, nd = C.c_void_p(mask.ctypes.data), len(drop)
+        else:
+            dp, nd = None, 0
+        bp, bkeep = _addr(blob) if len(table) else (None, None)
+        r = self._chk(self.L.zngamd_bgzf_trim_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                      text_off, text_end, bp, len(blob) if len(table) else 0,
+                                                      C.c_void_p(table.ctypes.data) if len(table) else None, len(table), delim, flags, C.byref(conf),
+                                                      record_base, C.c_void_p(st.ctypes.data), dp, nd, tp, tcap, rp, rcap, op, ocap, fn, None,
+                                                      C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and tot.covered and tot.seen and not tot.bad and not tot.drop_short
+        n = tot.kept + (tot.too_short if conf.flags & BGZF_TRIM_KEEP_SHORT else 0) if got and group else 0
+        if caps is None:
+            trim_out = box[0] if got else np.empty(0, TRIM_ROW_DTYPE)
+            rows_out, packed = (box[1], box[2]) if n else (np.empty(0, GREP_ROW_DTYPE), b"")
+        else:
+            trim_out = trim[:tot.seen] if got else np.empty(0, TRIM_ROW_DTYPE)
+            rows_out, packed = (rows[:n], _take(out, tot.bytes)) if n else (np.empty(0, GREP_ROW_DTYPE), b"")
+        return r, st[:nm], tot, trim_out, rows_out, packed
+
+    def bgzf_trim_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, conf, record_base, d_scratch,
+                              scratch_cap, d_status, d_drop, n_drop, d_trim, trim_cap, d_rows, rows_cap, d_out, out_cap):
+        """zngamd_bgzf_trim_records_dev on device pointers (the adapters and conf: host memory) -> (code, totals); trim rows, rows and records
+        stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        table = np.ascontiguousarray(table, np.uint32).reshape(-1, 2)
+        tot = BgzfTrimTotals()
+        bp, bkeep = _addr(blob) if len(table) else (None, None)
+        r = self._chk(self.L.zngamd_bgzf_trim_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp,
+                                                          len(blob) if len(table) else 0, C.c_void_p(table.ctypes.data) if len(table) else None,
+                                                          len(table), delim, flags, C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status),
+                                                          v(d_drop), n_drop, v(d_trim), trim_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
+                      (OK, BUF_ERROR))
+        return r, tot
 
     def _bgzf_grep(self, fn_c, tot, data, members, text_off, text_end, blob, table, delim, flags, extra, caps):
         nm = len(members)

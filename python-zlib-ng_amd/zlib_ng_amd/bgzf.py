@@ -52,7 +52,7 @@ from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
-           "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP",
+           "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP", "trim_records", "TrimResult", "KEPT", "TOO_SHORT", "DROPPED",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
 BadGzipFile = zlib_ng.BadGzipFile
@@ -699,7 +699,8 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
     unit that is counted, numbered, carried over a window's end and bounded by max_line is the record.  classify (with records): a
     _ClassifySink -- every window's records are not selected but assigned to their nearest pattern (classify_records(), demux()), the
     sink takes what each window gives, and what its finish() returns is the result.  partition (with records, instead of patterns): a
-    _PartitionSink -- every window's records are split by the labels it holds (partition_records())."""
+    _PartitionSink -- every window's records are split by the labels it holds (partition_records()) -- or a _TrimSink -- they are cut
+    (trim_records())."""
     if partition is None:
         pats, delimiter = _grep_patterns(patterns, delimiter)
         mismatches = _grep_mismatches(mismatches, pats)
@@ -777,6 +778,9 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
             if records is not None:
                 if tot.bad == 2 and partition is not None:
                     raise ValueError(f"record {tot.bad_record}: its label is neither a class nor DROP")
+                if tot.bad == 3 and partition is not None:
+                    v = int(voffsets_of(np.array([tot.bad_src], np.int64))[0])
+                    raise ValueError(partition.length_fault(int(tot.bad_record), v))
                 if tot.bad:
                     v = int(voffsets_of(np.array([tot.bad_src], np.int64))[0])
                     raise ValueError(f"record {tot.bad_record} at virtual offset {v} does not start with {bytes([rec_b])!r} (first_byte)")
@@ -1172,6 +1176,198 @@ def partition_records(file, labels, outputs, record_lines=4, *, first_byte=None,
                                      allow_short=allow_short)
     return _partition_file(file, None, labels, outputs, record_lines, first_byte, delimiter, compresslevel, block_size, start, stop, first_record,
                            max_record, allow_short)
+
+
+# ---- records trimmed: the fixed cut, the low-quality ends, the 3' adapter, the reads that are too short
+KEPT, TOO_SHORT, DROPPED = _lib.BGZF_TRIM_KEPT, _lib.BGZF_TRIM_TOO_SHORT, _lib.BGZF_TRIM_DROPPED      # a TrimResult's verdicts
+_DROP_OUT_OF_STEP = "the file holds {} records and drop has {} entries: the files are out of step"
+
+
+class TrimResult:
+    """What trim_records() decided.  Per record, in the order of the file: begin and end (int64: the cut [begin, end) of the sequence
+    body), adapter (int16: the adapter the read was cut at, -1 none), verdict (uint8: 0 kept, 1 too short, 2 dropped), steps (uint8: bit 0
+    the fixed cut moved an end, bit 1 quality did, bit 2 an adapter did).  The counts: records, kept, too_short, dropped, bases_in (the
+    sequence bytes read), bases_out (those of the kept records as written), quality_trimmed and adapter_trimmed (the bases each step took,
+    over all records) and adapter_counts (int64, the records cut at every adapter)."""
+
+    def __init__(self, rows, counts, adapter_counts):
+        self.begin, self.end = rows["begin"].astype(np.int64), rows["end"].astype(np.int64)
+        self.adapter = rows["adapter"].astype(np.int16)
+        self.adapter[self.adapter == _lib.BGZF_TRIM_NO_ADAPTER] = -1
+        self.verdict, self.steps = rows["verdict"].copy(), rows["steps"].copy()
+        self.records = len(rows)
+        for name, value in counts.items():
+            setattr(self, name, int(value))
+        self.adapter_counts = adapter_counts
+
+    def __len__(self):
+        return self.records
+
+    def __repr__(self):
+        return (f"<TrimResult: {self.records} records, {self.kept} kept, {self.too_short} too short, {self.dropped} dropped, "
+                f"{self.bases_out} of {self.bases_in} bases>")
+
+
+_TRIM_COUNTS = ("kept", "too_short", "dropped", "bases_in", "bases_out", "quality_trimmed", "adapter_trimmed")
+
+
+def _trim_int(value, lo, hi, what):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+        raise ValueError(f"{what} is an integer between {lo} and {hi}, not {value!r}")
+    return int(value)
+
+
+def _trim_pair(value, lo, hi, what):
+    if isinstance(value, (int, np.integer)) and not isinstance(value, bool):
+        value = (0, value)                                   # (one number: the 3' end, as cutadapt -q takes it)
+    if not isinstance(value, (tuple, list)) or len(value) != 2:
+        raise ValueError(f"{what} is a pair (5' end, 3' end)")
+    return _trim_int(value[0], lo, hi, f"{what}[0]"), _trim_int(value[1], lo, hi, f"{what}[1]")
+
+
+def _trim_conf(record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches, min_overlap, min_length, first_byte, delimiter):
+    """-> (BgzfTrimConf, adapters as a list of bytes, delimiter as bytes); ValueError as trim_records() documents it"""
+    delimiter = _partition_delimiter(delimiter)
+    k, _, b = _grep_record_args(record_lines, None, first_byte)
+    s = _trim_int(seq_line, 0, k - 1, "seq_line")
+    q = -1 if qual_line is None else _trim_int(qual_line, 0, k - 1, "qual_line")
+    if q == s:
+        raise ValueError(f"seq_line and qual_line are two lines of the record, not both {s}")
+    cut = _trim_pair(cut, 0, 0xFFFFFFFF, "cut")
+    quality = _trim_pair(quality, 0, _lib.BGZF_TRIM_MAX_QUALITY, "quality")
+    if q < 0 and any(quality):
+        raise ValueError("quality needs a qual_line")
+    base = _trim_int(quality_base, 0, 255, "quality_base")
+    if isinstance(adapters, (bytes, bytearray, memoryview)):
+        adapters = [adapters]
+    pats = [bytes(a) for a in adapters]
+    if pats:
+        pats, _ = _grep_patterns(pats, delimiter)
+        kmm = _grep_mismatches(mismatches, pats)
+    else:
+        kmm = _trim_int(mismatches, 0, _lib.BGZF_GREP_MAX_MISMATCH, "mismatches")
+    cf = _lib.BgzfTrimConf(k, s, q, b, cut[0], cut[1], quality[0], quality[1], base, kmm, _trim_int(min_overlap, 1, _lib.BGZF_GREP_MAX_PATTERN, "min_overlap"),
+                           _trim_int(min_length, 0, 0xFFFFFFFF, "min_length"), 0)
+    return cf, pats, delimiter
+
+
+def _trim_drop(drop):
+    if drop is None:
+        return None
+    drop = np.asarray(drop)
+    if drop.ndim != 1 or (drop.size and drop.dtype.kind not in "biu"):
+        raise ValueError("drop is a one-dimensional array of booleans, one per record")
+    return (drop != 0).astype(np.uint8)
+
+
+class _TrimSink:
+    """what _grep_file hands a window's records to when they are cut: drop[i] (uint8, or None) belongs to record first_record + i;
+    writers: None (count only) or [kept, too short], None where a class is written nowhere"""
+
+    def __init__(self, conf, pats, drop, first_record, writers=None):
+        self.conf, self.pats, self.drop, self.first_record, self.writers = conf, pats, drop, int(first_record), writers
+        self.blob, self.table = _lib.grep_pattern_table(pats) if pats else (b"", np.empty((0, 2), np.uint32))
+        self.flags = _lib.BGZF_CLASSIFY_GROUP if writers is not None and any(w is not None for w in writers) else 0
+        conf.flags = _lib.BGZF_TRIM_KEEP_SHORT if self.flags and writers[1] is not None else 0
+        self.rows, self.short, self.args = [], False, None
+        self.counts = dict.fromkeys(_TRIM_COUNTS, 0)
+        self.adapter_counts = np.zeros(len(pats), np.int64)
+
+    def _engine(self, ctx, conf, group, drop):
+        data, members, text_off, text_end, delim, flags, record_base = self.args
+        return ctx.bgzf_trim_records(data, members, text_off, text_end, self.blob if conf is self.conf else b"",
+                                     self.table if conf is self.conf else self.table[:0], delim, flags | group, conf, record_base, drop)
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        self.ctx, self.args = ctx, (data, members, text_off, text_end, delim, flags, record_base)
+        at = record_base - self.first_record
+        drop, group = (None, self.flags) if self.drop is None else (self.drop[:0], 0) if self.short else (self.drop[at:], self.flags)
+        _, status, tot, self.trim, self.grows, packed = self._engine(ctx, self.conf, group, drop)
+        return status, tot, packed
+
+    def length_fault(self, record, voffset):
+        """the message for bad = 3: the engine is asked for the two bodies' lengths, each line taken as a sequence without qualities"""
+        r, lens = record - self.args[6], []
+        for line in (self.conf.seq_line, self.conf.qual_line):
+            cf = _lib.BgzfTrimConf(self.conf.record_lines, line, -1, -1, 0, 0, 0, 0, 33, 0, 1, 0, 0)
+            rows = self._engine(self.ctx, cf, 0, None)[3]
+            lens.append(int(rows["end"][r]) if r < len(rows) else -1)
+        return (f"record {record} at virtual offset {voffset}: line {self.conf.seq_line} (the sequence) has {lens[0]} bytes and line "
+                f"{self.conf.qual_line} (the qualities) has {lens[1]}")
+
+    def window(self, tot, packed):
+        self.short = self.short or bool(tot.drop_short)
+        if self.short:
+            return
+        self.rows.append(self.trim)
+        for name in _TRIM_COUNTS:
+            self.counts[name] += int(getattr(tot, name))
+        self.adapter_counts += np.frombuffer(tot.adapter_records, np.uint64)[:len(self.pats)].astype(np.int64)
+        if not self.flags:
+            return
+        nkept = int(self.grows["len"][:tot.kept].sum())
+        with memoryview(packed) as mv:
+            if self.writers[0] is not None and nkept:
+                self.writers[0].write(mv[:nkept])
+            if self.writers[1] is not None and len(packed) > nkept:
+                self.writers[1].write(mv[nkept:])
+        if len(packed) != int(tot.bytes):
+            raise RuntimeError("trim: the classes' bytes do not add up to the records")
+
+    def finish(self, searched):
+        if self.drop is not None and (self.short or searched != len(self.drop)):
+            raise ValueError(_DROP_OUT_OF_STEP.format(searched, len(self.drop)))
+        rows = np.concatenate(self.rows) if self.rows else np.empty(0, _lib.TRIM_ROW_DTYPE)
+        return TrimResult(rows, self.counts, self.adapter_counts)
+
+
+def _trim_file(fp, ctx, output, too_short, record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches, min_overlap, min_length,
+               drop, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record, allow_short):
+    conf, pats, delimiter = _trim_conf(record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches, min_overlap, min_length,
+                                       first_byte, delimiter)
+    drop = _trim_drop(drop)
+    _check_block_size(block_size)
+
+    def run(writers):
+        sink = _TrimSink(conf, pats, drop, first_record, writers)
+        return _grep_file(fp, ctx, None, delimiter, False, False, False, None, start, stop, first_record, max_record,
+                          (record_lines, None, first_byte, allow_short), 0, None, sink)
+
+    if output is None and too_short is None:
+        return run(None)
+    return _with_writers("trim_records", [output, too_short], compresslevel, block_size, run)
+
+
+def trim_records(file, output, record_lines=4, *, seq_line=1, qual_line=3, cut=(0, 0), quality=(0, 0), quality_base=33, adapters=(), mismatches=0,
+                 min_overlap=3, min_length=0, too_short=None, drop=None, first_byte=None, delimiter=b"\n", compresslevel=6,
+                 block_size=MAX_BLOCK_INPUT, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+    """Cut the reads of a BGZF file of records as cutadapt, fastp or Trimmomatic cut them, on the GPU, and write what is left.  seq_line
+    and qual_line (None: the records have no qualities) name the two lines of a record that are cut, at the same places; every other
+    line is written whole.  For every read, in this order: cut = (front, back) takes that many bases off the two ends; quality = (5'
+    cutoff, 3' cutoff) (each 0 .. 93, 0: off; one number: the 3' end) trims the low-quality ends by BWA's running-sum rule, the one of
+    cutadapt -q, with qualities read as byte - quality_base; adapters (0 to 64 byte strings of 1 to 255 bytes) are 3' adapters: the read
+    is cut where the first of them begins, an adapter counting as found when at least min_overlap of its bytes (or all of it) lie in the
+    read and differ in at most mismatches * overlap // len(adapter) places -- so one that runs over the read's end is found too; bytes
+    are compared as they are.  A read with fewer than min_length bases left is too short; drop (an array of booleans, drop[i] for record
+    first_record + i) names records that are written nowhere whatever is left of them, which is how the mates of a paired run stay in
+    step.  output is a path or writable binary file for the kept records, too_short an optional second one for the too-short records;
+    each is written through a BgzfWriter (compresslevel, block_size): a complete BGZF file.  output=None writes nothing: the records are
+    judged and counted only.  A read cut to nothing is written with empty lines.  record_lines, first_byte, delimiter, start, stop,
+    first_record, max_record, allow_short and the errors of the file are those of grep_records().  -> TrimResult.
+    A record whose sequence and qualities differ in length is a ValueError that names the record, its virtual offset and both lengths; a
+    file that holds more or fewer records than drop is one that names both counts and says that the files are out of step.  If anything
+    is raised the outputs written so far are closed, and the error says that they are incomplete."""
+    if _is_path(file):
+        _trim_conf(record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches, min_overlap, min_length, first_byte, delimiter)
+        _trim_drop(drop)                                         # (judged before the file is opened)
+        _check_block_size(block_size)
+        with _builtin_open(file, "rb") as f:
+            return trim_records(f, output, record_lines, seq_line=seq_line, qual_line=qual_line, cut=cut, quality=quality, quality_base=quality_base,
+                                adapters=adapters, mismatches=mismatches, min_overlap=min_overlap, min_length=min_length, too_short=too_short, drop=drop,
+                                first_byte=first_byte, delimiter=delimiter, compresslevel=compresslevel, block_size=block_size, start=start, stop=stop,
+                                first_record=first_record, max_record=max_record, allow_short=allow_short)
+    return _trim_file(file, None, output, too_short, record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches, min_overlap,
+                      min_length, drop, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record, allow_short)
 
 
 def _per_file(value, n_files, name):
@@ -2767,6 +2963,22 @@ class BgzfReader(io.BufferedIOBase):
         try:
             return _partition_file(self._fp, self._ctx, labels, outputs, record_lines, first_byte, delimiter, compresslevel, block_size, start, stop,
                                    first_record, max_record, allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def trim_records(self, output, record_lines=4, *, seq_line=1, qual_line=3, cut=(0, 0), quality=(0, 0), quality_base=33, adapters=(), mismatches=0,
+                     min_overlap=3, min_length=0, too_short=None, drop=None, first_byte=None, delimiter=b"\n", compresslevel=6,
+                     block_size=MAX_BLOCK_INPUT, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+        """bgzf.trim_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("trim_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _trim_file(self._fp, self._ctx, output, too_short, record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches,
+                              min_overlap, min_length, drop, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record,
+                              allow_short)
         finally:
             self._fp.seek(at)
 
