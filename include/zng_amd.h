@@ -880,6 +880,96 @@ int zngamd_bgzf_trim_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len
                              zngamd_bgzf_trim_row *trim, uint64_t trim_cap, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out,
                              uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_trim_totals *totals);
 
+/* ---- BGZF quality control (zlib_ng_amd/bgzf.py: qc_records).  What FastQC, fastp's report and seqkit stats -a
+ * count: per-cycle base composition and quality tables, the length, GC and mean-quality distributions, the totals and, when asked for,
+ * one row of figures per record.  Nothing is selected, cut or written.  The record model is that of zngamd_bgzf_grep_records
+ * (record_lines k, first_byte, _FINAL, the open tail, the cover contract).  conf names two lines of the record: seq_line s (0 <= s < k)
+ * and qual_line q (-1: none; otherwise 0 <= q < k, q != s).  A line's body is its bytes without the delimiter; a CR is a body byte.  A
+ * short last record under _FINAL is judged on the lines it has: a line it lacks is an empty body.  For a record with a seq body of n
+ * bytes, all in integers:
+ *   class   of a byte, case folded (byte & 0xDF): 0 A, 1 C, 2 G, 3 T, 4 N, 5 anything else.
+ *   quality Q_i = clamp(qual[i] - quality_base, 0, 93); every byte that was clamped counts in quality_clamped.
+ *   row     of position i: min(i, C), C = cycles.  Row C collects everything at or beyond `cycles`: a long read is counted whole.
+ *   tables  uint64_t, contiguous, in this order (ZNGAMD_BGZF_QC_TABLE_WORDS(C) words; the call overwrites them, the caller does not
+ *           zero them):
+ *             base_pos[C + 1][6]     bytes of every class at every row
+ *             qual_pos[C + 1][94]    bytes of every quality at every row (all zero when q = -1)
+ *             length_hist[C + 2]     records with n bases at index n (n <= C), longer ones at index C + 1
+ *             gc_hist[101]           records with n >= 1 at bin (100 * gc) / n, gc = bases of class 1 or 2
+ *             meanq_hist[94]         records with n >= 1 at bin qsum / n, qsum = the sum of Q_i (q >= 0 only)
+ *   totals  seen, bytes_in, bases (sum of n), min_len and max_len (min_len = UINT64_MAX when seen = 0), empty (n = 0), base_total[6],
+ *           quality_sum, q20_bases and q30_bases (Q >= 20, Q >= 30), low_bases (Q < low_quality), quality_clamped; the quality figures
+ *           are 0 when q = -1.
+ *   rows    (ZNGAMD_BGZF_QC_ROWS in conf.flags) one zngamd_bgzf_qc_row per record in record order: qsum, len = n, gc, n = bases of
+ *           class 4, low = bases with Q < low_quality.  Without the flag only the tables and the totals leave the device.
+ * Faults: bad = 1, a first_byte violation; bad = 3, q >= 0 and the two bodies differ in length (2 is the label fault of
+ * zngamd_bgzf_partition_records and is not used here).  Of the two the one at the smaller record is reported, a record with both for its
+ * first byte; with bad set the tables, the rows and the totals other than the fault fields are not to be used.
+ * flags: _FINAL; anything else is ZNGAMD_E_ARG.  ZNGAMD_BUF_ERROR: tables_cap (in words) below ZNGAMD_BGZF_QC_TABLE_WORDS(cycles), before
+ * anything is launched; or, with _QC_ROWS, rows_cap < seen: no row is written, tables and totals are valid.  Hostile arguments -- conf
+ * NULL or a field out of range, q == s, a reserved word set, flags, totals or the tables NULL, rows NULL with _QC_ROWS (and, in the
+ * host form, no alloc) -- are ZNGAMD_E_ARG before the context is touched.  Device memory beside the tiles: 8 bytes per line of the
+ * text, and in the host form the tables (at most 3.3 MB) and 24 bytes per record with _QC_ROWS. */
+#define ZNGAMD_BGZF_QC_MAX_CYCLES 4096u
+#define ZNGAMD_BGZF_QC_BASES      6u
+#define ZNGAMD_BGZF_QC_QUALITIES  94u
+#define ZNGAMD_BGZF_QC_MAX_LOW    93u
+#define ZNGAMD_BGZF_QC_GC_BINS    101u
+#define ZNGAMD_BGZF_QC_ROWS       1u     /* conf.flags: one row per record leaves the device */
+/* words of the tables for `cycles` C: (C + 1) * (6 + 94) + (C + 2) + 101 + 94 */
+#define ZNGAMD_BGZF_QC_TABLE_WORDS(C) (((uint64_t)(C) + 1u) * (ZNGAMD_BGZF_QC_BASES + ZNGAMD_BGZF_QC_QUALITIES) + ((uint64_t)(C) + 2u) + \
+                                       ZNGAMD_BGZF_QC_GC_BINS + ZNGAMD_BGZF_QC_QUALITIES)
+typedef struct {
+    uint32_t record_lines;  /* k, 1 .. 64 */
+    int32_t  seq_line;      /* s */
+    int32_t  qual_line;     /* q; -1: none */
+    int32_t  first_byte;    /* 0 .. 255; -1: no check */
+    uint32_t quality_base;  /* 0 .. 255; 33 for Sanger / Illumina 1.8+ */
+    uint32_t cycles;        /* C, 1 .. ZNGAMD_BGZF_QC_MAX_CYCLES */
+    uint32_t low_quality;   /* 0 .. 93: a base with Q below it is a low one */
+    uint32_t flags;         /* ZNGAMD_BGZF_QC_ROWS */
+    uint32_t reserved[8];   /* 0 */
+} zngamd_bgzf_qc_conf;                                                                            /* 64 B */
+typedef struct {
+    uint64_t qsum;          /* sum of Q_i; 0 when q = -1 */
+    uint32_t len;           /* n */
+    uint32_t gc;            /* bases of class 1 or 2 */
+    uint32_t n;             /* bases of class 4 */
+    uint32_t low;           /* bases with Q < low_quality; 0 when q = -1 */
+} zngamd_bgzf_qc_row;                                                                             /* 24 B */
+typedef struct {
+    uint64_t seen;            /* records of the text that were counted (the open tail is not one of them) */
+    uint64_t bytes_in;        /* bytes of the records as they lie in the text */
+    uint64_t bases;           /* sum of n */
+    uint64_t min_len;         /* UINT64_MAX when seen = 0 */
+    uint64_t max_len;
+    uint64_t empty;           /* records with n = 0 */
+    uint64_t base_total[ZNGAMD_BGZF_QC_BASES];
+    uint64_t quality_sum;     /* sum of Q_i over all records */
+    uint64_t q20_bases;       /* Q >= 20 */
+    uint64_t q30_bases;       /* Q >= 30 */
+    uint64_t low_bases;       /* Q < low_quality */
+    uint64_t quality_clamped; /* quality bytes below quality_base or above quality_base + 93 */
+    uint64_t tail_off;        /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;      /* bad != 0: the number of the record at fault */
+    uint64_t bad_src;         /*           and where it starts in the scratch */
+    uint32_t covered;         /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;     /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;             /* 0; 1: the first byte is not first_byte; 3: the bodies of seq_line and qual_line differ in length */
+    uint32_t reserved;
+} zngamd_bgzf_qc_totals;                                                                          /* 176 B */
+int zngamd_bgzf_qc_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                               uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_qc_conf *conf,
+                               uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, uint64_t *d_tables,
+                               uint64_t tables_cap, zngamd_bgzf_qc_row *d_rows, uint64_t rows_cap, zngamd_bgzf_qc_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; status, the tables and, with _QC_ROWS, the rows come back.  With alloc
+ * (rows = NULL, rows_cap 0) the caller's memory is asked for seen * 24 bytes once seen is known and not 0; NULL from it:
+ * ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_qc_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                           uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_qc_conf *conf,
+                           uint64_t record_base, int32_t *status, uint64_t *tables, uint64_t tables_cap, zngamd_bgzf_qc_row *rows,
+                           uint64_t rows_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_qc_totals *totals);
+
 /* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
  * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM
  * preset, is ZNGAMD_E_ARG), the columns of the name, the start and the end (from 1; col_end 0: none), the byte that opens a comment

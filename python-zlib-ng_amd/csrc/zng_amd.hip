@@ -14,6 +14,7 @@
 #include "za_classify.hip"
 #include "za_partition.hip"
 #include "za_trim.hip"
+#include "za_qc.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
 #include "za_batch.hip"
@@ -59,6 +60,11 @@ static_assert(sizeof(zngamd_bgzf_trim_totals) == sizeof(ZaTrimTotals) && sizeof(
               sizeof(ZaTrimRow) == 12 && sizeof(zngamd_bgzf_trim_conf) == 64 && ZNGAMD_BGZF_TRIM_KEPT == ZA_TRIM_KEPT && ZNGAMD_BGZF_TRIM_TOO_SHORT == ZA_TRIM_TOO_SHORT &&
               ZNGAMD_BGZF_TRIM_DROPPED == ZA_TRIM_DROPPED && ZNGAMD_BGZF_TRIM_KEEP_SHORT == ZA_TRIM_KEEP_SHORT && ZNGAMD_BGZF_TRIM_NO_ADAPTER == ZA_TRIM_NO_ADAPTER &&
               ZA_TRIM_STAGE_WORDS == 16u + (ZA_GREP_MAX_LEN + 3u) / 4u, "bgzf trim layout");
+static_assert(sizeof(zngamd_bgzf_qc_totals) == sizeof(ZaQcTotals) && sizeof(ZaQcTotals) == 176 && offsetof(ZaQcTotals, covered) == offsetof(zngamd_bgzf_qc_totals, covered) &&
+              offsetof(ZaQcTotals, tail_off) == offsetof(zngamd_bgzf_qc_totals, tail_off) && offsetof(ZaQcTotals, min_len) == offsetof(zngamd_bgzf_qc_totals, min_len) &&
+              sizeof(zngamd_bgzf_qc_row) == sizeof(ZaQcRow) && sizeof(ZaQcRow) == 24 && sizeof(zngamd_bgzf_qc_conf) == 64 && ZNGAMD_BGZF_QC_MAX_CYCLES == ZA_QC_MAX_CYCLES &&
+              ZNGAMD_BGZF_QC_BASES == ZA_QC_BASES && ZNGAMD_BGZF_QC_QUALITIES == ZA_QC_QUALS && ZNGAMD_BGZF_QC_GC_BINS == ZA_QC_GC_BINS && ZNGAMD_BGZF_QC_ROWS == ZA_QC_ROWS &&
+              ZNGAMD_BGZF_QC_TABLE_WORDS(ZA_QC_MAX_CYCLES) == (uint64_t)(ZA_QC_MAX_CYCLES + 1u) * ZA_QC_COLS + ZA_QC_HIST_MAX, "bgzf qc layout");
 static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_tabix_name) == sizeof(ZaTbxName) && sizeof(zngamd_tabix_bin) == sizeof(ZaTbxBin) &&
               sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
               sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
@@ -178,6 +184,8 @@ struct zngamd_ctx {
     // records trimmed (za_trim.hip, section 5f.5; line starts, lengths, table and labels are gr_start, cl_len, cl_tab and pt_lab): the trim
     // rows; the host form's drop mask; the totals, the two first faults, the scan's sum, the counts and what za_k_part_hist sums beside them
     DevBuf<ZaTrimRow> tr_row; DevBuf<uint8_t> tr_drop; DevBuf<unsigned long long> tr_tot;
+    // records counted (za_qc.hip, section 5f.6; line starts are gr_start): the totals and the two first faults; the host form's tables and rows
+    DevBuf<unsigned long long> qc_tot, qc_tab; DevBuf<ZaQcRow> qc_row;
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -332,6 +340,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->gr_start.release(); c->gr_sel.release(); c->gr_len.release(); c->gr_hit.release();
     c->cl_min.release(); c->cl_row.release(); c->cl_len.release(); c->cl_cls.release(); c->cl_tot.release(); c->cl_tab.release(); c->pt_lab.release(); c->pt_tot.release();
     c->tr_row.release(); c->tr_drop.release(); c->tr_tot.release();
+    c->qc_tot.release(); c->qc_tab.release(); c->qc_row.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -4446,6 +4455,119 @@ try {
     if (alloc) trim = (zngamd_bgzf_trim_row *)alloc(user, seen * sizeof(zngamd_bgzf_trim_row));      // the caller's memory is asked for: trim rows, rows, bytes
     return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap, alloc ? trim != nullptr : seen <= trim_cap, n != 0,
                            [&] { HIPCHK(c, hipMemcpyAsync(trim, c->tr_row.p, (size_t)seen * sizeof(ZaTrimRow), hipMemcpyDeviceToHost, c->stream)); return ZNGAMD_OK; });
+} ZA_ABI_GUARD
+
+// ---- records counted (za_qc.hip)
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool qc_args_ok(int delim, uint32_t flags, const zngamd_bgzf_qc_conf *cf, const uint64_t *tables, const zngamd_bgzf_qc_row *rows, bool alloc,
+                       const zngamd_bgzf_qc_totals *totals)
+{
+    if (!totals || !cf || !tables || (flags & ~ZNGAMD_BGZF_GREP_FINAL) || delim < 0 || delim > 255) return false;
+    if (!grep_records_ok(cf->record_lines, -1, cf->first_byte)) return false;
+    if (cf->seq_line < 0 || cf->seq_line >= (int32_t)cf->record_lines || cf->qual_line < -1 || cf->qual_line >= (int32_t)cf->record_lines ||
+        cf->qual_line == cf->seq_line) return false;
+    if (cf->quality_base > 255u || cf->cycles < 1u || cf->cycles > ZNGAMD_BGZF_QC_MAX_CYCLES || cf->low_quality > ZNGAMD_BGZF_QC_MAX_LOW ||
+        (cf->flags & ~ZNGAMD_BGZF_QC_ROWS)) return false;
+    for (uint32_t v : cf->reserved) if (v) return false;
+    return !(cf->flags & ZNGAMD_BGZF_QC_ROWS) || rows || alloc;
+}
+
+// d_tables is zeroed, the lines pass for the delimiters alone, [the host waits for the line count], lines, eval, close, [the host waits
+// for the totals].  d_tables: ZNGAMD_BGZF_QC_TABLE_WORDS(cf.cycles) words of device memory.  own: the rows go to qc_row; otherwise to d_rows
+// when rows_cap holds them, and nowhere (*rows_short) when it does not.
+static int bgzf_qc_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, const zngamd_bgzf_qc_conf &cf, uint64_t record_base, unsigned long long *d_tables,
+                       bool own, ZaQcRow *d_rows, uint64_t rows_cap, bool *rows_short, zngamd_bgzf_qc_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    totals->min_len = UINT64_MAX;
+    *rows_short = false;
+    HIPCHK(c, hipMemsetAsync(d_tables, 0, (size_t)ZNGAMD_BGZF_QC_TABLE_WORDS(cf.cycles) * 8u, c->stream));
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
+    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+    if (r) return r;
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const uint64_t lines = R.lines, nrec = R.nrec;
+    const bool want_rows = (cf.flags & ZA_QC_ROWS) != 0;
+    constexpr size_t TOT_WORDS = sizeof(ZaQcTotals) / 8u;                                // then the two faults
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->qc_tot.ensure(TOT_WORDS + 2u));
+    if (want_rows && own) { HIPCHK(c, c->qc_row.ensure(nrec)); d_rows = c->qc_row.p; }
+    else if (want_rows && rows_cap < nrec) { *rows_short = true; d_rows = nullptr; }
+    else if (!want_rows) d_rows = nullptr;
+    // the persistent grid: ZA_QC_WG_PER_CU workgroups per CU, each with one span of at least ZA_QC_SPAN_MIN records
+    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_QC_WG_PER_CU;
+    const uint64_t span = std::min<uint64_t>(std::max<uint64_t>((nrec + slots - 1u) / slots, ZA_QC_SPAN_MIN), ZA_QC_SPAN_MAX);
+    const ZaQcPar P = {k, (uint32_t)cf.seq_line, cf.qual_line, cf.first_byte, cf.quality_base, cf.cycles, cf.low_quality, w.delim};
+    ZaQcTotals *d_tot = (ZaQcTotals *)c->qc_tot.p;
+    unsigned long long *d_bad = c->qc_tot.p + TOT_WORDS;
+    HIPCHK(c, hipMemsetAsync(c->qc_tot.p, 0, TOT_WORDS * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(&d_tot->min_len, 0xFF, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 16, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_qc_eval, dim3((uint32_t)((nrec + span - 1u) / span)), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, span,
+                         P, d_tables, d_rows, d_tot);
+      hipLaunchKernelGGL(za_k_qc_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_qc_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                               uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_qc_conf *conf, uint64_t record_base, void *d_scratch,
+                               uint64_t scratch_cap, int32_t *d_status, uint64_t *d_tables, uint64_t tables_cap, zngamd_bgzf_qc_row *d_rows, uint64_t rows_cap,
+                               zngamd_bgzf_qc_totals *totals)
+try {
+    if (!qc_args_ok(delim, flags, conf, d_tables, d_rows, false, totals)) return ZNGAMD_E_ARG;
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (tables_cap < ZNGAMD_BGZF_QC_TABLE_WORDS(conf->cycles)) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    HIPCHK(c, hipSetDevice(c->device));
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    bool rows_short = false;
+    int r = bgzf_qc_dev(c, w, flags, *conf, record_base, (unsigned long long *)d_tables, false, (ZaQcRow *)d_rows, rows_cap, &rows_short, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (rows_short && !totals->bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_qc_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                           uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_qc_conf *conf, uint64_t record_base, int32_t *status, uint64_t *tables,
+                           uint64_t tables_cap, zngamd_bgzf_qc_row *rows, uint64_t rows_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_qc_totals *totals)
+try {
+    if (!qc_args_ok(delim, flags, conf, tables, rows, alloc != nullptr, totals)) return ZNGAMD_E_ARG;
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (alloc && rows)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    const uint64_t words = ZNGAMD_BGZF_QC_TABLE_WORDS(conf->cycles);
+    if (tables_cap < words) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    HIPCHK(c, c->qc_tab.ensure(words));
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    bool rows_short = false;
+    r = bgzf_qc_dev(c, w, flags, *conf, record_base, c->qc_tab.p, true, nullptr, 0, &rows_short, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tables, c->qc_tab.p, (size_t)words * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t seen = totals->seen;
+    if (!(conf->flags & ZNGAMD_BGZF_QC_ROWS) || !totals->covered || totals->bad || !seen) return ZNGAMD_OK;
+    if (alloc) {
+        rows = (zngamd_bgzf_qc_row *)alloc(user, seen * sizeof(zngamd_bgzf_qc_row));
+        if (!rows) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
+    } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    HIPCHK(c, hipMemcpyAsync(rows, c->qc_row.p, (size_t)seen * sizeof(ZaQcRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
 } ZA_ABI_GUARD
 
 // ---- fields of a line (za_tabix.hip)

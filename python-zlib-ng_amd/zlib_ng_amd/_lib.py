@@ -87,6 +87,7 @@ SYMBOLS = [
     "zngamd_bgzf_classify_records_dev", "zngamd_bgzf_classify_records",
     "zngamd_bgzf_partition_records_dev", "zngamd_bgzf_partition_records",
     "zngamd_bgzf_trim_records_dev", "zngamd_bgzf_trim_records",
+    "zngamd_bgzf_qc_records_dev", "zngamd_bgzf_qc_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
@@ -218,6 +219,42 @@ class BgzfTrimTotals(C.Structure):             # zngamd_bgzf_trim_totals
 
     @property
     def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is judged)
+        return self.seen
+
+
+BGZF_QC_MAX_CYCLES, BGZF_QC_BASES, BGZF_QC_QUALITIES, BGZF_QC_MAX_LOW, BGZF_QC_GC_BINS, BGZF_QC_ROWS = 4096, 6, 94, 93, 101, 1      # ZNGAMD_BGZF_QC_*
+QC_ROW_DTYPE = np.dtype([("qsum", "<u8"), ("len", "<u4"), ("gc", "<u4"), ("n", "<u4"), ("low", "<u4")])      # zngamd_bgzf_qc_row
+
+
+def bgzf_qc_table_words(cycles):
+    """ZNGAMD_BGZF_QC_TABLE_WORDS: the words of base_pos, qual_pos, length_hist, gc_hist and meanq_hist for `cycles`"""
+    return (cycles + 1) * (BGZF_QC_BASES + BGZF_QC_QUALITIES) + (cycles + 2) + BGZF_QC_GC_BINS + BGZF_QC_QUALITIES
+
+
+def bgzf_qc_split(tables, cycles):
+    """the five tables of a zngamd_bgzf_qc_records call as views of its words: base_pos, qual_pos, length_hist, gc_hist, meanq_hist"""
+    a = (cycles + 1) * BGZF_QC_BASES
+    b = a + (cycles + 1) * BGZF_QC_QUALITIES
+    c = b + cycles + 2
+    d = c + BGZF_QC_GC_BINS
+    return (tables[:a].reshape(cycles + 1, BGZF_QC_BASES), tables[a:b].reshape(cycles + 1, BGZF_QC_QUALITIES), tables[b:c], tables[c:d],
+            tables[d:d + BGZF_QC_QUALITIES])
+
+
+class BgzfQcConf(C.Structure):                 # zngamd_bgzf_qc_conf
+    _fields_ = [("record_lines", C.c_uint32), ("seq_line", C.c_int32), ("qual_line", C.c_int32), ("first_byte", C.c_int32), ("quality_base", C.c_uint32),
+                ("cycles", C.c_uint32), ("low_quality", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 8)]
+
+
+class BgzfQcTotals(C.Structure):               # zngamd_bgzf_qc_totals
+    _fields_ = [("seen", C.c_uint64), ("bytes_in", C.c_uint64), ("bases", C.c_uint64), ("min_len", C.c_uint64), ("max_len", C.c_uint64),
+                ("empty", C.c_uint64), ("base_total", C.c_uint64 * BGZF_QC_BASES), ("quality_sum", C.c_uint64), ("q20_bases", C.c_uint64),
+                ("q30_bases", C.c_uint64), ("low_bases", C.c_uint64), ("quality_clamped", C.c_uint64), ("tail_off", C.c_uint64),
+                ("bad_record", C.c_uint64), ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is counted)
         return self.seen
 
 
@@ -401,6 +438,11 @@ def load():
             L.zngamd_bgzf_trim_records_dev.argtypes = exact[:13] + [vp] + exact[16:20] + [vp, C.c_uint64, vp, C.c_uint64] + exact[20:]
             exact = L.zngamd_bgzf_grep_records.argtypes
             L.zngamd_bgzf_trim_records.argtypes = exact[:13] + [vp] + exact[16:18] + [vp, C.c_uint64, vp, C.c_uint64] + exact[18:]
+        if hasattr(L, "zngamd_bgzf_qc_records"):            # no patterns: delim and flags behind text_end, then the conf; tables and rows with their capacities
+            L.zngamd_bgzf_qc_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp,
+                                                     C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_qc_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp, vp,
+                                                 C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
         if hasattr(L, "zngamd_bgzf_tabix"):
             L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
                                                 C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1573,6 +1615,50 @@ class Context:
                                                           len(table), delim, flags, C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status),
                                                           v(d_drop), n_drop, v(d_trim), trim_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
                       (OK, BUF_ERROR))
+        return r, tot
+
+    def bgzf_qc_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):
+        """zngamd_bgzf_qc_records: every record counted by the rule of conf (a BgzfQcConf) -> (code, block statuses, totals (BgzfQcTotals),
+        tables (uint64, bgzf_qc_table_words(conf.cycles) words: bgzf_qc_split() names them), rows (QC_ROW_DTYPE, one per record in record
+        order; empty without BGZF_QC_ROWS in conf.flags or when totals.bad is set)).  caps None: the tables are sized for conf.cycles and
+        the rows are allocated once the engine knows how many there are; (table words, rows): buffers of those sizes, and code is
+        BUF_ERROR when the result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfQcTotals()
+        want = bool(conf.flags & BGZF_QC_ROWS)
+        box = []
+
+        def alloc(_user, nbytes):
+            box.append(np.empty(nbytes // QC_ROW_DTYPE.itemsize, QC_ROW_DTYPE))
+            return box[0].ctypes.data
+
+        if caps is None:
+            tcap, rp, rcap, fn = bgzf_qc_table_words(conf.cycles), None, 0, ALLOC_FN(alloc)
+        else:
+            tcap, rcap = caps
+            rows = np.zeros(max(1, rcap), QC_ROW_DTYPE)
+            rp, fn = C.c_void_p(rows.ctypes.data) if rcap or want else None, ALLOC_FN()
+        tables = np.full(max(1, tcap), 0x5A5A5A5A5A5A5A5A, np.uint64)       # (the engine overwrites what it is given)
+        r = self._chk(self.L.zngamd_bgzf_qc_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                    text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
+                                                    C.c_void_p(tables.ctypes.data), tcap, rp, rcap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and want and tot.covered and tot.seen and not tot.bad
+        if caps is None:
+            rows_out = box[0] if got else np.empty(0, QC_ROW_DTYPE)
+        else:
+            rows_out = rows[:tot.seen] if got else np.empty(0, QC_ROW_DTYPE)
+        return r, st[:nm], tot, tables[:tcap], rows_out
+
+    def bgzf_qc_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, record_base, d_scratch, scratch_cap,
+                            d_status, d_tables, tables_cap, d_rows, rows_cap):
+        """zngamd_bgzf_qc_records_dev on device pointers (conf: host memory) -> (code, totals); tables and rows stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfQcTotals()
+        r = self._chk(self.L.zngamd_bgzf_qc_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
+                                                        C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_tables), tables_cap,
+                                                        v(d_rows), rows_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def _bgzf_grep(self, fn_c, tot, data, members, text_off, text_end, blob, table, delim, flags, extra, caps):

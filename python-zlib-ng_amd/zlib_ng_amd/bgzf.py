@@ -52,7 +52,7 @@ from . import _lib, devmem, zlib_ng
 
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
-           "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP", "trim_records", "TrimResult", "KEPT", "TOO_SHORT", "DROPPED",
+           "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP", "trim_records", "TrimResult", "KEPT", "TOO_SHORT", "DROPPED", "qc_records", "QcResult",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
 BadGzipFile = zlib_ng.BadGzipFile
@@ -700,7 +700,7 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
     _ClassifySink -- every window's records are not selected but assigned to their nearest pattern (classify_records(), demux()), the
     sink takes what each window gives, and what its finish() returns is the result.  partition (with records, instead of patterns): a
     _PartitionSink -- every window's records are split by the labels it holds (partition_records()) -- or a _TrimSink -- they are cut
-    (trim_records())."""
+    (trim_records()) -- or a _QcSink -- they are counted (qc_records())."""
     if partition is None:
         pats, delimiter = _grep_patterns(patterns, delimiter)
         mismatches = _grep_mismatches(mismatches, pats)
@@ -1368,6 +1368,182 @@ def trim_records(file, output, record_lines=4, *, seq_line=1, qual_line=3, cut=(
                                 first_record=first_record, max_record=max_record, allow_short=allow_short)
     return _trim_file(file, None, output, too_short, record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches, min_overlap,
                       min_length, drop, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record, allow_short)
+
+
+# ---- records counted: per-cycle base and quality tables, the distributions, the totals, a row per record
+_QC_TOTALS = ("bytes_in", "bases", "empty", "quality_sum", "q20_bases", "q30_bases", "low_bases", "quality_clamped")
+_QC_ROWS = (("length", "len"), ("gc", "gc"), ("n_bases", "n"), ("low_bases_per_record", "low"), ("quality_sum_per_record", "qsum"))
+
+
+class QcResult:
+    """What qc_records() counted.  The tables (numpy int64): base_pos[cycles + 1, 6] (the bases A, C, G, T, N and anything else at every
+    position; the last row collects every position at or beyond cycles), qual_pos[cycles + 1, 94] (the qualities 0 .. 93 likewise; all
+    zero without a qual_line), length_hist[cycles + 2] (reads of every length; the last entry collects the reads longer than cycles),
+    gc_hist[101] (non-empty reads by 100 * GC // length) and meanq_hist[94] (non-empty reads by quality sum // length).  The totals
+    (int): records, bytes_in, bases, min_len and max_len (0 without a record), empty, quality_sum, q20_bases, q30_bases, low_bases (below
+    low_quality), quality_clamped (quality bytes outside quality_base .. quality_base + 93, counted as 0 or 93), and base_total (int64,
+    6).  With per_record=True, one entry per record in the order of the file (otherwise None): length, gc, n_bases, low_bases_per_record
+    (all int64) and quality_sum_per_record (int64).  Results of parts of a file add up: a + b."""
+
+    def __init__(self, cycles, low_quality, tables, totals, base_total, rows):
+        self.cycles, self.low_quality = int(cycles), int(low_quality)
+        self._tables = tables
+        self.base_pos, self.qual_pos, self.length_hist, self.gc_hist, self.meanq_hist = _lib.bgzf_qc_split(tables, self.cycles)
+        for name, value in totals.items():
+            setattr(self, name, int(value))
+        self.base_total = base_total
+        self.per_record = rows is not None
+        for name, field in _QC_ROWS:
+            setattr(self, name, rows[field].astype(np.int64) if rows is not None else None)
+
+    def __len__(self):
+        return self.records
+
+    @property
+    def mean_length(self):
+        return self.bases / self.records if self.records else 0.0
+
+    @property
+    def q20_rate(self):
+        return self.q20_bases / self.bases if self.bases else 0.0
+
+    @property
+    def q30_rate(self):
+        return self.q30_bases / self.bases if self.bases else 0.0
+
+    @property
+    def gc_fraction(self):
+        """the share of C and G among all bases"""
+        return int(self.base_total[1] + self.base_total[2]) / self.bases if self.bases else 0.0
+
+    def mean_quality_by_cycle(self):
+        """float64[cycles + 1]: the mean quality at every row of qual_pos; nan where no base was counted"""
+        n = self.qual_pos.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (self.qual_pos * np.arange(_lib.BGZF_QC_QUALITIES)).sum(axis=1) / n
+
+    def base_fraction_by_cycle(self):
+        """float64[cycles + 1, 6]: the share of every base class at every row of base_pos; nan where no base was counted"""
+        n = self.base_pos.sum(axis=1, keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.base_pos / n
+
+    def __add__(self, other):
+        if not isinstance(other, QcResult):
+            return NotImplemented
+        if (self.cycles, self.low_quality) != (other.cycles, other.low_quality):
+            raise ValueError(f"results with cycles {self.cycles} and {other.cycles}, low_quality {self.low_quality} and {other.low_quality} do not add up")
+        totals = {name: getattr(self, name) + getattr(other, name) for name in ("records",) + _QC_TOTALS}
+        both = [r for r in (self, other) if r.records]
+        totals["min_len"] = min((r.min_len for r in both), default=0)
+        totals["max_len"] = max((r.max_len for r in both), default=0)
+        rows = None
+        if self.per_record and other.per_record:
+            rows = np.empty(self.records + other.records, _lib.QC_ROW_DTYPE)
+            for name, field in _QC_ROWS:
+                rows[field] = np.concatenate([getattr(self, name), getattr(other, name)])
+        return QcResult(self.cycles, self.low_quality, self._tables + other._tables, totals, self.base_total + other.base_total, rows)
+
+    def merge(self, other):
+        return self + other
+
+    def __repr__(self):
+        return (f"<QcResult: {self.records} records, {self.bases} bases, lengths {self.min_len} .. {self.max_len}, Q20 {100 * self.q20_rate:.1f} %, "
+                f"Q30 {100 * self.q30_rate:.1f} %, GC {100 * self.gc_fraction:.1f} %>")
+
+
+def _qc_conf(record_lines, seq_line, qual_line, quality_base, cycles, low_quality, per_record, first_byte, delimiter):
+    """-> (BgzfQcConf, delimiter as bytes); ValueError as qc_records() documents it"""
+    delimiter = _partition_delimiter(delimiter)
+    k, _, b = _grep_record_args(record_lines, None, first_byte)
+    s = _trim_int(seq_line, 0, k - 1, "seq_line")
+    q = -1 if qual_line is None else _trim_int(qual_line, 0, k - 1, "qual_line")
+    if q == s:
+        raise ValueError(f"seq_line and qual_line are two lines of the record, not both {s}")
+    if not isinstance(per_record, (bool, np.bool_)):
+        raise ValueError(f"per_record is True or False, not {per_record!r}")
+    cf = _lib.BgzfQcConf(k, s, q, b, _trim_int(quality_base, 0, 255, "quality_base"), _trim_int(cycles, 1, _lib.BGZF_QC_MAX_CYCLES, "cycles"),
+                         _trim_int(low_quality, 0, _lib.BGZF_QC_MAX_LOW, "low_quality"), _lib.BGZF_QC_ROWS if per_record else 0)
+    return cf, delimiter
+
+
+class _QcSink:
+    """what _grep_file hands a window's records to when they are counted: the windows' tables and totals are added (the shortest and the
+    longest read combined), their rows put one behind the other"""
+
+    def __init__(self, conf):
+        self.conf, self.args, self.rows = conf, None, []
+        self.tables = np.zeros(_lib.bgzf_qc_table_words(conf.cycles), np.int64)
+        self.totals = dict.fromkeys(_QC_TOTALS, 0)
+        self.min_len = self.max_len = None
+        self.base_total = np.zeros(_lib.BGZF_QC_BASES, np.int64)
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        self.ctx, self.args = ctx, (data, members, text_off, text_end, delim, flags, record_base)
+        _, status, tot, self.win_tables, self.win_rows = ctx.bgzf_qc_records(data, members, text_off, text_end, delim, flags, self.conf, record_base)
+        return status, tot, b""
+
+    def length_fault(self, record, voffset):
+        """the message for bad = 3: the engine is asked for the two bodies' lengths, each line taken as a sequence without qualities"""
+        data, members, text_off, text_end, delim, flags, record_base = self.args
+        r, lens = record - record_base, []
+        for line in (self.conf.seq_line, self.conf.qual_line):
+            cf = _lib.BgzfQcConf(self.conf.record_lines, line, -1, -1, 33, 1, 0, _lib.BGZF_QC_ROWS)
+            rows = self.ctx.bgzf_qc_records(data, members, text_off, text_end, delim, flags, cf, record_base)[4]
+            lens.append(int(rows["len"][r]) if r < len(rows) else -1)
+        return (f"record {record} at virtual offset {voffset}: line {self.conf.seq_line} (the sequence) has {lens[0]} bytes and line "
+                f"{self.conf.qual_line} (the qualities) has {lens[1]}")
+
+    def window(self, tot, packed):
+        self.tables += self.win_tables.view(np.int64)
+        if not tot.seen:
+            return
+        for name in _QC_TOTALS:
+            self.totals[name] += int(getattr(tot, name))
+        self.base_total += np.frombuffer(tot.base_total, np.uint64).astype(np.int64)
+        self.min_len = int(tot.min_len) if self.min_len is None else min(self.min_len, int(tot.min_len))
+        self.max_len = int(tot.max_len) if self.max_len is None else max(self.max_len, int(tot.max_len))
+        if self.conf.flags & _lib.BGZF_QC_ROWS:
+            if len(self.win_rows) != tot.seen:
+                raise RuntimeError("qc: the rows do not add up to the records")
+            self.rows.append(self.win_rows)
+
+    def finish(self, searched):
+        rows = None
+        if self.conf.flags & _lib.BGZF_QC_ROWS:
+            rows = np.concatenate(self.rows) if self.rows else np.empty(0, _lib.QC_ROW_DTYPE)
+        totals = dict(self.totals, records=searched, min_len=self.min_len or 0, max_len=self.max_len or 0)
+        return QcResult(self.conf.cycles, self.conf.low_quality, self.tables, totals, self.base_total, rows)
+
+
+def _qc_file(fp, ctx, record_lines, seq_line, qual_line, quality_base, cycles, low_quality, per_record, first_byte, delimiter, start, stop, first_record,
+             max_record, allow_short):
+    conf, delimiter = _qc_conf(record_lines, seq_line, qual_line, quality_base, cycles, low_quality, per_record, first_byte, delimiter)
+    return _grep_file(fp, ctx, None, delimiter, False, False, False, None, start, stop, first_record, max_record,
+                      (record_lines, None, first_byte, allow_short), 0, None, _QcSink(conf))
+
+
+def qc_records(file, record_lines=4, *, seq_line=1, qual_line=3, quality_base=33, cycles=512, low_quality=15, per_record=False, first_byte=None,
+               delimiter=b"\n", start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+    """Quality control of a BGZF file of records on the GPU -- what FastQC, fastp's report and seqkit stats -a count; nothing but the
+    counts leaves the device.  seq_line and qual_line (None: the records have no qualities) name the lines of a record that hold the
+    bases and the qualities.  A base is A, C, G, T or N in either case, or something else; a quality is byte - quality_base, counted as
+    0 below 0 and as 93 above 93 (quality_clamped says how often).  cycles (1 to 4096) is the number of positions the per-position tables
+    have a row for; one further row collects everything at or beyond it, so a long read is counted whole.  low_quality (0 to 93): a base
+    with a quality below it counts in low_bases.  per_record=True also returns every record's length, GC count, N count, low-quality
+    bases and quality sum -- fastp's read filters are then a line of numpy whose result is the drop= of trim_records() or the labels of
+    partition_records().  record_lines, first_byte, delimiter, start, stop, first_record, max_record, allow_short and the errors of the
+    file are those of grep_records().  -> QcResult; the results of the parts of LineIndex.shards(reader, n, lines_per_record=k) add up
+    to the whole file's.
+    A record whose sequence and qualities differ in length is a ValueError that names the record, its virtual offset and both lengths."""
+    if _is_path(file):
+        _qc_conf(record_lines, seq_line, qual_line, quality_base, cycles, low_quality, per_record, first_byte, delimiter)      # (judged before the file is opened)
+        with _builtin_open(file, "rb") as f:
+            return qc_records(f, record_lines, seq_line=seq_line, qual_line=qual_line, quality_base=quality_base, cycles=cycles, low_quality=low_quality,
+                              per_record=per_record, first_byte=first_byte, delimiter=delimiter, start=start, stop=stop, first_record=first_record,
+                              max_record=max_record, allow_short=allow_short)
+    return _qc_file(file, None, record_lines, seq_line, qual_line, quality_base, cycles, low_quality, per_record, first_byte, delimiter, start, stop,
+                    first_record, max_record, allow_short)
 
 
 def _per_file(value, n_files, name):
@@ -2979,6 +3155,20 @@ class BgzfReader(io.BufferedIOBase):
             return _trim_file(self._fp, self._ctx, output, too_short, record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches,
                               min_overlap, min_length, drop, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record,
                               allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def qc_records(self, record_lines=4, *, seq_line=1, qual_line=3, quality_base=33, cycles=512, low_quality=15, per_record=False, first_byte=None,
+                   delimiter=b"\n", start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+        """bgzf.qc_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("qc_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _qc_file(self._fp, self._ctx, record_lines, seq_line, qual_line, quality_base, cycles, low_quality, per_record, first_byte, delimiter,
+                            start, stop, first_record, max_record, allow_short)
         finally:
             self._fp.seek(at)
 
