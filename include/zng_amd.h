@@ -970,6 +970,93 @@ int zngamd_bgzf_qc_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, 
                            uint64_t record_base, int32_t *status, uint64_t *tables, uint64_t tables_cap, zngamd_bgzf_qc_row *rows,
                            uint64_t rows_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_qc_totals *totals);
 
+/* ---- BGZF duplicate records (zlib_ng_amd/bgzf.py: key_records, dedup_keys, dedup_records, dedup_paired).  Two
+ * calls.  zngamd_bgzf_key_records reduces the sequence of every record of a window to a 16-byte key; zngamd_dedup_keys finds, for any
+ * number of such keys -- of one window, a file, several files, all shards -- the first record that carries each key and how many carry
+ * it.  Keys are comparable wherever they were made, so the key function is part of this interface:
+ *   part    the keyed part of a record is body[first : first + length] of its seq_line (length 0: to the end), clipped to the body: a
+ *           body shorter than `first` has an empty part.  n is the part's length, c_0 .. c_{n-1} its bytes; with _KEY_IGNORE_CASE every
+ *           byte a .. z is taken as A .. Z.  The record model is that of zngamd_bgzf_qc_records (a line the record lacks is an empty body).
+ *   mix(x)  the splitmix64 step, modulo 2^64: x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ *           x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^= x >> 31.
+ *   word_w  = mix(S_w ^ (1 << 63 | n)) + sum over i of mix(S_w ^ (i << 8 | c_i)), modulo 2^64, for w = 0, 1 with the seeds
+ *           S_0 = ZNGAMD_BGZF_KEY_SEED0 and S_1 = ZNGAMD_BGZF_KEY_SEED1.  The key is (lo, hi) = (word_0, word_1).
+ *   _KEY_CANONICAL  the key of the reverse complement -- position n - 1 - i and byte comp(c_i) in place of i and c_i; comp maps A<->T,
+ *           C<->G, a<->t, c<->g, U->A, u->a and every other byte to itself (applied behind the case fold) -- is formed beside it, and the
+ *           record's key is the smaller of the two as the 128-bit number hi << 64 | lo.
+ * Equal keys are taken as equal sequences (as fastp takes its hashes): two different sequences share a key with a probability of about
+ * 2^-128 per pair.
+ * rows: one zngamd_bgzf_key_row per record in record order.  totals: seen, bytes_in, bases (the bytes of the seq_line bodies, whole),
+ * tail_off, covered, short_lines and the fault words as zngamd_bgzf_qc_totals has them; bad = 1 is a first_byte violation, the smallest
+ * record at fault is reported, and with bad set the rows are not to be used.  flags: _FINAL; anything else is ZNGAMD_E_ARG.
+ * ZNGAMD_BUF_ERROR: rows_cap < seen: no row is written, the totals are valid.  Hostile arguments -- conf NULL or a field out of range, a
+ * reserved word set, flags, totals NULL, rows NULL (and, in the host form, no alloc) -- are ZNGAMD_E_ARG before the context is touched.
+ * Device memory beside the tiles: 8 bytes per line of the text, and in the host form 16 bytes per record. */
+#define ZNGAMD_BGZF_KEY_IGNORE_CASE 1u
+#define ZNGAMD_BGZF_KEY_CANONICAL   2u
+#define ZNGAMD_BGZF_KEY_SEED0 0x243F6A8885A308D3ull
+#define ZNGAMD_BGZF_KEY_SEED1 0x13198A2E03707344ull
+typedef struct {
+    uint32_t record_lines;  /* k, 1 .. 64 */
+    int32_t  seq_line;      /* s, 0 <= s < k */
+    int32_t  first_byte;    /* 0 .. 255; -1: no check */
+    uint32_t first;         /* where the keyed part begins in the body */
+    uint32_t length;        /* its length; 0: to the end of the body */
+    uint32_t flags;         /* ZNGAMD_BGZF_KEY_IGNORE_CASE | ZNGAMD_BGZF_KEY_CANONICAL */
+    uint32_t reserved[10];  /* 0 */
+} zngamd_bgzf_key_conf;                                                                           /* 64 B */
+typedef struct {
+    uint64_t lo;            /* word_0 */
+    uint64_t hi;            /* word_1 */
+} zngamd_bgzf_key_row;                                                                            /* 16 B */
+typedef struct {
+    uint64_t seen;            /* records of the text that were keyed (the open tail is not one of them) */
+    uint64_t bytes_in;        /* bytes of the records as they lie in the text */
+    uint64_t bases;           /* bytes of the seq_line bodies */
+    uint64_t tail_off;        /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;      /* bad != 0: the number of the record at fault */
+    uint64_t bad_src;         /*           and where it starts in the scratch */
+    uint32_t covered;         /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;     /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;             /* 0; 1: the first byte is not first_byte */
+    uint32_t reserved;
+} zngamd_bgzf_key_totals;                                                                         /* 64 B */
+int zngamd_bgzf_key_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_key_conf *conf,
+                                uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_key_row *d_rows,
+                                uint64_t rows_cap, zngamd_bgzf_key_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; status and the rows come back.  With alloc (rows = NULL, rows_cap 0) the
+ * caller's memory is asked for seen * 16 bytes once seen is known and not 0; NULL from it: ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_key_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                            uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_key_conf *conf,
+                            uint64_t record_base, int32_t *status, zngamd_bgzf_key_row *rows, uint64_t rows_cap, zngamd_alloc_fn alloc,
+                            void *user, zngamd_bgzf_key_totals *totals);
+
+/* zngamd_dedup_keys: for n keys (any 16-byte rows; those of zngamd_bgzf_key_records, or of pairs, files and shards put together),
+ * first[r] = the smallest r' with keys[r'] == keys[r] (both words), count[r] = how many rows carry keys[r] when first[r] == r and 0
+ * otherwise (it would saturate at 2^32 - 1; n <= ZNGAMD_DEDUP_MAX_KEYS keeps it below), and the totals: unique (the distinct keys),
+ * duplicates = n - unique, max_count (the largest group) and max_first (its first row; the lowest such row when groups tie; 0 when n = 0).
+ * first and count, either or both, may be NULL: the totals alone.  The result depends on the keys alone.  The work area is an
+ * open-addressed table of cap = the smallest power of two that is >= 2 n and >= 64 slots of 8 bytes with cap counters of 4 bytes:
+ * zngamd_dedup_scratch_bytes(n) bytes (0 for n > ZNGAMD_DEDUP_MAX_KEYS), 8-byte aligned.  n = 0 launches nothing.  ZNGAMD_E_ARG before
+ * the context is touched: totals NULL, keys NULL with n != 0, n > ZNGAMD_DEDUP_MAX_KEYS, a scratch pointer that is NULL with n != 0 or
+ * not 8-byte aligned.  ZNGAMD_BUF_ERROR: scratch_cap below zngamd_dedup_scratch_bytes(n); nothing is launched. */
+#define ZNGAMD_DEDUP_MAX_KEYS (1ull << 30)
+typedef struct {
+    uint64_t n;
+    uint64_t unique;
+    uint64_t duplicates;
+    uint64_t max_count;
+    uint64_t max_first;
+    uint64_t reserved;
+} zngamd_dedup_totals;                                                                            /* 48 B */
+uint64_t zngamd_dedup_scratch_bytes(uint64_t n);
+int zngamd_dedup_keys_dev(zngamd_ctx *ctx, const zngamd_bgzf_key_row *d_keys, uint64_t n, void *d_scratch, uint64_t scratch_cap,
+                          uint64_t *d_first, uint32_t *d_count, zngamd_dedup_totals *totals);
+/* Host-buffer form: the keys are uploaded, the table is the context's, first and count (each NULL or n entries) come back. */
+int zngamd_dedup_keys(zngamd_ctx *ctx, const zngamd_bgzf_key_row *keys, uint64_t n, uint64_t *first, uint32_t *count,
+                      zngamd_dedup_totals *totals);
+
 /* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
  * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM
  * preset, is ZNGAMD_E_ARG), the columns of the name, the start and the end (from 1; col_end 0: none), the byte that opens a comment

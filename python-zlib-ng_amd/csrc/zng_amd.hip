@@ -15,6 +15,7 @@
 #include "za_partition.hip"
 #include "za_trim.hip"
 #include "za_qc.hip"
+#include "za_dedup.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
 #include "za_batch.hip"
@@ -65,6 +66,11 @@ static_assert(sizeof(zngamd_bgzf_qc_totals) == sizeof(ZaQcTotals) && sizeof(ZaQc
               sizeof(zngamd_bgzf_qc_row) == sizeof(ZaQcRow) && sizeof(ZaQcRow) == 24 && sizeof(zngamd_bgzf_qc_conf) == 64 && ZNGAMD_BGZF_QC_MAX_CYCLES == ZA_QC_MAX_CYCLES &&
               ZNGAMD_BGZF_QC_BASES == ZA_QC_BASES && ZNGAMD_BGZF_QC_QUALITIES == ZA_QC_QUALS && ZNGAMD_BGZF_QC_GC_BINS == ZA_QC_GC_BINS && ZNGAMD_BGZF_QC_ROWS == ZA_QC_ROWS &&
               ZNGAMD_BGZF_QC_TABLE_WORDS(ZA_QC_MAX_CYCLES) == (uint64_t)(ZA_QC_MAX_CYCLES + 1u) * ZA_QC_COLS + ZA_QC_HIST_MAX, "bgzf qc layout");
+static_assert(sizeof(zngamd_bgzf_key_totals) == sizeof(ZaKeyTotals) && sizeof(ZaKeyTotals) == 64 && offsetof(ZaKeyTotals, covered) == offsetof(zngamd_bgzf_key_totals, covered) &&
+              offsetof(ZaKeyTotals, tail_off) == offsetof(zngamd_bgzf_key_totals, tail_off) && sizeof(zngamd_bgzf_key_row) == sizeof(ZaKeyRow) && sizeof(ZaKeyRow) == 16 &&
+              sizeof(zngamd_bgzf_key_conf) == 64 && ZNGAMD_BGZF_KEY_IGNORE_CASE == ZA_KEY_IGNORE_CASE && ZNGAMD_BGZF_KEY_CANONICAL == ZA_KEY_CANONICAL &&
+              ZNGAMD_BGZF_KEY_SEED0 == ZA_KEY_SEED0 && ZNGAMD_BGZF_KEY_SEED1 == ZA_KEY_SEED1 && sizeof(zngamd_dedup_totals) == sizeof(ZaDedupTotals) &&
+              sizeof(ZaDedupTotals) == 48, "bgzf dedup layout");
 static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_tabix_name) == sizeof(ZaTbxName) && sizeof(zngamd_tabix_bin) == sizeof(ZaTbxBin) &&
               sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
               sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
@@ -186,6 +192,9 @@ struct zngamd_ctx {
     DevBuf<ZaTrimRow> tr_row; DevBuf<uint8_t> tr_drop; DevBuf<unsigned long long> tr_tot;
     // records counted (za_qc.hip, section 5f.6; line starts are gr_start): the totals and the two first faults; the host form's tables and rows
     DevBuf<unsigned long long> qc_tot, qc_tab; DevBuf<ZaQcRow> qc_row;
+    // records keyed and keys resolved (za_dedup.hip, section 5f.7; line starts are gr_start): the key pass's totals and first fault; the host
+    // forms' rows, table, first[] and count[]
+    DevBuf<unsigned long long> dd_tot, dd_first; DevBuf<ZaKeyRow> dd_row; DevBuf<uint8_t> dd_tab; DevBuf<uint32_t> dd_count;
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -341,6 +350,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->cl_min.release(); c->cl_row.release(); c->cl_len.release(); c->cl_cls.release(); c->cl_tot.release(); c->cl_tab.release(); c->pt_lab.release(); c->pt_tot.release();
     c->tr_row.release(); c->tr_drop.release(); c->tr_tot.release();
     c->qc_tot.release(); c->qc_tab.release(); c->qc_row.release();
+    c->dd_tot.release(); c->dd_first.release(); c->dd_row.release(); c->dd_tab.release(); c->dd_count.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -4566,6 +4576,176 @@ try {
         if (!rows) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
     } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
     HIPCHK(c, hipMemcpyAsync(rows, c->qc_row.p, (size_t)seen * sizeof(ZaQcRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- records keyed, keys resolved (za_dedup.hip)
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool key_args_ok(int delim, uint32_t flags, const zngamd_bgzf_key_conf *cf, const zngamd_bgzf_key_row *rows, bool alloc, const zngamd_bgzf_key_totals *totals)
+{
+    if (!totals || !cf || (flags & ~ZNGAMD_BGZF_GREP_FINAL) || delim < 0 || delim > 255) return false;
+    if (!grep_records_ok(cf->record_lines, -1, cf->first_byte)) return false;
+    if (cf->seq_line < 0 || cf->seq_line >= (int32_t)cf->record_lines || (cf->flags & ~(ZNGAMD_BGZF_KEY_IGNORE_CASE | ZNGAMD_BGZF_KEY_CANONICAL))) return false;
+    for (uint32_t v : cf->reserved) if (v) return false;
+    return rows || alloc;
+}
+
+// The lines pass for the delimiters alone, [the host waits for the line count], lines, keys, close, [the host waits for the totals].
+// own: the rows go to dd_row; otherwise to d_rows when rows_cap holds them, and nowhere (*rows_short) when it does not.
+static int bgzf_key_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, const zngamd_bgzf_key_conf &cf, uint64_t record_base, bool own, ZaKeyRow *d_rows,
+                        uint64_t rows_cap, bool *rows_short, zngamd_bgzf_key_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    *rows_short = false;
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
+    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+    if (r) return r;
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const uint64_t lines = R.lines, nrec = R.nrec;
+    constexpr size_t TOT_WORDS = sizeof(ZaKeyTotals) / 8u;                               // then the fault
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->dd_tot.ensure(TOT_WORDS + 1u));
+    if (own) { HIPCHK(c, c->dd_row.ensure(nrec)); d_rows = c->dd_row.p; }
+    else if (rows_cap < nrec) { *rows_short = true; d_rows = nullptr; }
+    // four records to a workgroup, at most ZA_KEY_WG_PER_CU workgroups per CU: beyond that a wave walks on to its next record
+    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_KEY_WG_PER_CU;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    const ZaKeyPar P = {k, (uint32_t)cf.seq_line, cf.first_byte, cf.first, cf.length, cf.flags, w.delim};
+    ZaKeyTotals *d_tot = (ZaKeyTotals *)c->dd_tot.p;
+    unsigned long long *d_bad = c->dd_tot.p + TOT_WORDS;
+    HIPCHK(c, hipMemsetAsync(c->dd_tot.p, 0, TOT_WORDS * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_dedup_keys, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, P, d_rows, d_tot);
+      hipLaunchKernelGGL(za_k_dedup_keys_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_key_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_key_conf *conf, uint64_t record_base, void *d_scratch,
+                                uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_key_row *d_rows, uint64_t rows_cap, zngamd_bgzf_key_totals *totals)
+try {
+    if (!key_args_ok(delim, flags, conf, d_rows, false, totals)) return ZNGAMD_E_ARG;
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    bool rows_short = false;
+    int r = bgzf_key_dev(c, w, flags, *conf, record_base, false, (ZaKeyRow *)d_rows, rows_cap, &rows_short, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (rows_short && !totals->bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_key_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                            uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_key_conf *conf, uint64_t record_base, int32_t *status,
+                            zngamd_bgzf_key_row *rows, uint64_t rows_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_key_totals *totals)
+try {
+    if (!key_args_ok(delim, flags, conf, rows, alloc != nullptr, totals)) return ZNGAMD_E_ARG;
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (alloc && rows)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    bool rows_short = false;
+    r = bgzf_key_dev(c, w, flags, *conf, record_base, true, nullptr, 0, &rows_short, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t seen = totals->seen;
+    if (!totals->covered || totals->bad || !seen) return ZNGAMD_OK;
+    if (alloc) {
+        rows = (zngamd_bgzf_key_row *)alloc(user, seen * sizeof(zngamd_bgzf_key_row));
+        if (!rows) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
+    } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    HIPCHK(c, hipMemcpyAsync(rows, c->dd_row.p, (size_t)seen * sizeof(ZaKeyRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// the slots of the table for n keys: the smallest power of two that is >= 2 n and >= ZA_DEDUP_MIN_CAP (n <= ZNGAMD_DEDUP_MAX_KEYS)
+static uint64_t dedup_cap(uint64_t n)
+{
+    uint64_t cap = ZA_DEDUP_MIN_CAP;
+    while (cap < 2u * n) cap <<= 1;
+    return cap;
+}
+
+// the slots, the counters, the two words the lookup sums, the totals
+uint64_t zngamd_dedup_scratch_bytes(uint64_t n)
+{
+    return n > ZNGAMD_DEDUP_MAX_KEYS ? 0 : dedup_cap(n) * 12u + 16u + sizeof(ZaDedupTotals);
+}
+
+static bool dedup_args_ok(const zngamd_bgzf_key_row *keys, uint64_t n, const zngamd_dedup_totals *totals)
+{
+    return totals && n <= ZNGAMD_DEDUP_MAX_KEYS && (keys || !n);
+}
+
+// n > 0.  The table is set up (slots all ones, the rest zero), insert, lookup, close, [the host waits for the totals].
+static int dedup_dev(zngamd_ctx *c, const ZaKeyRow *d_keys, uint64_t n, uint8_t *d_scratch, unsigned long long *d_first, uint32_t *d_count, zngamd_dedup_totals *totals)
+{
+    const uint64_t cap = dedup_cap(n);
+    unsigned long long *slot = (unsigned long long *)d_scratch;
+    uint32_t *cnt = (uint32_t *)(d_scratch + cap * 8u);
+    unsigned long long *acc = (unsigned long long *)(d_scratch + cap * 12u);
+    ZaDedupTotals *d_tot = (ZaDedupTotals *)(acc + 2);
+    HIPCHK(c, hipMemsetAsync(slot, 0xFF, (size_t)cap * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(cnt, 0, (size_t)cap * 4u + 16u + sizeof(ZaDedupTotals), c->stream));
+    const uint32_t grid = (uint32_t)((n + 255u) / 256u);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_dedup_insert, dim3(grid), dim3(256), 0, c->stream, d_keys, n, slot, cnt, cap - 1u);
+      hipLaunchKernelGGL(za_k_dedup_lookup, dim3(grid), dim3(256), 0, c->stream, d_keys, n, slot, cnt, cap - 1u, d_first, d_count, acc);
+      hipLaunchKernelGGL(za_k_dedup_close, dim3(1), dim3(1), 0, c->stream, acc, n, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+}
+
+int zngamd_dedup_keys_dev(zngamd_ctx *c, const zngamd_bgzf_key_row *d_keys, uint64_t n, void *d_scratch, uint64_t scratch_cap, uint64_t *d_first,
+                          uint32_t *d_count, zngamd_dedup_totals *totals)
+try {
+    if (!dedup_args_ok(d_keys, n, totals) || (n && !d_scratch) || ((uintptr_t)d_scratch & 7u)) return ZNGAMD_E_ARG;
+    if (!c) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (n && scratch_cap < zngamd_dedup_scratch_bytes(n)) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    memset(totals, 0, sizeof *totals);
+    if (!n) return ZNGAMD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return dedup_dev(c, (const ZaKeyRow *)d_keys, n, (uint8_t *)d_scratch, (unsigned long long *)d_first, d_count, totals);
+} ZA_ABI_GUARD
+
+int zngamd_dedup_keys(zngamd_ctx *c, const zngamd_bgzf_key_row *keys, uint64_t n, uint64_t *first, uint32_t *count, zngamd_dedup_totals *totals)
+try {
+    if (!dedup_args_ok(keys, n, totals)) return ZNGAMD_E_ARG;
+    if (!c) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    memset(totals, 0, sizeof *totals);
+    if (!n) return ZNGAMD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->dd_row.ensure(n)); HIPCHK(c, c->dd_tab.ensure(zngamd_dedup_scratch_bytes(n)));
+    if (first) HIPCHK(c, c->dd_first.ensure(n));
+    if (count) HIPCHK(c, c->dd_count.ensure(n));
+    HIPCHK(c, hipMemcpyAsync(c->dd_row.p, keys, (size_t)n * sizeof(ZaKeyRow), hipMemcpyHostToDevice, c->stream));
+    int r = dedup_dev(c, c->dd_row.p, n, c->dd_tab.p, first ? c->dd_first.p : nullptr, count ? c->dd_count.p : nullptr, totals);
+    if (r) return r;
+    if (first) HIPCHK(c, hipMemcpyAsync(first, c->dd_first.p, (size_t)n * 8u, hipMemcpyDeviceToHost, c->stream));
+    if (count) HIPCHK(c, hipMemcpyAsync(count, c->dd_count.p, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ZNGAMD_OK;
 } ZA_ABI_GUARD

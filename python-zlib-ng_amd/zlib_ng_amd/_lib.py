@@ -88,6 +88,7 @@ SYMBOLS = [
     "zngamd_bgzf_partition_records_dev", "zngamd_bgzf_partition_records",
     "zngamd_bgzf_trim_records_dev", "zngamd_bgzf_trim_records",
     "zngamd_bgzf_qc_records_dev", "zngamd_bgzf_qc_records",
+    "zngamd_bgzf_key_records_dev", "zngamd_bgzf_key_records", "zngamd_dedup_scratch_bytes", "zngamd_dedup_keys_dev", "zngamd_dedup_keys",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
@@ -256,6 +257,31 @@ class BgzfQcTotals(C.Structure):               # zngamd_bgzf_qc_totals
     @property
     def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is counted)
         return self.seen
+
+
+BGZF_KEY_IGNORE_CASE, BGZF_KEY_CANONICAL = 1, 2                                             # ZNGAMD_BGZF_KEY_*
+BGZF_KEY_SEED0, BGZF_KEY_SEED1 = 0x243F6A8885A308D3, 0x13198A2E03707344                       # ZNGAMD_BGZF_KEY_SEED0 / 1
+DEDUP_MAX_KEYS = 1 << 30                                                                      # ZNGAMD_DEDUP_MAX_KEYS
+KEY_ROW_DTYPE = np.dtype([("lo", "<u8"), ("hi", "<u8")])                                      # zngamd_bgzf_key_row
+
+
+class BgzfKeyConf(C.Structure):                # zngamd_bgzf_key_conf
+    _fields_ = [("record_lines", C.c_uint32), ("seq_line", C.c_int32), ("first_byte", C.c_int32), ("first", C.c_uint32), ("length", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 10)]
+
+
+class BgzfKeyTotals(C.Structure):              # zngamd_bgzf_key_totals
+    _fields_ = [("seen", C.c_uint64), ("bytes_in", C.c_uint64), ("bases", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64),
+                ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is keyed)
+        return self.seen
+
+
+class DedupTotals(C.Structure):                # zngamd_dedup_totals
+    _fields_ = [("n", C.c_uint64), ("unique", C.c_uint64), ("duplicates", C.c_uint64), ("max_count", C.c_uint64), ("max_first", C.c_uint64),
+                ("reserved", C.c_uint64)]
 
 
 BGZF_TABIX_FINAL, BGZF_FETCH_COUNT_ONLY, BGZF_FETCH_MAX_REGIONS = 4, 8, 4096      # ZNGAMD_BGZF_TABIX_FINAL, ZNGAMD_BGZF_FETCH_*
@@ -443,6 +469,15 @@ def load():
                                                      C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
             L.zngamd_bgzf_qc_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp, vp,
                                                  C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
+        if hasattr(L, "zngamd_bgzf_key_records"):           # as qc without the tables; then the two resolve calls and the size of their work area
+            L.zngamd_bgzf_key_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp,
+                                                      C.c_uint64, vp, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_key_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp, vp,
+                                                  C.c_uint64, ALLOC_FN, vp, vp]
+            L.zngamd_dedup_scratch_bytes.argtypes = [C.c_uint64]
+            L.zngamd_dedup_scratch_bytes.restype = C.c_uint64
+            L.zngamd_dedup_keys_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
+            L.zngamd_dedup_keys.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
         if hasattr(L, "zngamd_bgzf_tabix"):
             L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
                                                 C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1659,6 +1694,65 @@ class Context:
         r = self._chk(self.L.zngamd_bgzf_qc_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
                                                         C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_tables), tables_cap,
                                                         v(d_rows), rows_cap, C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def bgzf_key_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):
+        """zngamd_bgzf_key_records: the key of every record by the rule of conf (a BgzfKeyConf) -> (code, block statuses, totals
+        (BgzfKeyTotals), rows (KEY_ROW_DTYPE, one per record in record order; empty when totals.bad is set)).  caps None: the rows are
+        allocated once the engine knows how many there are; an integer: a buffer of that many rows, and code is BUF_ERROR when the
+        result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfKeyTotals()
+        box = []
+
+        def alloc(_user, nbytes):
+            box.append(np.empty(nbytes // KEY_ROW_DTYPE.itemsize, KEY_ROW_DTYPE))
+            return box[0].ctypes.data
+
+        if caps is None:
+            rp, rcap, fn = None, 0, ALLOC_FN(alloc)
+        else:
+            rcap = caps
+            rows = np.zeros(max(1, rcap), KEY_ROW_DTYPE)
+            rp, fn = C.c_void_p(rows.ctypes.data), ALLOC_FN()
+        r = self._chk(self.L.zngamd_bgzf_key_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                     text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
+                                                     rp, rcap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and tot.covered and tot.seen and not tot.bad
+        if caps is None:
+            rows_out = box[0] if got else np.empty(0, KEY_ROW_DTYPE)
+        else:
+            rows_out = rows[:tot.seen] if got else np.empty(0, KEY_ROW_DTYPE)
+        return r, st[:nm], tot, rows_out
+
+    def bgzf_key_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, record_base, d_scratch, scratch_cap,
+                             d_status, d_rows, rows_cap):
+        """zngamd_bgzf_key_records_dev on device pointers (conf: host memory) -> (code, totals); the rows stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfKeyTotals()
+        r = self._chk(self.L.zngamd_bgzf_key_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
+                                                         C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap,
+                                                         C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def dedup_keys(self, keys, want_first=True, want_count=True):
+        """zngamd_dedup_keys: keys (KEY_ROW_DTYPE) -> (totals (DedupTotals), first (uint64, or None), count (uint32, or None))"""
+        keys = np.ascontiguousarray(keys, KEY_ROW_DTYPE)
+        n = len(keys)
+        first = np.empty(n, np.uint64) if want_first else None
+        count = np.empty(n, np.uint32) if want_count else None
+        tot = DedupTotals()
+        p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and len(a) else None
+        self._chk(self.L.zngamd_dedup_keys(self.h, p(keys), n, p(first), p(count), C.byref(tot)))
+        return tot, first, count
+
+    def dedup_keys_dev(self, d_keys, n, d_scratch, scratch_cap, d_first, d_count):
+        """zngamd_dedup_keys_dev on device pointers -> (code, totals); first and count (either may be 0) stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = DedupTotals()
+        r = self._chk(self.L.zngamd_dedup_keys_dev(self.h, v(d_keys), n, v(d_scratch), scratch_cap, v(d_first), v(d_count), C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def _bgzf_grep(self, fn_c, tot, data, members, text_off, text_end, blob, table, delim, flags, extra, caps):

@@ -53,6 +53,7 @@ from . import _lib, devmem, zlib_ng
 __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offset", "split_virtual_offset", "BgzfReader", "BgzfWriter",
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
            "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP", "trim_records", "TrimResult", "KEPT", "TOO_SHORT", "DROPPED", "qc_records", "QcResult",
+           "key_records", "KeyResult", "pair_keys", "dedup_keys", "DedupResult", "dedup_records", "dedup_paired",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
 BadGzipFile = zlib_ng.BadGzipFile
@@ -700,7 +701,7 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
     _ClassifySink -- every window's records are not selected but assigned to their nearest pattern (classify_records(), demux()), the
     sink takes what each window gives, and what its finish() returns is the result.  partition (with records, instead of patterns): a
     _PartitionSink -- every window's records are split by the labels it holds (partition_records()) -- or a _TrimSink -- they are cut
-    (trim_records()) -- or a _QcSink -- they are counted (qc_records())."""
+    (trim_records()) -- or a _QcSink -- they are counted (qc_records()) -- or a _KeySink -- they are keyed (key_records())."""
     if partition is None:
         pats, delimiter = _grep_patterns(patterns, delimiter)
         mismatches = _grep_mismatches(mismatches, pats)
@@ -1544,6 +1545,289 @@ def qc_records(file, record_lines=4, *, seq_line=1, qual_line=3, quality_base=33
                               max_record=max_record, allow_short=allow_short)
     return _qc_file(file, None, record_lines, seq_line, qual_line, quality_base, cycles, low_quality, per_record, first_byte, delimiter, start, stop,
                     first_record, max_record, allow_short)
+
+
+# ---- duplicate records: a 16-byte key per record; the first record of every key and how many carry it
+_KEY_OPTIONS = ("first", "length", "ignore_case", "canonical")
+_M64 = (1 << 64) - 1
+DEDUP_LEVELS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 50, 100, 500, 1000, 5000, 10000)      # FastQC's duplication levels: 1 .. 9, >10, >50, ..
+
+
+class KeyResult:
+    """What key_records() made: keys (numpy, structured: lo and hi, uint64, one per record in the order of the file), records, bases
+    (the bytes of the sequence lines) and the options the keys were made with (first, length, ignore_case, canonical).  Keys made with
+    the same options are comparable wherever they come from: a + b puts the keys of two shards, or of two files, one behind the other,
+    and is a ValueError when the options differ."""
+
+    def __init__(self, keys, bases, options):
+        self.keys, self.records, self.bases = keys, len(keys), int(bases)
+        self.options = dict(options)
+        for name in _KEY_OPTIONS:
+            setattr(self, name, self.options[name])
+
+    def __len__(self):
+        return self.records
+
+    def __add__(self, other):
+        if not isinstance(other, KeyResult):
+            return NotImplemented
+        if self.options != other.options:
+            raise ValueError(f"keys made with {self.options} and with {other.options} are not comparable")
+        return KeyResult(np.concatenate([self.keys, other.keys]), self.bases + other.bases, self.options)
+
+    def __repr__(self):
+        return f"<KeyResult: {self.records} records, {self.bases} bases>"
+
+
+def _key_conf(record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter):
+    """-> (BgzfKeyConf, delimiter as bytes, the options of a KeyResult); ValueError as key_records() documents it"""
+    delimiter = _partition_delimiter(delimiter)
+    k, _, b = _grep_record_args(record_lines, None, first_byte)
+    s = _trim_int(seq_line, 0, k - 1, "seq_line")
+    for name, value in (("ignore_case", ignore_case), ("canonical", canonical)):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{name} is True or False, not {value!r}")
+    first, length = _trim_int(first, 0, (1 << 32) - 1, "first"), _trim_int(length, 0, (1 << 32) - 1, "length")
+    flags = (_lib.BGZF_KEY_IGNORE_CASE if ignore_case else 0) | (_lib.BGZF_KEY_CANONICAL if canonical else 0)
+    return (_lib.BgzfKeyConf(k, s, b, first, length, flags), delimiter,
+            dict(first=first, length=length, ignore_case=bool(ignore_case), canonical=bool(canonical)))
+
+
+class _KeySink:
+    """what _grep_file hands a window's records to when they are keyed: the windows' rows are put one behind the other"""
+
+    def __init__(self, conf, options):
+        self.conf, self.options, self.rows, self.bases = conf, options, [], 0
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        _, status, tot, self.win_rows = ctx.bgzf_key_records(data, members, text_off, text_end, delim, flags, self.conf, record_base)
+        return status, tot, b""
+
+    def window(self, tot, packed):
+        if not tot.seen:
+            return
+        if len(self.win_rows) != tot.seen:
+            raise RuntimeError("key_records: the rows do not add up to the records")
+        self.bases += int(tot.bases)
+        self.rows.append(self.win_rows)
+
+    def finish(self, searched):
+        keys = np.concatenate(self.rows) if self.rows else np.empty(0, _lib.KEY_ROW_DTYPE)
+        if len(keys) != searched:
+            raise RuntimeError("key_records: the rows do not add up to the records")
+        return KeyResult(keys, self.bases, self.options)
+
+
+def _key_file(fp, ctx, record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter, start, stop, first_record, max_record,
+              allow_short):
+    conf, delimiter, options = _key_conf(record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter)
+    return _grep_file(fp, ctx, None, delimiter, False, False, False, None, start, stop, first_record, max_record,
+                      (record_lines, None, first_byte, allow_short), 0, None, _KeySink(conf, options))
+
+
+def key_records(file, record_lines=4, *, seq_line=1, first=0, length=0, ignore_case=False, canonical=False, first_byte=None, delimiter=b"\n",
+                start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+    """The sequence of every record of a BGZF file reduced to a 16-byte key on the GPU: equal sequences get equal keys, in any window,
+    shard or file.  The keyed part is body[first : first + length] of the line seq_line (length 0: to the end; a shorter body gives what
+    it has).  ignore_case takes a .. z as A .. Z; canonical gives a read and its reverse complement (A<->T, C<->G, U->A, in either case)
+    the same key.  The key function is fixed and documented: two 64-bit sums of splitmix64-mixed (position, byte)
+    terms.  Equal keys are treated as equal sequences, as fastp treats its hashes: two different sequences meet in a key with a
+    probability of about 2**-128 per pair.  record_lines, first_byte, delimiter, start, stop, first_record, max_record, allow_short and
+    the errors of the file are those of grep_records().  -> KeyResult; the results of the parts of
+    LineIndex.shards(reader, n, lines_per_record=k), put together with +, are the whole file's."""
+    if _is_path(file):
+        _key_conf(record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter)      # (judged before the file is opened)
+        with _builtin_open(file, "rb") as f:
+            return key_records(f, record_lines, seq_line=seq_line, first=first, length=length, ignore_case=ignore_case, canonical=canonical,
+                               first_byte=first_byte, delimiter=delimiter, start=start, stop=stop, first_record=first_record, max_record=max_record,
+                               allow_short=allow_short)
+    return _key_file(file, None, record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter, start, stop, first_record,
+                     max_record, allow_short)
+
+
+def _key_array(keys):
+    """keys as one-dimensional KEY_ROW_DTYPE: a KeyResult, a structured array of lo and hi, or uint64 of shape (n, 2)"""
+    if isinstance(keys, KeyResult):
+        keys = keys.keys
+    keys = np.asarray(keys)
+    if keys.dtype == _lib.KEY_ROW_DTYPE and keys.ndim == 1:
+        return np.ascontiguousarray(keys)
+    if keys.dtype == np.uint64 and keys.ndim == 2 and keys.shape[1] == 2:
+        return np.ascontiguousarray(keys).view(_lib.KEY_ROW_DTYPE).reshape(-1)
+    raise ValueError("keys is a KeyResult, a one-dimensional array of (lo, hi) rows or a uint64 array of shape (n, 2)")
+
+
+def _mix64(x):
+    """the splitmix64 step on a uint64 array"""
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+def pair_keys(a, b):
+    """Paired-end keys, on the host alone: the key of the pair (record i of a, record i of b), for dedup_keys().  Two pairs get the
+    same key when both mates' keys are equal, as fastp dedups pairs; the order counts: (x, y) and (y, x) differ.  Word w of the pair's
+    key is mix(mix(mix(mix(S_w ^ a.lo) ^ a.hi) ^ b.lo) ^ b.hi) with the mixer and seeds of key_records().  a and b are KeyResults (made
+    with the same options) or key arrays of equal length; -> a KeyResult when both are, otherwise the key array."""
+    results = isinstance(a, KeyResult) and isinstance(b, KeyResult)
+    if results and a.options != b.options:
+        raise ValueError(f"keys made with {a.options} and with {b.options} are not comparable")
+    ka, kb = _key_array(a), _key_array(b)
+    if len(ka) != len(kb):
+        raise ValueError(f"pair_keys: the two files hold {len(ka)} and {len(kb)} records (unequal length): the files are out of step")
+    out = np.empty(len(ka), _lib.KEY_ROW_DTYPE)
+    for word, seed in (("lo", _lib.BGZF_KEY_SEED0), ("hi", _lib.BGZF_KEY_SEED1)):
+        h = _mix64(np.uint64(seed) ^ ka["lo"])
+        for x in (ka["hi"], kb["lo"], kb["hi"]):
+            h = _mix64(h ^ x)
+        out[word] = h
+    return KeyResult(out, a.bases + b.bases, a.options) if results else out
+
+
+class DedupResult:
+    """What dedup_keys() found.  Per record, in the order of the keys: first (int64: the first record that carries the record's key;
+    first[i] == i for a record that is kept), count (int64: at the first record of a key, how many records carry it; 0 elsewhere) and
+    duplicate (bool: first[i] != i).  The totals: records, unique (the distinct keys), duplicates (records - unique),
+    duplication_rate (duplicates / records), max_count (the largest group) and max_first (its first record)."""
+
+    def __init__(self, first, count, unique, max_count, max_first):
+        self.first, self.count = first, count
+        self.records = len(first)
+        self.duplicate = first != np.arange(self.records, dtype=np.int64)
+        self.unique, self.max_count, self.max_first = int(unique), int(max_count), int(max_first)
+        self.duplicates = self.records - self.unique
+
+    def __len__(self):
+        return self.records
+
+    @property
+    def duplication_rate(self):
+        return self.duplicates / self.records if self.records else 0.0
+
+    def most_common(self, k=10):
+        """-> (first records, counts) of the k largest groups, the largest first, the earlier record first among equals"""
+        heads = np.nonzero(self.count)[0]
+        order = heads[np.argsort(-self.count[heads], kind="stable")][:max(0, int(k))]
+        return order, self.count[order]
+
+    def levels(self, edges=DEDUP_LEVELS):
+        """FastQC's duplication-level table: bin i holds the sequences that occur edges[i] .. edges[i + 1] - 1 times, the last bin those
+        that occur edges[-1] times or more.  -> (distinct, reads), int64, one entry per edge: the distinct sequences of every bin and
+        the reads they stand for.  edges rise strictly from 1."""
+        e = np.asarray(edges)
+        if e.ndim != 1 or not len(e) or e.dtype.kind not in "iu" or e[0] != 1 or (np.diff(e) <= 0).any():
+            raise ValueError("edges is a list of integers that rise strictly from 1")
+        sizes = self.count[self.count > 0]
+        at = np.searchsorted(e, sizes, "right") - 1
+        distinct = np.bincount(at, minlength=len(e)).astype(np.int64)
+        reads = np.bincount(at, weights=sizes, minlength=len(e)).astype(np.int64)
+        return distinct, reads
+
+    def drop(self):
+        """uint8, one per record, 1 for a duplicate: the drop= of trim_records()"""
+        return self.duplicate.astype(np.uint8)
+
+    def labels(self, duplicate_class=1):
+        """int64, one per record for partition_records(): 0 for a record that is kept, duplicate_class (which may be DROP) for a duplicate"""
+        return np.where(self.duplicate, np.int64(duplicate_class), np.int64(0))
+
+    def __repr__(self):
+        return (f"<DedupResult: {self.records} records, {self.unique} unique, {self.duplicates} duplicates "
+                f"({100 * self.duplication_rate:.1f} %), the most common one {self.max_count} times>")
+
+
+def _dedup(ctx, keys):
+    keys = _key_array(keys)
+    if len(keys) > _lib.DEDUP_MAX_KEYS:
+        raise ValueError(f"dedup_keys takes at most {_lib.DEDUP_MAX_KEYS} keys, not {len(keys)}")
+    ctx = ctx or zlib_ng._ctx()                              # (the arguments are judged before a context is asked for)
+    tot, first, count = ctx.dedup_keys(keys)
+    if tot.n != len(keys):
+        raise RuntimeError("dedup_keys: the engine counted other keys than it was given")
+    return DedupResult(first.astype(np.int64), count.astype(np.int64), tot.unique, tot.max_count, tot.max_first)
+
+
+def dedup_keys(keys):
+    """Resolve keys on the GPU: for every key the first record that carries it and how many do.  keys is a KeyResult (of a file, or
+    of several shards or files put together with +, or of pair_keys()), a structured array of (lo, hi) rows or uint64 of shape (n, 2);
+    at most 2**30 of them.  Equal keys are treated as equal sequences.  -> DedupResult; it depends on the keys alone."""
+    return _dedup(None, keys)
+
+
+def _dedup_outputs(res, output, duplicates):
+    """-> (labels, outputs) for partition_records: the first record of every key to output, the rest to duplicates or nowhere"""
+    if duplicates is None:
+        return res.labels(DROP), [output]
+    return res.labels(1), [output, duplicates]
+
+
+def _dedup_file(fp, ctx, output, duplicates, record_lines, compresslevel, block_size, seq_line, first, length, ignore_case, canonical, first_byte, delimiter,
+                start, stop, first_record, max_record, allow_short):
+    _key_conf(record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter)
+    _check_block_size(block_size)
+    keys = _key_file(fp, ctx, record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter, start, stop, first_record, max_record,
+                     allow_short)
+    res = _dedup(ctx, keys)
+    if output is None and duplicates is None:
+        return res
+    labels, outputs = _dedup_outputs(res, output, duplicates)
+    _partition_file(fp, ctx, labels, outputs, record_lines, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record,
+                    allow_short)
+    return res
+
+
+def dedup_records(file, output, record_lines=4, *, duplicates=None, compresslevel=6, block_size=MAX_BLOCK_INPUT, seq_line=1, first=0, length=0,
+                  ignore_case=False, canonical=False, first_byte=None, delimiter=b"\n", start=None, stop=None, first_record=0, max_record=64 << 20,
+                  allow_short=False):
+    """Remove the duplicate records of a BGZF file -- fastp --dedup, seqkit rmdup -s, clumpify dedupe: records whose sequences are equal
+    (by the key options of key_records(): seq_line, first, length, ignore_case, canonical).  Two passes over the file: key_records()
+    and one dedup_keys(), then partition_records(): the first record of every sequence goes to output, whole and in the order of the
+    file; the others go to duplicates (a path, a file, or None: they are written nowhere).  output=None (with duplicates=None) only
+    counts and makes no second pass.  compresslevel and block_size are those of the outputs; the other keywords and the errors of the
+    file are those of grep_records().  -> DedupResult.  Equal keys are treated as equal sequences (see key_records()).
+    Not done here: keeping the copy of the best quality instead of the first, near-duplicates (reads that differ by a sequencing error),
+    optical duplicates by their coordinates."""
+    if _is_path(file):
+        _key_conf(record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter)      # (judged before the file is opened)
+        _check_block_size(block_size)
+        with _builtin_open(file, "rb") as f:
+            return dedup_records(f, output, record_lines, duplicates=duplicates, compresslevel=compresslevel, block_size=block_size, seq_line=seq_line,
+                                 first=first, length=length, ignore_case=ignore_case, canonical=canonical, first_byte=first_byte, delimiter=delimiter,
+                                 start=start, stop=stop, first_record=first_record, max_record=max_record, allow_short=allow_short)
+    return _dedup_file(file, None, output, duplicates, record_lines, compresslevel, block_size, seq_line, first, length, ignore_case, canonical, first_byte,
+                       delimiter, start, stop, first_record, max_record, allow_short)
+
+
+def dedup_paired(files, outputs, record_lines=4, *, duplicates=None, compresslevel=6, block_size=MAX_BLOCK_INPUT, seq_line=1, first=0, length=0,
+                 ignore_case=False, canonical=False, first_byte=None, delimiter=b"\n", start=None, stop=None, first_record=0, max_record=64 << 20,
+                 allow_short=False):
+    """dedup_records() for the two files of a paired-end run: a pair is a duplicate when BOTH mates equal those of an earlier pair
+    (pair_keys(): as fastp dedups pairs).  files are two paths or seekable binary files whose records go together; outputs one output
+    per file (or None: count only); duplicates None or one entry per file; start and stop None or one virtual offset per file.  Every
+    file is split by the same labels, so mates stay in step: record i of outputs[0] and record i of outputs[1] are a pair.  -> the
+    DedupResult of the pairs.  Files that hold different numbers of records are a ValueError that says they are out of step."""
+    files = list(files) if isinstance(files, (list, tuple)) else [files]
+    nf = len(files)
+    if nf != 2:
+        raise ValueError(f"dedup_paired takes the two files of a paired run, not {nf}")
+    _key_conf(record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter)
+    _check_block_size(block_size)
+    if outputs is not None and (not isinstance(outputs, (list, tuple)) or len(outputs) != nf):
+        raise ValueError(f"dedup_paired: outputs is None or one entry per file ({nf})")
+    duplicates, start, stop = _per_file(duplicates, nf, "duplicates"), _per_file(start, nf, "start"), _per_file(stop, nf, "stop")
+    with contextlib.ExitStack() as stack:
+        fps = [stack.enter_context(_builtin_open(f, "rb")) if _is_path(f) else f for f in files]
+        keys = [_key_file(fps[f], None, record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter, start[f], stop[f],
+                          first_record, max_record, allow_short) for f in range(nf)]
+        res = _dedup(None, pair_keys(keys[0], keys[1]))
+        if outputs is not None:
+            for f in range(nf):
+                labels, outs = _dedup_outputs(res, outputs[f], duplicates[f])
+                _partition_file(fps[f], None, labels, outs, record_lines, first_byte, delimiter, compresslevel, block_size, start[f], stop[f],
+                                first_record, max_record, allow_short)
+    return res
 
 
 def _per_file(value, n_files, name):
@@ -3169,6 +3453,35 @@ class BgzfReader(io.BufferedIOBase):
         try:
             return _qc_file(self._fp, self._ctx, record_lines, seq_line, qual_line, quality_base, cycles, low_quality, per_record, first_byte, delimiter,
                             start, stop, first_record, max_record, allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def key_records(self, record_lines=4, *, seq_line=1, first=0, length=0, ignore_case=False, canonical=False, first_byte=None, delimiter=b"\n",
+                    start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+        """bgzf.key_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("key_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _key_file(self._fp, self._ctx, record_lines, seq_line, first, length, ignore_case, canonical, first_byte, delimiter, start, stop,
+                             first_record, max_record, allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def dedup_records(self, output, record_lines=4, *, duplicates=None, compresslevel=6, block_size=MAX_BLOCK_INPUT, seq_line=1, first=0, length=0,
+                      ignore_case=False, canonical=False, first_byte=None, delimiter=b"\n", start=None, stop=None, first_record=0,
+                      max_record=64 << 20, allow_short=False):
+        """bgzf.dedup_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("dedup_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _dedup_file(self._fp, self._ctx, output, duplicates, record_lines, compresslevel, block_size, seq_line, first, length, ignore_case,
+                               canonical, first_byte, delimiter, start, stop, first_record, max_record, allow_short)
         finally:
             self._fp.seek(at)
 
