@@ -166,7 +166,15 @@ int zngamd_deflate_blocks_packed_dev(zngamd_ctx *ctx, const void *d_in, uint64_t
  * resolve them.  unit_in_len / unit_out_len are HOST arrays (compressed bytes of a unit including its sync marker; its output
  * bytes), d_index device memory, d_dict / dict_len the history in front of the first unit (may be NULL / 0).  Returns
  * ZNGAMD_STREAM_END with *out_len, ZNGAMD_BUF_ERROR with the size needed, ZNGAMD_E_INDEX when stream and index do not fit (the
- * caller then decodes with zngamd_inflate_raw_dev), ZNGAMD_DATA_ERROR for invalid deflate data. */
+ * caller then decodes with zngamd_inflate_raw_dev), ZNGAMD_DATA_ERROR for invalid deflate data.
+ * d_def must be readable for 64 bytes past def_len (the decoder's look-ahead, as for the other device entry points); the three
+ * index arrays may hold anything: every number in them is checked against the stream before a byte is handed out (see DESIGN.md
+ * section 5, "What pins the index"), so ZNGAMD_STREAM_END means the bytes any inflater decodes from the sum(unit_in_len) bytes
+ * the units cover (whether those are all of the stream is the caller's to compare: the call does not look behind them) -- an index the
+ * checks cannot vouch for is ZNGAMD_E_INDEX (or ZNGAMD_DATA_ERROR where a wrong entry sends a lane into the middle of a code).
+ * A unit with unit_out_len 0 must be the empty unit the packer writes (00 00 00 FF FF, or 03 00 closing the stream).  Also
+ * ZNGAMD_E_INDEX: a batch of units (ZNGAMD_UNIT_BATCH, default 16 384) that starts behind fewer than 32 768 bytes of output --
+ * units of a few hundred bytes; such a stream is decoded without its index. */
 #define ZNGAMD_INDEX_STRIDE 68
 int zngamd_deflate_index_dev(zngamd_ctx *ctx, uint32_t *d_index, uint32_t n_units);
 int zngamd_inflate_units_indexed_dev(zngamd_ctx *ctx, const void *d_def, uint64_t def_len, const uint32_t *unit_in_len,
@@ -1338,7 +1346,8 @@ int zngamd_abi(void);
 #define ZNGAMD_PATH_SEQUENTIAL 3
 #define ZNGAMD_PATH_COUNT      4
 int zngamd_decode_paths(zngamd_ctx *ctx, uint64_t *members /*[ZNGAMD_PATH_COUNT]*/, int reset);
-/* units decoded with a writer's segment index (zngamd_inflate_units_indexed_dev, or the windowed reader with zngamd_gz_state.index) */
+/* units decoded with a writer's segment index (zngamd_inflate_units_indexed_dev, or the windowed reader with zngamd_gz_state.index);
+ * a batch the index was refused for is not counted */
 uint64_t zngamd_indexed_units(zngamd_ctx *ctx, int reset);
 
 /* ---- debugging aid for the parity tests: copy a stage's intermediate of unit `u` of the last

@@ -34,7 +34,17 @@ __global__ __launch_bounds__(64, 5) void za_k_inflate_units_marked(const uint8_t
     const int n = (int)m.out_len;
     const int nseg = (int)m.nseg;
     if (m.in_off + m.in_len > in_total || m.out_off + ZA_WIN + (uint64_t)m.out_len > out_cap || n > ZA_MAX_UNIT || m.in_len > (1u << 20) ||
-        nseg != ((n + ZA_SEG - 1) >> ZA_SEG_SHIFT) || n == 0 || hist > (uint32_t)ZA_WIN) ZA_UM_FAIL(ZA_I_INDEX);
+        nseg != ((n + ZA_SEG - 1) >> ZA_SEG_SHIFT) || hist > (uint32_t)ZA_WIN) ZA_UM_FAIL(ZA_I_INDEX);
+    if (n == 0) {
+        // a unit the index calls EMPTY must be what za_k_pack writes for no input: the sync marker alone (an empty stored block,
+        // 00 00 00 FF FF) or, as the stream's last block, 03 00 -- anything else holds bytes that the index would hide.  (The host
+        // puts these units behind the batch's others: no area, no queue, no index row is theirs, and none is touched.)
+        const bool sync = m.in_len == 5u && src[0] == 0u && za_ld32(src + 1) == 0xFFFF0000u;
+        const bool fin = m.in_len == 2u && src[0] == 0x03u && src[1] == 0u;
+        if (!sync && !fin) ZA_UM_FAIL(ZA_I_INDEX);
+        if (lane == 0) { ZaChunkRes r; r.status = fin ? ZA_I_END : ZA_I_SYNC; r.max_back = 0; r.bits = (m.in_off + m.in_len) * 8ull; r.out_len = 0; res_out[blockIdx.x] = r; }
+        return;
+    }
     const uint32_t *index = ext_index + (size_t)blockIdx.x * ZA_CIDX_STRIDE;
     if (index[nseg] == 0u) {
         // a unit of STORED blocks (what the packer writes for input that does not compress; its index is all zeros): blocks of at

@@ -2222,10 +2222,13 @@ static int inflate_units_core(zngamd_ctx *c, const uint8_t *d_def, uint64_t def_
     constexpr uint64_t AREA = (uint64_t)ZA_WIN + ZA_MAX_UNIT;                 // symbols of a unit's area: markers, then the unit
     static const uint32_t batch = [] { const char *e = getenv("ZNGAMD_UNIT_BATCH"); long v = e ? atol(e) : 16384; return (uint32_t)(v < 64 ? 64 : v > 65536 ? 65536 : v); }();
     uint64_t in_at = 0, out_at = 0;
-    std::vector<ZaMember> hm; std::vector<ZaChunk> chain; std::vector<ZaChunkRes> res; std::vector<uint32_t> uidx;
+    std::vector<ZaMember> hm, he; std::vector<ZaChunk> chain; std::vector<ZaChunkRes> res; std::vector<uint32_t> uidx;
     for (uint32_t u0 = 0; u0 < n_units; u0 += batch) {
         const uint32_t u1 = std::min(n_units, u0 + batch);
-        hm.clear(); chain.clear(); uidx.clear();
+        // (the window kernels take the bytes in front of a batch from the output: a batch behind fewer than 32 768 of them -- blocks
+        // of a few hundred bytes -- is left to the decoder that needs no index)
+        if (out_at && out_at < (uint64_t)ZA_WIN) return fail(c, ZNGAMD_E_INDEX, "a batch of units shorter than the window: decode it without the index");
+        hm.clear(); he.clear(); chain.clear(); uidx.clear();
         uint64_t acc = 0;                                                     // output of this batch so far
         for (uint32_t u = u0; u < u1; u++) {
             if (unit_out_len[u] != 0) {
@@ -2237,11 +2240,16 @@ static int inflate_units_core(zngamd_ctx *c, const uint8_t *d_def, uint64_t def_
                 ch.src_off = m.out_off + ZA_WIN;
                 hm.push_back(m); chain.push_back(ch); uidx.push_back(u);
                 acc += unit_out_len[u];
+            } else {
+                // a unit the index calls empty decodes to nothing, but its bytes must BE an empty unit: the kernel looks at them
+                ZaMember m;
+                m.in_off = in_at; m.in_len = unit_in_len[u]; m.out_off = 0; m.out_len = 0; m.crc = 0; m.index_off = 0; m.nseg = 0;
+                he.push_back(m);
             }
             in_at += unit_in_len[u];
         }
-        const uint32_t m = (uint32_t)hm.size();
-        if (m == 0) continue;
+        const uint32_t m = (uint32_t)hm.size(), ne = (uint32_t)he.size();      // units with output (areas, rows, windows); then the empty ones
+        hm.insert(hm.end(), he.begin(), he.end());
         // the units' index rows are picked by unit number: the kernel reads row blockIdx.x, so a batch without empty units passes
         // its first row; one with empty units has its rows gathered
         const uint32_t *d_rows = d_index + (size_t)u0 * ZA_CIDX_STRIDE;
@@ -2260,33 +2268,33 @@ static int inflate_units_core(zngamd_ctx *c, const uint8_t *d_def, uint64_t def_
             if (c->uarea.cap != cap0 || c->uarea.p != p0) c->uarea_marked = 0;
         }
         if (c->uarea.cap < (size_t)m * AREA + 64) return fail(c, ZNGAMD_E_HIP, "unit areas");
-        HIPCHK(c, c->members.ensure(m)); HIPCHK(c, c->cres.ensure(m)); HIPCHK(c, c->cchunks.ensure(m));
+        HIPCHK(c, c->members.ensure(m + ne)); HIPCHK(c, c->cres.ensure(m + ne)); HIPCHK(c, c->cchunks.ensure(m));
         HIPCHK(c, c->matchq.ensure((size_t)m * 64 * ZA_MATCHQ_PER_SEG));
         const uint32_t groups = (m + ZA_CHUNK_GROUP - 1) / ZA_CHUNK_GROUP;
         HIPCHK(c, c->winbuf.ensure((size_t)groups * ZA_WIN)); HIPCHK(c, c->ccomp.ensure((size_t)m * ZA_WIN));
-        HIPCHK(c, hipMemcpyAsync(c->members.p, hm.data(), (size_t)m * sizeof(ZaMember), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->cchunks.p, chain.data(), (size_t)m * sizeof(ZaChunk), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->members.p, hm.data(), (size_t)(m + ne) * sizeof(ZaMember), hipMemcpyHostToDevice, c->stream));
+        if (m) HIPCHK(c, hipMemcpyAsync(c->cchunks.p, chain.data(), (size_t)m * sizeof(ZaChunk), hipMemcpyHostToDevice, c->stream));
         { ProfScope ps(c, ZNGAMD_K_INFLATE);
           if (c->uarea_marked < m) {
               hipLaunchKernelGGL(za_k_fill_marker_prefix, dim3(m - c->uarea_marked), dim3(256), 0, c->stream, c->uarea.p + (uint64_t)c->uarea_marked * AREA, AREA);
               c->uarea_marked = m;
           }
-          hipLaunchKernelGGL(za_k_inflate_units_marked, dim3(m), dim3(64), 0, c->stream, d_def, def_len, c->members.p, c->uarea.p, (uint64_t)c->uarea.cap,
+          hipLaunchKernelGGL(za_k_inflate_units_marked, dim3(m + ne), dim3(64), 0, c->stream, d_def, def_len, c->members.p, c->uarea.p, (uint64_t)c->uarea.cap,
                              c->matchq.p, d_rows, c->cres.p); }
         HIPCHK(c, hipGetLastError());
-        res.resize(m);
-        HIPCHK(c, hipMemcpyAsync(res.data(), c->cres.p, (size_t)m * sizeof(ZaChunkRes), hipMemcpyDeviceToHost, c->stream));
+        res.resize(m + ne);
+        HIPCHK(c, hipMemcpyAsync(res.data(), c->cres.p, (size_t)(m + ne) * sizeof(ZaChunkRes), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->indexed_units += m;
-        for (uint32_t k = 0; k < m; k++) {
+        for (uint32_t k = 0; k < m + ne; k++) {
             if (res[k].status == ZA_I_DATA) return fail(c, ZNGAMD_DATA_ERROR, "invalid deflate data");
             if ((res[k].status != ZA_I_SYNC && res[k].status != ZA_I_END) || res[k].out_len != hm[k].out_len)
                 return fail(c, ZNGAMD_E_INDEX, "the index does not fit the stream (or the stream is not this engine's indexed form): decode it without the index");
         }
+        c->indexed_units += m;                  // (counted once the index has held for them: a refused batch decodes nothing)
+        if (m == 0) continue;                   // only empty units: nothing for the windows
         // windows in front of the units, then markers -> bytes (the chunk pipeline's kernels: a unit is a chunk)
         const uint8_t *bd = out_at ? d_out + out_at - std::min<uint64_t>(ZA_WIN, out_at) : (const uint8_t *)d_dict;
         const uint32_t bdl = out_at ? (uint32_t)std::min<uint64_t>(ZA_WIN, out_at) : dict_len;
-        if (out_at && out_at < (uint64_t)ZA_WIN) return fail(c, ZNGAMD_E_ARG, "a batch of units shorter than the window");
         { ProfScope ps(c, ZNGAMD_K_INFLATE);
           hipLaunchKernelGGL(za_k_chunk_compose, dim3(groups), dim3(1024), 0, c->stream, c->uarea.p, c->cchunks.p, m, c->ccomp.p);
           hipLaunchKernelGGL(za_k_chunk_chain, dim3(1), dim3(1024), 0, c->stream, c->ccomp.p, m, c->winbuf.p, bd, bdl);

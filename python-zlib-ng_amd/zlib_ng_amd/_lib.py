@@ -838,6 +838,10 @@ def parse_index_tail(fp, start, end):
         rec = np.concatenate(parts) if len(parts) != 1 else parts[0]
         if int(rec["in_len"].astype(np.int64).sum()) + 10 + 10 != dbytes:        # header, units, 03 00, trailer
             return None
+        fp.seek(start + dbytes - 4)                                  # the units' output is the member's: ISIZE (modulo 2^32)
+        isize = fp.read(4)
+        if len(isize) != 4 or (int(rec["out_len"].astype(np.int64).sum()) & 0xFFFFFFFF) != struct.unpack("<I", isize)[0]:
+            return None
         rows = np.zeros((nu, INDEX_STRIDE), np.uint32)
         nseg = (rec["out_len"].astype(np.int64) + 2047) >> 11
         cum = np.cumsum(rec["e"].astype(np.uint32), axis=1, dtype=np.uint32)

@@ -342,7 +342,8 @@ def test_index_members_round_trip_and_are_skipped_by_any_gzip_reader():
     e[5] = 0                                                 # a unit of stored blocks: all zeros
     rec["e"] = e
     payload = bytes(int(rec["in_len"].astype(np.int64).sum()))     # stands for the units' deflate bytes (never decoded here)
-    data_member = bytes.fromhex("1f8b0800" "00000000" "00ff") + payload + b"\x03\x00" + struct.pack("<II", 0, 0)
+    isize = int(rec["out_len"].astype(np.int64).sum()) & 0xFFFFFFFF    # (the parser holds the units' output against the member's ISIZE)
+    data_member = bytes.fromhex("1f8b0800" "00000000" "00ff") + payload + b"\x03\x00" + struct.pack("<II", 0, isize)
     tail = _lib.index_members([rec[:1000], rec[1000:]], len(data_member))
     plain = bytes.fromhex("1f8b0800" "00000000" "00ff" "0300" "00000000" "00000000")
     for blob in (data_member + tail, data_member + tail + plain, b"x" * 777 + data_member + tail + plain):

@@ -23,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ("fuzz_indexed_chain.py", 3, 25),        # the writer's segment index: units of every kind and size decoded side by side, files through writer and readers
     ("fuzz_small_calls.py", 5, 40),          # the one-shot calls' small paths: 16 KiB units, one-copy results, checksums beside the kernels, the small inflate path
     ("fuzz_long_matches.py", 11, 30),        # zero runs, periods and sparse bytes at levels 4-9: the dynamic programme's long-match path, multi-unit batches
+    ("fuzz_index_rows.py", 3, 40),           # wrong segment indexes (tests/index_mutations.py, composed) into the unit decoder: refused, or the right bytes
 ])
 def test_fuzz_script_smallest_seed(script, seed, cases):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "profiles", script), str(seed), str(cases)], cwd=ROOT,
