@@ -9,7 +9,9 @@
 //   k_chains<A|B|C>  one 4-wave workgroup per run of units, launched once per link table (5-, 3-, 12-byte contexts); 32-bit head
 //             table (64 KiB) in LDS; the 64 positions of a step are inserted by ONE returning LDS atomic maximum, which also
 //             yields every position's link
-//   k_search  one 1024-thread workgroup per run; links of table A and the bytes of the sliding window staged in LDS rings;
+//   k_chains2<B,C|A,B>  the same for two link tables from one staging of the input: one 8-wave workgroup per run (levels 5-9: B and
+//             C behind k_chains<A>; levels 1-4: A and B, no other chain launch)
+//   k_search one 1024-thread workgroup per run; links of table A and the bytes of the sliding window staged in LDS rings;
 //             every position searched in parallel: a walk over chain A, then its own links in tables B and C
 //   k_dpstats + k_optparse (levels 4-9)  the unit's cost table from a quarter of its entries; then one wave per unit, one lane per
 //             segment: backward dynamic programme over estimated bit costs, rewrites the search results so that the greedy parse
@@ -59,6 +61,23 @@
 // (a right shift and an AND; a left shift runs at half rate on this chip, profiles/ubench_issue2.hip)
 #define ZA_CH_OFFS(x) (((x) >> (32 - ZA_HASH_BITS - 2)) & (((1u << ZA_HASH_BITS) - 1u) << 2))
 #define ZA_CH_CHUNK (64 * ZA_CH_GROUP)         // positions = bytes of a group: 16 per lane
+// Which link tables are built by one launch (za_k_chains2, below): 1 = with table C (levels 5-9) A, then B and C together,
+// without it A and B together; 2 = A and B together, then C (the other pairing, for timing); 0 = one launch per table.  The
+// profiling and ablation switches of the single-table kernel select 0: they measure that kernel.
+#if defined(ZA_CH_STATS) || defined(ZA_ABL_CH_NOHASH) || defined(ZA_ABL_CH_NOATOMIC) || defined(ZA_ABL_CH_NOCHECK) || defined(ZA_ABL_CH_NOSTORE) || \
+    defined(ZA_ABL_CH_HALFREADS) || defined(ZA_ABL_CH_HALFWRITES)
+#undef ZA_CH_PAIR
+#define ZA_CH_PAIR 0
+#endif
+#ifndef ZA_CH_PAIR
+#define ZA_CH_PAIR 1
+#endif
+// -DZA_CH_FORCE_FIX: every group's links go through the lane-by-lane fallback of the order check (both kernels; testing only)
+#ifdef ZA_CH_FORCE_FIX
+#define ZA_CH_FORCE_FIX_ON true
+#else
+#define ZA_CH_FORCE_FIX_ON false
+#endif
 
 // A 16-byte load whose wait is written by hand.  The compiler's own waits were the chain kernel's whole time: it staged a chunk
 // behind `s_waitcnt vmcnt(0)` -- every load in flight, the one issued a moment ago included, because it had shuffled that load's
@@ -292,7 +311,7 @@ __global__ __launch_bounds__(256) void za_k_chains(const uint8_t *__restrict__ i
 #pragma unroll
             for (int g = 0; g < ZA_CH_GROUP; g++) top |= (A0 + 64u * (uint32_t)g - old[g] - 1u);
 #ifndef ZA_ABL_CH_NOCHECK
-            if (__builtin_expect(__ballot((int)top < 0) != 0ull, 0)) {
+            if (__builtin_expect(ZA_CH_FORCE_FIX_ON || __ballot((int)top < 0) != 0ull, 0)) {
 #pragma unroll 1
                 for (int g = 0; g < ZA_CH_GROUP; g++) {
                     const int i = (int)li + 64 * g;
@@ -421,6 +440,298 @@ __global__ __launch_bounds__(256) void za_k_chains(const uint8_t *__restrict__ i
     if (lane == 0 && role == 2u && TABLE == 0) for (int i = 0; i < 4; i++) atomicAdd(&za_ch_stat[24 + i], st_ph[i]);
     if (lane == 0) { atomicAdd(&za_ch_stat[8 * TABLE + 2 * role], st_wait); atomicAdd(&za_ch_stat[8 * TABLE + 2 * role + 1], clock64() - st_t0); }
 #endif
+}
+
+// A row shorter than one 16-byte load (a stream of up to 15 bytes without a dictionary, nothing carried), by one wave: lane i
+// takes row index i and looks at the lanes below it; no table is touched, nothing follows such a row.  A row shorter than the
+// context inserts nothing and gets zeros.
+template <int TABLE>
+__device__ __forceinline__ void za_ch_short_row(const uint8_t *row, uint32_t lane, int first, int total, uint16_t *prevdist)
+{
+    constexpr int HB = ZaTableBytes<TABLE>::value;
+    uint32_t h = 0xFFFFFFFFu;
+    const bool ins = (int)lane >= first && (int)lane <= total - HB;
+    if (ins) {
+        uint32_t w[3] = {0u, 0u, 0u};                // exactly the context's bytes, one by one (the row may end at the caller's last byte)
+#pragma unroll
+        for (int b = 0; b < HB; b++) w[b >> 2] |= (uint32_t)row[lane + b] << (8 * (b & 3));
+        h = za_hash_x<TABLE>(w[0], w[1], w[2]) >> (32 - ZA_HASH_BITS);
+    }
+    uint32_t d = 0;
+    for (int j = 0; j < 16; j++) {
+        const uint32_t hj = (uint32_t)__builtin_amdgcn_readlane((int)h, j);
+        if (ins && j < (int)lane && hj == h) d = lane - (uint32_t)j;
+    }
+    if ((int)lane >= first && (int)lane < total) prevdist[lane] = (uint16_t)d;
+}
+
+// the bucket's byte offset (ZA_CH_OFFS of za_hash_x<TABLE>) from p = w0 * ZA_K1, the product all three hashes start with:
+// tables built together multiply a position's first dword once
+template <int TABLE> __device__ __forceinline__ uint32_t za_ch_offs_p(uint32_t p, uint32_t w1, uint32_t w2)
+{
+    if (TABLE == ZA_TABLE_A) return ZA_CH_OFFS(p ^ ((w1 & 0xFFu) * ZA_K2));
+    if (TABLE == ZA_TABLE_B) return ZA_CH_OFFS(p << 8);                          // w0 * (ZA_K1 << 8)
+    const uint32_t x = p ^ (w1 * ZA_K2);
+    return ZA_CH_OFFS(((x ^ (x >> 15)) * ZA_K2) ^ (w2 * ZA_K3));
+}
+
+// TWO link tables (T1 < T2) from one staging of the input: the stream's bytes are loaded once, pass through the ring once, and
+// a hashing lane takes its ring dwords once for both tables' buckets.  Everything behind the hash is per table, exactly as in
+// za_k_chains: the returning atomic maximum into the table's own 64 KiB, the order check with its fallback, the links and their
+// 16-byte stores into the table's own row.  EIGHT wavefronts, one workgroup per CU (2 x 64 KiB of tables + 30 KiB), one barrier per
+// tick.  Hashing is the small part of a tick (za_k_chains' hashing waves idle half the time); what a tick lasts is the chain of
+// LDS round trips in the wave with the atomics and in the wave with the links.  So: waves 0 / 1 hash half of group t each for
+// both tables (wave 0 the second half, behind its staging of group t + 1); waves 2 / 3 read the offsets of group t - 1 and issue
+// the atomics of group t - 2 into table T1 / T2 -- the reads of one group travel under the atomics of the group in front, one
+// round trip less per tick; waves 4-7 turn what came back for half of group t - 3 into links and store those of group t - 4
+// (4 / 5 the first half of T1's / T2's, 6 / 7 the second).  Per table nothing differs from the single kernel but where a row's groups start: at the lower of the two
+// tables' first positions, rounded down to 64 (a carried unit starts HB - 1 positions early, HB being the table's own).
+template <int T1, int T2>
+__global__ __launch_bounds__(512) void za_k_chains2(const uint8_t *__restrict__ in, const ZaUnit *__restrict__ units,
+                                                    const uint32_t *__restrict__ run_start,
+                                                    uint16_t *__restrict__ prev_ws1, uint16_t *__restrict__ prev_ws2,
+                                                    uint32_t *__restrict__ cost_ws = nullptr)    // (with table A) the units' "has a long match" words are cleared for the search
+{
+    static_assert(T1 < T2, "tables in order");
+    __shared__ __attribute__((aligned(16))) uint32_t head[2 << ZA_HASH_BITS];                // T1's table, then T2's
+    __shared__ __attribute__((aligned(16))) uint32_t ring[(2 * ZA_CH_CHUNK + 16) / 4];
+    __shared__ __attribute__((aligned(16))) uint16_t hbuf[2][2][ZA_CH_CHUNK];                // [table][group & 1]
+    __shared__ __attribute__((aligned(16))) uint32_t obuf[2][2][ZA_CH_CHUNK];
+    __shared__ __attribute__((aligned(16))) uint16_t lbuf[2][ZA_CH_CHUNK];                   // [table]: the links of a group on their way out
+    constexpr int HB1 = ZaTableBytes<T1>::value, HB2 = ZaTableBytes<T2>::value;
+    constexpr bool WIDE = T2 == ZA_TABLE_C;                       // a context beyond two dwords: four ring dwords per lane
+    const uint32_t lane = (uint32_t)za_lane();
+    const uint32_t role = threadIdx.x >> 6;
+    const uint32_t ti = role & 1u;                                // (waves 2-7) my table: 0 = T1, 1 = T2
+    const uint32_t u0 = run_start[blockIdx.x], u1 = run_start[blockIdx.x + 1];
+    uint32_t goff = 0;                                // positions of the run in front of the current unit
+    uint32_t n_prev = 0;
+#pragma unroll 1
+    for (uint32_t ui = u0; ui < u1; ui++) {
+        const ZaUnit u = units[ui];
+        const int n = (int)u.in_len, dict_len = (int)u.dict_len;
+        if (T1 == ZA_TABLE_A && cost_ws && threadIdx.x == 0) cost_ws[(size_t)ui * ZA_DP_COSTS + 258] = 0u;
+        const uint8_t *row = in + u.in_off - dict_len;
+        uint16_t *prevdist = (ti ? prev_ws2 : prev_ws1) + (size_t)ui * ZA_PREV_STRIDE;      // (waves 2-7) my table's row
+#ifdef ZA_ABL_NO_CARRY
+        const bool carry = false;
+#else
+        const bool carry = ui > u0 && (u.flags & ZA_FLAG_CARRY) != 0u;
+#endif
+        if (carry) goff += n_prev;
+        else {
+            goff = 0;                                 // fresh tables, both
+            for (uint32_t i = threadIdx.x * 4u; i < (2u << ZA_HASH_BITS); i += 2048u) *(uint4 *)&head[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        __syncthreads();                                       // (the tables; and all waves are through with the unit in front)
+        n_prev = (uint32_t)n;
+        const int total = dict_len + n;
+        const int first1 = carry ? dict_len - (HB1 - 1) : 0, first2 = carry ? dict_len - (HB2 - 1) : 0;   // the late inserts are per table
+        const int first = ti ? first2 : first1;
+        const uint32_t abase = goff + (uint32_t)(2 * ZA_WIN - dict_len) + 1u;
+        if (total < 16) {                           // (uniform) no 16-byte load fits: each table's atomics wave on its own
+            if (role == 2u) za_ch_short_row<T1>(row, lane, first1, total, prevdist);
+            else if (role == 3u) za_ch_short_row<T2>(row, lane, first2, total, prevdist);
+            continue;
+        }
+        const int iclamp_hi = total - (ti ? HB2 : HB1);        // (waves 2-7) my table's last row index with a whole context
+        const int t0 = (first1 < first2 ? first1 : first2) & ~63;
+        const int ngroups = (total - t0 + ZA_CH_CHUNK - 1) / ZA_CH_CHUNK;
+        const int last16 = total - 16;
+        auto fetch = [&](int c, za_v4u32 &dst) {
+            int at = t0 + c * ZA_CH_CHUNK + 16 * (int)lane;
+            at = at > last16 ? last16 : at;
+            za_issue_load16(dst, row + at);
+        };
+        auto stage = [&](int c, uint4 v) {                      // chunk c into its half of the ring (as in za_k_chains)
+            const int cbase = t0 + c * ZA_CH_CHUNK;
+            if (cbase + ZA_CH_CHUNK > total) {
+                const int at = cbase + 16 * (int)lane;
+                const int delta = at > last16 ? at - last16 : 0;
+                const uint32_t w[8] = {v.x, v.y, v.z, v.w, 0u, 0u, 0u, 0u};
+                uint32_t r[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    uint32_t lo = 0, hi = 0;
+#pragma unroll
+                    for (int j = 0; j < 8; j++) { lo = (i + (delta >> 2)) == j ? w[j] : lo; hi = (i + (delta >> 2) + 1) == j ? w[j] : hi; }
+                    r[i] = delta >= 16 ? 0u : __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)delta & 3u);
+                }
+                v = make_uint4(r[0], r[1], r[2], r[3]);
+            }
+            *(uint4 *)(ring + (c & 1) * (ZA_CH_CHUNK / 4) + 4 * lane) = v;
+            if ((c & 1) == 0 && lane == 0) *(uint4 *)(ring + 2 * ZA_CH_CHUNK / 4) = v;
+        };
+        // a quarter of a group's positions (steps g0 .. g0 + 3) hashed for both tables: a lane takes four consecutive positions
+        // out of one set of aligned dwords and leaves their bucket offsets as one 8-byte store per table.  The last quarter reaches
+        // into the head of chunk k + 1.
+        auto hash_quarter = [&](int k, int g0) {
+            const uint32_t *w = ring + (k & 1) * (ZA_CH_CHUNK / 4) + 16 * g0 + lane;     // dword of position 64 g0 + 4 lane
+            const uint32_t d0 = w[0], d1 = w[1];
+            uint32_t d2 = 0u, d3 = 0u;
+            if constexpr (WIDE) { d2 = w[2]; d3 = w[3]; }
+            uint32_t o1[4], o2[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint32_t w0 = q ? __builtin_amdgcn_alignbyte(d1, d0, q) : d0;
+                uint32_t w1, w2 = 0u;
+                if constexpr (WIDE) { w1 = q ? __builtin_amdgcn_alignbyte(d2, d1, q) : d1; w2 = q ? __builtin_amdgcn_alignbyte(d3, d2, q) : d2; }
+                else w1 = d1 >> (8 * q);
+                const uint32_t p = w0 * ZA_K1;
+                o1[q] = za_ch_offs_p<T1>(p, w1, w2);
+                o2[q] = za_ch_offs_p<T2>(p, w1, w2);
+            }
+            const int at = 64 * g0 + 4 * (int)lane;
+            *(uint2 *)(&hbuf[0][k & 1][at]) = make_uint2(o1[0] | (o1[1] << 16), o1[2] | (o1[3] << 16));
+            *(uint2 *)(&hbuf[1][k & 1][at]) = make_uint2(o2[0] | (o2[1] << 16), o2[2] | (o2[3] << 16));
+        };
+        auto group_inner = [&](int k) -> bool {                 // (uniform) group k lies wholly inside my table's part of the row
+            const int tbase = t0 + k * ZA_CH_CHUNK;
+            return tbase >= first && tbase + ZA_CH_CHUNK - 1 <= iclamp_hi;
+        };
+        // waves 2 / 3: my table's atomics.  The bucket offsets of a group are read one tick before its atomics go out (load_offs:
+        // the reads of the next group travel while this group's atomics are issued), then the atomics back to back and the order
+        // check, as in za_k_chains' inserting wave
+        auto load_offs = [&](const uint16_t *hb, uint32_t (&hh)[ZA_CH_GROUP]) {
+#pragma unroll
+            for (int g = 0; g < ZA_CH_GROUP; g++) hh[g] = hb[64 * g + lane];
+        };
+        auto insert_as = [&](auto inner_tag, int tbase, uint32_t *hd, uint32_t (&hh)[ZA_CH_GROUP], uint32_t *ob) {
+            constexpr bool inner = decltype(inner_tag)::value;
+            const uint32_t li = (uint32_t)tbase + lane;
+            uint32_t old[ZA_CH_GROUP];
+            const uint32_t A0 = abase + li;
+#pragma unroll
+            for (int g = 0; g < ZA_CH_GROUP; g++) {
+                const int i = (int)li + 64 * g;
+                const bool ins = inner || (i >= first && i <= iclamp_hi);
+                old[g] = 0u;
+                if (ins) old[g] = atomicMax((uint32_t *)((uint8_t *)hd + hh[g]), A0 + 64u * (uint32_t)g);
+            }
+            uint32_t top = 0;
+#pragma unroll
+            for (int g = 0; g < ZA_CH_GROUP; g++) top |= (A0 + 64u * (uint32_t)g - old[g] - 1u);
+            if (__builtin_expect(ZA_CH_FORCE_FIX_ON || __ballot((int)top < 0) != 0ull, 0)) {
+#pragma unroll 1
+                for (int g = 0; g < ZA_CH_GROUP; g++) {
+                    const int i = (int)li + 64 * g;
+                    const bool ins = inner || (i >= first && i <= iclamp_hi);
+                    const uint32_t A = A0 + 64u * (uint32_t)g;
+                    uint32_t hg = hh[0], og = old[0];
+#pragma unroll
+                    for (int q = 1; q < ZA_CH_GROUP; q++) { hg = g == q ? hh[q] : hg; og = g == q ? old[q] : og; }
+                    const uint32_t ofix = za_chains_fix(hg >> 2, A, og, ins);
+#pragma unroll
+                    for (int q = 0; q < ZA_CH_GROUP; q++) old[q] = g == q ? ofix : old[q];
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < ZA_CH_GROUP; g++) ob[64 * g + lane] = old[g];
+        };
+        // waves 4-7: my table's links of half a group (za_k_chains' storing wave on eight steps), in two ticks so that neither waits
+        // for the other's LDS round trip: make_links collects a half's links in lbuf (a half that does not lie wholly inside the
+        // table's part of the row stores its links lane by lane at once), send_links takes them out 16 bytes per lane a tick later
+        auto half_inner = [&](int tbase) -> bool { return tbase >= first && tbase + ZA_CH_CHUNK / 2 - 1 <= iclamp_hi; };     // (uniform)
+        auto send_links = [&](int k, int half) {
+            const int tbase = t0 + k * ZA_CH_CHUNK + half * (ZA_CH_CHUNK / 2);
+            if (half_inner(tbase)) *(uint4 *)(prevdist + tbase + 8 * (int)lane) = *(const uint4 *)&lbuf[ti][half * (ZA_CH_CHUNK / 2) + 8 * lane];
+        };
+        auto make_links = [&](int k, int half, uint32_t *obk) {
+            constexpr int HSTEPS = ZA_CH_GROUP / 2;
+            const int tbase = t0 + k * ZA_CH_CHUNK + half * (ZA_CH_CHUNK / 2);
+            uint32_t *ob = obk + half * (ZA_CH_CHUNK / 2);
+            const uint32_t A0 = abase + (uint32_t)tbase + lane;
+            uint32_t dd[HSTEPS];
+#pragma unroll
+            for (int g = 0; g < HSTEPS; g++) dd[g] = A0 + 64u * (uint32_t)g - ob[64 * g + lane];
+            if (half_inner(tbase)) {
+                uint16_t *lb = &lbuf[ti][half * (ZA_CH_CHUNK / 2)];
+#pragma unroll
+                for (int g = 0; g < HSTEPS; g++) lb[64 * g + lane] = (uint16_t)(dd[g] <= (uint32_t)ZA_WIN ? dd[g] : 0u);
+            } else {
+#pragma unroll
+                for (int g = 0; g < HSTEPS; g++) {
+                    const int i = tbase + (int)lane + 64 * g;
+                    if (i >= first && i < total) prevdist[i] = (uint16_t)((i <= iclamp_hi && dd[g] <= (uint32_t)ZA_WIN) ? dd[g] : 0u);
+                }
+            }
+        };
+        auto wg_barrier = [&] {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        };
+        // Ticks t = 0 .. ngroups + 3, one barrier behind each (and one behind wave 0's prologue): group t is hashed, the offsets of
+        // group t - 1 are read, the atomics of group t - 2 go out, the links of group t - 3 are made, those of group t - 4 stored.
+        // Wave 0 asks for the bytes four groups ahead, as in za_k_chains.
+        const int tlast = ngroups + 3;
+        if (role == 0u) {
+            za_v4u32 p0 = {0u, 0u, 0u, 0u}, p1 = p0, p2 = p0, p3 = p0;
+            fetch(0, p0);
+            za_wait_loads<0>(p0, p1, p2, p3);
+            stage(0, make_uint4(p0.x, p0.y, p0.z, p0.w));
+            fetch(1, p1); fetch(2, p2); fetch(3, p3); fetch(4, p0);
+            wg_barrier();
+            auto tick = [&](int t, za_v4u32 &pend) {
+                if (t < ngroups) {
+                    za_wait_loads<3>(p0, p1, p2, p3);
+                    stage(t + 1, make_uint4(pend.x, pend.y, pend.z, pend.w));
+                    fetch(t + 5, pend);
+                    hash_quarter(t, 2 * ZA_CH_GROUP / 4);
+                    hash_quarter(t, 3 * ZA_CH_GROUP / 4);
+                }
+                wg_barrier();
+            };
+#pragma unroll 1
+            for (int t = 0; t <= tlast; t += 4) {
+                tick(t, p1);
+                if (t + 1 > tlast) break;
+                tick(t + 1, p2);
+                if (t + 2 > tlast) break;
+                tick(t + 2, p3);
+                if (t + 3 > tlast) break;
+                tick(t + 3, p0);
+            }
+            za_wait_loads<0>(p0, p1, p2, p3);
+        } else if (role == 1u) {
+            wg_barrier();
+#pragma unroll 1
+            for (int t = 0; t <= tlast; t++) {
+                if (t < ngroups) { hash_quarter(t, 0); hash_quarter(t, ZA_CH_GROUP / 4); }
+                wg_barrier();
+            }
+        } else if (role < 4u) {
+            uint32_t *hd = head + ti * (1u << ZA_HASH_BITS);
+            uint32_t ha[ZA_CH_GROUP], hn[ZA_CH_GROUP];                 // two sets of offsets in turn: the loop is unrolled twice, no set is copied
+#pragma unroll
+            for (int g = 0; g < ZA_CH_GROUP; g++) ha[g] = hn[g] = 0u;
+            auto tick = [&](int t, uint32_t (&cur)[ZA_CH_GROUP], uint32_t (&nxt)[ZA_CH_GROUP]) {    // cur: group t - 2's offsets; nxt: takes group t - 1's
+                if (t >= 1 && t - 1 < ngroups) load_offs(hbuf[ti][(t - 1) & 1], nxt);
+                if (t >= 2 && t - 2 < ngroups) {
+                    const int k = t - 2, tbase = t0 + k * ZA_CH_CHUNK;
+                    if (group_inner(k)) insert_as(std::true_type{}, tbase, hd, cur, obuf[ti][k & 1]);
+                    else insert_as(std::false_type{}, tbase, hd, cur, obuf[ti][k & 1]);
+                }
+                wg_barrier();
+            };
+            wg_barrier();
+#pragma unroll 1
+            for (int t = 0; t <= tlast; t += 2) {
+                tick(t, ha, hn);
+                if (t + 1 > tlast) break;
+                tick(t + 1, hn, ha);
+            }
+        } else {
+            const int half = (int)(role - 4u) >> 1;
+            wg_barrier();
+#pragma unroll 1
+            for (int t = 0; t <= tlast; t++) {
+                if (t >= 4) send_links(t - 4, half);                      // (first: its read is under way while the next half's entries are read)
+                if (t >= 3 && t - 3 < ngroups) make_links(t - 3, half, obuf[ti][(t - 3) & 1]);
+                wg_barrier();
+            }
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -84,7 +84,7 @@ static_assert(ZNGAMD_UNIT_MAX == ZA_MAX_UNIT && ZNGAMD_SEG == ZA_SEG, "constants
 
 // the level table (the same numbers as the oracle's): chain steps over table A, nice, cap, table C, dynamic programme,
 // too_far3, too_far4, shortest match (6 under Z_FILTERED, set per call), fixed-code costs (Z_FIXED, set per call).  Within 2 % of zlib 1.2.11 at the same level on held-out real files, at least zlib on the synthetic corpora.
-#define ZA_CH_STREAMS_PER_CU (ZA_HASH_BITS >= 14 ? 2u : 3u)     // what the chain kernel's LDS (table + 14 KiB) lets a CU hold
+#define ZA_CH_STREAMS_PER_CU (ZA_HASH_BITS >= 14 ? 2u : 3u)     // what the single-table chain kernel's LDS (table + 14 KiB) lets a CU hold (the two-table kernel: one workgroup, as the search)
 #define ZA_WS_SHARE_DIV 4u          // ZA_WS_SHARE = 1 / 4: the most of the free device memory that the deflate workspace of a call without ZNGAMD_CHUNK_UNITS takes
 static const ZaLevel ZA_LEVELS[10] = {
     {0, 0, ZA_WIN, 0, 0, 0, 0, 0, 3, 0},
@@ -798,9 +798,28 @@ static int deflate_units_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_len
                                    d_unit_crc + c0, c->d_crc_table, c->d_x8k);
         } else if (search) {
             { ProfScope ps(c, ZNGAMD_K_CHAINS);
-              hipLaunchKernelGGL(za_k_chains<ZA_TABLE_A>, dim3(nruns), dim3(256), 0, c->stream, d_in, du, d_runs, c->prev_p, L.dp ? c->dpcost.p : (uint32_t *)nullptr);
-              hipLaunchKernelGGL(za_k_chains<ZA_TABLE_B>, dim3(nruns), dim3(256), 0, c->stream, d_in, du, d_runs, c->linkb_p, (uint32_t *)nullptr);
-              if (L.use_c) hipLaunchKernelGGL(za_k_chains<ZA_TABLE_C>, dim3(nruns), dim3(256), 0, c->stream, d_in, du, d_runs, c->linkc_p, (uint32_t *)nullptr); }
+              uint32_t *const d_clear = L.dp ? c->dpcost.p : (uint32_t *)nullptr;       // (with table A) the units' long-match words
+              // Two of the tables come from one launch (za_k_chains2; ZA_CH_PAIR, za_deflate.hip): with table C (levels 5-9) A on its
+              // own, then B and C together -- measured, that pairing is the faster one --, without it A and B together.
+#define ZA_LAUNCH_CH1(T, dst, clr) hipLaunchKernelGGL(za_k_chains<T>, dim3(nruns), dim3(256), 0, c->stream, d_in, du, d_runs, dst, clr)
+#define ZA_LAUNCH_CH2(T1, T2, dst1, dst2, clr) hipLaunchKernelGGL((za_k_chains2<T1, T2>), dim3(nruns), dim3(512), 0, c->stream, d_in, du, d_runs, dst1, dst2, clr)
+              uint32_t *const no_clear = nullptr;
+#if ZA_CH_PAIR == 0
+              ZA_LAUNCH_CH1(ZA_TABLE_A, c->prev_p, d_clear);
+              ZA_LAUNCH_CH1(ZA_TABLE_B, c->linkb_p, no_clear);
+              if (L.use_c) ZA_LAUNCH_CH1(ZA_TABLE_C, c->linkc_p, no_clear);
+#else
+              if (L.use_c && ZA_CH_PAIR == 1) {
+                  ZA_LAUNCH_CH1(ZA_TABLE_A, c->prev_p, d_clear);
+                  ZA_LAUNCH_CH2(ZA_TABLE_B, ZA_TABLE_C, c->linkb_p, c->linkc_p, no_clear);
+              } else {
+                  ZA_LAUNCH_CH2(ZA_TABLE_A, ZA_TABLE_B, c->prev_p, c->linkb_p, d_clear);
+                  if (L.use_c) ZA_LAUNCH_CH1(ZA_TABLE_C, c->linkc_p, no_clear);
+              }
+#endif
+#undef ZA_LAUNCH_CH1
+#undef ZA_LAUNCH_CH2
+            }
             { ProfScope ps(c, ZNGAMD_K_SEARCH);
 #define ZA_LAUNCH_SEARCH(...) hipLaunchKernelGGL((za_k_search<__VA_ARGS__>), dim3(nruns), dim3(ZA_SEARCH_THREADS), 0, c->stream, d_in, in_len, du, d_runs, \
                                                  c->prev_p, c->linkb_p, L.use_c ? c->linkc_p : c->linkb_p, c->best.p, c->dpcost.p, L)
