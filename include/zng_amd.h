@@ -1065,6 +1065,146 @@ int zngamd_dedup_keys_dev(zngamd_ctx *ctx, const zngamd_bgzf_key_row *d_keys, ui
 int zngamd_dedup_keys(zngamd_ctx *ctx, const zngamd_bgzf_key_row *keys, uint64_t n, uint64_t *first, uint32_t *count,
                       zngamd_dedup_totals *totals);
 
+/* ---- BGZF overlap (zlib_ng_amd/bgzf.py: overlap_records).  The one preprocessing step that needs both mates
+ * of a pair at once: where the two reads of a pair lie over each other, and with that the adapter read-through cut off, bases
+ * corrected and the pair merged into one read -- fastp's overlap analysis (-c, -m), bbmerge, PEAR, FLASH, vsearch
+ * --fastq_mergepairs.  Interleaved input only: one record is one pair.  All integers, all bytes exact.
+ * Record model.  The record model of zngamd_bgzf_grep_records applies (record_lines k, first_byte, _FINAL, the open tail, the cover
+ * contract).
+ *   - record_lines k is even, 2 <= k <= 64, m = k / 2.
+ *   - Mate 1 is lines [0, m) of the record.  Mate 2 is lines [m, k).
+ *   - seq_line s and qual_line q (-1: none) lie in [0, m), q != s.  They name the same line of both mates.
+ *   - Bodies are the lines without the delimiter.
+ *   - Under _FINAL, a line the short last record lacks is an empty body.
+ * Notation.
+ *   - a is mate 1's sequence body (n1 bytes), qa its quality body.
+ *   - y, qy are mate 2's bodies (n2 bytes).
+ *   - b[j] = comp(y[n2 - 1 - j]) and qb[j] = qy[n2 - 1 - j].
+ *   - comp is za_key_comp's map (the one behind ZNGAMD_BGZF_KEY_CANONICAL): A<->T and C<->G in either case, U -> A, u -> a, every
+ *     other byte itself.
+ *   - Qx = qx - quality_base, signed.  With q = -1 every Q counts as 0.
+ * 1. Search.  For every offset o in [-(n2 - 1), n1 - 1], b[j] lies under a[o + j].
+ *   - The overlap is i in [max(0, o), min(n1, o + n2)).
+ *   - L(o) is its length.
+ *   - d(o) is the number of i with a[i] != b[i - o].  Bytes are compared as they are, so N equals N.
+ *   - o is acceptable when L >= min_overlap and d <= min(max_mismatch, L * max_percent / 100).
+ *   - The acceptable offset that is first in this order wins:
+ *       1. larger L;
+ *       2. then smaller d;
+ *       3. then smaller |o|;
+ *       4. then o >= 0 before o < 0.
+ *   - No two offsets share all four values, so the winner is unique.  This is fastp's "longest acceptable overlap first", made total.
+ *   - Limits: min_overlap 1 .. 1024, max_mismatch 0 .. 1024, max_percent 0 .. 100.
+ *   - A pair with n1 or n2 above ZNGAMD_BGZF_OVERLAP_MAX_READ (1024) is not searched: verdict _TOO_LONG.
+ *   - Reason for the limit: it bounds a wave's LDS stage and the worst case.  Illumina's longest mate is 300.
+ *   - With an overlap found, insert = o + n2 (>= 1).
+ * 2. Correction (conf.flags & _OVERLAP_CORRECT; needs q >= 0, else ZNGAMD_E_ARG).  At every overlap position with a[i] != b[i - o]:
+ *   - if Qa >= q_high and Qb <= q_low, mate 2 takes mate 1's byte and quality there (y gets comp(a[i]));
+ *   - else if Qb >= q_high and Qa <= q_low, mate 1 takes b's byte and quality.
+ *   - q_high and q_low are 0 .. 93; fastp's are 30 and 14.
+ *   - `corrected` counts the positions.  It is counted whether or not the pair is then merged.
+ * 3. Cut (_OVERLAP_CUT), for a pair with an overlap found.
+ *   - Mate 1 keeps a[0, min(n1, insert)).
+ *   - Mate 2 keeps y[0, min(n2, n2 + o)).
+ *   - What falls off is adapter read-through.
+ *   - It is summed in adapter_trimmed (bases) and adapter_pairs, whether or not the pair is then merged.
+ * 4. Merge (_OVERLAP_MERGE), for a pair with an overlap found.  The merged read has `insert` positions c.
+ *   - Where only one mate covers c, it gives base and quality.
+ *   - Where both cover c, the mate with the higher Q gives base and quality.  This uses the Q of the source text as it stood before
+ *     step 2.  Mate 1 wins on ties, so always with q = -1.
+ *   - Correction therefore changes no merged byte; it only counts.
+ *   - Written: mate 1's m lines, with lines s and q carrying the merged bodies, every other line whole, every delimiter mate 1's
+ *     source has.  Nothing of mate 2's other lines is written.
+ * Verdicts (uint8): _NONE 0, _FOUND 1 (overlap, _MERGE off), _MERGED 2, _TOO_LONG 3.
+ * Classes.
+ *   - Class 0 is the merged records (m lines each).
+ *   - Class 1 is every other pair (k lines each, as step 2 and step 3 left them; a _TOO_LONG pair whole).
+ *   - With ZNGAMD_BGZF_CLASSIFY_GROUP, class 0 is gathered: d_rows holds a row per merged pair in record order (src_off: where the
+ *     record starts in the scratch; number = record_base + r; len: its bytes as written; reserved: the class), d_out the bytes.
+ *   - Class 1 is gathered behind it only with _OVERLAP_KEEP_UNMERGED.  This is exactly how _TRIM_KEEP_SHORT works.
+ *   - Without _GROUP only d_overlap[0 .. seen), one row per pair in record order, and the totals leave the kernels.
+ * Faults.
+ *   - bad = 1: the first byte of line 0 or of line m is not first_byte (a line the record lacks has no first byte).
+ *   - bad = 3: a mate's sequence and quality bodies differ in length.
+ *   - The smaller record wins.  A record with both faults reports 1.  With bad set, nothing is written; the counts are valid except
+ *     that a pair whose bodies differ is not searched.  This is trim's contract.
+ * flags: _FINAL and ZNGAMD_BGZF_CLASSIFY_GROUP; anything else is ZNGAMD_E_ARG.  ZNGAMD_BUF_ERROR: overlap_cap < seen or, with _GROUP,
+ * rows_cap or out_cap too small; nothing is written, the totals are valid.  Hostile arguments -- conf NULL or a field out of range, k
+ * odd, s or q not below m, q == s, _OVERLAP_CORRECT with q = -1, a reserved word set, flags, totals NULL -- are ZNGAMD_E_ARG before
+ * the context is touched.  Device memory beside the tiles: 8 bytes per line and 22 bytes per record of the text, and 16 bytes per 256
+ * records. */
+#define ZNGAMD_BGZF_OVERLAP_NONE     0u
+#define ZNGAMD_BGZF_OVERLAP_FOUND    1u
+#define ZNGAMD_BGZF_OVERLAP_MERGED   2u
+#define ZNGAMD_BGZF_OVERLAP_TOO_LONG 3u
+#define ZNGAMD_BGZF_OVERLAP_MERGE         1u   /* conf.flags: step 4 */
+#define ZNGAMD_BGZF_OVERLAP_CORRECT       2u   /*             step 2 */
+#define ZNGAMD_BGZF_OVERLAP_CUT           4u   /*             step 3 */
+#define ZNGAMD_BGZF_OVERLAP_KEEP_UNMERGED 8u   /*             class 1 is gathered behind class 0, not only counted */
+#define ZNGAMD_BGZF_OVERLAP_MAX_READ    1024u
+#define ZNGAMD_BGZF_OVERLAP_MAX_QUALITY 93u
+typedef struct {
+    uint32_t record_lines;  /* k, even, 2 .. 64 */
+    int32_t  seq_line;      /* s, below k / 2 */
+    int32_t  qual_line;     /* q; -1: none */
+    int32_t  first_byte;    /* 0 .. 255; -1: no check */
+    uint32_t quality_base;  /* 0 .. 255; 33 for Sanger / Illumina 1.8+ */
+    uint32_t min_overlap;   /* step 1: 1 .. 1024 */
+    uint32_t max_mismatch;  /* 0 .. 1024 */
+    uint32_t max_percent;   /* 0 .. 100 */
+    uint32_t q_high;        /* step 2: 0 .. 93 */
+    uint32_t q_low;
+    uint32_t flags;         /* ZNGAMD_BGZF_OVERLAP_MERGE | _CORRECT | _CUT | _KEEP_UNMERGED */
+    uint32_t reserved[5];   /* 0 */
+} zngamd_bgzf_overlap_conf;                                                                       /* 64 B */
+typedef struct {
+    int32_t  offset;        /* o; 0 without an overlap */
+    uint32_t insert;        /* o + n2; 0: none */
+    uint16_t overlap;       /* L */
+    uint16_t mismatches;    /* d */
+    uint16_t corrected;     /* positions step 2 changed */
+    uint8_t  verdict;       /* ZNGAMD_BGZF_OVERLAP_NONE / _FOUND / _MERGED / _TOO_LONG */
+    uint8_t  steps;         /* bit 0: mate 1 cut, bit 1: mate 2 cut, bit 2: corrected */
+} zngamd_bgzf_overlap_row;                                                                        /* 16 B */
+typedef struct {
+    uint64_t seen;            /* pairs of the text that were decided (the open tail is not one of them) */
+    uint64_t none;            /* of them, per verdict */
+    uint64_t found;
+    uint64_t merged;
+    uint64_t too_long;
+    uint64_t bytes_in;        /* bytes of the records as they lie in the text */
+    uint64_t bytes;           /* bytes of the records as written: class 0 and, with _OVERLAP_KEEP_UNMERGED, class 1 */
+    uint64_t bases_in;        /* sum of n1 + n2 */
+    uint64_t bases_merged;    /* sum of insert over the merged pairs */
+    uint64_t corrected;       /* positions step 2 changed, over all pairs */
+    uint64_t corrected_pairs; /* pairs with at least one */
+    uint64_t adapter_pairs;   /* pairs step 3 cut */
+    uint64_t adapter_trimmed; /* bases step 3 took, over both mates */
+    uint64_t overlap_sum;     /* sum of L over the pairs with an overlap */
+    uint64_t mismatch_sum;    /* sum of d over them */
+    uint64_t tail_off;        /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;      /* bad != 0: the number of the record at fault */
+    uint64_t bad_src;         /*           and where it starts in the scratch */
+    uint32_t covered;         /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;     /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;             /* 0; 1: line 0 or line m does not begin with first_byte; 3: a mate's two bodies differ in length */
+    uint32_t reserved;
+} zngamd_bgzf_overlap_totals;                                                                     /* 160 B */
+int zngamd_bgzf_overlap_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                    uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_overlap_conf *conf,
+                                    uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                                    zngamd_bgzf_overlap_row *d_overlap, uint64_t overlap_cap, zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap,
+                                    void *d_out, uint64_t out_cap, zngamd_bgzf_overlap_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; status, the overlap rows and, with _GROUP, the rows and the written
+ * records come back.  With alloc (overlap = rows = out = NULL, the capacities 0) the caller's memory is asked for once the sizes are
+ * known, in the order overlap rows (seen * 16 bytes), rows ((merged [+ the others]) * 24 bytes), bytes -- the last two with _GROUP
+ * and a record to write only; NULL from it: ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_overlap_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                                uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_overlap_conf *conf,
+                                uint64_t record_base, int32_t *status, zngamd_bgzf_overlap_row *overlap, uint64_t overlap_cap,
+                                zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out, uint64_t out_cap, zngamd_alloc_fn alloc,
+                                void *user, zngamd_bgzf_overlap_totals *totals);
+
 /* ---- BGZF by region (zlib_ng_amd/bgzf.py: TabixIndex, fetch).  Both calls read the FIELDS of tab-separated
  * lines by the rules of tabix.  conf: format (0 generic, 2 VCF, | 0x10000: the coordinates are zero-based, half-open; 1, the SAM
  * preset, is ZNGAMD_E_ARG), the columns of the name, the start and the end (from 1; col_end 0: none), the byte that opens a comment

@@ -16,6 +16,7 @@
 #include "za_trim.hip"
 #include "za_qc.hip"
 #include "za_dedup.hip"
+#include "za_overlap.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
 #include "za_batch.hip"
@@ -71,6 +72,13 @@ static_assert(sizeof(zngamd_bgzf_key_totals) == sizeof(ZaKeyTotals) && sizeof(Za
               sizeof(zngamd_bgzf_key_conf) == 64 && ZNGAMD_BGZF_KEY_IGNORE_CASE == ZA_KEY_IGNORE_CASE && ZNGAMD_BGZF_KEY_CANONICAL == ZA_KEY_CANONICAL &&
               ZNGAMD_BGZF_KEY_SEED0 == ZA_KEY_SEED0 && ZNGAMD_BGZF_KEY_SEED1 == ZA_KEY_SEED1 && sizeof(zngamd_dedup_totals) == sizeof(ZaDedupTotals) &&
               sizeof(ZaDedupTotals) == 48, "bgzf dedup layout");
+static_assert(sizeof(zngamd_bgzf_overlap_totals) == sizeof(ZaOvlTotals) && sizeof(ZaOvlTotals) == 160 && offsetof(ZaOvlTotals, covered) == offsetof(zngamd_bgzf_overlap_totals, covered) &&
+              offsetof(ZaOvlTotals, mismatch_sum) == offsetof(zngamd_bgzf_overlap_totals, mismatch_sum) && offsetof(ZaOvlTotals, mismatch_sum) == (ZA_OVL_SUMS - 1u) * 8u &&
+              sizeof(zngamd_bgzf_overlap_row) == sizeof(ZaOvlRow) && sizeof(ZaOvlRow) == 16 && sizeof(zngamd_bgzf_overlap_conf) == 64 &&
+              ZNGAMD_BGZF_OVERLAP_NONE == ZA_OVL_NONE && ZNGAMD_BGZF_OVERLAP_FOUND == ZA_OVL_FOUND && ZNGAMD_BGZF_OVERLAP_MERGED == ZA_OVL_MERGED &&
+              ZNGAMD_BGZF_OVERLAP_TOO_LONG == ZA_OVL_TOO_LONG && ZNGAMD_BGZF_OVERLAP_MERGE == ZA_OVL_MERGE && ZNGAMD_BGZF_OVERLAP_CORRECT == ZA_OVL_CORRECT &&
+              ZNGAMD_BGZF_OVERLAP_CUT == ZA_OVL_CUT && ZNGAMD_BGZF_OVERLAP_KEEP_UNMERGED == ZA_OVL_KEEP_UNMERGED && ZNGAMD_BGZF_OVERLAP_MAX_READ == ZA_OVL_MAX_READ,
+              "bgzf overlap layout");
 static_assert(sizeof(zngamd_tabix_conf) == sizeof(ZaTbxConf) && sizeof(zngamd_tabix_name) == sizeof(ZaTbxName) && sizeof(zngamd_tabix_bin) == sizeof(ZaTbxBin) &&
               sizeof(zngamd_tabix_win) == sizeof(ZaTbxWin) && sizeof(zngamd_tabix_region) == sizeof(ZaTbxRegion) && sizeof(zngamd_tabix_span) == sizeof(ZaTbxSpan) &&
               sizeof(zngamd_tabix_row) == sizeof(ZaTbxRow) && sizeof(zngamd_bgzf_tabix_totals) == 104 && sizeof(ZaTbxState) <= 64 &&
@@ -195,6 +203,9 @@ struct zngamd_ctx {
     // records keyed and keys resolved (za_dedup.hip, section 5f.7; line starts are gr_start): the key pass's totals and first fault; the host
     // forms' rows, table, first[] and count[]
     DevBuf<unsigned long long> dd_tot, dd_first; DevBuf<ZaKeyRow> dd_row; DevBuf<uint8_t> dd_tab; DevBuf<uint32_t> dd_count;
+    // pairs laid over each other (za_overlap.hip, section 5f.8; line starts, lengths, table, labels and the totals' words are gr_start, cl_len,
+    // cl_tab, pt_lab and tr_tot): the overlap rows
+    DevBuf<ZaOvlRow> ov_row;
     std::vector<uint8_t> gp_host;                // the parameter block of the last grep call as it was uploaded
     uint8_t *h_stage = nullptr; size_t h_stage_cap = 0;      // pinned host staging for device-to-host results (grow-only)
     uint8_t *h_up = nullptr; size_t h_up_cap = 0;            // pinned host staging for small uploads (r06): the input of a small call, the unit / run tables
@@ -348,7 +359,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->gp_par.release(); c->gp_bits.release(); c->gp_tiles.release(); c->gp_carry.release(); c->gp_rows.release(); c->gp_lens.release();
     c->gr_start.release(); c->gr_sel.release(); c->gr_len.release(); c->gr_hit.release();
     c->cl_min.release(); c->cl_row.release(); c->cl_len.release(); c->cl_cls.release(); c->cl_tot.release(); c->cl_tab.release(); c->pt_lab.release(); c->pt_tot.release();
-    c->tr_row.release(); c->tr_drop.release(); c->tr_tot.release();
+    c->tr_row.release(); c->tr_drop.release(); c->tr_tot.release(); c->ov_row.release();
     c->qc_tot.release(); c->qc_tab.release(); c->qc_row.release();
     c->dd_tot.release(); c->dd_first.release(); c->dd_row.release(); c->dd_tab.release(); c->dd_count.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
@@ -4775,6 +4786,129 @@ try {
     if (count) HIPCHK(c, hipMemcpyAsync(count, c->dd_count.p, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- pairs laid over each other (za_overlap.hip)
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool overlap_args_ok(int delim, uint32_t flags, const zngamd_bgzf_overlap_conf *cf, const zngamd_bgzf_overlap_totals *totals)
+{
+    if (!totals || !cf || (flags & ~(ZNGAMD_BGZF_GREP_FINAL | ZNGAMD_BGZF_CLASSIFY_GROUP)) || delim < 0 || delim > 255) return false;
+    if (!grep_records_ok(cf->record_lines, -1, cf->first_byte) || cf->record_lines < 2u || (cf->record_lines & 1u)) return false;
+    const int32_t m = (int32_t)(cf->record_lines / 2u);
+    if (cf->seq_line < 0 || cf->seq_line >= m || cf->qual_line < -1 || cf->qual_line >= m || cf->qual_line == cf->seq_line) return false;
+    if (cf->quality_base > 255u || cf->min_overlap < 1u || cf->min_overlap > ZNGAMD_BGZF_OVERLAP_MAX_READ || cf->max_mismatch > ZNGAMD_BGZF_OVERLAP_MAX_READ ||
+        cf->max_percent > 100u || cf->q_high > ZNGAMD_BGZF_OVERLAP_MAX_QUALITY || cf->q_low > ZNGAMD_BGZF_OVERLAP_MAX_QUALITY) return false;
+    if ((cf->flags & ~(ZNGAMD_BGZF_OVERLAP_MERGE | ZNGAMD_BGZF_OVERLAP_CORRECT | ZNGAMD_BGZF_OVERLAP_CUT | ZNGAMD_BGZF_OVERLAP_KEEP_UNMERGED)) ||
+        ((cf->flags & ZNGAMD_BGZF_OVERLAP_CORRECT) && cf->qual_line < 0)) return false;
+    for (uint32_t r : cf->reserved) if (r) return false;
+    return true;
+}
+
+// the lines pass for the delimiters alone, [the host waits for the line count], lines, eval, hist, with _GROUP the scan, close, [the
+// host waits for the totals], then with _GROUP scatter, offsets and gather, and the overlap rows (own: they stay in ov_row).
+static int bgzf_overlap_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, const zngamd_bgzf_overlap_conf &cf, uint64_t record_base,
+                            zngamd_bgzf_overlap_row *d_overlap, uint64_t overlap_cap, BgzfDest dst, zngamd_bgzf_overlap_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines, ncls = 2u;
+    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+    if (r) return r;
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const bool group = (flags & ZA_CLS_GROUP) != 0, keep = (cf.flags & ZA_OVL_KEEP_UNMERGED) != 0;
+    const uint64_t lines = R.lines, nrec = R.nrec;
+    const uint32_t nwg = (uint32_t)((nrec + ZA_PART_WG_RECORDS - 1u) / ZA_PART_WG_RECORDS);
+    const uint64_t ntab = (uint64_t)ncls * nwg;
+    constexpr size_t TOT_WORDS = sizeof(ZaOvlTotals) / 8u;                               // then the two faults, the scan's sum, the counts, hist's totals
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab)); HIPCHK(c, c->pt_lab.ensure(nrec));
+    HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u)); HIPCHK(c, c->ov_row.ensure(nrec));
+    HIPCHK(c, c->tr_tot.ensure(TOT_WORDS + 3u + 2u * ncls + sizeof(ZaPartTotals) / 8u));
+    const ZaOvlPar P = {k, k / 2u, (uint32_t)cf.seq_line, cf.qual_line, cf.first_byte, cf.quality_base, cf.min_overlap, cf.max_mismatch, cf.max_percent,
+                        (int32_t)cf.q_high, (int32_t)cf.q_low, cf.flags, w.delim};
+    ZaOvlTotals *d_tot = (ZaOvlTotals *)c->tr_tot.p;
+    unsigned long long *d_bad = c->tr_tot.p + TOT_WORDS, *d_sum = d_bad + 2, *d_cnt = d_bad + 3;
+    ZaPartTotals *d_ptot = (ZaPartTotals *)(d_cnt + 2u * ncls);
+    HIPCHK(c, hipMemsetAsync(c->tr_tot.p, 0, (TOT_WORDS + 3u + 2u * ncls) * 8u + sizeof(ZaPartTotals), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 16, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_ovl_eval, dim3((uint32_t)((nrec + ZA_OVL_WG_RECORDS - 1u) / ZA_OVL_WG_RECORDS)), dim3(256), 0, c->stream, w.d_scratch, w.text_end,
+                         c->gr_start.p, lines, nrec, P, c->ov_row.p, c->cl_len.p, c->pt_lab.p, d_tot);
+      hipLaunchKernelGGL(za_k_part_hist, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, c->pt_lab.p, nrec, c->cl_len.p, nrec, ncls, nwg, c->cl_tab.p, d_cnt, d_ptot);
+      if (group) tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
+      hipLaunchKernelGGL(za_k_ovl_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_cnt, d_bad, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (totals->bad) return ZNGAMD_OK;
+    const uint64_t n = group ? totals->merged + (keep ? totals->seen - totals->merged : 0ull) : 0ull, bytes = group ? totals->bytes : 0ull;
+    if (!dst.own && totals->seen > overlap_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
+    r = bgzf_dest_ready(c, dst, n, bytes);
+    if (r) return r;
+    if (n) {
+        HIPCHK(c, c->gp_lens.ensure(n)); HIPCHK(c, c->st_off.ensure(n));
+        uint64_t *d_bytes = (uint64_t *)((uint8_t *)c->d_small + 128);
+        { ProfScope ps(c, ZNGAMD_K_GATHER);
+          hipLaunchKernelGGL(za_k_part_scatter, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, c->pt_lab.p, nrec, c->cl_len.p, c->gr_start.p, nrec, k, ncls, nwg,
+                             c->cl_tab.p, record_base, dst.d_rows, n, c->gp_lens.p);
+          hipLaunchKernelGGL(za_k_offsets, dim3(1), dim3(n <= 64 ? 64 : 1024), 0, c->stream, c->gp_lens.p, (uint32_t)n, 0u, 0ull, c->st_off.p, d_bytes,
+                             (const ZaUnit *)nullptr);
+          hipLaunchKernelGGL(za_k_ovl_gather, dim3((uint32_t)((n + 3u) / 4u)), dim3(256), 0, c->stream, w.d_scratch, c->gr_start.p, lines, record_base, P,
+                             c->ov_row.p, dst.d_rows, c->st_off.p, n, dst.d_out, bytes); }
+        c->bgzf_stats[2] += n;
+        HIPCHK(c, hipGetLastError());
+    }
+    if (!dst.own) HIPCHK(c, hipMemcpyAsync(d_overlap, c->ov_row.p, (size_t)totals->seen * sizeof(ZaOvlRow), hipMemcpyDeviceToDevice, c->stream));
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_overlap_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                    uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_overlap_conf *conf, uint64_t record_base, void *d_scratch,
+                                    uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_overlap_row *d_overlap, uint64_t overlap_cap,
+                                    zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_overlap_totals *totals)
+try {
+    if (!overlap_args_ok(delim, flags, conf, totals)) return ZNGAMD_E_ARG;
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_overlap && overlap_cap) || (!d_rows && rows_cap) ||
+        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    int r = bgzf_overlap_dev(c, w, flags, *conf, record_base, d_overlap, overlap_cap, {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_overlap_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                                uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_overlap_conf *conf, uint64_t record_base, int32_t *status,
+                                zngamd_bgzf_overlap_row *overlap, uint64_t overlap_cap, zngamd_bgzf_grep_row *rows, uint64_t rows_cap, uint8_t *out,
+                                uint64_t out_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_overlap_totals *totals)
+try {
+    if (!overlap_args_ok(delim, flags, conf, totals)) return ZNGAMD_E_ARG;
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!overlap && overlap_cap) || (!rows && rows_cap) || (!out && out_cap) ||
+        (alloc && (overlap || rows || out))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    r = bgzf_overlap_dev(c, w, flags, *conf, record_base, nullptr, 0, {nullptr, 0, nullptr, 0, true}, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t seen = totals->seen;
+    const bool group = (flags & ZNGAMD_BGZF_CLASSIFY_GROUP) != 0;
+    if (!totals->covered || totals->bad || !seen) return ZNGAMD_OK;
+    const uint64_t n = group ? totals->merged + ((conf->flags & ZNGAMD_BGZF_OVERLAP_KEEP_UNMERGED) ? seen - totals->merged : 0ull) : 0ull;
+    if (alloc) overlap = (zngamd_bgzf_overlap_row *)alloc(user, seen * sizeof(zngamd_bgzf_overlap_row));      // the caller's memory is asked for: overlap rows, rows, bytes
+    return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap, alloc ? overlap != nullptr : seen <= overlap_cap, n != 0,
+                           [&] { HIPCHK(c, hipMemcpyAsync(overlap, c->ov_row.p, (size_t)seen * sizeof(ZaOvlRow), hipMemcpyDeviceToHost, c->stream)); return ZNGAMD_OK; });
 } ZA_ABI_GUARD
 
 // ---- fields of a line (za_tabix.hip)

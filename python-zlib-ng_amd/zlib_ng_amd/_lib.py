@@ -89,6 +89,7 @@ SYMBOLS = [
     "zngamd_bgzf_trim_records_dev", "zngamd_bgzf_trim_records",
     "zngamd_bgzf_qc_records_dev", "zngamd_bgzf_qc_records",
     "zngamd_bgzf_key_records_dev", "zngamd_bgzf_key_records", "zngamd_dedup_scratch_bytes", "zngamd_dedup_keys_dev", "zngamd_dedup_keys",
+    "zngamd_bgzf_overlap_records_dev", "zngamd_bgzf_overlap_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
 ]
@@ -220,6 +221,31 @@ class BgzfTrimTotals(C.Structure):             # zngamd_bgzf_trim_totals
 
     @property
     def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is judged)
+        return self.seen
+
+
+BGZF_OVERLAP_NONE, BGZF_OVERLAP_FOUND, BGZF_OVERLAP_MERGED, BGZF_OVERLAP_TOO_LONG = 0, 1, 2, 3      # ZNGAMD_BGZF_OVERLAP_*: an overlap row's verdict
+BGZF_OVERLAP_MERGE, BGZF_OVERLAP_CORRECT, BGZF_OVERLAP_CUT, BGZF_OVERLAP_KEEP_UNMERGED = 1, 2, 4, 8      # conf.flags
+BGZF_OVERLAP_MAX_READ, BGZF_OVERLAP_MAX_QUALITY = 1024, 93
+OVERLAP_ROW_DTYPE = np.dtype([("offset", "<i4"), ("insert", "<u4"), ("overlap", "<u2"), ("mismatches", "<u2"), ("corrected", "<u2"), ("verdict", "u1"),
+                              ("steps", "u1")])      # zngamd_bgzf_overlap_row
+
+
+class BgzfOverlapConf(C.Structure):            # zngamd_bgzf_overlap_conf
+    _fields_ = [("record_lines", C.c_uint32), ("seq_line", C.c_int32), ("qual_line", C.c_int32), ("first_byte", C.c_int32), ("quality_base", C.c_uint32),
+                ("min_overlap", C.c_uint32), ("max_mismatch", C.c_uint32), ("max_percent", C.c_uint32), ("q_high", C.c_uint32), ("q_low", C.c_uint32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class BgzfOverlapTotals(C.Structure):          # zngamd_bgzf_overlap_totals
+    _fields_ = [("seen", C.c_uint64), ("none", C.c_uint64), ("found", C.c_uint64), ("merged", C.c_uint64), ("too_long", C.c_uint64), ("bytes_in", C.c_uint64),
+                ("bytes", C.c_uint64), ("bases_in", C.c_uint64), ("bases_merged", C.c_uint64), ("corrected", C.c_uint64), ("corrected_pairs", C.c_uint64),
+                ("adapter_pairs", C.c_uint64), ("adapter_trimmed", C.c_uint64), ("overlap_sum", C.c_uint64), ("mismatch_sum", C.c_uint64),
+                ("tail_off", C.c_uint64), ("bad_record", C.c_uint64), ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32),
+                ("bad", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every pair is judged)
         return self.seen
 
 
@@ -478,6 +504,11 @@ def load():
             L.zngamd_dedup_scratch_bytes.restype = C.c_uint64
             L.zngamd_dedup_keys_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
             L.zngamd_dedup_keys.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+        if hasattr(L, "zngamd_bgzf_overlap_records"):       # as qc without the tables: overlap rows, rows and bytes with their capacities
+            L.zngamd_bgzf_overlap_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp,
+                                                          C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_overlap_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp, vp,
+                                                      C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, ALLOC_FN, vp, vp]
         if hasattr(L, "zngamd_bgzf_tabix"):
             L.zngamd_bgzf_tabix_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint32, C.c_uint64, vp,
                                                 C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1654,6 +1685,65 @@ class Context:
                                                           len(table), delim, flags, C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status),
                                                           v(d_drop), n_drop, v(d_trim), trim_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
                       (OK, BUF_ERROR))
+        return r, tot
+
+    def bgzf_overlap_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):
+        """zngamd_bgzf_overlap_records: every pair judged by the rule of conf (a BgzfOverlapConf) -> (code, block statuses, totals
+        (BgzfOverlapTotals), overlap rows (OVERLAP_ROW_DTYPE, one per pair in record order), rows (GREP_ROW_DTYPE: the merged pairs, then
+        with BGZF_OVERLAP_KEEP_UNMERGED the others; len: the bytes as written), the records as written in that order); rows and records
+        only with BGZF_CLASSIFY_GROUP in flags; nothing comes back when totals.bad is set.  caps None: the arrays are allocated once the
+        engine knows their sizes; (overlap rows, rows, bytes): buffers of those sizes, and code is BUF_ERROR (nothing written) when the
+        result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfOverlapTotals()
+        group = bool(flags & BGZF_CLASSIFY_GROUP)
+        box = []
+
+        def alloc(_user, nbytes):
+            if not box:
+                arr = np.empty(nbytes // OVERLAP_ROW_DTYPE.itemsize, OVERLAP_ROW_DTYPE)
+            elif len(box) == 1:
+                arr = np.empty(nbytes // GREP_ROW_DTYPE.itemsize, GREP_ROW_DTYPE)
+            else:
+                obj, addr = _new_bytes(nbytes)
+                box.append(obj)
+                return addr.value
+            box.append(arr)
+            return arr.ctypes.data
+
+        if caps is None:
+            vrp, vcap, rp, rcap, op, ocap, fn = None, 0, None, 0, None, 0, ALLOC_FN(alloc)
+        else:
+            vcap, rcap, ocap = caps
+            ovl, rows = np.zeros(max(1, vcap), OVERLAP_ROW_DTYPE), np.zeros(max(1, rcap), GREP_ROW_DTYPE)
+            out, op = _new_bytes(ocap)
+            vrp, rp, fn = C.c_void_p(ovl.ctypes.data) if vcap else None, C.c_void_p(rows.ctypes.data) if rcap else None, ALLOC_FN()
+            if not ocap:
+                op = None
+        r = self._chk(self.L.zngamd_bgzf_overlap_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                         text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
+                                                         vrp, vcap, rp, rcap, op, ocap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and tot.covered and tot.seen and not tot.bad
+        n = tot.merged + (tot.seen - tot.merged if conf.flags & BGZF_OVERLAP_KEEP_UNMERGED else 0) if got and group else 0
+        if caps is None:
+            ovl_out = box[0] if got else np.empty(0, OVERLAP_ROW_DTYPE)
+            rows_out, packed = (box[1], box[2]) if n else (np.empty(0, GREP_ROW_DTYPE), b"")
+        else:
+            ovl_out = ovl[:tot.seen] if got else np.empty(0, OVERLAP_ROW_DTYPE)
+            rows_out, packed = (rows[:n], _take(out, tot.bytes)) if n else (np.empty(0, GREP_ROW_DTYPE), b"")
+        return r, st[:nm], tot, ovl_out, rows_out, packed
+
+    def bgzf_overlap_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, record_base, d_scratch, scratch_cap,
+                                 d_status, d_overlap, overlap_cap, d_rows, rows_cap, d_out, out_cap):
+        """zngamd_bgzf_overlap_records_dev on device pointers (conf: host memory) -> (code, totals); overlap rows, rows and records stay on
+        the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfOverlapTotals()
+        r = self._chk(self.L.zngamd_bgzf_overlap_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
+                                                             C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_overlap),
+                                                             overlap_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_qc_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):

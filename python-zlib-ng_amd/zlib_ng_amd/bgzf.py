@@ -54,6 +54,7 @@ __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offse
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
            "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP", "trim_records", "TrimResult", "KEPT", "TOO_SHORT", "DROPPED", "qc_records", "QcResult",
            "key_records", "KeyResult", "pair_keys", "dedup_keys", "DedupResult", "dedup_records", "dedup_paired",
+           "overlap_records", "OverlapResult", "NONE", "FOUND", "MERGED", "TOO_LONG",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
 BadGzipFile = zlib_ng.BadGzipFile
@@ -701,7 +702,8 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
     _ClassifySink -- every window's records are not selected but assigned to their nearest pattern (classify_records(), demux()), the
     sink takes what each window gives, and what its finish() returns is the result.  partition (with records, instead of patterns): a
     _PartitionSink -- every window's records are split by the labels it holds (partition_records()) -- or a _TrimSink -- they are cut
-    (trim_records()) -- or a _QcSink -- they are counted (qc_records()) -- or a _KeySink -- they are keyed (key_records())."""
+    (trim_records()) -- or a _QcSink -- they are counted (qc_records()) -- or a _KeySink -- they are keyed (key_records()) -- or an
+    _OverlapSink -- the mates of every pair are laid over each other (overlap_records())."""
     if partition is None:
         pats, delimiter = _grep_patterns(patterns, delimiter)
         mismatches = _grep_mismatches(mismatches, pats)
@@ -1910,6 +1912,179 @@ def pair_labels(first, second, pairs):
     out[(a == na) | (b == nb)] = n
     out[(a == na + 1) | (b == nb + 1)] = n + 1
     return out
+
+
+# ---- pairs laid over each other: the overlap of the two mates, bases corrected, adapters cut, pairs merged
+NONE, FOUND, MERGED, TOO_LONG = _lib.BGZF_OVERLAP_NONE, _lib.BGZF_OVERLAP_FOUND, _lib.BGZF_OVERLAP_MERGED, _lib.BGZF_OVERLAP_TOO_LONG      # an OverlapResult's verdicts
+_OVERLAP_COUNTS = ("none", "found", "merged", "too_long", "bases_in", "bases_merged", "corrected", "corrected_pairs", "adapter_pairs", "adapter_trimmed",
+                   "overlap_sum", "mismatch_sum")
+
+
+class OverlapResult:
+    """What overlap_records() decided.  Per pair, in the order of the file: offset (int64: where the reverse complement of mate 2 begins
+    under mate 1, 0 without an overlap), insert (int64: the fragment's length, 0 without an overlap), overlap and mismatches (int64: the
+    length of the overlap and the places in it where the mates differ), corrected_per_pair (int64: the positions correction changed),
+    verdict (uint8: NONE, FOUND, MERGED, TOO_LONG), steps (uint8: bit 0 mate 1 was cut, bit 1 mate 2 was, bit 2 a base was corrected).
+    The counts: records, none, found, merged, too_long, bases_in (the sequence bytes of both mates), bases_merged (those of the merged
+    reads), corrected and corrected_pairs (the positions correction changed and the pairs that have one), adapter_pairs and
+    adapter_trimmed (the pairs and the bases the cut took), overlap_sum and mismatch_sum (over the pairs with an overlap)."""
+
+    def __init__(self, rows, counts):
+        self.offset, self.insert = rows["offset"].astype(np.int64), rows["insert"].astype(np.int64)
+        self.overlap, self.mismatches, self.corrected_per_pair = (rows[name].astype(np.int64) for name in ("overlap", "mismatches", "corrected"))
+        self.verdict, self.steps = rows["verdict"].copy(), rows["steps"].copy()
+        self.records = len(rows)
+        for name, value in counts.items():
+            setattr(self, name, int(value))
+
+    def insert_sizes(self):
+        """-> int64, entry i: the pairs whose insert is i (entry 0: the pairs without an overlap) -- fastp's insert-size histogram"""
+        return np.bincount(self.insert).astype(np.int64)
+
+    @property
+    def mean_overlap(self):
+        """the mean length of the overlaps found; 0.0 when there is none"""
+        n = self.found + self.merged
+        return self.overlap_sum / n if n else 0.0
+
+    def __len__(self):
+        return self.records
+
+    def __repr__(self):
+        return (f"<OverlapResult: {self.records} pairs, {self.merged} merged, {self.found} with an overlap, {self.none} without, "
+                f"{self.too_long} too long, {self.corrected} bases corrected, {self.adapter_trimmed} cut>")
+
+
+def _overlap_conf(record_lines, seq_line, qual_line, quality_base, min_overlap, mismatches, mismatch_percent, merge, correct, correct_quality,
+                  cut_adapters, first_byte, delimiter):
+    """-> (BgzfOverlapConf without _KEEP_UNMERGED, delimiter as bytes); ValueError as overlap_records() documents it"""
+    delimiter = _partition_delimiter(delimiter)
+    k, _, b = _grep_record_args(record_lines, None, first_byte)
+    if k % 2:
+        raise ValueError(f"record_lines is even, a pair per record (8 for interleaved FASTQ), not {k}")
+    m = k // 2
+    s = _trim_int(seq_line, 0, m - 1, "seq_line")
+    q = -1 if qual_line is None else _trim_int(qual_line, 0, m - 1, "qual_line")
+    if q == s:
+        raise ValueError(f"seq_line and qual_line are two lines of a mate, not both {s}")
+    for name, value in (("merge", merge), ("correct", correct), ("cut_adapters", cut_adapters)):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{name} is True or False, not {value!r}")
+    if correct and q < 0:
+        raise ValueError("correct needs a qual_line")
+    if not isinstance(correct_quality, (tuple, list)) or len(correct_quality) != 2:
+        raise ValueError("correct_quality is a pair (high, low)")
+    hi = _trim_int(correct_quality[0], 0, _lib.BGZF_OVERLAP_MAX_QUALITY, "correct_quality[0]")
+    lo = _trim_int(correct_quality[1], 0, _lib.BGZF_OVERLAP_MAX_QUALITY, "correct_quality[1]")
+    flags = (_lib.BGZF_OVERLAP_MERGE if merge else 0) | (_lib.BGZF_OVERLAP_CORRECT if correct else 0) | (_lib.BGZF_OVERLAP_CUT if cut_adapters else 0)
+    cf = _lib.BgzfOverlapConf(k, s, q, b, _trim_int(quality_base, 0, 255, "quality_base"), _trim_int(min_overlap, 1, _lib.BGZF_OVERLAP_MAX_READ, "min_overlap"),
+                              _trim_int(mismatches, 0, _lib.BGZF_OVERLAP_MAX_READ, "mismatches"), _trim_int(mismatch_percent, 0, 100, "mismatch_percent"),
+                              hi, lo, flags)
+    return cf, delimiter
+
+
+class _OverlapSink:
+    """what _grep_file hands a window's pairs to when their mates are laid over each other; writers: None (count only) or [merged,
+    unmerged], None where a class is written nowhere"""
+
+    def __init__(self, conf, writers=None):
+        self.conf, self.writers = conf, writers
+        self.flags = _lib.BGZF_CLASSIFY_GROUP if writers is not None and any(w is not None for w in writers) else 0
+        conf.flags = (conf.flags & ~_lib.BGZF_OVERLAP_KEEP_UNMERGED) | (_lib.BGZF_OVERLAP_KEEP_UNMERGED if self.flags and writers[1] is not None else 0)
+        self.rows, self.args = [], None
+        self.counts = dict.fromkeys(_OVERLAP_COUNTS, 0)
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        self.ctx, self.args = ctx, (data, members, text_off, text_end, delim, flags, record_base)
+        _, status, tot, self.ovl, self.grows, packed = ctx.bgzf_overlap_records(data, members, text_off, text_end, delim, flags | self.flags, self.conf,
+                                                                                record_base)
+        return status, tot, packed
+
+    def length_fault(self, record, voffset):
+        """the message for bad = 3: the engine is asked for the four bodies' lengths, each line taken as a sequence without qualities"""
+        data, members, text_off, text_end, delim, flags, record_base = self.args
+        k, m, r, lens = self.conf.record_lines, self.conf.record_lines // 2, record - self.args[6], []
+        for line in (self.conf.seq_line, self.conf.qual_line, m + self.conf.seq_line, m + self.conf.qual_line):
+            cf = _lib.BgzfTrimConf(k, line, -1, -1, 0, 0, 0, 0, 33, 0, 1, 0, 0)
+            rows = self.ctx.bgzf_trim_records(data, members, text_off, text_end, b"", np.empty((0, 2), np.uint32), delim, flags, cf, record_base)[3]
+            lens.append(int(rows["end"][r]) if r < len(rows) else -1)
+        mate = 0 if lens[0] != lens[1] else 1
+        return (f"record {record} at virtual offset {voffset}: line {mate * m + self.conf.seq_line} (the sequence of mate {mate + 1}) has "
+                f"{lens[2 * mate]} bytes and line {mate * m + self.conf.qual_line} (its qualities) has {lens[2 * mate + 1]}")
+
+    def window(self, tot, packed):
+        self.rows.append(self.ovl)
+        for name in _OVERLAP_COUNTS:
+            self.counts[name] += int(getattr(tot, name))
+        if not self.flags:
+            return
+        nmerged = int(self.grows["len"][:tot.merged].sum())
+        with memoryview(packed) as mv:
+            if self.writers[0] is not None and nmerged:
+                self.writers[0].write(mv[:nmerged])
+            if self.writers[1] is not None and len(packed) > nmerged:
+                self.writers[1].write(mv[nmerged:])
+        if len(packed) != int(tot.bytes):
+            raise RuntimeError("overlap: the classes' bytes do not add up to the records")
+
+    def finish(self, searched):
+        rows = np.concatenate(self.rows) if self.rows else np.empty(0, _lib.OVERLAP_ROW_DTYPE)
+        return OverlapResult(rows, self.counts)
+
+
+def _overlap_file(fp, ctx, merged, unmerged, record_lines, seq_line, qual_line, quality_base, min_overlap, mismatches, mismatch_percent, merge, correct,
+                  correct_quality, cut_adapters, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record, allow_short):
+    conf, delimiter = _overlap_conf(record_lines, seq_line, qual_line, quality_base, min_overlap, mismatches, mismatch_percent, merge, correct,
+                                    correct_quality, cut_adapters, first_byte, delimiter)
+    _check_block_size(block_size)
+
+    def run(writers):
+        sink = _OverlapSink(conf, writers)
+        return _grep_file(fp, ctx, None, delimiter, False, False, False, None, start, stop, first_record, max_record,
+                          (record_lines, None, first_byte, allow_short), 0, None, sink)
+
+    if merged is None and unmerged is None:
+        return run(None)
+    return _with_writers("overlap_records", [merged, unmerged], compresslevel, block_size, run)
+
+
+def overlap_records(file, merged=None, unmerged=None, record_lines=8, *, seq_line=1, qual_line=3, quality_base=33, min_overlap=30, mismatches=5,
+                    mismatch_percent=20, merge=True, correct=False, correct_quality=(30, 14), cut_adapters=False, first_byte=None, delimiter=b"\n",
+                    compresslevel=6, block_size=MAX_BLOCK_INPUT, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+    """Lay the two mates of every pair of an INTERLEAVED BGZF file over each other on the GPU, as fastp's overlap analysis, bbmerge, PEAR,
+    FLASH and vsearch --fastq_mergepairs do: one record is one pair, mate 1 its first record_lines / 2 lines and mate 2 the rest (what
+    fastp --interleaved_in, bbmerge in= and seqtk mergepe read and write; two separate files are not taken).  seq_line and qual_line
+    (None: no qualities) name the same line of both mates.  The reverse complement of mate 2 is tried at every offset under mate 1; an
+    offset counts when the mates overlap in at least min_overlap bases that differ in at most min(mismatches, overlap *
+    mismatch_percent // 100) places, and of those the longest overlap wins, then the fewest mismatches, then the offset nearest 0, then
+    the one that is not negative -- include/zng_amd.h states the rule.  With an overlap the fragment's length is known (insert), and
+        correct       where the mates differ in the overlap and one side has a quality of at least correct_quality[0] and the other of at
+                      most correct_quality[1], the weak side takes the strong side's base and quality (fastp -c)
+        cut_adapters  what lies beyond the fragment's end in either mate is adapter read-through and is cut off: the one adapter finder
+                      that needs no adapter sequence
+        merge         the pair becomes ONE read of `insert` bases under mate 1's name: where both mates cover a position the base with
+                      the higher quality stands (mate 1's on ties), its quality with it (fastp -m)
+    merged is a path or writable binary file for the merged reads (record_lines / 2 lines each), unmerged an optional second one for
+    every other pair (record_lines lines each, as correction and cut left them); each is written through a BgzfWriter (compresslevel,
+    block_size): a complete BGZF file.  Both None: the pairs are judged and counted only.  A mate of more than 1024 bases is not
+    searched (TOO_LONG) and is written whole.  Reads to be filtered first go through trim_records(..., record_lines=8, drop=); its
+    output is this call's input.  record_lines, first_byte (here of both mates' first lines), delimiter, start, stop, first_record,
+    max_record, allow_short and the errors of the file are those of grep_records().  -> OverlapResult.
+    A mate whose sequence and qualities differ in length is a ValueError that names the record, its virtual offset and both lengths.  If
+    anything is raised the outputs written so far are closed, and the error says that they are incomplete."""
+    if _is_path(file):
+        _overlap_conf(record_lines, seq_line, qual_line, quality_base, min_overlap, mismatches, mismatch_percent, merge, correct, correct_quality,
+                      cut_adapters, first_byte, delimiter)       # (judged before the file is opened)
+        _check_block_size(block_size)
+        with _builtin_open(file, "rb") as f:
+            return overlap_records(f, merged, unmerged, record_lines, seq_line=seq_line, qual_line=qual_line, quality_base=quality_base,
+                                   min_overlap=min_overlap, mismatches=mismatches, mismatch_percent=mismatch_percent, merge=merge, correct=correct,
+                                   correct_quality=correct_quality, cut_adapters=cut_adapters, first_byte=first_byte, delimiter=delimiter,
+                                   compresslevel=compresslevel, block_size=block_size, start=start, stop=stop, first_record=first_record,
+                                   max_record=max_record, allow_short=allow_short)
+    return _overlap_file(file, None, merged, unmerged, record_lines, seq_line, qual_line, quality_base, min_overlap, mismatches, mismatch_percent, merge,
+                         correct, correct_quality, cut_adapters, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record,
+                         allow_short)
 
 
 # ---- lines by region (DESIGN.md section 5g): a tabix index built on the GPU, and the rows of a region filtered there
@@ -3439,6 +3614,22 @@ class BgzfReader(io.BufferedIOBase):
             return _trim_file(self._fp, self._ctx, output, too_short, record_lines, seq_line, qual_line, cut, quality, quality_base, adapters, mismatches,
                               min_overlap, min_length, drop, first_byte, delimiter, compresslevel, block_size, start, stop, first_record, max_record,
                               allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def overlap_records(self, merged=None, unmerged=None, record_lines=8, *, seq_line=1, qual_line=3, quality_base=33, min_overlap=30, mismatches=5,
+                        mismatch_percent=20, merge=True, correct=False, correct_quality=(30, 14), cut_adapters=False, first_byte=None, delimiter=b"\n",
+                        compresslevel=6, block_size=MAX_BLOCK_INPUT, start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+        """bgzf.overlap_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("overlap_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _overlap_file(self._fp, self._ctx, merged, unmerged, record_lines, seq_line, qual_line, quality_base, min_overlap, mismatches,
+                                 mismatch_percent, merge, correct, correct_quality, cut_adapters, first_byte, delimiter, compresslevel, block_size,
+                                 start, stop, first_record, max_record, allow_short)
         finally:
             self._fp.seek(at)
 
