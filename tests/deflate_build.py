@@ -165,8 +165,12 @@ class _Coded:
 class Fixed(_Coded):
     btype = 1
 
+    _fixed = []                                          # the two fixed codes, computed once
+
     def _codes(self):
-        return canonical(FIXED_L), canonical(FIXED_D)
+        if not Fixed._fixed:
+            Fixed._fixed += [canonical(FIXED_L), canonical(FIXED_D)]
+        return Fixed._fixed
 
     def write(self, w, final):
         w.bits(1 if final else 0, 1)
@@ -265,6 +269,18 @@ def end_bit(blocks, final=True):
     w = BitWriter()
     assemble(blocks, final, w)
     return w.bitlen
+
+
+def block_bits(blocks, final=True, start=0):
+    """-> ([the bit at which each block's header starts], the end bit) of the stream written from bit `start` on (a stored block
+    pads to a byte of the whole stream, so `start & 7` matters)"""
+    w = BitWriter()
+    w.bits(0, start & 7)
+    base, hdr = start - (start & 7), []
+    for i, b in enumerate(blocks):
+        hdr.append(base + w.bitlen)
+        b.write(w, final and i == len(blocks) - 1)
+    return hdr, base + w.bitlen
 
 
 def replay(blocks, zdict=b""):
@@ -494,8 +510,8 @@ def random_complete_lengths(rng, n, maxlen):
     return [int(x) for x in leaves]
 
 
-def random_stream(rng):
-    """A valid stream of 1..12 blocks of random kind -> (blob, expect).  Output <= 40 KiB, input <= 8 KiB."""
+def random_stream_blocks(rng):
+    """The blocks of a valid stream of 1..12 blocks of random kind.  Output <= 40 KiB, input <= 8 KiB."""
     while True:
         blocks, out = [], 0
         for _ in range(int(rng.integers(1, 13))):
@@ -532,9 +548,14 @@ def random_stream(rng):
                     toks.append(lits[int(rng.integers(0, len(lits)))])
                     out += 1
             blocks.append(Fixed(toks) if kind == 1 else Dynamic(ll, d, toks, rle=bool(rng.integers(0, 2))))
-        blob = assemble(blocks)
-        if len(blob) <= 8192 and out <= 40 * 1024:
-            return blob, replay(blocks)[0]
+        if len(assemble(blocks)) <= 8192 and out <= 40 * 1024:
+            return blocks
+
+
+def random_stream(rng):
+    """A valid stream of random_stream_blocks -> (blob, expect)"""
+    blocks = random_stream_blocks(rng)
+    return assemble(blocks), replay(blocks)[0]
 
 
 def random_streams(seed=1951, n=300):
@@ -544,5 +565,265 @@ def random_streams(seed=1951, n=300):
     return [random_stream(rng) for _ in range(n)]
 
 
+def random_block_streams(seed=1951, n=300):
+    """The blocks of the same n cases -> [blocks]"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    return [random_stream_blocks(rng) for _ in range(n)]
+
+
 def match_count(blocks):
     return sum(isinstance(t, M) for b in blocks if not isinstance(b, Stored) for t in b.tokens)
+
+
+# ---- vectors for a decoder that starts behind a window: the span decoder of the seek-point index --------------------------------------
+# A span is a run of blocks decoded with the 32 KiB in front of it as its dictionary (tests/span_tables.py cuts vectors into spans).
+# Every valid vector's name states a property, and the builder asserts it here, from its own tokens.
+
+RING = 512                     # the small history ring of the member / span kernels: the sources below lie around its edge
+EDGE_W = (1, 511, 512, 513, 32767, 32768)
+EDGE_OPS = (0, 1, 2, 300, 511, 512, 513, 700)
+
+
+def _nine_bit(j):
+    """nine literals of which j take nine bits in the fixed code: a fixed block of 82 + j bits"""
+    return [200] * j + [33] * (9 - j)
+
+
+def hdr_every_bit_blocks(target=64 << 10):
+    """About `target` bytes of non-final blocks of 0..9 bytes each, and an empty final block.  Fixed blocks of nine literals, j of
+    them of nine bits, move the next header by 2 + j bits; every seventh block is a dynamic one (a one-bit or a two-bit code for
+    its literal), every seventh a stored one of 1..9 bytes, and every 64th an empty stored or an end-of-block-only dynamic block."""
+    blocks, w, i = [], BitWriter(), 0
+    eob_only = spread([256], [1], 257)
+    while w.bitlen < 8 * target:
+        c = 32 + i % 90
+        if i % 64 == 31:
+            b = Stored(b"") if i % 128 == 31 else Dynamic(eob_only, [0], rle=True)
+        elif i % 7 == 3:
+            n = 1 + (i // 7) % 9
+            if (i // 7) % 2:
+                b = Dynamic(spread([c, 256], [1, 1], 257), [0], [c] * n, rle=True)
+            else:
+                b = Dynamic(spread([c, c + 1, 256], [1, 2, 2], 257), [0], ([c, c + 1] * 5)[:n], rle=True)
+        elif i % 7 == 6:
+            b = Stored(bytes((c + k) & 0xFF for k in range(1 + (i // 7) % 9)))
+        else:
+            b = Fixed(_nine_bit((i * 3 + i // 10) % 10))
+        blocks.append(b)
+        b.write(w, False)
+        i += 1
+    return blocks + [Fixed([])]
+
+
+def hdr_every_bit_census(blocks):
+    """What the vector's name promises, counted from block_bits: {(kind of the block in front, header bit & 7)}, the bits at which
+    a stored block with data starts, the kinds in front of which an empty block stands, and the lowest output / input ratio of
+    any 4096 stream bytes"""
+    hdr, end = block_bits(blocks)
+    kind = lambda b: ("stored" if b.data else "empty_stored") if isinstance(b, Stored) else \
+        ("fixed" if isinstance(b, Fixed) else ("dynamic" if b.tokens else "eob_only"))
+    front = {(kind(blocks[i - 1]), hdr[i] & 7) for i in range(1, len(blocks))}
+    stored_at = {hdr[i] & 7 for i, b in enumerate(blocks) if kind(b) == "stored"}
+    outs = [0]
+    for b in blocks:
+        outs.append(outs[-1] + (len(b.data) if isinstance(b, Stored) else len(b.tokens)))
+    # the output of the blocks that START in each 4096-byte piece of the stream
+    per = {}
+    for i, h in enumerate(hdr):
+        per[h >> 15] = per.get(h >> 15, 0) + outs[i + 1] - outs[i]
+    ratio = min(per[k] for k in range(max(per))) / 4096.0          # (the last piece is not a full one)
+    return front, stored_at, ratio, (end + 7) >> 3
+
+
+def _edge_vector(name, w, tokens, seed):
+    return _vec(name, [Fixed(tokens)], zdict=_pattern(w, seed))
+
+
+def win_edge_vectors():
+    """win_edges_<w>: a window of w bytes and one fixed block whose FIRST token reaches the window's first byte, M(3, w); then
+    overlapping copies at distances 1 and 2 with 0, 1 and 2 literals in front, one at distance 4 whose source starts at -1, and
+    further on copies at exactly op + w (while that is a distance) and at 511, 512 and 513.
+    win_edges_<w>_op<T>_<what>: T literals and then ONE 258-byte copy at op = T: `first` = at distance T + w, the window's first
+    byte; d511 / d512 / d513 = from around the ring's edge.  At T = 0, 1, 2 and w = 1 `first` has dist < len and a source that
+    straddles -1/0; so have the vectors ..._straddle (distance T + 1 and T + 2).
+    -> (vectors, {name: (op, length, dist) of the copy the name is about})"""
+    out, about = [], {}
+    for w in EDGE_W:
+        seed = 100 + w
+        lit = lambda n, s: list(_pattern(n, s))
+        toks = [M(3, w), M(258, 4)]
+        for k in range(3):
+            toks += lit(k, 7 + k) + [M(258, 1)] + lit(k, 17 + k) + [M(258, 2)]
+        toks += lit(5, 3)
+        op = replay([Fixed(toks)], _pattern(w, seed))[0].__len__()
+        for _ in range(3):
+            if op + w <= 32768:
+                toks += [M(3, op + w), 77]
+                op += 4
+            toks += [M(258, 511), M(200, 512), M(258, 513), 78]
+            op += 258 + 200 + 258 + 1
+        out.append(_edge_vector("win_edges_%d" % w, w, toks, seed))
+        about["win_edges_%d" % w] = (0, 3, w)
+        for t in EDGE_OPS:
+            cases = [("first", t + w)] + [("d%d" % d, d) for d in (511, 512, 513)]
+            if t < 3:
+                cases += [("straddle%d" % k, t + k) for k in (1, 2)]
+            for what, d in cases:
+                if d > min(32768, t + w) or (what != "first" and d == t + w):
+                    continue
+                name = "win_edges_%d_op%d_%s" % (w, t, what)
+                out.append(_edge_vector(name, w, lit(t, 31 + t) + [M(258, d), 1, 2], seed))
+                about[name] = (t, 258, d)
+    return out, about
+
+
+def win_beyond_vectors():
+    """win_beyond_<w>: the start of win_edges_<w>, then one copy at op + w + 1, one byte in front of the window (w = 32767: at
+    op = 0, since 32768 is the largest distance there is)"""
+    tail = [Raw(0x5A5A5A5A, 32)] * 4
+    out = []
+    for w in (1, 511, 512, 32767):
+        head = [] if w == 32767 else [M(3, w)]
+        op = 3 * len(head)
+        out.append(_vec("win_beyond_%d" % w, [Fixed(head + [M(3, op + w + 1)] + tail, eob=False)], zdict=_pattern(w, 100 + w), invalid=True))
+    return out
+
+
+def long_block_vector(seed=4242, ntok=6300):
+    """long_block_into_window: ONE dynamic block of `ntok` tokens behind a window of 32768 bytes, a third of them matches whose
+    distances are spread over 1 .. op + 32768 -> (vector, counts)"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    ll = [8] * 240 + [9] * 18 + [10] * 28
+    d30 = [4, 4] + [5] * 28
+    assert kraft(ll) == 32768 and kraft(d30) == 32768
+    toks, op = [], 0
+    for _ in range(ntok):
+        if rng.random() < 1 / 3:
+            length = 258 if rng.random() < 0.02 else int(rng.integers(3, 20))
+            reach = min(32768, op + 32768)
+            r = rng.random()
+            if r < 0.1 and op + length - 1 <= 32768:
+                dist = op + int(rng.integers(1, length))                   # starts in the window, ends in the output
+            elif r < 0.2:
+                dist = int(rng.integers(1, min(reach, 20) + 1))            # short, often dist < length
+            elif r < 0.3:
+                dist = min(reach, int(rng.integers(RING - 2, RING + 3)))   # around the ring's edge
+            else:
+                dist = int(rng.integers(1, reach + 1))
+            toks.append(M(length, dist))
+            op += length
+        else:
+            toks.append(int(rng.integers(0, 256)))
+            op += 1
+    v = _vec("long_block_into_window", [Dynamic(ll, d30, toks, rle=True)], zdict=_pattern(32768, 5))
+    return v, long_block_counts(v)
+
+
+def long_block_counts(v):
+    """from replay alone: tokens, matches, sources that begin in the window, that straddle -1/0, that lie more than RING back"""
+    plain, matches = replay(v.blocks, v.zdict)
+    c = dict(tokens=len(v.blocks[0].tokens), matches=len(matches), in_window=0, straddle=0, far=0, stream=len(v.blob), out=len(plain))
+    op = 0
+    for t in v.blocks[0].tokens:
+        if isinstance(t, M):
+            c["in_window"] += t.dist > op
+            c["straddle"] += op < t.dist < op + t.length
+            c["far"] += t.dist > RING
+            op += t.length
+        else:
+            op += 1
+    return c
+
+
+def crc_fold_vector(n):
+    """crc_fold_<n>: n bytes out of fixed blocks of one literal and 63 copies of 258 bytes at distance 1 (a last, shorter block)"""
+    blocks, left, i = [], n, 0
+    while left:
+        m = min(left, 1 + 63 * 258) - 1
+        toks = [65 + i % 26] + [M(258, 1)] * (m // 258)
+        m %= 258
+        toks += [M(m, 1)] if m >= 3 else [65 + i % 26] * m
+        blocks.append(Fixed(toks))
+        left -= min(left, 1 + 63 * 258)
+        i += 1
+    return _vec("crc_fold_%d" % n, blocks)
+
+
+REFILL_W = (1, 100, 240)
+
+
+def refill_edge_vector(w, beyond=False):
+    """refill_edge_<w>: a window of w bytes and one fixed block of 240 literals and eight copies, each at exactly op + w, with
+    op + w < RING all the way.  The block is long enough for a parallel sweep and its last tokens are left to the sequential
+    rounds behind it, whose ring is refilled from the output AND the window: the window's first byte is then the oldest byte
+    that the refill has to bring back.  beyond: the last copy reaches one byte further (invalid)."""
+    toks = list(_pattern(240, 9 + w))
+    for k in range(8):
+        toks.append(M(3, 240 + 3 * k + w + (1 if beyond and k == 7 else 0)))
+    if beyond:
+        return _vec("refill_beyond_%d" % w, [Fixed(toks + [Raw(0x5A5A5A5A, 32)] * 4, eob=False)], zdict=_pattern(w, 200 + w), invalid=True)
+    return _vec("refill_edge_%d" % w, [Fixed(toks)], zdict=_pattern(w, 200 + w))
+
+
+_span_cache = []
+
+
+def span_vectors():
+    """The vectors above, the valid ones first; each valid one's property is asserted here.  Built once per process."""
+    if _span_cache:
+        return list(_span_cache)
+    v = []
+    blocks = hdr_every_bit_blocks()
+    front, stored_at, ratio, nbytes = hdr_every_bit_census(blocks)
+    for p in range(8):
+        assert ("fixed", p) in front and ("dynamic", p) in front and p in stored_at, p
+    assert ("stored", 0) in front and any(k == "empty_stored" for k, _ in front) and any(k == "eob_only" for k, _ in front)
+    # the index builder reads at most 4096 / ratio bytes of this stream per call (spacing 4096): more than ten calls
+    assert 65536 <= nbytes <= 65536 + 64 and nbytes * ratio / 4096 > 10, (nbytes, ratio)
+    assert all(0 <= (len(b.data) if isinstance(b, Stored) else len(b.tokens)) <= 9 for b in blocks)
+    v.append(_vec("hdr_every_bit", blocks))
+    edges, about = win_edge_vectors()
+    for e in edges:
+        op, length, dist = about[e.name]
+        w = len(e.zdict)
+        toks = e.blocks[0].tokens
+        assert toks[op] == M(length, dist) and all(isinstance(t, int) for t in toks[:op]), e.name
+        what = e.name.split("_")[-1]
+        if what == "first" or e.name.count("_") == 2:
+            assert dist == op + w                                              # the window's first byte, exactly
+        elif what.startswith("straddle"):
+            assert op < dist < length and dist <= op + w                       # starts in the window, runs into its own output
+        else:
+            assert dist in (RING - 1, RING, RING + 1) and dist <= op + w
+    for w in EDGE_W:                                                           # ... and every kind of ring-edge source occurs
+        kinds = set()
+        for e in edges:
+            op, length, dist = about[e.name]
+            if len(e.zdict) == w and dist in (RING - 1, RING, RING + 1):
+                kinds.add("window" if dist >= op + length else ("output" if dist <= op else "across"))
+        assert kinds == ({"window", "across", "output"} if w >= RING - 1 else {"across", "output"}), (w, kinds)
+    v += edges
+    lb, c = long_block_vector()
+    assert c["tokens"] >= 6000 and abs(c["matches"] / c["tokens"] - 1 / 3) < 0.03 and c["stream"] >= 3 * 3072, c
+    assert c["in_window"] >= 200 and c["straddle"] >= 20 and c["far"] >= 200 and len(lb.zdict) == 32768, c
+    v.append(lb)
+    for n in (131072, 131073, 262149):
+        f = crc_fold_vector(n)
+        assert len(f.expect) == n and len(f.blocks) > 1
+        v.append(f)
+    for w in REFILL_W:
+        r = refill_edge_vector(w)
+        op = 0
+        for t in r.blocks[0].tokens:
+            if isinstance(t, M):
+                assert t.dist == op + w < RING and op >= 240, (w, op)
+            op += t.length if isinstance(t, M) else 1
+        # (a sweep wants 12 * 64 + 64 bits of input in front of it and room for 256 bytes)
+        assert op >= 256 and 8 * len(r.blob) >= 2000 and match_count(r.blocks) == 8
+        v.append(r)
+    v += win_beyond_vectors()
+    v.append(refill_edge_vector(100, beyond=True))
+    _span_cache.extend(v)
+    return list(v)

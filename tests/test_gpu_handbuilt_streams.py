@@ -10,6 +10,7 @@ oracle's.  Verdicts: 1 = the stream ended, -3 = data error, -5 = wants more inpu
     za_k_chunk_decode<512>        ctx.gunzip of ONE member of sync-delimited pieces: one pass (pieces of >= 8 KiB), count pass + tables
                                   of the two-pass branch (pieces of 3 KiB); markers that cross a chunk edge
     the streaming object          zlib_ng.decompressobj(-15) fed in halves and byte by byte
+    za_k_inflate_spans            the span decoder of the seek-point index: tests/test_gpu_span_handbuilt.py
 The valid half of a decoder's vectors runs before its invalid half (two test functions)."""
 import gzip
 import struct
