@@ -212,10 +212,18 @@ int zngamd_inflate_raw(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len,
  * ZNGAMD_BUF_ERROR (input ran out), the caller keeps in[*block_bits/8 ..], the last 32 KiB of output up to
  * *block_out, and calls again once more input has arrived.  ZNGAMD_E_OVERFLOW = out_cap reached.
  * Pieces of at least 64 KiB are decoded chunk-parallel up to their last complete block (then *out_len == *block_out:
- * the incomplete block is not decoded at all); smaller pieces run on the sequential wavefront decoder. */
+ * the incomplete block is not decoded at all; with ZNGAMD_STREAM_END the checkpoint is a block header that was entered, not
+ * necessarily the last one); smaller pieces run on the sequential wavefront decoder. */
 int zngamd_inflate_resume(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, uint32_t start_bit,
                           const uint8_t *dict, uint32_t dict_len, uint8_t *out, uint64_t out_cap,
                           uint64_t *out_len, uint64_t *in_bits, uint64_t *block_bits, uint64_t *block_out);
+/* what the chunk-parallel decoder of streams without an index (zngamd_gunzip path 3, large zngamd_inflate_raw / _resume calls) found
+ * since the last reset, summed over every attempt that completed its list of chunk boundaries: out[0] hits of the sync-marker scan
+ * (00 00 FF FF), out[1] bit offsets that passed the first test of the block-header finder (0 where sync markers were dense enough
+ * and the finder did not run), out[2] boundaries after sorting and removing duplicates, the start of the stream among them,
+ * out[3] chunks of the attempts that produced the call's bytes.  A header the finder misses costs speed, never bytes: these
+ * numbers are the only place where a miss shows.  Costs no launch and no synchronisation. */
+int zngamd_chunk_stats(zngamd_ctx *ctx, uint64_t *out /*[4]*/, int reset);
 
 /* gzip member table entry produced by the index scan (pass 1) */
 typedef struct {

@@ -2209,14 +2209,16 @@ __global__ __launch_bounds__(64) void za_k_chunk_count(const uint8_t *__restrict
     __shared__ ZaParBufT<BITS, 1, ZA_CHUNK_MAXIT> PS;
     const uint64_t abit = cands[blockIdx.x];                 // absolute bit offset of a possible block header
     const uint64_t off = abit >> 3;
-    uint64_t bits = 0, op = 0;
+    uint64_t bits = 0, op = 0, cpb = abit & 7u, cpo = 0;
     int status = ZA_I_DATA;
     if (off <= in_len)
         status = za_inflate_serial_core<1, uint8_t, ZA_WIN, ZaParBufT<BITS, 1, ZA_CHUNK_MAXIT>>(in + off, in_len - off, nullptr, 0, nullptr, ZA_COUNT_CAP, T, nullptr, scratch, PS.stage,
-                                                    bits, op, (uint32_t)(abit & 7u), nullptr, nullptr,
+                                                    bits, op, (uint32_t)(abit & 7u), &cpb, &cpo,
                                                     whole_streams ? 0u : (abit == first_bit ? first_hist : (uint32_t)ZA_WIN), !whole_streams, nullptr,
                                                     cands, whole_streams ? 0u : ncands, off * 8ull, &PS);
-    // bits = position relative to byte `off`; report the absolute end
+    // bits = position relative to byte `off`; report the absolute end.  Where the input ran out, what is reported is the header of
+    // the last block that was entered and the output in front of it: the place where a resumed stream goes on
+    if (status == ZA_I_INPUT) { bits = cpb; op = cpo; }
     if (za_lane() == 0) { ZaChunkRes r; r.status = status; r.max_back = 0; r.bits = off * 8ull + bits; r.out_len = op; res[blockIdx.x] = r; }
 }
 

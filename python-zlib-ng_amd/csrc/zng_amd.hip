@@ -169,6 +169,7 @@ struct zngamd_ctx {
     uint64_t paths[4] = {0, 0, 0, 0};            // members decoded per path, see zngamd_decode_paths
     uint64_t indexed_units = 0;                  // units decoded with a writer's index (zngamd_indexed_units)
     uint64_t span_stats[2] = {0, 0};             // spans and bytes of the span decoder (zngamd_span_stats)
+    uint64_t chunk_stats[4] = {0, 0, 0, 0};      // sync hits, finder survivors, boundaries, chunks of inflate_chunked_once (zngamd_chunk_stats)
     DevBuf<uint8_t> sp_in, sp_win, sp_out; DevBuf<ZaSpan> sp_tab; DevBuf<int32_t> sp_status;      // staging of zngamd_inflate_spans
     DevBuf<uint8_t> bt_out, bt_out2, bt_def; DevBuf<ZaBatchItem> bt_items, bt_items2; DevBuf<ZaBatchResult> bt_res, bt_res2;    // the batch API (za_batch.hip)
     DevBuf<uint32_t> bt_first, bt_ulen, bt_ucrc; DevBuf<uint64_t> bt_uoff, bt_total;
@@ -1341,7 +1342,7 @@ static int inflate_serial_dev(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_le
 
 // a stream that is resumed at a block header (bit offset + history) and / or may run past the end of the buffer
 struct ChunkOpts { uint32_t start_bit = 0; const uint8_t *d_dict = nullptr; uint32_t dict_len = 0; bool allow_cut = false; };
-struct ChunkInfo { bool cut = false; bool ended = false; uint64_t end_bit = 0; };
+struct ChunkInfo { bool cut = false; bool ended = false; uint64_t end_bit = 0; uint64_t last_bit = 0, last_out = 0; };    // last_*: the last listed block header the chain entered, and the output in front of it
 // from this many chunks (or block candidates) on, the chunk kernels run in their small-LDS size: more than the 1 024
 // wavefronts the large size keeps resident (256 CUs x 4 workgroups)
 #ifndef ZNGAMD_CHUNKS_SMALL_FROM
@@ -1491,7 +1492,8 @@ try {
         if (cr == 0) {
             chunked = true;
             res.status = ci.ended ? ZA_I_END : ZA_I_INPUT; res.out_len = clen; res.in_bits = ci.end_bit;
-            res.block_bits = ci.end_bit; res.block_out = clen;
+            // the checkpoint: the header of the block that was cut off; of a stream that ended, the last listed header it entered
+            res.block_bits = ci.ended ? ci.last_bit : ci.end_bit; res.block_out = ci.ended ? ci.last_out : clen;
         }   // (not enough room, or nothing to gain: the sequential decoder below fills out_cap / gives the verdict)
     }
     if (!chunked) {
@@ -1687,6 +1689,14 @@ try {
     std::lock_guard<std::mutex> g(c->mu);
     out[0] = c->span_stats[0]; out[1] = c->span_stats[1];
     if (reset) c->span_stats[0] = c->span_stats[1] = 0;
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_chunk_stats(zngamd_ctx *c, uint64_t *out, int reset)
+try {
+    if (!c || !out) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    for (int i = 0; i < 4; i++) { out[i] = c->chunk_stats[i]; if (reset) c->chunk_stats[i] = 0; }
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
 
@@ -2543,6 +2553,7 @@ static int inflate_chunked_dev(zngamd_ctx *c, const uint8_t *d_def, uint64_t ava
         if (lastb || bi.ended) {
             *out_len = acc; *in_used = byte0 + bu;
             info->cut = bi.cut; info->ended = bi.ended; info->end_bit = byte0 * 8ull + bi.end_bit;
+            info->last_bit = byte0 * 8ull + bi.last_bit; info->last_out = acc - bl + bi.last_out;
             return 0;
         }
         pos_bit = byte0 * 8ull + bi.end_bit;
@@ -2617,6 +2628,7 @@ static int inflate_chunked_once(zngamd_ctx *c, const uint8_t *d_def, uint64_t av
     cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
     const uint32_t n = (uint32_t)cand.size();
     if (getenv("ZNGAMD_DEBUG")) fprintf(stderr, "zng_amd: chunk finder: %u sync hits, %u header survivors, %u candidates\n", cnt[0], cnt[1], n);
+    c->chunk_stats[0] += cnt[0]; c->chunk_stats[1] += cnt[1]; c->chunk_stats[2] += n;
     if (n < 8 || n > max_c) return chunk_bail(3);                    // too few boundaries to be worth it
     std::vector<ZaChunk> chain;
     std::vector<ZaChunkRes> res;
@@ -2673,7 +2685,7 @@ static int inflate_chunked_once(zngamd_ctx *c, const uint8_t *d_def, uint64_t av
                 if (it == cand.end() || *it != r.bits) { good = false; break; }
                 i = (size_t)(it - cand.begin());
             }
-            if (good && (ended || (o.allow_cut && cut && !chain.empty())) && chain.size() >= (resumed ? 1u : 4u)) { placed = true; info->cut = cut; }
+            if (good && (ended || (o.allow_cut && cut && !chain.empty())) && chain.size() >= (resumed ? 1u : 4u)) { placed = true; info->cut = cut; info->last_bit = chain.back().in_bit; info->last_out = chain.back().out_off; }
             else { chain.clear(); acc = 0; end_bit = 0; ended = false; }         // anything odd: the two passes decide
         }
     }
@@ -2700,7 +2712,16 @@ static int inflate_chunked_once(zngamd_ctx *c, const uint8_t *d_def, uint64_t av
             const ZaChunkRes &r = res[i];
             if (r.status == ZA_I_INPUT) {
                 info->cut = true;
-                if (o.allow_cut && !blocks.empty()) { end_bit = cand[i]; break; }      // stop in front of the incomplete block
+                // stop in front of the incomplete block: the last header this piece entered (r.bits, with r.out_len bytes in front
+                // of it).  Blocks that the finder does not list -- stored, fixed, a dynamic header cut by the end of the input --
+                // are complete up to there, and a stream resumed at the piece's own start would decode them again on every call.
+                if (o.allow_cut && r.bits > cand[i] && r.bits <= avail * 8ull && (r.out_len > 0 || !blocks.empty())) {
+                    ZaChunk b; b.in_bit = cand[i]; b.out_off = acc; b.out_len = r.out_len; b.end_bit = r.bits; b.src_off = acc;
+                    blocks.push_back(b);
+                    acc += r.out_len;
+                    end_bit = r.bits; break;
+                }
+                if (o.allow_cut && !blocks.empty()) { end_bit = cand[i]; break; }
             }
             if (r.status != ZA_I_SYNC && r.status != ZA_I_END) return chunk_bail(4);
             ZaChunk b; b.in_bit = cand[i]; b.out_off = acc; b.out_len = r.out_len; b.end_bit = r.bits; b.src_off = acc;
@@ -2712,6 +2733,7 @@ static int inflate_chunked_once(zngamd_ctx *c, const uint8_t *d_def, uint64_t av
             i = (size_t)(it - cand.begin());
         }
     }
+    if (!blocks.empty()) { info->last_bit = blocks.back().in_bit; info->last_out = blocks.back().out_off; }
     static const uint64_t chunk_div = [] { const long v = getenv("ZNGAMD_CHUNK_DIV") ? atol(getenv("ZNGAMD_CHUNK_DIV")) : 4096; return (uint64_t)(v < 1 ? 1 : v); }();
     const uint64_t target = std::max<uint64_t>(32u << 10, acc / chunk_div);
     for (size_t b = 0; b < blocks.size();) {
@@ -2763,6 +2785,7 @@ static int inflate_chunked_once(zngamd_ctx *c, const uint8_t *d_def, uint64_t av
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
+    c->chunk_stats[3] += m;
     return 0;
 }
 

@@ -76,7 +76,7 @@ SYMBOLS = [
     "zngamd_comm_allgather_stream", "zngamd_comm_offsets", "zngamd_comm_wait", "zngamd_comm_barrier", "zngamd_comm_max_f64",
     "zngamd_gunzip", "zngamd_gunzip_partial", "zngamd_gunzip_stream", "zngamd_gzip_members", "zngamd_gzip_members_dev", "zngamd_profiling",
     "zngamd_kernel_times", "zngamd_kernel_class_count", "zngamd_abi", "zngamd_decode_paths", "zngamd_deflate_index_dev", "zngamd_inflate_units_indexed_dev", "zngamd_index_create", "zngamd_index_destroy", "zngamd_deflate_index", "zngamd_deflate_blocks_packed_indexed", "zngamd_indexed_units", "zngamd_debug_fetch", "zngamd_debug_keep", "zngamd_d2d", "zngamd_dmemset", "zngamd_mem_info",
-    "zngamd_inflate_spans_dev", "zngamd_inflate_spans", "zngamd_span_stats",
+    "zngamd_inflate_spans_dev", "zngamd_inflate_spans", "zngamd_span_stats", "zngamd_chunk_stats",
     "zngamd_inflate_batch_dev", "zngamd_inflate_batch", "zngamd_deflate_batch_dev", "zngamd_deflate_batch",
     "zngamd_inflate_batch_dict_dev", "zngamd_inflate_batch_dict", "zngamd_deflate_batch_dict_dev", "zngamd_deflate_batch_dict",
     "zngamd_train_dict_dev", "zngamd_train_dict",
@@ -432,6 +432,7 @@ def load():
         L.zngamd_inflate_spans_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp]
         L.zngamd_inflate_spans.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, u8p, C.c_uint64, u8p, C.c_uint64, vp]
         L.zngamd_span_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
+        L.zngamd_chunk_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]
         L.zngamd_inflate_batch_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, vp, C.c_uint64, vp]
         L.zngamd_inflate_batch.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, ALLOC_FN, vp, vp]
         L.zngamd_deflate_batch_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, C.c_uint64, vp,
@@ -1248,6 +1249,12 @@ class Context:
         m = (C.c_uint64 * 2)()
         self._chk(self.L.zngamd_span_stats(self.h, m, 1 if reset else 0))
         return int(m[0]), int(m[1])
+
+    def chunk_stats(self, reset=True):
+        """(sync-scan hits, header-finder survivors, boundaries, chunks decoded) of the chunk-parallel decoder since the last reset"""
+        m = (C.c_uint64 * 4)()
+        self._chk(self.L.zngamd_chunk_stats(self.h, m, 1 if reset else 0))
+        return tuple(int(x) for x in m)
 
     # ---- the batch API (batch.py): always the _dict entry points; zdict None = no dictionary (NULL, 0), else a bytes-like shared
     # by every item

@@ -2,7 +2,8 @@
 test can feed the decoders what no ordinary encoder writes -- 15-bit codes, one-code and empty distance sets, length 258 spelled as
 code 284 + 31, references that reach exactly the first byte of the history, hundreds of tiny blocks -- and headers that are INVALID
 for one chosen reason.  The builder computes the plaintext itself, by replaying its own tokens over zdict + output; it never asks a
-decoder.  tests/test_cpu_handbuilt_streams.py proves every vector against the system zlib (the referee) before any GPU test uses it.
+decoder.  tests/test_cpu_handbuilt_streams.py proves every vector against the system zlib (the referee) before any GPU test uses it
+(tests/test_cpu_span_vectors.py the span vectors, tests/test_cpu_finder_vectors.py the finder vectors at the end of this file).
 Holds no test and no GPU code.  Not a conftest: imported by the test files that use it, like deflate_walk.
 
 A stream is a list of blocks: Stored, Fixed or Dynamic.  A block of the two compressed kinds carries a token list:
@@ -827,3 +828,305 @@ def span_vectors():
     v.append(refill_edge_vector(100, beyond=True))
     _span_cache.extend(v)
     return list(v)
+
+
+# ---- vectors for the block finder and the chunk chain behind it: streams without sync points ----------------------------------------
+# What inflate_chunked_once asks of a stream before it takes it is stated once, in finder_gate(); tests/finder_ref.py is the referee
+# of the finder.  Every vector ends in a final stored block of QUIET_TAIL bytes 0xFF, in which no header can start.
+
+QUIET_TAIL = 96
+SYNC = b"\x00\x00\xff\xff"
+WIN = 32768
+FINDER_HCLENS = (5, 12, 19)
+
+
+def quiet_filler(n, seed):
+    """n incompressible bytes without a sync marker, from a fixed seed (drawn again until there is none)"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    while True:
+        data = rng.bytes(n)
+        if SYNC not in data:
+            return data
+
+
+def block_out_lens(blocks):
+    return [len(b.data) if isinstance(b, Stored) else sum(t.length if isinstance(t, M) else 1 for t in b.tokens) for b in blocks]
+
+
+def stored_payload_bits(blocks, final=True):
+    """[(first bit, end bit)] of the payload of every stored block"""
+    hdr, _ = block_bits(blocks, final)
+    return [(8 * (((h + 3 + 7) >> 3) + 4), 8 * (((h + 3 + 7) >> 3) + 4 + len(b.data))) for h, b in zip(hdr, blocks) if isinstance(b, Stored)]
+
+
+def true_dynamic_bits(blocks, final=True):
+    """the header bits of the non-final dynamic blocks: what the finder is there to find"""
+    hdr, _ = block_bits(blocks, final)
+    return [h for i, (h, b) in enumerate(zip(hdr, blocks)) if isinstance(b, Dynamic) and not (final and i == len(blocks) - 1)]
+
+
+def chain_chunks(blocks, listed, start_bit=0):
+    """The host's rule (inflate_chunked_once) on the builder's own numbers: the stream is cut at every block header that is in
+    `listed` (and at its start), the pieces are merged front to back until each has max(32 KiB, total / 4096) bytes of output, a
+    short last one joins its predecessor -> [(header bit, output offset, output length)] of the chunks"""
+    hdr, _ = block_bits(blocks, True, start_bit)
+    lens = block_out_lens(blocks)
+    listed = set(listed) | {hdr[0]}
+    pieces, off = [], 0
+    for h, n in zip(hdr, lens):
+        if h in listed:
+            pieces.append([h, off, 0])
+        pieces[-1][2] += n
+        off += n
+    target = max(WIN, off // 4096)
+    chunks = []
+    for p in pieces:
+        if chunks and chunks[-1][2] < target:
+            chunks[-1][2] += p[2]
+        else:
+            chunks.append(list(p))
+    if len(chunks) > 1 and chunks[-1][2] < target:
+        last = chunks.pop()
+        chunks[-1][2] += last[2]
+    return [tuple(c) for c in chunks]
+
+
+def finder_gate(blob, ncand, chunks):
+    """what inflate_chunked_once demands before it takes a stream without sync points, from the bytes: -> list of what is missing"""
+    miss = []
+    if len(blob) < 65536:
+        miss.append("fewer than 65536 bytes of deflate data")
+    if blob.count(SYNC) >= 8:
+        miss.append("8 or more sync markers: the finder would not run")
+    if ncand < 8:
+        miss.append("fewer than 8 candidates")
+    if len(chunks) < 4 or min(c[2] for c in chunks) < WIN:
+        miss.append("no chain of 4 chunks of 32 KiB")
+    return miss
+
+
+def _quiet_end():
+    return Stored(b"\xff" * QUIET_TAIL)
+
+
+def _mid_hclen_block():
+    """a dynamic block whose code-length code ends at symbol 4: HCLEN = 12"""
+    syms = list(range(65, 96)) + [256]
+    b = Dynamic(spread(syms, [4] * 8 + [5] * 8 + [6] * 16, 257), [0], [65, 80, 95, 66, 94])
+    assert b.hclen == 12 and kraft(b.ll) == 32768
+    return b
+
+
+def _finder_kinds():
+    """the dynamic blocks of the phase vector by name: the three HCLENs of the grid, then the header kinds that phase B has branches for"""
+    by = {v.name: v.blocks for v in valid_vectors()}
+    kinds = [("hclen5", by["hclen5"][0]), ("hclen12", _mid_hclen_block()), ("hclen19", by["hclen19"][0])]
+    for name in ("no_distance_code", "skew_ll_onecode_dist", "nlen286_ndist30", "nlen258_ndist1", "repeat_across_the_sets"):
+        kinds.append((name, by[name][0]))
+    kinds.append(("eob_only", by["two_eob_only_blocks"][0]))
+    assert [k[1].hclen for k in kinds[:3]] == list(FINDER_HCLENS)
+    return kinds
+
+
+def _put_at_phase(blocks, w, block, byte_phase, bit):
+    """append `block` so that its header starts at a byte = byte_phase mod 4 and at bit `bit` of it: a stored block of 1..4 bytes
+    moves the byte, a fixed block of nine literals the bit (82 + j bits)"""
+    shim = 82 + (bit - 2) % 8
+    p0 = ((w.bitlen + 3 + 7) >> 3) + 4                               # the byte behind a stored header written here
+    k = (byte_phase - p0 - (shim >> 3)) % 4 or 4
+    for b in (Stored(_pattern(k, 50 + len(blocks))), Fixed(_nine_bit((bit - 2) % 8)), block):
+        assert not isinstance(b, Dynamic) or ((w.bitlen >> 3) & 3, w.bitlen & 7) == (byte_phase, bit)
+        blocks.append(b)
+        b.write(w, False)
+
+
+def finder_phase_blocks(reach=0, defect=None, filler=33000):
+    """Non-final dynamic blocks at every one of the 32 phases (stream byte mod 4, bit 0..7) for each HCLEN of FINDER_HCLENS, and the
+    other header kinds of _finder_kinds at eight phases each; five stored blocks of incompressible filler between them, so that the
+    true chain has chunks of 32 KiB.  reach: the first block is a fixed one whose first match reaches back `reach` bytes, to the
+    first byte of a dictionary of that size.  defect: blocks (of an invalid vector) spliced in behind the third filler."""
+    kinds = _finder_kinds()
+    work = [(blk, bp, bit) for blk in (k[1] for k in kinds[:3]) for bp in range(4) for bit in range(8)]
+    work += [(blk, (i + bit) & 3, bit) for i, (_, blk) in enumerate(kinds[3:]) for bit in range(8)]
+    blocks, w = [], BitWriter()
+    if reach:
+        blocks.append(Fixed([M(3, reach), 9, M(4, 2)]))
+        blocks[-1].write(w, False)
+    per = -(-len(work) // 5)
+    for part in range(5):
+        blocks.append(Stored(quiet_filler(filler, 300 + part)))
+        blocks[-1].write(w, False)
+        if part == 3 and defect:
+            for b in defect:
+                blocks.append(b)
+                b.write(w, False)
+        for blk, bp, bit in work[part * per:(part + 1) * per]:
+            _put_at_phase(blocks, w, blk, bp, bit)
+    # the last header of the chain, then the end: a resumed call that reaches the end reports this header
+    _put_at_phase(blocks, w, kinds[0][1], 0, 0)
+    return blocks + [_quiet_end()]
+
+
+def finder_phase_census(blocks, start=0):
+    """{(byte & 3, bit & 7, hclen)} of the non-final dynamic headers, from block_bits"""
+    hdr, _ = block_bits(blocks, True, start)
+    return {((h >> 3) & 3, h & 7, b.hclen) for h, b in zip(hdr[:-1], blocks[:-1]) if isinstance(b, Dynamic)}
+
+
+def _generated_text(n, mul):
+    return b"".join(b"record %d of the run, value %d, flag %s\n" % (i * mul % 9973, i * i % 1000003, b"yes" if i % 3 else b"no") for i in range(n))
+
+
+def decoy_inner_stream():
+    """a complete valid raw stream of many small dynamic blocks and a final one: zlib with memLevel 1 over generated text"""
+    import zlib
+    z = zlib.compressobj(6, zlib.DEFLATED, -15, 1)
+    s = z.compress(_generated_text(6000, 31)) + z.flush()          # 228 non-final dynamic blocks in 49 KB: one stored payload
+    assert len(s) <= 65535 and SYNC not in s
+    return s
+
+
+def _header_only(block):
+    """the bytes of a non-final dynamic block up to the end of its code lengths and two more: a header whose tokens are whatever follows"""
+    w = BitWriter()
+    Dynamic(block.ll, block.d, [], eob=False, rle=True).write(w, False)
+    n = (w.bitlen + 7) // 8 + 2
+    return assemble([block], False)[:n]
+
+
+def finder_decoy_blocks():
+    """A true chain of dynamic blocks; between them stored blocks whose payloads hold headers that are none: a whole valid stream
+    of its own, a byte copy of a stretch of this very stream (true headers and all, at the same bit phases), and a valid header in
+    the last 20 bytes of a payload, whose tokens are the blocks behind it."""
+    kinds = dict(_finder_kinds())
+    text = [Dynamic([8] * 240 + [9] * 18 + [10] * 28, [4, 4] + [5] * 28, list(_generated_text(6, 7 + i)) + [M(30, 40), M(258, 33)], rle=True) for i in range(12)]
+    blocks = [Stored(quiet_filler(33000, 400))]
+    blocks += [text[0], Stored(decoy_inner_stream()), text[1]]
+    first = len(blocks)
+    blocks += [text[2], kinds["hclen19"], Fixed(_nine_bit(3)), text[3], kinds["skew_ll_onecode_dist"], Fixed(_nine_bit(6)), text[4], kinds["hclen5"], text[5]]
+    hdr, end = block_bits(blocks, False)
+    so_far = assemble(blocks, False)
+    stretch = so_far[hdr[first] >> 3:]                               # from the byte of text[2]'s header to the end so far
+    assert 200 < len(stretch) < 4000
+    blocks += [Stored(quiet_filler(33000, 401)), text[6], Stored(quiet_filler(9000, 402) + stretch + quiet_filler(24000, 403)), text[7]]
+    tail = _header_only(Dynamic(spread([65, 66, 256], [1, 2, 2], 257), [0], [65] * 400, rle=True))
+    assert 12 <= len(tail) <= 20
+    blocks += [Stored(quiet_filler(33000, 404) + tail), text[8], text[9], Stored(quiet_filler(33000, 405)), text[10], text[11]]
+    return blocks + [_quiet_end()]
+
+
+WINDOW_P = (0, 1, 2, 1023, 1024, 1025, 2000)                # where in its chunk an edge block's probes start
+WINDOW_W = (1, 1023, 1024, 1025, 32767, 32768)               # ... and how far back they reach: around the chunk's first byte and the 1 024-symbol ring
+WINDOW_ODD = (32769, 40001, 65537)
+_WIN_LL, _WIN_D = [8] * 240 + [9] * 18 + [10] * 28, [4, 4] + [5] * 28
+
+
+def _relay(n):
+    """n bytes, all from matches at distance 32768 (n >= 3), the longest first"""
+    toks = [M(258, WIN)] * (n // 258)
+    r = n % 258
+    if 0 < r < 3:                                               # no match is shorter than 3: shorten the last long one
+        toks[-1:] = [M(255 + r, WIN), M(3, WIN)]
+    elif r:
+        toks.append(M(r, WIN))
+    return toks
+
+
+def relay_block():
+    toks = [M(258, WIN)] * 126 + [M(257, WIN), M(3, WIN)]
+    return Dynamic(_WIN_LL, _WIN_D, toks, rle=True)
+
+
+def edge_block(p, w, total, seed):
+    """One chunk of `total` bytes: p bytes of lead-in, M(3, w) and M(258, w) at chunk offset p, three marker bytes and an overlapping
+    M(258, 2), a 258-copy whose source begins 100 bytes in front of the chunk -- at offset 100 where the lead-in has room for it,
+    else behind the probes -- and relay matches to the end.  -> (block, {what: chunk offset})"""
+    lits = list(_pattern(110, seed))
+    toks, at = [], {}
+    if p >= 358:
+        toks += lits[:100] + [M(258, 200)] + (_relay(p - 358) if p - 358 >= 3 else lits[100:100 + p - 358])
+        at["straddle"] = 100
+    else:
+        toks += lits[:p]
+    at["probe"] = p
+    toks += [M(3, w), M(258, w), M(3, WIN), M(258, 2)]
+    op = p + 3 + 258 + 3 + 258
+    at["overlap"] = op - 258
+    if "straddle" not in at:
+        toks.append(M(258, op + 100))
+        at["straddle"] = op
+        op += 258
+    toks += _relay(total - op)
+    return Dynamic(_WIN_LL, _WIN_D, toks, rle=True), at
+
+
+def finder_window_blocks(nrelay=90):
+    """72 KiB of stored random bytes, `nrelay` relay blocks, the 42 edge blocks (every p with every w), the quiet end.  Every
+    dynamic block makes a chunk of its own; every byte behind the seed that is not one of the edge blocks' few literals reaches
+    the output only through the marker windows.  -> (blocks, [the edge blocks' offsets])"""
+    seed = quiet_filler(72 << 10, 500)
+    blocks = [Stored(seed[:36 << 10]), Stored(seed[36 << 10:])]
+    blocks += [relay_block() for _ in range(nrelay)]
+    about = []
+    for i, (p, w) in enumerate((p, w) for p in WINDOW_P for w in WINDOW_W):
+        total = WINDOW_ODD[(i // 5) % 3] if i % 5 == 2 else WIN
+        b, at = edge_block(p, w, total, 600 + i)
+        blocks.append(b)
+        about.append((p, w, total, at))
+    return blocks + [_quiet_end()], about
+
+
+FINDER_DEFECTS = ("unused_code_of_one_code_distance_set", "fixed_distance_code_30", "incomplete_distance_set")
+
+
+def finder_invalid_vectors():
+    """the phase vector with one defective block in its chain, behind more than two chunks -> [Vector] (expect = DATA)"""
+    bad = {v.name: v.blocks for v, _ in invalid_vectors()}
+    return [Vector("finder_phase_" + name, assemble(finder_phase_blocks(defect=bad[name])), b"", DATA, None) for name in FINDER_DEFECTS]
+
+
+_finder_cache = {}
+
+
+def finder_vectors():
+    """{name: Vector} of the three valid finder vectors (blocks kept); built once per process"""
+    if not _finder_cache:
+        for name, blocks in (("finder_phase", finder_phase_blocks()), ("finder_decoy", finder_decoy_blocks()), ("finder_window", finder_window_blocks()[0])):
+            _finder_cache[name] = _vec(name, blocks)
+    return dict(_finder_cache)
+
+
+def gzip_member(body, plain, name_len=0):
+    """a gzip member around a deflate body; an FNAME field of name_len characters puts the first deflate byte at offset 11 + name_len"""
+    import struct
+    import zlib
+    head = b"\x1f\x8b\x08" + (b"\x08" if name_len else b"\x00") + bytes(4) + b"\x00\xff" + ((b"n" * name_len + b"\x00") if name_len else b"")
+    return head + body + struct.pack("<II", zlib.crc32(plain), len(plain) & 0xFFFFFFFF)
+
+
+FINDER_DICTS = (32768, 100, 1)
+
+
+def finder_resumed_vector(reach):
+    """the phase vector behind a dictionary of `reach` bytes whose first byte its first match reaches"""
+    blocks = finder_phase_blocks(reach=reach)
+    return _vec("finder_phase_reach%d" % reach, blocks, zdict=_pattern(reach, 700 + reach))
+
+
+def finder_cuts(blocks, start=0):
+    """Six places to cut the phase vector written from bit `start` on, all in its last third -> {what: bytes kept}.  The places are
+    found from block_bits: inside the tokens of a dynamic block (two bytes short of its end), inside a dynamic header (three bytes
+    in), in the middle of the last filler's payload, on a block boundary that is a byte boundary (behind a stored block), one
+    byte behind it, and one byte short of the end."""
+    hdr, end = block_bits(blocks, True, start)
+    big = [i for i, b in enumerate(blocks) if isinstance(b, Stored) and len(b.data) > 4096]
+    last = big[-1]
+    dyn = [i for i in range(last + 1, len(blocks) - 1) if isinstance(blocks[i], Dynamic)]
+    long_dyn = [i for i in dyn if len(blocks[i].tokens) >= 40]
+    small = [i for i in range(last + 1, len(blocks) - 1) if isinstance(blocks[i], Stored)]
+    i, j, s = long_dyn[len(long_dyn) // 2], dyn[len(dyn) // 2], small[len(small) // 2]
+    assert hdr[s + 1] % 8 == 0
+    cuts = {"in_tokens": (hdr[i + 1] >> 3) - 2, "in_header": (hdr[j] >> 3) + 3, "in_stored": (hdr[last] >> 3) + 5 + len(blocks[last].data) // 2,
+            "on_boundary": hdr[s + 1] >> 3, "behind_boundary": (hdr[s + 1] >> 3) + 1, "short_of_end": ((end + 7) >> 3) - 1}
+    return cuts

@@ -23,6 +23,8 @@ def test_library_exports_every_declared_symbol():
     missing = [s for s in declared if not hasattr(L, s)]
     assert not missing, missing
     assert sorted(_lib.SYMBOLS) == declared
+    assert {"zngamd_span_stats", "zngamd_bgzf_stats", "zngamd_chunk_stats"} <= set(declared)      # the counters the GPU tests read
+    assert hasattr(_lib.Context, "chunk_stats")
     assert L.zngamd_version().startswith(b"zng_amd")
     # the library must not depend on the oracle or on torch
     import subprocess

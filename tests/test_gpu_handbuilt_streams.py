@@ -11,6 +11,9 @@ oracle's.  Verdicts: 1 = the stream ended, -3 = data error, -5 = wants more inpu
                                   of the two-pass branch (pieces of 3 KiB); markers that cross a chunk edge
     the streaming object          zlib_ng.decompressobj(-15) fed in halves and byte by byte
     za_k_inflate_spans            the span decoder of the seek-point index: tests/test_gpu_span_handbuilt.py
+    za_k_find_blocks_a / _b       the block finder of a stream without sync points, za_k_chunk_count and the marker decoder behind it,
+                                  compose / chain / resolve over more than two groups of chunks, ctx.inflate_resume at 64 KiB and more:
+                                  tests/test_gpu_finder_handbuilt.py
 The valid half of a decoder's vectors runs before its invalid half (two test functions)."""
 import gzip
 import struct
