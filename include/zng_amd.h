@@ -1502,7 +1502,12 @@ uint64_t zngamd_indexed_units(zngamd_ctx *ctx, int reset);
  * deflate call to the host.  what: 0 links of table A (u16) 1 best(u32, as the parse kernel read it: behind the dynamic
  * programme on levels 4-9) 2 tokens(u32) 3 seg_ntok(u32) 4 hist(u32) 5 codes(u32) 6 seg_bits(u32) 7 plan(4 x u32)
  * 8 chunk index(u32) 9 / 10 links of tables B / C (u16) 11 best as the search left it (u32) 12 the dynamic programme's cost
- * table (258 x u32, levels 4-9).  Stages 0, 9, 10 and 11 exist only for calls made after zngamd_debug_keep(ctx, 1): without it the
+ * table (258 x u32, levels 4-9).  Forms: stages 1 and 11 come back as length << 16 | distance, 0 = no match (the kernels keep
+ * distance - 1 | length << 15 | the position's byte << 24; zngamd_debug_fetch converts and drops the byte); stage 2 is the
+ * kernels' own token word (a match: bit 31 | length code << 26 | length extra << 21 | distance code << 16 | distance extra; else
+ * one to three literals in bits 0..23, their number - 1 in bits 24..25); every other stage is the kernels' own array.  Under
+ * Z_FIXED stage 12 holds the ESTIMATED table: the programme puts the fixed code's costs over it when it loads it.
+ * Stages 0, 9, 10 and 11 exist only for calls made after zngamd_debug_keep(ctx, 1): without it the
  * token words are written over the link tables (a third of the workspace saved), and nothing copies the search results aside. */
 int zngamd_debug_keep(zngamd_ctx *ctx, int on);
 int zngamd_debug_fetch(zngamd_ctx *ctx, int what, uint32_t unit, void *host_dst, size_t bytes);

@@ -2710,7 +2710,8 @@ __global__ __launch_bounds__(64) void za_k_plan(const ZaUnit *__restrict__ units
     if (cost_fix <= bestc) { bestc = cost_fix; btype = 1; }
     if (cost_sto <= bestc) { bestc = cost_sto; btype = 0; }
     // Z_FIXED: never a dynamic block -- fixed, or stored where stored beats BOTH Huffman forms (zlib's _tr_flush_block: stored if
-    // stored_len + 4 <= min(opt_lenb, static_lenb), else static under Z_FIXED)
+    // stored_len + 4 <= min(opt_lenb, static_lenb), else static under Z_FIXED).  Where dynamic beat stored and stored beats fixed
+    // the unit is LARGER than its stored form, up to 9 bits a byte: the host's bound for a packed stream allows for it.
     if (fixed_only && btype == 2) btype = 1;
     ZA_PLAN_T(7);
     plan.btype = (uint32_t)btype;

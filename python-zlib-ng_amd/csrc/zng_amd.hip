@@ -1073,9 +1073,13 @@ static int deflate_host_common(zngamd_ctx *c, uint64_t in_len, const zngamd_bloc
     if (r) return r;
     const uint32_t n = (uint32_t)hu.size();
     // Packed: every unit's size is planned before it is packed and the packer writes at its final offset (no slots, no gather).
-    // A unit is never larger than its stored form: its bytes + 5 per stored chunk of 65 535 + an empty stored block behind it.
+    // A unit is never larger than its stored form: its bytes + 5 per stored chunk of 65 535 + an empty stored block behind it --
+    // but for Z_FIXED, which takes a fixed block wherever a dynamic one would have won, also where stored beats fixed: at most 9
+    // bits a byte (a literal is 8 or 9 bits, and a match of l bytes at most 7 + 5 + 13 extra bits for l = 3, 4, at most 8 + 5 + 5 + 13
+    // for longer ones: never more than 9 l)
+    const bool fixed_only = strategy_of(blocks, n_blocks) == ZNGAMD_STRATEGY_FIXED;
     uint64_t bound = 64;
-    for (const ZaUnit &u : hu) bound += (uint64_t)u.in_len + 32u;
+    for (const ZaUnit &u : hu) bound += (uint64_t)u.in_len + (fixed_only ? u.in_len / 8u : 0u) + 32u;
     // Everything the host wants back lies in ONE device buffer, the results in front of the stream -- the stream's size, the units'
     // sizes, CRCs and pack status, the checksum kernel's partial sums -- so that a small call fetches results and bytes with one
     // copy (r06: five copies of a few bytes each, staged one after the other, cost a small call 60 us):
