@@ -621,6 +621,16 @@ static int strategy_of(const zngamd_block *blocks, uint32_t n_blocks) { return n
 static uint32_t unit_size_of(const zngamd_block &b) { return (b.flags & ZNGAMD_FLAG_UNITS16K) ? ZA_SMALL_UNIT : (uint32_t)ZA_MAX_UNIT; }
 static uint32_t units_of(const zngamd_block &b) { const uint64_t U = unit_size_of(b); return b.len == 0 ? 1u : (uint32_t)(((uint64_t)b.len + U - 1) / U); }
 
+// The most bytes a unit of in_len bytes takes in a packed stream under the call's strategy (every host bound is a
+// sum of these).  A unit is never larger than its stored form: its bytes + 5 per stored chunk of 65 535 (three in a full unit) +
+// an empty stored block behind it -- but for Z_FIXED, which takes a fixed block wherever a dynamic one would have won, also where
+// stored beats fixed: at most 9 bits a byte (a literal is 8 or 9 bits, and a match of l bytes at most 7 + 5 + 13 extra bits for
+// l = 3, 4, at most 8 + 5 + 5 + 13 for longer ones: never more than 9 l), so ceil((3 + 9 n + 7 + 3) / 8) + 4 bytes.
+static uint64_t unit_bound(uint32_t in_len, int strategy)
+{
+    return (uint64_t)in_len + (strategy == ZNGAMD_STRATEGY_FIXED ? in_len / 8u : 0u) + 32u;
+}
+
 uint32_t zngamd_count_units(const zngamd_block *blocks, uint32_t n_blocks)
 {
     uint64_t t = 0;
@@ -1073,13 +1083,10 @@ static int deflate_host_common(zngamd_ctx *c, uint64_t in_len, const zngamd_bloc
     if (r) return r;
     const uint32_t n = (uint32_t)hu.size();
     // Packed: every unit's size is planned before it is packed and the packer writes at its final offset (no slots, no gather).
-    // A unit is never larger than its stored form: its bytes + 5 per stored chunk of 65 535 + an empty stored block behind it --
-    // but for Z_FIXED, which takes a fixed block wherever a dynamic one would have won, also where stored beats fixed: at most 9
-    // bits a byte (a literal is 8 or 9 bits, and a match of l bytes at most 7 + 5 + 13 extra bits for l = 3, 4, at most 8 + 5 + 5 + 13
-    // for longer ones: never more than 9 l)
-    const bool fixed_only = strategy_of(blocks, n_blocks) == ZNGAMD_STRATEGY_FIXED;
+    // The stream's bound is the sum of its units' (unit_bound: a unit's stored form, under Z_FIXED nine bits a byte).
+    const int strategy = strategy_of(blocks, n_blocks);
     uint64_t bound = 64;
-    for (const ZaUnit &u : hu) bound += (uint64_t)u.in_len + (fixed_only ? u.in_len / 8u : 0u) + 32u;
+    for (const ZaUnit &u : hu) bound += unit_bound(u.in_len, strategy);
     // Everything the host wants back lies in ONE device buffer, the results in front of the stream -- the stream's size, the units'
     // sizes, CRCs and pack status, the checksum kernel's partial sums -- so that a small call fetches results and bytes with one
     // copy (r06: five copies of a few bytes each, staged one after the other, cost a small call 60 us):
@@ -1986,7 +1993,7 @@ static int deflate_batch_locked(zngamd_ctx *c, const uint8_t *d_in, uint64_t in_
         std::vector<uint32_t> first(m + 1, nu);
         for (uint32_t u = nu; u-- > 0;) first[hu[u].block] = u;
         uint64_t bound = 64;
-        for (const ZaUnit &u : hu) bound += (uint64_t)u.in_len + 32u;
+        for (const ZaUnit &u : hu) bound += unit_bound(u.in_len, strategy);
         HIPCHK(c, c->bt_def.ensure(bound)); HIPCHK(c, c->bt_uoff.ensure(nu)); HIPCHK(c, c->bt_ulen.ensure(nu)); HIPCHK(c, c->bt_ucrc.ensure(nu));
         HIPCHK(c, c->bt_total.ensure(1)); HIPCHK(c, c->bt_first.ensure(m + 1)); HIPCHK(c, c->bt_items.ensure(n));
         HIPCHK(c, hipMemcpyAsync(c->bt_first.p, first.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, c->stream));
@@ -2075,11 +2082,14 @@ try {
     if (r) return r;
     BatchDict bd;
     if (dict) { r = batch_dict_upload(c, dict, dict_len, dictid, &bd); if (r) return r; }
-    // the output's bound: every item's packed deflate (32 bytes a 16 KiB unit, more than 128 KiB units need) and its framing
+    // the output's bound: every item's framing (18 bytes at most, gzip's) and the bound of each unit it is cut into (unit_bound:
+    // under Z_FIXED a unit can be an eighth larger than its bytes) -- units of 16 KiB up to 128 KiB, of 128 KiB beyond; with a
+    // dictionary every item goes in units of 128 KiB, which need no more than the smaller ones are given here
     uint64_t cap = 64 + (uint64_t)n * 18;
     for (uint32_t i = 0; i < n; i++) {
-        const uint64_t U = items[i].in_len <= ZA_MAX_UNIT ? ZA_SMALL_UNIT : ZA_MAX_UNIT;
-        cap += items[i].in_len + 32 * std::max<uint64_t>(1, (items[i].in_len + U - 1) / U);
+        const uint32_t U = items[i].in_len <= ZA_MAX_UNIT ? ZA_SMALL_UNIT : (uint32_t)ZA_MAX_UNIT;
+        const uint32_t full = items[i].in_len / U, rest = items[i].in_len - full * U;
+        cap += full * unit_bound(U, strategy) + (rest || !full ? unit_bound(rest, strategy) : 0u);
     }
     HIPCHK(c, c->bt_out.ensure(cap)); HIPCHK(c, c->bt_res.ensure(n));
     r = deflate_batch_locked(c, c->st_in.p, in_len, items, n, level, wbits, strategy, dict ? &bd : nullptr, c->bt_out.p, cap, c->bt_res.p, total);

@@ -266,13 +266,21 @@ def decompress(items, wbits=MAX_WBITS, *, errors="raise", zdict=None):
 
 
 # ---- device-resident forms
-def _frame_bound(lengths, wbits, zdict=None):
+def _unit_bound(n, strategy):
+    """the most bytes a unit of n bytes takes in a packed stream: unit_bound of zng_amd.hip"""
+    return n + (n // 8 if strategy == _lib.STRATEGY_FIXED else 0) + 32
+
+
+def _frame_bound(lengths, wbits, zdict=None, strategy=Z_DEFAULT_STRATEGY):
+    """room that compress_dev's output never exceeds: every item's framing and the bound of each unit it is cut into (units of
+    16 KiB up to 128 KiB, of 128 KiB beyond)"""
     kind, _ = _z._container(wbits)
     ovh = (6 if zdict is None else 10) if kind == "zlib" else 18 if kind == "gzip" else 0
     total = 64
     for ln in lengths:
         u = 16384 if ln <= 131072 else 131072
-        total += ln + 32 * max(1, -(-ln // u)) + ovh
+        full, rest = divmod(ln, u)
+        total += full * _unit_bound(u, strategy) + (_unit_bound(rest, strategy) if rest or not full else 0) + ovh
     return total
 
 
@@ -296,7 +304,7 @@ def compress_dev(ctx, d_in, offsets, lengths, level=Z_DEFAULT_COMPRESSION, wbits
     for i in range(n):
         items[i].in_off = int(offsets[i])
         items[i].in_len = int(lengths[i])
-    cap = _frame_bound([int(x) for x in lengths], wbits, zdict)
+    cap = _frame_bound([int(x) for x in lengths], wbits, zdict, strategy)
     out = devmem.DeviceBuffer(ctx, cap)
     d_res = devmem.DeviceBuffer(ctx, 16 * max(n, 1))
     r, total = ctx.deflate_batch_dev(d_in.ptr, in_len, items, n, level, wbits, strategy, out.ptr, cap, d_res.ptr, zdict=zdict)
