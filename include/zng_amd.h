@@ -1073,6 +1073,133 @@ int zngamd_dedup_keys_dev(zngamd_ctx *ctx, const zngamd_bgzf_key_row *d_keys, ui
 int zngamd_dedup_keys(zngamd_ctx *ctx, const zngamd_bgzf_key_row *keys, uint64_t n, uint64_t *first, uint32_t *count,
                       zngamd_dedup_totals *totals);
 
+/* ---- BGZF sort (zlib_ng_amd/bgzf.py: sort_key_records, sort_keys, permute_records, sort_records).  Three
+ * calls, each usable alone: a key per record whose memcmp order is the order wanted, a stable sort of any such keys, and records
+ * written to the places the caller names.  The record model of zngamd_bgzf_key_records applies (record_lines k, first_byte, _FINAL, the
+ * open tail, the cover contract; a line the record lacks is an empty body).
+ * The key.  conf holds 0 .. 4 parts; the key is the parts' bytes one behind the other, padded with 0x00 to W = the next multiple of 8
+ * (W <= 256; W = 0 with no part: the lengths alone).  A part names a field -- line `line` of the record, whole (column = -1) or its
+ * 0-based field `column` when the body is cut at the byte `sep`; a line the record lacks or a column the line lacks is an empty field --
+ * and how its bytes are made:
+ *   _SORT_BYTES   width bytes (8 .. 128, a multiple of 8): field[first : first + width], padded with 0x00; with _IGNORE_CASE a .. z
+ *                 become A .. Z.  A field longer than first + width is fault 3 unless the part has _TRUNCATE.
+ *   _SORT_NUMBER  8 bytes, big-endian: the field as an unsigned decimal number; leading zeros are allowed.  An empty field, a byte that
+ *                 is no digit, or a value above 2^64 - 1 is fault 2.
+ *   _SORT_LENGTH  4 bytes, big-endian: the length of the field.
+ * _REVERSE complements the part's bytes.  A record whose first byte is meta_byte (-1: none) gets the all-zero key and no fault of a
+ * part: with the stable sort the header lines of a VCF stay in front and in order.
+ * Rows.  rows: row r is the W key bytes of record r, row-major; lengths[r] (uint32_t): the record's bytes as they lie in the text --
+ * except that the last record of a _FINAL text whose last line lacks its delimiter counts one byte more: zngamd_bgzf_place_records
+ * writes that delimiter, so a reordered file never glues two lines together.  This is the one deviation from "the output's bytes
+ * are a permutation of the input's records".
+ * totals: seen, bytes_in, tail_off, covered, short_lines and the fault words as zngamd_bgzf_key_totals has them; key_width = W; bad:
+ * 1 a first_byte violation, 2 not a number, 3 a _SORT_BYTES field too long (max_field: the longest such field of the window, so
+ * that a caller can say which width would do).  The smallest record at fault is reported (of two faults at one record the one
+ * with the lower number); with bad set the rows are not to be used.  flags: _FINAL; anything else is ZNGAMD_E_ARG.
+ * ZNGAMD_BUF_ERROR: rows_cap < seen: nothing is written, the totals are valid.  Hostile arguments -- conf NULL or a field out of range
+ * (record_lines, first_byte, meta_byte, n_parts > 4, line, column < -1, kind, width, a part's flags), a reserved word set, W > 256,
+ * flags, delim, totals NULL, lengths NULL or rows NULL with W != 0 (and, in the host form, no alloc) -- are ZNGAMD_E_ARG before the
+ * context is touched.  Device memory beside the tiles: 8 bytes per line of the text, and in the host form W + 4 bytes per record. */
+#define ZNGAMD_BGZF_SORT_BYTES  0u
+#define ZNGAMD_BGZF_SORT_NUMBER 1u
+#define ZNGAMD_BGZF_SORT_LENGTH 2u
+#define ZNGAMD_BGZF_SORT_REVERSE     1u
+#define ZNGAMD_BGZF_SORT_IGNORE_CASE 2u
+#define ZNGAMD_BGZF_SORT_TRUNCATE    4u
+#define ZNGAMD_BGZF_SORT_MAX_PARTS 4u
+#define ZNGAMD_SORT_MAX_WIDTH 256u
+typedef struct {
+    int32_t  line;          /* 0 <= line < record_lines */
+    int32_t  column;        /* -1: the whole body; otherwise the 0-based field between separators */
+    uint32_t width;         /* _SORT_BYTES: 8 .. 128, a multiple of 8; otherwise 0 */
+    uint32_t first;         /* _SORT_BYTES: where the keyed bytes begin in the field; otherwise 0 */
+    uint16_t flags;         /* ZNGAMD_BGZF_SORT_REVERSE | _IGNORE_CASE | _TRUNCATE (the last two: _SORT_BYTES only) */
+    uint8_t  kind;          /* ZNGAMD_BGZF_SORT_BYTES, _NUMBER, _LENGTH */
+    uint8_t  sep;           /* the separator of the columns */
+} zngamd_bgzf_sort_part;                                                                          /* 20 B */
+typedef struct {
+    uint32_t record_lines;  /* k, 1 .. 64 */
+    int32_t  first_byte;    /* 0 .. 255; -1: no check */
+    int32_t  meta_byte;     /* 0 .. 255; -1: none */
+    uint32_t n_parts;       /* 0 .. 4 */
+    zngamd_bgzf_sort_part part[4];
+    uint32_t reserved[8];   /* 0; so are the parts at and behind n_parts */
+} zngamd_bgzf_sort_conf;                                                                          /* 128 B */
+typedef struct {
+    uint64_t seen;            /* records of the text that were keyed (the open tail is not one of them) */
+    uint64_t bytes_in;        /* bytes of the records as they lie in the text */
+    uint64_t max_field;       /* bad = 3: the longest field that was too long */
+    uint64_t tail_off;        /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;      /* bad != 0: the number of the record at fault */
+    uint64_t bad_src;         /*           and where it starts in the scratch */
+    uint32_t covered;         /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;     /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;             /* 0; 1: the first byte is not first_byte; 2: not a number; 3: a field too long */
+    uint32_t key_width;       /* W */
+} zngamd_bgzf_sort_key_totals;                                                                    /* 64 B */
+int zngamd_bgzf_sort_key_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                     uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_sort_conf *conf,
+                                     uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, uint8_t *d_rows,
+                                     uint32_t *d_lengths, uint64_t rows_cap, zngamd_bgzf_sort_key_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; status, the rows and the lengths come back.  With alloc (rows = lengths =
+ * NULL, rows_cap 0) the caller's memory is asked for once seen is known and not 0, in the order rows (seen * W bytes; not with W = 0),
+ * lengths (seen * 4 bytes); NULL from it: ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_sort_key_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                                 uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_sort_conf *conf,
+                                 uint64_t record_base, int32_t *status, uint8_t *rows, uint32_t *lengths, uint64_t rows_cap,
+                                 zngamd_alloc_fn alloc, void *user, zngamd_bgzf_sort_key_totals *totals);
+
+/* zngamd_sort_keys: n rows of `width` bytes (a multiple of 8, 8 .. 256), row-major, of any origin.  order[j] (uint32_t) = the row that
+ * stands j-th in memcmp order; equal rows come in ascending row number (the sort is stable), so the result depends on the rows
+ * alone.  rank (NULL, or n entries) is the inverse: rank[order[j]] = j.  An LSD radix sort over bytes, the last byte first; a byte
+ * position that is the same in every row (the OR of the rows equals their AND there) gets no pass, so the cost follows the bytes
+ * that vary, not the width.  The rows are never written.  The device form's work area is zngamd_sort_scratch_bytes(n, width)
+ * bytes (0 for n > ZNGAMD_SORT_MAX_KEYS or a width out of range), 8-byte aligned, as d_keys is.  n = 0 launches nothing.
+ * ZNGAMD_E_ARG before the context is touched: order NULL or keys NULL with n != 0, n > ZNGAMD_SORT_MAX_KEYS, a width out of range, a
+ * work area or d_keys that is NULL with n != 0 or not 8-byte aligned.  ZNGAMD_BUF_ERROR: scratch_cap below
+ * zngamd_sort_scratch_bytes(n, width); nothing is launched. */
+#define ZNGAMD_SORT_MAX_KEYS (1ull << 30)
+uint64_t zngamd_sort_scratch_bytes(uint64_t n, uint32_t width);
+int zngamd_sort_keys_dev(zngamd_ctx *ctx, const uint8_t *d_keys, uint64_t n, uint32_t width, void *d_scratch, uint64_t scratch_cap,
+                         uint32_t *d_order, uint32_t *d_rank);
+/* Host-buffer form: the rows are uploaded, the work area is the context's, order and rank (NULL or n entries) come back. */
+int zngamd_sort_keys(zngamd_ctx *ctx, const uint8_t *keys, uint64_t n, uint32_t width, uint32_t *order, uint32_t *rank);
+
+/* zngamd_bgzf_place_records: the window is decoded as in every record call, and record record_base + r is copied whole to
+ * d_out + dst[r]; dst[r] = ZNGAMD_BGZF_PLACE_SKIP: the record is not in this pass.  length[r] is what zngamd_bgzf_sort_key_records
+ * reported: where it counted the delimiter an open last line lacks, the delimiter is written behind the record.  Nothing is written
+ * outside [dst[r], dst[r] + length[r]), and d_out (out_cap bytes) is DEVICE memory in both forms.  Faults (the smallest record at
+ * fault; a record at fault is not copied, the others are): bad = 1 a first_byte violation; 4 the record's length in the text is not
+ * length[r] -- the file changed between the passes; 5 dst[r] + length[r] > out_cap.  Only the first min(n, seen) entries of the
+ * arrays are read; seen > n: labels_short = 1 and nothing is written, as in zngamd_bgzf_partition_records; n > seen is no fault: the
+ * next call takes dst + seen.  totals: seen, placed (records copied), placed_bytes (the sum of their length[r]) and the rest as
+ * zngamd_bgzf_partition_totals has it.  flags: _FINAL.  Hostile arguments -- dst or length NULL with n != 0, d_out NULL with
+ * out_cap != 0, record_lines / first_byte, delim, flags, totals NULL -- are ZNGAMD_E_ARG before the context is touched. */
+#define ZNGAMD_BGZF_PLACE_SKIP (~0ull)
+typedef struct {
+    uint64_t seen;          /* records of the text that were decided (the open tail is not one of them) */
+    uint64_t placed;        /* records copied */
+    uint64_t placed_bytes;  /* and the bytes written for them */
+    uint64_t tail_off;      /* scratch offset where the open record starts; text_end when there is none */
+    uint64_t bad_record;    /* bad != 0: the number of the record at fault */
+    uint64_t bad_src;       /*           and where it starts in the scratch */
+    uint32_t covered;       /* 1: decoded blocks cover the text and the figures describe it */
+    uint32_t short_lines;   /* with _FINAL: lines of a short last record; 0 when the last record is whole */
+    uint32_t bad;           /* 0; 1: the first byte is not first_byte; 4: the length is not length[r]; 5: the record does not fit */
+    uint32_t labels_short;  /* 1: the text holds more records than n */
+} zngamd_bgzf_place_totals;                                                                       /* 64 B */
+int zngamd_bgzf_place_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                  uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, uint32_t record_lines,
+                                  int32_t first_byte, uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status,
+                                  const uint64_t *d_dst, const uint32_t *d_length, uint64_t n, void *d_out, uint64_t out_cap,
+                                  zngamd_bgzf_place_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; dst and length are host memory, of which min(n, seen) entries are
+ * uploaded once the line count is known; status comes back; d_out stays a device pointer. */
+int zngamd_bgzf_place_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                              uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, uint32_t record_lines,
+                              int32_t first_byte, uint64_t record_base, int32_t *status, const uint64_t *dst, const uint32_t *length,
+                              uint64_t n, void *d_out, uint64_t out_cap, zngamd_bgzf_place_totals *totals);
+
 /* ---- BGZF overlap (zlib_ng_amd/bgzf.py: overlap_records).  The one preprocessing step that needs both mates
  * of a pair at once: where the two reads of a pair lie over each other, and with that the adapter read-through cut off, bases
  * corrected and the pair merged into one read -- fastp's overlap analysis (-c, -m), bbmerge, PEAR, FLASH, vsearch

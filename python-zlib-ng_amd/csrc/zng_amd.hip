@@ -16,6 +16,7 @@
 #include "za_trim.hip"
 #include "za_qc.hip"
 #include "za_dedup.hip"
+#include "za_sort.hip"
 #include "za_overlap.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
@@ -204,6 +205,9 @@ struct zngamd_ctx {
     // records keyed and keys resolved (za_dedup.hip, section 5f.7; line starts are gr_start): the key pass's totals and first fault; the host
     // forms' rows, table, first[] and count[]
     DevBuf<unsigned long long> dd_tot, dd_first; DevBuf<ZaKeyRow> dd_row; DevBuf<uint8_t> dd_tab; DevBuf<uint32_t> dd_count;
+    // records in another order (za_sort.hip, section 5f.9; line starts are gr_start): the totals and faults of the key and place passes; the
+    // host forms' rows and lengths, keys, work area, order[] and rank[], dst[]
+    DevBuf<unsigned long long> so_tot, so_key, so_tab, so_dst; DevBuf<uint8_t> so_row; DevBuf<uint32_t> so_len, so_ord, so_rank;
     // pairs laid over each other (za_overlap.hip, section 5f.8; line starts, lengths, table, labels and the totals' words are gr_start, cl_len,
     // cl_tab, pt_lab and tr_tot): the overlap rows
     DevBuf<ZaOvlRow> ov_row;
@@ -363,6 +367,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->tr_row.release(); c->tr_drop.release(); c->tr_tot.release(); c->ov_row.release();
     c->qc_tot.release(); c->qc_tab.release(); c->qc_row.release();
     c->dd_tot.release(); c->dd_first.release(); c->dd_row.release(); c->dd_tab.release(); c->dd_count.release();
+    c->so_tot.release(); c->so_key.release(); c->so_tab.release(); c->so_dst.release(); c->so_row.release(); c->so_len.release(); c->so_ord.release(); c->so_rank.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -4822,6 +4827,302 @@ try {
     if (first) HIPCHK(c, hipMemcpyAsync(first, c->dd_first.p, (size_t)n * 8u, hipMemcpyDeviceToHost, c->stream));
     if (count) HIPCHK(c, hipMemcpyAsync(count, c->dd_count.p, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- records in another order (za_sort.hip)
+// the key's width W for a judged configuration: the parts' bytes, rounded up to 8
+static uint32_t sort_key_width(const zngamd_bgzf_sort_conf &cf)
+{
+    uint32_t w = 0;
+    for (uint32_t p = 0; p < cf.n_parts; p++) w += cf.part[p].kind == ZNGAMD_BGZF_SORT_BYTES ? cf.part[p].width : cf.part[p].kind == ZNGAMD_BGZF_SORT_NUMBER ? 8u : 4u;
+    return (w + 7u) & ~7u;
+}
+
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool sort_key_args_ok(int delim, uint32_t flags, const zngamd_bgzf_sort_conf *cf, const uint8_t *rows, const uint32_t *lengths, bool alloc,
+                             const zngamd_bgzf_sort_key_totals *totals)
+{
+    if (!totals || !cf || (flags & ~ZNGAMD_BGZF_GREP_FINAL) || delim < 0 || delim > 255) return false;
+    if (!grep_records_ok(cf->record_lines, -1, cf->first_byte) || cf->meta_byte < -1 || cf->meta_byte > 255 || cf->n_parts > ZNGAMD_BGZF_SORT_MAX_PARTS) return false;
+    for (uint32_t v : cf->reserved) if (v) return false;
+    uint32_t w = 0;
+    for (uint32_t p = 0; p < ZNGAMD_BGZF_SORT_MAX_PARTS; p++) {
+        const zngamd_bgzf_sort_part &q = cf->part[p];
+        if (p >= cf->n_parts) {
+            if (q.line || q.column || q.width || q.first || q.flags || q.kind || q.sep) return false;
+            continue;
+        }
+        if (q.line < 0 || q.line >= (int32_t)cf->record_lines || q.column < -1 || q.kind > ZNGAMD_BGZF_SORT_LENGTH) return false;
+        const bool bytes = q.kind == ZNGAMD_BGZF_SORT_BYTES;
+        if (q.flags & ~(bytes ? ZNGAMD_BGZF_SORT_REVERSE | ZNGAMD_BGZF_SORT_IGNORE_CASE | ZNGAMD_BGZF_SORT_TRUNCATE : ZNGAMD_BGZF_SORT_REVERSE)) return false;
+        if (bytes ? (q.width < 8u || q.width > 128u || (q.width & 7u)) : (q.width || q.first)) return false;
+        w += bytes ? q.width : q.kind == ZNGAMD_BGZF_SORT_NUMBER ? 8u : 4u;
+    }
+    if (w > ZNGAMD_SORT_MAX_WIDTH) return false;
+    return alloc || (lengths && (rows || !w));
+}
+
+// The lines pass for the delimiters alone, [the host waits for the line count], lines, keys, close, [the host waits for the totals].
+// own: the rows and lengths go to so_row and so_len; otherwise to d_rows and d_len when rows_cap holds them, and nowhere (*rows_short)
+// when it does not.
+static int bgzf_sort_key_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, const zngamd_bgzf_sort_conf &cf, uint64_t record_base, bool own, uint8_t *d_rows,
+                             uint32_t *d_len, uint64_t rows_cap, bool *rows_short, zngamd_bgzf_sort_key_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    *rows_short = false;
+    const uint32_t W = sort_key_width(cf);
+    totals->key_width = W;
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
+    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+    if (r) return r;
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const uint64_t lines = R.lines, nrec = R.nrec;
+    constexpr size_t TOT_WORDS = sizeof(ZaSortKeyTotals) / 8u;                           // then the three faults
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->so_tot.ensure(TOT_WORDS + 3u));
+    if (own) { HIPCHK(c, c->so_row.ensure(nrec * W + 8u)); HIPCHK(c, c->so_len.ensure(nrec)); d_rows = c->so_row.p; d_len = c->so_len.p; }
+    else if (rows_cap < nrec) { *rows_short = true; d_rows = nullptr; d_len = nullptr; }
+    // four records to a workgroup, at most ZA_SORT_WG_PER_CU workgroups per CU: beyond that a wave walks on to its next record
+    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_SORT_WG_PER_CU;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    ZaSortPar P = {};
+    P.k_lines = k; P.first_byte = cf.first_byte; P.meta_byte = cf.meta_byte; P.n_parts = cf.n_parts; P.delim = w.delim; P.width = W; P.final = lflags ? 1u : 0u;
+    static_assert(sizeof(ZaSortPart) == sizeof(zngamd_bgzf_sort_part) && sizeof(ZaSortPart) == 20, "the parts are copied as they are");
+    memcpy(P.part, cf.part, sizeof P.part);
+    ZaSortKeyTotals *d_tot = (ZaSortKeyTotals *)c->so_tot.p;
+    unsigned long long *d_bad = c->so_tot.p + TOT_WORDS;
+    HIPCHK(c, hipMemsetAsync(c->so_tot.p, 0, TOT_WORDS * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 24, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_sort_keys, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, P, d_rows, d_len, d_tot);
+      hipLaunchKernelGGL(za_k_sort_keys_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, W, d_bad, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_sort_key_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                     uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_sort_conf *conf, uint64_t record_base, void *d_scratch,
+                                     uint64_t scratch_cap, int32_t *d_status, uint8_t *d_rows, uint32_t *d_lengths, uint64_t rows_cap,
+                                     zngamd_bgzf_sort_key_totals *totals)
+try {
+    if (!sort_key_args_ok(delim, flags, conf, d_rows, d_lengths, false, totals)) return ZNGAMD_E_ARG;
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    bool rows_short = false;
+    int r = bgzf_sort_key_dev(c, w, flags, *conf, record_base, false, d_rows, d_lengths, rows_cap, &rows_short, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (rows_short && !totals->bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_sort_key_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                                 uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_sort_conf *conf, uint64_t record_base, int32_t *status,
+                                 uint8_t *rows, uint32_t *lengths, uint64_t rows_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_sort_key_totals *totals)
+try {
+    if (!sort_key_args_ok(delim, flags, conf, rows, lengths, alloc != nullptr, totals)) return ZNGAMD_E_ARG;
+    if (!c || (!in && in_len) || (n_members && (!members || !status)) || (alloc && (rows || lengths))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    bool rows_short = false;
+    r = bgzf_sort_key_dev(c, w, flags, *conf, record_base, true, nullptr, nullptr, 0, &rows_short, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t seen = totals->seen, W = totals->key_width;
+    if (!totals->covered || totals->bad || !seen) return ZNGAMD_OK;
+    if (alloc) {
+        if (W) rows = (uint8_t *)alloc(user, seen * W);
+        lengths = (uint32_t *)alloc(user, seen * 4u);
+        if ((W && !rows) || !lengths) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
+    } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    if (W) HIPCHK(c, hipMemcpyAsync(rows, c->so_row.p, (size_t)(seen * W), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(lengths, c->so_len.p, (size_t)seen * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// the work area of the sort: the second order array, the digits, the table of counts (256 values x tiles), the 256 totals, OR and AND
+static uint64_t sort_tiles(uint64_t n) { return (n + ZA_SORT_TILE - 1u) / ZA_SORT_TILE; }
+static uint64_t sort_r8(uint64_t x) { return (x + 7u) & ~7ull; }
+static bool sort_width_ok(uint32_t width) { return width >= 8u && width <= ZNGAMD_SORT_MAX_WIDTH && !(width & 7u); }
+
+uint64_t zngamd_sort_scratch_bytes(uint64_t n, uint32_t width)
+{
+    if (n > ZNGAMD_SORT_MAX_KEYS || !sort_width_ok(width)) return 0;
+    return sort_r8(n * 4u) + sort_r8(n) + sort_tiles(n) * 1024u + 1024u + 2u * width;
+}
+
+// n > 0.  OR and AND, [the host waits for them], the order array set to 0 .. n - 1 in the buffer from which the passes end in d_order,
+// then per byte position that varies, the last first: hist, scan, scatter; rank.
+static int sort_dev(zngamd_ctx *c, const uint8_t *d_keys, uint64_t n, uint32_t W, uint8_t *d_scratch, uint32_t *d_order, uint32_t *d_rank)
+{
+    const uint32_t tiles = (uint32_t)sort_tiles(n), w8 = W / 8u, n32 = (uint32_t)n, grid_n = (uint32_t)((n + 255u) / 256u);
+    uint32_t *other = (uint32_t *)d_scratch;
+    uint8_t *dig = d_scratch + sort_r8(n * 4u);
+    uint32_t *tab = (uint32_t *)(dig + sort_r8(n)), *dtot = tab + (uint64_t)tiles * 256u;
+    unsigned long long *acc = (unsigned long long *)(dtot + 256);
+    uint8_t host[2u * ZNGAMD_SORT_MAX_WIDTH];
+    HIPCHK(c, hipMemsetAsync(acc, 0, W, c->stream));
+    HIPCHK(c, hipMemsetAsync(acc + w8, 0xFF, W, c->stream));
+    const uint64_t words = n * w8;
+    { ProfScope ps(c, ZNGAMD_K_SCAN);
+      hipLaunchKernelGGL(za_k_sort_orand, dim3((uint32_t)std::min<uint64_t>((words + 4095u) / 4096u, 1024u)), dim3(256), 0, c->stream,
+                         (const unsigned long long *)d_keys, words, w8, acc); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(host, acc, 2u * (size_t)W, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint32_t pos[ZNGAMD_SORT_MAX_WIDTH], np = 0;                                         // the byte positions that vary, the last first
+    for (uint32_t p = W; p-- > 0;) if (host[p] != host[W + p]) pos[np++] = p;
+    uint32_t *src = (np & 1u) ? other : d_order, *dst = (np & 1u) ? d_order : other;
+    { ProfScope ps(c, ZNGAMD_K_SCAN);
+      hipLaunchKernelGGL(za_k_sort_iota, dim3(grid_n), dim3(256), 0, c->stream, src, n32);
+      for (uint32_t i = 0; i < np; i++) {
+          hipLaunchKernelGGL(za_k_sort_hist, dim3(tiles), dim3(256), 0, c->stream, d_keys, W, pos[i], (const uint32_t *)src, n32, dig, tab);
+          hipLaunchKernelGGL(za_k_sort_scan, dim3(256), dim3(256), 0, c->stream, tab, tiles, dtot);
+          hipLaunchKernelGGL(za_k_sort_scatter, dim3(tiles), dim3(256), 0, c->stream, (const uint8_t *)dig, (const uint32_t *)src, n32, (const uint32_t *)tab,
+                             (const uint32_t *)dtot, dst);
+          std::swap(src, dst);
+      }
+      if (d_rank) hipLaunchKernelGGL(za_k_sort_rank, dim3(grid_n), dim3(256), 0, c->stream, (const uint32_t *)d_order, n32, d_rank); }
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+int zngamd_sort_keys_dev(zngamd_ctx *c, const uint8_t *d_keys, uint64_t n, uint32_t width, void *d_scratch, uint64_t scratch_cap, uint32_t *d_order,
+                         uint32_t *d_rank)
+try {
+    if (n > ZNGAMD_SORT_MAX_KEYS || !sort_width_ok(width) || (n && (!d_keys || !d_order || !d_scratch)) || ((uintptr_t)d_scratch & 7u) ||
+        ((uintptr_t)d_keys & 7u)) return ZNGAMD_E_ARG;
+    if (!c) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (n && scratch_cap < zngamd_sort_scratch_bytes(n, width)) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    if (!n) return ZNGAMD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int r = sort_dev(c, d_keys, n, width, (uint8_t *)d_scratch, d_order, d_rank);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_sort_keys(zngamd_ctx *c, const uint8_t *keys, uint64_t n, uint32_t width, uint32_t *order, uint32_t *rank)
+try {
+    if (n > ZNGAMD_SORT_MAX_KEYS || !sort_width_ok(width) || (n && (!keys || !order))) return ZNGAMD_E_ARG;
+    if (!c) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!n) return ZNGAMD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->so_key.ensure(n * (width / 8u))); HIPCHK(c, c->so_tab.ensure(zngamd_sort_scratch_bytes(n, width) / 8u)); HIPCHK(c, c->so_ord.ensure(n));
+    if (rank) HIPCHK(c, c->so_rank.ensure(n));
+    HIPCHK(c, hipMemcpyAsync(c->so_key.p, keys, (size_t)(n * width), hipMemcpyHostToDevice, c->stream));
+    int r = sort_dev(c, (const uint8_t *)c->so_key.p, n, width, (uint8_t *)c->so_tab.p, c->so_ord.p, rank ? c->so_rank.p : nullptr);
+    if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(order, c->so_ord.p, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
+    if (rank) HIPCHK(c, hipMemcpyAsync(rank, c->so_rank.p, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool place_args_ok(int delim, uint32_t flags, uint32_t record_lines, int32_t first_byte, const uint64_t *dst, const uint32_t *length, uint64_t n,
+                          const void *d_out, uint64_t out_cap, const zngamd_bgzf_place_totals *totals)
+{
+    if (!totals || (flags & ~ZNGAMD_BGZF_GREP_FINAL) || delim < 0 || delim > 255 || !grep_records_ok(record_lines, -1, first_byte)) return false;
+    return (!n || (dst && length)) && (d_out || !out_cap);
+}
+
+// the lines pass for the delimiters alone, [the host waits for the line count], lines, place, close, [the host waits for the totals].
+// own: dst and length are host memory and go to so_dst and so_len once the line count says how many are needed.
+static int bgzf_place_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, uint32_t k, int32_t first_byte, uint64_t record_base, bool own, const uint64_t *dst,
+                          const uint32_t *length, uint64_t n, uint8_t *d_out, uint64_t out_cap, zngamd_bgzf_place_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL;
+    const int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+    if (r) return r;
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const uint64_t lines = R.lines, nrec = R.nrec;
+    const bool all = n >= nrec;                                                          // otherwise nothing is placed: labels_short
+    constexpr size_t TOT_WORDS = sizeof(ZaPlaceTotals) / 8u;                             // then the three faults
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->so_tot.ensure(TOT_WORDS + 3u));
+    if (own && all) {
+        HIPCHK(c, c->so_dst.ensure(nrec)); HIPCHK(c, c->so_len.ensure(nrec));
+        HIPCHK(c, hipMemcpyAsync(c->so_dst.p, dst, (size_t)nrec * 8u, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->so_len.p, length, (size_t)nrec * 4u, hipMemcpyHostToDevice, c->stream));
+        dst = (const uint64_t *)c->so_dst.p; length = c->so_len.p;
+    }
+    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_SORT_WG_PER_CU;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    ZaPlaceTotals *d_tot = (ZaPlaceTotals *)c->so_tot.p;
+    unsigned long long *d_bad = c->so_tot.p + TOT_WORDS;
+    HIPCHK(c, hipMemsetAsync(c->so_tot.p, 0, TOT_WORDS * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 24, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      if (all) hipLaunchKernelGGL(za_k_sort_place, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, k, first_byte, w.delim,
+                                  lflags ? 1u : 0u, (const unsigned long long *)dst, length, d_out, out_cap, d_tot);
+      hipLaunchKernelGGL(za_k_sort_place_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, n, k, lflags, w.text_end, record_base, d_bad, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_place_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                  uint64_t text_end, int delim, uint32_t flags, uint32_t record_lines, int32_t first_byte, uint64_t record_base, void *d_scratch,
+                                  uint64_t scratch_cap, int32_t *d_status, const uint64_t *d_dst, const uint32_t *d_length, uint64_t n, void *d_out,
+                                  uint64_t out_cap, zngamd_bgzf_place_totals *totals)
+try {
+    if (!place_args_ok(delim, flags, record_lines, first_byte, d_dst, d_length, n, d_out, out_cap, totals)) return ZNGAMD_E_ARG;
+    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    int r = bgzf_place_dev(c, w, flags, record_lines, first_byte, record_base, false, d_dst, d_length, n, (uint8_t *)d_out, out_cap, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_place_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                              uint64_t text_end, int delim, uint32_t flags, uint32_t record_lines, int32_t first_byte, uint64_t record_base, int32_t *status,
+                              const uint64_t *dst, const uint32_t *length, uint64_t n, void *d_out, uint64_t out_cap, zngamd_bgzf_place_totals *totals)
+try {
+    if (!place_args_ok(delim, flags, record_lines, first_byte, dst, length, n, d_out, out_cap, totals)) return ZNGAMD_E_ARG;
+    if (!c || (!in && in_len) || (n_members && (!members || !status))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    r = bgzf_place_dev(c, w, flags, record_lines, first_byte, record_base, true, dst, length, n, (uint8_t *)d_out, out_cap, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
 

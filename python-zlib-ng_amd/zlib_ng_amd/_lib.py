@@ -89,6 +89,8 @@ SYMBOLS = [
     "zngamd_bgzf_trim_records_dev", "zngamd_bgzf_trim_records",
     "zngamd_bgzf_qc_records_dev", "zngamd_bgzf_qc_records",
     "zngamd_bgzf_key_records_dev", "zngamd_bgzf_key_records", "zngamd_dedup_scratch_bytes", "zngamd_dedup_keys_dev", "zngamd_dedup_keys",
+    "zngamd_bgzf_sort_key_records_dev", "zngamd_bgzf_sort_key_records", "zngamd_sort_scratch_bytes", "zngamd_sort_keys_dev", "zngamd_sort_keys",
+    "zngamd_bgzf_place_records_dev", "zngamd_bgzf_place_records",
     "zngamd_bgzf_overlap_records_dev", "zngamd_bgzf_overlap_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
@@ -310,6 +312,40 @@ class DedupTotals(C.Structure):                # zngamd_dedup_totals
                 ("reserved", C.c_uint64)]
 
 
+BGZF_SORT_BYTES, BGZF_SORT_NUMBER, BGZF_SORT_LENGTH = 0, 1, 2                               # ZNGAMD_BGZF_SORT_*: a part's kind
+BGZF_SORT_REVERSE, BGZF_SORT_IGNORE_CASE, BGZF_SORT_TRUNCATE = 1, 2, 4                      # a part's flags
+BGZF_SORT_MAX_PARTS, SORT_MAX_WIDTH, SORT_MAX_KEYS = 4, 256, 1 << 30                        # ZNGAMD_BGZF_SORT_MAX_PARTS, ZNGAMD_SORT_MAX_*
+BGZF_PLACE_SKIP = (1 << 64) - 1                                                             # ZNGAMD_BGZF_PLACE_SKIP
+
+
+class BgzfSortPart(C.Structure):               # zngamd_bgzf_sort_part
+    _fields_ = [("line", C.c_int32), ("column", C.c_int32), ("width", C.c_uint32), ("first", C.c_uint32), ("flags", C.c_uint16), ("kind", C.c_uint8),
+                ("sep", C.c_uint8)]
+
+
+class BgzfSortConf(C.Structure):               # zngamd_bgzf_sort_conf
+    _fields_ = [("record_lines", C.c_uint32), ("first_byte", C.c_int32), ("meta_byte", C.c_int32), ("n_parts", C.c_uint32), ("part", BgzfSortPart * 4),
+                ("reserved", C.c_uint32 * 8)]
+
+
+class BgzfSortKeyTotals(C.Structure):          # zngamd_bgzf_sort_key_totals
+    _fields_ = [("seen", C.c_uint64), ("bytes_in", C.c_uint64), ("max_field", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64),
+                ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("key_width", C.c_uint32)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is keyed)
+        return self.seen
+
+
+class BgzfPlaceTotals(C.Structure):            # zngamd_bgzf_place_totals
+    _fields_ = [("seen", C.c_uint64), ("placed", C.c_uint64), ("placed_bytes", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64),
+                ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("labels_short", C.c_uint32)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is looked at)
+        return self.seen
+
+
 BGZF_TABIX_FINAL, BGZF_FETCH_COUNT_ONLY, BGZF_FETCH_MAX_REGIONS = 4, 8, 4096      # ZNGAMD_BGZF_TABIX_FINAL, ZNGAMD_BGZF_FETCH_*
 TABIX_MAX_POS = 1 << 29                        # ZNGAMD_TABIX_MAX_POS
 TABIX_NAME_DTYPE = np.dtype([("src_off", "<u8"), ("first", "<u8"), ("line", "<u8"), ("len", "<u4"), ("reserved", "<u4")])      # zngamd_tabix_name
@@ -505,6 +541,19 @@ def load():
             L.zngamd_dedup_scratch_bytes.restype = C.c_uint64
             L.zngamd_dedup_keys_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp]
             L.zngamd_dedup_keys.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+        if hasattr(L, "zngamd_bgzf_sort_key_records"):      # as key with the lengths beside the rows; the sort and the size of its work area; place
+            L.zngamd_bgzf_sort_key_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp,
+                                                           C.c_uint64, vp, vp, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_sort_key_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp, vp,
+                                                       vp, C.c_uint64, ALLOC_FN, vp, vp]
+            L.zngamd_sort_scratch_bytes.argtypes = [C.c_uint64, C.c_uint32]
+            L.zngamd_sort_scratch_bytes.restype = C.c_uint64
+            L.zngamd_sort_keys_dev.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp]
+            L.zngamd_sort_keys.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp]
+            L.zngamd_bgzf_place_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_int32,
+                                                        C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_place_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_int32,
+                                                    C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
         if hasattr(L, "zngamd_bgzf_overlap_records"):       # as qc without the tables: overlap rows, rows and bytes with their capacities
             L.zngamd_bgzf_overlap_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp,
                                                           C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1854,6 +1903,92 @@ class Context:
         v = lambda x: C.c_void_p(int(x)) if x else None
         tot = DedupTotals()
         r = self._chk(self.L.zngamd_dedup_keys_dev(self.h, v(d_keys), n, v(d_scratch), scratch_cap, v(d_first), v(d_count), C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def bgzf_sort_key_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):
+        """zngamd_bgzf_sort_key_records: the sort key of every record by conf (a BgzfSortConf) -> (code, block statuses, totals
+        (BgzfSortKeyTotals), rows (uint8 of shape (seen, W)), lengths (uint32); both empty when totals.bad is set).  caps None: the
+        arrays are allocated once the engine knows how many rows there are; an integer: buffers of that many rows, and code is BUF_ERROR
+        when the result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfSortKeyTotals()
+        W = sum(q.width if q.kind == BGZF_SORT_BYTES else 8 if q.kind == BGZF_SORT_NUMBER else 4 for q in conf.part[:conf.n_parts]) + 7 & ~7
+        box = []
+
+        def alloc(_user, nbytes):
+            box.append(np.empty(nbytes, np.uint8))
+            return box[-1].ctypes.data
+
+        if caps is None:
+            rp, lp, rcap, fn = None, None, 0, ALLOC_FN(alloc)
+        else:
+            rcap = caps
+            rows, lens = np.zeros(max(1, rcap * W), np.uint8), np.zeros(max(1, rcap), np.uint32)
+            rp, lp, fn = C.c_void_p(rows.ctypes.data), C.c_void_p(lens.ctypes.data), ALLOC_FN()
+        r = self._chk(self.L.zngamd_bgzf_sort_key_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                          text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
+                                                          rp, lp, rcap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and tot.covered and tot.seen and not tot.bad
+        n = tot.seen if got else 0
+        if caps is None and got:
+            rows_out = box[0] if W else np.empty(0, np.uint8)
+            lens_out = box[-1].view(np.uint32)
+        elif got:
+            rows_out, lens_out = rows[:n * W], lens[:n]
+        else:
+            rows_out, lens_out = np.empty(0, np.uint8), np.empty(0, np.uint32)
+        return r, st[:nm], tot, rows_out.reshape(n, W), lens_out
+
+    def bgzf_sort_key_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, record_base, d_scratch, scratch_cap,
+                                  d_status, d_rows, d_lengths, rows_cap):
+        """zngamd_bgzf_sort_key_records_dev on device pointers (conf: host memory) -> (code, totals); rows and lengths stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfSortKeyTotals()
+        r = self._chk(self.L.zngamd_bgzf_sort_key_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
+                                                              C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), v(d_lengths),
+                                                              rows_cap, C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def sort_keys(self, keys, want_rank=False):
+        """zngamd_sort_keys: keys (C-contiguous uint8 of shape (n, W)) -> (order (uint32), rank (uint32, or None))"""
+        n, w = keys.shape
+        order = np.empty(n, np.uint32)
+        rank = np.empty(n, np.uint32) if want_rank else None
+        p = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        self._chk(self.L.zngamd_sort_keys(self.h, p(keys), n, w, p(order), p(rank)))
+        return order, rank
+
+    def sort_keys_dev(self, d_keys, n, width, d_scratch, scratch_cap, d_order, d_rank):
+        """zngamd_sort_keys_dev on device pointers -> code; order and rank (which may be 0) stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        return self._chk(self.L.zngamd_sort_keys_dev(self.h, v(d_keys), n, width, v(d_scratch), scratch_cap, v(d_order), v(d_rank)), (OK, BUF_ERROR))
+
+    def bgzf_place_records(self, data, members, text_off, text_end, delim, flags, record_lines, first_byte, record_base, dst, length, d_out, out_cap):
+        """zngamd_bgzf_place_records: record record_base + r copied to the device buffer d_out + dst[r] (uint64; BGZF_PLACE_SKIP: not in
+        this pass) with length[r] (uint32) as bgzf_sort_key_records reported it -> (code, block statuses, totals (BgzfPlaceTotals))"""
+        nm = len(members)
+        p, keep = _addr(data)
+        dst, length = np.ascontiguousarray(dst, np.uint64), np.ascontiguousarray(length, np.uint32)
+        n = min(len(dst), len(length))
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfPlaceTotals()
+        r = self._chk(self.L.zngamd_bgzf_place_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                       text_off, text_end, delim, flags, record_lines, first_byte, record_base,
+                                                       C.c_void_p(st.ctypes.data), C.c_void_p(dst.ctypes.data) if n else None,
+                                                       C.c_void_p(length.ctypes.data) if n else None, n, C.c_void_p(int(d_out)) if d_out else None, out_cap,
+                                                       C.byref(tot)))
+        return r, st[:nm], tot
+
+    def bgzf_place_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, record_lines, first_byte, record_base,
+                               d_scratch, scratch_cap, d_status, d_dst, d_length, n, d_out, out_cap):
+        """zngamd_bgzf_place_records_dev on device pointers -> (code, totals)"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfPlaceTotals()
+        r = self._chk(self.L.zngamd_bgzf_place_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
+                                                           record_lines, first_byte, record_base, v(d_scratch), scratch_cap, v(d_status), v(d_dst),
+                                                           v(d_length), n, v(d_out), out_cap, C.byref(tot)))
         return r, tot
 
     def _bgzf_grep(self, fn_c, tot, data, members, text_off, text_end, blob, table, delim, flags, extra, caps):

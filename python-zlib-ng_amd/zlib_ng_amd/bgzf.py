@@ -54,6 +54,7 @@ __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offse
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
            "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP", "trim_records", "TrimResult", "KEPT", "TOO_SHORT", "DROPPED", "qc_records", "QcResult",
            "key_records", "KeyResult", "pair_keys", "dedup_keys", "DedupResult", "dedup_records", "dedup_paired",
+           "SortKey", "SortKeyResult", "SortResult", "sort_key_records", "sort_keys", "permute_records", "sort_records",
            "overlap_records", "OverlapResult", "NONE", "FOUND", "MERGED", "TOO_LONG",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
 
@@ -779,6 +780,10 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
                 return (coffs[at] + c_next).astype(np.uint64) << np.uint64(16) | (src - members["out_off"][at].astype(np.int64)).astype(np.uint64)
 
             if records is not None:
+                if tot.bad and hasattr(partition, "fault"):          # (a sink with faults of its own: the sort key and the place sinks)
+                    msg = partition.fault(tot, int(voffsets_of(np.array([tot.bad_src], np.int64))[0]))
+                    if msg:
+                        raise ValueError(msg)
                 if tot.bad == 2 and partition is not None:
                     raise ValueError(f"record {tot.bad_record}: its label is neither a class nor DROP")
                 if tot.bad == 3 and partition is not None:
@@ -1830,6 +1835,403 @@ def dedup_paired(files, outputs, record_lines=4, *, duplicates=None, compresslev
                 _partition_file(fps[f], None, labels, outs, record_lines, first_byte, delimiter, compresslevel, block_size, start[f], stop[f],
                                 first_record, max_record, allow_short)
     return res
+
+
+# ---- records in another order: a key per record, a stable sort of keys, records written in any order
+_SORT_KINDS = {"bytes": _lib.BGZF_SORT_BYTES, "number": _lib.BGZF_SORT_NUMBER, "length": _lib.BGZF_SORT_LENGTH}
+_SORT_LINE_PRESETS = {"bed": (1, 2, b"#"), "gff": (1, 4, b"#"), "vcf": (1, 2, b"#"), "sam": (3, 4, b"@")}      # name column, start column (from 1), meta
+_SORT_OUT_OF_STEP = "the file holds {} records and lengths has {} entries: the files are out of step"
+
+
+class SortKey:
+    """One part of a sort key: the field it reads and the bytes it becomes.  line: the line of the record; column: None for the whole
+    line, otherwise the 0-based field when the line is cut at sep (one byte).  kind "bytes": field[first : first + width] padded with
+    0x00 (width 8 .. 128, a multiple of 8; ignore_case takes a .. z as A .. Z; a longer field is a ValueError of the call unless it
+    truncates), "number": an unsigned decimal number (8 bytes), "length": the length of the field (4 bytes).  reverse turns the part's
+    order round.  truncate: None follows the call's truncate=."""
+
+    def __init__(self, line=0, column=None, sep=b"\t", kind="bytes", width=32, first=0, reverse=False, ignore_case=False, truncate=None):
+        if kind not in _SORT_KINDS:
+            raise ValueError(f"kind is 'bytes', 'number' or 'length', not {kind!r}")
+        for name, value in (("reverse", reverse), ("ignore_case", ignore_case)):
+            if not isinstance(value, (bool, np.bool_)):
+                raise ValueError(f"{name} is True or False, not {value!r}")
+        if truncate is not None and not isinstance(truncate, (bool, np.bool_)):
+            raise ValueError(f"truncate is None, True or False, not {truncate!r}")
+        sep = bytes(sep)
+        if len(sep) != 1:
+            raise ValueError("sep is exactly one byte")
+        self.line = _trim_int(line, 0, _lib.BGZF_GREP_MAX_RECORD_LINES - 1, "line")
+        self.column = None if column is None else _trim_int(column, 0, (1 << 31) - 1, "column")
+        self.sep, self.kind, self.reverse, self.ignore_case, self.truncate = sep, kind, bool(reverse), bool(ignore_case), truncate
+        if kind == "bytes":
+            self.width, self.first = _trim_int(width, 8, 128, "width"), _trim_int(first, 0, (1 << 32) - 1, "first")
+            if self.width % 8:
+                raise ValueError(f"width is a multiple of 8, not {self.width}")
+        else:
+            self.width, self.first = 0, 0
+            if ignore_case or truncate:
+                raise ValueError("ignore_case and truncate belong to kind 'bytes'")
+
+    @property
+    def nbytes(self):
+        return self.width if self.kind == "bytes" else 8 if self.kind == "number" else 4
+
+    def _spec(self, truncate):
+        t = self.kind == "bytes" and bool(truncate if self.truncate is None else self.truncate)
+        return (self.line, -1 if self.column is None else self.column, self.sep, self.kind, self.width, self.first, self.reverse, self.ignore_case, t)
+
+    def __repr__(self):
+        return (f"SortKey(line={self.line}, column={self.column}, sep={self.sep!r}, kind={self.kind!r}, width={self.width}, first={self.first}, "
+                f"reverse={self.reverse}, ignore_case={self.ignore_case}, truncate={self.truncate})")
+
+
+def _sort_preset(name, record_lines, meta):
+    """-> (parts, record_lines, meta) of a preset name; ValueError for any other"""
+    if name == "name":
+        return [SortKey(0, 0, b" ", width=64)], record_lines, meta
+    if name == "sequence":
+        return [SortKey(1, width=128, truncate=True), SortKey(1, width=128, first=128, truncate=True)], record_lines, meta
+    if name == "length":
+        return [SortKey(1, kind="length")], record_lines, meta
+    if name in _SORT_LINE_PRESETS:
+        seq, beg, m = _SORT_LINE_PRESETS[name]
+        return [SortKey(0, seq - 1), SortKey(0, beg - 1, kind="number")], 1, m if meta is None else meta
+    raise ValueError(f"unknown preset {name!r}: name, sequence, length, bed, gff, vcf or sam")
+
+
+def _sort_conf(key, record_lines, meta, truncate, reverse, first_byte, delimiter):
+    """-> (BgzfSortConf, delimiter as bytes, record_lines, the specification of a SortKeyResult); ValueError as sort_key_records()
+    documents it"""
+    delimiter = _partition_delimiter(delimiter)
+    for name, value in (("truncate", truncate), ("reverse", reverse)):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{name} is True or False, not {value!r}")
+    if isinstance(key, str):
+        parts, record_lines, meta = _sort_preset(key, record_lines, meta)
+    elif isinstance(key, SortKey):
+        parts = [key]
+    else:
+        parts = list(key)
+        if not all(isinstance(p, SortKey) for p in parts):
+            raise ValueError("key is a SortKey, a list of up to four, or the name of a preset")
+    if len(parts) > _lib.BGZF_SORT_MAX_PARTS:
+        raise ValueError(f"a key has at most {_lib.BGZF_SORT_MAX_PARTS} parts, not {len(parts)}")
+    k, _, b = _grep_record_args(record_lines, None, first_byte)
+    _, _, m = _grep_record_args(1, None, meta)
+    width = sum(p.nbytes for p in parts)
+    if width > _lib.SORT_MAX_WIDTH:
+        raise ValueError(f"the key's parts add up to {width} bytes: at most {_lib.SORT_MAX_WIDTH}")
+    conf = _lib.BgzfSortConf(k, b, m, len(parts))
+    spec = []
+    for i, p in enumerate(parts):
+        if p.line >= k:
+            raise ValueError(f"line lies between 0 and {k - 1}, not {p.line}")
+        s = p._spec(truncate)
+        rev = s[6] != bool(reverse)
+        flags = (_lib.BGZF_SORT_REVERSE if rev else 0) | (_lib.BGZF_SORT_IGNORE_CASE if s[7] else 0) | (_lib.BGZF_SORT_TRUNCATE if s[8] else 0)
+        conf.part[i] = _lib.BgzfSortPart(s[0], s[1], s[4], s[5], flags, _SORT_KINDS[s[3]], s[2][0])
+        spec.append(s[:6] + (rev,) + s[7:])
+    return conf, delimiter, k, dict(record_lines=k, meta=None if m < 0 else m, width=(width + 7) // 8 * 8, parts=tuple(spec))
+
+
+class SortKeyResult:
+    """What sort_key_records() made: keys (uint8 of shape (records, W): row r is the key of record r, and memcmp order of the rows is the
+    order asked for), lengths (uint32: the bytes of every record as permute_records() writes it), records, and spec, the key
+    specification the rows were made with.  a + b puts the rows of two shards, or of two files, one behind the other, and is a
+    ValueError when the specifications differ."""
+
+    def __init__(self, keys, lengths, spec):
+        self.keys, self.lengths, self.records, self.spec = keys, lengths, len(lengths), dict(spec)
+        if keys.ndim != 2 or keys.dtype != np.uint8 or len(keys) != self.records or keys.shape[1] != self.spec["width"]:
+            raise ValueError("keys is uint8 of shape (records, W) with the specification's W")
+
+    @property
+    def key_width(self):
+        return self.spec["width"]
+
+    def __len__(self):
+        return self.records
+
+    def __add__(self, other):
+        if not isinstance(other, SortKeyResult):
+            return NotImplemented
+        if self.spec != other.spec:
+            raise ValueError(f"keys made with {self.spec} and with {other.spec} are not comparable")
+        return SortKeyResult(np.concatenate([self.keys, other.keys]), np.concatenate([self.lengths, other.lengths]), self.spec)
+
+    def __repr__(self):
+        return f"<SortKeyResult: {self.records} records, keys of {self.key_width} bytes>"
+
+
+class _SortKeySink:
+    """what _grep_file hands a window's records to when their sort keys are made: the windows' rows and lengths are put one behind the
+    other"""
+
+    def __init__(self, conf, spec):
+        self.conf, self.spec, self.rows, self.lens = conf, spec, [], []
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        _, status, tot, self.win_rows, self.win_lens = ctx.bgzf_sort_key_records(data, members, text_off, text_end, delim, flags, self.conf, record_base)
+        return status, tot, b""
+
+    def fault(self, tot, voffset):
+        if tot.bad == 2:
+            return f"record {tot.bad_record} at virtual offset {voffset}: a number field is empty, holds a byte that is no digit, or is above 2**64 - 1"
+        if tot.bad == 3:
+            return (f"record {tot.bad_record} at virtual offset {voffset}: a field is longer than its part's first + width; the longest such field of "
+                    f"the window has {tot.max_field} bytes: a width of {(int(tot.max_field) + 7) // 8 * 8} behind first would do, or truncate=True")
+        return None
+
+    def window(self, tot, packed):
+        if not tot.seen:
+            return
+        if len(self.win_rows) != tot.seen or len(self.win_lens) != tot.seen:
+            raise RuntimeError("sort_key_records: the rows do not add up to the records")
+        self.rows.append(self.win_rows)
+        self.lens.append(self.win_lens)
+
+    def finish(self, searched):
+        w = self.spec["width"]
+        keys = np.concatenate(self.rows) if self.rows else np.empty((0, w), np.uint8)
+        lens = np.concatenate(self.lens) if self.lens else np.empty(0, np.uint32)
+        if len(lens) != searched:
+            raise RuntimeError("sort_key_records: the rows do not add up to the records")
+        return SortKeyResult(keys, lens, self.spec)
+
+
+def _sort_key_file(fp, ctx, key, record_lines, meta, truncate, reverse, first_byte, delimiter, start, stop, first_record, max_record, allow_short):
+    conf, delimiter, k, spec = _sort_conf(key, record_lines, meta, truncate, reverse, first_byte, delimiter)
+    return _grep_file(fp, ctx, None, delimiter, False, False, False, None, start, stop, first_record, max_record, (k, None, first_byte, allow_short), 0,
+                      None, _SortKeySink(conf, spec))
+
+
+def sort_key_records(file, key, record_lines=4, *, meta=None, truncate=False, first_byte=None, delimiter=b"\n", start=None, stop=None,
+                     first_record=0, max_record=64 << 20, allow_short=False):
+    """A sort key per record of a BGZF file, made on the GPU: rows of W bytes whose memcmp order is the order asked for.  key is a
+    SortKey, a list of up to four (the first counts most), or a preset: "name" (line 0 up to the first blank, 64 bytes), "sequence"
+    (line 1, its first 256 bytes), "length" (the length of line 1), or "bed", "gff", "vcf", "sam" -- line formats: record_lines is 1
+    whatever is passed, the key is the name column (32 bytes) and then the start column as a number, and the lines that begin with
+    meta (b"#", for sam b"@") get the all-zero key, so that a stable sort leaves them in front and in order.  The parts' bytes add up
+    to at most 256; W is their sum rounded up to 8.  truncate=True cuts a "bytes" field that is longer than its width instead of
+    raising.  record_lines, first_byte, delimiter, start, stop, first_record, max_record, allow_short and the errors of the file are those
+    of grep_records().  A number field that is empty, holds another byte than a digit or exceeds 2**64 - 1, and a field that is too
+    long, are ValueErrors that name the record and its virtual offset.  -> SortKeyResult; the results of the parts of
+    LineIndex.shards(reader, n, lines_per_record=k), put together with +, are the whole file's.  A last record whose last line
+    lacks its delimiter is counted with one: permute_records() writes it."""
+    if _is_path(file):
+        _sort_conf(key, record_lines, meta, truncate, False, first_byte, delimiter)      # (judged before the file is opened)
+        with _builtin_open(file, "rb") as f:
+            return sort_key_records(f, key, record_lines, meta=meta, truncate=truncate, first_byte=first_byte, delimiter=delimiter, start=start, stop=stop,
+                                    first_record=first_record, max_record=max_record, allow_short=allow_short)
+    return _sort_key_file(file, None, key, record_lines, meta, truncate, False, first_byte, delimiter, start, stop, first_record, max_record, allow_short)
+
+
+def _sort_rows(keys):
+    """keys as C-contiguous uint8 of shape (n, W), W a multiple of 8 between 8 and 256; ValueError as sort_keys() documents it"""
+    if isinstance(keys, SortKeyResult):
+        keys = keys.keys
+    keys = np.asarray(keys)
+    if keys.dtype != np.uint8 or keys.ndim != 2 or not keys.flags.c_contiguous:
+        raise ValueError("keys is a SortKeyResult or a C-contiguous uint8 array of shape (n, W)")
+    n, w = keys.shape
+    if w % 8 or not 8 <= w <= _lib.SORT_MAX_WIDTH:
+        raise ValueError(f"the rows' width is a multiple of 8 between 8 and {_lib.SORT_MAX_WIDTH}, not {w}")
+    if n > _lib.SORT_MAX_KEYS:
+        raise ValueError(f"sort_keys takes at most {_lib.SORT_MAX_KEYS} rows, not {n}")
+    return keys
+
+
+def _sort(ctx, keys, rank):
+    keys = _sort_rows(keys)
+    ctx = ctx or zlib_ng._ctx()                              # (the arguments are judged before a context is asked for)
+    order, inverse = ctx.sort_keys(keys, bool(rank))
+    return (order.astype(np.int64), inverse.astype(np.int64)) if rank else order.astype(np.int64)
+
+
+def sort_keys(keys, *, rank=False):
+    """Sort rows on the GPU: order[j] (int64) is the row that stands j-th in memcmp order, and equal rows come in ascending row number:
+    the sort is stable, so the result depends on the rows alone.  keys is a SortKeyResult (of a file, or of shards or files put together
+    with +) or any C-contiguous uint8 array of shape (n, W) with W a multiple of 8 between 8 and 256; at most 2**30 rows.
+    rank=True: -> (order, rank) with rank[order[j]] == j.  Byte positions that are the same in every row cost nothing."""
+    return _sort(None, keys, rank)
+
+
+def _permute_order(order, n):
+    """order as int64, judged: one dimension, every number at most once, and, when n is known, below it"""
+    order = np.asarray(order)
+    if order.ndim != 1 or (order.size and order.dtype.kind not in "iu"):
+        raise ValueError("order is a one-dimensional array of record numbers")
+    order = order.astype(np.int64)
+    if len(order):
+        if int(order.min()) < 0 or (n is not None and int(order.max()) >= n):
+            i = int(np.nonzero((order < 0) | (order >= (n if n is not None else 1 << 62)))[0][0])
+            raise ValueError(f"order[{i}] is {int(order[i])}: a record number lies between 0 and {'the last record' if n is None else n - 1}")
+        s = np.sort(order)
+        dup = np.nonzero(s[1:] == s[:-1])[0]
+        if len(dup):
+            raise ValueError(f"order holds record {int(s[dup[0]])} more than once")
+    return order
+
+
+def _permute_lengths(lengths):
+    lengths = np.asarray(lengths)
+    if lengths.ndim != 1 or (lengths.size and lengths.dtype.kind not in "iu") or (lengths.size and (int(lengths.min()) < 0 or int(lengths.max()) >= 1 << 32)):
+        raise ValueError("lengths is a one-dimensional array of record lengths below 2**32")
+    return lengths.astype(np.uint32)
+
+
+class _PlaceSink:
+    """what _grep_file hands a window's records to when they are written where dst says: dst[i] and lengths[i] belong to record i"""
+
+    def __init__(self, dst, lengths, d_out, out_cap):
+        self.dst, self.lengths, self.d_out, self.out_cap = dst, lengths, d_out, out_cap
+        self.placed, self.bytes, self.short = 0, 0, False
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        dst, lens = (self.dst[:0], self.lengths[:0]) if self.short else (self.dst[record_base:], self.lengths[record_base:])
+        _, status, tot = ctx.bgzf_place_records(data, members, text_off, text_end, delim, flags, k, first_byte, record_base, dst, lens, self.d_out, self.out_cap)
+        return status, tot, b""
+
+    def fault(self, tot, voffset):
+        if tot.bad == 4:
+            return (f"record {tot.bad_record} at virtual offset {voffset}: its length is not lengths[{tot.bad_record}] "
+                    f"({int(self.lengths[tot.bad_record]) if tot.bad_record < len(self.lengths) else '?'}): the file changed between the passes")
+        if tot.bad == 5:
+            return f"record {tot.bad_record} at virtual offset {voffset} does not fit the bucket it was placed in"
+        return None
+
+    def window(self, tot, packed):
+        self.short = self.short or bool(tot.labels_short)
+        self.placed, self.bytes = self.placed + int(tot.placed), self.bytes + int(tot.placed_bytes)
+
+    def finish(self, searched):
+        if self.short or searched != len(self.lengths):
+            raise ValueError(_SORT_OUT_OF_STEP.format(searched, len(self.lengths)))
+        return self.placed, self.bytes
+
+
+def _permute_buckets(sizes, chunk_bytes):
+    """-> [(a, b)]: sizes[a:b] are written together; at most chunk_bytes per bucket, but at least one record"""
+    ends = np.cumsum(sizes.astype(np.int64))
+    cuts, a = [], 0
+    while a < len(sizes):
+        base = int(ends[a - 1]) if a else 0
+        b = max(int(np.searchsorted(ends, base + chunk_bytes, "right")), a + 1)
+        cuts.append((a, b))
+        a = b
+    return cuts
+
+
+def _permute_file(fp, ctx, order, output, record_lines, lengths, chunk_bytes, compresslevel, block_size, first_byte, delimiter, max_record=64 << 20):
+    delimiter = _partition_delimiter(delimiter)
+    _grep_record_args(record_lines, None, first_byte)
+    block_size = _check_block_size(block_size)
+    chunk_bytes = _trim_int(chunk_bytes, 1, 1 << 40, "chunk_bytes")
+    if lengths is not None:
+        lengths = _permute_lengths(lengths)
+    order = _permute_order(order, None if lengths is None else len(lengths))
+    ctx = ctx or zlib_ng._ctx()                             # (the arguments are judged before a context is asked for)
+    if lengths is None:
+        lengths = _sort_key_file(fp, ctx, [], record_lines, None, False, False, first_byte, delimiter, None, None, 0, max_record, True).lengths
+        order = _permute_order(order, len(lengths))
+    n = len(lengths)
+    sizes = lengths[order]
+    buckets = _permute_buckets(sizes, chunk_bytes)
+    starts = np.cumsum(sizes.astype(np.int64)) - sizes.astype(np.int64)
+    cap = max([int(sizes[a:b].astype(np.int64).sum()) for a, b in buckets], default=0)
+    out = _builtin_open(output, "wb") if _is_path(output) else output
+    written = 0
+    try:
+        if buckets:
+            d_out = devmem.empty(ctx, cap + 64)                  # (room behind the bucket, as every device input of the writer has)
+            d_z = devmem.empty(ctx, ctx.bgzf_room(cap, block_size))
+        for i, (a, b) in enumerate(buckets):
+            nbytes = int(sizes[a:b].astype(np.int64).sum())
+            dst = np.full(n, _lib.BGZF_PLACE_SKIP, np.uint64)
+            dst[order[a:b]] = (starts[a:b] - int(starts[a])).astype(np.uint64)
+            sink = _PlaceSink(dst, lengths, d_out.ptr, nbytes)
+            placed, got = _grep_file(fp, ctx, None, delimiter, False, False, False, None, None, None, 0, max_record,
+                                     (record_lines, None, first_byte, True), 0, None, sink)
+            if placed != b - a or got != nbytes:
+                raise RuntimeError(f"permute_records: {placed} records and {got} bytes were placed in a bucket of {b - a} records and {nbytes} bytes")
+            _, zbytes, _ = compress_dev(ctx, d_out, nbytes, compresslevel, block_size=block_size, eof=i == len(buckets) - 1, out=d_z, table=False)
+            out.write(d_z[:zbytes].cpu().tobytes())
+            written += nbytes
+        if not buckets:
+            out.write(EOF_BLOCK)                                 # (an empty order: the empty BGZF file)
+    except Exception as e:
+        if out is not output:
+            out.close()
+        note = "permute_records: the output written so far was closed and is incomplete"
+        e.args = ((f"{e.args[0]} ({note})",) + e.args[1:]) if e.args and isinstance(e.args[0], str) else e.args + (note,)
+        raise
+    if out is not output:
+        out.close()
+    return len(order), written
+
+
+def permute_records(file, order, output, record_lines=4, *, lengths=None, chunk_bytes=1 << 30, compresslevel=6, block_size=MAX_BLOCK_INPUT,
+                    first_byte=None, delimiter=b"\n"):
+    """Write the records of a BGZF file in another order: order[j] is the number of the record written j-th.  Every record number
+    appears at most once; a subset is allowed, which makes a shuffle, the head of a sorted file and a sample one call.  A number that is
+    negative, repeated or -- once the record count is known: at once with lengths -- out of range is a ValueError before the output is
+    opened.  lengths: SortKeyResult.lengths of the same file; without it a pass over the file gets them first.  output (a path or a
+    writable binary file) becomes a complete BGZF file (compresslevel, block_size) of the records in that order, whole; a last record
+    whose last line lacks its delimiter gets one, so no two lines are ever glued together.
+    The output is cut at record boundaries into buckets of at most chunk_bytes (a bucket takes at least one record).  For every
+    bucket the file is decoded once, its records are copied on the device to their places in a buffer of the largest bucket's size, and
+    the buffer is compressed there.  A file of at most chunk_bytes costs one decode; a larger one costs ceil(text / chunk_bytes)
+    decodes, with device memory bounded by chunk_bytes.  A file that holds more or fewer records than lengths is a ValueError that
+    says the files are out of step; a record whose length is not its lengths entry is a ValueError that names it.  If anything is
+    raised the output is closed, and the error says that it is incomplete.  -> (records written, bytes written, uncompressed)."""
+    if _is_path(file):
+        _permute_order(order, None if lengths is None else len(_permute_lengths(lengths)))      # (judged before a file is opened)
+        _partition_delimiter(delimiter), _grep_record_args(record_lines, None, first_byte), _check_block_size(block_size)
+        with _builtin_open(file, "rb") as f:
+            return permute_records(f, order, output, record_lines, lengths=lengths, chunk_bytes=chunk_bytes, compresslevel=compresslevel,
+                                   block_size=block_size, first_byte=first_byte, delimiter=delimiter)
+    return _permute_file(file, None, order, output, record_lines, lengths, chunk_bytes, compresslevel, block_size, first_byte, delimiter)
+
+
+class SortResult:
+    """What sort_records() did: order (int64: order[j] is the input's record that was written j-th), records, bytes (written,
+    uncompressed) and key_width."""
+
+    def __init__(self, order, records, nbytes, key_width):
+        self.order, self.records, self.bytes, self.key_width = order, int(records), int(nbytes), int(key_width)
+
+    def __len__(self):
+        return self.records
+
+    def __repr__(self):
+        return f"<SortResult: {self.records} records, {self.bytes} bytes, keys of {self.key_width} bytes>"
+
+
+def _sort_file(fp, ctx, output, key, record_lines, reverse, meta, truncate, chunk_bytes, compresslevel, block_size, first_byte, delimiter, max_record,
+               allow_short):
+    _, _, k, _ = _sort_conf(key, record_lines, meta, truncate, reverse, first_byte, delimiter)
+    _check_block_size(block_size)
+    keys = _sort_key_file(fp, ctx, key, record_lines, meta, truncate, reverse, first_byte, delimiter, None, None, 0, max_record, allow_short)
+    order = _sort(ctx, keys, False) if keys.key_width and keys.records else np.arange(keys.records, dtype=np.int64)
+    records, nbytes = _permute_file(fp, ctx, order, output, k, keys.lengths, chunk_bytes, compresslevel, block_size, first_byte, delimiter, max_record)
+    return SortResult(order, records, nbytes, keys.key_width)
+
+
+def sort_records(file, output, key, record_lines=4, *, reverse=False, meta=None, truncate=False, chunk_bytes=1 << 30, compresslevel=6,
+                 block_size=MAX_BLOCK_INPUT, first_byte=None, delimiter=b"\n", max_record=64 << 20, allow_short=False):
+    """Sort the records of a BGZF file on the GPU: sort_key_records(), sort_keys() and permute_records() in a row.  key, meta and truncate
+    are those of sort_key_records(); reverse=True turns every part's order round (meta lines stay in front).  Records with equal keys
+    keep the order of the input.  output, chunk_bytes, compresslevel and block_size are those of permute_records().  -> SortResult."""
+    if _is_path(file):
+        _sort_conf(key, record_lines, meta, truncate, reverse, first_byte, delimiter)      # (judged before the file is opened)
+        _check_block_size(block_size)
+        with _builtin_open(file, "rb") as f:
+            return sort_records(f, output, key, record_lines, reverse=reverse, meta=meta, truncate=truncate, chunk_bytes=chunk_bytes,
+                                compresslevel=compresslevel, block_size=block_size, first_byte=first_byte, delimiter=delimiter, max_record=max_record,
+                                allow_short=allow_short)
+    return _sort_file(file, None, output, key, record_lines, reverse, meta, truncate, chunk_bytes, compresslevel, block_size, first_byte, delimiter,
+                      max_record, allow_short)
 
 
 def _per_file(value, n_files, name):
@@ -3673,6 +4075,51 @@ class BgzfReader(io.BufferedIOBase):
         try:
             return _dedup_file(self._fp, self._ctx, output, duplicates, record_lines, compresslevel, block_size, seq_line, first, length, ignore_case,
                                canonical, first_byte, delimiter, start, stop, first_record, max_record, allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def sort_key_records(self, key, record_lines=4, *, meta=None, truncate=False, first_byte=None, delimiter=b"\n", start=None, stop=None,
+                         first_record=0, max_record=64 << 20, allow_short=False):
+        """bgzf.sort_key_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("sort_key_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _sort_key_file(self._fp, self._ctx, key, record_lines, meta, truncate, False, first_byte, delimiter, start, stop, first_record,
+                                  max_record, allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def sort_keys(self, keys, *, rank=False):
+        """bgzf.sort_keys() on this reader's context"""
+        return _sort(self._ctx, keys, rank)
+
+    def permute_records(self, order, output, record_lines=4, *, lengths=None, chunk_bytes=1 << 30, compresslevel=6, block_size=MAX_BLOCK_INPUT,
+                        first_byte=None, delimiter=b"\n"):
+        """bgzf.permute_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("permute_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _permute_file(self._fp, self._ctx, order, output, record_lines, lengths, chunk_bytes, compresslevel, block_size, first_byte, delimiter)
+        finally:
+            self._fp.seek(at)
+
+    def sort_records(self, output, key, record_lines=4, *, reverse=False, meta=None, truncate=False, chunk_bytes=1 << 30, compresslevel=6,
+                     block_size=MAX_BLOCK_INPUT, first_byte=None, delimiter=b"\n", max_record=64 << 20, allow_short=False):
+        """bgzf.sort_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("sort_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _sort_file(self._fp, self._ctx, output, key, record_lines, reverse, meta, truncate, chunk_bytes, compresslevel, block_size, first_byte,
+                              delimiter, max_record, allow_short)
         finally:
             self._fp.seek(at)
 
