@@ -1200,6 +1200,110 @@ int zngamd_bgzf_place_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_le
                               int32_t first_byte, uint64_t record_base, int32_t *status, const uint64_t *dst, const uint32_t *length,
                               uint64_t n, void *d_out, uint64_t out_cap, zngamd_bgzf_place_totals *totals);
 
+/* ---- BGZF screen (zlib_ng_amd/bgzf.py: KmerSet, screen_records, screen_filter).  Which reads come from
+ * something that should not be in the library -- bbduk ref=phix.fa k=31, fastq_screen, rRNA depletion, spike-in and vector removal: a
+ * set of the k-mers of up to 64 references on the device, and every k-mer of every read looked up in it.  The rule:
+ *   bases      A, C, G, T in either case are 0, 1, 2, 3; U and u count as T; every other byte is invalid.
+ *   forward    a k-mer is k consecutive bytes of ONE sequence, 1 <= k <= 31; its forward code is the sum over i of base_i << 2 (k - 1 - i):
+ *              the first base is the most significant.
+ *   canonical  with ZNGAMD_KMER_CANONICAL the code is the smaller of the forward code and the code of the reverse complement (the
+ *              complement of base b is 3 - b).  A k-mer with an invalid byte has no code.
+ *   empty      every code is below 4^31 = 2^62; the all-ones word marks an empty slot.
+ *   set        made from R references, 1 <= R <= 64, each a byte string: every code that occurs at some position of some reference, with
+ *              a 64-bit mask whose bit j is set when reference j holds the code.  k-mers do not span references; a reference shorter
+ *              than k adds nothing; a set may be empty.
+ *   record     the sequence is the body of seq_line, n bytes (the record model is that of the key call above; a line the record lacks
+ *              is an empty body); its positions are p = 0 .. n - k, none when n < k.  kmers: the positions whose k-mer is valid.  hits: the
+ *              valid positions whose code is in the set.  refs: the OR of the masks of the hit codes.  best: the reference that the most
+ *              hit positions count for -- a position counts for every reference whose bit is set in its mask -- the lowest number among
+ *              equals, ZNGAMD_KMER_NONE when hits == 0.  best_hits: the count for best.
+ *   match      a record is matched when hits >= min_hits (min_hits >= 1).
+ * The set is an opaque object: read-only once made, bound to the context it was made in (free it before that context is destroyed), and
+ * usable by any number of later calls.  Its table is cap slots of 16 bytes, code and mask; cap is the smallest power of two that is
+ * >= 2 x positions (so >= 2 x valid; for the load call: >= 2 n) and >= 64; a code's home slot is mix(code) & (cap - 1) with the mix of the
+ * key call above, probing is linear with wrap.  At most ZNGAMD_KMER_MAX_POSITIONS reference positions (the sum of len - k + 1 over the
+ * references of at least k bytes).
+ *   _build   the references lie one behind the other in seqs (host memory): reference j is seqs[offsets[j] .. offsets[j + 1]); offsets
+ *            has n_refs + 1 entries that do not decrease.  The set is built on the GPU.  info (may be NULL): k, flags, n_refs, positions,
+ *            valid (the positions whose k-mer is valid), distinct (the codes of the set), cap.
+ *   _load    the same table from n (code, mask) pairs; a code that appears twice ORs its masks.  ZNGAMD_E_ARG when a code is >= 4^k, or
+ *            a mask is 0 or has a bit at or above n_refs.  info: positions = valid = n.
+ *   _export  the set's pairs in no particular order; *n = distinct.  ZNGAMD_BUF_ERROR, with *n set, when cap_pairs < distinct.
+ *   _describe  the info of a set; _free releases it (NULL: nothing happens).
+ * ZNGAMD_E_ARG before the context is touched: k out of range, n_refs 0 or above 64, offsets that decrease, too many positions, unknown
+ * flags, a NULL pointer (seqs may be NULL when the references hold no byte, codes and masks when n = 0). */
+#define ZNGAMD_KMER_CANONICAL     1u
+#define ZNGAMD_KMER_NONE          0xFFFFFFFFu
+#define ZNGAMD_KMER_MAX_K         31u
+#define ZNGAMD_KMER_MAX_REFS      64u
+#define ZNGAMD_KMER_MAX_POSITIONS (1ull << 28)
+typedef struct zngamd_kmer_set zngamd_kmer_set;
+typedef struct {
+    uint32_t k;
+    uint32_t flags;           /* ZNGAMD_KMER_CANONICAL */
+    uint32_t n_refs;
+    uint32_t reserved;
+    uint64_t positions;       /* reference positions (pairs given, for a loaded set) */
+    uint64_t valid;           /* of them, those whose k-mer is valid */
+    uint64_t distinct;        /* codes in the set */
+    uint64_t cap;             /* slots of the table */
+} zngamd_kmer_set_info;                                                                           /* 48 B */
+int zngamd_kmer_set_build(zngamd_ctx *ctx, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_refs, uint32_t k, uint32_t flags,
+                          zngamd_kmer_set **out, zngamd_kmer_set_info *info);
+int zngamd_kmer_set_load(zngamd_ctx *ctx, uint32_t k, uint32_t flags, uint32_t n_refs, const uint64_t *codes, const uint64_t *masks,
+                         uint64_t n, zngamd_kmer_set **out, zngamd_kmer_set_info *info);
+int zngamd_kmer_set_export(zngamd_kmer_set *set, uint64_t *codes, uint64_t *masks, uint64_t cap_pairs, uint64_t *n);
+int zngamd_kmer_set_describe(const zngamd_kmer_set *set, zngamd_kmer_set_info *info);
+void zngamd_kmer_set_free(zngamd_kmer_set *set);
+
+/* The screen of a window: the window arguments, delimiter and flags of the key call, the rule above with the k and flags of the set.
+ * rows: one zngamd_bgzf_screen_row per record in record order.  totals: those of zngamd_bgzf_key_totals, then kmers, hits (summed
+ * over the records) and matched (the records with hits >= min_hits).  bad, tail_off, short_lines, _FINAL, rows_cap < seen
+ * (ZNGAMD_BUF_ERROR: no row is written, the totals are valid) and the alloc form behave exactly as in the key call.  ZNGAMD_E_ARG before
+ * the context is touched: what the key call refuses, conf.flags or a reserved word set, min_hits == 0, set NULL, a set made in
+ * another context.  Device memory beside the tiles: 8 bytes per line of the text, and in the host form 24 bytes per record. */
+typedef struct {
+    uint32_t record_lines;  /* 1 .. 64 */
+    int32_t  seq_line;      /* 0 <= s < record_lines */
+    int32_t  first_byte;    /* 0 .. 255; -1: no check */
+    uint32_t min_hits;      /* >= 1 */
+    uint32_t flags;         /* 0: none yet */
+    uint32_t reserved[11];  /* 0 */
+} zngamd_bgzf_screen_conf;                                                                        /* 64 B */
+typedef struct {
+    uint64_t refs;          /* the OR of the masks of the hit codes */
+    uint32_t kmers;         /* valid positions */
+    uint32_t hits;          /* of them, those whose code is in the set */
+    uint32_t best;          /* the reference with the most hit positions; ZNGAMD_KMER_NONE */
+    uint32_t best_hits;     /* its count */
+} zngamd_bgzf_screen_row;                                                                         /* 24 B */
+typedef struct {
+    uint64_t seen;            /* as zngamd_bgzf_key_totals ... */
+    uint64_t bytes_in;
+    uint64_t bases;
+    uint64_t tail_off;
+    uint64_t bad_record;
+    uint64_t bad_src;
+    uint32_t covered;
+    uint32_t short_lines;
+    uint32_t bad;
+    uint32_t reserved;
+    uint64_t kmers;           /* ... then the valid positions of all records */
+    uint64_t hits;            /* the hit positions of all records */
+    uint64_t matched;         /* records with hits >= min_hits */
+} zngamd_bgzf_screen_totals;                                                                      /* 88 B */
+int zngamd_bgzf_screen_records_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                   uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_screen_conf *conf,
+                                   const zngamd_kmer_set *set, uint64_t record_base, void *d_scratch, uint64_t scratch_cap,
+                                   int32_t *d_status, zngamd_bgzf_screen_row *d_rows, uint64_t rows_cap,
+                                   zngamd_bgzf_screen_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; status and the rows come back.  With alloc (rows = NULL, rows_cap 0) the
+ * caller's memory is asked for seen * 24 bytes once seen is known and not 0; NULL from it: ZNGAMD_MEM_ERROR. */
+int zngamd_bgzf_screen_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                               uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_screen_conf *conf,
+                               const zngamd_kmer_set *set, uint64_t record_base, int32_t *status, zngamd_bgzf_screen_row *rows,
+                               uint64_t rows_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_screen_totals *totals);
+
 /* ---- BGZF overlap (zlib_ng_amd/bgzf.py: overlap_records).  The one preprocessing step that needs both mates
  * of a pair at once: where the two reads of a pair lie over each other, and with that the adapter read-through cut off, bases
  * corrected and the pair merged into one read -- fastp's overlap analysis (-c, -m), bbmerge, PEAR, FLASH, vsearch

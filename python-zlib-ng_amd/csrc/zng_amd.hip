@@ -17,6 +17,7 @@
 #include "za_qc.hip"
 #include "za_dedup.hip"
 #include "za_sort.hip"
+#include "za_screen.hip"
 #include "za_overlap.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
@@ -73,6 +74,10 @@ static_assert(sizeof(zngamd_bgzf_key_totals) == sizeof(ZaKeyTotals) && sizeof(Za
               sizeof(zngamd_bgzf_key_conf) == 64 && ZNGAMD_BGZF_KEY_IGNORE_CASE == ZA_KEY_IGNORE_CASE && ZNGAMD_BGZF_KEY_CANONICAL == ZA_KEY_CANONICAL &&
               ZNGAMD_BGZF_KEY_SEED0 == ZA_KEY_SEED0 && ZNGAMD_BGZF_KEY_SEED1 == ZA_KEY_SEED1 && sizeof(zngamd_dedup_totals) == sizeof(ZaDedupTotals) &&
               sizeof(ZaDedupTotals) == 48, "bgzf dedup layout");
+static_assert(sizeof(zngamd_bgzf_screen_totals) == sizeof(ZaScreenTotals) && sizeof(ZaScreenTotals) == 88 && offsetof(ZaScreenTotals, covered) == offsetof(zngamd_bgzf_screen_totals, covered) &&
+              offsetof(ZaScreenTotals, tail_off) == offsetof(zngamd_bgzf_key_totals, tail_off) && offsetof(ZaScreenTotals, kmers) == sizeof(zngamd_bgzf_key_totals) &&
+              sizeof(zngamd_bgzf_screen_row) == sizeof(ZaScreenRow) && sizeof(ZaScreenRow) == 24 && sizeof(zngamd_bgzf_screen_conf) == 64 && sizeof(ZaKmerSlot) == 16 &&
+              sizeof(zngamd_kmer_set_info) == 48 && ZNGAMD_KMER_CANONICAL == ZA_KMER_CANONICAL && ZNGAMD_KMER_NONE == ZA_KMER_NONE, "bgzf screen layout");
 static_assert(sizeof(zngamd_bgzf_overlap_totals) == sizeof(ZaOvlTotals) && sizeof(ZaOvlTotals) == 160 && offsetof(ZaOvlTotals, covered) == offsetof(zngamd_bgzf_overlap_totals, covered) &&
               offsetof(ZaOvlTotals, mismatch_sum) == offsetof(zngamd_bgzf_overlap_totals, mismatch_sum) && offsetof(ZaOvlTotals, mismatch_sum) == (ZA_OVL_SUMS - 1u) * 8u &&
               sizeof(zngamd_bgzf_overlap_row) == sizeof(ZaOvlRow) && sizeof(ZaOvlRow) == 16 && sizeof(zngamd_bgzf_overlap_conf) == 64 &&
@@ -208,6 +213,10 @@ struct zngamd_ctx {
     // records in another order (za_sort.hip, section 5f.9; line starts are gr_start): the totals and faults of the key and place passes; the
     // host forms' rows and lengths, keys, work area, order[] and rank[], dst[]
     DevBuf<unsigned long long> so_tot, so_key, so_tab, so_dst; DevBuf<uint8_t> so_row; DevBuf<uint32_t> so_len, so_ord, so_rank;
+    // reads screened against reference k-mers (za_screen.hip, section 5f.10; line starts are gr_start): the totals and first fault of the
+    // screen pass, or the two counts of a set being made, or the cursor of an export; the host form's rows; references, pairs and exports on
+    // their way (a set's table is the set's own)
+    DevBuf<unsigned long long> sc_tot; DevBuf<ZaScreenRow> sc_row; DevBuf<uint8_t> sc_tmp;
     // pairs laid over each other (za_overlap.hip, section 5f.8; line starts, lengths, table, labels and the totals' words are gr_start, cl_len,
     // cl_tab, pt_lab and tr_tot): the overlap rows
     DevBuf<ZaOvlRow> ov_row;
@@ -368,6 +377,7 @@ void zngamd_ctx_destroy(zngamd_ctx *c)
     c->qc_tot.release(); c->qc_tab.release(); c->qc_row.release();
     c->dd_tot.release(); c->dd_first.release(); c->dd_row.release(); c->dd_tab.release(); c->dd_count.release();
     c->so_tot.release(); c->so_key.release(); c->so_tab.release(); c->so_dst.release(); c->so_row.release(); c->so_len.release(); c->so_ord.release(); c->so_rank.release();
+    c->sc_tot.release(); c->sc_row.release(); c->sc_tmp.release();
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_up) (void)hipHostFree(c->h_up);
     if (c->h_tab) (void)hipHostFree(c->h_tab);
@@ -5123,6 +5133,273 @@ try {
     if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- reads screened against reference k-mers (za_screen.hip)
+// The set: read-only once made.  The table is its own; everything else a call needs is the context's.
+struct zngamd_kmer_set {
+    zngamd_ctx *ctx = nullptr;
+    zngamd_kmer_set_info info = {};
+    ZaKmerSlot *tab = nullptr;
+};
+
+// the slots of the table for n insertions: the smallest power of two that is >= 2 n and >= ZA_KMER_MIN_CAP (n <= ZNGAMD_KMER_MAX_POSITIONS)
+static uint64_t kmer_cap(uint64_t n)
+{
+    uint64_t cap = ZA_KMER_MIN_CAP;
+    while (cap < 2u * n) cap <<= 1;
+    return cap;
+}
+
+static bool kmer_rule_ok(uint32_t k, uint32_t flags, uint32_t n_refs)
+{
+    return k >= 1u && k <= ZNGAMD_KMER_MAX_K && !(flags & ~ZNGAMD_KMER_CANONICAL) && n_refs >= 1u && n_refs <= ZNGAMD_KMER_MAX_REFS;
+}
+
+// a set with an empty table of kmer_cap(n) slots in *out (the caller holds the context's mutex); acc = sc_tot[0 .. 2) zeroed
+static int kmer_set_new(zngamd_ctx *c, uint32_t k, uint32_t flags, uint32_t n_refs, uint64_t n, zngamd_kmer_set **out)
+{
+    zngamd_kmer_set *s = new zngamd_kmer_set;
+    s->ctx = c; s->info.k = k; s->info.flags = flags; s->info.n_refs = n_refs; s->info.positions = n; s->info.cap = kmer_cap(n);
+    *out = s;                                                                       // (the caller frees it when a later step fails)
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMalloc((void **)&s->tab, (size_t)s->info.cap * sizeof(ZaKmerSlot)));
+    HIPCHK(c, c->sc_tot.ensure(2));
+    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, 16, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_kmer_clear, dim3((uint32_t)((s->info.cap + 255u) / 256u)), dim3(256), 0, c->stream, s->tab, s->info.cap); }
+    return ZNGAMD_OK;
+}
+
+// [the host waits for the two counts]: valid (unless the caller knows it) and distinct
+static int kmer_set_counts(zngamd_ctx *c, zngamd_kmer_set *s, bool valid_too)
+{
+    unsigned long long acc[2] = {0, 0};
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(acc, c->sc_tot.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (valid_too) s->info.valid = acc[0];
+    s->info.distinct = acc[1];
+    return ZNGAMD_OK;
+}
+
+static void kmer_set_drop(zngamd_kmer_set *s)
+{
+    if (s->tab) (void)hipFree(s->tab);
+    delete s;
+}
+
+int zngamd_kmer_set_build(zngamd_ctx *c, const uint8_t *seqs, const uint64_t *offsets, uint32_t n_refs, uint32_t k, uint32_t flags, zngamd_kmer_set **out,
+                          zngamd_kmer_set_info *info)
+try {
+    if (!out || !offsets || !kmer_rule_ok(k, flags, n_refs)) return ZNGAMD_E_ARG;
+    uint64_t positions = 0;
+    for (uint32_t j = 0; j < n_refs; j++) {
+        if (offsets[j + 1u] < offsets[j]) return ZNGAMD_E_ARG;
+        const uint64_t len = offsets[j + 1u] - offsets[j];
+        if (len >= k) positions += len - k + 1u;
+        if (positions > ZNGAMD_KMER_MAX_POSITIONS) return ZNGAMD_E_ARG;
+    }
+    const uint64_t first = offsets[0], bytes = offsets[n_refs] - first;
+    if ((bytes && !seqs) || !c) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    zngamd_kmer_set *s = nullptr;
+    int r = kmer_set_new(c, k, flags, n_refs, positions, &s);
+    if (!r && positions) r = [&]() -> int {
+        // the references and their offsets (taken from the first one's) behind each other in sc_tmp
+        const size_t off_at = (size_t)((bytes + 7u) & ~7ull);
+        std::vector<unsigned long long> rel(n_refs + 1u);
+        for (uint32_t j = 0; j <= n_refs; j++) rel[j] = offsets[j] - first;
+        HIPCHK(c, c->sc_tmp.ensure(off_at + (size_t)(n_refs + 1u) * 8u));
+        HIPCHK(c, hipMemcpyAsync(c->sc_tmp.p, seqs + first, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->sc_tmp.p + off_at, rel.data(), rel.size() * 8u, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));                                // (rel leaves with this scope)
+        uint64_t longest = 0;
+        for (uint32_t j = 0; j < n_refs; j++) longest = std::max<uint64_t>(longest, rel[j + 1u] - rel[j]);
+        // four strips to a workgroup; beyond what the device holds at once a wave walks on to its next strip
+        const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_SCREEN_WG_PER_CU;
+        const uint32_t gx = (uint32_t)std::min<uint64_t>((longest + 255u) / 256u, slots);
+        { ProfScope ps(c, ZNGAMD_K_GATHER);
+          hipLaunchKernelGGL(za_k_kmer_insert, dim3(gx, n_refs), dim3(256), 0, c->stream, c->sc_tmp.p, (const unsigned long long *)(c->sc_tmp.p + off_at), k,
+                             flags & ZNGAMD_KMER_CANONICAL, s->tab, s->info.cap - 1u, c->sc_tot.p); }
+        return ZNGAMD_OK;
+    }();
+    if (!r) r = kmer_set_counts(c, s, true);
+    if (r) { if (s) kmer_set_drop(s); return r; }
+    if (info) *info = s->info;
+    *out = s;
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_kmer_set_load(zngamd_ctx *c, uint32_t k, uint32_t flags, uint32_t n_refs, const uint64_t *codes, const uint64_t *masks, uint64_t n,
+                         zngamd_kmer_set **out, zngamd_kmer_set_info *info)
+try {
+    if (!out || !kmer_rule_ok(k, flags, n_refs) || n > ZNGAMD_KMER_MAX_POSITIONS || (n && (!codes || !masks))) return ZNGAMD_E_ARG;
+    const uint64_t code_end = 1ull << (2u * k), mask_bad = n_refs == 64u ? 0ull : ~0ull << n_refs;
+    for (uint64_t i = 0; i < n; i++) if (codes[i] >= code_end || !masks[i] || (masks[i] & mask_bad)) return ZNGAMD_E_ARG;
+    if (!c) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    zngamd_kmer_set *s = nullptr;
+    int r = kmer_set_new(c, k, flags, n_refs, n, &s);
+    if (!r && n) r = [&]() -> int {
+        HIPCHK(c, c->sc_tmp.ensure((size_t)n * 16u));
+        unsigned long long *d_codes = (unsigned long long *)c->sc_tmp.p, *d_masks = d_codes + n;
+        HIPCHK(c, hipMemcpyAsync(d_codes, codes, (size_t)n * 8u, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_masks, masks, (size_t)n * 8u, hipMemcpyHostToDevice, c->stream));
+        { ProfScope ps(c, ZNGAMD_K_GATHER);
+          hipLaunchKernelGGL(za_k_kmer_load, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, c->stream, d_codes, d_masks, n, s->tab, s->info.cap - 1u, c->sc_tot.p); }
+        return ZNGAMD_OK;
+    }();
+    if (!r) r = kmer_set_counts(c, s, false);
+    if (r) { if (s) kmer_set_drop(s); return r; }
+    s->info.valid = n;
+    if (info) *info = s->info;
+    *out = s;
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_kmer_set_export(zngamd_kmer_set *s, uint64_t *codes, uint64_t *masks, uint64_t cap_pairs, uint64_t *n)
+try {
+    if (!s || !n || !s->ctx || (cap_pairs && (!codes || !masks))) return ZNGAMD_E_ARG;
+    zngamd_ctx *c = s->ctx;
+    std::lock_guard<std::mutex> g(c->mu);
+    const uint64_t d = s->info.distinct;
+    *n = d;
+    if (cap_pairs < d) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    if (!d) return ZNGAMD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->sc_tmp.ensure((size_t)d * 16u)); HIPCHK(c, c->sc_tot.ensure(2));
+    unsigned long long *d_codes = (unsigned long long *)c->sc_tmp.p, *d_masks = d_codes + d;
+    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, 8, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_kmer_export, dim3((uint32_t)((s->info.cap + 255u) / 256u)), dim3(256), 0, c->stream, s->tab, s->info.cap, d_codes, d_masks, d, c->sc_tot.p); }
+    HIPCHK(c, hipGetLastError());
+    unsigned long long wrote = 0;
+    HIPCHK(c, hipMemcpyAsync(&wrote, c->sc_tot.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(codes, d_codes, (size_t)d * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(masks, d_masks, (size_t)d * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (wrote != d) return fail(c, ZNGAMD_E_HIP, "the set's table does not hold the codes it was made with");
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_kmer_set_describe(const zngamd_kmer_set *s, zngamd_kmer_set_info *info)
+{
+    if (!s || !info) return ZNGAMD_E_ARG;
+    *info = s->info;
+    return ZNGAMD_OK;
+}
+
+void zngamd_kmer_set_free(zngamd_kmer_set *s)
+{
+    if (!s) return;
+    if (s->ctx) {
+        std::lock_guard<std::mutex> g(s->ctx->mu);
+        (void)hipSetDevice(s->ctx->device);
+        (void)hipStreamSynchronize(s->ctx->stream);                                 // (no launch of this context still reads the table)
+        kmer_set_drop(s);
+    } else kmer_set_drop(s);
+}
+
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool screen_args_ok(const zngamd_ctx *c, int delim, uint32_t flags, const zngamd_bgzf_screen_conf *cf, const zngamd_kmer_set *set,
+                           const zngamd_bgzf_screen_row *rows, bool alloc, const zngamd_bgzf_screen_totals *totals)
+{
+    if (!totals || !cf || !set || (flags & ~ZNGAMD_BGZF_GREP_FINAL) || delim < 0 || delim > 255) return false;
+    if (!grep_records_ok(cf->record_lines, -1, cf->first_byte)) return false;
+    if (cf->seq_line < 0 || cf->seq_line >= (int32_t)cf->record_lines || cf->flags || !cf->min_hits) return false;
+    for (uint32_t v : cf->reserved) if (v) return false;
+    return (rows || alloc) && c && set->ctx == c;
+}
+
+// The lines pass for the delimiters alone, [the host waits for the line count], lines, screen, close, [the host waits for the totals].
+// own: the rows go to sc_row; otherwise to d_rows when rows_cap holds them, and nowhere (*rows_short) when it does not.
+static int bgzf_screen_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, const zngamd_bgzf_screen_conf &cf, const zngamd_kmer_set *set,
+                           uint64_t record_base, bool own, ZaScreenRow *d_rows, uint64_t rows_cap, bool *rows_short, zngamd_bgzf_screen_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    *rows_short = false;
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
+    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+    if (r) return r;
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const uint64_t lines = R.lines, nrec = R.nrec;
+    constexpr size_t TOT_WORDS = sizeof(ZaScreenTotals) / 8u;                            // then the fault
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->sc_tot.ensure(TOT_WORDS + 1u));
+    if (own) { HIPCHK(c, c->sc_row.ensure(nrec)); d_rows = c->sc_row.p; }
+    else if (rows_cap < nrec) { *rows_short = true; d_rows = nullptr; }
+    // four records to a workgroup, at most ZA_SCREEN_WG_PER_CU workgroups per CU: beyond that a wave walks on to its next record
+    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_SCREEN_WG_PER_CU;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    const ZaScreenPar P = {k, (uint32_t)cf.seq_line, cf.first_byte, cf.min_hits, w.delim, set->info.k, set->info.flags & ZNGAMD_KMER_CANONICAL};
+    ZaScreenTotals *d_tot = (ZaScreenTotals *)c->sc_tot.p;
+    unsigned long long *d_bad = c->sc_tot.p + TOT_WORDS;
+    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, TOT_WORDS * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_screen, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, P, (const ZaKmerSlot *)set->tab,
+                         set->info.cap - 1u, d_rows, d_tot, d_bad);
+      hipLaunchKernelGGL(za_k_screen_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+int zngamd_bgzf_screen_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                   uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_screen_conf *conf, const zngamd_kmer_set *set,
+                                   uint64_t record_base, void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_screen_row *d_rows, uint64_t rows_cap,
+                                   zngamd_bgzf_screen_totals *totals)
+try {
+    if (!screen_args_ok(c, delim, flags, conf, set, d_rows, false, totals)) return ZNGAMD_E_ARG;
+    if ((n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    bool rows_short = false;
+    int r = bgzf_screen_dev(c, w, flags, *conf, set, record_base, false, (ZaScreenRow *)d_rows, rows_cap, &rows_short, totals);
+    if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (rows_short && !totals->bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_screen_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                               uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_screen_conf *conf, const zngamd_kmer_set *set,
+                               uint64_t record_base, int32_t *status, zngamd_bgzf_screen_row *rows, uint64_t rows_cap, zngamd_alloc_fn alloc, void *user,
+                               zngamd_bgzf_screen_totals *totals)
+try {
+    if (!screen_args_ok(c, delim, flags, conf, set, rows, alloc != nullptr, totals)) return ZNGAMD_E_ARG;
+    if ((!in && in_len) || (n_members && (!members || !status)) || (alloc && rows)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    bool rows_short = false;
+    r = bgzf_screen_dev(c, w, flags, *conf, set, record_base, true, nullptr, 0, &rows_short, totals);
+    if (r) return r;
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    const uint64_t seen = totals->seen;
+    if (!totals->covered || totals->bad || !seen) return ZNGAMD_OK;
+    if (alloc) {
+        rows = (zngamd_bgzf_screen_row *)alloc(user, seen * sizeof(zngamd_bgzf_screen_row));
+        if (!rows) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
+    } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    HIPCHK(c, hipMemcpyAsync(rows, c->sc_row.p, (size_t)seen * sizeof(ZaScreenRow), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return ZNGAMD_OK;
 } ZA_ABI_GUARD
 

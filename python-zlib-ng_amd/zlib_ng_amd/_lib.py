@@ -4,6 +4,7 @@ There is no fallback: if the library is missing, or no MI355X-class GPU is usabl
 works but the first call that needs the engine raises ``RuntimeError``.
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import mmap as _mmap
@@ -91,6 +92,8 @@ SYMBOLS = [
     "zngamd_bgzf_key_records_dev", "zngamd_bgzf_key_records", "zngamd_dedup_scratch_bytes", "zngamd_dedup_keys_dev", "zngamd_dedup_keys",
     "zngamd_bgzf_sort_key_records_dev", "zngamd_bgzf_sort_key_records", "zngamd_sort_scratch_bytes", "zngamd_sort_keys_dev", "zngamd_sort_keys",
     "zngamd_bgzf_place_records_dev", "zngamd_bgzf_place_records",
+    "zngamd_kmer_set_build", "zngamd_kmer_set_load", "zngamd_kmer_set_export", "zngamd_kmer_set_describe", "zngamd_kmer_set_free",
+    "zngamd_bgzf_screen_records_dev", "zngamd_bgzf_screen_records",
     "zngamd_bgzf_overlap_records_dev", "zngamd_bgzf_overlap_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
@@ -337,6 +340,26 @@ class BgzfSortKeyTotals(C.Structure):          # zngamd_bgzf_sort_key_totals
         return self.seen
 
 
+KMER_CANONICAL, KMER_NONE, KMER_MAX_K, KMER_MAX_REFS, KMER_MAX_POSITIONS = 1, 0xFFFFFFFF, 31, 64, 1 << 28      # ZNGAMD_KMER_*
+SCREEN_ROW_DTYPE = np.dtype([("refs", "<u8"), ("kmers", "<u4"), ("hits", "<u4"), ("best", "<u4"), ("best_hits", "<u4")])      # zngamd_bgzf_screen_row
+
+
+class KmerSetInfo(C.Structure):                # zngamd_kmer_set_info
+    _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("n_refs", C.c_uint32), ("reserved", C.c_uint32), ("positions", C.c_uint64),
+                ("valid", C.c_uint64), ("distinct", C.c_uint64), ("cap", C.c_uint64)]
+
+
+class BgzfScreenConf(C.Structure):             # zngamd_bgzf_screen_conf
+    _fields_ = [("record_lines", C.c_uint32), ("seq_line", C.c_int32), ("first_byte", C.c_int32), ("min_hits", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 11)]
+
+
+class BgzfScreenTotals(C.Structure):           # zngamd_bgzf_screen_totals
+    _fields_ = [("seen", C.c_uint64), ("bytes_in", C.c_uint64), ("bases", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64),
+                ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("reserved", C.c_uint32),
+                ("kmers", C.c_uint64), ("hits", C.c_uint64), ("matched", C.c_uint64)]
+
+
 class BgzfPlaceTotals(C.Structure):            # zngamd_bgzf_place_totals
     _fields_ = [("seen", C.c_uint64), ("placed", C.c_uint64), ("placed_bytes", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64),
                 ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("labels_short", C.c_uint32)]
@@ -554,6 +577,17 @@ def load():
                                                         C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
             L.zngamd_bgzf_place_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_int32,
                                                     C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp]
+        if hasattr(L, "zngamd_bgzf_screen_records"):        # the set's calls; the screen: as key with the set behind the conf
+            L.zngamd_kmer_set_build.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+            L.zngamd_kmer_set_load.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, C.c_uint64, vp, vp]
+            L.zngamd_kmer_set_export.argtypes = [vp, vp, vp, C.c_uint64, vp]
+            L.zngamd_kmer_set_describe.argtypes = [vp, vp]
+            L.zngamd_kmer_set_free.argtypes = [vp]
+            L.zngamd_kmer_set_free.restype = None
+            L.zngamd_bgzf_screen_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, vp, C.c_uint64, vp,
+                                                         C.c_uint64, vp, vp, C.c_uint64, vp]
+            L.zngamd_bgzf_screen_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, vp, C.c_uint64, vp, vp,
+                                                     C.c_uint64, ALLOC_FN, vp, vp]
         if hasattr(L, "zngamd_bgzf_overlap_records"):       # as qc without the tables: overlap rows, rows and bytes with their capacities
             L.zngamd_bgzf_overlap_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp,
                                                           C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -962,6 +996,40 @@ def block_table(blocks):
     return arr, n
 
 
+class DeviceKmerSet:
+    """A zngamd_kmer_set: the table of a k-mer set on the device, read-only, bound to the context it was made in.  free() releases it;
+    so do the end of the object and the close() of its context."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    @property
+    def info(self):
+        info = KmerSetInfo()
+        if self.ctx.L.zngamd_kmer_set_describe(self.h, C.byref(info)) != OK:
+            raise ValueError("the set was freed")
+        return info
+
+    def export(self):
+        """-> (codes, masks), uint64, in no particular order"""
+        n = C.c_uint64(self.info.distinct)
+        codes, masks = np.empty(n.value, np.uint64), np.empty(n.value, np.uint64)
+        p = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
+        self.ctx._chk(self.ctx.L.zngamd_kmer_set_export(self.h, p(codes), p(masks), len(codes), C.byref(n)))
+        return codes[:n.value], masks[:n.value]
+
+    def free(self):
+        if self.h:
+            self.ctx.L.zngamd_kmer_set_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class Context:
     """One engine context = one GPU + one HIP stream + grow-only device workspaces."""
 
@@ -992,6 +1060,8 @@ class Context:
 
     def close(self):
         if self.h:
+            for kset in list(self.__dict__.get("_kmer_sets", ())):      # (a set is freed before the context it was made in)
+                kset.free()
             self.L.zngamd_ctx_destroy(self.h)
             self.h = None
 
@@ -1903,6 +1973,74 @@ class Context:
         v = lambda x: C.c_void_p(int(x)) if x else None
         tot = DedupTotals()
         r = self._chk(self.L.zngamd_dedup_keys_dev(self.h, v(d_keys), n, v(d_scratch), scratch_cap, v(d_first), v(d_count), C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def _kmer_set(self, handle):
+        kset = DeviceKmerSet(self, handle)
+        self.__dict__.setdefault("_kmer_sets", weakref.WeakSet()).add(kset)
+        return kset
+
+    def kmer_set_build(self, references, k, flags=KMER_CANONICAL):
+        """zngamd_kmer_set_build: references (a list of bytes-likes, at most 64) -> DeviceKmerSet; the set is built on the GPU"""
+        refs = [bytes(r) for r in references]
+        blob = b"".join(refs)
+        offsets = np.zeros(len(refs) + 1, np.uint64)
+        np.cumsum([len(r) for r in refs], out=offsets[1:])
+        h, info = C.c_void_p(), KmerSetInfo()
+        self._chk(self.L.zngamd_kmer_set_build(self.h, C.cast(C.c_char_p(blob), C.c_void_p) if blob else None, C.c_void_p(offsets.ctypes.data), len(refs), k,
+                                               flags, C.byref(h), C.byref(info)))
+        return self._kmer_set(h)
+
+    def kmer_set_load(self, k, flags, n_refs, codes, masks):
+        """zngamd_kmer_set_load: (code, mask) pairs (uint64 arrays of equal length) -> DeviceKmerSet"""
+        codes, masks = np.ascontiguousarray(codes, np.uint64), np.ascontiguousarray(masks, np.uint64)
+        n = len(codes)
+        if len(masks) != n:
+            raise ValueError("codes and masks are of equal length")
+        p = lambda a: C.c_void_p(a.ctypes.data) if n else None
+        h, info = C.c_void_p(), KmerSetInfo()
+        self._chk(self.L.zngamd_kmer_set_load(self.h, k, flags, n_refs, p(codes), p(masks), n, C.byref(h), C.byref(info)))
+        return self._kmer_set(h)
+
+    def bgzf_screen_records(self, data, members, text_off, text_end, delim, flags, conf, kset, record_base=0, caps=None):
+        """zngamd_bgzf_screen_records: every k-mer of every record looked up in kset (a DeviceKmerSet of this context) by conf (a
+        BgzfScreenConf) -> (code, block statuses, totals (BgzfScreenTotals), rows (SCREEN_ROW_DTYPE, one per record in record order; empty
+        when totals.bad is set)).  caps None: the rows are allocated once the engine knows how many there are; an integer: a buffer of
+        that many rows, and code is BUF_ERROR when the result needs more"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfScreenTotals()
+        box = []
+
+        def alloc(_user, nbytes):
+            box.append(np.empty(nbytes // SCREEN_ROW_DTYPE.itemsize, SCREEN_ROW_DTYPE))
+            return box[0].ctypes.data
+
+        if caps is None:
+            rp, rcap, fn = None, 0, ALLOC_FN(alloc)
+        else:
+            rcap = caps
+            rows = np.zeros(max(1, rcap), SCREEN_ROW_DTYPE)
+            rp, fn = C.c_void_p(rows.ctypes.data), ALLOC_FN()
+        r = self._chk(self.L.zngamd_bgzf_screen_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                        text_off, text_end, delim, flags, C.byref(conf), kset.h, record_base, C.c_void_p(st.ctypes.data),
+                                                        rp, rcap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        got = r == OK and tot.covered and tot.seen and not tot.bad
+        if caps is None:
+            rows_out = box[0] if got else np.empty(0, SCREEN_ROW_DTYPE)
+        else:
+            rows_out = rows[:tot.seen] if got else np.empty(0, SCREEN_ROW_DTYPE)
+        return r, st[:nm], tot, rows_out
+
+    def bgzf_screen_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, kset, record_base, d_scratch, scratch_cap,
+                                d_status, d_rows, rows_cap):
+        """zngamd_bgzf_screen_records_dev on device pointers (conf: host memory) -> (code, totals); the rows stay on the device"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfScreenTotals()
+        r = self._chk(self.L.zngamd_bgzf_screen_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
+                                                            C.byref(conf), kset.h, record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap,
+                                                            C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_sort_key_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):

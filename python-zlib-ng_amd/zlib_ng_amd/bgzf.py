@@ -42,9 +42,11 @@ file whose last entry points at it.  An index is untrusted: load() and the reade
 """
 import bisect
 import contextlib
+import hashlib
 import io
 import os
 import struct
+import weakref
 
 import numpy as np
 
@@ -54,6 +56,7 @@ __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offse
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
            "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP", "trim_records", "TrimResult", "KEPT", "TOO_SHORT", "DROPPED", "qc_records", "QcResult",
            "key_records", "KeyResult", "pair_keys", "dedup_keys", "DedupResult", "dedup_records", "dedup_paired",
+           "KmerSet", "ScreenResult", "screen_records", "screen_filter",
            "SortKey", "SortKeyResult", "SortResult", "sort_key_records", "sort_keys", "permute_records", "sort_records",
            "overlap_records", "OverlapResult", "NONE", "FOUND", "MERGED", "TOO_LONG",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
@@ -703,8 +706,8 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
     _ClassifySink -- every window's records are not selected but assigned to their nearest pattern (classify_records(), demux()), the
     sink takes what each window gives, and what its finish() returns is the result.  partition (with records, instead of patterns): a
     _PartitionSink -- every window's records are split by the labels it holds (partition_records()) -- or a _TrimSink -- they are cut
-    (trim_records()) -- or a _QcSink -- they are counted (qc_records()) -- or a _KeySink -- they are keyed (key_records()) -- or an
-    _OverlapSink -- the mates of every pair are laid over each other (overlap_records())."""
+    (trim_records()) -- or a _QcSink -- they are counted (qc_records()) -- or a _KeySink -- they are keyed (key_records()) -- or a
+    _ScreenSink -- their k-mers are looked up in a set (screen_records()) -- or an _OverlapSink -- the mates of every pair are laid over each other (overlap_records())."""
     if partition is None:
         pats, delimiter = _grep_patterns(patterns, delimiter)
         mismatches = _grep_mismatches(mismatches, pats)
@@ -1835,6 +1838,287 @@ def dedup_paired(files, outputs, record_lines=4, *, duplicates=None, compresslev
                 _partition_file(fps[f], None, labels, outs, record_lines, first_byte, delimiter, compresslevel, block_size, start[f], stop[f],
                                 first_record, max_record, allow_short)
     return res
+
+
+# ---- reads screened against reference k-mers: a k-mer set, the screen of a file, the screen and a split
+def _kmer_rule(k, canonical):
+    k = _trim_int(k, 1, _lib.KMER_MAX_K, "k")
+    if not isinstance(canonical, (bool, np.bool_)):
+        raise ValueError(f"canonical is True or False, not {canonical!r}")
+    return k, bool(canonical)
+
+
+def _kmer_names(names, n_refs):
+    if not 1 <= n_refs <= _lib.KMER_MAX_REFS:
+        raise ValueError(f"a k-mer set is made from 1 to {_lib.KMER_MAX_REFS} references, not {n_refs}")
+    if names is None:
+        return tuple(f"ref{j}" for j in range(n_refs))
+    names = tuple(n.decode() if isinstance(n, (bytes, bytearray)) else str(n) for n in names)
+    if len(names) != n_refs:
+        raise ValueError(f"names has {len(names)} entries for {n_refs} references")
+    return names
+
+
+class KmerSet:
+    """The k-mers of up to 64 references, as host data: k, canonical, names (one per reference) and codes and masks, sorted uint64
+    arrays of equal length -- every code that occurs in some reference, and the mask whose bit j says that reference j holds it.  The
+    rule of the codes is fixed and documented: A, C, G, T in either case are 0 .. 3, U counts as T, the first base of
+    a k-mer is the most significant, and with canonical the code is the smaller of the k-mer's and its reverse complement's.  The
+    device table that screen_records() reads is made on first use, one per context, and freed with the object.  len(): the distinct
+    codes.  a | b: the union of two sets of equal k, canonical and names."""
+
+    def __init__(self, k, canonical, names, codes, masks):
+        self.k, self.canonical, self.names = int(k), bool(canonical), tuple(names)
+        self.codes, self.masks = codes, masks
+        self._tables = weakref.WeakKeyDictionary()       # context -> its DeviceKmerSet
+        self._id = None
+
+    @property
+    def n_refs(self):
+        return len(self.names)
+
+    def __len__(self):
+        return len(self.codes)
+
+    @property
+    def identity(self):
+        """what two results must share to be added: the rule, the names and a digest of the pairs"""
+        if self._id is None:
+            h = hashlib.sha1(self.codes.tobytes())
+            h.update(self.masks.tobytes())
+            self._id = (self.k, self.canonical, self.names, len(self.codes), h.hexdigest())
+        return self._id
+
+    def _flags(self):
+        return _lib.KMER_CANONICAL if self.canonical else 0
+
+    def _table(self, ctx):
+        t = self._tables.get(ctx)
+        if t is None or not t.h:
+            t = self._tables[ctx] = ctx.kmer_set_load(self.k, self._flags(), self.n_refs, self.codes, self.masks)
+        return t
+
+    @classmethod
+    def from_codes(cls, k, codes, masks, n_refs, canonical=True, names=None):
+        """A set from (code, mask) pairs: a code that appears twice ORs its masks.  ValueError for a code that is not below 4**k, for a
+        mask that is 0 or has a bit at or above n_refs."""
+        k, canonical = _kmer_rule(k, canonical)
+        names = _kmer_names(names, _trim_int(n_refs, 1, _lib.KMER_MAX_REFS, "n_refs"))
+        codes, masks = np.asarray(codes), np.asarray(masks)
+        if codes.ndim != 1 or masks.shape != codes.shape or (len(codes) and (codes.dtype.kind not in "iu" or masks.dtype.kind not in "iu")):
+            raise ValueError("codes and masks are one-dimensional integer arrays of equal length")
+        if len(codes) and (codes.min() < 0 or masks.min() < 0):
+            raise ValueError("codes and masks are not negative")
+        codes, masks = codes.astype(np.uint64), masks.astype(np.uint64)
+        if len(codes) > _lib.KMER_MAX_POSITIONS:
+            raise ValueError(f"a k-mer set holds at most {_lib.KMER_MAX_POSITIONS} pairs, not {len(codes)}")
+        if len(codes) and int(codes.max()) >= 4 ** k:
+            raise ValueError(f"a code of a {k}-mer lies below 4**{k}")
+        if len(codes) and (not masks.all() or (len(names) < 64 and int(masks.max()) >> len(names))):
+            raise ValueError(f"a mask is not 0 and has no bit at or above n_refs ({len(names)})")
+        order = np.argsort(codes, kind="stable")
+        codes, masks = codes[order], masks[order]
+        if len(codes):
+            heads = np.concatenate([[True], codes[1:] != codes[:-1]])
+            at = np.nonzero(heads)[0]
+            codes, masks = codes[at], np.bitwise_or.reduceat(masks, at)
+        return cls(k, canonical, names, codes, masks)
+
+    @classmethod
+    def build(cls, references, k=31, canonical=True, names=None):
+        """The set of `references` (1 to 64 bytes-likes, or strings), built on the GPU.  k-mers do not span references; a k-mer with a byte
+        other than A, C, G, T, U in either case is in no set; a reference shorter than k adds nothing."""
+        k, canonical = _kmer_rule(k, canonical)
+        if isinstance(references, (bytes, bytearray, memoryview, str)):
+            references = [references]
+        refs = [r.encode() if isinstance(r, str) else bytes(r) for r in references]
+        names = _kmer_names(names, len(refs))
+        positions = sum(max(0, len(r) - k + 1) for r in refs)
+        if positions > _lib.KMER_MAX_POSITIONS:
+            raise ValueError(f"the references hold {positions} positions; a k-mer set takes at most {_lib.KMER_MAX_POSITIONS}")
+        ctx = zlib_ng._ctx()                                     # (the arguments are judged before a context is asked for)
+        table = ctx.kmer_set_build(refs, k, _lib.KMER_CANONICAL if canonical else 0)
+        codes, masks = table.export()
+        order = np.argsort(codes, kind="stable")
+        kset = cls(k, canonical, names, codes[order], masks[order])
+        kset._tables[ctx] = table
+        return kset
+
+    @classmethod
+    def from_fasta(cls, path, k=31, canonical=True):
+        """The set of the records of a bgzipped FASTA (at most 64): FaidxIndex.build() and fetch_seq() read it, the names are the
+        records' names"""
+        k, canonical = _kmer_rule(k, canonical)
+        index = FaidxIndex.build(path)
+        names = index.names
+        _kmer_names(names, len(names))
+        seqs = fetch_seq(path, index, [(n, 0, None) for n in names])
+        return cls.build([seqs[i] for i in range(len(names))], k, canonical, names)
+
+    def save(self, path):
+        """the set as an .npz: k, canonical, names, codes, masks"""
+        np.savez(path, k=np.int64(self.k), canonical=np.bool_(self.canonical), names=np.array(self.names, dtype=np.str_), codes=self.codes,
+                 masks=self.masks)
+
+    @classmethod
+    def load(cls, path):
+        """a set that save() wrote; it is judged as from_codes() judges its arguments"""
+        with np.load(path, allow_pickle=False) as z:
+            names = [str(n) for n in z["names"]]
+            return cls.from_codes(int(z["k"]), z["codes"], z["masks"], len(names), bool(z["canonical"]), names)
+
+    def __or__(self, other):
+        if not isinstance(other, KmerSet):
+            return NotImplemented
+        if (self.k, self.canonical, self.names) != (other.k, other.canonical, other.names):
+            raise ValueError("the union is of two k-mer sets of equal k, canonical and names")
+        return KmerSet.from_codes(self.k, np.concatenate([self.codes, other.codes]), np.concatenate([self.masks, other.masks]), self.n_refs, self.canonical,
+                                  self.names)
+
+    def __eq__(self, other):
+        return isinstance(other, KmerSet) and self.identity == other.identity
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"<KmerSet: k = {self.k}{', canonical' if self.canonical else ''}, {self.n_refs} references, {len(self)} codes>"
+
+
+class ScreenResult:
+    """What screen_records() found.  Per record, in the order of the file (int64 unless said): kmers (the positions whose k-mer is
+    valid), hits (those whose code is in the set), refs (uint64: the OR of the masks of the hit codes), best (the reference that the
+    most hit positions count for, the lowest among equals; -1 when nothing hit), best_hits (its count) and matched (bool: hits >=
+    min_hits).  The totals: records, bases (the bytes of the sequence lines), matched_records.  a + b puts the results of two shards,
+    or of two files, one behind the other, and is a ValueError when they were not made with the same set and min_hits."""
+
+    def __init__(self, kmers, hits, refs, best, best_hits, bases, min_hits, names, set_id=None):
+        self.kmers, self.hits, self.refs, self.best, self.best_hits = kmers, hits, refs, best, best_hits
+        self.records, self.bases, self.min_hits = len(hits), int(bases), int(min_hits)
+        self.names, self.set_id = tuple(names), set_id
+        self.matched = hits >= self.min_hits
+        self.matched_records = int(self.matched.sum())
+
+    def __len__(self):
+        return self.records
+
+    def by_reference(self):
+        """int64, one per reference: the records whose best reference it is"""
+        return np.bincount(self.best[self.best >= 0], minlength=len(self.names)).astype(np.int64)
+
+    def drop(self):
+        """uint8, one per record, 1 for a matched one: the drop= of trim_records()"""
+        return self.matched.astype(np.uint8)
+
+    def labels(self, matched_class=1, unmatched_class=0):
+        """int64, one per record for partition_records(); either class may be DROP"""
+        return np.where(self.matched, np.int64(matched_class), np.int64(unmatched_class))
+
+    def __add__(self, other):
+        if not isinstance(other, ScreenResult):
+            return NotImplemented
+        if (self.set_id, self.names, self.min_hits) != (other.set_id, other.names, other.min_hits):
+            raise ValueError("screen results made with different k-mer sets or min_hits are not comparable")
+        cat = lambda name: np.concatenate([getattr(self, name), getattr(other, name)])
+        return ScreenResult(cat("kmers"), cat("hits"), cat("refs"), cat("best"), cat("best_hits"), self.bases + other.bases, self.min_hits, self.names,
+                            self.set_id)
+
+    def __repr__(self):
+        return f"<ScreenResult: {self.records} records, {self.matched_records} matched (min_hits {self.min_hits})>"
+
+
+def _screen_conf(kset, record_lines, seq_line, min_hits, first_byte, delimiter):
+    """-> (BgzfScreenConf, delimiter as bytes); ValueError as screen_records() documents it"""
+    if not isinstance(kset, KmerSet):
+        raise ValueError(f"kset is a KmerSet, not {type(kset).__name__}")
+    delimiter = _partition_delimiter(delimiter)
+    k, _, b = _grep_record_args(record_lines, None, first_byte)
+    s = _trim_int(seq_line, 0, k - 1, "seq_line")
+    return _lib.BgzfScreenConf(k, s, b, _trim_int(min_hits, 1, (1 << 32) - 1, "min_hits"), 0), delimiter
+
+
+class _ScreenSink:
+    """what _grep_file hands a window's records to when they are screened: the windows' rows are put one behind the other"""
+
+    def __init__(self, conf, kset):
+        self.conf, self.kset, self.rows, self.bases = conf, kset, [], 0
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        _, status, tot, self.win_rows = ctx.bgzf_screen_records(data, members, text_off, text_end, delim, flags, self.conf, self.kset._table(ctx),
+                                                                record_base)
+        return status, tot, b""
+
+    def window(self, tot, packed):
+        if not tot.seen:
+            return
+        if len(self.win_rows) != tot.seen:
+            raise RuntimeError("screen_records: the rows do not add up to the records")
+        self.bases += int(tot.bases)
+        self.rows.append(self.win_rows)
+
+    def finish(self, searched):
+        rows = np.concatenate(self.rows) if self.rows else np.empty(0, _lib.SCREEN_ROW_DTYPE)
+        if len(rows) != searched:
+            raise RuntimeError("screen_records: the rows do not add up to the records")
+        best = rows["best"].astype(np.int64)
+        best[best == _lib.KMER_NONE] = -1
+        return ScreenResult(rows["kmers"].astype(np.int64), rows["hits"].astype(np.int64), rows["refs"].copy(), best, rows["best_hits"].astype(np.int64),
+                            self.bases, self.conf.min_hits, self.kset.names, self.kset.identity)
+
+
+def _screen_file(fp, ctx, kset, record_lines, seq_line, min_hits, first_byte, delimiter, start, stop, first_record, max_record, allow_short):
+    conf, delimiter = _screen_conf(kset, record_lines, seq_line, min_hits, first_byte, delimiter)
+    return _grep_file(fp, ctx, None, delimiter, False, False, False, None, start, stop, first_record, max_record,
+                      (record_lines, None, first_byte, allow_short), 0, None, _ScreenSink(conf, kset))
+
+
+def screen_records(file, kset, record_lines=4, *, seq_line=1, min_hits=1, first_byte=None, delimiter=b"\n", start=None, stop=None, first_record=0,
+                   max_record=64 << 20, allow_short=False):
+    """Every k-mer of every read of a BGZF file looked up in a KmerSet on the GPU -- the contaminant screen of bbduk ref= k=,
+    fastq_screen and rRNA depletion.  The sequence of a record is the line seq_line; a k-mer with a byte other than A, C, G, T, U in
+    either case counts for nothing; a read is matched when at least min_hits of its k-mers are in the set.  record_lines, first_byte,
+    delimiter, start, stop, first_record, max_record, allow_short and the errors of the file are those of grep_records().
+    -> ScreenResult; the results of the parts of LineIndex.shards(reader, n, lines_per_record=k), put together with +, are the whole
+    file's."""
+    if _is_path(file):
+        _screen_conf(kset, record_lines, seq_line, min_hits, first_byte, delimiter)      # (judged before the file is opened)
+        with _builtin_open(file, "rb") as f:
+            return screen_records(f, kset, record_lines, seq_line=seq_line, min_hits=min_hits, first_byte=first_byte, delimiter=delimiter, start=start,
+                                  stop=stop, first_record=first_record, max_record=max_record, allow_short=allow_short)
+    return _screen_file(file, None, kset, record_lines, seq_line, min_hits, first_byte, delimiter, start, stop, first_record, max_record, allow_short)
+
+
+def _screen_filter_file(fp, ctx, kset, output, matched, record_lines, compresslevel, block_size, seq_line, min_hits, first_byte, delimiter, start, stop,
+                        first_record, max_record, allow_short):
+    _screen_conf(kset, record_lines, seq_line, min_hits, first_byte, delimiter)
+    _check_block_size(block_size)
+    res = _screen_file(fp, ctx, kset, record_lines, seq_line, min_hits, first_byte, delimiter, start, stop, first_record, max_record, allow_short)
+    outputs, classes = [], []
+    for out in (output, matched):                            # unmatched, matched: a class each, or DROP
+        classes.append(len(outputs) if out is not None else DROP)
+        if out is not None:
+            outputs.append(out)
+    if outputs:
+        _partition_file(fp, ctx, res.labels(classes[1], classes[0]), outputs, record_lines, first_byte, delimiter, compresslevel, block_size, start, stop,
+                        first_record, max_record, allow_short)
+    return res
+
+
+def screen_filter(file, kset, output, matched=None, record_lines=4, *, seq_line=1, min_hits=1, compresslevel=6, block_size=MAX_BLOCK_INPUT,
+                  first_byte=None, delimiter=b"\n", start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+    """screen_records(), then partition_records() -- bbduk's out= and outm=: the reads that are not matched go to output, whole and in
+    the order of the file; the matched ones go to matched (a path, a file, or None: they are written nowhere).  output may be None
+    too: then only the matched reads are written, or, with both None, nothing is and no second pass is made.  compresslevel and
+    block_size are those of the outputs; the other keywords and the errors of the file are those of screen_records().
+    -> ScreenResult.  For a paired run screen both files and split both by a.matched | b.matched."""
+    if _is_path(file):
+        _screen_conf(kset, record_lines, seq_line, min_hits, first_byte, delimiter)      # (judged before the file is opened)
+        _check_block_size(block_size)
+        with _builtin_open(file, "rb") as f:
+            return screen_filter(f, kset, output, matched, record_lines, seq_line=seq_line, min_hits=min_hits, compresslevel=compresslevel,
+                                 block_size=block_size, first_byte=first_byte, delimiter=delimiter, start=start, stop=stop, first_record=first_record,
+                                 max_record=max_record, allow_short=allow_short)
+    return _screen_filter_file(file, None, kset, output, matched, record_lines, compresslevel, block_size, seq_line, min_hits, first_byte, delimiter, start,
+                               stop, first_record, max_record, allow_short)
 
 
 # ---- records in another order (DESIGN.md section 5f.9): a key per record, a stable sort of keys, records written in any order
@@ -4075,6 +4359,34 @@ class BgzfReader(io.BufferedIOBase):
         try:
             return _dedup_file(self._fp, self._ctx, output, duplicates, record_lines, compresslevel, block_size, seq_line, first, length, ignore_case,
                                canonical, first_byte, delimiter, start, stop, first_record, max_record, allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def screen_records(self, kset, record_lines=4, *, seq_line=1, min_hits=1, first_byte=None, delimiter=b"\n", start=None, stop=None, first_record=0,
+                       max_record=64 << 20, allow_short=False):
+        """bgzf.screen_records() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("screen_records() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _screen_file(self._fp, self._ctx, kset, record_lines, seq_line, min_hits, first_byte, delimiter, start, stop, first_record, max_record,
+                                allow_short)
+        finally:
+            self._fp.seek(at)
+
+    def screen_filter(self, kset, output, matched=None, record_lines=4, *, seq_line=1, min_hits=1, compresslevel=6, block_size=MAX_BLOCK_INPUT,
+                      first_byte=None, delimiter=b"\n", start=None, stop=None, first_record=0, max_record=64 << 20, allow_short=False):
+        """bgzf.screen_filter() on this reader's file; the read position stays where it was"""
+        if self.closed:
+            raise ValueError("screen_filter() on closed BgzfReader object")
+        if not self.seekable():
+            raise io.UnsupportedOperation("the underlying file cannot seek")
+        at = self._fp.tell()
+        try:
+            return _screen_filter_file(self._fp, self._ctx, kset, output, matched, record_lines, compresslevel, block_size, seq_line, min_hits, first_byte,
+                                       delimiter, start, stop, first_record, max_record, allow_short)
         finally:
             self._fp.seek(at)
 
