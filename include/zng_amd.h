@@ -1304,6 +1304,96 @@ int zngamd_bgzf_screen_records(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_l
                                const zngamd_kmer_set *set, uint64_t record_base, int32_t *status, zngamd_bgzf_screen_row *rows,
                                uint64_t rows_cap, zngamd_alloc_fn alloc, void *user, zngamd_bgzf_screen_totals *totals);
 
+/* ---- BGZF count (zlib_ng_amd/bgzf.py: KmerCounter, count_kmers, KmerCounts).  Which k-mers the reads of a
+ * library hold themselves, and how often -- jellyfish count and histo, KMC, FastQC's "Kmer Content", the k-mer spectrum behind
+ * genome-size and heterozygosity estimates, and the solid k-mers that become the set of the next screen.  The rule:
+ *   codes      bases, forward and canonical codes and invalid bytes are exactly those of the screen section above; 1 <= k <= 31;
+ *              ZNGAMD_KMER_CANONICAL applies as there.
+ *   record     the sequence is the body of seq_line, n bytes (the record model is that of the key call); its positions are 0 .. n - k,
+ *              none when n < k.  Every position whose k-mer is valid adds 1 to the count of its code.
+ *   counter    an opaque object that accumulates over any number of calls -- windows, files, shards.  Counts are exact uint64_t.
+ *   runs       (bookkeeping only, it changes no count) the positions of a record are taken in strips of 64 from position 0; within a
+ *              strip a run is a longest stretch of consecutive valid positions with one code, and costs one atomic add.  adds: the runs.
+ * The counter owns its device table and is bound to the context it was made in (free it before that context is destroyed).  The table
+ * is cap slots of 16 bytes, code and count; cap is a power of two >= 64; an empty slot has the code all ones and the count 0; a code's
+ * home slot is mix(code) & (cap - 1) with the mix of the key call, probing is linear with wrap.  INVARIANT: before anything is launched
+ * the host checks distinct + room <= cap / 2, where distinct is the slots claimed so far and room bounds what the launch can claim
+ * (text_end - text_off for a window, n for _add, the old distinct for a rehash); so at most cap / 2 slots are ever claimed, an empty
+ * slot lies ahead of every home and every probe loop ends.  A call that fails the check returns ZNGAMD_BUF_ERROR, launches nothing and
+ * leaves the counter as it was: _reserve first.
+ *   _new        k, flags, and room for `room` codes: cap is the smallest power of two >= max(64, 2 * room).
+ *   _reserve    nothing when distinct + room <= cap / 2; otherwise a table of the smallest power of two >= 4 * (distinct + room) slots is
+ *               cleared, the pairs are rehashed into it and the old one is freed after that.  ZNGAMD_MEM_ERROR when the device cannot give
+ *               the table, ZNGAMD_E_ARG above ZNGAMD_KMER_COUNTER_MAX_CAP slots: the counter is unchanged in both cases.
+ *   _add        n (code, count) pairs from host memory; a code that appears twice adds its counts.  ZNGAMD_E_ARG, judged before any
+ *               launch, for a code >= 4^k or a count of 0; ZNGAMD_BUF_ERROR unless distinct + n <= cap / 2.
+ *   _describe   k, flags, poisoned, cap, distinct and total, the sum of all counts.
+ *   _histogram  2 <= bins <= ZNGAMD_KMER_HIST_MAX_BINS.  hist[0] = 0; hist[c] is the number of codes with count c for c < bins - 1;
+ *               hist[bins - 1] is the number of codes with count >= bins - 1 (jellyfish histo -h).
+ *   _export     the pairs with min_count <= count <= max_count in no particular order; min_count >= 1; max_count 0: no upper bound.
+ *               *n: how many there are.  ZNGAMD_BUF_ERROR, with *n set and nothing written, when cap_pairs is less.
+ *   _free       releases it (NULL: nothing happens).
+ * POISON: a window call that ends with totals.bad != 0, or that fails after its kernels have started, has added an unknown part of the
+ * window.  The counter is then poisoned: info.poisoned = 1, and every later call on it but _describe and _free returns ZNGAMD_E_ARG. */
+#define ZNGAMD_KMER_COUNTER_MAX_CAP (1ull << 33)
+#define ZNGAMD_KMER_HIST_MAX_BINS   16384u
+typedef struct zngamd_kmer_counter zngamd_kmer_counter;
+typedef struct {
+    uint32_t k;
+    uint32_t flags;           /* ZNGAMD_KMER_CANONICAL */
+    uint32_t poisoned;        /* 1: a window call left an unknown part of its window in the counts */
+    uint32_t reserved;
+    uint64_t cap;             /* slots of the table */
+    uint64_t distinct;        /* codes counted: the slots claimed */
+    uint64_t total;           /* the sum of all counts */
+    uint64_t reserved2[3];
+} zngamd_kmer_counter_info;                                                                       /* 64 B */
+int zngamd_kmer_counter_new(zngamd_ctx *ctx, uint32_t k, uint32_t flags, uint64_t room, zngamd_kmer_counter **out);
+int zngamd_kmer_counter_reserve(zngamd_kmer_counter *counter, uint64_t room);
+int zngamd_kmer_counter_add(zngamd_kmer_counter *counter, const uint64_t *codes, const uint64_t *counts, uint64_t n);
+int zngamd_kmer_counter_describe(const zngamd_kmer_counter *counter, zngamd_kmer_counter_info *info);
+int zngamd_kmer_counter_histogram(zngamd_kmer_counter *counter, uint64_t *hist, uint32_t bins);
+int zngamd_kmer_counter_export(zngamd_kmer_counter *counter, uint64_t min_count, uint64_t max_count, uint64_t *codes, uint64_t *counts,
+                               uint64_t cap_pairs, uint64_t *n);
+void zngamd_kmer_counter_free(zngamd_kmer_counter *counter);
+
+/* The count of a window: the window arguments, delimiter and flags of the screen call, the rule above with the k and flags of the
+ * counter.  No rows.  totals: those of zngamd_bgzf_key_totals at their offsets, then kmers (the valid positions), claimed (the slots
+ * newly claimed: the counter's distinct grows by it) and adds (the runs).  bad, tail_off, short_lines, covered and _FINAL behave as in
+ * the key call; the open tail behind the last complete record is not counted, the next window counts it.  ZNGAMD_E_ARG before the
+ * context is touched: what the screen call refuses, a counter that is NULL, poisoned or of another context.  ZNGAMD_BUF_ERROR, with
+ * nothing launched, unless distinct + (text_end - text_off) <= cap / 2.  Device memory beside the tiles: 8 bytes per line of the text. */
+typedef struct {
+    uint32_t record_lines;  /* 1 .. 64 */
+    int32_t  seq_line;      /* 0 <= s < record_lines */
+    int32_t  first_byte;    /* 0 .. 255; -1: no check */
+    uint32_t flags;         /* 0: none yet */
+    uint32_t reserved[12];  /* 0 */
+} zngamd_bgzf_count_conf;                                                                         /* 64 B */
+typedef struct {
+    uint64_t seen;            /* as zngamd_bgzf_key_totals ... */
+    uint64_t bytes_in;
+    uint64_t bases;
+    uint64_t tail_off;
+    uint64_t bad_record;
+    uint64_t bad_src;
+    uint32_t covered;
+    uint32_t short_lines;
+    uint32_t bad;
+    uint32_t reserved;
+    uint64_t kmers;           /* ... then the valid positions of all records */
+    uint64_t claimed;         /* the slots newly claimed */
+    uint64_t adds;            /* the atomic adds issued: the runs */
+} zngamd_bgzf_count_totals;                                                                       /* 88 B */
+int zngamd_bgzf_count_kmers_dev(zngamd_ctx *ctx, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members,
+                                uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_count_conf *conf,
+                                zngamd_kmer_counter *counter, uint64_t record_base, void *d_scratch, uint64_t scratch_cap,
+                                int32_t *d_status, zngamd_bgzf_count_totals *totals);
+/* Host-buffer form: stages as zngamd_bgzf_grep_records does; status comes back. */
+int zngamd_bgzf_count_kmers(zngamd_ctx *ctx, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members,
+                            uint64_t text_off, uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_count_conf *conf,
+                            zngamd_kmer_counter *counter, uint64_t record_base, int32_t *status, zngamd_bgzf_count_totals *totals);
+
 /* ---- BGZF overlap (zlib_ng_amd/bgzf.py: overlap_records).  The one preprocessing step that needs both mates
  * of a pair at once: where the two reads of a pair lie over each other, and with that the adapter read-through cut off, bases
  * corrected and the pair merged into one read -- fastp's overlap analysis (-c, -m), bbmerge, PEAR, FLASH, vsearch

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "zlib_ng_amd", "libzng_amd.so")
 SOURCES = ["zng_amd.hip"]
-DEPS = ["zng_amd.hip", "zng_stream.hip", "za_common.h", "za_crc.h", "za_deflate.hip", "za_inflate.hip", "za_inflate_units.hip", "za_inflate_spans.hip", "za_bgzf.hip", "za_grep.hip", "za_grep_records.hip", "za_classify.hip", "za_partition.hip", "za_trim.hip", "za_qc.hip", "za_dedup.hip", "za_sort.hip", "za_screen.hip", "za_overlap.hip", "za_tabix.hip", "za_faidx.hip", "za_batch.hip", "za_dict.hip", "za_checksum.hip",
+DEPS = ["zng_amd.hip", "zng_stream.hip", "za_common.h", "za_crc.h", "za_deflate.hip", "za_inflate.hip", "za_inflate_units.hip", "za_inflate_spans.hip", "za_bgzf.hip", "za_grep.hip", "za_grep_records.hip", "za_classify.hip", "za_partition.hip", "za_trim.hip", "za_qc.hip", "za_dedup.hip", "za_sort.hip", "za_screen.hip", "za_kcount.hip", "za_overlap.hip", "za_tabix.hip", "za_faidx.hip", "za_batch.hip", "za_dict.hip", "za_checksum.hip",
         os.path.join("..", "..", "include", "zng_amd.h")]
 
 

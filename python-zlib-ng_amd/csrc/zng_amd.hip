@@ -18,6 +18,7 @@
 #include "za_dedup.hip"
 #include "za_sort.hip"
 #include "za_screen.hip"
+#include "za_kcount.hip"
 #include "za_overlap.hip"
 #include "za_tabix.hip"
 #include "za_faidx.hip"
@@ -78,6 +79,10 @@ static_assert(sizeof(zngamd_bgzf_screen_totals) == sizeof(ZaScreenTotals) && siz
               offsetof(ZaScreenTotals, tail_off) == offsetof(zngamd_bgzf_key_totals, tail_off) && offsetof(ZaScreenTotals, kmers) == sizeof(zngamd_bgzf_key_totals) &&
               sizeof(zngamd_bgzf_screen_row) == sizeof(ZaScreenRow) && sizeof(ZaScreenRow) == 24 && sizeof(zngamd_bgzf_screen_conf) == 64 && sizeof(ZaKmerSlot) == 16 &&
               sizeof(zngamd_kmer_set_info) == 48 && ZNGAMD_KMER_CANONICAL == ZA_KMER_CANONICAL && ZNGAMD_KMER_NONE == ZA_KMER_NONE, "bgzf screen layout");
+static_assert(sizeof(zngamd_bgzf_count_totals) == sizeof(ZaKcountTotals) && sizeof(ZaKcountTotals) == sizeof(ZaScreenTotals) && offsetof(ZaKcountTotals, covered) == offsetof(ZaScreenTotals, covered) &&
+              offsetof(ZaKcountTotals, tail_off) == offsetof(zngamd_bgzf_key_totals, tail_off) && offsetof(ZaKcountTotals, kmers) == sizeof(zngamd_bgzf_key_totals) &&
+              offsetof(zngamd_bgzf_count_totals, adds) == 80 && sizeof(zngamd_bgzf_count_conf) == 64 && sizeof(zngamd_kmer_counter_info) == 64 &&
+              ZNGAMD_KMER_HIST_MAX_BINS == ZA_KCOUNT_MAX_BINS && ZNGAMD_KMER_HIST_MAX_BINS * 4u == 65536u, "bgzf count layout");
 static_assert(sizeof(zngamd_bgzf_overlap_totals) == sizeof(ZaOvlTotals) && sizeof(ZaOvlTotals) == 160 && offsetof(ZaOvlTotals, covered) == offsetof(zngamd_bgzf_overlap_totals, covered) &&
               offsetof(ZaOvlTotals, mismatch_sum) == offsetof(zngamd_bgzf_overlap_totals, mismatch_sum) && offsetof(ZaOvlTotals, mismatch_sum) == (ZA_OVL_SUMS - 1u) * 8u &&
               sizeof(zngamd_bgzf_overlap_row) == sizeof(ZaOvlRow) && sizeof(ZaOvlRow) == 16 && sizeof(zngamd_bgzf_overlap_conf) == 64 &&
@@ -5401,6 +5406,302 @@ try {
     HIPCHK(c, hipMemcpyAsync(rows, c->sc_row.p, (size_t)seen * sizeof(ZaScreenRow), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+// ---- the k-mers of the reads counted (za_kcount.hip)
+// The counter: the table is its own and grows; everything else a call needs is the context's (sc_tot, sc_tmp).  INVARIANT, checked by
+// kcount_room_ok before anything is launched: distinct + room <= cap / 2, where room bounds what the launch can claim.  So at most
+// cap / 2 slots are ever claimed and every probe loop of za_kmer_claim ends.
+struct zngamd_kmer_counter {
+    zngamd_ctx *ctx = nullptr;
+    uint32_t k = 0, flags = 0, poisoned = 0;
+    uint64_t cap = 0, distinct = 0, total = 0;
+    ZaKmerSlot *tab = nullptr;
+};
+
+// A launch takes a thread per slot or pair, and a grid holds fewer than 2^32 threads: tables of 2^32 slots and more are cleared,
+// rehashed and exported in launches of 2^31 each (the cursor and the claim count go on from launch to launch).
+constexpr uint64_t KCOUNT_LAUNCH = 1ull << 31;
+
+static bool kcount_room_ok(const zngamd_kmer_counter *kc, uint64_t room)
+{
+    const uint64_t half = kc->cap / 2u;
+    return room <= half && kc->distinct <= half - room;
+}
+
+// the smallest power of two that is >= want and >= ZA_KMER_MIN_CAP (want <= ZNGAMD_KMER_COUNTER_MAX_CAP)
+static uint64_t kcount_pow2(uint64_t want)
+{
+    uint64_t cap = ZA_KMER_MIN_CAP;
+    while (cap < want) cap <<= 1;
+    return cap;
+}
+
+// an empty table of cap slots in *tab (the caller holds the context's mutex); ZNGAMD_MEM_ERROR when the device cannot give it
+static int kcount_table(zngamd_ctx *c, uint64_t cap, ZaKmerSlot **tab)
+{
+    *tab = nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    const hipError_t e = hipMalloc((void **)tab, (size_t)cap * sizeof(ZaKmerSlot));
+    if (e != hipSuccess) {
+        *tab = nullptr;
+        (void)hipGetLastError();
+        if (e == hipErrorOutOfMemory) return fail(c, ZNGAMD_MEM_ERROR, "the device cannot give the k-mer table");
+        HIPCHK(c, e);
+    }
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      for (uint64_t at = 0; at < cap; at += KCOUNT_LAUNCH) {
+          const uint64_t m = std::min<uint64_t>(KCOUNT_LAUNCH, cap - at);
+          hipLaunchKernelGGL(za_k_kcount_clear, dim3((uint32_t)((m + 255u) / 256u)), dim3(256), 0, c->stream, *tab + at, m);
+      } }
+    HIPCHK(c, hipGetLastError());
+    return ZNGAMD_OK;
+}
+
+// n pairs (codes[step i], counts[step i]) on the device into tab; [the host waits] *claimed: the slots newly claimed
+static int kcount_pairs(zngamd_ctx *c, const unsigned long long *d_codes, const unsigned long long *d_counts, uint64_t n, uint32_t step, ZaKmerSlot *tab, uint64_t cap,
+                        uint64_t *claimed)
+{
+    unsigned long long acc = 0;
+    HIPCHK(c, c->sc_tot.ensure(2));
+    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, 8, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      for (uint64_t at = 0; at < n; at += KCOUNT_LAUNCH) {
+          const uint64_t m = std::min<uint64_t>(KCOUNT_LAUNCH, n - at);
+          hipLaunchKernelGGL(za_k_kcount_pairs, dim3((uint32_t)((m + 255u) / 256u)), dim3(256), 0, c->stream, d_codes + at * step, d_counts + at * step, m, step, tab,
+                             cap - 1u, c->sc_tot.p);
+      } }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(&acc, c->sc_tot.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    *claimed = acc;
+    return ZNGAMD_OK;
+}
+
+int zngamd_kmer_counter_new(zngamd_ctx *c, uint32_t k, uint32_t flags, uint64_t room, zngamd_kmer_counter **out)
+try {
+    if (!out || !kmer_rule_ok(k, flags, 1u) || room > ZNGAMD_KMER_COUNTER_MAX_CAP / 2u || !c) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    zngamd_kmer_counter *kc = new zngamd_kmer_counter;
+    kc->ctx = c; kc->k = k; kc->flags = flags; kc->cap = kcount_pow2(2u * room);
+    int r = kcount_table(c, kc->cap, &kc->tab);
+    if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(c, ZNGAMD_E_HIP, "the k-mer table could not be cleared");
+    if (r) { if (kc->tab) (void)hipFree(kc->tab); delete kc; return r; }
+    *out = kc;
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_kmer_counter_reserve(zngamd_kmer_counter *kc, uint64_t room)
+try {
+    if (!kc || !kc->ctx || kc->poisoned) return ZNGAMD_E_ARG;
+    zngamd_ctx *c = kc->ctx;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (kcount_room_ok(kc, room)) return ZNGAMD_OK;
+    if (room > ZNGAMD_KMER_COUNTER_MAX_CAP / 4u || kc->distinct + room > ZNGAMD_KMER_COUNTER_MAX_CAP / 4u) return ZNGAMD_E_ARG;
+    const uint64_t cap = kcount_pow2(4u * (kc->distinct + room));
+    ZaKmerSlot *tab = nullptr;
+    int r = kcount_table(c, cap, &tab);
+    uint64_t claimed = 0;
+    // the rehash: every occupied slot of the old table is a pair; it can claim the old distinct, and distinct <= cap / 4 here
+    if (!r && kc->distinct) r = kcount_pairs(c, &kc->tab->code, &kc->tab->mask, kc->cap, 2u, tab, cap, &claimed);
+    else if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(c, ZNGAMD_E_HIP, "the k-mer table could not be cleared");
+    if (!r && claimed != kc->distinct) r = fail(c, ZNGAMD_E_HIP, "the counter's table does not hold the codes it has counted");
+    if (r) { if (tab) { (void)hipStreamSynchronize(c->stream); (void)hipFree(tab); } return r; }      // (the counter is as it was)
+    (void)hipFree(kc->tab);                                                         // (the stream is drained: nothing reads the old table)
+    kc->tab = tab; kc->cap = cap;
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_kmer_counter_add(zngamd_kmer_counter *kc, const uint64_t *codes, const uint64_t *counts, uint64_t n)
+try {
+    if (!kc || !kc->ctx || kc->poisoned || (n && (!codes || !counts))) return ZNGAMD_E_ARG;
+    const uint64_t code_end = 1ull << (2u * kc->k);
+    for (uint64_t i = 0; i < n; i++) if (codes[i] >= code_end || !counts[i]) return ZNGAMD_E_ARG;
+    zngamd_ctx *c = kc->ctx;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!kcount_room_ok(kc, n)) return fail(c, ZNGAMD_BUF_ERROR, "the k-mer table has no room: reserve first");
+    if (!n) return ZNGAMD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->sc_tmp.ensure((size_t)n * 16u));
+    unsigned long long *d_codes = (unsigned long long *)c->sc_tmp.p, *d_counts = d_codes + n;
+    HIPCHK(c, hipMemcpyAsync(d_codes, codes, (size_t)n * 8u, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_counts, counts, (size_t)n * 8u, hipMemcpyHostToDevice, c->stream));
+    uint64_t claimed = 0;
+    const int r = kcount_pairs(c, d_codes, d_counts, n, 1u, kc->tab, kc->cap, &claimed);
+    if (r) { kc->poisoned = 1; return r; }                                          // (an unknown part of the pairs is in the table)
+    kc->distinct += claimed;
+    for (uint64_t i = 0; i < n; i++) kc->total += counts[i];
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_kmer_counter_describe(const zngamd_kmer_counter *kc, zngamd_kmer_counter_info *info)
+{
+    if (!kc || !info) return ZNGAMD_E_ARG;
+    memset(info, 0, sizeof *info);
+    info->k = kc->k; info->flags = kc->flags; info->poisoned = kc->poisoned; info->cap = kc->cap; info->distinct = kc->distinct; info->total = kc->total;
+    return ZNGAMD_OK;
+}
+
+int zngamd_kmer_counter_histogram(zngamd_kmer_counter *kc, uint64_t *hist, uint32_t bins)
+try {
+    if (!kc || !kc->ctx || kc->poisoned || !hist || bins < 2u || bins > ZNGAMD_KMER_HIST_MAX_BINS) return ZNGAMD_E_ARG;
+    zngamd_ctx *c = kc->ctx;
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->sc_tot.ensure(bins));
+    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, (size_t)bins * 8u, c->stream));
+    // a few workgroups per CU, so that the flush stays small: beyond that a workgroup walks on to its next 256 slots
+    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_KCOUNT_HIST_PER_CU;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((kc->cap + 255u) / 256u, slots);
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      hipLaunchKernelGGL(za_k_kcount_hist, dim3(grid), dim3(256), (size_t)bins * 4u, c->stream, (const ZaKmerSlot *)kc->tab, kc->cap, bins, c->sc_tot.p); }
+    HIPCHK(c, hipGetLastError());
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "histogram words");
+    HIPCHK(c, hipMemcpyAsync(hist, c->sc_tot.p, (size_t)bins * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+int zngamd_kmer_counter_export(zngamd_kmer_counter *kc, uint64_t min_count, uint64_t max_count, uint64_t *codes, uint64_t *counts, uint64_t cap_pairs, uint64_t *n)
+try {
+    if (!kc || !kc->ctx || kc->poisoned || !n || !min_count || (max_count && max_count < min_count) || (cap_pairs && (!codes || !counts))) return ZNGAMD_E_ARG;
+    zngamd_ctx *c = kc->ctx;
+    std::lock_guard<std::mutex> g(c->mu);
+    *n = 0;
+    if (!kc->distinct) return ZNGAMD_OK;
+    // the kernel counts every pair of the filter and writes those that have a place: room for more than distinct pairs is never used
+    const uint64_t room = std::min<uint64_t>(cap_pairs, kc->distinct);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->sc_tmp.ensure((size_t)std::max<uint64_t>(room, 1u) * 16u)); HIPCHK(c, c->sc_tot.ensure(2));
+    unsigned long long *d_codes = (unsigned long long *)c->sc_tmp.p, *d_counts = d_codes + room;
+    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, 8, c->stream));
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      for (uint64_t at = 0; at < kc->cap; at += KCOUNT_LAUNCH) {
+          const uint64_t m = std::min<uint64_t>(KCOUNT_LAUNCH, kc->cap - at);
+          hipLaunchKernelGGL(za_k_kcount_export, dim3((uint32_t)((m + 255u) / 256u)), dim3(256), 0, c->stream, (const ZaKmerSlot *)kc->tab + at, m,
+                             (unsigned long long)min_count, max_count ? (unsigned long long)max_count : ~0ull, d_codes, d_counts, room, c->sc_tot.p);
+      } }
+    HIPCHK(c, hipGetLastError());
+    unsigned long long found = 0;
+    HIPCHK(c, hipMemcpyAsync(&found, c->sc_tot.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (found > kc->distinct) return fail(c, ZNGAMD_E_HIP, "the counter's table does not hold the codes it has counted");
+    *n = found;
+    if (found > cap_pairs) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    if (!found) return ZNGAMD_OK;
+    HIPCHK(c, hipMemcpyAsync(codes, d_codes, (size_t)found * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(counts, d_counts, (size_t)found * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+} ZA_ABI_GUARD
+
+void zngamd_kmer_counter_free(zngamd_kmer_counter *kc)
+{
+    if (!kc) return;
+    if (kc->ctx) {
+        std::lock_guard<std::mutex> g(kc->ctx->mu);
+        (void)hipSetDevice(kc->ctx->device);
+        (void)hipStreamSynchronize(kc->ctx->stream);                                // (no launch of this context still touches the table)
+        if (kc->tab) (void)hipFree(kc->tab);
+    }
+    delete kc;
+}
+
+// Everything the caller gave that needs no context to be judged: before a context is touched or anything is launched.
+static bool count_args_ok(const zngamd_ctx *c, int delim, uint32_t flags, const zngamd_bgzf_count_conf *cf, const zngamd_kmer_counter *kc,
+                          const zngamd_bgzf_count_totals *totals)
+{
+    if (!totals || !cf || !kc || (flags & ~ZNGAMD_BGZF_GREP_FINAL) || delim < 0 || delim > 255) return false;
+    if (!grep_records_ok(cf->record_lines, -1, cf->first_byte)) return false;
+    if (cf->seq_line < 0 || cf->seq_line >= (int32_t)cf->record_lines || cf->flags) return false;
+    for (uint32_t v : cf->reserved) if (v) return false;
+    return c && kc->ctx == c && !kc->poisoned;
+}
+
+// The lines pass for the delimiters alone, [the host waits for the line count], lines, reads, close, [the host waits for the totals].
+// *started: the reads kernel was launched, so the table may hold a part of the window.
+static int bgzf_count_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, const zngamd_bgzf_count_conf &cf, zngamd_kmer_counter *kc, uint64_t record_base,
+                          bool *started, zngamd_bgzf_count_totals *totals)
+{
+    memset(totals, 0, sizeof *totals);
+    ZaGrepTotals lt;
+    static const uint8_t no_bytes[1] = {0};
+    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+    const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
+    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+    if (r) return r;
+    BgzfRecords R;
+    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    const uint64_t lines = R.lines, nrec = R.nrec;
+    constexpr size_t TOT_WORDS = sizeof(ZaKcountTotals) / 8u;                            // then the fault
+    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->sc_tot.ensure(TOT_WORDS + 1u));
+    // four records to a workgroup, at most ZA_KCOUNT_WG_PER_CU workgroups per CU: beyond that a wave walks on to its next record
+    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_KCOUNT_WG_PER_CU;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    const ZaKcountPar P = {k, (uint32_t)cf.seq_line, cf.first_byte, w.delim, kc->k, kc->flags & ZNGAMD_KMER_CANONICAL};
+    ZaKcountTotals *d_tot = (ZaKcountTotals *)c->sc_tot.p;
+    unsigned long long *d_bad = c->sc_tot.p + TOT_WORDS;
+    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, TOT_WORDS * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    *started = true;
+    { ProfScope ps(c, ZNGAMD_K_GATHER);
+      R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
+      hipLaunchKernelGGL(za_k_kcount_reads, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, P, kc->tab, kc->cap - 1u, d_tot, d_bad);
+      hipLaunchKernelGGL(za_k_screen_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, (ZaScreenTotals *)d_tot); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+// what a window call leaves in the counter: the slots it claimed and the positions it counted, or the poison
+static int count_settle(zngamd_kmer_counter *kc, int r, bool started, const zngamd_bgzf_count_totals *totals)
+{
+    if (started && (r || totals->bad)) kc->poisoned = 1;
+    else if (!r) { kc->distinct += totals->claimed; kc->total += totals->kmers; }
+    return r;
+}
+
+int zngamd_bgzf_count_kmers_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
+                                uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_count_conf *conf, zngamd_kmer_counter *kc, uint64_t record_base,
+                                void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_count_totals *totals)
+try {
+    if (!count_args_ok(c, delim, flags, conf, kc, totals)) return ZNGAMD_E_ARG;
+    if ((n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!kcount_room_ok(kc, text_end > text_off ? text_end - text_off : 0u)) return fail(c, ZNGAMD_BUF_ERROR, "the k-mer table has no room: reserve first");
+    HIPCHK(c, hipSetDevice(c->device));
+    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
+                          scratch_cap, d_status};
+    bool started = false;
+    int r = bgzf_count_dev(c, w, flags, *conf, kc, record_base, &started, totals);
+    if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(c, ZNGAMD_E_HIP, "hipStreamSynchronize");
+    prof_collect(c);
+    return count_settle(kc, r, started, totals);
+} ZA_ABI_GUARD
+
+int zngamd_bgzf_count_kmers(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                            uint64_t text_end, int delim, uint32_t flags, const zngamd_bgzf_count_conf *conf, zngamd_kmer_counter *kc, uint64_t record_base,
+                            int32_t *status, zngamd_bgzf_count_totals *totals)
+try {
+    if (!count_args_ok(c, delim, flags, conf, kc, totals)) return ZNGAMD_E_ARG;
+    if ((!in && in_len) || (n_members && (!members || !status))) return ZNGAMD_E_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!kcount_room_ok(kc, text_end > text_off ? text_end - text_off : 0u)) return fail(c, ZNGAMD_BUF_ERROR, "the k-mer table has no room: reserve first");
+    uint64_t scratch = 0;
+    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    bool started = false;
+    r = bgzf_count_dev(c, w, flags, *conf, kc, record_base, &started, totals);
+    if (!r && n_members && hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        r = fail(c, ZNGAMD_E_HIP, "hipMemcpyAsync of the block statuses");
+    if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(c, ZNGAMD_E_HIP, "hipStreamSynchronize");
+    prof_collect(c);
+    return count_settle(kc, r, started, totals);
 } ZA_ABI_GUARD
 
 // ---- pairs laid over each other (za_overlap.hip)

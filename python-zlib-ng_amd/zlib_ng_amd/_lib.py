@@ -94,6 +94,8 @@ SYMBOLS = [
     "zngamd_bgzf_place_records_dev", "zngamd_bgzf_place_records",
     "zngamd_kmer_set_build", "zngamd_kmer_set_load", "zngamd_kmer_set_export", "zngamd_kmer_set_describe", "zngamd_kmer_set_free",
     "zngamd_bgzf_screen_records_dev", "zngamd_bgzf_screen_records",
+    "zngamd_kmer_counter_new", "zngamd_kmer_counter_reserve", "zngamd_kmer_counter_add", "zngamd_kmer_counter_describe", "zngamd_kmer_counter_histogram",
+    "zngamd_kmer_counter_export", "zngamd_kmer_counter_free", "zngamd_bgzf_count_kmers_dev", "zngamd_bgzf_count_kmers",
     "zngamd_bgzf_overlap_records_dev", "zngamd_bgzf_overlap_records",
     "zngamd_bgzf_tabix_dev", "zngamd_bgzf_tabix", "zngamd_bgzf_fetch_dev", "zngamd_bgzf_fetch",
     "zngamd_bgzf_faidx_dev", "zngamd_bgzf_faidx", "zngamd_bgzf_faidx_fetch_dev", "zngamd_bgzf_faidx_fetch",
@@ -360,6 +362,28 @@ class BgzfScreenTotals(C.Structure):           # zngamd_bgzf_screen_totals
                 ("kmers", C.c_uint64), ("hits", C.c_uint64), ("matched", C.c_uint64)]
 
 
+KMER_COUNTER_MAX_CAP, KMER_HIST_MAX_BINS = 1 << 33, 16384      # ZNGAMD_KMER_COUNTER_MAX_CAP, ZNGAMD_KMER_HIST_MAX_BINS
+
+
+class KmerCounterInfo(C.Structure):            # zngamd_kmer_counter_info
+    _fields_ = [("k", C.c_uint32), ("flags", C.c_uint32), ("poisoned", C.c_uint32), ("reserved", C.c_uint32), ("cap", C.c_uint64),
+                ("distinct", C.c_uint64), ("total", C.c_uint64), ("reserved2", C.c_uint64 * 3)]
+
+
+class BgzfCountConf(C.Structure):              # zngamd_bgzf_count_conf
+    _fields_ = [("record_lines", C.c_uint32), ("seq_line", C.c_int32), ("first_byte", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 12)]
+
+
+class BgzfCountTotals(C.Structure):            # zngamd_bgzf_count_totals
+    _fields_ = [("seen", C.c_uint64), ("bytes_in", C.c_uint64), ("bases", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64),
+                ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("reserved", C.c_uint32),
+                ("kmers", C.c_uint64), ("claimed", C.c_uint64), ("adds", C.c_uint64)]
+
+    @property
+    def matched(self):                         # (the name the window loop of bgzf.grep reads: every record is counted)
+        return self.seen
+
+
 class BgzfPlaceTotals(C.Structure):            # zngamd_bgzf_place_totals
     _fields_ = [("seen", C.c_uint64), ("placed", C.c_uint64), ("placed_bytes", C.c_uint64), ("tail_off", C.c_uint64), ("bad_record", C.c_uint64),
                 ("bad_src", C.c_uint64), ("covered", C.c_uint32), ("short_lines", C.c_uint32), ("bad", C.c_uint32), ("labels_short", C.c_uint32)]
@@ -588,6 +612,18 @@ def load():
                                                          C.c_uint64, vp, vp, C.c_uint64, vp]
             L.zngamd_bgzf_screen_records.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, vp, C.c_uint64, vp, vp,
                                                      C.c_uint64, ALLOC_FN, vp, vp]
+        if hasattr(L, "zngamd_bgzf_count_kmers"):           # the counter's calls; the count: as screen without the rows
+            L.zngamd_kmer_counter_new.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, vp]
+            L.zngamd_kmer_counter_reserve.argtypes = [vp, C.c_uint64]
+            L.zngamd_kmer_counter_add.argtypes = [vp, vp, vp, C.c_uint64]
+            L.zngamd_kmer_counter_describe.argtypes = [vp, vp]
+            L.zngamd_kmer_counter_histogram.argtypes = [vp, vp, C.c_uint32]
+            L.zngamd_kmer_counter_export.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, vp]
+            L.zngamd_kmer_counter_free.argtypes = [vp]
+            L.zngamd_kmer_counter_free.restype = None
+            L.zngamd_bgzf_count_kmers_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, vp, C.c_uint64, vp,
+                                                      C.c_uint64, vp, vp]
+            L.zngamd_bgzf_count_kmers.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, vp, C.c_uint64, vp, vp]
         if hasattr(L, "zngamd_bgzf_overlap_records"):       # as qc without the tables: overlap rows, rows and bytes with their capacities
             L.zngamd_bgzf_overlap_records_dev.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, vp, C.c_uint64, vp,
                                                           C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
@@ -1021,6 +1057,72 @@ class DeviceKmerSet:
     def free(self):
         if self.h:
             self.ctx.L.zngamd_kmer_set_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class DeviceKmerCounter:
+    """A zngamd_kmer_counter: the (code, count) table of a k-mer counter on the device, bound to the context it was made in.  free()
+    releases it; so do the end of the object and the close() of its context.  Every call on a freed counter is a ValueError."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+
+    def _handle(self):
+        if not self.h:
+            raise ValueError("the counter was freed")
+        return self.h
+
+    @property
+    def info(self):
+        info = KmerCounterInfo()
+        if self.ctx.L.zngamd_kmer_counter_describe(self._handle(), C.byref(info)) != OK:
+            raise ValueError("the counter was freed")
+        return info
+
+    def reserve(self, room):
+        """zngamd_kmer_counter_reserve -> code: OK, or MEM_ERROR when the device cannot give the grown table (the counter is unchanged)"""
+        return self.ctx._chk(self.ctx.L.zngamd_kmer_counter_reserve(self._handle(), room), (OK, MEM_ERROR))
+
+    def add(self, codes, counts):
+        """zngamd_kmer_counter_add: (code, count) pairs (uint64 arrays of equal length) -> code: OK, or BUF_ERROR when the table lacks the
+        room (nothing was added: reserve first)"""
+        codes, counts = np.ascontiguousarray(codes, np.uint64), np.ascontiguousarray(counts, np.uint64)
+        n = len(codes)
+        if len(counts) != n:
+            raise ValueError("codes and counts are of equal length")
+        p = lambda a: C.c_void_p(a.ctypes.data) if n else None
+        return self.ctx._chk(self.ctx.L.zngamd_kmer_counter_add(self._handle(), p(codes), p(counts), n), (OK, BUF_ERROR))
+
+    def histogram(self, bins):
+        """zngamd_kmer_counter_histogram -> uint64 of `bins` entries: [c] the codes with count c, [bins - 1] those with at least that"""
+        hist = np.zeros(max(int(bins), 1), np.uint64)
+        self.ctx._chk(self.ctx.L.zngamd_kmer_counter_histogram(self._handle(), C.c_void_p(hist.ctypes.data), bins))
+        return hist
+
+    def export(self, min_count=1, max_count=0, cap_pairs=None):
+        """zngamd_kmer_counter_export -> (code, codes, counts, n): the pairs with min_count <= count <= max_count (0: no upper bound) in no
+        particular order.  cap_pairs None: the pairs are counted first and all come back; an integer: room for that many, and code is
+        BUF_ERROR, with n set and no pair, when there are more"""
+        h = self._handle()
+        n = C.c_uint64(0)
+        if cap_pairs is None:
+            self.ctx._chk(self.ctx.L.zngamd_kmer_counter_export(h, min_count, max_count, None, None, 0, C.byref(n)), (OK, BUF_ERROR))
+            cap_pairs = n.value
+        codes, counts = np.empty(cap_pairs, np.uint64), np.empty(cap_pairs, np.uint64)
+        p = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
+        r = self.ctx._chk(self.ctx.L.zngamd_kmer_counter_export(h, min_count, max_count, p(codes), p(counts), cap_pairs, C.byref(n)), (OK, BUF_ERROR))
+        got = n.value if r == OK else 0
+        return r, codes[:got], counts[:got], n.value
+
+    def free(self):
+        if self.h:
+            self.ctx.L.zngamd_kmer_counter_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -2041,6 +2143,37 @@ class Context:
         r = self._chk(self.L.zngamd_bgzf_screen_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
                                                             C.byref(conf), kset.h, record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap,
                                                             C.byref(tot)), (OK, BUF_ERROR))
+        return r, tot
+
+    def kmer_counter_new(self, k, flags=KMER_CANONICAL, room=0):
+        """zngamd_kmer_counter_new: an empty counter with a table for `room` codes -> DeviceKmerCounter"""
+        h = C.c_void_p()
+        self._chk(self.L.zngamd_kmer_counter_new(self.h, k, flags, room, C.byref(h)))
+        counter = DeviceKmerCounter(self, h)
+        self.__dict__.setdefault("_kmer_sets", weakref.WeakSet()).add(counter)      # (freed before the context, as a set is)
+        return counter
+
+    def bgzf_count_kmers(self, data, members, text_off, text_end, delim, flags, conf, counter, record_base=0):
+        """zngamd_bgzf_count_kmers: every valid k-mer of every record added to counter (a DeviceKmerCounter of this context) by conf (a
+        BgzfCountConf) -> (code, block statuses, totals (BgzfCountTotals)); code is BUF_ERROR when the table lacks the room for the
+        window (nothing was launched: reserve text_end - text_off first)"""
+        nm = len(members)
+        p, keep = _addr(data)
+        st = np.zeros(max(1, nm), np.int32)
+        tot = BgzfCountTotals()
+        r = self._chk(self.L.zngamd_bgzf_count_kmers(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+                                                     text_off, text_end, delim, flags, C.byref(conf), counter._handle(), record_base,
+                                                     C.c_void_p(st.ctypes.data), C.byref(tot)), (OK, BUF_ERROR))
+        return r, st[:nm], tot
+
+    def bgzf_count_kmers_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, counter, record_base, d_scratch, scratch_cap,
+                             d_status):
+        """zngamd_bgzf_count_kmers_dev on device pointers (conf: host memory) -> (code, totals)"""
+        v = lambda x: C.c_void_p(int(x)) if x else None
+        tot = BgzfCountTotals()
+        r = self._chk(self.L.zngamd_bgzf_count_kmers_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
+                                                         C.byref(conf), counter._handle(), record_base, v(d_scratch), scratch_cap, v(d_status),
+                                                         C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_sort_key_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):

@@ -56,7 +56,7 @@ __all__ = ["open", "compress", "compress_dev", "decompress", "make_virtual_offse
            "GziIndex", "LineIndex", "BadGzipFile", "EOF_BLOCK", "MAX_BLOCK_INPUT", "grep", "grep_records", "GrepResult",
            "classify_records", "demux", "ClassifyResult", "UNASSIGNED", "AMBIGUOUS", "partition_records", "demux_paired", "pair_labels", "DROP", "trim_records", "TrimResult", "KEPT", "TOO_SHORT", "DROPPED", "qc_records", "QcResult",
            "key_records", "KeyResult", "pair_keys", "dedup_keys", "DedupResult", "dedup_records", "dedup_paired",
-           "KmerSet", "ScreenResult", "screen_records", "screen_filter",
+           "KmerSet", "ScreenResult", "screen_records", "screen_filter", "KmerCounter", "KmerCounts", "count_kmers",
            "SortKey", "SortKeyResult", "SortResult", "sort_key_records", "sort_keys", "permute_records", "sort_records",
            "overlap_records", "OverlapResult", "NONE", "FOUND", "MERGED", "TOO_LONG",
            "TabixIndex", "FetchResult", "fetch", "parse_region", "reg2bin", "reg2bins", "FaidxIndex", "SeqResult", "fetch_seq"]
@@ -707,7 +707,8 @@ def _grep_file(fp, ctx, patterns, delimiter, invert, line_start, count, max_coun
     sink takes what each window gives, and what its finish() returns is the result.  partition (with records, instead of patterns): a
     _PartitionSink -- every window's records are split by the labels it holds (partition_records()) -- or a _TrimSink -- they are cut
     (trim_records()) -- or a _QcSink -- they are counted (qc_records()) -- or a _KeySink -- they are keyed (key_records()) -- or a
-    _ScreenSink -- their k-mers are looked up in a set (screen_records()) -- or an _OverlapSink -- the mates of every pair are laid over each other (overlap_records())."""
+    _ScreenSink -- their k-mers are looked up in a set (screen_records()) -- or a _KmerCountSink -- their k-mers are counted
+    (KmerCounter.add_file()) -- or an _OverlapSink -- the mates of every pair are laid over each other (overlap_records())."""
     if partition is None:
         pats, delimiter = _grep_patterns(patterns, delimiter)
         mismatches = _grep_mismatches(mismatches, pats)
@@ -2119,6 +2120,330 @@ def screen_filter(file, kset, output, matched=None, record_lines=4, *, seq_line=
                                  max_record=max_record, allow_short=allow_short)
     return _screen_filter_file(file, None, kset, output, matched, record_lines, compresslevel, block_size, seq_line, min_hits, first_byte, delimiter, start,
                                stop, first_record, max_record, allow_short)
+
+
+# ---- the k-mers of the reads counted: a counter on the device, its pairs and its spectrum as host data
+_KMER_BASES = b"ACGT"
+
+
+def _kmer_encode(kmer, k, canonical):
+    """the code of one k-mer (bytes or str) by the rule of the screen: ValueError for another length or a byte that is no base"""
+    b = kmer.encode() if isinstance(kmer, str) else bytes(kmer)
+    if len(b) != k:
+        raise ValueError(f"{kmer!r} is not a {k}-mer")
+    f = r = 0
+    for i, ch in enumerate(b):
+        v = b"ACGTU".find(bytes([ch]).upper())
+        if v < 0:
+            raise ValueError(f"{kmer!r} holds a byte that is no base")
+        v = min(v, 3)
+        f = f << 2 | v
+        r |= (3 - v) << (2 * i)
+    return min(f, r) if canonical else f
+
+
+def _kmer_decode(codes, k):
+    """the k-mers of `codes` as a list of bytes, the first base from the most significant bits"""
+    codes = np.asarray(codes, np.uint64)
+    out = np.empty((len(codes), k), np.uint8)
+    lut = np.frombuffer(_KMER_BASES, np.uint8)
+    for i in range(k):
+        out[:, i] = lut[((codes >> np.uint64(2 * (k - 1 - i))) & np.uint64(3)).astype(np.intp)]
+    return [row.tobytes() for row in out]
+
+
+def _kmer_spectrum(counts, bins):
+    """uint64 of `bins` entries: [c] the codes with count c, [bins - 1] those with at least that"""
+    return np.bincount(np.minimum(counts, np.uint64(bins - 1)).astype(np.int64), minlength=bins).astype(np.uint64)
+
+
+def _count_filter(min_count, max_count, bins):
+    if min_count is not None:
+        min_count = _trim_int(min_count, 1, (1 << 64) - 1, "min_count")
+    if max_count is not None:
+        max_count = _trim_int(max_count, min_count or 1, (1 << 64) - 1, "max_count")
+    return min_count, max_count, _trim_int(bins, 2, _lib.KMER_HIST_MAX_BINS, "bins")
+
+
+class KmerCounts:
+    """The k-mers of a library and how often each occurs, as host data: k, canonical; codes (sorted uint64) and counts (uint64) of equal
+    length -- the pairs with min_count <= count <= max_count (None: no upper bound; min_count None: no pair was exported); spectrum
+    (uint64, bins entries): [c] is the number of codes that occur c times, the last entry those that occur at least bins - 1 times --
+    of ALL codes, whatever the filter; records, bases, kmers (the valid positions: the sum of all counts) and distinct (all codes).
+    The rule of the codes is that of KmerSet.  len(): the pairs held.  a + b: the counts of two shards or files -- of equal k and
+    canonical, both unfiltered and of equal bins (ValueError otherwise: filtered counts do not add)."""
+
+    def __init__(self, k, canonical, codes, counts, spectrum, *, min_count=1, max_count=None, records=0, bases=0, kmers=None, distinct=None):
+        k, canonical = _kmer_rule(k, canonical)
+        codes, counts, spectrum = np.asarray(codes), np.asarray(counts), np.asarray(spectrum)
+        if codes.ndim != 1 or counts.shape != codes.shape or spectrum.ndim != 1:
+            raise ValueError("codes and counts are one-dimensional arrays of equal length, spectrum is one-dimensional")
+        for a in (codes, counts, spectrum):
+            if len(a) and (a.dtype.kind not in "iu" or a.min() < 0):
+                raise ValueError("codes, counts and spectrum are integers that are not negative")
+        codes, counts, spectrum = codes.astype(np.uint64), counts.astype(np.uint64), spectrum.astype(np.uint64)
+        min_count, max_count, _ = _count_filter(min_count, max_count, len(spectrum))
+        if len(codes) and int(codes.max()) >= 4 ** k:
+            raise ValueError(f"a code of a {k}-mer lies below 4**{k}")
+        if len(codes) > 1 and not (codes[1:] > codes[:-1]).all():
+            raise ValueError("codes ascend and none appears twice")
+        if min_count is None and len(codes):
+            raise ValueError("min_count None goes with no pair")
+        if len(codes) and (int(counts.min()) < min_count or (max_count is not None and int(counts.max()) > max_count)):
+            raise ValueError("a count lies outside min_count .. max_count")
+        if int(spectrum[0]):
+            raise ValueError("spectrum[0] is 0: no code occurs 0 times")
+        self.k, self.canonical, self.codes, self.counts, self.spectrum = k, canonical, codes, counts, spectrum
+        self.min_count, self.max_count = min_count, max_count
+        self.records, self.bases = int(records), int(bases)
+        self.distinct = int(spectrum.sum()) if distinct is None else int(distinct)
+        self.kmers = (int(counts.sum()) if self.unfiltered else 0) if kmers is None else int(kmers)
+        if self.distinct != int(spectrum.sum()) or (self.unfiltered and (self.distinct != len(codes) or self.kmers != int(counts.sum()))):
+            raise ValueError("distinct, kmers, the spectrum and the pairs do not agree")
+
+    @property
+    def unfiltered(self):
+        return self.min_count == 1 and self.max_count is None
+
+    @property
+    def bins(self):
+        return len(self.spectrum)
+
+    def __len__(self):
+        return len(self.codes)
+
+    def count_of(self, kmers_or_codes):
+        """the counts (uint64; 0 for one that is not held) of k-mers -- bytes or str, one or a list -- or of codes (integers)"""
+        one = isinstance(kmers_or_codes, (bytes, bytearray, str, int, np.integer))
+        items = [kmers_or_codes] if one else list(kmers_or_codes)
+        want = np.array([_kmer_encode(x, self.k, self.canonical) if isinstance(x, (bytes, bytearray, str)) else int(x) for x in items], np.uint64)
+        at = np.searchsorted(self.codes, want)
+        out = np.zeros(len(want), np.uint64)
+        inside = at < len(self.codes)
+        hit = np.zeros(len(want), bool)
+        hit[inside] = self.codes[at[inside]] == want[inside]
+        out[hit] = self.counts[at[hit]]
+        return int(out[0]) if one else out
+
+    def kmer_bytes(self):
+        """the codes decoded, a list of bytes in the order of codes (`kmers` itself is the number of valid positions)"""
+        return _kmer_decode(self.codes, self.k)
+
+    def most_common(self, n=None):
+        """[(k-mer as bytes, count)], the largest counts first, equal counts by ascending code"""
+        order = np.lexsort((self.codes, np.iinfo(np.uint64).max - self.counts))
+        if n is not None:
+            order = order[:max(int(n), 0)]
+        return list(zip(_kmer_decode(self.codes[order], self.k), (int(c) for c in self.counts[order])))
+
+    def to_kmerset(self, min_count=1, max_count=None, name="counted"):
+        """the codes with min_count <= count <= max_count as a KmerSet of one reference: the solid k-mers of this run as the set of the
+        next screen"""
+        min_count, max_count, _ = _count_filter(min_count, max_count, 2)
+        if min_count is None:
+            raise ValueError("min_count is an integer")
+        take = self.counts >= np.uint64(min_count)
+        if max_count is not None:
+            take &= self.counts <= np.uint64(max_count)
+        codes = self.codes[take]
+        return KmerSet.from_codes(self.k, codes, np.ones(len(codes), np.uint64), 1, self.canonical, [name])
+
+    def __add__(self, other):
+        if not isinstance(other, KmerCounts):
+            return NotImplemented
+        if (self.k, self.canonical) != (other.k, other.canonical):
+            raise ValueError("k-mer counts of different k or canonical do not add")
+        if not (self.unfiltered and other.unfiltered) or self.bins != other.bins:
+            raise ValueError("only unfiltered k-mer counts of equal bins add: a filtered count has lost the codes that the sum needs")
+        codes, counts = np.concatenate([self.codes, other.codes]), np.concatenate([self.counts, other.counts])
+        order = np.argsort(codes, kind="stable")
+        codes, counts = codes[order], counts[order]
+        if len(codes):
+            at = np.nonzero(np.concatenate([[True], codes[1:] != codes[:-1]]))[0]
+            codes, counts = codes[at], np.add.reduceat(counts, at)
+        return KmerCounts(self.k, self.canonical, codes, counts, _kmer_spectrum(counts, self.bins), records=self.records + other.records,
+                          bases=self.bases + other.bases, kmers=self.kmers + other.kmers, distinct=len(codes))
+
+    def save(self, path):
+        """the counts as an .npz"""
+        np.savez(path, k=np.int64(self.k), canonical=np.bool_(self.canonical), codes=self.codes, counts=self.counts, spectrum=self.spectrum,
+                 filter=np.array([self.min_count or 0, self.max_count or 0], np.uint64),      # (0: None)
+                 totals=np.array([self.records, self.bases, self.kmers, self.distinct], np.uint64))
+
+    @classmethod
+    def load(cls, path):
+        """counts that save() wrote; they are judged as the constructor judges its arguments"""
+        with np.load(path, allow_pickle=False) as z:
+            lo, hi = (int(v) for v in z["filter"])
+            records, bases, kmers, distinct = (int(v) for v in z["totals"])
+            return cls(int(z["k"]), bool(z["canonical"]), z["codes"], z["counts"], z["spectrum"], min_count=lo or None, max_count=hi or None,
+                       records=records, bases=bases, kmers=kmers, distinct=distinct)
+
+    def __eq__(self, other):
+        return (isinstance(other, KmerCounts) and (self.k, self.canonical, self.min_count, self.max_count, self.records, self.bases, self.kmers, self.distinct) ==
+                (other.k, other.canonical, other.min_count, other.max_count, other.records, other.bases, other.kmers, other.distinct) and
+                np.array_equal(self.codes, other.codes) and np.array_equal(self.counts, other.counts) and np.array_equal(self.spectrum, other.spectrum))
+
+    __hash__ = None
+
+    def __repr__(self):
+        return (f"<KmerCounts: k = {self.k}{', canonical' if self.canonical else ''}, {self.distinct} codes of {self.kmers} k-mers in {self.records} records, "
+                f"{len(self)} pairs (count >= {self.min_count}{'' if self.max_count is None else f', <= {self.max_count}'})>")
+
+
+def _count_conf(record_lines, seq_line, first_byte, delimiter):
+    """-> (BgzfCountConf, delimiter as bytes); ValueError as KmerCounter.add_file() documents it"""
+    delimiter = _partition_delimiter(delimiter)
+    k, _, b = _grep_record_args(record_lines, None, first_byte)
+    return _lib.BgzfCountConf(k, _trim_int(seq_line, 0, k - 1, "seq_line"), b, 0), delimiter
+
+
+class _KmerCountSink:
+    """what _grep_file hands a window's records to when their k-mers are counted: before every window the counter's table is given
+    room for the window's text, then the window is added"""
+
+    def __init__(self, conf, owner):
+        self.conf, self.owner, self.bases, self.kmers, self.started = conf, owner, 0, 0, False
+
+    def call(self, ctx, data, members, text_off, text_end, delim, flags, k, first_byte, record_base):
+        table = self.owner._reserve(ctx, text_end - text_off)
+        self.started = True
+        r, status, tot = ctx.bgzf_count_kmers(data, members, text_off, text_end, delim, flags, self.conf, table, record_base)
+        if r != _lib.OK:
+            raise RuntimeError("count_kmers: the table had no room for a window it was reserved for")
+        return status, tot, b""
+
+    def window(self, tot, packed):
+        self.bases += int(tot.bases)
+        self.kmers += int(tot.kmers)
+
+    def finish(self, searched):
+        return searched, self.bases, self.kmers
+
+
+class KmerCounter:
+    """Counts the k-mers of the reads of any number of BGZF files -- or of shards of them -- on the GPU: jellyfish count and histo, KMC,
+    the k-mer spectrum.  The table lives on the device and grows as the files are read; the text never comes to the host.
+      k, canonical       the rule of KmerSet: 1 <= k <= 31; with canonical a k-mer and its reverse complement are one code
+      max_table_bytes    MemoryError, naming the bytes needed, before the table would grow beyond this (None: what the device gives)
+    add_file() adds a file, add_counts() a KmerCounts, result() gives the KmerCounts of everything added so far, close() frees the
+    table.  After an error of a file (a bad block, a first_byte violation, ...) the counter holds an unknown part of a window and
+    refuses further use (ValueError)."""
+
+    def __init__(self, k=31, canonical=True, *, max_table_bytes=None, _room=0):
+        self.k, self.canonical = _kmer_rule(k, canonical)
+        self.max_table_bytes = None if max_table_bytes is None else _trim_int(max_table_bytes, 0, 1 << 62, "max_table_bytes")
+        self._room = _trim_int(_room, 0, _lib.KMER_COUNTER_MAX_CAP // 2, "_room")
+        self._ctx = self._table = None
+        self.records = self.bases = 0
+        self._closed = self._broken = False
+
+    def _live(self):
+        if self._closed:
+            raise ValueError("the counter is closed")
+        if self._broken:
+            raise ValueError("the counter holds an unknown part of a file after an error and cannot be used")
+
+    def _device(self, ctx):
+        """the DeviceKmerCounter, made on first use in the context of that use"""
+        if self._table is None:
+            self._ctx = ctx or zlib_ng._ctx()
+            self._table = self._ctx.kmer_counter_new(self.k, _lib.KMER_CANONICAL if self.canonical else 0, self._room)
+        elif ctx is not None and ctx is not self._ctx:
+            raise ValueError("a KmerCounter stays in the context of its first use")
+        return self._table
+
+    def _reserve(self, ctx, room):
+        """room for `room` more codes, by the rule of the C call; MemoryError, with nothing launched, when that cannot be had"""
+        table = self._device(ctx)
+        info = table.info
+        need = info.distinct + int(room)
+        if need <= info.cap // 2:
+            return table
+        cap = 64
+        while cap < 4 * need:
+            cap <<= 1
+        nbytes = cap * 16
+        if cap > _lib.KMER_COUNTER_MAX_CAP or (self.max_table_bytes is not None and nbytes > self.max_table_bytes):
+            raise MemoryError(f"the k-mer table needs {nbytes} bytes for {info.distinct} codes and {int(room)} more (max_table_bytes)")
+        if table.reserve(int(room)) != _lib.OK:
+            raise MemoryError(f"the device cannot give the {nbytes} bytes that the k-mer table needs")
+        return table
+
+    def add_file(self, file, record_lines=4, *, seq_line=1, first_byte=None, delimiter=b"\n", start=None, stop=None, first_record=0, max_record=64 << 20,
+                 allow_short=False, _ctx=None):
+        """Adds the k-mers of the reads of a BGZF file (a path or a seekable binary file).  The sequence of a record is the line
+        seq_line; a k-mer with a byte other than A, C, G, T, U in either case counts for nothing.  record_lines, first_byte, delimiter,
+        start, stop, first_record, max_record, allow_short and the errors of the file are those of grep_records().  -> self"""
+        self._live()
+        conf, delimiter = _count_conf(record_lines, seq_line, first_byte, delimiter)      # (judged before the file is opened)
+        if _is_path(file):
+            with _builtin_open(file, "rb") as f:
+                return self.add_file(f, record_lines, seq_line=seq_line, first_byte=first_byte, delimiter=delimiter, start=start, stop=stop,
+                                     first_record=first_record, max_record=max_record, allow_short=allow_short, _ctx=_ctx)
+        sink = _KmerCountSink(conf, self)
+        try:
+            records, bases, _ = _grep_file(file, _ctx or self._ctx, None, delimiter, False, False, False, None, start, stop, first_record, max_record,
+                                           (record_lines, None, first_byte, allow_short), 0, None, sink)
+        except BaseException:
+            self._broken = sink.started                      # (a part of the file is in the counts; before the first window nothing is)
+            raise
+        self.records, self.bases = self.records + records, self.bases + bases
+        return self
+
+    def add_counts(self, counts):
+        """Adds a KmerCounts of the same k and canonical that holds all its pairs (unfiltered).  -> self"""
+        self._live()
+        if not isinstance(counts, KmerCounts) or (counts.k, counts.canonical) != (self.k, self.canonical) or not counts.unfiltered:
+            raise ValueError("add_counts takes unfiltered KmerCounts of the counter's k and canonical")
+        table = self._reserve(None, len(counts))
+        if table.add(counts.codes, counts.counts) != _lib.OK:
+            raise RuntimeError("add_counts: the table had no room for the pairs it was reserved for")
+        self.records, self.bases = self.records + counts.records, self.bases + counts.bases
+        return self
+
+    def result(self, min_count=1, max_count=None, bins=10001):
+        """-> KmerCounts: the pairs with min_count <= count <= max_count (max_count None: no upper bound; min_count None: no pair, the
+        spectrum only) and the spectrum of ALL codes in `bins` entries (2 to 16384)."""
+        self._live()
+        min_count, max_count, bins = _count_filter(min_count, max_count, bins)
+        table = self._device(None)
+        info = table.info
+        if info.poisoned:
+            raise ValueError("the counter holds an unknown part of a file after an error and cannot be used")
+        spectrum = table.histogram(bins)
+        codes = counts = np.empty(0, np.uint64)
+        if min_count is not None:
+            _, codes, counts, _ = table.export(min_count, max_count or 0)
+            order = np.argsort(codes, kind="stable")
+            codes, counts = codes[order], counts[order]
+        return KmerCounts(self.k, self.canonical, codes, counts, spectrum, min_count=min_count, max_count=max_count, records=self.records,
+                          bases=self.bases, kmers=info.total, distinct=info.distinct)
+
+    def close(self):
+        if self._table is not None:
+            self._table.free()
+        self._table, self._closed = None, True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def count_kmers(file_or_files, k=31, *, canonical=True, min_count=1, max_count=None, bins=10001, record_lines=4, seq_line=1, first_byte=None,
+                delimiter=b"\n", max_record=64 << 20, allow_short=False, max_table_bytes=None):
+    """The k-mers of the reads of one BGZF file, or of a list of them (R1 and R2, the lanes of a run), counted on the GPU in one call:
+    a KmerCounter, add_file() for each, result(), close().  -> KmerCounts.  k, canonical and max_table_bytes are KmerCounter's,
+    min_count, max_count and bins are result()'s, the other keywords are add_file()'s."""
+    _count_filter(min_count, max_count, bins)                # (judged before a file is looked at)
+    _count_conf(record_lines, seq_line, first_byte, delimiter)
+    files = list(file_or_files) if isinstance(file_or_files, (list, tuple)) else [file_or_files]
+    with KmerCounter(k, canonical, max_table_bytes=max_table_bytes) as counter:
+        for f in files:
+            counter.add_file(f, record_lines, seq_line=seq_line, first_byte=first_byte, delimiter=delimiter, max_record=max_record, allow_short=allow_short)
+        return counter.result(min_count, max_count, bins)
 
 
 # ---- records in another order (DESIGN.md section 5f.9): a key per record, a stable sort of keys, records written in any order
