@@ -9,7 +9,7 @@
 //                      slot's counter
 //   za_k_dedup_lookup  one thread per key: the slot again, first[] and count[], the totals
 //   za_k_dedup_close   one thread: the totals as the caller reads them
-//   za_k_dedup_keys_close  one thread: the fault words, tail_off, short_lines of the key pass
+// The close kernel of the key pass is za_k_rec_close<ZaKeyTotals> of za_grep_records.hip.
 // Included by zng_amd.hip behind za_qc.hip (za_trim_body reads a line's body here too).
 #include "za_common.h"
 
@@ -100,15 +100,6 @@ __global__ __launch_bounds__(256) void za_k_dedup_keys(const uint8_t *__restrict
         if (bytes_in) atomicAdd((unsigned long long *)&tot->bytes_in, (unsigned long long)bytes_in);
         if (bases) atomicAdd((unsigned long long *)&tot->bases, (unsigned long long)bases);
     }
-}
-
-// one thread.  nrec > 0.
-__global__ void za_k_dedup_keys_close(const unsigned long long *__restrict__ start, uint64_t lines, uint64_t nrec, uint32_t k_lines, uint32_t flags, uint64_t text_end,
-                                      uint64_t record_base, const unsigned long long *__restrict__ bad, ZaKeyTotals *__restrict__ tot)
-{
-    if (blockIdx.x || threadIdx.x) return;
-    tot->covered = 1; tot->seen = nrec;
-    za_rec_close(start, lines, nrec, k_lines, flags, text_end, record_base, bad[0], 1u, tot);
 }
 
 // ---- the table.  cap (a power of two, >= 2 n, >= 64) slots of 64 bits, all ones for an empty one, otherwise the number of a record;

@@ -87,6 +87,17 @@ __device__ __forceinline__ void za_rec_close(const unsigned long long *__restric
     if (b < nrec) { tot->bad = kind; tot->bad_record = record_base + b; tot->bad_src = start[(uint64_t)k * b]; }
 }
 
+// one thread.  nrec > 0.  The close kernel of the calls whose only fault is a wrong first byte and whose eval kernel has summed everything
+// else already (za_dedup.hip, za_screen.hip, za_kcount.hip): covered, seen, and what za_rec_close sets.
+template <typename Totals>
+__global__ void za_k_rec_close(const unsigned long long *__restrict__ start, uint64_t lines, uint64_t nrec, uint32_t k_lines, uint32_t flags, uint64_t text_end,
+                               uint64_t record_base, const unsigned long long *__restrict__ bad, Totals *__restrict__ tot)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    tot->covered = 1; tot->seen = nrec;
+    za_rec_close(start, lines, nrec, k_lines, flags, text_end, record_base, bad[0], 1u, tot);
+}
+
 // grid: one thread per record.  sel[r] = 1 for a selected record, len[r] = its bytes (0 when it is not selected): what the scans sum.
 __global__ __launch_bounds__(256) void za_k_grep_rec_eval(const uint8_t *__restrict__ scratch, uint64_t text_off, uint64_t text_end,
                                                           const unsigned long long *__restrict__ start, uint64_t lines, const uint8_t *__restrict__ hit,

@@ -7,7 +7,7 @@
 //   za_k_kcount_pairs   one thread per (code, count) pair, given as two arrays or as the slots of an older table: claim and add
 //   za_k_kcount_export  one thread per slot: the slots whose count lies in [min_count, max_count] compacted
 //   za_k_kcount_hist    grid-stride over slots: a histogram of the counts per workgroup in LDS, flushed with 64-bit atomics
-// The close kernel of the reads pass is za_k_screen_close: the totals begin as the screen's do and are as long.
+// The close kernel of the reads pass is za_k_rec_close<ZaKcountTotals> of za_grep_records.hip.
 // Included by zng_amd.hip behind za_screen.hip.  A slot is a ZaKmerSlot whose second word is the count, so that za_kmer_claim serves as it is.
 #include "za_common.h"
 

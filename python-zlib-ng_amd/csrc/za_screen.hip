@@ -9,7 +9,7 @@
 //   za_k_kmer_export   one thread per slot: the occupied slots compacted, one ballot and one atomicAdd on a cursor per wave
 //   za_k_screen        one WAVE per record, its seq_line in strips of 64 positions: codes as in the insert, a plain load per probe, the
 //                      counts per reference in the lane that owns the reference.  No LDS, no scratch, no atomics but the totals'.
-//   za_k_screen_close  one thread: the fault words, tail_off, short_lines of the screen pass
+// The close kernel of the screen pass is za_k_rec_close<ZaScreenTotals> of za_grep_records.hip.
 // Included by zng_amd.hip behind za_sort.hip (za_trim_body reads a line's body, za_key_mix finds a code's home).
 #include "za_common.h"
 
@@ -259,13 +259,4 @@ __global__ __launch_bounds__(256) void za_k_screen(const uint8_t *__restrict__ s
         if (t_hits) atomicAdd((unsigned long long *)&tot->hits, (unsigned long long)t_hits);
         if (t_matched) atomicAdd((unsigned long long *)&tot->matched, (unsigned long long)t_matched);
     }
-}
-
-// one thread.  nrec > 0.
-__global__ void za_k_screen_close(const unsigned long long *__restrict__ start, uint64_t lines, uint64_t nrec, uint32_t k_lines, uint32_t flags, uint64_t text_end,
-                                  uint64_t record_base, const unsigned long long *__restrict__ bad, ZaScreenTotals *__restrict__ tot)
-{
-    if (blockIdx.x || threadIdx.x) return;
-    tot->covered = 1; tot->seen = nrec;
-    za_rec_close(start, lines, nrec, k_lines, flags, text_end, record_base, bad[0], 1u, tot);
 }

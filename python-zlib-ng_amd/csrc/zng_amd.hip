@@ -3858,6 +3858,75 @@ struct BgzfWindow { const uint8_t *d_in; uint64_t in_len; const ZaMember *d_memb
                     uint8_t *d_scratch; uint64_t scratch_cap; int32_t *d_status; };
 struct BgzfDest { ZaGrepRow *d_rows; uint64_t rows_cap; uint8_t *d_out; uint64_t out_cap; bool own; };
 
+// The window of a _dev form, out of the caller's device pointers.  -> false: a pointer that every _dev form needs is missing.
+static bool bgzf_dev_window(BgzfWindow *w, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off, uint64_t text_end,
+                            int delim, void *d_scratch, uint64_t scratch_cap, int32_t *d_status)
+{
+    if ((n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return false;
+    *w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch, scratch_cap, d_status};
+    return true;
+}
+
+// The tail of a _dev form: the stream is waited for.  rows_short: the caller's rows_cap did not hold the rows -- an error, unless a
+// record was bad: then there are no rows to miss, the code is OK and the totals name the record.
+static int bgzf_dev_finish(zngamd_ctx *c, bool rows_short = false, bool bad = false)
+{
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    if (rows_short && !bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    return ZNGAMD_OK;
+}
+
+// The window of a host form: the input and its member rows are staged, the window lies over the context's buffers.
+static int bgzf_host_window(zngamd_ctx *c, BgzfWindow *w, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
+                            uint64_t text_end, int delim)
+{
+    uint64_t scratch = 0;
+    const int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    if (r) return r;
+    *w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
+    return ZNGAMD_OK;
+}
+
+// the members' status words to the caller, and the stream is waited for
+static int bgzf_host_status(zngamd_ctx *c, int32_t *status, uint32_t n_members)
+{
+    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    prof_collect(c);
+    return ZNGAMD_OK;
+}
+
+// The `seen` rows of row_bytes each that a host form's call left in d_rows, to the caller.  The size is known, so the caller's memory is
+// asked for now; without an allocator rows_cap must hold them.
+static int bgzf_host_rows(zngamd_ctx *c, zngamd_alloc_fn alloc, void *user, void *rows, uint64_t rows_cap, const void *d_rows, uint64_t seen, size_t row_bytes)
+{
+    if (alloc) {
+        rows = alloc(user, seen * row_bytes);
+        if (!rows) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
+    } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
+    HIPCHK(c, hipMemcpyAsync(rows, d_rows, (size_t)seen * row_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+// [the host waits for the totals]: the launches so far are judged, and `bytes` bytes of d_tot come to `totals`
+static int bgzf_totals_read(zngamd_ctx *c, void *totals, const void *d_tot, size_t bytes)
+{
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(totals, d_tot, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return ZNGAMD_OK;
+}
+
+// the grid of a kernel that takes a WAVE per record: four records to a workgroup, at most per_cu workgroups per CU -- beyond that a wave
+// walks on to its next record
+static uint32_t bgzf_wave_grid(const zngamd_ctx *c, uint64_t nrec, uint32_t per_cu)
+{
+    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * per_cu;
+    return (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+}
+
 // decode, cover, mark (max_mismatch 0: za_k_grep_mark; more: za_k_grep_mark_approx), scan, and the host waits for the scan's totals: the first `totals_len` bytes of ZaGrepTotals go to `totals`.
 // After it every tile has its bits, its summary and its carry (gp_bits, gp_tiles, gp_carry), unless covered is 0.
 // marks = false (with max_mismatch 0): the delimiters alone -- za_k_grep_mark with an empty prefilter and no pattern, so no line matches.
@@ -3901,10 +3970,7 @@ static int bgzf_grep_lines_pass(zngamd_ctx *c, const BgzfWindow &w, const uint8_
                              c->gp_bits.p, c->gp_tiles.p);
       hipLaunchKernelGGL(za_k_grep_scan, dim3(1), dim3(ZA_GREP_SCAN_THREADS), 0, c->stream, c->gp_tiles.p, ntiles, tile0, w.text_off, w.text_end, flags, line_base,
                          d_cover, c->gp_carry.p, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, totals_len, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+    return bgzf_totals_read(c, totals, d_tot, totals_len);
 }
 
 // offsets, place, gather: the n rows' bytes packed into d_out in the order of the rows (gp_lens holds their lengths)
@@ -3930,6 +3996,29 @@ static int bgzf_dest_ready(zngamd_ctx *c, BgzfDest &d, uint64_t n, uint64_t byte
 }
 
 extern "C++" {
+// The totals area of a record call in buf: the call's totals struct, then n_bad fault words.  The struct is zeroed, a fault word is all
+// ones as long as no record has the fault.
+template <typename Totals>
+static int bgzf_totals_area(zngamd_ctx *c, DevBuf<unsigned long long> &buf, uint32_t n_bad, Totals **d_tot, unsigned long long **d_bad)
+{
+    constexpr size_t TOT_WORDS = sizeof(Totals) / 8u;
+    HIPCHK(c, buf.ensure(TOT_WORDS + n_bad));
+    *d_tot = (Totals *)buf.p; *d_bad = buf.p + TOT_WORDS;
+    HIPCHK(c, hipMemsetAsync(buf.p, 0, TOT_WORDS * 8u, c->stream));
+    HIPCHK(c, hipMemsetAsync(*d_bad, 0xFF, n_bad * 8u, c->stream));
+    return ZNGAMD_OK;
+}
+
+// Where a call's nrec rows go.  own: buf, the context's, made to hold them; otherwise the caller's *d_rows when rows_cap holds them, and
+// nowhere (*rows_short) when it does not.
+template <typename Row>
+static int bgzf_rows_dest(zngamd_ctx *c, DevBuf<Row> &buf, uint64_t nrec, bool own, Row **d_rows, uint64_t rows_cap, bool *rows_short)
+{
+    if (own) { HIPCHK(c, buf.ensure(nrec)); *d_rows = buf.p; }
+    else if (rows_cap < nrec) { *rows_short = true; *d_rows = nullptr; }
+    return ZNGAMD_OK;
+}
+
 // The last step of the four drivers below, once the host has read the totals: the destination, then emit(rows) -- the launch that
 // writes the n rows and their lengths (gp_lens) -- and the pack.
 template <typename Emit>
@@ -4005,18 +4094,15 @@ int zngamd_bgzf_grep_approx_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len
                                 zngamd_bgzf_grep_totals *totals)
 try {
     if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim, max_mismatch)) return ZNGAMD_E_ARG;
-    if (!c || !totals || (flags & ~15u) || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) ||
-        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !totals || (flags & ~15u) || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status) ||
+        (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     int r = bgzf_grep_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, line_base,
                           {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_grep(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -4037,15 +4123,12 @@ try {
     if (!c || !totals || (flags & ~15u) || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!out && out_cap) ||
         (alloc && (rows || out))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     r = bgzf_grep_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, line_base, {nullptr, 0, nullptr, 0, true}, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t n = totals->matched;
     if (!totals->covered || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !n) return ZNGAMD_OK;
     return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap);
@@ -4060,7 +4143,9 @@ static bool grep_records_ok(uint32_t record_lines, int32_t match_line, int32_t f
            first_byte >= -1 && first_byte <= 255;
 }
 
-// The records of a window, once the lines pass has said how many lines its text holds: what the three record drivers below begin with.
+// The records of a window, once the lines pass has said how many lines its text holds: what the eleven record drivers below begin with.
+// Nine of them (partition, trim, qc, key, sort key, place, screen, count, overlap) have no patterns of their own and call open(); grep
+// records and classify hand their patterns to the lines pass themselves and call begin().
 struct BgzfRecords {
     uint64_t lines, nrec, tile0; uint32_t ntiles, grid;             // grid: workgroups of 256 with a thread per record
     // lt: what the lines pass read.  covered and tail_off of the call's totals are set.  -> false: the call ends here (the member rows
@@ -4078,6 +4163,22 @@ struct BgzfRecords {
         ntiles = (uint32_t)((w.text_end - 1ull) / ZA_GREP_TILE - tile0 + 1ull);      // (a line was decided: the text is not empty)
         grid = (uint32_t)((nrec + 255u) / 256u);
         return true;
+    }
+    // The prologue of a call without patterns: the lines pass for the delimiters alone, [the host waits for the line count], begin, and
+    // gr_start made to hold the line starts.  *done: the call ends here, with the code returned (an error, or begin said so).
+    int open(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, uint32_t k, uint32_t *covered, uint64_t *tail_off, bool *done)
+    {
+        *done = true;
+        ZaGrepTotals lt;
+        static const uint8_t no_bytes[1] = {0};
+        static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
+        const uint32_t lflags = flags & ZA_GREP_FINAL;
+        const int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
+        if (r) return r;
+        if (!begin(w, lt, flags, k, covered, tail_off)) return ZNGAMD_OK;
+        HIPCHK(c, c->gr_start.ensure(lines + 1u));
+        *done = false;
+        return ZNGAMD_OK;
     }
     // where every line starts (gr_start, lines + 1 entries), and a byte per record with a line that matched into hit[] (or none: no pointer, capacity 0)
     void launch_lines(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, uint32_t k, int32_t match_line, uint8_t *hit, uint64_t hit_cap) const
@@ -4115,9 +4216,8 @@ static int bgzf_grep_records_dev(zngamd_ctx *c, const BgzfWindow &w, const uint8
       tbx_scan(c, c->gr_len.p, nrec, ZA_TBX_SUM, d_sums + 1);
       hipLaunchKernelGGL(za_k_grep_rec_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_sums, d_sums + 1,
                          d_sums + 2, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int rt = bgzf_totals_read(c, totals, d_tot, sizeof *totals);
+    if (rt) return rt;
     if (totals->bad || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !totals->selected) return ZNGAMD_OK;
     const uint64_t n = totals->selected;
     return bgzf_pack_rows(c, w, dst, n, totals->bytes, [&](ZaGrepRow *d_rows) {
@@ -4143,18 +4243,15 @@ int zngamd_bgzf_grep_records_approx_dev(zngamd_ctx *c, const void *d_in, uint64_
                                         uint64_t out_cap, zngamd_bgzf_grep_records_totals *totals)
 try {
     if (!grep_patterns_ok(patterns, patterns_len, table, n_patterns, delim, max_mismatch) || !grep_records_ok(record_lines, match_line, first_byte)) return ZNGAMD_E_ARG;
-    if (!c || !totals || (flags & ~15u) || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) ||
-        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !totals || (flags & ~15u) || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status) ||
+        (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     int r = bgzf_grep_records_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, record_lines, match_line, first_byte, record_base,
                                   {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_grep_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -4178,16 +4275,13 @@ try {
     if (!c || !totals || (flags & ~15u) || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!out && out_cap) ||
         (alloc && (rows || out))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     r = bgzf_grep_records_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, record_lines, match_line, first_byte, record_base,
                               {nullptr, 0, nullptr, 0, true}, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t n = totals->selected;
     if (!totals->covered || totals->bad || (flags & ZNGAMD_BGZF_GREP_COUNT_ONLY) || !n) return ZNGAMD_OK;
     return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap);
@@ -4248,9 +4342,8 @@ static int bgzf_classify_dev(zngamd_ctx *c, const BgzfWindow &w, const uint8_t *
       hipLaunchKernelGGL(za_k_cls_hist, dim3(nwg), dim3(ZA_CLS_WG_RECORDS), 0, c->stream, c->cl_cls.p, c->cl_len.p, nrec, ncls, nwg, c->cl_tab.p, d_tot);
       tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
       hipLaunchKernelGGL(za_k_cls_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, ncls, d_bad, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    r = bgzf_totals_read(c, totals, d_tot, sizeof *totals);
+    if (r) return r;
     if (totals->bad) return ZNGAMD_OK;
     const uint64_t n = totals->seen;
     // The class rows are n entries more for the caller's memory to hold: one capacity stands for both arrays; without _GROUP there
@@ -4274,18 +4367,15 @@ int zngamd_bgzf_classify_records_dev(zngamd_ctx *c, const void *d_in, uint64_t i
                                      zngamd_bgzf_classify_totals *totals)
 try {
     if (!classify_args_ok(patterns, patterns_len, table, n_patterns, delim, flags, max_mismatch, record_lines, match_line, first_byte, totals)) return ZNGAMD_E_ARG;
-    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_class && class_cap) || (!d_rows && rows_cap) ||
-        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status) || (!d_class && class_cap) ||
+        (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     int r = bgzf_classify_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, record_lines, match_line, first_byte, record_base, d_class,
                               class_cap, {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_classify_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -4298,16 +4388,13 @@ try {
     if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!cls && class_cap) || (!rows && rows_cap) || (!out && out_cap) ||
         (alloc && (cls || rows || out))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     r = bgzf_classify_dev(c, w, patterns, patterns_len, table, n_patterns, flags, max_mismatch, record_lines, match_line, first_byte, record_base, nullptr, 0,
                           {nullptr, 0, nullptr, 0, true}, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t n = totals->seen;
     const bool group = (flags & ZNGAMD_BGZF_CLASSIFY_GROUP) != 0;
     if (!totals->covered || totals->bad || !n) return ZNGAMD_OK;
@@ -4335,19 +4422,16 @@ static int bgzf_partition_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags
 {
     memset(totals, 0, sizeof *totals);
     memset(class_records, 0, (size_t)ncls * 8u); memset(class_bytes, 0, (size_t)ncls * 8u);
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL;
-    const int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const bool group = (flags & ZA_CLS_GROUP) != 0;
     const uint64_t lines = R.lines, nrec = R.nrec, nlab = std::min<uint64_t>(n_labels, nrec);
     const uint32_t nwg = (uint32_t)((nrec + ZA_PART_WG_RECORDS - 1u) / ZA_PART_WG_RECORDS);
     const uint64_t ntab = (uint64_t)ncls * nwg;
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab));
+    HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab));
     HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u)); HIPCHK(c, c->pt_tot.ensure(12u + 2u * ZA_PART_MAX_CLASSES));
     if (dst.own && nlab) {
         HIPCHK(c, c->pt_lab.ensure(nlab));
@@ -4366,11 +4450,10 @@ static int bgzf_partition_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags
       if (group) tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
       hipLaunchKernelGGL(za_k_part_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, nlab, k, lflags, w.text_end, record_base, ncls, d_cnt, d_bad,
                          d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(class_records, d_cnt, (size_t)ncls * 8u, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(class_records, d_cnt, (size_t)ncls * 8u, hipMemcpyDeviceToHost, c->stream));      // (the counts come with the totals: one wait)
     HIPCHK(c, hipMemcpyAsync(class_bytes, d_cnt + ncls, (size_t)ncls * 8u, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    r = bgzf_totals_read(c, totals, d_tot, sizeof *totals);
+    if (r) return r;
     const uint64_t n = totals->seen - totals->dropped;
     if (totals->bad || totals->labels_short || !group || !n) return ZNGAMD_OK;
     return bgzf_pack_rows(c, w, dst, n, totals->bytes, [&](ZaGrepRow *d_rows) {
@@ -4385,17 +4468,15 @@ int zngamd_bgzf_partition_records_dev(zngamd_ctx *c, const void *d_in, uint64_t 
                                       uint64_t *class_bytes, zngamd_bgzf_partition_totals *totals)
 try {
     if (!partition_args_ok(delim, flags, record_lines, first_byte, d_labels, n_labels, n_classes, class_records, class_bytes, totals)) return ZNGAMD_E_ARG;
-    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status) || (!d_rows && rows_cap) ||
+        (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     int r = bgzf_partition_dev(c, w, flags, record_lines, first_byte, record_base, {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, d_labels,
                                n_labels, n_classes, class_records, class_bytes, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_partition_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -4407,16 +4488,13 @@ try {
     if (!partition_args_ok(delim, flags, record_lines, first_byte, labels, n_labels, n_classes, class_records, class_bytes, totals)) return ZNGAMD_E_ARG;
     if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!rows && rows_cap) || (!out && out_cap) || (alloc && (rows || out))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     r = bgzf_partition_dev(c, w, flags, record_lines, first_byte, record_base, {nullptr, 0, nullptr, 0, true}, labels, n_labels, n_classes, class_records,
                            class_bytes, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t n = totals->seen - totals->dropped;
     if (!totals->covered || totals->bad || totals->labels_short || !(flags & ZNGAMD_BGZF_CLASSIFY_GROUP) || !n) return ZNGAMD_OK;
     return bgzf_host_fetch(c, alloc, user, n, totals->bytes, rows, rows_cap, out, out_cap);
@@ -4446,20 +4524,17 @@ static int bgzf_trim_dev(zngamd_ctx *c, const BgzfWindow &w, const uint8_t *patt
                          uint64_t trim_cap, BgzfDest dst, zngamd_bgzf_trim_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines, ncls = 2u;
-    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const bool group = (flags & ZA_CLS_GROUP) != 0, keep_short = (cf.flags & ZA_TRIM_KEEP_SHORT) != 0;
     const uint64_t lines = R.lines, nrec = R.nrec, ndrop = std::min<uint64_t>(n_drop, nrec);
     const uint32_t nwg = (uint32_t)((nrec + ZA_PART_WG_RECORDS - 1u) / ZA_PART_WG_RECORDS);
     const uint64_t ntab = (uint64_t)ncls * nwg;
     constexpr size_t TOT_WORDS = sizeof(ZaTrimTotals) / 8u;                              // then the two faults, the scan's sum, the counts, hist's totals
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab)); HIPCHK(c, c->pt_lab.ensure(nrec));
+    HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab)); HIPCHK(c, c->pt_lab.ensure(nrec));
     HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u)); HIPCHK(c, c->tr_row.ensure(nrec));
     HIPCHK(c, c->tr_tot.ensure(TOT_WORDS + 3u + 2u * ncls + sizeof(ZaPartTotals) / 8u));
     if (dst.own && drop && ndrop) {
@@ -4488,9 +4563,8 @@ static int bgzf_trim_dev(zngamd_ctx *c, const BgzfWindow &w, const uint8_t *patt
       if (group) tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
       hipLaunchKernelGGL(za_k_trim_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, ndrop, drop ? 1u : 0u, k, lflags, w.text_end, record_base,
                          d_cnt, d_bad, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    r = bgzf_totals_read(c, totals, d_tot, sizeof *totals);
+    if (r) return r;
     if (totals->bad || totals->drop_short) return ZNGAMD_OK;
     const uint64_t n = group ? totals->kept + (keep_short ? totals->too_short : 0ull) : 0ull, bytes = group ? totals->bytes : 0ull;
     if (!dst.own && totals->seen > trim_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
@@ -4520,18 +4594,15 @@ int zngamd_bgzf_trim_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_le
                                  zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_trim_totals *totals)
 try {
     if (!trim_args_ok(patterns, patterns_len, table, n_patterns, delim, flags, conf, d_drop, n_drop, totals)) return ZNGAMD_E_ARG;
-    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_trim && trim_cap) || (!d_rows && rows_cap) ||
-        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status) || (!d_trim && trim_cap) ||
+        (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     int r = bgzf_trim_dev(c, w, patterns, table, n_patterns, flags, *conf, record_base, d_drop, n_drop, d_trim, trim_cap,
                           {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_trim_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -4544,15 +4615,12 @@ try {
     if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!trim && trim_cap) || (!rows && rows_cap) || (!out && out_cap) ||
         (alloc && (trim || rows || out))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     r = bgzf_trim_dev(c, w, patterns, table, n_patterns, flags, *conf, record_base, drop, n_drop, nullptr, 0, {nullptr, 0, nullptr, 0, true}, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t seen = totals->seen;
     const bool group = (flags & ZNGAMD_BGZF_CLASSIFY_GROUP) != 0;
     if (!totals->covered || totals->bad || totals->drop_short || !seen) return ZNGAMD_OK;
@@ -4587,39 +4655,30 @@ static int bgzf_qc_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, const
     totals->min_len = UINT64_MAX;
     *rows_short = false;
     HIPCHK(c, hipMemsetAsync(d_tables, 0, (size_t)ZNGAMD_BGZF_QC_TABLE_WORDS(cf.cycles) * 8u, c->stream));
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
-    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const uint64_t lines = R.lines, nrec = R.nrec;
-    const bool want_rows = (cf.flags & ZA_QC_ROWS) != 0;
-    constexpr size_t TOT_WORDS = sizeof(ZaQcTotals) / 8u;                                // then the two faults
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->qc_tot.ensure(TOT_WORDS + 2u));
-    if (want_rows && own) { HIPCHK(c, c->qc_row.ensure(nrec)); d_rows = c->qc_row.p; }
-    else if (want_rows && rows_cap < nrec) { *rows_short = true; d_rows = nullptr; }
-    else if (!want_rows) d_rows = nullptr;
+    if (cf.flags & ZA_QC_ROWS) r = bgzf_rows_dest(c, c->qc_row, nrec, own, &d_rows, rows_cap, rows_short);
+    else d_rows = nullptr;
+    if (r) return r;
     // the persistent grid: ZA_QC_WG_PER_CU workgroups per CU, each with one span of at least ZA_QC_SPAN_MIN records
     const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_QC_WG_PER_CU;
     const uint64_t span = std::min<uint64_t>(std::max<uint64_t>((nrec + slots - 1u) / slots, ZA_QC_SPAN_MIN), ZA_QC_SPAN_MAX);
     const ZaQcPar P = {k, (uint32_t)cf.seq_line, cf.qual_line, cf.first_byte, cf.quality_base, cf.cycles, cf.low_quality, w.delim};
-    ZaQcTotals *d_tot = (ZaQcTotals *)c->qc_tot.p;
-    unsigned long long *d_bad = c->qc_tot.p + TOT_WORDS;
-    HIPCHK(c, hipMemsetAsync(c->qc_tot.p, 0, TOT_WORDS * 8u, c->stream));
+    ZaQcTotals *d_tot;
+    unsigned long long *d_bad;                                                           // the two faults
+    r = bgzf_totals_area(c, c->qc_tot, 2u, &d_tot, &d_bad);
+    if (r) return r;
     HIPCHK(c, hipMemsetAsync(&d_tot->min_len, 0xFF, 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 16, c->stream));
     { ProfScope ps(c, ZNGAMD_K_GATHER);
       R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
       hipLaunchKernelGGL(za_k_qc_eval, dim3((uint32_t)((nrec + span - 1u) / span)), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, span,
                          P, d_tables, d_rows, d_tot);
       hipLaunchKernelGGL(za_k_qc_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+    return bgzf_totals_read(c, totals, d_tot, sizeof *totals);
 }
 
 int zngamd_bgzf_qc_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
@@ -4628,19 +4687,16 @@ int zngamd_bgzf_qc_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len,
                                zngamd_bgzf_qc_totals *totals)
 try {
     if (!qc_args_ok(delim, flags, conf, d_tables, d_rows, false, totals)) return ZNGAMD_E_ARG;
-    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_rows && rows_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status) || (!d_rows && rows_cap))
+        return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     if (tables_cap < ZNGAMD_BGZF_QC_TABLE_WORDS(conf->cycles)) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     bool rows_short = false;
     int r = bgzf_qc_dev(c, w, flags, *conf, record_base, (unsigned long long *)d_tables, false, (ZaQcRow *)d_rows, rows_cap, &rows_short, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (rows_short && !totals->bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c, rows_short, totals->bad != 0);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_qc_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -4652,27 +4708,19 @@ try {
     std::lock_guard<std::mutex> g(c->mu);
     const uint64_t words = ZNGAMD_BGZF_QC_TABLE_WORDS(conf->cycles);
     if (tables_cap < words) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
     HIPCHK(c, c->qc_tab.ensure(words));
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     bool rows_short = false;
     r = bgzf_qc_dev(c, w, flags, *conf, record_base, c->qc_tab.p, true, nullptr, 0, &rows_short, totals);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(tables, c->qc_tab.p, (size_t)words * 8u, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
+    HIPCHK(c, hipMemcpyAsync(tables, c->qc_tab.p, (size_t)words * 8u, hipMemcpyDeviceToHost, c->stream));      // (the tables come with the status words: one wait)
+    r = bgzf_host_status(c, status, n_members);
+    if (r) return r;
     const uint64_t seen = totals->seen;
     if (!(conf->flags & ZNGAMD_BGZF_QC_ROWS) || !totals->covered || totals->bad || !seen) return ZNGAMD_OK;
-    if (alloc) {
-        rows = (zngamd_bgzf_qc_row *)alloc(user, seen * sizeof(zngamd_bgzf_qc_row));
-        if (!rows) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
-    } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    HIPCHK(c, hipMemcpyAsync(rows, c->qc_row.p, (size_t)seen * sizeof(ZaQcRow), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+    return bgzf_host_rows(c, alloc, user, rows, rows_cap, c->qc_row.p, seen, sizeof(ZaQcRow));
 } ZA_ABI_GUARD
 
 // ---- records keyed, keys resolved (za_dedup.hip)
@@ -4693,35 +4741,25 @@ static int bgzf_key_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, cons
 {
     memset(totals, 0, sizeof *totals);
     *rows_short = false;
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
-    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const uint64_t lines = R.lines, nrec = R.nrec;
-    constexpr size_t TOT_WORDS = sizeof(ZaKeyTotals) / 8u;                               // then the fault
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->dd_tot.ensure(TOT_WORDS + 1u));
-    if (own) { HIPCHK(c, c->dd_row.ensure(nrec)); d_rows = c->dd_row.p; }
-    else if (rows_cap < nrec) { *rows_short = true; d_rows = nullptr; }
-    // four records to a workgroup, at most ZA_KEY_WG_PER_CU workgroups per CU: beyond that a wave walks on to its next record
-    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_KEY_WG_PER_CU;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    r = bgzf_rows_dest(c, c->dd_row, nrec, own, &d_rows, rows_cap, rows_short);
+    if (r) return r;
+    const uint32_t grid = bgzf_wave_grid(c, nrec, ZA_KEY_WG_PER_CU);
     const ZaKeyPar P = {k, (uint32_t)cf.seq_line, cf.first_byte, cf.first, cf.length, cf.flags, w.delim};
-    ZaKeyTotals *d_tot = (ZaKeyTotals *)c->dd_tot.p;
-    unsigned long long *d_bad = c->dd_tot.p + TOT_WORDS;
-    HIPCHK(c, hipMemsetAsync(c->dd_tot.p, 0, TOT_WORDS * 8u, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    ZaKeyTotals *d_tot;
+    unsigned long long *d_bad;                                                           // the fault
+    r = bgzf_totals_area(c, c->dd_tot, 1u, &d_tot, &d_bad);
+    if (r) return r;
     { ProfScope ps(c, ZNGAMD_K_GATHER);
       R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
       hipLaunchKernelGGL(za_k_dedup_keys, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, P, d_rows, d_tot);
-      hipLaunchKernelGGL(za_k_dedup_keys_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+      hipLaunchKernelGGL(za_k_rec_close<ZaKeyTotals>, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
+    return bgzf_totals_read(c, totals, d_tot, sizeof *totals);
 }
 
 int zngamd_bgzf_key_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
@@ -4729,18 +4767,14 @@ int zngamd_bgzf_key_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len
                                 uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_key_row *d_rows, uint64_t rows_cap, zngamd_bgzf_key_totals *totals)
 try {
     if (!key_args_ok(delim, flags, conf, d_rows, false, totals)) return ZNGAMD_E_ARG;
-    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     bool rows_short = false;
     int r = bgzf_key_dev(c, w, flags, *conf, record_base, false, (ZaKeyRow *)d_rows, rows_cap, &rows_short, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (rows_short && !totals->bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c, rows_short, totals->bad != 0);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_key_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -4750,25 +4784,16 @@ try {
     if (!key_args_ok(delim, flags, conf, rows, alloc != nullptr, totals)) return ZNGAMD_E_ARG;
     if (!c || (!in && in_len) || (n_members && (!members || !status)) || (alloc && rows)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     bool rows_short = false;
     r = bgzf_key_dev(c, w, flags, *conf, record_base, true, nullptr, 0, &rows_short, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t seen = totals->seen;
     if (!totals->covered || totals->bad || !seen) return ZNGAMD_OK;
-    if (alloc) {
-        rows = (zngamd_bgzf_key_row *)alloc(user, seen * sizeof(zngamd_bgzf_key_row));
-        if (!rows) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
-    } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    HIPCHK(c, hipMemcpyAsync(rows, c->dd_row.p, (size_t)seen * sizeof(ZaKeyRow), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+    return bgzf_host_rows(c, alloc, user, rows, rows_cap, c->dd_row.p, seen, sizeof(ZaKeyRow));
 } ZA_ABI_GUARD
 
 // the slots of the table for n keys: the smallest power of two that is >= 2 n and >= ZA_DEDUP_MIN_CAP (n <= ZNGAMD_DEDUP_MAX_KEYS)
@@ -4805,9 +4830,8 @@ static int dedup_dev(zngamd_ctx *c, const ZaKeyRow *d_keys, uint64_t n, uint8_t 
       hipLaunchKernelGGL(za_k_dedup_insert, dim3(grid), dim3(256), 0, c->stream, d_keys, n, slot, cnt, cap - 1u);
       hipLaunchKernelGGL(za_k_dedup_lookup, dim3(grid), dim3(256), 0, c->stream, d_keys, n, slot, cnt, cap - 1u, d_first, d_count, acc);
       hipLaunchKernelGGL(za_k_dedup_close, dim3(1), dim3(1), 0, c->stream, acc, n, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int r = bgzf_totals_read(c, totals, d_tot, sizeof *totals);
+    if (r) return r;
     prof_collect(c);
     return ZNGAMD_OK;
 }
@@ -4888,38 +4912,28 @@ static int bgzf_sort_key_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags,
     *rows_short = false;
     const uint32_t W = sort_key_width(cf);
     totals->key_width = W;
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
-    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const uint64_t lines = R.lines, nrec = R.nrec;
-    constexpr size_t TOT_WORDS = sizeof(ZaSortKeyTotals) / 8u;                           // then the three faults
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->so_tot.ensure(TOT_WORDS + 3u));
     if (own) { HIPCHK(c, c->so_row.ensure(nrec * W + 8u)); HIPCHK(c, c->so_len.ensure(nrec)); d_rows = c->so_row.p; d_len = c->so_len.p; }
     else if (rows_cap < nrec) { *rows_short = true; d_rows = nullptr; d_len = nullptr; }
-    // four records to a workgroup, at most ZA_SORT_WG_PER_CU workgroups per CU: beyond that a wave walks on to its next record
-    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_SORT_WG_PER_CU;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    const uint32_t grid = bgzf_wave_grid(c, nrec, ZA_SORT_WG_PER_CU);
     ZaSortPar P = {};
     P.k_lines = k; P.first_byte = cf.first_byte; P.meta_byte = cf.meta_byte; P.n_parts = cf.n_parts; P.delim = w.delim; P.width = W; P.final = lflags ? 1u : 0u;
     static_assert(sizeof(ZaSortPart) == sizeof(zngamd_bgzf_sort_part) && sizeof(ZaSortPart) == 20, "the parts are copied as they are");
     memcpy(P.part, cf.part, sizeof P.part);
-    ZaSortKeyTotals *d_tot = (ZaSortKeyTotals *)c->so_tot.p;
-    unsigned long long *d_bad = c->so_tot.p + TOT_WORDS;
-    HIPCHK(c, hipMemsetAsync(c->so_tot.p, 0, TOT_WORDS * 8u, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 24, c->stream));
+    ZaSortKeyTotals *d_tot;
+    unsigned long long *d_bad;                                                           // the three faults
+    r = bgzf_totals_area(c, c->so_tot, 3u, &d_tot, &d_bad);
+    if (r) return r;
     { ProfScope ps(c, ZNGAMD_K_GATHER);
       R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
       hipLaunchKernelGGL(za_k_sort_keys, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, P, d_rows, d_len, d_tot);
       hipLaunchKernelGGL(za_k_sort_keys_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, W, d_bad, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+    return bgzf_totals_read(c, totals, d_tot, sizeof *totals);
 }
 
 int zngamd_bgzf_sort_key_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
@@ -4928,18 +4942,14 @@ int zngamd_bgzf_sort_key_records_dev(zngamd_ctx *c, const void *d_in, uint64_t i
                                      zngamd_bgzf_sort_key_totals *totals)
 try {
     if (!sort_key_args_ok(delim, flags, conf, d_rows, d_lengths, false, totals)) return ZNGAMD_E_ARG;
-    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     bool rows_short = false;
     int r = bgzf_sort_key_dev(c, w, flags, *conf, record_base, false, d_rows, d_lengths, rows_cap, &rows_short, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (rows_short && !totals->bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c, rows_short, totals->bad != 0);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_sort_key_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -4949,16 +4959,13 @@ try {
     if (!sort_key_args_ok(delim, flags, conf, rows, lengths, alloc != nullptr, totals)) return ZNGAMD_E_ARG;
     if (!c || (!in && in_len) || (n_members && (!members || !status)) || (alloc && (rows || lengths))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     bool rows_short = false;
     r = bgzf_sort_key_dev(c, w, flags, *conf, record_base, true, nullptr, nullptr, 0, &rows_short, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t seen = totals->seen, W = totals->key_width;
     if (!totals->covered || totals->bad || !seen) return ZNGAMD_OK;
     if (alloc) {
@@ -5069,39 +5076,30 @@ static int bgzf_place_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, ui
                           const uint32_t *length, uint64_t n, uint8_t *d_out, uint64_t out_cap, zngamd_bgzf_place_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL;
-    const int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const uint64_t lines = R.lines, nrec = R.nrec;
     const bool all = n >= nrec;                                                          // otherwise nothing is placed: labels_short
-    constexpr size_t TOT_WORDS = sizeof(ZaPlaceTotals) / 8u;                             // then the three faults
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->so_tot.ensure(TOT_WORDS + 3u));
     if (own && all) {
         HIPCHK(c, c->so_dst.ensure(nrec)); HIPCHK(c, c->so_len.ensure(nrec));
         HIPCHK(c, hipMemcpyAsync(c->so_dst.p, dst, (size_t)nrec * 8u, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->so_len.p, length, (size_t)nrec * 4u, hipMemcpyHostToDevice, c->stream));
         dst = (const uint64_t *)c->so_dst.p; length = c->so_len.p;
     }
-    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_SORT_WG_PER_CU;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
-    ZaPlaceTotals *d_tot = (ZaPlaceTotals *)c->so_tot.p;
-    unsigned long long *d_bad = c->so_tot.p + TOT_WORDS;
-    HIPCHK(c, hipMemsetAsync(c->so_tot.p, 0, TOT_WORDS * 8u, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 24, c->stream));
+    const uint32_t grid = bgzf_wave_grid(c, nrec, ZA_SORT_WG_PER_CU);
+    ZaPlaceTotals *d_tot;
+    unsigned long long *d_bad;                                                           // the three faults
+    r = bgzf_totals_area(c, c->so_tot, 3u, &d_tot, &d_bad);
+    if (r) return r;
     { ProfScope ps(c, ZNGAMD_K_GATHER);
       R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
       if (all) hipLaunchKernelGGL(za_k_sort_place, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, k, first_byte, w.delim,
                                   lflags ? 1u : 0u, (const unsigned long long *)dst, length, d_out, out_cap, d_tot);
       hipLaunchKernelGGL(za_k_sort_place_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, n, k, lflags, w.text_end, record_base, d_bad, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+    return bgzf_totals_read(c, totals, d_tot, sizeof *totals);
 }
 
 int zngamd_bgzf_place_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
@@ -5110,16 +5108,13 @@ int zngamd_bgzf_place_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_l
                                   uint64_t out_cap, zngamd_bgzf_place_totals *totals)
 try {
     if (!place_args_ok(delim, flags, record_lines, first_byte, d_dst, d_length, n, d_out, out_cap, totals)) return ZNGAMD_E_ARG;
-    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     int r = bgzf_place_dev(c, w, flags, record_lines, first_byte, record_base, false, d_dst, d_length, n, (uint8_t *)d_out, out_cap, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_place_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -5129,16 +5124,12 @@ try {
     if (!place_args_ok(delim, flags, record_lines, first_byte, dst, length, n, d_out, out_cap, totals)) return ZNGAMD_E_ARG;
     if (!c || (!in && in_len) || (n_members && (!members || !status))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     r = bgzf_place_dev(c, w, flags, record_lines, first_byte, record_base, true, dst, length, n, (uint8_t *)d_out, out_cap, totals);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
+    return bgzf_host_status(c, status, n_members);
 } ZA_ABI_GUARD
 
 // ---- reads screened against reference k-mers (za_screen.hip)
@@ -5327,36 +5318,26 @@ static int bgzf_screen_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, c
 {
     memset(totals, 0, sizeof *totals);
     *rows_short = false;
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
-    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const uint64_t lines = R.lines, nrec = R.nrec;
-    constexpr size_t TOT_WORDS = sizeof(ZaScreenTotals) / 8u;                            // then the fault
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->sc_tot.ensure(TOT_WORDS + 1u));
-    if (own) { HIPCHK(c, c->sc_row.ensure(nrec)); d_rows = c->sc_row.p; }
-    else if (rows_cap < nrec) { *rows_short = true; d_rows = nullptr; }
-    // four records to a workgroup, at most ZA_SCREEN_WG_PER_CU workgroups per CU: beyond that a wave walks on to its next record
-    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_SCREEN_WG_PER_CU;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    r = bgzf_rows_dest(c, c->sc_row, nrec, own, &d_rows, rows_cap, rows_short);
+    if (r) return r;
+    const uint32_t grid = bgzf_wave_grid(c, nrec, ZA_SCREEN_WG_PER_CU);
     const ZaScreenPar P = {k, (uint32_t)cf.seq_line, cf.first_byte, cf.min_hits, w.delim, set->info.k, set->info.flags & ZNGAMD_KMER_CANONICAL};
-    ZaScreenTotals *d_tot = (ZaScreenTotals *)c->sc_tot.p;
-    unsigned long long *d_bad = c->sc_tot.p + TOT_WORDS;
-    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, TOT_WORDS * 8u, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    ZaScreenTotals *d_tot;
+    unsigned long long *d_bad;                                                           // the fault
+    r = bgzf_totals_area(c, c->sc_tot, 1u, &d_tot, &d_bad);
+    if (r) return r;
     { ProfScope ps(c, ZNGAMD_K_GATHER);
       R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
       hipLaunchKernelGGL(za_k_screen, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, P, (const ZaKmerSlot *)set->tab,
                          set->info.cap - 1u, d_rows, d_tot, d_bad);
-      hipLaunchKernelGGL(za_k_screen_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+      hipLaunchKernelGGL(za_k_rec_close<ZaScreenTotals>, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
+    return bgzf_totals_read(c, totals, d_tot, sizeof *totals);
 }
 
 int zngamd_bgzf_screen_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len, const zngamd_member *d_members, uint32_t n_members, uint64_t text_off,
@@ -5365,18 +5346,14 @@ int zngamd_bgzf_screen_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in_
                                    zngamd_bgzf_screen_totals *totals)
 try {
     if (!screen_args_ok(c, delim, flags, conf, set, d_rows, false, totals)) return ZNGAMD_E_ARG;
-    if ((n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     bool rows_short = false;
     int r = bgzf_screen_dev(c, w, flags, *conf, set, record_base, false, (ZaScreenRow *)d_rows, rows_cap, &rows_short, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    if (rows_short && !totals->bad) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c, rows_short, totals->bad != 0);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_screen_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -5387,25 +5364,16 @@ try {
     if (!screen_args_ok(c, delim, flags, conf, set, rows, alloc != nullptr, totals)) return ZNGAMD_E_ARG;
     if ((!in && in_len) || (n_members && (!members || !status)) || (alloc && rows)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     bool rows_short = false;
     r = bgzf_screen_dev(c, w, flags, *conf, set, record_base, true, nullptr, 0, &rows_short, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t seen = totals->seen;
     if (!totals->covered || totals->bad || !seen) return ZNGAMD_OK;
-    if (alloc) {
-        rows = (zngamd_bgzf_screen_row *)alloc(user, seen * sizeof(zngamd_bgzf_screen_row));
-        if (!rows) return fail(c, ZNGAMD_MEM_ERROR, "the caller's allocator returned NULL");
-    } else if (seen > rows_cap) return fail(c, ZNGAMD_BUF_ERROR, "destination too small");
-    HIPCHK(c, hipMemcpyAsync(rows, c->sc_row.p, (size_t)seen * sizeof(ZaScreenRow), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+    return bgzf_host_rows(c, alloc, user, rows, rows_cap, c->sc_row.p, seen, sizeof(ZaScreenRow));
 } ZA_ABI_GUARD
 
 // ---- the k-mers of the reads counted (za_kcount.hip)
@@ -5627,34 +5595,24 @@ static int bgzf_count_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, co
                           bool *started, zngamd_bgzf_count_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines;
-    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const uint64_t lines = R.lines, nrec = R.nrec;
-    constexpr size_t TOT_WORDS = sizeof(ZaKcountTotals) / 8u;                            // then the fault
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->sc_tot.ensure(TOT_WORDS + 1u));
-    // four records to a workgroup, at most ZA_KCOUNT_WG_PER_CU workgroups per CU: beyond that a wave walks on to its next record
-    const uint64_t slots = (uint64_t)std::max<uint32_t>(c->search_slots, 1u) * ZA_KCOUNT_WG_PER_CU;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((nrec + 3u) / 4u, slots);
+    const uint32_t grid = bgzf_wave_grid(c, nrec, ZA_KCOUNT_WG_PER_CU);
     const ZaKcountPar P = {k, (uint32_t)cf.seq_line, cf.first_byte, w.delim, kc->k, kc->flags & ZNGAMD_KMER_CANONICAL};
-    ZaKcountTotals *d_tot = (ZaKcountTotals *)c->sc_tot.p;
-    unsigned long long *d_bad = c->sc_tot.p + TOT_WORDS;
-    HIPCHK(c, hipMemsetAsync(c->sc_tot.p, 0, TOT_WORDS * 8u, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    ZaKcountTotals *d_tot;
+    unsigned long long *d_bad;                                                           // the fault
+    r = bgzf_totals_area(c, c->sc_tot, 1u, &d_tot, &d_bad);
+    if (r) return r;
     *started = true;
     { ProfScope ps(c, ZNGAMD_K_GATHER);
       R.launch_lines(c, w, lflags, k, -1, nullptr, 0);      // (no line matched: the starts alone)
       hipLaunchKernelGGL(za_k_kcount_reads, dim3(grid), dim3(256), 0, c->stream, w.d_scratch, w.text_end, c->gr_start.p, lines, nrec, P, kc->tab, kc->cap - 1u, d_tot, d_bad);
-      hipLaunchKernelGGL(za_k_screen_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, (ZaScreenTotals *)d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return ZNGAMD_OK;
+      hipLaunchKernelGGL(za_k_rec_close<ZaKcountTotals>, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_bad, d_tot); }
+    return bgzf_totals_read(c, totals, d_tot, sizeof *totals);      // (an error after *started: count_settle sees the code)
 }
 
 // what a window call leaves in the counter: the slots it claimed and the positions it counted, or the poison
@@ -5670,12 +5628,11 @@ int zngamd_bgzf_count_kmers_dev(zngamd_ctx *c, const void *d_in, uint64_t in_len
                                 void *d_scratch, uint64_t scratch_cap, int32_t *d_status, zngamd_bgzf_count_totals *totals)
 try {
     if (!count_args_ok(c, delim, flags, conf, kc, totals)) return ZNGAMD_E_ARG;
-    if ((n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     if (!kcount_room_ok(kc, text_end > text_off ? text_end - text_off : 0u)) return fail(c, ZNGAMD_BUF_ERROR, "the k-mer table has no room: reserve first");
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     bool started = false;
     int r = bgzf_count_dev(c, w, flags, *conf, kc, record_base, &started, totals);
     if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(c, ZNGAMD_E_HIP, "hipStreamSynchronize");
@@ -5691,10 +5648,9 @@ try {
     if ((!in && in_len) || (n_members && (!members || !status))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     if (!kcount_room_ok(kc, text_end > text_off ? text_end - text_off : 0u)) return fail(c, ZNGAMD_BUF_ERROR, "the k-mer table has no room: reserve first");
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     bool started = false;
     r = bgzf_count_dev(c, w, flags, *conf, kc, record_base, &started, totals);
     if (!r && n_members && hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
@@ -5726,20 +5682,17 @@ static int bgzf_overlap_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, 
                             zngamd_bgzf_overlap_row *d_overlap, uint64_t overlap_cap, BgzfDest dst, zngamd_bgzf_overlap_totals *totals)
 {
     memset(totals, 0, sizeof *totals);
-    ZaGrepTotals lt;
-    static const uint8_t no_bytes[1] = {0};
-    static const zngamd_bgzf_pattern no_table[1] = {{0, 0}};
     const uint32_t lflags = flags & ZA_GREP_FINAL, k = cf.record_lines, ncls = 2u;
-    int r = bgzf_grep_lines_pass(c, w, no_bytes, 0, no_table, 0, lflags, 0, 0, &lt, sizeof lt, false);
-    if (r) return r;
     BgzfRecords R;
-    if (!R.begin(w, lt, flags, k, &totals->covered, &totals->tail_off)) return ZNGAMD_OK;
+    bool done;
+    int r = R.open(c, w, flags, k, &totals->covered, &totals->tail_off, &done);
+    if (r || done) return r;
     const bool group = (flags & ZA_CLS_GROUP) != 0, keep = (cf.flags & ZA_OVL_KEEP_UNMERGED) != 0;
     const uint64_t lines = R.lines, nrec = R.nrec;
     const uint32_t nwg = (uint32_t)((nrec + ZA_PART_WG_RECORDS - 1u) / ZA_PART_WG_RECORDS);
     const uint64_t ntab = (uint64_t)ncls * nwg;
     constexpr size_t TOT_WORDS = sizeof(ZaOvlTotals) / 8u;                               // then the two faults, the scan's sum, the counts, hist's totals
-    HIPCHK(c, c->gr_start.ensure(lines + 1u)); HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab)); HIPCHK(c, c->pt_lab.ensure(nrec));
+    HIPCHK(c, c->cl_len.ensure(nrec)); HIPCHK(c, c->cl_tab.ensure(ntab)); HIPCHK(c, c->pt_lab.ensure(nrec));
     HIPCHK(c, c->tb_blk.ensure(ntab / ZA_TBX_SCAN_ITEMS + 2u)); HIPCHK(c, c->ov_row.ensure(nrec));
     HIPCHK(c, c->tr_tot.ensure(TOT_WORDS + 3u + 2u * ncls + sizeof(ZaPartTotals) / 8u));
     const ZaOvlPar P = {k, k / 2u, (uint32_t)cf.seq_line, cf.qual_line, cf.first_byte, cf.quality_base, cf.min_overlap, cf.max_mismatch, cf.max_percent,
@@ -5756,9 +5709,8 @@ static int bgzf_overlap_dev(zngamd_ctx *c, const BgzfWindow &w, uint32_t flags, 
       hipLaunchKernelGGL(za_k_part_hist, dim3(nwg), dim3(ZA_PART_WG_RECORDS), 0, c->stream, c->pt_lab.p, nrec, c->cl_len.p, nrec, ncls, nwg, c->cl_tab.p, d_cnt, d_ptot);
       if (group) tbx_scan(c, c->cl_tab.p, ntab, ZA_TBX_SUM, d_sum);
       hipLaunchKernelGGL(za_k_ovl_close, dim3(1), dim3(1), 0, c->stream, c->gr_start.p, lines, nrec, k, lflags, w.text_end, record_base, d_cnt, d_bad, d_tot); }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(totals, d_tot, sizeof *totals, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    r = bgzf_totals_read(c, totals, d_tot, sizeof *totals);
+    if (r) return r;
     if (totals->bad) return ZNGAMD_OK;
     const uint64_t n = group ? totals->merged + (keep ? totals->seen - totals->merged : 0ull) : 0ull, bytes = group ? totals->bytes : 0ull;
     if (!dst.own && totals->seen > overlap_cap) { prof_collect(c); return fail(c, ZNGAMD_BUF_ERROR, "destination too small"); }
@@ -5787,17 +5739,14 @@ int zngamd_bgzf_overlap_records_dev(zngamd_ctx *c, const void *d_in, uint64_t in
                                     zngamd_bgzf_grep_row *d_rows, uint64_t rows_cap, void *d_out, uint64_t out_cap, zngamd_bgzf_overlap_totals *totals)
 try {
     if (!overlap_args_ok(delim, flags, conf, totals)) return ZNGAMD_E_ARG;
-    if (!c || (n_members && (!d_in || !d_members || !d_status)) || (!d_scratch && scratch_cap) || (!d_overlap && overlap_cap) || (!d_rows && rows_cap) ||
-        (!d_out && out_cap)) return ZNGAMD_E_ARG;
+    BgzfWindow w;
+    if (!c || !bgzf_dev_window(&w, d_in, in_len, d_members, n_members, text_off, text_end, delim, d_scratch, scratch_cap, d_status) || (!d_overlap && overlap_cap) ||
+        (!d_rows && rows_cap) || (!d_out && out_cap)) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    const BgzfWindow w = {(const uint8_t *)d_in, in_len, (const ZaMember *)d_members, n_members, text_off, text_end, (uint32_t)delim, (uint8_t *)d_scratch,
-                          scratch_cap, d_status};
     int r = bgzf_overlap_dev(c, w, flags, *conf, record_base, d_overlap, overlap_cap, {(ZaGrepRow *)d_rows, rows_cap, (uint8_t *)d_out, out_cap, false}, totals);
     if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
-    return ZNGAMD_OK;
+    return bgzf_dev_finish(c);
 } ZA_ABI_GUARD
 
 int zngamd_bgzf_overlap_records(zngamd_ctx *c, const uint8_t *in, uint64_t in_len, const zngamd_member *members, uint32_t n_members, uint64_t text_off,
@@ -5809,15 +5758,12 @@ try {
     if (!c || (!in && in_len) || (n_members && (!members || !status)) || (!overlap && overlap_cap) || (!rows && rows_cap) || (!out && out_cap) ||
         (alloc && (overlap || rows || out))) return ZNGAMD_E_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    uint64_t scratch = 0;
-    int r = bgzf_host_stage(c, in, in_len, members, n_members, &scratch);
+    BgzfWindow w;
+    int r = bgzf_host_window(c, &w, in, in_len, members, n_members, text_off, text_end, delim);
     if (r) return r;
-    const BgzfWindow w = {c->st_in.p, in_len, c->members.p, n_members, text_off, text_end, (uint32_t)delim, c->st_out.p, scratch, c->mstatus.p};
     r = bgzf_overlap_dev(c, w, flags, *conf, record_base, nullptr, 0, {nullptr, 0, nullptr, 0, true}, totals);
+    if (!r) r = bgzf_host_status(c, status, n_members);
     if (r) return r;
-    if (n_members) HIPCHK(c, hipMemcpyAsync(status, c->mstatus.p, (size_t)n_members * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    prof_collect(c);
     const uint64_t seen = totals->seen;
     const bool group = (flags & ZNGAMD_BGZF_CLASSIFY_GROUP) != 0;
     if (!totals->covered || totals->bad || !seen) return ZNGAMD_OK;

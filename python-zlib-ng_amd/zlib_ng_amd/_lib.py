@@ -748,6 +748,45 @@ def _addr(buf):
     return C.cast(C.c_char_p(b), C.c_void_p), b
 
 
+def _dv(x):
+    """A device pointer as the _dev forms take it (an int or anything int() takes; 0 or None: NULL)."""
+    return C.c_void_p(int(x)) if x else None
+
+
+def _window_in(data, members):
+    """What every host form of a BGZF call begins with: data = packed compressed blocks, members = numpy table of MEMBER rows ->
+    (the four arguments (input, its bytes, member rows or NULL, their number), the block statuses int32[n] for the engine to fill,
+    what keeps the input alive)"""
+    nm = len(members)
+    p, keep = _addr(data)
+    st = np.zeros(max(1, nm), np.int32)[:nm]         # (no member: a view of no entries whose address is still a real one)
+    return (p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm), st, keep
+
+
+class _RowsOut:
+    """Where the rows of a host form come back, one row of `dtype` per record.  caps None: the engine asks .fn for them once it knows
+    how many there are; a number: a buffer of that many rows (.ptr, .cap), which the engine refuses with BUF_ERROR when it is too small."""
+
+    def __init__(self, dtype, caps):
+        self.dtype, self.box, self.rows = dtype, [], None
+
+        def alloc(_user, nbytes):
+            self.box.append(np.empty(nbytes // dtype.itemsize, dtype))
+            return self.box[0].ctypes.data
+
+        if caps is None:
+            self.ptr, self.cap, self.fn = None, 0, ALLOC_FN(alloc)
+        else:
+            self.rows = np.zeros(max(1, caps), dtype)
+            self.ptr, self.cap, self.fn = C.c_void_p(self.rows.ctypes.data), caps, ALLOC_FN()
+
+    def take(self, got, seen):
+        """the rows when the call has left them (got), otherwise none"""
+        if not got:
+            return np.empty(0, self.dtype)
+        return self.box[0] if self.rows is None else self.rows[:seen]
+
+
 _py = C.pythonapi
 _py.PyBytes_FromStringAndSize.restype = C.py_object
 _py.PyBytes_FromStringAndSize.argtypes = [C.c_void_p, C.c_ssize_t]
@@ -1461,9 +1500,8 @@ class Context:
 
     def inflate_spans_dev(self, d_in, in_len, d_spans, n, d_windows, windows_len, d_out, out_cap, d_status):
         """zngamd_inflate_spans_dev on device pointers (ints or c_void_p); the statuses stay in d_status."""
-        v = lambda x: C.c_void_p(int(x)) if x else None
-        self._chk(self.L.zngamd_inflate_spans_dev(self.h, v(d_in), in_len, v(d_spans), n, v(d_windows), windows_len, v(d_out), out_cap,
-                                                  v(d_status)))
+        self._chk(self.L.zngamd_inflate_spans_dev(self.h, _dv(d_in), in_len, _dv(d_spans), n, _dv(d_windows), windows_len, _dv(d_out), out_cap,
+                                                  _dv(d_status)))
 
     def span_stats(self, reset=True):
         """(spans launched, bytes decoded OK by the host-buffer form) since the last reset"""
@@ -1517,19 +1555,17 @@ class Context:
 
     def inflate_batch_dev(self, d_in, in_len, d_items, n, wbits, count_only, d_out, out_cap, d_results, zdict=None):
         """zngamd_inflate_batch_dict_dev on device pointers (ints or c_void_p); the results stay in d_results."""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         dp, dkeep, dlen = _dict_arg(zdict)
-        self._chk(self.L.zngamd_inflate_batch_dict_dev(self.h, v(d_in), in_len, v(d_items), n, wbits, dp, dlen, 1 if count_only else 0,
-                                                       v(d_out), out_cap, v(d_results)))
+        self._chk(self.L.zngamd_inflate_batch_dict_dev(self.h, _dv(d_in), in_len, _dv(d_items), n, wbits, dp, dlen, 1 if count_only else 0,
+                                                       _dv(d_out), out_cap, _dv(d_results)))
 
     def deflate_batch_dev(self, d_in, in_len, items, n, level, wbits, strategy, d_out, out_cap, d_results, zdict=None):
         """zngamd_deflate_batch_dict_dev: items = a HOST ctypes array of BatchItem (out_off written) -> (code, total); code OK or
         BUF_ERROR (total = the size needed)"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         dp, dkeep, dlen = _dict_arg(zdict)
         total = C.c_uint64(0)
-        r = self._chk(self.L.zngamd_deflate_batch_dict_dev(self.h, v(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy,
-                                                           dp, dlen, v(d_out), out_cap, v(d_results), C.byref(total)), (OK, BUF_ERROR))
+        r = self._chk(self.L.zngamd_deflate_batch_dict_dev(self.h, _dv(d_in), in_len, C.cast(items, C.c_void_p), n, level, wbits, strategy,
+                                                           dp, dlen, _dv(d_out), out_cap, _dv(d_results), C.byref(total)), (OK, BUF_ERROR))
         return r, total.value
 
     def train_dict(self, data, items, n, dict_size, k, d):
@@ -1545,10 +1581,9 @@ class Context:
     def train_dict_dev(self, d_in, in_len, d_items, n, dict_size, k, d):
         """zngamd_train_dict_dev on device pointers (ints or c_void_p): the samples and the item table in device memory -> (code, the
         dictionary as bytes); code OK or E_ARG (an item outside the buffer, samples outside [k, 4 GiB): no bytes)"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         out = (C.c_uint8 * dict_size)()
         ln = C.c_uint32(0)
-        r = self._chk(self.L.zngamd_train_dict_dev(self.h, v(d_in), in_len, v(d_items), n, dict_size, k, d, C.cast(out, C.c_void_p),
+        r = self._chk(self.L.zngamd_train_dict_dev(self.h, _dv(d_in), in_len, _dv(d_items), n, dict_size, k, d, C.cast(out, C.c_void_p),
                                                    C.byref(ln)), (OK, E_ARG))
         return r, bytes(out[:ln.value])
 
@@ -1574,9 +1609,8 @@ class Context:
 
     def bgzf_compress_dev(self, d_in, n, block_size, level, eof, d_out, out_cap, d_table):
         """zngamd_bgzf_compress_dev on device pointers -> (stream bytes, rows written to d_table)"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         ol, nb = C.c_uint64(0), C.c_uint32(0)
-        self._chk(self.L.zngamd_bgzf_compress_dev(self.h, v(d_in), n, block_size, level, 1 if eof else 0, v(d_out), out_cap, C.byref(ol), v(d_table),
+        self._chk(self.L.zngamd_bgzf_compress_dev(self.h, _dv(d_in), n, block_size, level, 1 if eof else 0, _dv(d_out), out_cap, C.byref(ol), _dv(d_table),
                                                   C.byref(nb)))
         return ol.value, nb.value
 
@@ -1606,43 +1640,36 @@ class Context:
     def bgzf_read_dev(self, d_in, in_len, d_members, n_members, d_slices, n_slices, d_scratch, scratch_cap, d_out, out_cap, d_status,
                       d_slice_status):
         """zngamd_bgzf_read_dev on device pointers (ints or c_void_p); statuses and result stay on the device."""
-        v = lambda x: C.c_void_p(int(x)) if x else None
-        self._chk(self.L.zngamd_bgzf_read_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_slices), n_slices, v(d_scratch), scratch_cap,
-                                              v(d_out), out_cap, v(d_status), v(d_slice_status)))
+        self._chk(self.L.zngamd_bgzf_read_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, _dv(d_slices), n_slices, _dv(d_scratch), scratch_cap,
+                                              _dv(d_out), out_cap, _dv(d_status), _dv(d_slice_status)))
 
     def bgzf_count(self, data, members, delim):
         """zngamd_bgzf_count: data = packed compressed blocks, members = numpy table of MEMBER rows -> (block statuses int32[n],
         rows uint32[n, 2] of (count, flags)); the decoded bytes stay on the device"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
-        rows = np.zeros((max(1, nm), 2), np.uint32)
-        self._chk(self.L.zngamd_bgzf_count(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm, delim,
-                                           C.c_void_p(st.ctypes.data), C.c_void_p(rows.ctypes.data)))
-        return st[:nm], rows[:nm]
+        win, st, keep = _window_in(data, members)
+        rows = np.zeros((max(1, len(members)), 2), np.uint32)
+        self._chk(self.L.zngamd_bgzf_count(self.h, *win, delim, C.c_void_p(st.ctypes.data), C.c_void_p(rows.ctypes.data)))
+        return st, rows[:len(members)]
 
     def bgzf_line_positions(self, data, members, queries, delim):
         """zngamd_bgzf_line_positions: queries = uint32[n, 2] of (member, rank) -> (block statuses, scratch offsets uint64[n], verdicts
         int32[n])"""
-        nm, nq = len(members), len(queries)
-        p, keep = _addr(data)
+        nq = len(queries)
+        win, st, keep = _window_in(data, members)
         queries = np.ascontiguousarray(queries, np.uint32)
-        st = np.zeros(max(1, nm), np.int32)
         pos = np.zeros(max(1, nq), np.uint64)
         ps = np.zeros(max(1, nq), np.int32)
-        self._chk(self.L.zngamd_bgzf_line_positions(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
-                                                    C.c_void_p(queries.ctypes.data) if nq else None, nq, delim, C.c_void_p(st.ctypes.data),
+        self._chk(self.L.zngamd_bgzf_line_positions(self.h, *win, C.c_void_p(queries.ctypes.data) if nq else None, nq, delim, C.c_void_p(st.ctypes.data),
                                                     C.c_void_p(pos.ctypes.data), C.c_void_p(ps.ctypes.data)))
-        return st[:nm], pos[:nq], ps[:nq]
+        return st, pos[:nq], ps[:nq]
 
     def bgzf_read_lines(self, data, members, ranges, delim, out_cap=None):
         """zngamd_bgzf_read_lines: ranges = uint32[n, 4] of (m0, r0, m1, r1) -> (code, block statuses, range verdicts, range lengths,
         packed lines, bytes needed).  out_cap None: the result is allocated once the engine knows its size; a number: a buffer of that
         size, and code is BUF_ERROR (no lines) when the lines need more"""
-        nm, nr = len(members), len(ranges)
-        p, keep = _addr(data)
+        nr = len(ranges)
+        win, st, keep = _window_in(data, members)
         ranges = np.ascontiguousarray(ranges, np.uint32)
-        st = np.zeros(max(1, nm), np.int32)
         rs = np.zeros(max(1, nr), np.int32)
         rl = np.zeros(max(1, nr), np.uint32)
         ol = C.c_uint64(0)
@@ -1658,7 +1685,7 @@ class Context:
         else:
             out, op = _new_bytes(out_cap)
             cap, fn = out_cap, ALLOC_FN()
-        r = self._chk(self.L.zngamd_bgzf_read_lines(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_read_lines(self.h, *win,
                                                     C.c_void_p(ranges.ctypes.data) if nr else None, nr, delim, op, cap, fn, None, C.byref(ol),
                                                     C.c_void_p(rl.ctypes.data), C.c_void_p(st.ctypes.data), C.c_void_p(rs.ctypes.data)),
                       (OK, BUF_ERROR))
@@ -1666,29 +1693,26 @@ class Context:
             packed = box[0] if box else b""
         else:
             packed = _take(out, ol.value) if r == OK else b""
-        return r, st[:nm], rs[:nr], rl[:nr], packed, ol.value
+        return r, st, rs[:nr], rl[:nr], packed, ol.value
 
     def bgzf_count_dev(self, d_in, in_len, d_members, n_members, delim, d_scratch, scratch_cap, d_status, d_rows):
         """zngamd_bgzf_count_dev on device pointers; statuses and rows stay on the device."""
-        v = lambda x: C.c_void_p(int(x)) if x else None
-        self._chk(self.L.zngamd_bgzf_count_dev(self.h, v(d_in), in_len, v(d_members), n_members, delim, v(d_scratch), scratch_cap, v(d_status),
-                                               v(d_rows)))
+        self._chk(self.L.zngamd_bgzf_count_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, delim, _dv(d_scratch), scratch_cap, _dv(d_status),
+                                               _dv(d_rows)))
 
     def bgzf_line_positions_dev(self, d_in, in_len, d_members, n_members, d_queries, n_queries, delim, d_scratch, scratch_cap, d_status, d_pos,
                                 d_pos_status):
         """zngamd_bgzf_line_positions_dev on device pointers."""
-        v = lambda x: C.c_void_p(int(x)) if x else None
-        self._chk(self.L.zngamd_bgzf_line_positions_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_queries), n_queries, delim,
-                                                        v(d_scratch), scratch_cap, v(d_status), v(d_pos), v(d_pos_status)))
+        self._chk(self.L.zngamd_bgzf_line_positions_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, _dv(d_queries), n_queries, delim,
+                                                        _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_pos), _dv(d_pos_status)))
 
     def bgzf_read_lines_dev(self, d_in, in_len, d_members, n_members, d_ranges, n_ranges, delim, d_scratch, scratch_cap, d_out, out_cap,
                             d_range_len, d_status, d_range_status):
         """zngamd_bgzf_read_lines_dev on device pointers -> (code, packed bytes, or the bytes needed when code is BUF_ERROR)"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         ol = C.c_uint64(0)
-        r = self._chk(self.L.zngamd_bgzf_read_lines_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_ranges), n_ranges, delim,
-                                                        v(d_scratch), scratch_cap, v(d_out), out_cap, C.byref(ol), v(d_range_len), v(d_status),
-                                                        v(d_range_status)), (OK, BUF_ERROR))
+        r = self._chk(self.L.zngamd_bgzf_read_lines_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, _dv(d_ranges), n_ranges, delim,
+                                                        _dv(d_scratch), scratch_cap, _dv(d_out), out_cap, C.byref(ol), _dv(d_range_len), _dv(d_status),
+                                                        _dv(d_range_status)), (OK, BUF_ERROR))
         return r, ol.value
 
     def bgzf_grep(self, data, members, text_off, text_end, blob, table, delim, flags, line_base=0, caps=None, mismatches=0):
@@ -1719,10 +1743,8 @@ class Context:
         the records packed in that order); rows and records only with BGZF_CLASSIFY_GROUP in flags; nothing comes back when totals.bad
         is set.  caps None: the arrays are allocated once the engine knows their sizes; (class rows, rows, bytes): buffers of those sizes,
         and code is BUF_ERROR (nothing written) when the result needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
+        win, st, keep = _window_in(data, members)
         table = np.ascontiguousarray(table, np.uint32)
-        st = np.zeros(max(1, nm), np.int32)
         tot = BgzfClassifyTotals()
         group = bool(flags & BGZF_CLASSIFY_GROUP)
         box = []
@@ -1749,7 +1771,7 @@ class Context:
             if not ocap:
                 op = None
         bp, bkeep = _addr(blob)
-        r = self._chk(self.L.zngamd_bgzf_classify_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_classify_records(self.h, *win,
                                                           text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table), delim, flags,
                                                           mismatches, record_lines, match_line, first_byte, record_base, C.c_void_p(st.ctypes.data),
                                                           cp, ccap, rp, rcap, op, ocap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
@@ -1762,21 +1784,20 @@ class Context:
             cls_out = cls[:tot.seen] if got else np.empty(0, CLASS_ROW_DTYPE)
             rows_out = rows[:tot.seen] if got and group else np.empty(0, GREP_ROW_DTYPE)
             packed = _take(out, tot.bytes) if got and group else b""
-        return r, st[:nm], tot, cls_out, rows_out, packed
+        return r, st, tot, cls_out, rows_out, packed
 
     def bgzf_classify_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, mismatches, record_lines,
                                   match_line, first_byte, record_base, d_scratch, scratch_cap, d_status, d_class, class_cap, d_rows, rows_cap, d_out,
                                   out_cap):
         """zngamd_bgzf_classify_records_dev on device pointers (the patterns: host memory) -> (code, totals); class rows, rows and records
         stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         table = np.ascontiguousarray(table, np.uint32)
         tot = BgzfClassifyTotals()
         bp, bkeep = _addr(blob)
-        r = self._chk(self.L.zngamd_bgzf_classify_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob),
+        r = self._chk(self.L.zngamd_bgzf_classify_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, bp, len(blob),
                                                               C.c_void_p(table.ctypes.data), len(table), delim, flags, mismatches, record_lines,
-                                                              match_line, first_byte, record_base, v(d_scratch), scratch_cap, v(d_status),
-                                                              v(d_class), class_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
+                                                              match_line, first_byte, record_base, _dv(d_scratch), scratch_cap, _dv(d_status),
+                                                              _dv(d_class), class_cap, _dv(d_rows), rows_cap, _dv(d_out), out_cap, C.byref(tot)),
                       (OK, BUF_ERROR))
         return r, tot
 
@@ -1788,10 +1809,8 @@ class Context:
         order); rows and records only with BGZF_CLASSIFY_GROUP in flags; nothing comes back when totals.bad or totals.labels_short is set.
         caps None: the arrays are allocated once the engine knows their sizes; (rows, bytes): buffers of those sizes, and code is
         BUF_ERROR (nothing written) when the result needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
+        win, st, keep = _window_in(data, members)
         labels = np.ascontiguousarray(labels, np.uint16)
-        st = np.zeros(max(1, nm), np.int32)
         tot = BgzfPartitionTotals()
         crec, cbytes = np.zeros(max(1, n_classes), np.uint64), np.zeros(max(1, n_classes), np.uint64)
         box = []
@@ -1814,7 +1833,7 @@ class Context:
             rp, fn = C.c_void_p(rows.ctypes.data) if rcap else None, ALLOC_FN()
             if not ocap:
                 op = None
-        r = self._chk(self.L.zngamd_bgzf_partition_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_partition_records(self.h, *win,
                                                            text_off, text_end, delim, flags, record_lines, first_byte, record_base,
                                                            C.c_void_p(st.ctypes.data), rp, rcap, op, ocap, fn, None,
                                                            C.c_void_p(labels.ctypes.data) if len(labels) else None, len(labels), n_classes,
@@ -1825,18 +1844,17 @@ class Context:
             rows_out, packed = (box[0], box[1]) if got else (np.empty(0, GREP_ROW_DTYPE), b"")
         else:
             rows_out, packed = (rows[:kept], _take(out, tot.bytes)) if got else (np.empty(0, GREP_ROW_DTYPE), b"")
-        return r, st[:nm], tot, crec[:n_classes], cbytes[:n_classes], rows_out, packed
+        return r, st, tot, crec[:n_classes], cbytes[:n_classes], rows_out, packed
 
     def bgzf_partition_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, record_lines, first_byte, record_base,
                                    d_scratch, scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap, d_labels, n_labels, n_classes):
         """zngamd_bgzf_partition_records_dev on device pointers -> (code, totals, records per class, bytes per class); rows and records stay
         on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfPartitionTotals()
         crec, cbytes = np.zeros(max(1, n_classes), np.uint64), np.zeros(max(1, n_classes), np.uint64)
-        r = self._chk(self.L.zngamd_bgzf_partition_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
-                                                               record_lines, first_byte, record_base, v(d_scratch), scratch_cap, v(d_status),
-                                                               v(d_rows), rows_cap, v(d_out), out_cap, v(d_labels), n_labels, n_classes,
+        r = self._chk(self.L.zngamd_bgzf_partition_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags,
+                                                               record_lines, first_byte, record_base, _dv(d_scratch), scratch_cap, _dv(d_status),
+                                                               _dv(d_rows), rows_cap, _dv(d_out), out_cap, _dv(d_labels), n_labels, n_classes,
                                                                C.c_void_p(crec.ctypes.data), C.c_void_p(cbytes.ctypes.data), C.byref(tot)),
                       (OK, BUF_ERROR))
         return r, tot, crec[:n_classes], cbytes[:n_classes]
@@ -1849,10 +1867,8 @@ class Context:
         when totals.bad or totals.drop_short is set.  drop: None or a uint8 array, entry r belongs to record record_base + r.  caps None:
         the arrays are allocated once the engine knows their sizes; (trim rows, rows, bytes): buffers of those sizes, and code is
         BUF_ERROR (nothing written) when the result needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
+        win, st, keep = _window_in(data, members)
         table = np.ascontiguousarray(table, np.uint32).reshape(-1, 2)
-        st = np.zeros(max(1, nm), np.int32)
         tot = BgzfTrimTotals()
         group = bool(flags & BGZF_CLASSIFY_GROUP)
         box = []
@@ -1885,7 +1901,7 @@ class Context:
         else:
             dp, nd = None, 0
         bp, bkeep = _addr(blob) if len(table) else (None, None)
-        r = self._chk(self.L.zngamd_bgzf_trim_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_trim_records(self.h, *win,
                                                       text_off, text_end, bp, len(blob) if len(table) else 0,
                                                       C.c_void_p(table.ctypes.data) if len(table) else None, len(table), delim, flags, C.byref(conf),
                                                       record_base, C.c_void_p(st.ctypes.data), dp, nd, tp, tcap, rp, rcap, op, ocap, fn, None,
@@ -1898,20 +1914,19 @@ class Context:
         else:
             trim_out = trim[:tot.seen] if got else np.empty(0, TRIM_ROW_DTYPE)
             rows_out, packed = (rows[:n], _take(out, tot.bytes)) if n else (np.empty(0, GREP_ROW_DTYPE), b"")
-        return r, st[:nm], tot, trim_out, rows_out, packed
+        return r, st, tot, trim_out, rows_out, packed
 
     def bgzf_trim_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, conf, record_base, d_scratch,
                               scratch_cap, d_status, d_drop, n_drop, d_trim, trim_cap, d_rows, rows_cap, d_out, out_cap):
         """zngamd_bgzf_trim_records_dev on device pointers (the adapters and conf: host memory) -> (code, totals); trim rows, rows and records
         stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         table = np.ascontiguousarray(table, np.uint32).reshape(-1, 2)
         tot = BgzfTrimTotals()
         bp, bkeep = _addr(blob) if len(table) else (None, None)
-        r = self._chk(self.L.zngamd_bgzf_trim_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp,
+        r = self._chk(self.L.zngamd_bgzf_trim_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, bp,
                                                           len(blob) if len(table) else 0, C.c_void_p(table.ctypes.data) if len(table) else None,
-                                                          len(table), delim, flags, C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status),
-                                                          v(d_drop), n_drop, v(d_trim), trim_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
+                                                          len(table), delim, flags, C.byref(conf), record_base, _dv(d_scratch), scratch_cap, _dv(d_status),
+                                                          _dv(d_drop), n_drop, _dv(d_trim), trim_cap, _dv(d_rows), rows_cap, _dv(d_out), out_cap, C.byref(tot)),
                       (OK, BUF_ERROR))
         return r, tot
 
@@ -1922,9 +1937,7 @@ class Context:
         only with BGZF_CLASSIFY_GROUP in flags; nothing comes back when totals.bad is set.  caps None: the arrays are allocated once the
         engine knows their sizes; (overlap rows, rows, bytes): buffers of those sizes, and code is BUF_ERROR (nothing written) when the
         result needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
+        win, st, keep = _window_in(data, members)
         tot = BgzfOverlapTotals()
         group = bool(flags & BGZF_CLASSIFY_GROUP)
         box = []
@@ -1950,7 +1963,7 @@ class Context:
             vrp, rp, fn = C.c_void_p(ovl.ctypes.data) if vcap else None, C.c_void_p(rows.ctypes.data) if rcap else None, ALLOC_FN()
             if not ocap:
                 op = None
-        r = self._chk(self.L.zngamd_bgzf_overlap_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_overlap_records(self.h, *win,
                                                          text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
                                                          vrp, vcap, rp, rcap, op, ocap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
         got = r == OK and tot.covered and tot.seen and not tot.bad
@@ -1961,17 +1974,16 @@ class Context:
         else:
             ovl_out = ovl[:tot.seen] if got else np.empty(0, OVERLAP_ROW_DTYPE)
             rows_out, packed = (rows[:n], _take(out, tot.bytes)) if n else (np.empty(0, GREP_ROW_DTYPE), b"")
-        return r, st[:nm], tot, ovl_out, rows_out, packed
+        return r, st, tot, ovl_out, rows_out, packed
 
     def bgzf_overlap_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, record_base, d_scratch, scratch_cap,
                                  d_status, d_overlap, overlap_cap, d_rows, rows_cap, d_out, out_cap):
         """zngamd_bgzf_overlap_records_dev on device pointers (conf: host memory) -> (code, totals); overlap rows, rows and records stay on
         the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfOverlapTotals()
-        r = self._chk(self.L.zngamd_bgzf_overlap_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
-                                                             C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_overlap),
-                                                             overlap_cap, v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
+        r = self._chk(self.L.zngamd_bgzf_overlap_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags,
+                                                             C.byref(conf), record_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_overlap),
+                                                             overlap_cap, _dv(d_rows), rows_cap, _dv(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_qc_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):
@@ -1980,42 +1992,24 @@ class Context:
         order; empty without BGZF_QC_ROWS in conf.flags or when totals.bad is set)).  caps None: the tables are sized for conf.cycles and
         the rows are allocated once the engine knows how many there are; (table words, rows): buffers of those sizes, and code is
         BUF_ERROR when the result needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
+        win, st, keep = _window_in(data, members)
         tot = BgzfQcTotals()
         want = bool(conf.flags & BGZF_QC_ROWS)
-        box = []
-
-        def alloc(_user, nbytes):
-            box.append(np.empty(nbytes // QC_ROW_DTYPE.itemsize, QC_ROW_DTYPE))
-            return box[0].ctypes.data
-
-        if caps is None:
-            tcap, rp, rcap, fn = bgzf_qc_table_words(conf.cycles), None, 0, ALLOC_FN(alloc)
-        else:
-            tcap, rcap = caps
-            rows = np.zeros(max(1, rcap), QC_ROW_DTYPE)
-            rp, fn = C.c_void_p(rows.ctypes.data) if rcap or want else None, ALLOC_FN()
+        tcap, rcap = (bgzf_qc_table_words(conf.cycles), None) if caps is None else caps
+        out = _RowsOut(QC_ROW_DTYPE, rcap)
+        rp = out.ptr if out.cap or want else None                           # (no rows asked for and no room for any: no pointer either)
         tables = np.full(max(1, tcap), 0x5A5A5A5A5A5A5A5A, np.uint64)       # (the engine overwrites what it is given)
-        r = self._chk(self.L.zngamd_bgzf_qc_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
-                                                    text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
-                                                    C.c_void_p(tables.ctypes.data), tcap, rp, rcap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
-        got = r == OK and want and tot.covered and tot.seen and not tot.bad
-        if caps is None:
-            rows_out = box[0] if got else np.empty(0, QC_ROW_DTYPE)
-        else:
-            rows_out = rows[:tot.seen] if got else np.empty(0, QC_ROW_DTYPE)
-        return r, st[:nm], tot, tables[:tcap], rows_out
+        r = self._chk(self.L.zngamd_bgzf_qc_records(self.h, *win, text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
+                                                    C.c_void_p(tables.ctypes.data), tcap, rp, out.cap, out.fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        return r, st, tot, tables[:tcap], out.take(r == OK and want and tot.covered and tot.seen and not tot.bad, tot.seen)
 
     def bgzf_qc_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, record_base, d_scratch, scratch_cap,
                             d_status, d_tables, tables_cap, d_rows, rows_cap):
         """zngamd_bgzf_qc_records_dev on device pointers (conf: host memory) -> (code, totals); tables and rows stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfQcTotals()
-        r = self._chk(self.L.zngamd_bgzf_qc_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
-                                                        C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_tables), tables_cap,
-                                                        v(d_rows), rows_cap, C.byref(tot)), (OK, BUF_ERROR))
+        r = self._chk(self.L.zngamd_bgzf_qc_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags,
+                                                        C.byref(conf), record_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_tables), tables_cap,
+                                                        _dv(d_rows), rows_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_key_records(self, data, members, text_off, text_end, delim, flags, conf, record_base=0, caps=None):
@@ -2023,39 +2017,19 @@ class Context:
         (BgzfKeyTotals), rows (KEY_ROW_DTYPE, one per record in record order; empty when totals.bad is set)).  caps None: the rows are
         allocated once the engine knows how many there are; an integer: a buffer of that many rows, and code is BUF_ERROR when the
         result needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
+        win, st, keep = _window_in(data, members)
         tot = BgzfKeyTotals()
-        box = []
-
-        def alloc(_user, nbytes):
-            box.append(np.empty(nbytes // KEY_ROW_DTYPE.itemsize, KEY_ROW_DTYPE))
-            return box[0].ctypes.data
-
-        if caps is None:
-            rp, rcap, fn = None, 0, ALLOC_FN(alloc)
-        else:
-            rcap = caps
-            rows = np.zeros(max(1, rcap), KEY_ROW_DTYPE)
-            rp, fn = C.c_void_p(rows.ctypes.data), ALLOC_FN()
-        r = self._chk(self.L.zngamd_bgzf_key_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
-                                                     text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
-                                                     rp, rcap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
-        got = r == OK and tot.covered and tot.seen and not tot.bad
-        if caps is None:
-            rows_out = box[0] if got else np.empty(0, KEY_ROW_DTYPE)
-        else:
-            rows_out = rows[:tot.seen] if got else np.empty(0, KEY_ROW_DTYPE)
-        return r, st[:nm], tot, rows_out
+        out = _RowsOut(KEY_ROW_DTYPE, caps)
+        r = self._chk(self.L.zngamd_bgzf_key_records(self.h, *win, text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
+                                                     out.ptr, out.cap, out.fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        return r, st, tot, out.take(r == OK and tot.covered and tot.seen and not tot.bad, tot.seen)
 
     def bgzf_key_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, record_base, d_scratch, scratch_cap,
                              d_status, d_rows, rows_cap):
         """zngamd_bgzf_key_records_dev on device pointers (conf: host memory) -> (code, totals); the rows stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfKeyTotals()
-        r = self._chk(self.L.zngamd_bgzf_key_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
-                                                         C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap,
+        r = self._chk(self.L.zngamd_bgzf_key_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags,
+                                                         C.byref(conf), record_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_rows), rows_cap,
                                                          C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
@@ -2072,9 +2046,8 @@ class Context:
 
     def dedup_keys_dev(self, d_keys, n, d_scratch, scratch_cap, d_first, d_count):
         """zngamd_dedup_keys_dev on device pointers -> (code, totals); first and count (either may be 0) stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = DedupTotals()
-        r = self._chk(self.L.zngamd_dedup_keys_dev(self.h, v(d_keys), n, v(d_scratch), scratch_cap, v(d_first), v(d_count), C.byref(tot)), (OK, BUF_ERROR))
+        r = self._chk(self.L.zngamd_dedup_keys_dev(self.h, _dv(d_keys), n, _dv(d_scratch), scratch_cap, _dv(d_first), _dv(d_count), C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def _kmer_set(self, handle):
@@ -2109,39 +2082,19 @@ class Context:
         BgzfScreenConf) -> (code, block statuses, totals (BgzfScreenTotals), rows (SCREEN_ROW_DTYPE, one per record in record order; empty
         when totals.bad is set)).  caps None: the rows are allocated once the engine knows how many there are; an integer: a buffer of
         that many rows, and code is BUF_ERROR when the result needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
+        win, st, keep = _window_in(data, members)
         tot = BgzfScreenTotals()
-        box = []
-
-        def alloc(_user, nbytes):
-            box.append(np.empty(nbytes // SCREEN_ROW_DTYPE.itemsize, SCREEN_ROW_DTYPE))
-            return box[0].ctypes.data
-
-        if caps is None:
-            rp, rcap, fn = None, 0, ALLOC_FN(alloc)
-        else:
-            rcap = caps
-            rows = np.zeros(max(1, rcap), SCREEN_ROW_DTYPE)
-            rp, fn = C.c_void_p(rows.ctypes.data), ALLOC_FN()
-        r = self._chk(self.L.zngamd_bgzf_screen_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
-                                                        text_off, text_end, delim, flags, C.byref(conf), kset.h, record_base, C.c_void_p(st.ctypes.data),
-                                                        rp, rcap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
-        got = r == OK and tot.covered and tot.seen and not tot.bad
-        if caps is None:
-            rows_out = box[0] if got else np.empty(0, SCREEN_ROW_DTYPE)
-        else:
-            rows_out = rows[:tot.seen] if got else np.empty(0, SCREEN_ROW_DTYPE)
-        return r, st[:nm], tot, rows_out
+        out = _RowsOut(SCREEN_ROW_DTYPE, caps)
+        r = self._chk(self.L.zngamd_bgzf_screen_records(self.h, *win, text_off, text_end, delim, flags, C.byref(conf), kset.h, record_base,
+                                                        C.c_void_p(st.ctypes.data), out.ptr, out.cap, out.fn, None, C.byref(tot)), (OK, BUF_ERROR))
+        return r, st, tot, out.take(r == OK and tot.covered and tot.seen and not tot.bad, tot.seen)
 
     def bgzf_screen_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, kset, record_base, d_scratch, scratch_cap,
                                 d_status, d_rows, rows_cap):
         """zngamd_bgzf_screen_records_dev on device pointers (conf: host memory) -> (code, totals); the rows stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfScreenTotals()
-        r = self._chk(self.L.zngamd_bgzf_screen_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
-                                                            C.byref(conf), kset.h, record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap,
+        r = self._chk(self.L.zngamd_bgzf_screen_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags,
+                                                            C.byref(conf), kset.h, record_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_rows), rows_cap,
                                                             C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
@@ -2157,22 +2110,19 @@ class Context:
         """zngamd_bgzf_count_kmers: every valid k-mer of every record added to counter (a DeviceKmerCounter of this context) by conf (a
         BgzfCountConf) -> (code, block statuses, totals (BgzfCountTotals)); code is BUF_ERROR when the table lacks the room for the
         window (nothing was launched: reserve text_end - text_off first)"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
+        win, st, keep = _window_in(data, members)
         tot = BgzfCountTotals()
-        r = self._chk(self.L.zngamd_bgzf_count_kmers(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_count_kmers(self.h, *win,
                                                      text_off, text_end, delim, flags, C.byref(conf), counter._handle(), record_base,
                                                      C.c_void_p(st.ctypes.data), C.byref(tot)), (OK, BUF_ERROR))
-        return r, st[:nm], tot
+        return r, st, tot
 
     def bgzf_count_kmers_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, counter, record_base, d_scratch, scratch_cap,
                              d_status):
         """zngamd_bgzf_count_kmers_dev on device pointers (conf: host memory) -> (code, totals)"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfCountTotals()
-        r = self._chk(self.L.zngamd_bgzf_count_kmers_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
-                                                         C.byref(conf), counter._handle(), record_base, v(d_scratch), scratch_cap, v(d_status),
+        r = self._chk(self.L.zngamd_bgzf_count_kmers_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags,
+                                                         C.byref(conf), counter._handle(), record_base, _dv(d_scratch), scratch_cap, _dv(d_status),
                                                          C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
@@ -2181,9 +2131,7 @@ class Context:
         (BgzfSortKeyTotals), rows (uint8 of shape (seen, W)), lengths (uint32); both empty when totals.bad is set).  caps None: the
         arrays are allocated once the engine knows how many rows there are; an integer: buffers of that many rows, and code is BUF_ERROR
         when the result needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
+        win, st, keep = _window_in(data, members)
         tot = BgzfSortKeyTotals()
         W = sum(q.width if q.kind == BGZF_SORT_BYTES else 8 if q.kind == BGZF_SORT_NUMBER else 4 for q in conf.part[:conf.n_parts]) + 7 & ~7
         box = []
@@ -2198,7 +2146,7 @@ class Context:
             rcap = caps
             rows, lens = np.zeros(max(1, rcap * W), np.uint8), np.zeros(max(1, rcap), np.uint32)
             rp, lp, fn = C.c_void_p(rows.ctypes.data), C.c_void_p(lens.ctypes.data), ALLOC_FN()
-        r = self._chk(self.L.zngamd_bgzf_sort_key_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_sort_key_records(self.h, *win,
                                                           text_off, text_end, delim, flags, C.byref(conf), record_base, C.c_void_p(st.ctypes.data),
                                                           rp, lp, rcap, fn, None, C.byref(tot)), (OK, BUF_ERROR))
         got = r == OK and tot.covered and tot.seen and not tot.bad
@@ -2210,15 +2158,14 @@ class Context:
             rows_out, lens_out = rows[:n * W], lens[:n]
         else:
             rows_out, lens_out = np.empty(0, np.uint8), np.empty(0, np.uint32)
-        return r, st[:nm], tot, rows_out.reshape(n, W), lens_out
+        return r, st, tot, rows_out.reshape(n, W), lens_out
 
     def bgzf_sort_key_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, conf, record_base, d_scratch, scratch_cap,
                                   d_status, d_rows, d_lengths, rows_cap):
         """zngamd_bgzf_sort_key_records_dev on device pointers (conf: host memory) -> (code, totals); rows and lengths stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfSortKeyTotals()
-        r = self._chk(self.L.zngamd_bgzf_sort_key_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
-                                                              C.byref(conf), record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), v(d_lengths),
+        r = self._chk(self.L.zngamd_bgzf_sort_key_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags,
+                                                              C.byref(conf), record_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_rows), _dv(d_lengths),
                                                               rows_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
@@ -2233,40 +2180,34 @@ class Context:
 
     def sort_keys_dev(self, d_keys, n, width, d_scratch, scratch_cap, d_order, d_rank):
         """zngamd_sort_keys_dev on device pointers -> code; order and rank (which may be 0) stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
-        return self._chk(self.L.zngamd_sort_keys_dev(self.h, v(d_keys), n, width, v(d_scratch), scratch_cap, v(d_order), v(d_rank)), (OK, BUF_ERROR))
+        return self._chk(self.L.zngamd_sort_keys_dev(self.h, _dv(d_keys), n, width, _dv(d_scratch), scratch_cap, _dv(d_order), _dv(d_rank)), (OK, BUF_ERROR))
 
     def bgzf_place_records(self, data, members, text_off, text_end, delim, flags, record_lines, first_byte, record_base, dst, length, d_out, out_cap):
         """zngamd_bgzf_place_records: record record_base + r copied to the device buffer d_out + dst[r] (uint64; BGZF_PLACE_SKIP: not in
         this pass) with length[r] (uint32) as bgzf_sort_key_records reported it -> (code, block statuses, totals (BgzfPlaceTotals))"""
-        nm = len(members)
-        p, keep = _addr(data)
+        win, st, keep = _window_in(data, members)
         dst, length = np.ascontiguousarray(dst, np.uint64), np.ascontiguousarray(length, np.uint32)
         n = min(len(dst), len(length))
-        st = np.zeros(max(1, nm), np.int32)
         tot = BgzfPlaceTotals()
-        r = self._chk(self.L.zngamd_bgzf_place_records(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_place_records(self.h, *win,
                                                        text_off, text_end, delim, flags, record_lines, first_byte, record_base,
                                                        C.c_void_p(st.ctypes.data), C.c_void_p(dst.ctypes.data) if n else None,
                                                        C.c_void_p(length.ctypes.data) if n else None, n, C.c_void_p(int(d_out)) if d_out else None, out_cap,
                                                        C.byref(tot)))
-        return r, st[:nm], tot
+        return r, st, tot
 
     def bgzf_place_records_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, record_lines, first_byte, record_base,
                                d_scratch, scratch_cap, d_status, d_dst, d_length, n, d_out, out_cap):
         """zngamd_bgzf_place_records_dev on device pointers -> (code, totals)"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfPlaceTotals()
-        r = self._chk(self.L.zngamd_bgzf_place_records_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags,
-                                                           record_lines, first_byte, record_base, v(d_scratch), scratch_cap, v(d_status), v(d_dst),
-                                                           v(d_length), n, v(d_out), out_cap, C.byref(tot)))
+        r = self._chk(self.L.zngamd_bgzf_place_records_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags,
+                                                           record_lines, first_byte, record_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_dst),
+                                                           _dv(d_length), n, _dv(d_out), out_cap, C.byref(tot)))
         return r, tot
 
     def _bgzf_grep(self, fn_c, tot, data, members, text_off, text_end, blob, table, delim, flags, extra, caps):
-        nm = len(members)
-        p, keep = _addr(data)
+        win, st, keep = _window_in(data, members)
         table = np.ascontiguousarray(table, np.uint32)
-        st = np.zeros(max(1, nm), np.int32)
         box = []
 
         def alloc(_user, nbytes):
@@ -2289,7 +2230,7 @@ class Context:
             if not rcap:
                 rp = None
         bp, bkeep = _addr(blob)
-        r = self._chk(fn_c(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm, text_off, text_end, bp, len(blob),
+        r = self._chk(fn_c(self.h, *win, text_off, text_end, bp, len(blob),
                            C.c_void_p(table.ctypes.data), len(table), delim, flags, *extra, C.c_void_p(st.ctypes.data), rp, rcap, op, ocap, fn, None,
                            C.byref(tot)), (OK, BUF_ERROR))
         got = r == OK and tot.covered and tot.matched and not flags & BGZF_GREP_COUNT_ONLY and not getattr(tot, "bad", 0)
@@ -2299,19 +2240,18 @@ class Context:
         else:
             rows_out = rows[:tot.matched] if got else np.empty(0, GREP_ROW_DTYPE)
             packed = _take(out, tot.bytes) if got else b""
-        return r, st[:nm], tot, rows_out, packed
+        return r, st, tot, rows_out, packed
 
     def bgzf_grep_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, blob, table, delim, flags, line_base, d_scratch,
                       scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap, mismatches=0):
         """zngamd_bgzf_grep_dev (mismatches > 0: zngamd_bgzf_grep_approx_dev) on device pointers (the patterns: host memory) -> (code, totals);
         rows and lines stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         table = np.ascontiguousarray(table, np.uint32)
         tot = BgzfGrepTotals()
         bp, bkeep = _addr(blob)
         fn, k = (self.L.zngamd_bgzf_grep_approx_dev, (mismatches,)) if mismatches else (self.L.zngamd_bgzf_grep_dev, ())
-        r = self._chk(fn(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table),
-                         delim, flags, *k, line_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap, v(d_out), out_cap, C.byref(tot)),
+        r = self._chk(fn(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table),
+                         delim, flags, *k, line_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_rows), rows_cap, _dv(d_out), out_cap, C.byref(tot)),
                       (OK, BUF_ERROR))
         return r, tot
 
@@ -2319,14 +2259,13 @@ class Context:
                               first_byte, record_base, d_scratch, scratch_cap, d_status, d_rows, rows_cap, d_out, out_cap, mismatches=0):
         """zngamd_bgzf_grep_records_dev (mismatches > 0: zngamd_bgzf_grep_records_approx_dev) on device pointers (the patterns: host memory)
         -> (code, totals); rows and records stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         table = np.ascontiguousarray(table, np.uint32)
         tot = BgzfGrepRecordsTotals()
         bp, bkeep = _addr(blob)
         fn, k = (self.L.zngamd_bgzf_grep_records_approx_dev, (mismatches,)) if mismatches else (self.L.zngamd_bgzf_grep_records_dev, ())
-        r = self._chk(fn(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table),
-                         delim, flags, *k, record_lines, match_line, first_byte, record_base, v(d_scratch), scratch_cap, v(d_status), v(d_rows), rows_cap,
-                         v(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
+        r = self._chk(fn(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, bp, len(blob), C.c_void_p(table.ctypes.data), len(table),
+                         delim, flags, *k, record_lines, match_line, first_byte, record_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_rows), rows_cap,
+                         _dv(d_out), out_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_tabix(self, data, members, text_off, text_end, conf, delim, flags, line_base=0, caps=None):
@@ -2334,9 +2273,7 @@ class Context:
         (TABIX_NAME_DTYPE), the names packed, bins (TABIX_BIN_DTYPE), wins (TABIX_WIN_DTYPE)).  caps None: the tables are allocated once
         the engine knows their sizes; (names, name bytes, bins, wins): buffers of those sizes, and code is BUF_ERROR (nothing written)
         when a table needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
+        win, st, keep = _window_in(data, members)
         tot = BgzfTabixTotals()
         cf = TabixConf(*[int(x) for x in conf])
         dts = (TABIX_NAME_DTYPE, np.dtype("u1"), TABIX_BIN_DTYPE, TABIX_WIN_DTYPE)
@@ -2355,7 +2292,7 @@ class Context:
             ptrs, fn = [], ALLOC_FN()
             for b, n in zip(bufs, caps):
                 ptrs += [C.c_void_p(b.ctypes.data) if n else None, n]
-        r = self._chk(self.L.zngamd_bgzf_tabix(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm, text_off,
+        r = self._chk(self.L.zngamd_bgzf_tabix(self.h, *win, text_off,
                                                text_end, C.byref(cf), delim, flags, line_base, C.c_void_p(st.ctypes.data), *ptrs, fn, None,
                                                C.byref(tot)), (OK, BUF_ERROR))
         counts = (tot.n_names, tot.name_bytes, tot.n_bins, tot.n_wins)
@@ -2367,17 +2304,16 @@ class Context:
             out = box
         else:
             out = [b[:n] for b, n in zip(bufs, counts)]
-        return r, st[:nm], tot, out[0], out[1].tobytes(), out[2], out[3]
+        return r, st, tot, out[0], out[1].tobytes(), out[2], out[3]
 
     def bgzf_tabix_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, conf, delim, flags, line_base, d_scratch, scratch_cap,
                        d_status, d_names, names_cap, d_blob, blob_cap, d_bins, bins_cap, d_wins, wins_cap):
         """zngamd_bgzf_tabix_dev on device pointers -> (code, totals); the tables stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfTabixTotals()
         cf = TabixConf(*[int(x) for x in conf])
-        r = self._chk(self.L.zngamd_bgzf_tabix_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, C.byref(cf), delim, flags,
-                                                   line_base, v(d_scratch), scratch_cap, v(d_status), v(d_names), names_cap, v(d_blob), blob_cap,
-                                                   v(d_bins), bins_cap, v(d_wins), wins_cap, C.byref(tot)), (OK, BUF_ERROR))
+        r = self._chk(self.L.zngamd_bgzf_tabix_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, C.byref(cf), delim, flags,
+                                                   line_base, _dv(d_scratch), scratch_cap, _dv(d_status), _dv(d_names), names_cap, _dv(d_blob), blob_cap,
+                                                   _dv(d_bins), bins_cap, _dv(d_wins), wins_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_fetch(self, data, members, conf, delim, flags, names, regions, spans, caps=None):
@@ -2385,11 +2321,10 @@ class Context:
         (code, block statuses, span verdicts, rows per span, totals, rows (TABIX_ROW_DTYPE), packed lines).  caps None: rows and lines
         are allocated once the engine knows their sizes; (rows, bytes): buffers of those sizes, and code is BUF_ERROR when the result
         needs more"""
-        nm, ns = len(members), len(spans)
-        p, keep = _addr(data)
+        ns = len(spans)
+        win, st, keep = _window_in(data, members)
         regions = np.ascontiguousarray(regions, TABIX_REGION_DTYPE)
         spans = np.ascontiguousarray(spans, TABIX_SPAN_DTYPE)
-        st = np.zeros(max(1, nm), np.int32)
         ss = np.zeros(max(1, ns), np.int32)
         sr = np.zeros(max(1, ns), np.uint32)
         tot = BgzfFetchTotals()
@@ -2417,7 +2352,7 @@ class Context:
                 rp = None
         names = bytes(names)
         bp, bkeep = _addr(names) if names else (None, None)
-        r = self._chk(self.L.zngamd_bgzf_fetch(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        r = self._chk(self.L.zngamd_bgzf_fetch(self.h, *win,
                                                C.byref(cf), delim, flags, bp, len(names), C.c_void_p(regions.ctypes.data), len(regions),
                                                C.c_void_p(spans.ctypes.data) if ns else None, ns, C.c_void_p(st.ctypes.data),
                                                C.c_void_p(ss.ctypes.data), C.c_void_p(sr.ctypes.data), rp, rcap, op, ocap, fn, None,
@@ -2429,20 +2364,19 @@ class Context:
         else:
             rows_out = rows[:tot.matched] if got else np.empty(0, TABIX_ROW_DTYPE)
             packed = _take(out, tot.bytes) if got else b""
-        return r, st[:nm], ss[:ns], sr[:ns], tot, rows_out, packed
+        return r, st, ss[:ns], sr[:ns], tot, rows_out, packed
 
     def bgzf_fetch_dev(self, d_in, in_len, d_members, n_members, conf, delim, flags, names, regions, d_spans, n_spans, d_scratch, scratch_cap,
                        d_status, d_span_status, d_span_rows, d_rows, rows_cap, d_out, out_cap):
         """zngamd_bgzf_fetch_dev on device pointers (the regions: host memory) -> (code, totals)"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         regions = np.ascontiguousarray(regions, TABIX_REGION_DTYPE)
         tot = BgzfFetchTotals()
         cf = TabixConf(*[int(x) for x in conf])
         names = bytes(names)
         bp, bkeep = _addr(names) if names else (None, None)
-        r = self._chk(self.L.zngamd_bgzf_fetch_dev(self.h, v(d_in), in_len, v(d_members), n_members, C.byref(cf), delim, flags, bp, len(names),
-                                                   C.c_void_p(regions.ctypes.data), len(regions), v(d_spans), n_spans, v(d_scratch), scratch_cap,
-                                                   v(d_status), v(d_span_status), v(d_span_rows), v(d_rows), rows_cap, v(d_out), out_cap,
+        r = self._chk(self.L.zngamd_bgzf_fetch_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, C.byref(cf), delim, flags, bp, len(names),
+                                                   C.c_void_p(regions.ctypes.data), len(regions), _dv(d_spans), n_spans, _dv(d_scratch), scratch_cap,
+                                                   _dv(d_status), _dv(d_span_status), _dv(d_span_rows), _dv(d_rows), rows_cap, _dv(d_out), out_cap,
                                                    C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
@@ -2450,9 +2384,7 @@ class Context:
         """zngamd_bgzf_faidx: carry = None (nothing is open) or a FaidxCarry -> (code, block statuses, totals (with the carry for the
         next call), rows (FAIDX_ROW_DTYPE), the names packed).  caps None: the tables are allocated once the engine knows their sizes;
         (rows, name bytes): buffers of those sizes, and code is BUF_ERROR (nothing written) when a table needs more"""
-        nm = len(members)
-        p, keep = _addr(data)
-        st = np.zeros(max(1, nm), np.int32)
+        win, st, keep = _window_in(data, members)
         tot = BgzfFaidxTotals()
         dts = (FAIDX_ROW_DTYPE, np.dtype("u1"))
         box = []
@@ -2469,7 +2401,7 @@ class Context:
             ptrs, fn = [], ALLOC_FN()
             for b, n in zip(bufs, caps):
                 ptrs += [C.c_void_p(b.ctypes.data) if n else None, n]
-        r = self._chk(self.L.zngamd_bgzf_faidx(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm, text_off,
+        r = self._chk(self.L.zngamd_bgzf_faidx(self.h, *win, text_off,
                                                text_end, delim, flags, line_base, C.byref(carry) if carry is not None else None,
                                                C.c_void_p(st.ctypes.data), *ptrs, fn, None, C.byref(tot)), (OK, BUF_ERROR))
         if r != OK or not tot.covered or not tot.records:
@@ -2478,37 +2410,34 @@ class Context:
             out = box + [np.empty(0, np.uint8)] * (2 - len(box))
         else:
             out = [b[:n] for b, n in zip(bufs, (tot.records, tot.name_bytes))]
-        return r, st[:nm], tot, out[0], out[1].tobytes()
+        return r, st, tot, out[0], out[1].tobytes()
 
     def bgzf_faidx_dev(self, d_in, in_len, d_members, n_members, text_off, text_end, delim, flags, line_base, carry, d_scratch, scratch_cap,
                        d_status, d_rows, rows_cap, d_blob, blob_cap):
         """zngamd_bgzf_faidx_dev on device pointers (the carry: host memory) -> (code, totals); rows and names stay on the device"""
-        v = lambda x: C.c_void_p(int(x)) if x else None
         tot = BgzfFaidxTotals()
-        r = self._chk(self.L.zngamd_bgzf_faidx_dev(self.h, v(d_in), in_len, v(d_members), n_members, text_off, text_end, delim, flags, line_base,
-                                                   C.byref(carry) if carry is not None else None, v(d_scratch), scratch_cap, v(d_status),
-                                                   v(d_rows), rows_cap, v(d_blob), blob_cap, C.byref(tot)), (OK, BUF_ERROR))
+        r = self._chk(self.L.zngamd_bgzf_faidx_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, text_off, text_end, delim, flags, line_base,
+                                                   C.byref(carry) if carry is not None else None, _dv(d_scratch), scratch_cap, _dv(d_status),
+                                                   _dv(d_rows), rows_cap, _dv(d_blob), blob_cap, C.byref(tot)), (OK, BUF_ERROR))
         return r, tot
 
     def bgzf_faidx_fetch(self, data, members, spans, out_cap):
         """zngamd_bgzf_faidx_fetch: spans = FAIDX_SPAN_DTYPE rows -> (block statuses int32[n], span verdicts int32[n], packed bases)"""
-        nm, ns = len(members), len(spans)
-        p, keep = _addr(data)
+        ns = len(spans)
+        win, st, keep = _window_in(data, members)
         spans = np.ascontiguousarray(spans, FAIDX_SPAN_DTYPE)
         out, op = _new_bytes(out_cap)
-        st = np.zeros(max(1, nm), np.int32)
         ss = np.zeros(max(1, ns), np.int32)
-        self._chk(self.L.zngamd_bgzf_faidx_fetch(self.h, p, memoryview(data).nbytes, C.c_void_p(members.ctypes.data) if nm else None, nm,
+        self._chk(self.L.zngamd_bgzf_faidx_fetch(self.h, *win,
                                                  C.c_void_p(spans.ctypes.data) if ns else None, ns, op if out_cap else None, out_cap,
                                                  C.c_void_p(st.ctypes.data), C.c_void_p(ss.ctypes.data)))
-        return st[:nm], ss[:ns], _take(out, out_cap)
+        return st, ss[:ns], _take(out, out_cap)
 
     def bgzf_faidx_fetch_dev(self, d_in, in_len, d_members, n_members, d_spans, n_spans, d_scratch, scratch_cap, d_out, out_cap, d_status,
                              d_span_status):
         """zngamd_bgzf_faidx_fetch_dev on device pointers; statuses and bases stay on the device."""
-        v = lambda x: C.c_void_p(int(x)) if x else None
-        self._chk(self.L.zngamd_bgzf_faidx_fetch_dev(self.h, v(d_in), in_len, v(d_members), n_members, v(d_spans), n_spans, v(d_scratch),
-                                                     scratch_cap, v(d_out), out_cap, v(d_status), v(d_span_status)))
+        self._chk(self.L.zngamd_bgzf_faidx_fetch_dev(self.h, _dv(d_in), in_len, _dv(d_members), n_members, _dv(d_spans), n_spans, _dv(d_scratch),
+                                                     scratch_cap, _dv(d_out), out_cap, _dv(d_status), _dv(d_span_status)))
 
     def bgzf_stats(self, reset=True):
         """(decode launches, blocks decoded, slices gathered) of the ranged reads since the last reset"""

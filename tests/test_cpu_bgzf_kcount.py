@@ -139,7 +139,7 @@ def test_symbols_declared_exported_and_bound():
     kernel = open(os.path.join(PKG_DIR, "csrc", "za_kcount.hip")).read()
     for k in ("za_k_kcount_clear", "za_k_kcount_reads", "za_k_kcount_pairs", "za_k_kcount_export", "za_k_kcount_hist"):
         assert "void %s(" % k in kernel and k in main
-    assert "za_k_screen_close" in main[main.index("za_k_kcount_reads"):][:1000]      # the close kernel is the screen's
+    assert "za_k_rec_close<ZaKcountTotals>" in main[main.index("za_k_kcount_reads"):][:1000]      # the close kernel is the shared one, for these totals
     assert kernel.count("__shared__") == 1                                         # the histogram's bins, nothing else
     for fn in ("za_kmer_claim", "za_kmer_cut", "za_kmer_code", "za_kmer_planes"):
         assert fn + "(" in kernel and not re.search(r"__device__[^\n]*\b%s\(" % fn, kernel)      # used here, defined in za_screen.hip alone

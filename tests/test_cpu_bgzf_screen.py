@@ -125,8 +125,10 @@ def test_symbols_declared_exported_and_bound():
     main = open(os.path.join(PKG_DIR, "csrc", "zng_amd.hip")).read()
     assert main.index('#include "za_sort.hip"') < main.index('#include "za_screen.hip"')
     kernel = open(os.path.join(PKG_DIR, "csrc", "za_screen.hip")).read()
-    for k in ("za_k_kmer_clear", "za_k_kmer_insert", "za_k_kmer_load", "za_k_kmer_export", "za_k_screen", "za_k_screen_close"):
+    for k in ("za_k_kmer_clear", "za_k_kmer_insert", "za_k_kmer_load", "za_k_kmer_export", "za_k_screen"):
         assert "void %s(" % k in kernel and k in main
+    # the close kernel is the one the one-fault calls share, for the screen's totals
+    assert "void za_k_rec_close(" in open(os.path.join(PKG_DIR, "csrc", "za_grep_records.hip")).read() and "za_k_rec_close<ZaScreenTotals>" in main
     assert "__shared__" not in kernel                                              # no LDS
 
 

@@ -212,6 +212,15 @@ def test_device_forms(ctx):
 
     code, tot = keys_dev(n - 1)
     assert code == _lib.BUF_ERROR and (tot.seen, tot.bad) == (n, 0) and d_rows.cpu().tobytes() == b"\xa5" * (16 * (n + 1))
+    # a fault together with a short destination: the fault wins -- the code is OK, the totals name the record, nothing is written
+    recs = I.fastq(I.grid_bodies())
+    bad = b"".join(recs[:n - 1]) + b"#" + recs[n - 1][1:]
+    b_blob, b_members = packed_of(bad)
+    d_bin, d_bm, d_bst = devmem.from_host(ctx, b_blob + bytes(64)), devmem.from_host(ctx, b_members.tobytes()), devmem.empty(ctx, 4 * len(b_members))
+    code, tot = ctx.bgzf_key_records_dev(d_bin.ptr, len(b_blob), d_bm.ptr, len(b_members), 0, nb, 10, F, conf_of(cf), BASE, d_scratch.ptr, nb, d_bst.ptr,
+                                         d_rows.ptr, n - 1)
+    assert len(bad) == nb and code == 0 and (tot.bad, tot.bad_record, tot.bad_src, tot.seen) == (1, BASE + n - 1, nb - len(recs[n - 1]), n)
+    assert d_rows.cpu().tobytes() == b"\xa5" * (16 * (n + 1))
     code, tot = keys_dev(n)
     assert code == 0 and (tot.seen, tot.bytes_in, tot.tail_off, tot.covered) == (n, nb, nb, 1)
     got = d_rows.cpu().tobytes()

@@ -236,6 +236,14 @@ def test_device_form(ctx):
     code, tot = dev(True, words, n - 1)
     assert code == _lib.BUF_ERROR and (tot.seen, tot.bases, tot.bad) == (n, tot_h.bases, 0) and d_rows.cpu().tobytes() == b"\xa5" * (24 * (n + 1))
     assert d_tab.cpu().tobytes() == tables_h.tobytes() + b"\xa5" * 8
+    # a fault together with a short destination: the fault wins -- the code is OK, the totals name the record, no row is written
+    t = b"".join(recs[:n - 1]) + b"#" + recs[n - 1][1:]
+    b, m = packed_of(t)
+    d_bin, d_bm, d_bst, d_btab = devmem.from_host(ctx, b + bytes(64)), devmem.from_host(ctx, m.tobytes()), devmem.empty(ctx, 4 * len(m)), canary(8 * words)
+    code, tot = ctx.bgzf_qc_records_dev(d_bin.ptr, len(b), d_bm.ptr, len(m), 0, nb, 10, F, conf_of(cf, True), BASE, d_scratch.ptr, nb, d_bst.ptr, d_btab.ptr,
+                                        words, d_rows.ptr, n - 1)
+    assert len(t) == nb and code == 0 and (tot.bad, tot.bad_record, tot.bad_src, tot.seen) == (1, BASE + n - 1, nb - len(recs[n - 1]), n)
+    assert d_rows.cpu().tobytes() == b"\xa5" * (24 * (n + 1))
     code, tot = dev(False, words, 0)                            # without rows the pointer may be NULL
     assert code == 0 and bytes(tot) == bytes(tot_h) and d_tab.cpu().tobytes() == tables_h.tobytes() + b"\xa5" * 8
     code, tot = dev(True, words, n)

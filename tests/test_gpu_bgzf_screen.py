@@ -221,6 +221,14 @@ def test_screen_capacity_and_faults(ctx):
                                                    d_rows.ptr, rcap)
     code, tot = dev(n - 1)
     assert code == _lib.BUF_ERROR and (tot.seen, tot.bad) == (n, 0) and d_rows.cpu().tobytes() == b"\xa5" * (24 * (n + 1))
+    # a fault together with a short destination: the fault wins -- the code is OK, the totals name the record, nothing is written
+    t = b"".join(b"#" + r[1:] if i == n - 1 else r for i, r in enumerate(recs))
+    b, m = packed_of(t)
+    d_bin, d_bm, d_bst = devmem.from_host(ctx, b + bytes(64)), devmem.from_host(ctx, m.tobytes()), devmem.empty(ctx, 4 * len(m))
+    code, tot = ctx.bgzf_screen_records_dev(d_bin.ptr, len(b), d_bm.ptr, len(m), 0, nb, 10, F, conf_of(5), kset, BASE, d_scratch.ptr, nb, d_bst.ptr, d_rows.ptr,
+                                            n - 1)
+    assert len(t) == nb and code == 0 and (tot.bad, tot.bad_record, tot.bad_src, tot.seen) == (1, BASE + n - 1, starts[n - 1], n)
+    assert d_rows.cpu().tobytes() == b"\xa5" * (24 * (n + 1))
     code, tot = dev(n)
     assert code == 0 and R.Totals(tot.seen, tot.bytes_in, tot.bases, tot.kmers, tot.hits, tot.matched) == totals_of(want, bodies, nb, 5)
     got = d_rows.cpu().tobytes()

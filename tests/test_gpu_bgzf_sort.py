@@ -225,6 +225,13 @@ def test_key_capacity_and_device_form(ctx):
 
     code, tot = keys_dev(n - 1)
     assert code == _lib.BUF_ERROR and (tot.seen, tot.bad) == (n, 0) and d_rows.cpu().tobytes() == b"\xa5" * (w * (n + 1)) and d_len.cpu().tobytes() == b"\xa5" * (4 * (n + 1))
+    # a fault together with a short destination: the fault wins -- the code is OK, the totals name the record, nothing is written.  (The
+    # table's records share no first byte, so none is overwritten: the first record that does not begin as record 0 does is at fault.)
+    fb = recs[0][:1]
+    j = next(i for i, r in enumerate(recs) if r[:1] != fb)
+    code, tot = keys_dev(n - 1, cf._replace(first_byte=fb))
+    assert code == 0 and (tot.bad, tot.bad_record, tot.bad_src, tot.seen) == (1, BASE + j, len(b"".join(recs[:j])), n)
+    assert d_rows.cpu().tobytes() == b"\xa5" * (w * (n + 1)) and d_len.cpu().tobytes() == b"\xa5" * (4 * (n + 1))
     code, tot = keys_dev(n)
     assert code == 0 and (tot.seen, tot.bytes_in, tot.tail_off, tot.covered, tot.key_width) == (n, nb, nb, 1, w)
     got, gl = d_rows.cpu().tobytes(), d_len.cpu().tobytes()
